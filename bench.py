@@ -55,6 +55,10 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 UNIQ = 64               # distinct seeded pairs of the global batch (pair g has the inputs of index g % UNIQ): a rank's 64 pairs are
 #                         all different, every rank of an N-GPU run computes the same 64 -- what the cross-rank check compares
 TFHE_UNIQ = 64          # distinct seeded gate inputs
+DUMP_SAMPLE = 1 << 21    # --dump-outputs: residues sampled from the C4 outputs (3 float64 arrays: 48 MiB)
+DUMP_GATES = 8192        # --dump-outputs: C5 gates written (33.6 MB)
+DUMP_SEED = 20240917
+DUMP_LIMIT = 64 * 10**6
 SIMDS, LANES = 1024, 16  # 256 CUs x 4 SIMDs, 16 lanes each: a wave64 vector instruction holds its SIMD for 4 cycles
 NCCL_TIMEOUT_S = 60
 PROFILE_JSON = os.path.join(ROOT, "profiles", "profile.json")
@@ -98,6 +102,10 @@ def parse_args(argv=None):
     ap.add_argument("--selftest-corrupt-rank", type=int, default=-1,
                     help="testing: one bit of this rank's key replica is flipped after the broadcast: the line must say "
                          "key_digest_equal / cross_rank_equal false and the run must fail")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's slice) to DIR/<name>.npy "
+                         "as float64, at most 64 MB: c4 a fixed seeded sample of the output ciphertexts' residues, each as two "
+                         "exact 32-bit halves, with the sampled positions; c5 the output LWE samples")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work: exercise launch, sharding, key replication and the max-over-ranks reduction on CPU")
     a = ap.parse_args(argv)
@@ -548,6 +556,19 @@ class C4:
     def twins(self):
         return twins_equal(self.torch, self.out, self.out_elems, self.B, UNIQ, self.first, used_elems=self.ct_elems)
 
+    def dump_arrays(self):
+        """the relinearized ciphertexts (B x 2 x Q x N residues, item-major): DUMP_SAMPLE positions drawn with DUMP_SEED
+        (all of them when there are fewer), each residue split into bits 0..31 and 32..63 so that float64 holds it exactly"""
+        total = self.B * self.ct_elems
+        if total <= DUMP_SAMPLE:
+            pos = np.arange(total, dtype=np.int64)
+        else:
+            pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE))
+        flat = (pos // self.ct_elems) * self.out_elems + pos % self.ct_elems
+        v = self.out[self.torch.from_numpy(flat).to(self.dev)].cpu().numpy().view(np.uint64)
+        return {"ct_out_index": pos.astype(np.float64), "ct_out_lo32": (v & 0xFFFFFFFF).astype(np.float64),
+                "ct_out_hi32": (v >> np.uint64(32)).astype(np.float64)}
+
     def output_digests(self):
         """(digest, present) per distinct input index: the first item of this rank's slice that has it"""
         d = row_digests(self.torch, self.out.view(self.B, self.out_elems)[:, :self.ct_elems])
@@ -691,6 +712,13 @@ class C5:
             dig[u], present[u] = v, 1
         return dig, present
 
+    def dump_arrays(self):
+        """the output LWE samples of the first (up to) DUMP_GATES gates: mask [.][512] and body [.] (torus32 as signed
+        int32 values)"""
+        g = min(self.S, DUMP_GATES)
+        return {"lwe_out_a": self.out_a.view(self.S, 512)[:g].cpu().numpy().astype(np.float64),
+                "lwe_out_b": self.out_b[:g].cpu().numpy().astype(np.float64)}
+
     def oracle_check(self, count):
         """the first `count` gates of this rank's slice against the CPU oracle (the checker; not timed here)"""
         from oracle import binding as ob
@@ -717,6 +745,19 @@ class C5:
 
 
 WORKLOADS = {"c4": C4, "c5": C5}
+
+
+def dump_outputs(work, path):
+    """--dump-outputs: the arrays of work.dump_arrays() (float64) as path/<name>.npy"""
+    torch = work.torch
+    with torch.cuda.device(work.dev):
+        torch.cuda.synchronize()
+        arrays = work.dump_arrays()
+    size = sum(a.nbytes for a in arrays.values())
+    assert size <= DUMP_LIMIT, "--dump-outputs: %d bytes exceed the %d-byte limit" % (size, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def line_skeleton(args, work, world, value, elapsed, per_rank, parallelism, distinct_devices):
@@ -989,6 +1030,8 @@ def run_single_process(args, reason):
     if errors:
         raise SystemExit("bench.py: a device thread failed: " + "; ".join(errors))
     elapsed = max(total)
+    if args.dump_outputs:
+        dump_outputs(works[0], args.dump_outputs)
     value = args.batch * world * args.steps / elapsed
     line = line_skeleton(args, works[0], world, value, elapsed, [w.B * args.steps / o for w, o in zip(works, own)],
                          "sharded x%d in ONE process: a thread, a stream and a context per device, keys replicated with "
@@ -1438,6 +1481,8 @@ def run_rank(args):
     torch.cuda.synchronize()
     elapsed = dist.max_float(time.perf_counter() - t0)
     per_rank = dist.gather_floats(B * args.steps / own_elapsed)
+    if args.dump_outputs and rank == 0:   # what the last timed step computed (before the repeat step below)
+        dump_outputs(work, args.dump_outputs)
     tw_n, tw_ok = work.twins()
     tw_all = dist.gather_floats(float(tw_n if tw_ok else -1))
     # ---- the line proves itself: (a) the same step once more gives the same bits (determinism without twins: all inputs

@@ -143,6 +143,41 @@ def test_gpus_1_takes_the_same_path_with_and_without_a_launcher():
     d.close()
 
 
+def test_dump_outputs_are_exact_seeded_and_bounded(monkeypatch):
+    """--dump-outputs: the C4 sample holds every sampled residue exactly (two float64 halves), the same positions on
+    every run, all positions when the output is small; C5 the output samples as they are; both under 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench()
+    assert b.parse_args(["--dump-outputs", "d", "--steps", "7"]).dump_outputs == "d"
+    assert 3 * b.DUMP_SAMPLE * 8 <= b.DUMP_LIMIT and b.DUMP_GATES * 513 * 8 <= b.DUMP_LIMIT
+
+    class W:
+        pass
+    w = W()
+    w.torch, w.dev, w.B, w.ct_elems, w.out_elems = torch, torch.device("cpu"), 3, 2 * 2 * 64, 3 * 2 * 64
+    w.out = torch.randint(0, 1 << 60, (w.B * w.out_elems,), dtype=torch.int64, generator=torch.Generator().manual_seed(5))
+    want = w.out.view(w.B, w.out_elems)[:, :w.ct_elems].reshape(-1).numpy().view(np.uint64)
+
+    def check(a):
+        assert all(v.dtype == np.float64 for v in a.values())
+        pos = a["ct_out_index"].astype(np.int64)
+        got = a["ct_out_hi32"].astype(np.uint64) << np.uint64(32) | a["ct_out_lo32"].astype(np.uint64)
+        assert np.array_equal(got, want[pos])
+        return pos
+    assert np.array_equal(check(b.C4.dump_arrays(w)), np.arange(w.B * w.ct_elems))
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 100)
+    pos = check(b.C4.dump_arrays(w))
+    assert 0 < len(pos) <= 100 and np.array_equal(pos, check(b.C4.dump_arrays(w)))
+
+    w5 = W()
+    w5.S = 4
+    w5.out_a = torch.randint(-2**31, 2**31, (w5.S * 512,), dtype=torch.int32)
+    w5.out_b = torch.randint(-2**31, 2**31, (w5.S,), dtype=torch.int32)
+    a = b.C5.dump_arrays(w5)
+    assert np.array_equal(a["lwe_out_a"].reshape(-1), w5.out_a.numpy()) and np.array_equal(a["lwe_out_b"], w5.out_b.numpy())
+
+
 def test_preflight_runs_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--preflight", "--gpus", "8"], capture_output=True,
                        text=True, timeout=300)

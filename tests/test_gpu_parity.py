@@ -437,16 +437,17 @@ def test_cpp_class_layer(torch):
 
 
 @pytest.mark.parametrize("name", ["ckks", "bfv", "tfhe"])
-def test_reference_benchmark_runs_unchanged(torch, name):
+def test_reference_benchmark_runs_unchanged(torch, name, tmp_path):
     """benchmark/benchmark_{ckks,bfv}.cpp of the reference, compiled unchanged against the class
-    layer by __graft_entry__.build() (where the reference tree is available), run to completion."""
+    layer by __graft_entry__.build() (oracle/ref_build.py, where the reference tree is available),
+    run to completion."""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "heongpu_amd", "lib", "ref_benchmark_" + name)
+    from oracle import ref_build
+    exe = ref_build.exe_path("ref_benchmark_" + name)
     if not os.path.exists(exe):
-        pytest.skip("reference benchmark binary not built (no /root/reference at build time)")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+        pytest.skip("reference benchmark binary not built (oracle/_ref/: no reference tree at build time)")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900, cwd=tmp_path)
     print(r.stdout[-2500:], r.stderr[-500:])
     assert r.returncode == 0
     if name == "tfhe":
@@ -475,18 +476,18 @@ _EXAMPLE_EXPECT = {
 
 
 @pytest.mark.parametrize("name", sorted(_EXAMPLE_EXPECT))
-def test_reference_example_runs_unchanged(torch, name):
+def test_reference_example_runs_unchanged(torch, name, tmp_path):
     """example/basic/<name>.cpp of the reference, compiled UNCHANGED against the class layer by
-    __graft_entry__.build() (where the reference tree is available), must run and print the results
-    its own comments announce."""
+    __graft_entry__.build() (oracle/ref_build.py, where the reference tree is available), must run and
+    print the results its own comments announce."""
     import os
     import re
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "heongpu_amd", "lib", "ref_example_" + name)
+    from oracle import ref_build
+    exe = ref_build.exe_path("ref_example_" + name)
     if not os.path.exists(exe):
-        pytest.skip("reference example binary not built (no /root/reference at build time)")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd="/tmp")
+        pytest.skip("reference example binary not built (oracle/_ref/: no reference tree at build time)")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd=tmp_path)
     print(r.stdout[-2500:], r.stderr[-500:])
     assert r.returncode == 0
     flat = re.sub(r"\s+", "", r.stdout)
@@ -522,17 +523,17 @@ _REFERENCE_TESTS = ["test_bfv_addition", "test_bfv_encoding", "test_bfv_encrypti
 
 
 @pytest.mark.parametrize("name", _REFERENCE_TESTS)
-def test_reference_own_test_passes(torch, name):
+def test_reference_own_test_passes(torch, name, tmp_path):
     """test/<name>.cpp of the reference -- its own encrypt -> operate -> decrypt checks over all its
     parameter sets (N = 2^12 .. 2^16, up to 37 primes, key-switching methods I and II) -- compiled
     UNCHANGED against the class layer (GoogleTest's TEST/EXPECT_EQ come from tests/cpp/gtest/gtest.h)
-    by __graft_entry__.build(), must pass on this backend."""
+    by __graft_entry__.build() (oracle/ref_build.py), must pass on this backend."""
     import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "heongpu_amd", "lib", "ref_" + name)
+    from oracle import ref_build
+    exe = ref_build.exe_path("ref_" + name)
     if not os.path.exists(exe):
-        pytest.skip("reference test binary not built (no /root/reference at build time)")
+        pytest.skip("reference test binary not built (oracle/_ref/: no reference tree at build time)")
     # Every program must pass on its FIRST run.  The one exception is a flaw of the reference's own
     # test: test_bfv_addition.cpp:55,154,254,354,456 expect `(m1 + m2 > t) ? m1 + m2 - t : m1 + m2`, i.e.
     # the value t instead of 0 in a slot where m1 + m2 == t -- about n/t per parameter set, 16 % per run
@@ -541,7 +542,7 @@ def test_reference_own_test_passes(torch, name):
     # the run is one of those `message_addition_result` comparisons.
     import re
     for attempt in range(4):
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=1500, cwd="/tmp")
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=1500, cwd=tmp_path)
         print(r.stdout[-3000:], r.stderr[-1000:])
         if r.returncode == 0 or name != "test_bfv_addition":
             break

@@ -16,8 +16,8 @@ python bench.py --gpus 2 --allow-shared-devices --workload c5 --detail $O/bench_
 python bench.py --gpus 2 --allow-shared-devices --single-process --no-secondary --detail $O/bench_c4_g2_single_process_detail.json > $O/bench_c4_g2_single_process_line.json 2>>$O/bench_stderr.txt
 python bench.py --preflight --gpus 8 2>/dev/null | tail -1 > $O/preflight.json
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 10 --warmup 2 --no-secondary --no-cpu-baseline --detail $O/bench_under_launcher_detail.json 2>>$O/bench_stderr.txt | tail -1 > $O/bench_under_launcher_line.json
-(for b in ckks bfv tfhe; do echo "######## benchmark_$b.cpp (reference source, compiled unchanged)"; ./heongpu_amd/lib/ref_benchmark_$b 2>&1; done) > $O/reference_benchmarks_unchanged.txt
-(for t in heongpu_amd/lib/ref_test_*; do echo "######## $(basename $t)"; $t 2>&1 | tail -4; done) > $O/reference_tests_unchanged.txt
+(for b in ckks bfv tfhe; do echo "######## benchmark_$b.cpp (reference source, compiled unchanged)"; ./oracle/_ref/ref_benchmark_$b 2>&1; done) > $O/reference_benchmarks_unchanged.txt
+(for t in oracle/_ref/ref_test_*; do echo "######## $(basename $t)"; $t 2>&1 | tail -4; done) > $O/reference_tests_unchanged.txt
 SOAK_REPS=40 python tools/soak.py > $O/soak.txt 2>&1; tail -1 $O/soak.txt
 for g in 8192 1024 8; do python tools/tfhe_bench.py --gates $g 2>&1 | grep -E "NAND|blind|key_sw"; done > $O/tfhe_bench.txt; cat $O/tfhe_bench.txt
 python tools/exp/overlap_free.py 20 2>&1 | grep -v amdgpu.ids > $O/overlap_free.txt
