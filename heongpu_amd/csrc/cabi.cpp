@@ -645,13 +645,6 @@ int hegpu_divide_round_lastq_permute(hegpu_context* ctx, const uint64_t* in, uin
                    "hegpu_divide_round_lastq_permute");
 }
 
-// location of depth's constants in the triangular rescale tables (reference ckks/operator.cu:1181-1187)
-static int rescale_location(const Context& c, int depth)
-{
-    int counter = c.Q_size - 1, location = 0;
-    for (int i = 0; i < depth; i++) { location += counter; counter--; }
-    return location;
-}
 #define SEAM_CKKS(ctx, depth, batch, min_limbs)                                                                    \
     NEED_CTX(ctx);                                                                                                 \
     const Context& c = (ctx)->c;                                                                                   \
@@ -670,8 +663,8 @@ int hegpu_divide_round_lastq_leveled_stage_one(hegpu_context* ctx, const uint64_
     if (rescale)
         return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
                                              c.d64("rescaled_half") + depth,
-                                             c.d64("rescaled_half_mod") + rescale_location(c, depth), c.n_power, l - 1,
-                                             l - 1, batch, (hipStream_t) stream),
+                                             c.d64("rescaled_half_mod") + triangle_offset(c.Q_size - 1, depth), c.n_power,
+                                             l - 1, l - 1, batch, (hipStream_t) stream),
                        "hegpu_divide_round_lastq_leveled_stage_one");
     if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
     return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
@@ -711,8 +704,8 @@ int hegpu_divide_round_lastq_rescale(hegpu_context* ctx, const uint64_t* in_last
     SEAM_CKKS(ctx, depth, batch, 2);
     return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, l, nullptr, 0,
                                          (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.d64("rescaled_last_q_modinv") + rescale_location(c, depth), c.n_power, l - 1,
-                                         0, batch, (hipStream_t) stream),
+                                         c.d64("rescaled_last_q_modinv") + triangle_offset(c.Q_size - 1, depth), c.n_power,
+                                         l - 1, 0, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_rescale");
 }
 
@@ -789,10 +782,8 @@ int hegpu_ckks_relinearize_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs
 {
     NEED_CTX(ctx);
     CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_RELIN, depth, batch, ws, ws_bytes);
-    return hip_ret(ctx->c.P_size == 1 ? op_ckks_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, depth, batch,
-                                                            (u64*) ws, (hipStream_t) stream)
-                                      : op_ckks_relinearize_II(ctx->c, (u64*) ct, cs, (const u64*) key, depth, batch,
-                                                               (u64*) ws, (hipStream_t) stream),
+    return hip_ret(op_ckks_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, depth, batch, (u64*) ws,
+                                       (hipStream_t) stream),
                    "hegpu_ckks_relinearize_inplace");
 }
 
@@ -864,11 +855,8 @@ int hegpu_ckks_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t cs,
     }
     if (galois_elt <= 0 || !(galois_elt & 1) || galois_elt >= 2 * (int) ctx->c.n)
         return fail(HEGPU_E_INVALID, "apply_galois: Galois elements are odd and below 2N");
-    return hip_ret(ctx->c.P_size == 1
-                       ? op_ckks_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key,
-                                              galois_elt, depth, batch, (u64*) ws, (hipStream_t) stream)
-                       : op_ckks_apply_galois_II(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key,
-                                                 galois_elt, depth, batch, (u64*) ws, (hipStream_t) stream),
+    return hip_ret(op_ckks_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key, galois_elt, depth,
+                                        batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_ckks_apply_galois");
 }
 
@@ -917,10 +905,7 @@ int hegpu_bfv_relinearize_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs,
 {
     NEED_CTX(ctx);
     CHECK_OP(ctx, SCHEME_BFV, OP_BFV_RELIN, 0, batch, ws, ws_bytes);
-    return hip_ret(ctx->c.P_size == 1 ? op_bfv_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, batch, (u64*) ws,
-                                                           (hipStream_t) stream)
-                                      : op_bfv_relinearize_II(ctx->c, (u64*) ct, cs, (const u64*) key, batch,
-                                                              (u64*) ws, (hipStream_t) stream),
+    return hip_ret(op_bfv_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_relinearize_inplace");
 }
 
@@ -935,11 +920,8 @@ int hegpu_bfv_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, 
         if (spans_overlap(ct, cs, words, out, so, words, batch))
             return fail(HEGPU_E_INVALID, "apply_galois: out must not alias ct (the result buffer must not contain the input)");
     }
-    return hip_ret(ctx->c.P_size == 1
-                       ? op_bfv_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key,
-                                             galois_elt, batch, (u64*) ws, (hipStream_t) stream)
-                       : op_bfv_apply_galois_II(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key,
-                                                galois_elt, batch, (u64*) ws, (hipStream_t) stream),
+    return hip_ret(op_bfv_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key, galois_elt, batch,
+                                       (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_apply_galois");
 }
 

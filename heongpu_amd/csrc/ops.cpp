@@ -13,11 +13,12 @@ namespace hegpu {
         if (e__ != hipSuccess) return e__; \
     } while (0)
 
-static int prime_loc_offset(const Context& c, int depth)
+static u64 inv_mod_2n(u64 g, u64 two_n)
 {
-    int counter = c.Qp_size, location = 0; // reference ckks/operator.cu:949-955
-    for (int i = 0; i < depth; i++) { location += counter; counter--; }
-    return location;
+    // g odd, two_n a power of two: Newton iteration
+    u64 x = g;
+    for (int i = 0; i < 6; i++) x *= 2 - g * x;
+    return x & (two_n - 1);
 }
 
 // The fused row pass + inner product runs one workgroup per (ciphertext, target modulus, 16-row tile) that walks
@@ -177,7 +178,6 @@ hipError_t op_ckks_multiply(const Context& c, const u64* ct1, u64 s1, const u64*
 //   out[part p] = moddown(sum_i digit_i(src) * key[i][p]) + (p < add_parts ? add[part p] : 0),   p = 0, 1
 // src: [l][N] per item, src_stride apart; add / out: [2][l][N] per item.  temp1: [l][rc][N], temp2: [2][rc][N]
 // per item, both `per` apart.  out may alias add.
-static u64 inv_mod_2n(u64 g, u64 two_n);
 static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_stride, const u64* add, u64 add_stride,
                                       int add_parts, u64* outp, u64 out_stride, const u64* key, int depth, int batch,
                                       u64* temp1, u64* temp2, u64 per, hipStream_t st, unsigned phases,
@@ -199,8 +199,8 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     NttArgs dgt = c.ntt_args(0);
     dgt.in = temp2; dgt.out = temp1; dgt.mod_count = rc; dgt.polys_per_item = l * rc; dgt.decomp_mods = rc;
     dgt.in_item_stride = per; dgt.out_item_stride = per;
-    dgt.mod_order = c.d32("new_prime_locations") + prime_loc_offset(c, depth);
-    fill_int_slots(c, dgt, c.h64("new_prime_locations").data() + prime_loc_offset(c, depth));
+    dgt.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    fill_int_slots(c, dgt, c.h64("new_prime_locations").data() + triangle_offset(Qp, depth));
     // When the decomposing column pass is the multi-modulus kernel (one launch for the whole batch), it also
     // finishes the inverse transform of its source tiles: only the row stages of the INTT run on their own.
     const bool fuse_inv = use_fused_row_mac(c, rc, batch) && c.fuse_inverse && (long) l * rc * batch <= 65535 &&
@@ -265,11 +265,135 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
                                  c.d64("last_q_modinv"), np, l, 1, batch, st);
 }
 
+// ------------------------------------------------------------------ method II (P_size > 1)
+static hipError_t dtoq(const Context& c, int lvl, const u64* in, u64 in_stride, u64* out, u64 out_stride, int l,
+                       int level, int batch, hipStream_t st)
+{
+    const Context::M2Level& L = c.m2_levels[lvl];
+    return rns_base_conversion_DtoQtilde(in, in_stride, out, out_stride, c.plan_qp.mods,
+                                         c.d64("m2_matrix_mg") + L.off_matrix, c.d64("m2_Mi_inv") + L.off_mi,
+                                         c.d64("m2_negprod_mg") + L.off_prod, c.d32("m2_I_j") + L.off_digits,
+                                         c.d32("m2_I_location") + L.off_digits, c.n_power, L.d, L.rc, l, level,
+                                         c.m2_width, batch, st);
+}
+
+// reference ckks/operator.cu:1025-1154
+// CKKS key switching with several special primes, tail: acc [2][rc][N] (NTT domain) -> out [2][l][N] =
+// moddown(acc) + ct (parts below add_parts; 0 = both) [-> Galois automorphism].  The reference runs the INTT of all
+// 2 rc limbs, divide_round_lastq_extended_leveled_kernel, the NTT of 2 l limbs and an addition
+// (ckks/operator.cu:1131-1149).  Here only the 2 P special limbs are inverse-transformed; from them one kernel
+// forms, per limb of Q, the value u whose transform the forward pass's epilogue subtracts from the accumulated limb
+// before multiplying by W0 = prod P_i^-1 (context.cpp m2_md_*): the same exact integer function, so the same
+// residues.  scratch: [2][l][N] per item (`per` apart).
+static hipError_t ckks_moddown_multi(const Context& c, u64* acc, u64* scratch, u64 per, const u64* ct, u64 cs,
+                                     int add_parts, u64* out, u64 so, int depth, int galois_elt, int batch,
+                                     hipStream_t st)
+{
+    const u64 n = c.n;
+    const int Q = c.Q_size, Qp = c.Qp_size, P = c.P_size;
+    const int l = Q - depth, rc = Qp - depth;
+    for (int part = 0; part < 2; part++) {
+        NttArgs a = c.ntt_args(0);
+        a.in = a.out = acc + (u64) (part * rc + l) * n;
+        a.mod_count = P; a.mod_offset = Q; a.polys_per_item = P;
+        a.in_item_stride = a.out_item_stride = per;
+        TRY(ntt_launch(a, P * batch, true, st));
+    }
+    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
+                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, rc, l, Qp, Q,
+                                    P, batch, st));
+    NttArgs a = c.ntt_args(0);
+    a.in = a.out = scratch; a.mod_count = l; a.polys_per_item = 2 * l;
+    a.in_item_stride = a.out_item_stride = per;
+    a.epi.on = 1;
+    a.epi.ks = acc; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = rc;
+    a.epi.ct = ct; a.epi.ct_item_stride = cs; a.epi.ct_parts = add_parts;
+    a.epi.out = out; a.epi.out_item_stride = so;
+    a.epi.inv = c.d64("m2_md_W0");
+    a.epi.limbs = l;
+    a.epi.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
+    return ntt_launch(a, 2 * l * batch, false, st);
+}
+
+// The reference-order tail of a CKKS rotation (ckks/operator.cu:1524-1541): INTT of the 2 rc accumulator limbs
+// acc [2][rc][N], mod-down + Galois permutation with c0 of the coefficient-domain ciphertext coef [2][l][N] added (both
+// `per` apart per item), NTT of the 2 l limbs of out.
+static hipError_t ckks_rotate_tail(const Context& c, u64* acc, const u64* coef, u64 per, u64* out, u64 so, int galois_elt,
+                                   int depth, int batch, hipStream_t st)
+{
+    const int Q = c.Q_size, Qp = c.Qp_size;
+    const int l = Q - depth, rc = Qp - depth;
+    NttArgs a = c.ntt_args(0);
+    a.in = acc; a.out = acc; a.mod_count = rc; a.polys_per_item = 2 * rc;
+    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    a.in_item_stride = a.out_item_stride = per;
+    TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1524
+    TRY(rns_moddown_permute(acc, per, coef, per, out, so, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
+                            c.d64("last_q_modinv"), galois_elt, c.n_power, rc, l, Qp, Q, c.P_size, batch, st)); // :1530
+    a = c.ntt_args(0);
+    a.in = out; a.out = out; a.mod_count = l; a.polys_per_item = 2 * l;
+    a.in_item_stride = a.out_item_stride = so;
+    return ntt_launch(a, 2 * l * batch, false, st);                                        // :1541
+}
+
+// Key switch, method II, of part `add_parts` of each ciphertext with the parts below it added: c2 for relinearize
+// (add_parts 2, out == ct; reference ckks/operator.cu:1025-1154), c1 for apply_galois (add_parts 1, then the
+// automorphism galois_elt; :1561-1720).  Relinearize inverse-transforms c2 in place; a rotation inverse-transforms c1
+// into a [2][l][N] coefficient-domain copy at the front of its workspace, and c0 too when its tail runs in the
+// reference order.  Workspace: OP_CKKS_RELIN / OP_CKKS_GALOIS.
+static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int add_parts, u64* out, u64 so,
+                                    const u64* key, int galois_elt, int depth, int batch, u64* ws, hipStream_t st)
+{
+    const int np = c.n_power;
+    const u64 n = c.n;
+    const int Q = c.Q_size, Qp = c.Qp_size;
+    const int l = Q - depth, rc = Qp - depth;
+    const int d = c.m2_levels[depth].d;
+    const bool relin = add_parts == 2;
+    // the mod-down as the epilogue of its forward transform (ckks_moddown_multi); a rotation's c0 then stays in the NTT
+    // domain (see op_ckks_apply_galois)
+    const bool ntt_domain = c.fused_moddown && (relin || c.ntt_galois);
+    const u64 copy = relin ? 0 : (u64) 2 * l * n;
+    const u64 per = copy + ((u64) l * rc + 2 * rc) * n;
+    u64* coef = relin ? out : ws; // the coefficient-domain parts, coef_stride apart
+    const u64 coef_stride = relin ? so : per;
+    u64* digits = ws + copy;              // [d][rc][N]
+    u64* acc = digits + (u64) l * rc * n; // [2][rc][N]
+    const int first = (relin || ntt_domain) ? add_parts : 0; // first part inverse-transformed
+    NttArgs a = c.ntt_args(0);
+    a.in = ct + (u64) first * l * n; a.out = coef + (u64) first * l * n; a.mod_count = l;
+    a.polys_per_item = (add_parts + 1 - first) * l;
+    a.in_item_stride = cs; a.out_item_stride = coef_stride;
+    TRY(ntt_launch(a, a.polys_per_item * batch, true, st));                                // :1052
+    TRY(dtoq(c, depth, coef + (u64) add_parts * l * n, coef_stride, digits, per, l, depth, batch, st)); // :1065
+    a = c.ntt_args(0);
+    a.in = digits; a.out = digits; a.mod_count = rc; a.polys_per_item = d * rc;
+    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    a.in_item_stride = a.out_item_stride = per;
+    TRY(keyswitch_ntt_mac(c, a, key, acc, per, d, rc, l, depth, nullptr, 0, batch, st));  // :1095-1125
+    // the front of the workspace (the digits of a relinearization, the coefficient-domain copy of a rotation) is free
+    // again: scratch of the mod-down; ct_parts 0 adds both parts
+    if (ntt_domain)
+        return ckks_moddown_multi(c, acc, ws, per, ct, cs, relin ? 0 : add_parts, out, so, depth, galois_elt, batch, st);
+    if (!relin) return ckks_rotate_tail(c, acc, ws, per, out, so, galois_elt, depth, batch, st);
+    a.in = acc; a.out = acc; a.polys_per_item = 2 * rc;
+    TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1131
+    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
+                             c.d64("last_q_modinv"), np, rc, l, Qp, Q, c.P_size, 0, batch, st)); // :1136
+    a = c.ntt_args(0);
+    a.in = ws; a.out = ws; a.mod_count = l; a.polys_per_item = 2 * l;
+    a.in_item_stride = a.out_item_stride = per;
+    TRY(ntt_launch(a, 2 * l * batch, false, st));                                          // :1145
+    // addition(temp1, ct, ct): per-item strides differ, so one launch per item batch via copy-free add
+    return rns_addition_strided(ws, per, ct, cs, out, so, c.plan_qp.mods, np, l, 2, batch, st); // :1149
+}
+
 // reference ckks/operator.cu:899-1023
 hipError_t op_ckks_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int depth, int batch, u64* ws,
                                hipStream_t st, unsigned phases)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (c.P_size > 1) return ckks_keyswitch_II(c, ct, cs, 2, ct, cs, key, 0, depth, batch, ws, st);
     const u64 n = c.n;
     const int l = c.Q_size - depth, rc = c.Qp_size - depth;
     const u64 per = ((u64) l * rc + 2 * rc) * n;
@@ -287,8 +411,7 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
     const u64 n = c.n;
     const int Q = c.Q_size, P = c.P_size;
     const int l = Q - depth;
-    int counter = Q - 1, location = 0;
-    for (int i = 0; i < depth; i++) { location += counter; counter--; }
+    const int location = triangle_offset(Q - 1, depth); // reference ckks/operator.cu:1181-1187
     const u64 per = ((u64) 2 * (l - 1) + 2 * l) * n;
     u64* temp1 = ws;                         // [2][l-1][N]
     u64* temp2 = ws + (u64) 2 * (l - 1) * n; // copy of ct, part stride l
@@ -342,6 +465,7 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
                                 int galois_elt, int depth, int batch, u64* ws, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (c.P_size > 1) return ckks_keyswitch_II(c, ct, cs, 1, out, so, key, galois_elt, depth, batch, ws, st);
     const int np = c.n_power;
     const u64 n = c.n;
     const int Q = c.Q_size, Qp = c.Qp_size;
@@ -350,8 +474,6 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
     u64* temp0 = ws;                       // [2][l][N] coefficient-domain copy of ct
     u64* temp2 = temp0 + (u64) 2 * l * n;  // [l][rc][N]
     u64* temp3 = temp2 + (u64) l * rc * n; // [2][rc][N]
-    const Mod* mods = c.plan_qp.mods;
-    const int* order = c.d32("new_prime_locations") + prime_loc_offset(c, depth);
 
     if (c.fused_moddown && c.ntt_galois) {
         // The key switch of c1 exactly as relinearize does it (c0 added to part 0 by the mod-down epilogue), all
@@ -374,18 +496,9 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
     a = c.ntt_args(0); // ckks_duplicate_kernel fused into the NTT load          :1467-1494
     a.in = temp0 + (u64) l * n; a.out = temp2; a.mod_count = rc; a.polys_per_item = l * rc; a.decomp_mods = rc;
     a.in_item_stride = a.out_item_stride = per;
-    a.mod_order = order;
+    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
     TRY(keyswitch_ntt_mac(c, a, key, temp3, per, l, rc, l, depth, ct + (u64) l * n, cs, batch, st)); // :1490-1520
-    a.decomp_mods = 0;
-    a.skip_identity = 0;
-    a.in = temp3; a.out = temp3; a.polys_per_item = 2 * rc;
-    TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1524
-    TRY(rns_moddown_permute(temp3, per, temp0, per, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                            c.d64("last_q_modinv"), galois_elt, np, rc, l, Qp, Q, c.P_size, batch, st)); // :1530
-    a = c.ntt_args(0);
-    a.in = out; a.out = out; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = a.out_item_stride = so;
-    return ntt_launch(a, 2 * l * batch, false, st);                                        // :1541
+    return ckks_rotate_tail(c, temp3, temp0, per, out, so, galois_elt, depth, batch, st);
 }
 
 // reference bfv/operator.cu:336-430
@@ -443,188 +556,96 @@ static hipError_t bfv_intt_moddown(const Context& c, u64* acc, u64 per, const u6
     return ntt_launch(a, 2 * Qp * batch, true, st);
 }
 
-// reference bfv/operator.cu:505-583
-hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws,
-                              hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
-    u64* temp1 = ws;
-    u64* temp2 = ws + (u64) Q * Qp * n;
-    const Mod* mods = c.plan_qp.mods;
-    NttArgs a = c.ntt_args(0); // cipher_broadcast_kernel fused into the NTT load    :515-534
-    a.in = ct + ((u64) Q << (np + 1)); a.out = temp1; a.mod_count = Qp; a.polys_per_item = Q * Qp;
-    a.decomp_mods = Qp;
-    a.in_item_stride = cs; a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, Q, Qp, Qp, 0, nullptr, 0, batch, st));             // :531-566
-    if (c.P_size == 1 && c.fused_moddown)
-        return bfv_intt_moddown(c, temp2, per, ct, cs, 2, ct, cs, 0, batch, st);            // :571-576 in one transform
-    a.decomp_mods = 0; a.in_item_stride = per;
-    a.in = temp2; a.out = temp2; a.polys_per_item = 2 * Qp;
-    TRY(ntt_launch(a, 2 * Qp * batch, true, st));                                          // :571
-    return rns_divide_round_lastq(temp2, per, ct, cs, ct, cs, mods, c.d64("half"), c.d64("half_mod"),
-                                  c.d64("last_q_modinv"), np, Q, 0, batch, st);            // :576
-}
-
-// reference bfv/operator.cu:771-864 (c0 is read straight from the input
-// ciphertext instead of being copied aside: out must not alias ct)
-hipError_t op_bfv_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
-                               int galois_elt, int batch, u64* ws, hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
-    u64* temp1 = ws;
-    u64* temp2 = ws + (u64) Q * Qp * n;
-    const Mod* mods = c.plan_qp.mods;
-    NttArgs a = c.ntt_args(0); // bfv_duplicate_kernel fused into the NTT load       :789-808
-    a.in = ct + (u64) Q * n; a.out = temp1; a.mod_count = Qp; a.polys_per_item = Q * Qp;
-    a.decomp_mods = Qp;
-    a.in_item_stride = cs; a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, Q, Qp, Qp, 0, nullptr, 0, batch, st));             // :805-840
-    if (c.P_size == 1 && c.fused_moddown)
-        return bfv_intt_moddown(c, temp2, per, ct, cs, 1, out, so, galois_elt, batch, st);  // :846-853 in one transform
-    a.decomp_mods = 0; a.in_item_stride = per;
-    a.in = temp2; a.out = temp2; a.polys_per_item = 2 * Qp;
-    TRY(ntt_launch(a, 2 * Qp * batch, true, st));                                          // :846
-    return rns_moddown_permute(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                               c.d64("last_q_modinv"), galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st); // :853
-}
-
-// ------------------------------------------------------------------ method II (P_size > 1)
-static hipError_t dtoq(const Context& c, int lvl, const u64* in, u64 in_stride, u64* out, u64 out_stride, int l,
-                       int level, int batch, hipStream_t st)
-{
-    const Context::M2Level& L = c.m2_levels[lvl];
-    return rns_base_conversion_DtoQtilde(in, in_stride, out, out_stride, c.plan_qp.mods,
-                                         c.d64("m2_matrix_mg") + L.off_matrix, c.d64("m2_Mi_inv") + L.off_mi,
-                                         c.d64("m2_negprod_mg") + L.off_prod, c.d32("m2_I_j") + L.off_digits,
-                                         c.d32("m2_I_location") + L.off_digits, c.n_power, L.d, L.rc, l, level,
-                                         c.m2_width, batch, st);
-}
-
-// reference ckks/operator.cu:1025-1154
-// CKKS key switching with several special primes, tail: acc [2][rc][N] (NTT domain) -> out [2][l][N] =
-// moddown(acc) + ct (parts below add_parts; 0 = both) [-> Galois automorphism].  The reference runs the INTT of all
-// 2 rc limbs, divide_round_lastq_extended_leveled_kernel, the NTT of 2 l limbs and an addition
-// (ckks/operator.cu:1131-1149).  Here only the 2 P special limbs are inverse-transformed; from them one kernel
-// forms, per limb of Q, the value u whose transform the forward pass's epilogue subtracts from the accumulated limb
-// before multiplying by W0 = prod P_i^-1 (context.cpp m2_md_*): the same exact integer function, so the same
-// residues.  scratch: [2][l][N] per item (`per` apart).
-static hipError_t ckks_moddown_multi(const Context& c, u64* acc, u64* scratch, u64 per, const u64* ct, u64 cs,
-                                     int add_parts, u64* out, u64 so, int depth, int galois_elt, int batch,
-                                     hipStream_t st)
+// BFV key switching with several special primes, tail: acc [2][Q'][N] (NTT domain) -> out [2][Q][N] = moddown(acc) + ct
+// (parts below add_parts) [-> Galois permutation].  The reference inverse-transforms all 2 Q' limbs and runs
+// divide_round_lastq_extended_kernel / divide_round_lastq_permute_bfv_kernel (bfv/operator.cu:657-667, 948-963).  Here
+// the 2 P special limbs are inverse-transformed first, one kernel forms u = sum_i lh_i G_i - C per limb of Q from them
+// (the chain among the special limbs run once per coefficient, context.cpp m2_md_*), and the division (x - u) * W0,
+// the added ciphertext and the permutation are the epilogue of the Q limbs' inverse transform (NttInvEpilogue::u):
+// the same exact integer function, the coefficient-domain accumulator is never written or read back.
+// scratch: [2][Q][N] per item (`per` apart).
+static hipError_t bfv_intt_moddown_multi(const Context& c, u64* acc, u64* scratch, u64 per, const u64* ct, u64 cs,
+                                         int add_parts, u64* out, u64 so, int galois_elt, int batch, hipStream_t st)
 {
     const u64 n = c.n;
     const int Q = c.Q_size, Qp = c.Qp_size, P = c.P_size;
-    const int l = Q - depth, rc = Qp - depth;
     for (int part = 0; part < 2; part++) {
         NttArgs a = c.ntt_args(0);
-        a.in = a.out = acc + (u64) (part * rc + l) * n;
+        a.in = a.out = acc + (u64) (part * Qp + Q) * n;
         a.mod_count = P; a.mod_offset = Q; a.polys_per_item = P;
         a.in_item_stride = a.out_item_stride = per;
         TRY(ntt_launch(a, P * batch, true, st));
     }
     TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, rc, l, Qp, Q,
-                                    P, batch, st));
+                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, Qp, Q, Qp, Q, P,
+                                    batch, st));
     NttArgs a = c.ntt_args(0);
-    a.in = a.out = scratch; a.mod_count = l; a.polys_per_item = 2 * l;
+    a.in = a.out = acc; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
     a.in_item_stride = a.out_item_stride = per;
-    a.epi.on = 1;
-    a.epi.ks = acc; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = rc;
-    a.epi.ct = ct; a.epi.ct_item_stride = cs; a.epi.ct_parts = add_parts;
-    a.epi.out = out; a.epi.out_item_stride = so;
-    a.epi.inv = c.d64("m2_md_W0");
-    a.epi.limbs = l;
-    a.epi.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
-    return ntt_launch(a, 2 * l * batch, false, st);
+    a.iepi.on = 1; a.iepi.limbs = Q; a.iepi.p_count = P; a.iepi.add_parts = add_parts; a.iepi.p_mod = Q;
+    a.iepi.galois_elt = galois_elt;
+    a.iepi.inv = c.d64("m2_md_W0");
+    a.iepi.u = scratch; a.iepi.u_item_stride = per;
+    a.iepi.ct = ct; a.iepi.ct_item_stride = cs;
+    a.iepi.out = out; a.iepi.out_item_stride = so;
+    return ntt_launch(a, 2 * Qp * batch, true, st);
 }
 
-hipError_t op_ckks_relinearize_II(const Context& c, u64* ct, u64 cs, const u64* key, int depth, int batch, u64* ws,
-                                  hipStream_t st)
+// BFV key switch of part `add_parts` of each ciphertext with the parts below it added: c2 for relinearize (add_parts 2,
+// out == ct; reference bfv/operator.cu:505-583, 585-672), c1 for apply_galois (add_parts 1, then the Galois permutation
+// galois_elt; :771-864, 866-973).  c0 is read straight from ct instead of being copied aside: a rotation's out must not
+// alias ct.  Method I decomposes into digits in the forward NTT's load (cipher_broadcast_kernel / bfv_duplicate_kernel),
+// method II converts them first (base_conversion_DtoQtilde).
+static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add_parts, u64* out, u64 so,
+                                const u64* key, int galois_elt, int batch, u64* ws, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     const int np = c.n_power;
     const u64 n = c.n;
     const int Q = c.Q_size, Qp = c.Qp_size;
-    const int l = Q - depth, rc = Qp - depth;
-    const int d = c.m2_levels[depth].d;
-    const u64 per = ((u64) l * rc + 2 * rc) * n;
-    u64* temp1 = ws;
-    u64* temp2 = ws + (u64) l * rc * n;
-    u64* c2 = ct + ((u64) l << (np + 1));
+    const bool m2 = c.P_size > 1;
+    const int digits = m2 ? c.m2_levels[0].d : Q;
+    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
+    u64* temp1 = ws;                    // [digits][Q'][N]
+    u64* temp2 = ws + (u64) Q * Qp * n; // [2][Q'][N]
     const Mod* mods = c.plan_qp.mods;
-    const int* order = c.d32("new_prime_locations") + prime_loc_offset(c, depth);
+    const u64* src = ct + (u64) add_parts * Q * n;
     NttArgs a = c.ntt_args(0);
-    a.in = c2; a.out = c2; a.mod_count = l; a.polys_per_item = l;
-    a.in_item_stride = a.out_item_stride = cs;
-    TRY(ntt_launch(a, l * batch, true, st));                                               // :1052
-    TRY(dtoq(c, depth, c2, cs, temp1, per, l, depth, batch, st));                          // :1065
-    a = c.ntt_args(0);
-    a.in = temp1; a.out = temp1; a.mod_count = rc; a.polys_per_item = d * rc; a.mod_order = order;
-    a.in_item_stride = a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, d, rc, l, depth, nullptr, 0, batch, st));          // :1095-1125
-    if (c.fused_moddown) // temp1 ([d][rc][N], the digits) is free again: scratch of the mod-down
-        return ckks_moddown_multi(c, temp2, temp1, per, ct, cs, 0, ct, cs, depth, 0, batch, st);
-    a.in = temp2; a.out = temp2; a.polys_per_item = 2 * rc;
-    TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1131
-    TRY(rns_moddown_extended(temp2, per, nullptr, 0, temp1, per, mods, c.d64("half"), c.d64("half_mod"),
-                             c.d64("last_q_modinv"), np, rc, l, Qp, Q, c.P_size, 0, batch, st)); // :1136
-    a = c.ntt_args(0);
-    a.in = temp1; a.out = temp1; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = a.out_item_stride = per;
-    TRY(ntt_launch(a, 2 * l * batch, false, st));                                          // :1145
-    // addition(temp1, ct, ct): per-item strides differ, so one launch per item batch via copy-free add
-    return rns_addition_strided(temp1, per, ct, cs, ct, cs, mods, np, l, 2, batch, st);     // :1149
-}
-
-// reference ckks/operator.cu:1561-1720
-hipError_t op_ckks_apply_galois_II(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
-                                   int galois_elt, int depth, int batch, u64* ws, hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const int l = Q - depth, rc = Qp - depth;
-    const int d = c.m2_levels[depth].d;
-    const u64 per = ((u64) 2 * l + (u64) l * rc + 2 * rc) * n;
-    u64* temp0 = ws;
-    u64* temp3 = temp0 + (u64) 2 * l * n;
-    u64* temp4 = temp3 + (u64) l * rc * n;
-    const Mod* mods = c.plan_qp.mods;
-    const int* order = c.d32("new_prime_locations") + prime_loc_offset(c, depth);
-    const bool ntt_domain = c.fused_moddown && c.ntt_galois;
-    NttArgs a = c.ntt_args(0);
-    a.in = ct; a.out = temp0; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = cs; a.out_item_stride = per;
-    if (ntt_domain) { // c0 stays in the NTT domain (see op_ckks_apply_galois): only c1 is needed as coefficients
-        a.in = ct + (u64) l * n; a.out = temp0 + (u64) l * n; a.polys_per_item = l;
-        TRY(ntt_launch(a, l * batch, true, st));
+    a.out = temp1; a.mod_count = Qp; a.polys_per_item = digits * Qp; a.out_item_stride = per;
+    if (m2) {
+        TRY(dtoq(c, 0, src, cs, temp1, per, Q, 0, batch, st));
+        a.in = temp1; a.in_item_stride = per;
     } else {
-        TRY(ntt_launch(a, 2 * l * batch, true, st));
+        a.in = src; a.in_item_stride = cs; a.decomp_mods = Qp;
     }
-    TRY(dtoq(c, depth, temp0 + (u64) l * n, per, temp3, per, l, depth, batch, st));
+    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, digits, Qp, Qp, 0, nullptr, 0, batch, st));
+    if (c.fused_moddown) { // temp1 (the digits) is free again: scratch of the multi-prime mod-down
+        if (m2) return bfv_intt_moddown_multi(c, temp2, temp1, per, ct, cs, add_parts, out, so, galois_elt, batch, st);
+        return bfv_intt_moddown(c, temp2, per, ct, cs, add_parts, out, so, galois_elt, batch, st);
+    }
     a = c.ntt_args(0);
-    a.in = temp3; a.out = temp3; a.mod_count = rc; a.polys_per_item = d * rc; a.mod_order = order;
+    a.in = temp2; a.out = temp2; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
     a.in_item_stride = a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp4, per, d, rc, l, depth, nullptr, 0, batch, st));
-    if (ntt_domain) // temp0 is free again: scratch of the mod-down; c0 added and the automorphism applied by its epilogue
-        return ckks_moddown_multi(c, temp4, temp0, per, ct, cs, 1, out, so, depth, galois_elt, batch, st);
-    a.in = temp4; a.out = temp4; a.polys_per_item = 2 * rc;
-    TRY(ntt_launch(a, 2 * rc * batch, true, st));
-    TRY(rns_moddown_permute(temp4, per, temp0, per, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                            c.d64("last_q_modinv"), galois_elt, np, rc, l, Qp, Q, c.P_size, batch, st));
-    a = c.ntt_args(0);
-    a.in = out; a.out = out; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = a.out_item_stride = so;
-    return ntt_launch(a, 2 * l * batch, false, st);
+    TRY(ntt_launch(a, 2 * Qp * batch, true, st));
+    if (add_parts == 1)
+        return rns_moddown_permute(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
+                                   c.d64("last_q_modinv"), galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st);
+    if (m2)
+        return rns_moddown_extended(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
+                                    c.d64("last_q_modinv"), np, Qp, Q, Qp, Q, c.P_size, 1, batch, st);
+    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
+                                  c.d64("last_q_modinv"), np, Q, 0, batch, st);
+}
+
+hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws, hipStream_t st)
+{
+    return bfv_keyswitch(c, ct, cs, 2, ct, cs, key, 0, batch, ws, st);
+}
+
+hipError_t op_bfv_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
+                               int galois_elt, int batch, u64* ws, hipStream_t st)
+{
+    return bfv_keyswitch(c, ct, cs, 1, out, so, key, galois_elt, batch, ws, st);
 }
 
 // Hoisted rotations: fast_single_hoisting_rotation_ckks_method_I / _II (reference ckks/operator.cu:4674-4953,
@@ -655,7 +676,7 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     u64* temp2 = temp0 + (u64) 2 * l * n;  // [digits][rc][N] NTT-domain digits
     u64* temp3 = temp2 + (u64) l * rc * n; // [group][2][rc][N]
     const Mod* mods = c.plan_qp.mods;
-    const int* order = c.d32("new_prime_locations") + prime_loc_offset(c, depth);
+    const int* order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
     const u64 ct_words = (u64) 2 * l * n;
     bool any = false;
     for (int i = 0; i < count; i++) {
@@ -669,11 +690,9 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
         int nz = 0, which = -1;
         for (int i = 0; i < count; i++)
             if (galois_elts[i] != 0) { nz++; which = i; }
-        if (nz == 1) {
-            u64* oi = out + (u64) which * ct_words;
-            return m2 ? op_ckks_apply_galois_II(c, ct, cs, oi, so, keys[which], galois_elts[which], depth, batch, ws, st)
-                      : op_ckks_apply_galois(c, ct, cs, oi, so, keys[which], galois_elts[which], depth, batch, ws, st);
-        }
+        if (nz == 1)
+            return op_ckks_apply_galois(c, ct, cs, out + (u64) which * ct_words, so, keys[which], galois_elts[which], depth,
+                                        batch, ws, st);
     }
 
     // With the mod-down fused into its transform every element stays in the NTT domain -- inner product, INTT of
@@ -733,116 +752,12 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
             continue;
         }
         if (group > 1) return hipErrorInvalidValue; // the reference-order tail works on one accumulator
-        NttArgs b = c.ntt_args(0);
-        b.in = temp3; b.out = temp3; b.mod_count = rc; b.polys_per_item = 2 * rc; b.mod_order = order;
-        b.in_item_stride = b.out_item_stride = per;
-        TRY(ntt_launch(b, 2 * rc * batch, true, st));
-        TRY(rns_moddown_permute(temp3, per, temp0, per, oi, so, mods, c.d64("half"), c.d64("half_mod"),
-                                c.d64("last_q_modinv"), galois_elts[i], np, rc, l, Qp, Q, c.P_size, batch, st));
-        b = c.ntt_args(0);
-        b.in = oi; b.out = oi; b.mod_count = l; b.polys_per_item = 2 * l;
-        b.in_item_stride = b.out_item_stride = so;
-        TRY(ntt_launch(b, 2 * l * batch, false, st));
+        TRY(ckks_rotate_tail(c, temp3, temp0, per, oi, so, galois_elts[i], depth, batch, st));
     }
     return hipSuccess;
 }
 
-// BFV key switching with several special primes, tail: acc [2][Q'][N] (NTT domain) -> out [2][Q][N] = moddown(acc) + ct
-// (parts below add_parts) [-> Galois permutation].  The reference inverse-transforms all 2 Q' limbs and runs
-// divide_round_lastq_extended_kernel / divide_round_lastq_permute_bfv_kernel (bfv/operator.cu:657-667, 948-963).  Here
-// the 2 P special limbs are inverse-transformed first, one kernel forms u = sum_i lh_i G_i - C per limb of Q from them
-// (the chain among the special limbs run once per coefficient, context.cpp m2_md_*), and the division (x - u) * W0,
-// the added ciphertext and the permutation are the epilogue of the Q limbs' inverse transform (NttInvEpilogue::u):
-// the same exact integer function, the coefficient-domain accumulator is never written or read back.
-// scratch: [2][Q][N] per item (`per` apart).
-static hipError_t bfv_intt_moddown_multi(const Context& c, u64* acc, u64* scratch, u64 per, const u64* ct, u64 cs,
-                                         int add_parts, u64* out, u64 so, int galois_elt, int batch, hipStream_t st)
-{
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size, P = c.P_size;
-    for (int part = 0; part < 2; part++) {
-        NttArgs a = c.ntt_args(0);
-        a.in = a.out = acc + (u64) (part * Qp + Q) * n;
-        a.mod_count = P; a.mod_offset = Q; a.polys_per_item = P;
-        a.in_item_stride = a.out_item_stride = per;
-        TRY(ntt_launch(a, P * batch, true, st));
-    }
-    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, Qp, Q, Qp, Q, P,
-                                    batch, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = a.out = acc; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
-    a.in_item_stride = a.out_item_stride = per;
-    a.iepi.on = 1; a.iepi.limbs = Q; a.iepi.p_count = P; a.iepi.add_parts = add_parts; a.iepi.p_mod = Q;
-    a.iepi.galois_elt = galois_elt;
-    a.iepi.inv = c.d64("m2_md_W0");
-    a.iepi.u = scratch; a.iepi.u_item_stride = per;
-    a.iepi.ct = ct; a.iepi.ct_item_stride = cs;
-    a.iepi.out = out; a.iepi.out_item_stride = so;
-    return ntt_launch(a, 2 * Qp * batch, true, st);
-}
-
-// reference bfv/operator.cu:585-672
-hipError_t op_bfv_relinearize_II(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws,
-                                 hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const int d = c.m2_levels[0].d;
-    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
-    u64* temp1 = ws;
-    u64* temp2 = ws + (u64) Q * Qp * n;
-    const Mod* mods = c.plan_qp.mods;
-    TRY(dtoq(c, 0, ct + ((u64) Q << (np + 1)), cs, temp1, per, Q, 0, batch, st));          // :599
-    NttArgs a = c.ntt_args(0);
-    a.in = temp1; a.out = temp1; a.mod_count = Qp; a.polys_per_item = d * Qp;
-    a.in_item_stride = a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, d, Qp, Qp, 0, nullptr, 0, batch, st));             // :619-650
-    if (c.fused_moddown) // temp1 (the digits) is free again: scratch of the mod-down
-        return bfv_intt_moddown_multi(c, temp2, temp1, per, ct, cs, 2, ct, cs, 0, batch, st);        // :657-667 in one transform
-    a.in = temp2; a.out = temp2; a.polys_per_item = 2 * Qp;
-    TRY(ntt_launch(a, 2 * Qp * batch, true, st));                                          // :657
-    return rns_moddown_extended(temp2, per, ct, cs, ct, cs, mods, c.d64("half"), c.d64("half_mod"),
-                                c.d64("last_q_modinv"), np, Qp, Q, Qp, Q, c.P_size, 1, batch, st); // :662
-}
-
-// reference bfv/operator.cu:866-973
-hipError_t op_bfv_apply_galois_II(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
-                                  int galois_elt, int batch, u64* ws, hipStream_t st)
-{
-    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
-    const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const int d = c.m2_levels[0].d;
-    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
-    u64* temp2 = ws;
-    u64* temp3 = ws + (u64) Q * Qp * n;
-    const Mod* mods = c.plan_qp.mods;
-    TRY(dtoq(c, 0, ct + (u64) Q * n, cs, temp2, per, Q, 0, batch, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = temp2; a.out = temp2; a.mod_count = Qp; a.polys_per_item = d * Qp;
-    a.in_item_stride = a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, temp3, per, d, Qp, Qp, 0, nullptr, 0, batch, st));
-    if (c.fused_moddown) // temp2 (the digits) is free again; c0 added to part 0, the permutation as the scatter of the store
-        return bfv_intt_moddown_multi(c, temp3, temp2, per, ct, cs, 1, out, so, galois_elt, batch, st);
-    a.in = temp3; a.out = temp3; a.polys_per_item = 2 * Qp;
-    TRY(ntt_launch(a, 2 * Qp * batch, true, st));
-    return rns_moddown_permute(temp3, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                               c.d64("last_q_modinv"), galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st);
-}
-
 // ------------------------------------------------------------------ keygen / encrypt / decrypt
-static u64 inv_mod_2n(u64 g, u64 two_n)
-{
-    // g odd, two_n a power of two: Newton iteration
-    u64 x = g;
-    for (int i = 0; i < 6; i++) x *= 2 - g * x;
-    return x & (two_n - 1);
-}
-
 hipError_t op_gen_secret_key(const Context& c, Rng& r, int hamming_weight, u64* sk, u64* ws, hipStream_t st)
 {
     const int n = (int) c.n;

@@ -12,9 +12,20 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
 
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
+// Offset of row `depth` in a triangular per-depth table whose rows hold first, first - 1, ... entries
+// (reference ckks/operator.cu:949-955, 1181-1187)
+inline int triangle_offset(int first, int depth)
+{
+    int location = 0;
+    for (int i = 0; i < depth; i++) location += first - i;
+    return location;
+}
+
 hipError_t op_ckks_multiply(const Context& c, const u64* ct1, u64 s1, const u64* ct2, u64 s2, u64* out, u64 so,
                             int depth, int batch, hipStream_t st);
-// `phases`: which launches of the sequence run (all by default; hegpu_probe_ckks_relinearize times them one by one)
+// Relinearize and apply_galois run key-switching method I with one special prime (P_size == 1), method II with several.
+// `phases` (method I only): which launches of the sequence run (all by default; hegpu_probe_ckks_relinearize times them
+// one by one)
 enum { RELIN_PHASE_INTT_C2 = 1, RELIN_PHASE_COLUMN = 2, RELIN_PHASE_ROW_MAC = 4, RELIN_PHASE_INTT_P = 8,
        RELIN_PHASE_MODDOWN = 16, RELIN_PHASE_ALL = 31 };
 hipError_t op_ckks_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int depth, int batch, u64* ws,
@@ -34,16 +45,6 @@ hipError_t op_bfv_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out
 hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* const* keys,
                                   const int* galois_elts, int count, int depth, int batch, u64* ws, hipStream_t st,
                                   int group = 1 /* accumulators in ws: 1 (OP_CKKS_GALOIS) or 4 (OP_CKKS_ROTATE_HOISTED) */);
-
-// key-switching method II (P_size > 1)
-hipError_t op_ckks_relinearize_II(const Context& c, u64* ct, u64 cs, const u64* key, int depth, int batch, u64* ws,
-                                  hipStream_t st);
-hipError_t op_ckks_apply_galois_II(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
-                                   int galois_elt, int depth, int batch, u64* ws, hipStream_t st);
-hipError_t op_bfv_relinearize_II(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws,
-                                 hipStream_t st);
-hipError_t op_bfv_apply_galois_II(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
-                                  int galois_elt, int batch, u64* ws, hipStream_t st);
 
 // ---- key generation / encryption / decryption, key-switch method I
 // The generator state: every sampling call consumes one stream id of the DRBG (drbg.hpp).
