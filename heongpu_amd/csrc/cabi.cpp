@@ -299,6 +299,7 @@ int hegpu_context_clone(const hegpu_context* src, hegpu_context** out)
         c.single_pass = s.single_pass; c.ntt_galois = s.ntt_galois; c.galois_scatter = s.galois_scatter;
         c.digit_split = s.digit_split; c.copy_along = s.copy_along; c.fuse_inverse = s.fuse_inverse;
         c.fp_ntt = s.fp_ntt; c.behz_split = s.behz_split; c.fused_tensor = s.fused_tensor;
+        c.moddown_in_mac = s.moddown_in_mac;
         *out = h;
         return 0;
     });

@@ -423,6 +423,7 @@ __device__ __forceinline__ PolySel select_poly(const NttArgs& a, int poly)
     u64 slot = a.poly_order ? (u64) a.poly_order[j] : (u64) j;
     s.digit = a.decomp_mods ? udiv16(j, a.mg_decomp_mods) : -1;
     u64 in_slot = a.decomp_mods ? (u64) s.digit * (a.decomp_in_mul ? a.decomp_in_mul : 1) + a.decomp_in_add : slot;
+    if (a.decomp_out_mul) slot = (u64) s.digit * a.decomp_out_mul + (u64) (j - s.digit * a.decomp_mods);
     s.in_off = (u64) item * a.in_item_stride + (in_slot << a.n_power);
     s.out_off = (u64) item * a.out_item_stride + (slot << a.n_power);
     s.item = item;
@@ -1127,8 +1128,9 @@ __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict
 struct KsIdx { int item, tile, slot; bool valid; int d0, d1; };
 __host__ __device__ __forceinline__ unsigned ks_slots(const KsMacArgs& a, int kind)
 {
-    if (a.int_slot_count <= 0 || kind == 0) return (unsigned) a.rc;
-    return kind == 1 ? (unsigned) a.int_slot_count : (unsigned) (a.rc - a.int_slot_count);
+    const int all = a.slot_count ? a.slot_count : a.rc; // KsMacArgs::slot_first / slot_count
+    if (a.int_slot_count <= 0 || kind == 0) return (unsigned) all;
+    return kind == 1 ? (unsigned) a.int_slot_count : (unsigned) (all - a.int_slot_count);
 }
 template <bool SPLIT, int KIND = 0>
 __device__ __forceinline__ KsIdx ks_index(const KsMacArgs& a)
@@ -1152,10 +1154,13 @@ __device__ __forceinline__ KsIdx ks_index(const KsMacArgs& a)
     int si = (int) (g - gt * nslots);
     if (KIND == 1 && a.int_slot_count > 0) {
         si = a.int_slots[r.valid ? si : 0];
-    } else if (KIND == 2 && a.int_slot_count > 0) {
+    } else {
+        si += a.slot_first;
+        if (KIND == 2 && a.int_slot_count > 0) {
 #pragma unroll
-        for (int q = 0; q < 8; q++) // the si-th slot that is not in the (ascending) list
-            if (q < a.int_slot_count && a.int_slots[q] <= si) si++;
+            for (int q = 0; q < 8; q++) // the si-th slot of the range that is not in the (ascending) list
+                if (q < a.int_slot_count && a.int_slots[q] <= si) si++;
+        }
     }
     r.slot = si;
     r.d0 = SPLIT ? (int) (sp * (unsigned) a.digits / splits) : 0;
@@ -1163,9 +1168,51 @@ __device__ __forceinline__ KsIdx ks_index(const KsMacArgs& a)
     return r;
 }
 
+// Mod-down tail of the fused key switch (KsMacArgs::tail), part p of one (item, slot, tile): acc / tv = the thread's 16
+// canonical accumulated / transformed-P-limb residues at e0 + 16 k of the limb (e0 = tile * 4096 + row * 256 + i0), cv
+// the added term if with_ct.  The residues of row_store_all.
+__device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int slot, int p, u64 e0, const Mod& md, u64 inv,
+                                              const u64 (&acc)[16], const u64 (&tv)[16], bool with_ct, const u64 (&cv)[16])
+{
+    const KsMacArgs::Tail& e = a.tail;
+    u64* out = e.out + e.out_item_stride * item + ((u64) (p * e.limbs + slot) << a.n_power);
+    u64 r[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) r[k] = mul_barrett(sub_mod(acc[k], tv[k], md.q), inv, md);
+    if (with_ct) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) r[k] = add_mod(cv[k], r[k], md.q);
+    }
+    if (e.galois_inv) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            const u32 el = (u32) e0 + 16 * k;
+            const u32 ex = ((2u * (__brev(el) >> (32 - a.n_power)) + 1u) * e.galois_inv) & ((2u << a.n_power) - 1u);
+            out[__brev((ex - 1u) >> 1) >> (32 - a.n_power)] = r[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) out[e0 + 16 * k] = r[k];
+    }
+}
+// the tail's operands of part p: the column-pass output T (row stages still to do) and the added term
+__device__ __forceinline__ const u64* ks_tail_T(const KsMacArgs& a, int item, int slot, int tile, int p)
+{
+    return a.tail.T + a.tail.T_item_stride * item + ((u64) (p * a.rc + slot) << a.n_power) + (u64) tile * 4096;
+}
+__device__ __forceinline__ bool ks_tail_ct(const KsMacArgs& a, int item, int slot, int p, u64 e0, u64 (&cv)[16])
+{
+    const KsMacArgs::Tail& e = a.tail;
+    if (!e.ct || (e.ct_parts && p >= e.ct_parts)) return false;
+    const u64* c = e.ct + e.ct_item_stride * item + ((u64) (p * e.limbs + slot) << a.n_power) + e0; // may alias out
+#pragma unroll
+    for (int k = 0; k < 16; k++) cv[k] = c[16 * k];
+    return true;
+}
+
 // (bodies shared by the kernels below; `twbuf`: KS_TW_LDS_BYTES of LDS for the digit-invariant twiddles)
 #define KS_TW_LDS_BYTES ((15 * 256 + 15 * 16) * 8)
-template <bool SPLIT>
+template <bool SPLIT, bool MD = false>
 __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const KsIdx& ki, const Mod& md, int midx,
                                                     u64* lds, void* twbuf)
 {
@@ -1193,6 +1240,9 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
     }
     wave_lds_fence();
 
+    // (see ks_row_mac_fp_body)
+    const int item_s = MD ? __builtin_amdgcn_readfirstlane(item) : 0, slot_s = MD ? __builtin_amdgcn_readfirstlane(slot) : 0;
+    const int tile_s = MD ? __builtin_amdgcn_readfirstlane(tile) : 0, midx_s = MD ? __builtin_amdgcn_readfirstlane(midx) : 0;
     u64 h0[16], l0[16], h1[16], l1[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) h0[k] = l0[k] = h1[k] = l1[k] = 0;
@@ -1215,6 +1265,41 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
             acc128(h0[k], l0[k], x[k], k0[16 * k]);
             acc128(h1[k], l1[k], x[k], k1[16 * k]);
         }
+    }
+    if constexpr (MD) {
+        // mod-down tail (see ks_row_mac_fp_body); T comes from a column pass like the digits', its row stages end
+        // canonical as in ntt_fwd_row
+        u64 acc0[16], acc1[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            acc0[k] = reduce128(h0[k], l0[k], md);
+            acc1[k] = reduce128(h1[k], l1[k], md);
+        }
+        int tt = threadIdx.x; // (see ks_row_mac_fp_body)
+        asm volatile("" : "+v"(tt));
+        const int trow = tt >> 4, ti0 = tt & 15;
+        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
+        const u64 inv = a.tail.inv[midx_s];
+        const bool lazy_t = row_stages_lazy(md, a.lazy_q_max);
+        const ulonglong2* __restrict__ ttb = a.twB + ((u64) midx_s * (15u << (a.n_power - 4))) + ((u64) (tile_s * 16 + trow) * 15 * 16 + ti0);
+        auto part = [&](int p, const u64 (&acc)[16]) {
+            u64 cv[16], x[16];
+            const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
+            const u64* pT = ks_tail_T(a, item_s, slot_s, tile_s, p);
+            if (lazy_t) {
+                ks_row_digit<true>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
+#pragma unroll
+                for (int k = 0; k < 16; k++) x[k] = reduce64(x[k], md);
+            } else {
+                ks_row_digit<false>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
+            }
+            ks_tail_store(a, item_s, slot_s, p, e0, md, inv, acc, x, with_ct, cv);
+        };
+        __builtin_amdgcn_sched_barrier(0);
+        part(0, acc0);
+        __builtin_amdgcn_sched_barrier(0);
+        part(1, acc1);
+        return;
     }
     // split launches: the partial sums over the first two digits of this workgroup's own range (KsMacArgs::splits)
     u64* po = (SPLIT ? const_cast<u64*>(pin) + dig_off * ki.d0 - (u64) tile * 4096
@@ -1241,13 +1326,150 @@ __global__ __launch_bounds__(NTT_THREADS, SPLIT ? 2 : 1) void ks_row_mac(KsMacAr
     ks_row_mac_int_body<SPLIT>(a, ki, md, midx, lds, twa);
 }
 
+// Row stages of one FP64 limb tile in a ks_row_mac_fp workgroup: xr = the thread's 16 column-pass outputs (raw
+// doubles, |x| <= q / 2) of row `row`, lanes i0 + 16 k; x = the transformed values at the same positions, un-reduced
+// (|x| <= 5.22 q).  `twl`: the parked twiddles (see ks_row_mac_fp_body).
+template <bool SPLIT>
+__device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], const double* twl, u64* lds, const FC& fc,
+                                          int s1, int row, int i0, int t)
+{
+    if constexpr (SPLIT) { // small launches (ks_row_mac_split shares its registers with the integer body): twiddles read where they are used
+#pragma unroll
+        for (int k = 0; k < 16; k++) x[k] = as_f64(xr[k]);
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int half = 8 >> s;
+            FP_STAGE(fc, s1 + s);
+#pragma unroll
+            for (int b = 0; b < (1 << s); b++) {
+                const double w = twl[15 * 256 + ((1 << s) - 1 + b) * 16 + row];
+                const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
+#pragma unroll
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
+            }
+        }
+        FP_STAGE(fc, s1 + 4);
+#pragma unroll
+        for (int k = 0; k < 16; k++) x[k] = fp_reduce(x[k], fc);
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[row_phys(row * 256 + i0 + 16 * k)] = as_bits(x[k]);
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            ulonglong2 v = *reinterpret_cast<const ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]);
+            x[2 * k] = as_f64(v.x);
+            x[2 * k + 1] = as_f64(v.y);
+        }
+        // last four stages; their output goes into the product un-reduced (|x| <= 5.22 q, see the product)
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int half = 8 >> s;
+            FP_STAGE(fc, s1 + 4 + s);
+#pragma unroll
+            for (int b = 0; b < (1 << s); b++) {
+                const double wd = twl[((1 << s) - 1 + b) * 256 + t];
+                const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
+#pragma unroll
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
+            }
+        }
+    } else {
+        // Round 5: the twiddles of a stage are REQUESTED ONE STAGE AHEAD of the butterflies that use them (those of the
+        // first two stages before the digit's coefficients are waited for) and pinned there with scheduling fences.
+        // Left to itself the compiler read each twiddle right in front of its butterflies: ds_read, s_waitcnt
+        // lgkmcnt(0), butterflies -- thirty exposed LDS round trips per digit at two waves per SIMD (the same find as in
+        // the blind rotate, profiles/r5d_c5/README.md).  All thirty at once do not fit: 236 registers are taken (64
+        // sums, 64 prefetched key values, the digit), a stage ahead costs at most 8 more doubles.  The indices are hidden
+        // from the optimiser: the twiddles do not depend on the digit and would be hoisted out of the loop for good.
+        int row_o = row, t_o = t;
+        asm volatile("" : "+v"(row_o), "+v"(t_o));
+        const double* twa = twl + 15 * 256 + row_o;
+        const double* twb = twl + t_o;
+        double wn[8], wc[8];
+        wc[0] = twa[0];
+        wn[0] = twa[16];
+        wn[1] = twa[32];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < 16; k++) x[k] = as_f64(xr[k]);
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int half = 8 >> s;
+            FP_STAGE(fc, s1 + s);
+            if (s > 0) {
+#pragma unroll
+                for (int b = 0; b < (1 << s); b++) wc[b] = wn[b];
+            }
+            if (s < 3) { // next stage's twiddles (the first stage's successor was requested above)
+                if (s > 0) {
+#pragma unroll
+                    for (int b = 0; b < (2 << s); b++) wn[b] = twa[((2 << s) - 1 + b) * 16];
+                }
+            } else {
+                wn[0] = twb[0]; // first of the last four stages
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int b = 0; b < (1 << s); b++) {
+                const double w = wc[b];
+                const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
+#pragma unroll
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
+            }
+        }
+        FP_STAGE(fc, s1 + 4);
+#pragma unroll
+        for (int k = 0; k < 16; k++) x[k] = fp_reduce(x[k], fc);
+#pragma unroll
+        for (int k = 0; k < 16; k++) lds[row_phys(row * 256 + i0 + 16 * k)] = as_bits(x[k]);
+        wave_lds_fence();
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            ulonglong2 v = *reinterpret_cast<const ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]);
+            x[2 * k] = as_f64(v.x);
+            x[2 * k + 1] = as_f64(v.y);
+        }
+        // last four stages; their output goes into the product un-reduced (|x| <= 5.22 q, see the product)
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const int half = 8 >> s;
+            FP_STAGE(fc, s1 + 4 + s);
+#pragma unroll
+            for (int b = 0; b < (1 << s); b++) wc[b] = wn[b];
+            if (s < 3) {
+#pragma unroll
+                for (int b = 0; b < (2 << s); b++) wn[b] = twb[((2 << s) - 1 + b) * 256];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int b = 0; b < (1 << s); b++) {
+                const double wd = wc[b];
+                const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
+#pragma unroll
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
+            }
+        }
+    }
+    // (round 5) NO centred reduction here: x goes into the product as the "twiddle" operand, whose magnitude only
+    // enters the quotient error -- see the bound at the product below
+    wave_lds_fence();
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        *reinterpret_cast<ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]) =
+            make_ulonglong2(as_bits(x[2 * k]), as_bits(x[2 * k + 1]));
+    wave_lds_fence();
+#pragma unroll
+    for (int k = 0; k < 16; k++) x[k] = as_f64(lds[row_phys(row * 256 + i0 + 16 * k)]);
+    wave_lds_fence();
+}
+
 // FP64 moduli (Mod::fp): same fused row pass + inner product, but the inner
 // product is accumulated in FP64 as well: each digit*key product is reduced by
 // fp_mul (|t| <= 2.46 q for the un-reduced digit, |digit| <= 5.22 q: bound at the product), the running sums are
 // re-centred after every third digit (|acc| <= 7.88 q < 2^53) and made canonical once at the end.
 // Two double accumulators per coefficient instead of two 128-bit integers
 // halve the register footprint (3 waves per SIMD instead of 2).
-template <bool SPLIT>
+template <bool SPLIT, bool MD = false>
 __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsIdx& ki, const Mod& md, int midx,
                                                    u64* lds, void* twbuf)
 {
@@ -1284,6 +1506,9 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
     }
     wave_lds_fence(); // every value is read back by the wavefront that wrote it
 
+    // the tail's uniform indices in scalar registers across the digit loop (ks_index forms them on the vector ALU)
+    const int item_s = MD ? __builtin_amdgcn_readfirstlane(item) : 0, slot_s = MD ? __builtin_amdgcn_readfirstlane(slot) : 0;
+    const int tile_s = MD ? __builtin_amdgcn_readfirstlane(tile) : 0, midx_s = MD ? __builtin_amdgcn_readfirstlane(midx) : 0;
     double a0[16], a1[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) a0[k] = a1[k] = 0.0;
@@ -1318,134 +1543,7 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
 #pragma unroll
             for (int k = 0; k < 16; k++) x[k] = fp_reduce(fp_from_u64(xr[k]), fc);
         } else {
-            if constexpr (SPLIT) { // small launches (ks_row_mac_split shares its registers with the integer body): twiddles read where they are used
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = as_f64(xr[k]);
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int half = 8 >> s;
-                    FP_STAGE(fc, s1 + s);
-#pragma unroll
-                    for (int b = 0; b < (1 << s); b++) {
-                        const double w = twl[15 * 256 + ((1 << s) - 1 + b) * 16 + row];
-                        const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
-#pragma unroll
-                        for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
-                    }
-                }
-                FP_STAGE(fc, s1 + 4);
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = fp_reduce(x[k], fc);
-#pragma unroll
-                for (int k = 0; k < 16; k++) lds[row_phys(row * 256 + i0 + 16 * k)] = as_bits(x[k]);
-                wave_lds_fence();
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    ulonglong2 v = *reinterpret_cast<const ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]);
-                    x[2 * k] = as_f64(v.x);
-                    x[2 * k + 1] = as_f64(v.y);
-                }
-                // last four stages; their output goes into the product un-reduced (|x| <= 5.22 q, see the product)
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int half = 8 >> s;
-                    FP_STAGE(fc, s1 + 4 + s);
-#pragma unroll
-                    for (int b = 0; b < (1 << s); b++) {
-                        const double wd = twl[((1 << s) - 1 + b) * 256 + t];
-                        const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
-#pragma unroll
-                        for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
-                    }
-                }
-            } else {
-                // Round 5: the twiddles of a stage are REQUESTED ONE STAGE AHEAD of the butterflies that use them (those of the
-                // first two stages before the digit's coefficients are waited for) and pinned there with scheduling fences.
-                // Left to itself the compiler read each twiddle right in front of its butterflies: ds_read, s_waitcnt
-                // lgkmcnt(0), butterflies -- thirty exposed LDS round trips per digit at two waves per SIMD (the same find as in
-                // the blind rotate, profiles/r5d_c5/README.md).  All thirty at once do not fit: 236 registers are taken (64
-                // sums, 64 prefetched key values, the digit), a stage ahead costs at most 8 more doubles.  The indices are hidden
-                // from the optimiser: the twiddles do not depend on the digit and would be hoisted out of the loop for good.
-                int row_o = row, t_o = t;
-                asm volatile("" : "+v"(row_o), "+v"(t_o));
-                const double* twa = twl + 15 * 256 + row_o;
-                const double* twb = twl + t_o;
-                double wn[8], wc[8];
-                wc[0] = twa[0];
-                wn[0] = twa[16];
-                wn[1] = twa[32];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = as_f64(xr[k]);
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int half = 8 >> s;
-                    FP_STAGE(fc, s1 + s);
-                    if (s > 0) {
-#pragma unroll
-                        for (int b = 0; b < (1 << s); b++) wc[b] = wn[b];
-                    }
-                    if (s < 3) { // next stage's twiddles (the first stage's successor was requested above)
-                        if (s > 0) {
-#pragma unroll
-                            for (int b = 0; b < (2 << s); b++) wn[b] = twa[((2 << s) - 1 + b) * 16];
-                        }
-                    } else {
-                        wn[0] = twb[0]; // first of the last four stages
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int b = 0; b < (1 << s); b++) {
-                        const double w = wc[b];
-                        const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
-#pragma unroll
-                        for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
-                    }
-                }
-                FP_STAGE(fc, s1 + 4);
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = fp_reduce(x[k], fc);
-#pragma unroll
-                for (int k = 0; k < 16; k++) lds[row_phys(row * 256 + i0 + 16 * k)] = as_bits(x[k]);
-                wave_lds_fence();
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    ulonglong2 v = *reinterpret_cast<const ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]);
-                    x[2 * k] = as_f64(v.x);
-                    x[2 * k + 1] = as_f64(v.y);
-                }
-                // last four stages; their output goes into the product un-reduced (|x| <= 5.22 q, see the product)
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int half = 8 >> s;
-                    FP_STAGE(fc, s1 + 4 + s);
-#pragma unroll
-                    for (int b = 0; b < (1 << s); b++) wc[b] = wn[b];
-                    if (s < 3) {
-#pragma unroll
-                        for (int b = 0; b < (2 << s); b++) wn[b] = twb[((2 << s) - 1 + b) * 256];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int b = 0; b < (1 << s); b++) {
-                        const double wd = wc[b];
-                        const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
-#pragma unroll
-                        for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
-                    }
-                }
-            }
-            // (round 5) NO centred reduction here: x goes into the product as the "twiddle" operand, whose magnitude only
-            // enters the quotient error -- see the bound at the product below
-            wave_lds_fence();
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                *reinterpret_cast<ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]) =
-                    make_ulonglong2(as_bits(x[2 * k]), as_bits(x[2 * k + 1]));
-            wave_lds_fence();
-#pragma unroll
-            for (int k = 0; k < 16; k++) x[k] = as_f64(lds[row_phys(row * 256 + i0 + 16 * k)]);
-            wave_lds_fence();
+            ks_fp_row<SPLIT>(x, xr, twl, lds, fc, s1, row, i0, t);
         }
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -1477,6 +1575,39 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
             }
         }
     }
+    if constexpr (MD) {
+        // mod-down tail, one part at a time: T's row stages exactly as a digit's, then the integer epilogue on the
+        // canonical residues.  The lane's indices are formed anew from an opaque copy of the thread index: kept from
+        // before the digit loop, they and what the compiler derives from them sit in AGPRs across it (one wave per SIMD).
+        int tt = threadIdx.x;
+        asm volatile("" : "+v"(tt));
+        const int trow = tt >> 4, ti0 = tt & 15;
+        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
+        const Mod mds = a.mods[midx_s];
+        const u64 inv = a.tail.inv[midx_s];
+        auto part = [&](int p, const double (&acc)[16]) {
+            const u64* pT = ks_tail_T(a, item_s, slot_s, tile_s, p);
+            u64 tr[16], cv[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) tr[k] = __builtin_nontemporal_load(&pT[trow * 256 + ti0 + 16 * k]);
+            const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
+            double x[16];
+            ks_fp_row<false>(x, tr, twl, lds, fc, s1, trow, ti0, tt);
+            FP_STAGE(fc, FP_STAGE_OUT);
+            u64 av[16], tv[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                av[k] = fp_to_u64(fp_canon(acc[k], fc));
+                tv[k] = fp_to_u64(fp_canon(x[k], fc));
+            }
+            ks_tail_store(a, item_s, slot_s, p, e0, mds, inv, av, tv, with_ct, cv);
+        };
+        __builtin_amdgcn_sched_barrier(0); // (one part at a time: the loads of the second are not hoisted into the first)
+        part(0, a0);
+        __builtin_amdgcn_sched_barrier(0);
+        part(1, a1);
+        return;
+    }
     u64* po = (SPLIT ? const_cast<u64*>(pin) + dig_off * ki.d0 - (u64) tile * 4096
                      : a.out + a.out_item_stride * item + ((u64) slot << a.n_power)) +
               (u64) tile * 4096 + row * 256 + i0;
@@ -1506,6 +1637,30 @@ __global__ __launch_bounds__(NTT_THREADS) void ks_row_mac_fp(KsMacArgs a)
     ks_row_mac_fp_body<SPLIT>(a, ki, md, midx, lds, twl);
 }
 
+// The same two kernels with the mod-down tail (KsMacArgs::tail): the Q slots of a method-I key switch
+__global__ __launch_bounds__(NTT_THREADS) void ks_row_mac_fp_moddown(KsMacArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[ROW_LDS_ELEMS];
+    __shared__ double twl[15 * 256 + 15 * 16];
+    const KsIdx ki = ks_index<false, 2>(a);
+    if (!ki.valid) return;
+    const int midx = a.mod_order ? a.mod_order[ki.slot] : ki.slot;
+    const Mod md = a.mods[midx];
+    if (!md.fp) return;
+    ks_row_mac_fp_body<false, true>(a, ki, md, midx, lds, twl);
+}
+__global__ __launch_bounds__(NTT_THREADS, 1) void ks_row_mac_moddown(KsMacArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[ROW_LDS_ELEMS];
+    __shared__ ulonglong2 twa[15 * 16];
+    const KsIdx ki = ks_index<false, 1>(a);
+    if (!ki.valid) return;
+    const int midx = a.mod_order ? a.mod_order[ki.slot] : ki.slot;
+    const Mod md = a.mods[midx];
+    if (md.fp) return;
+    ks_row_mac_int_body<false, true>(a, ki, md, midx, lds, twa);
+}
+
 // Split launches are small launches (fewer workgroups than the chip holds, or barely more): the integer and the
 // FP64 moduli of a chain in ONE grid instead of two half-empty ones one after the other -- at N = 2^16, one
 // ciphertext, four pieces the two kernels took 87 + 58 us (the two integer moduli of the chain alone 58: 128
@@ -1526,6 +1681,9 @@ hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st)
 {
     if (a.digits > 64 || items <= 0) return hipErrorInvalidValue;
     if (a.splits > 1 && a.digits < 2 * a.splits) return hipErrorInvalidValue;
+    if (a.tail.on && (a.splits > 1 || !a.tail.out || !a.tail.T || !a.tail.inv)) return hipErrorInvalidValue;
+    if (a.slot_first < 0 || a.slot_count < 0 || a.slot_first + (a.slot_count ? a.slot_count : a.rc) > a.rc)
+        return hipErrorInvalidValue;
     KsMacArgs k = a;
     k.items = items;
     if (k.int_slot_count < 0 || k.int_slot_count > 8) k.int_slot_count = 0;
@@ -1535,10 +1693,14 @@ hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st)
         hipLaunchKernelGGL(ks_row_mac_split, grid_of(0), dim3(NTT_THREADS), 0, st, k);
     } else {
         // each kernel over the slots of its kind where the caller named them, else over all (the other kind exits)
-        if (!a.no_fp && ks_slots(k, 2) > 0)
-            hipLaunchKernelGGL(ks_row_mac_fp<false>, grid_of(2), dim3(NTT_THREADS), 0, st, k);
-        if (!a.no_int && ks_slots(k, 1) > 0)
-            hipLaunchKernelGGL(ks_row_mac<false>, grid_of(1), dim3(NTT_THREADS), 0, st, k);
+        if (!a.no_fp && ks_slots(k, 2) > 0) {
+            if (a.tail.on) hipLaunchKernelGGL(ks_row_mac_fp_moddown, grid_of(2), dim3(NTT_THREADS), 0, st, k);
+            else hipLaunchKernelGGL(ks_row_mac_fp<false>, grid_of(2), dim3(NTT_THREADS), 0, st, k);
+        }
+        if (!a.no_int && ks_slots(k, 1) > 0) {
+            if (a.tail.on) hipLaunchKernelGGL(ks_row_mac_moddown, grid_of(1), dim3(NTT_THREADS), 0, st, k);
+            else hipLaunchKernelGGL(ks_row_mac<false>, grid_of(1), dim3(NTT_THREADS), 0, st, k);
+        }
     }
     return hipGetLastError();
 }
@@ -2060,7 +2222,8 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
         ps.item = item;
         ps.j = digit * rc + k;
         ps.in_off = 0;
-        ps.out_off = (u64) item * a.out_item_stride + ((u64) ps.j << a.n_power);
+        ps.out_off = (u64) item * a.out_item_stride +
+                     ((u64) (a.decomp_out_mul ? digit * a.decomp_out_mul + k : ps.j) << a.n_power);
         if (a.skip_identity && ps.mod == digit) continue;
         const Mod md = ld_const_mod(a.mods + ps.mod);
         if (!md.fp) continue; // integer target moduli: ntt_fwd_col<S1, true> with only_int

@@ -122,6 +122,9 @@ struct NttArgs {
     // mod-down (divide_round_lastq_leveled_stage_one_kernel, switchkey.cu:678-705) as the load
     // transform of the NTT that follows it.
     int decomp_in_mul, decomp_in_add;
+    // Decomposing launches: target slot k of digit d is written to output slot d * decomp_out_mul + k (0: to
+    // d * decomp_mods + k, i.e. polynomial j of the item)
+    int decomp_out_mul;
     int half_on, half_src_mod;
     u64 half;
     const u64* half_mod;
@@ -215,6 +218,28 @@ struct KsMacArgs {
     // NttArgs::int_slots): each kernel then runs on a compact grid over the slots of its own kind.
     int int_slot_count;
     int int_slots[8];
+    // The grids run over the limb slots [slot_first, slot_first + slot_count) only (slot_count 0: all rc slots);
+    // int_slots then lists only the integer slots of that range.
+    int slot_first, slot_count;
+    // Optional mod-down tail (method I, one special prime P; the counterpart of NttEpilogue): the accumulated limb acc
+    // of part p, slot k (modulus q_k) is not stored; instead
+    //     out = (acc - T) * inv[q_k] + ct   (ct for parts below ct_parts only; 0: every part)
+    // where T is the transform at q_k of the inverse-transformed P limb, read as a column-pass output (the row
+    // stages still to do) from T [item][2][rc][N].  With galois_inv != 0 the result is scattered as in
+    // NttEpilogue.  ct / out: [item][2][limbs][N]; out may alias ct unless galois_inv != 0.
+    struct Tail {
+        int on;
+        const u64* T;
+        u64 T_item_stride;
+        const u64* ct;
+        u64 ct_item_stride;
+        int ct_parts;
+        unsigned galois_inv;
+        u64* out;
+        u64 out_item_stride;
+        const u64* inv;
+        int limbs;
+    } tail;
 };
 hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st);
 

@@ -62,6 +62,14 @@ static bool use_fused_row_mac(const Context& c, int rc, int batch)
     if (c.fused_row_mac >= 0) return c.fused_row_mac != 0;
     return (long) batch * rc * (long) (c.n >> 12) >= fused_row_mac_need(c);
 }
+// Method I on the large-launch fused path: the mod-down runs as the tail of the fused row pass + inner product
+// (Context::moddown_in_mac, see ckks_keyswitch_core).  `key` null: the accumulator comes from elsewhere (hoisted
+// rotations).
+static bool use_moddown_in_mac(const Context& c, const u64* key, int l, int rc, int batch)
+{
+    return c.moddown_in_mac && c.fused_moddown && key && c.P_size == 1 && use_fused_row_mac(c, rc, batch) &&
+           !fused_digit_splits(c, rc, l, batch) && (long) 2 * l * batch <= 65535;
+}
 
 // The target slots of a decomposing launch over the Q' chain whose moduli run on the integer butterflies
 // (NttArgs::int_slots).  `order`: host copy of the launch's mod_order (nullptr: slot k is modulus k).
@@ -88,15 +96,19 @@ static void fill_int_slots(const Context& c, NttArgs& a, const u64* order)
 // taken from there instead of being transformed.
 // `which`: 1 = column pass only, 2 = row pass + inner product only, 3 = both (the measurement seam of
 // hegpu_probe_ckks_relinearize; the unfused path ignores it)
+// Fused path only: the row pass + inner product covers the limb slots [slot_first, slot_first + slot_count) (0: all),
+// and `tail` (if not null) is the mod-down it ends with (KsMacArgs::tail, item pointers of the whole batch).
 static hipError_t keyswitch_ntt_mac(const Context& c, NttArgs a, const u64* key, u64* acc, u64 acc_stride,
                                     int digits, int rc, int split, int level, const u64* ident, u64 ident_stride,
-                                    int batch, hipStream_t st, int which = 3)
+                                    int batch, hipStream_t st, int which = 3, int slot_first = 0, int slot_count = 0,
+                                    const KsMacArgs::Tail* tail = nullptr)
 {
     const int ppi = digits * rc;
     const int skip_identity = ident ? 1 : 0;
     a.skip_identity = skip_identity;
     const int splits = fused_digit_splits(c, rc, digits, batch);
     if (!splits && !use_fused_row_mac(c, rc, batch)) {
+        if (slot_count || tail) return hipErrorInvalidValue;
         // identity digits (digit d at modulus d: the transform gives back the NTT-domain limb): copied instead of
         // transformed -- unless this path was chosen for a small launch, where one kernel less is worth more than
         // one transform in ten (same residues either way)
@@ -127,6 +139,21 @@ static hipError_t keyswitch_ntt_mac(const Context& c, NttArgs a, const u64* key,
         k.no_int = !a.plan_has_int || a.int_slot_count < 0;
         k.int_slot_count = a.int_slot_count > 0 ? a.int_slot_count : 0;
         for (int q = 0; q < 8; q++) k.int_slots[q] = a.int_slots[q];
+        k.slot_first = slot_first; k.slot_count = slot_count;
+        if (slot_count && a.int_slot_count > 0) { // the integer slots of the range
+            int cnt = 0;
+            for (int q = 0; q < a.int_slot_count; q++)
+                if (a.int_slots[q] >= slot_first && a.int_slots[q] < slot_first + slot_count) k.int_slots[cnt++] = a.int_slots[q];
+            k.int_slot_count = cnt;
+            k.no_int = cnt == 0;
+            k.no_fp = k.no_fp || cnt == slot_count;
+        }
+        if (tail) {
+            k.tail = *tail;
+            k.tail.T += (u64) b0 * tail->T_item_stride;
+            if (tail->ct) k.tail.ct += (u64) b0 * tail->ct_item_stride;
+            k.tail.out += (u64) b0 * tail->out_item_stride;
+        }
         TRY(ks_row_mac_launch(k, nb, st));
         if (splits > 1)
             TRY(rns_sum_partials(ca.out, a.out_item_stride, k.out, acc_stride, c.plan_qp.mods, a.mod_order, c.n_power,
@@ -214,7 +241,16 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     a = dgt;
     // forward NTT of the digits + inner product with the key      (:956-988)
     const int which = ((phases & RELIN_PHASE_COLUMN) ? 1 : 0) | ((phases & RELIN_PHASE_ROW_MAC) ? 2 : 0);
-    if (which) TRY(keyswitch_ntt_mac(c, a, key, temp2, per, l, rc, l, depth, src, src_stride, batch, st, which));
+    // Mod-down inside the fused kernels: the inner product of the P slot first, its INTT, the mod-down's column pass
+    // (T, the P limb at every q_j, into the Q slots of temp2, which are never written as accumulators), and only then
+    // the inner product of the Q slots, whose workgroups finish T's row stages and apply the mod-down to their sums
+    // while they are still in registers: the 2 l accumulator limbs are neither stored nor read back, and the mod-down
+    // row pass has no launch of its own.  ROW_MAC covers both inner-product launches.
+    const bool in_mac = use_moddown_in_mac(c, key, l, rc, batch);
+    if (which) // with in_mac: the P slot (slot l) only
+        TRY(keyswitch_ntt_mac(c, a, key, temp2, per, l, rc, l, depth, src, src_stride, batch, st, which, in_mac ? l : 0,
+                              in_mac ? 1 : 0));
+    const NttArgs dgt_args = a;
     // INTT of the two P-limb polynomials only                        (:996)
     a = c.ntt_args(0);
     a.in = temp2; a.out = temp2; a.mod_count = 1; a.mod_offset = Q; a.polys_per_item = 2;
@@ -232,6 +268,25 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     if (phases & RELIN_PHASE_INTT_P) {
         if (fuse_inv_p) TRY(ntt_launch_inv_rows(a, 2 * batch, st));
         else TRY(ntt_launch(a, 2 * batch, true, st));
+    }
+    if (in_mac) {
+        if (phases & RELIN_PHASE_MODDOWN) {
+            a = md;
+            a.out = temp2; a.decomp_out_mul = l + 1; // T of part p, limb j: slot j of part p in temp2 [2][l+1][N]
+            a.half = c.h64("half")[0]; a.half_mod = c.d64("half_mod");
+            a.src_inv = fuse_inv_p ? 1 : 0;
+            TRY(ntt_launch_fwd_col(a, 2 * l * batch, st));
+        }
+        if (!(phases & RELIN_PHASE_ROW_MAC)) return hipSuccess;
+        KsMacArgs::Tail t{};
+        t.on = 1;
+        t.T = temp2; t.T_item_stride = per;
+        t.ct = add; t.ct_item_stride = add_stride; t.ct_parts = add_parts;
+        t.out = outp; t.out_item_stride = out_stride;
+        t.inv = c.d64("last_q_modinv");
+        t.limbs = l;
+        t.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
+        return keyswitch_ntt_mac(c, dgt_args, key, temp2, per, l, rc, l, depth, src, src_stride, batch, st, 2, 0, l, &t);
     }
     if (!(phases & RELIN_PHASE_MODDOWN)) return hipSuccess;
     // stage one: P limb (+half) reduced into every q_j               (:1003)
