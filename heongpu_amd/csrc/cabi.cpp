@@ -1110,6 +1110,7 @@ int hegpu_bfv_encode(hegpu_context* ctx, const int64_t* message, int message_siz
         return fail(HEGPU_E_LOGIC, "batching needs a prime plain modulus with 2N | t - 1");
     if (message_size < 0 || message_size > (int) ctx->c.n)
         return fail(HEGPU_E_INVALID, "Message size can not be higher than the slot count."); // bfv/encoder.cuh:60
+    if (!message && message_size > 0) return fail(HEGPU_E_INVALID, "message is null");
     return hip_ret(op_bfv_encode(ctx->c, (const long long*) message, message_size, (u64*) plain,
                                  (hipStream_t) stream),
                    "hegpu_bfv_encode");
@@ -1139,6 +1140,7 @@ static int ckks_encode_any(hegpu_context* ctx, int mode, const double* message, 
     } else if (mode != 3 && (message_size < 0 || message_size > (int) (ctx->c.n >> 1))) {
         return fail(HEGPU_E_INVALID, "Vector size can not be higher than slot count!");            // :74
     }
+    if (mode != 3 && !message && message_size > 0) return fail(HEGPU_E_INVALID, "message is null");
     if (!(scale > 0.0)) return fail(HEGPU_E_INVALID, "Scale out of bounds");                       // :63
     if (mode < 2 && (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_CKKS_ENCODE, 0, 1)))
         return fail(HEGPU_E_INVALID, "workspace too small");

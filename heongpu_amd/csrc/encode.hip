@@ -33,14 +33,15 @@ __device__ __forceinline__ cplx csub_(cplx a, cplx b) { return {a.re - b.re, a.i
 #define EN_FFT_THREADS 1024
 
 struct EnIo {
-    const double* real_in; // encode: the message (nullptr: the transform reads `data`)
+    int from_message;      // encode: the load reads the message (in_size entries, zeros beyond), not `data`
+    const double* real_in; // may be nullptr when in_size == 0
     int in_size, in_complex;
     double* real_out;      // decode: the message (nullptr: the transform writes `data`)
     int out_complex;
 };
 __device__ __forceinline__ cplx en_load(const cplx* __restrict__ v, const EnIo& io, int e)
 {
-    if (!io.real_in) return v[e];
+    if (!io.from_message) return v[e];
     if (io.in_complex) return e < io.in_size ? reinterpret_cast<const cplx*>(io.real_in)[e] : cplx{0.0, 0.0};
     return {e < io.in_size ? io.real_in[e] : 0.0, 0.0};
 }
@@ -202,8 +203,8 @@ hipError_t en_special_fft(void* data, const void* roots, int log_slots, bool inv
                                                      (int) (sizeof(cplx) << EN_LOG_CHUNK));
     (void) a0;
     (void) a1;
-    const EnIo plain{nullptr, 0, 0, nullptr, 0};
-    const EnIo in_io{real_in, in_size, in_complex, nullptr, 0}, out_io{nullptr, 0, 0, real_out, out_complex};
+    const EnIo plain{0, nullptr, 0, 0, nullptr, 0};
+    const EnIo in_io{1, real_in, in_size, in_complex, nullptr, 0}, out_io{0, nullptr, 0, 0, real_out, out_complex};
     cplx* v = (cplx*) data;
     const cplx* r = (const cplx*) roots;
     const int outer_grid = ((1 << log_slots) >> (rem == 2 ? 2 : 1)) / EN_THREADS;
@@ -255,23 +256,24 @@ hipError_t en_conversion(u64* plain, const void* msg, const Mod* mods, int limbs
     return hipGetLastError();
 }
 
-// encode_kernel_coeff_ckks_conversion (encoding.cu:106-137): coefficient idx = round(message[idx] * scale);
-// encode_kernel_double_ckks_conversion (:43-77): every entry = round(value) (message == nullptr)
+// encode_kernel_coeff_ckks_conversion (encoding.cu:106-137): coefficient idx = round(message[idx] * scale), zero beyond
+// `size` (message may be nullptr when size == 0); encode_kernel_double_ckks_conversion (:43-77): every entry =
+// round(value) (scalar != 0, message unused)
 __global__ __launch_bounds__(EN_THREADS) void k_en_coeff_conversion(u64* __restrict__ plain,
                                                                     const double* __restrict__ message, int size,
-                                                                    double scale_or_value, const Mod* __restrict__ mods,
-                                                                    int limbs, int n_power)
+                                                                    int scalar, double scale_or_value,
+                                                                    const Mod* __restrict__ mods, int limbs, int n_power)
 {
     const int idx = blockIdx.x * EN_THREADS + threadIdx.x;
-    const double v = message ? (idx < size ? message[idx] : 0.0) * scale_or_value : scale_or_value;
+    const double v = scalar ? scale_or_value : (idx < size ? message[idx] : 0.0) * scale_or_value;
     en_store_rns(plain, (u64) idx, v, mods, limbs, n_power);
 }
 
-hipError_t en_coeff_conversion(u64* plain, const double* message, int size, double scale_or_value, const Mod* mods,
-                               int limbs, int n_power, hipStream_t st)
+hipError_t en_coeff_conversion(u64* plain, const double* message, int size, bool scalar, double scale_or_value,
+                               const Mod* mods, int limbs, int n_power, hipStream_t st)
 {
     hipLaunchKernelGGL(k_en_coeff_conversion, dim3((1u << n_power) / EN_THREADS), dim3(EN_THREADS), 0, st, plain, message,
-                       size, scale_or_value, mods, limbs, n_power);
+                       size, scalar ? 1 : 0, scale_or_value, mods, limbs, n_power);
     return hipGetLastError();
 }
 

@@ -75,9 +75,10 @@ hipError_t kg_bfv_decode_gather(u64* message, const u64* in, const int* location
 hipError_t en_special_fft(void* data, const void* roots, int log_slots, bool inverse, double fix, hipStream_t st,
                           const double* real_in = nullptr, int in_size = 0, int in_complex = 0, double* real_out = nullptr,
                           int out_complex = 0);
-// message == nullptr: the constant round(scale_or_value) everywhere
-hipError_t en_coeff_conversion(u64* plain, const double* message, int size, double scale_or_value, const Mod* mods,
-                               int limbs, int n_power, hipStream_t st);
+// scalar: the constant round(scale_or_value) everywhere (message unused); otherwise round(message[i] * scale_or_value)
+// for i < size and zero beyond (message may be nullptr when size == 0)
+hipError_t en_coeff_conversion(u64* plain, const double* message, int size, bool scalar, double scale_or_value,
+                               const Mod* mods, int limbs, int n_power, hipStream_t st);
 hipError_t en_coeff_compose(double* message, const u64* plain, const Mod* mods, const u64* Mi_inv, const u64* Mi,
                             const u64* upper_half, const u64* M, int l, double scale, int n_power, hipStream_t st);
 hipError_t en_conversion(u64* plain, const void* msg, const Mod* mods, int limbs, const int* reverse_order, int n_power,

@@ -1004,12 +1004,12 @@ hipError_t op_ckks_encode(const Context& c, int mode, const double* message, int
 {
     const int slots = (int) (c.n >> 1), Q = c.Q_size;
     if (mode == 3)                                                                         // encoder.cu:412-446
-        return en_coeff_conversion(plain, nullptr, 0, scalar * scale, c.plan_qp.mods, Q, c.n_power, st);
+        return en_coeff_conversion(plain, nullptr, 0, true, scalar * scale, c.plan_qp.mods, Q, c.n_power, st);
     NttArgs a = c.ntt_args(0);
     a.in = plain; a.out = plain; a.mod_count = Q;
     if (mode == 2) {                                                                       // :222-261
         if (message_size < 0 || message_size > (int) c.n) return hipErrorInvalidValue;
-        TRY(en_coeff_conversion(plain, message, message_size, scale, c.plan_qp.mods, Q, c.n_power, st));
+        TRY(en_coeff_conversion(plain, message, message_size, false, scale, c.plan_qp.mods, Q, c.n_power, st));
         return ntt_launch(a, Q, false, st);
     }
     if (message_size < 0 || message_size > slots) return hipErrorInvalidValue;

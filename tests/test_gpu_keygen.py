@@ -151,7 +151,7 @@ def test_bfv_encrypt_decrypt_bit_exact_and_pipeline(hg, oracle, torch):
     assert np.array_equal(hg.to_host(c.bfv_decrypt(rot, sk)), want), "decrypt(rotate(c1)) = sigma_g(m1)"
 
 
-@pytest.mark.parametrize("n,t", [(4096, 1032193), (8192, 65537)])
+@pytest.mark.parametrize("n,t", [(4096, 1032193), (8192, 65537), (16384, 786433), (32768, 786433), (65536, 786433)])
 def test_bfv_batch_encoder_bit_exact(hg, oracle, torch, n, t):
     """encode / decode vs the oracle, decode(encode) = identity, short and negative messages,
     and the plain-modulus table set through hegpu_ntt."""
@@ -160,7 +160,8 @@ def test_bfv_batch_encoder_bit_exact(hg, oracle, torch, n, t):
     o = oracle.OracleContext(oracle.BFV, c.n_power, primes, c.Q_size, c.P_size, t)
     c.upload()
     g = np.random.default_rng(3)
-    for msg in (g.integers(0, t, n), g.integers(-t // 2, t // 2, n), np.array([-1, 5, -7, 3]), np.zeros(1)):
+    for msg in (g.integers(0, t, n), g.integers(-t // 2, t // 2, n), np.array([-1, 5, -7, 3]), np.zeros(1), np.array([-2]),
+                np.zeros(0)):
         msg = msg.astype(np.int64)
         plain = c.bfv_encode(torch.from_numpy(msg).cuda())
         want = o.bfv_encode(msg)
