@@ -14,6 +14,7 @@
 #include <vector>
 #include <cstring>
 #include <sys/random.h>
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -107,7 +108,7 @@ static void check_degree(int n, int& n_power)
     n_power = 31 - __builtin_clz((unsigned) n);
 }
 
-static int finish_create(hegpu_context* h, int scheme, int n_power, uint64_t plain_modulus, int q_count,
+static int finish_create(std::unique_ptr<hegpu_context> h, int scheme, int n_power, uint64_t plain_modulus, int q_count,
                          int p_count, hegpu_context** out)
 {
     Context& c = h->c;
@@ -119,7 +120,7 @@ static int finish_create(hegpu_context* h, int scheme, int n_power, uint64_t pla
     if (scheme == SCHEME_BFV && plain_modulus < 2) throw std::logic_error("plain modulus is not specified");
     c.build_host();
     c.seed_options_from_env(); // defaults only; hegpu_context_set_option is the interface
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
@@ -145,14 +146,9 @@ int hegpu_context_create(int scheme, int n, const int* qb, int qn, const int* pb
         } else if (sec_level != HEGPU_SEC_NONE) {
             throw std::runtime_error("Invalid security level");
         }
-        hegpu_context* h = new hegpu_context();
-        try {
-            h->c.primes = host::find_primes((u64) n, bits);
-            return finish_create(h, scheme, n_power, plain_modulus, qn, pn, out);
-        } catch (...) {
-            delete h;
-            throw;
-        }
+        std::unique_ptr<hegpu_context> h(new hegpu_context());
+        h->c.primes = host::find_primes((u64) n, bits);
+        return finish_create(std::move(h), scheme, n_power, plain_modulus, qn, pn, out);
     });
 }
 
@@ -169,14 +165,9 @@ int hegpu_context_create_default(int scheme, int n, int p_count, uint64_t plain_
             throw std::runtime_error("Invalid security level"); // bfv/context.cu:285-360: no default chain without a level
         std::vector<u64> chain = host::default_chain((u64) n, sec_level);
         if (chain.empty() || (int) chain.size() <= p_count) throw std::logic_error("no default chain");
-        hegpu_context* h = new hegpu_context();
-        try {
-            h->c.primes = chain;
-            return finish_create(h, scheme, n_power, plain_modulus, (int) chain.size() - p_count, p_count, out);
-        } catch (...) {
-            delete h;
-            throw;
-        }
+        std::unique_ptr<hegpu_context> h(new hegpu_context());
+        h->c.primes = chain;
+        return finish_create(std::move(h), scheme, n_power, plain_modulus, (int) chain.size() - p_count, p_count, out);
     });
 }
 
@@ -193,14 +184,9 @@ int hegpu_context_create_from_primes(int scheme, int n, const uint64_t* primes, 
             if (primes[i] >> 61) throw std::logic_error("invalid modulus bit size");
             if ((primes[i] - 1) % (2 * (u64) n)) throw std::logic_error("no sufficient root unity");
         }
-        hegpu_context* h = new hegpu_context();
-        try {
-            h->c.primes.assign(primes, primes + qn + pn);
-            return finish_create(h, scheme, n_power, plain_modulus, qn, pn, out);
-        } catch (...) {
-            delete h;
-            throw;
-        }
+        std::unique_ptr<hegpu_context> h(new hegpu_context());
+        h->c.primes.assign(primes, primes + qn + pn);
+        return finish_create(std::move(h), scheme, n_power, plain_modulus, qn, pn, out);
     });
 }
 
@@ -255,14 +241,19 @@ int hegpu_context_get_option(const hegpu_context* ctx, const char* name, int* va
     return 0;
 }
 
+// the number of HIP devices, at least one -- or the error every device entry point ends with on a box without one
+static int need_device(int* cnt)
+{
+    if (hipGetDeviceCount(cnt) == hipSuccess && *cnt > 0) return 0;
+    (void) hipGetLastError();
+    return fail(HEGPU_E_NODEVICE, "no HIP device available: the HIP backend cannot run (no CPU fallback)");
+}
+
 int hegpu_context_upload(hegpu_context* ctx)
 {
     if (!ctx) return fail(HEGPU_E_INVALID, "null context");
     int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) {
-        (void) hipGetLastError();
-        return fail(HEGPU_E_NODEVICE, "no HIP device available: the HIP backend cannot run (no CPU fallback)");
-    }
+    if (int r = need_device(&cnt)) return r;
     return hip_ret(ctx->c.upload(), "context upload");
 }
 
@@ -270,10 +261,7 @@ int hegpu_context_upload_device(hegpu_context* ctx, int device)
 {
     if (!ctx) return fail(HEGPU_E_INVALID, "null context");
     int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) {
-        (void) hipGetLastError();
-        return fail(HEGPU_E_NODEVICE, "no HIP device available: the HIP backend cannot run (no CPU fallback)");
-    }
+    if (int r = need_device(&cnt)) return r;
     if (device < 0 || device >= cnt) return fail(HEGPU_E_INVALID, "no such device");
     if (ctx->c.uploaded)
         return ctx->c.device == device ? 0 : fail(HEGPU_E_LOGIC, "the context is already uploaded to another device");
@@ -287,20 +275,10 @@ int hegpu_context_clone(const hegpu_context* src, hegpu_context** out)
 {
     return guarded([&]() -> int {
         if (!src || !out) throw std::invalid_argument("null argument");
-        hegpu_context* h = new hegpu_context();
-        Context& c = h->c;
-        const Context& s = src->c;
+        std::unique_ptr<hegpu_context> h(new hegpu_context());
         // host state and options only: the clone owns its own device tables once uploaded
-        c.scheme = s.scheme; c.n_power = s.n_power; c.n = s.n;
-        c.Q_size = s.Q_size; c.P_size = s.P_size; c.Qp_size = s.Qp_size; c.bsk_size = s.bsk_size;
-        c.plain_modulus = s.plain_modulus; c.primes = s.primes; c.host = s.host;
-        c.m2_levels = s.m2_levels; c.m2_width = s.m2_width;
-        c.fused_row_mac = s.fused_row_mac; c.fused_moddown = s.fused_moddown; c.col_multi = s.col_multi;
-        c.single_pass = s.single_pass; c.ntt_galois = s.ntt_galois; c.galois_scatter = s.galois_scatter;
-        c.digit_split = s.digit_split; c.copy_along = s.copy_along; c.fuse_inverse = s.fuse_inverse;
-        c.fp_ntt = s.fp_ntt; c.behz_split = s.behz_split; c.fused_tensor = s.fused_tensor;
-        c.moddown_in_mac = s.moddown_in_mac;
-        *out = h;
+        static_cast<ContextHost&>(h->c) = src->c;
+        *out = h.release();
         return 0;
     });
 }
@@ -345,10 +323,7 @@ int hegpu_broadcast_bytes(const int* devices, int n, void* const* bufs, size_t b
     if (path_out) *path_out = 0;
     if (!devices || !bufs || n < 1) return fail(HEGPU_E_INVALID, "null argument");
     int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) {
-        (void) hipGetLastError();
-        return fail(HEGPU_E_NODEVICE, "no HIP device available: the HIP backend cannot run (no CPU fallback)");
-    }
+    if (int r = need_device(&cnt)) return r;
     for (int i = 0; i < n; i++) {
         if (!bufs[i]) return fail(HEGPU_E_INVALID, "null buffer");
         if (devices[i] < 0 || devices[i] >= cnt) return fail(HEGPU_E_INVALID, "no such device");
@@ -609,9 +584,9 @@ int hegpu_base_conversion_DtoQtilde(hegpu_context* ctx, const uint64_t* in, uint
     if (depth < 0 || depth >= (int) c.m2_levels.size()) return fail(HEGPU_E_INVALID, "invalid depth");
     const Context::M2Level& L = c.m2_levels[depth];
     return hip_ret(rns_base_conversion_DtoQtilde((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                                 c.d64("m2_matrix_mg") + L.off_matrix, c.d64("m2_Mi_inv") + L.off_mi,
-                                                 c.d64("m2_negprod_mg") + L.off_prod, c.d32("m2_I_j") + L.off_digits,
-                                                 c.d32("m2_I_location") + L.off_digits, c.n_power, L.d, L.rc,
+                                                 c.tab.m2_matrix_mg + L.off_matrix, c.tab.m2_Mi_inv + L.off_mi,
+                                                 c.tab.m2_negprod_mg + L.off_prod, c.tab.m2_I_j + L.off_digits,
+                                                 c.tab.m2_I_location + L.off_digits, c.n_power, L.d, L.rc,
                                                  c.Q_size - depth, depth, c.m2_width, batch, (hipStream_t) stream),
                    "hegpu_base_conversion_DtoQtilde");
 }
@@ -624,8 +599,8 @@ int hegpu_divide_round_lastq(hegpu_context* ctx, const uint64_t* in, uint64_t in
     const Context& c = ctx->c;
     if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "divide_round_lastq needs a single special prime (method I)");
     return hip_ret(rns_divide_round_lastq((const u64*) in, in_stride, (const u64*) ct, ct_stride, (u64*) out,
-                                          out_stride, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                          c.d64("last_q_modinv"), c.n_power, c.Q_size, switchkey, batch,
+                                          out_stride, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                                          c.tab.last_q_modinv, c.n_power, c.Q_size, switchkey, batch,
                                           (hipStream_t) stream),
                    "hegpu_divide_round_lastq");
 }
@@ -639,8 +614,8 @@ int hegpu_divide_round_lastq_permute(hegpu_context* ctx, const uint64_t* in, uin
     const Context& c = ctx->c;
     if (c.scheme == SCHEME_BFV && depth != 0) return fail(HEGPU_E_INVALID, "BFV ciphertexts have no depth");
     return hip_ret(rns_moddown_permute((const u64*) in, in_stride, (const u64*) in2, in2_stride, (u64*) out,
-                                       out_stride, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                       c.d64("last_q_modinv"), galois_elt, c.n_power, c.Qp_size - depth,
+                                       out_stride, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                                       c.tab.last_q_modinv, galois_elt, c.n_power, c.Qp_size - depth,
                                        c.Q_size - depth, c.Qp_size, c.Q_size, c.P_size, batch,
                                        (hipStream_t) stream),
                    "hegpu_divide_round_lastq_permute");
@@ -663,13 +638,13 @@ int hegpu_divide_round_lastq_leveled_stage_one(hegpu_context* ctx, const uint64_
     SEAM_CKKS(ctx, depth, batch, rescale ? 2 : 1);
     if (rescale)
         return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                             c.d64("rescaled_half") + depth,
-                                             c.d64("rescaled_half_mod") + triangle_offset(c.Q_size - 1, depth), c.n_power,
+                                             c.tab.rescaled_half + depth,
+                                             c.tab.rescaled_half_mod + triangle_offset(c.Q_size - 1, depth), c.n_power,
                                              l - 1, l - 1, batch, (hipStream_t) stream),
                        "hegpu_divide_round_lastq_leveled_stage_one");
     if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
     return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.d64("half"), c.d64("half_mod"), c.n_power, c.Q_size, l, batch,
+                                         c.tab.half, c.tab.half_mod, c.n_power, c.Q_size, l, batch,
                                          (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_one");
 }
@@ -684,7 +659,7 @@ int hegpu_divide_round_lastq_leveled_stage_two(hegpu_context* ctx, const uint64_
     if (!ct) return fail(HEGPU_E_INVALID, "ct must not be NULL");
     return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, l + 1,
                                          (const u64*) ct, ct_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.d64("last_q_modinv"), c.n_power, l, switchkey ? 2 : 1, batch,
+                                         c.tab.last_q_modinv, c.n_power, l, switchkey ? 2 : 1, batch,
                                          (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_two");
 }
@@ -705,7 +680,7 @@ int hegpu_divide_round_lastq_rescale(hegpu_context* ctx, const uint64_t* in_last
     SEAM_CKKS(ctx, depth, batch, 2);
     return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, l, nullptr, 0,
                                          (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.d64("rescaled_last_q_modinv") + triangle_offset(c.Q_size - 1, depth), c.n_power,
+                                         c.tab.rescaled_last_q_modinv + triangle_offset(c.Q_size - 1, depth), c.n_power,
                                          l - 1, 0, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_rescale");
 }
@@ -723,7 +698,7 @@ int hegpu_divide_round_lastq_extended(hegpu_context* ctx, const uint64_t* in, ui
     if (batch < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");
     if (batch == 0) return 0;
     return hip_ret(rns_moddown_extended((const u64*) in, in_stride, (const u64*) ct, ct_stride, (u64*) out, out_stride,
-                                        c.plan_qp.mods, c.d64("half"), c.d64("half_mod"), c.d64("last_q_modinv"),
+                                        c.plan_qp.mods, c.tab.half, c.tab.half_mod, c.tab.last_q_modinv,
                                         c.n_power, c.Qp_size - depth, c.Q_size - depth, c.Qp_size, c.Q_size, c.P_size,
                                         mode, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_extended");
@@ -1241,7 +1216,7 @@ int hegpu_ckks_gaussian_integer_op(hegpu_context* ctx, int op, const uint64_t* c
     for (double v : {re, im}) // any finite double, as the reference's NTL conversion (ckks/operator.cu:583-617)
         if (!std::isfinite(v)) return fail(HEGPU_E_INVALID, "constant is not a finite number");
     return guarded([&]() -> int {
-        return hip_ret(kg_ckks_gaussian((const u64*) ct, re, im, (u64*) out, ctx->c.d64("psi_half"), ctx->c.plan_qp.mods,
+        return hip_ret(kg_ckks_gaussian((const u64*) ct, re, im, (u64*) out, ctx->c.tab.psi_half, ctx->c.plan_qp.mods,
                                         ctx->c.n_power, limbs, parts, op, (hipStream_t) stream),
                        "hegpu_ckks_gaussian_integer_op");
     });
@@ -1254,7 +1229,7 @@ int hegpu_ckks_mult_i(hegpu_context* ctx, const uint64_t* ct, uint64_t* out, int
     if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
     if (limbs <= 0 || limbs > ctx->c.Q_size || parts < 2 || parts > 3) return fail(HEGPU_E_INVALID, "bad ciphertext shape");
     return guarded([&]() -> int {
-        return hip_ret(kg_ckks_mult_i((const u64*) ct, (u64*) out, ctx->c.d64("psi_half"), ctx->c.plan_qp.mods,
+        return hip_ret(kg_ckks_mult_i((const u64*) ct, (u64*) out, ctx->c.tab.psi_half, ctx->c.plan_qp.mods,
                                       ctx->c.n_power, limbs, parts, divide, (hipStream_t) stream),
                        "hegpu_ckks_mult_i");
     });
@@ -1268,8 +1243,8 @@ int hegpu_bfv_plain_addsub(hegpu_context* ctx, const uint64_t* ct, const uint64_
     const Context& c = ctx->c;
     return guarded([&]() -> int {
         return hip_ret(kg_bfv_plain_addsub((const u64*) ct, (const u64*) plain, (u64*) out, c.plan_qp.mods,
-                                           c.d64("coeff_div_plain_modulus"), c.h64("Q_mod_t")[0],
-                                           c.h64("upper_threshold")[0], c.plain_modulus, c.n_power, c.Q_size, sub,
+                                           c.tab.coeff_div_plain_modulus, c.hv.Q_mod_t,
+                                           c.hv.upper_threshold, c.plain_modulus, c.n_power, c.Q_size, sub,
                                            (hipStream_t) stream),
                        "hegpu_bfv_plain_addsub");
     });
@@ -1454,10 +1429,7 @@ static int tfhe_need(hegpu_tfhe_context* ctx)
     if (!ctx) return fail(HEGPU_E_INVALID, "null context");
     if (ctx->uploaded) return 0; // (the bad-key flag is NOT looked at here: hegpu_tfhe_status / the bootstrapping entries own it)
     int cnt = 0;
-    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0) {
-        (void) hipGetLastError();
-        return fail(HEGPU_E_NODEVICE, "no HIP device available: the HIP backend cannot run (no CPU fallback)");
-    }
+    if (int r = need_device(&cnt)) return r;
     hipError_t e;
     if ((e = hipMalloc((void**) &ctx->dtw, 1024 * sizeof(ulonglong2))) != hipSuccess) return hip_ret(e, "tfhe upload");
     if ((e = hipMalloc((void**) &ctx->ditw, 1024 * sizeof(ulonglong2))) != hipSuccess) return hip_ret(e, "tfhe upload");

@@ -26,6 +26,7 @@ void Context::build_host()
     const int Q = Q_size, P = P_size, Qp = Qp_size;
     if ((int) primes.size() != Qp) throw std::logic_error("prime chain size mismatch");
     host.clear();
+    hv = HostVals();
     host["modulus"] = primes;
 
     vec psi, ninv, fwd, inv;
@@ -60,6 +61,7 @@ void Context::build_host()
     }
     host["last_q_modinv"] = lqm;
     host["half"] = half;
+    hv.half = half[0];
     host["half_mod"] = half_mod;
     host["factor"] = factor;
 
@@ -78,6 +80,7 @@ void Context::build_host()
         host["rescaled_last_q_modinv"] = r_inv;
         host["rescaled_half_mod"] = r_half_mod;
         host["rescaled_half"] = r_half;
+        hv.rescaled_half = r_half;
         // ---- decoding: CRT composition tables per level (ckks/context.cu:370-421, util.cu:772-888):
         // for l = Q - depth limbs, Mi[i] = prod_{j != i} q_j and M = prod q_j as l little-endian
         // 64-bit words, Mi_inv[i] = (Mi[i] mod q_i)^-1, upper_half_threshold = (M + 1) >> 1
@@ -172,6 +175,7 @@ void Context::build_host()
             iloc.push_back(2 * c - 1);
         }
         host["new_prime_locations"] = ploc;
+        hv.new_prime_locations = ploc;
         host["new_input_locations"] = iloc;
     }
 
@@ -235,8 +239,8 @@ void Context::build_host()
                 int loc = 0;
                 for (int i = 0; i < P; i++) {
                     G[(size_t) y * P + i] = g;
-                    c = (c + mul_mod(host["half_mod"][loc + y], g, q)) % q;
-                    w = mul_mod(w, host["last_q_modinv"][loc + y], q);
+                    c = (c + mul_mod(half_mod[loc + y], g, q)) % q;
+                    w = mul_mod(w, lqm[loc + y], q);
                     g = mul_mod(g, primes[Qp - 1 - i] % q, q);
                     loc += (Qp - 1) - i;
                 }
@@ -273,6 +277,7 @@ void Context::build_host()
         const u64 msk = B[bsk - 1];
         host["base_Bsk"] = B;
         host["gamma"] = vec{gamma};
+        hv.gamma = gamma;
         vec Bpsi;
         for (u64 b : B) Bpsi.push_back(host::minimal_primitive_root(2 * n, b));
         host["base_Bsk_psi"] = Bpsi;
@@ -333,13 +338,15 @@ void Context::build_host()
         host["inv_punctured_prod_mod_base_array"] = inv_punct;
         host["base_change_matrix_m_tilde"] = m_mt;
         host["inv_prod_q_mod_m_tilde"] = vec{inv_prod_q_mt};
+        hv.inv_prod_q_mod_m_tilde = inv_prod_q_mt;
         host["inv_m_tilde_mod_Bsk"] = inv_mt_B;
         host["prod_q_mod_Bsk"] = prod_q_B;
         host["inv_prod_q_mod_Bsk"] = inv_prod_q_B;
         host["base_change_matrix_q"] = m_B_q;
         host["base_change_matrix_msk"] = m_msk;
         host["inv_punctured_prod_mod_B_array"] = inv_punct_B;
-        host["inv_prod_B_mod_m_sk"] = vec{inv_mod_prime(prod_B_msk, msk)};
+        hv.inv_prod_B_mod_m_sk = inv_mod_prime(prod_B_msk, msk);
+        host["inv_prod_B_mod_m_sk"] = vec{hv.inv_prod_B_mod_m_sk};
         host["prod_B_mod_q"] = prod_B_q;
         // Products of constants that the reference multiplies in one after the other
         // (multiplication.cu:37-41, 160-164, 196-205): one Barrett product per coefficient instead of two.
@@ -460,8 +467,10 @@ void Context::build_host()
         {
             u64 Q_mod_t = 1;
             for (int i = 0; i < Q; i++) Q_mod_t = mul_mod(Q_mod_t, primes[i] % t, t);
-            host["Q_mod_t"] = vec{Q_mod_t};
-            host["upper_threshold"] = vec{(t + 1) >> 1};
+            hv.Q_mod_t = Q_mod_t;
+            hv.upper_threshold = (t + 1) >> 1;
+            host["Q_mod_t"] = vec{hv.Q_mod_t};
+            host["upper_threshold"] = vec{hv.upper_threshold};
             vec inc; // plain_upper_half_increment (bfv/context.cu:503-508)
             for (int i = 0; i < Q; i++) inc.push_back(primes[i] - t);
             host["upper_halfincrement"] = inc;
@@ -512,9 +521,12 @@ void Context::build_host()
                 mt_ = mul_mod(mt_, inv_mod_prime(primes[i] % t, t), t);
                 mg_ = mul_mod(mg_, inv_mod_prime(primes[i] % gamma, gamma), gamma);
             }
-            host["mulq_inv_t"] = vec{t - mt_};
-            host["mulq_inv_gamma"] = vec{gamma - mg_};
-            host["inv_gamma"] = vec{inv_mod_prime(gamma % t, t)};
+            hv.mulq_inv_t = t - mt_;
+            hv.mulq_inv_gamma = gamma - mg_;
+            hv.inv_gamma = inv_mod_prime(gamma % t, t);
+            host["mulq_inv_t"] = vec{hv.mulq_inv_t};
+            host["mulq_inv_gamma"] = vec{hv.mulq_inv_gamma};
+            host["inv_gamma"] = vec{hv.inv_gamma};
         }
     }
 }
@@ -643,70 +655,54 @@ hipError_t Context::upload()
     if ((e = build_plan(plan_qp, host["modulus"], host["ntt_table"], host["intt_table"], host["n_inverse"],
                         n_power, fp_ntt)) != hipSuccess)
         return e;
-    static const char* u64_tables[] = {"psi_half",
-                                       "last_q_modinv",
-                                       "half",
-                                       "half_mod",
-                                       "factor",
-                                       "m2_md_W0",
-                                       "m2_md_G",
-                                       "m2_md_C",
-                                       "rescaled_last_q_modinv",
-                                       "rescaled_half_mod",
-                                       "rescaled_half",
-                                       "base_change_matrix_Bsk",
-                                       "inv_punctured_prod_mod_base_array",
-                                       "base_change_matrix_m_tilde",
-                                       "inv_m_tilde_mod_Bsk",
-                                       "prod_q_mod_Bsk",
-                                       "inv_prod_q_mod_Bsk",
-                                       "base_change_matrix_q",
-                                       "base_change_matrix_msk",
-                                       "inv_punctured_prod_mod_B_array",
-                                       "behz_mtilde_inv_punct",
-                                       "behz_t_inv_punct",
-                                       "behz_invq_inv_punct_B",
-                                       "behz_msk_mod_q",
-                                       "behz_fc_matrix",
-                                       "behz_fc_c1",
-                                       "behz_ff_matrix",
-                                       "behz_ff_tc",
-                                       "behz_ff_q_matrix",
-                                       "behz_ff_msk_matrix",
-                                       "behz_ff_prod_B",
-                                       "behz_ff_neg_prod_B",
-                                       "prod_B_mod_q",
-                                       "Mi",
-                                       "Mi_inv",
-                                       "upper_half_threshold",
-                                       "decryption_modulus",
-                                       "special_fft_roots_table",
-                                       "special_ifft_roots_table",
-                                       "coeff_div_plain_modulus",
-                                       "upper_halfincrement",
-                                       "Qi_t",
-                                       "Qi_gamma",
-                                       "Qi_inverse",
-                                       "m2_Mi_inv",
-                                       "m2_matrix",
-                                       "m2_prod",
-                                       "m2_matrix_mg",
-                                       "m2_negprod_mg"};
-    for (const char* nm : u64_tables) {
-        auto it = host.find(nm);
+    // THE list of device tables: a row uploads the host table of its name, if build_host() made one, into its typed
+    // member (u64 tables; `ints`: as 32-bit ints) and registers the pointer under the name (hegpu_context_device_ptr)
+    const struct { const char* name; const u64** slot; const int** ints; } rows[] = {
+        {"psi_half", &tab.psi_half}, {"last_q_modinv", &tab.last_q_modinv}, {"half", &tab.half},
+        {"half_mod", &tab.half_mod}, {"factor", &tab.factor},
+        {"m2_md_W0", &tab.m2_md_W0}, {"m2_md_G", &tab.m2_md_G}, {"m2_md_C", &tab.m2_md_C},
+        {"rescaled_last_q_modinv", &tab.rescaled_last_q_modinv}, {"rescaled_half_mod", &tab.rescaled_half_mod},
+        {"rescaled_half", &tab.rescaled_half},
+        {"base_change_matrix_Bsk", &behz.base_change_matrix_Bsk},
+        {"inv_punctured_prod_mod_base_array", &behz.inv_punctured_prod_mod_base_array},
+        {"base_change_matrix_m_tilde", &behz.base_change_matrix_m_tilde},
+        {"inv_m_tilde_mod_Bsk", &behz.inv_m_tilde_mod_Bsk}, {"prod_q_mod_Bsk", &behz.prod_q_mod_Bsk},
+        {"inv_prod_q_mod_Bsk", &behz.inv_prod_q_mod_Bsk}, {"base_change_matrix_q", &behz.base_change_matrix_q},
+        {"base_change_matrix_msk", &behz.base_change_matrix_msk},
+        {"inv_punctured_prod_mod_B_array", &behz.inv_punctured_prod_mod_B_array},
+        {"behz_mtilde_inv_punct", &behz.mtilde_inv_punct}, {"behz_t_inv_punct", &behz.t_inv_punct},
+        {"behz_invq_inv_punct_B", &behz.invq_inv_punct_B}, {"behz_msk_mod_q", &behz.msk_mod_q},
+        {"behz_fc_matrix", &behz.fc_matrix}, {"behz_fc_c1", &behz.fc_c1}, {"behz_ff_matrix", &behz.ff_matrix},
+        {"behz_ff_tc", &behz.ff_tc}, {"behz_ff_q_matrix", &behz.ff_q_matrix},
+        {"behz_ff_msk_matrix", &behz.ff_msk_matrix}, {"behz_ff_prod_B", &behz.ff_prod_B},
+        {"behz_ff_neg_prod_B", &behz.ff_neg_prod_B}, {"prod_B_mod_q", &behz.prod_B_mod_q},
+        {"Mi", &tab.Mi}, {"Mi_inv", &tab.Mi_inv}, {"upper_half_threshold", &tab.upper_half_threshold},
+        {"decryption_modulus", &tab.decryption_modulus}, {"special_fft_roots_table", &tab.special_fft_roots_table},
+        {"special_ifft_roots_table", &tab.special_ifft_roots_table},
+        {"coeff_div_plain_modulus", &tab.coeff_div_plain_modulus}, {"upper_halfincrement", &tab.upper_halfincrement},
+        {"Qi_t", &tab.Qi_t}, {"Qi_gamma", &tab.Qi_gamma}, {"Qi_inverse", &tab.Qi_inverse},
+        {"m2_Mi_inv", &tab.m2_Mi_inv}, {"m2_matrix", &tab.m2_matrix}, {"m2_prod", &tab.m2_prod},
+        {"m2_matrix_mg", &tab.m2_matrix_mg}, {"m2_negprod_mg", &tab.m2_negprod_mg},
+        {"new_prime_locations", nullptr, &tab.new_prime_locations},
+        {"new_input_locations", nullptr, &tab.new_input_locations}, {"m2_I_j", nullptr, &tab.m2_I_j},
+        {"m2_I_location", nullptr, &tab.m2_I_location}, {"encoding_location", nullptr, &tab.encoding_location},
+        {"reverse_order", nullptr, &tab.reverse_order},
+    };
+    for (const auto& r : rows) {
+        auto it = host.find(r.name);
         if (it == host.end()) continue;
-        u64* d = nullptr;
-        if ((e = to_device(it->second, &d)) != hipSuccess) return e;
-        dev[nm] = d;
-    }
-    for (const char* nm : {"new_prime_locations", "new_input_locations", "m2_I_j", "m2_I_location", "encoding_location",
-                           "reverse_order"}) {
-        auto it = host.find(nm);
-        if (it == host.end()) continue;
-        std::vector<int> v(it->second.begin(), it->second.end());
-        int* d = nullptr;
-        if ((e = to_device(v, &d)) != hipSuccess) return e;
-        dev[nm] = d;
+        if (r.slot) {
+            u64* d = nullptr;
+            if ((e = to_device(it->second, &d)) != hipSuccess) return e;
+            dev[r.name] = d;
+            *r.slot = d;
+        } else {
+            std::vector<int> v(it->second.begin(), it->second.end());
+            int* d = nullptr;
+            if ((e = to_device(v, &d)) != hipSuccess) return e;
+            dev[r.name] = d;
+            *r.ints = d;
+        }
     }
     if (scheme == SCHEME_BFV) {
         if ((e = build_plan(plan_merge, host["q_Bsk_merge_modulus"], host["q_Bsk_merge_ntt_tables"],
@@ -720,30 +716,8 @@ hipError_t Context::upload()
         behz.obase = plan_merge.mods + Q_size;
         behz.m_tilde = make_mod(((u64) 1) << 32);
         behz.plain = make_mod(plain_modulus);
-        behz.inv_prod_q_mod_m_tilde = host["inv_prod_q_mod_m_tilde"][0];
-        behz.inv_prod_B_mod_m_sk = host["inv_prod_B_mod_m_sk"][0];
-        behz.inv_m_tilde_mod_Bsk = d64("inv_m_tilde_mod_Bsk");
-        behz.prod_q_mod_Bsk = d64("prod_q_mod_Bsk");
-        behz.base_change_matrix_Bsk = d64("base_change_matrix_Bsk");
-        behz.base_change_matrix_m_tilde = d64("base_change_matrix_m_tilde");
-        behz.inv_punctured_prod_mod_base_array = d64("inv_punctured_prod_mod_base_array");
-        behz.inv_prod_q_mod_Bsk = d64("inv_prod_q_mod_Bsk");
-        behz.inv_punctured_prod_mod_B_array = d64("inv_punctured_prod_mod_B_array");
-        behz.base_change_matrix_q = d64("base_change_matrix_q");
-        behz.base_change_matrix_msk = d64("base_change_matrix_msk");
-        behz.prod_B_mod_q = d64("prod_B_mod_q");
-        behz.mtilde_inv_punct = d64("behz_mtilde_inv_punct");
-        behz.t_inv_punct = d64("behz_t_inv_punct");
-        behz.invq_inv_punct_B = d64("behz_invq_inv_punct_B");
-        behz.msk_mod_q = d64("behz_msk_mod_q");
-        behz.fc_matrix = d64("behz_fc_matrix");
-        behz.fc_c1 = d64("behz_fc_c1");
-        behz.ff_matrix = d64("behz_ff_matrix");
-        behz.ff_tc = d64("behz_ff_tc");
-        behz.ff_q_matrix = d64("behz_ff_q_matrix");
-        behz.ff_msk_matrix = d64("behz_ff_msk_matrix");
-        behz.ff_prod_B = d64("behz_ff_prod_B");
-        behz.ff_neg_prod_B = d64("behz_ff_neg_prod_B");
+        behz.inv_prod_q_mod_m_tilde = hv.inv_prod_q_mod_m_tilde;
+        behz.inv_prod_B_mod_m_sk = hv.inv_prod_B_mod_m_sk;
         behz.ibase_size = Q_size;
         behz.obase_size = bsk_size;
         behz.split = behz_split;
@@ -755,68 +729,62 @@ hipError_t Context::upload()
 // ---- options (hegpu_context_set_option).  Environment variables HEGPU_<NAME> only seed the defaults, once, when the
 // context is created; nothing on a call path reads the environment.
 namespace {
-struct OptDesc { const char* name; const char* env; int lo, hi; };
-const OptDesc kOptions[] = {
-    {"fused_row_mac", "HEGPU_FUSED_ROW_MAC", -1, 1}, {"fused_moddown", "HEGPU_FUSED_MODDOWN", 0, 1},
-    {"col_multi", "HEGPU_COL_MULTI", -1, 1},         {"single_pass", "HEGPU_SINGLE_PASS", -1, 1},
-    {"ntt_galois", "HEGPU_NTT_GALOIS", 0, 1},        {"galois_scatter", "HEGPU_GALOIS_SCATTER", 0, 1},
-    {"fuse_inverse", "HEGPU_FUSE_INVERSE", 0, 1},    {"copy_along", "HEGPU_COPY_ALONG", 0, 1},
-    {"digit_split", "HEGPU_DIGIT_SPLIT", -1, 4},     {"fp_ntt", "HEGPU_FP_NTT", 0, 1},
-    {"behz_split", "HEGPU_BEHZ_SPLIT", -1, 1},       {"fused_tensor", "HEGPU_FUSED_TENSOR", 0, 1},
-    {"moddown_in_mac", "HEGPU_MODDOWN_IN_MAC", 0, 1},
+struct OptDesc {
+    // a value that passed the range check is still refused (2) / refused once the tables are on the device (3) /
+    // copied into the BEHZ kernels' argument block as well
+    enum Rule { PLAIN, NOT_1_OR_3, BEFORE_UPLOAD, MIRROR_BEHZ };
+    const char* name;
+    const char* env;
+    int lo, hi;
+    int ContextHost::*i;  // where the value lives: an int ...
+    bool ContextHost::*b; // ... or a bool member
+    Rule rule;
+    constexpr OptDesc(const char* nm, const char* ev, int l, int h, int ContextHost::*m, Rule r = PLAIN)
+        : name(nm), env(ev), lo(l), hi(h), i(m), b(nullptr), rule(r) {}
+    constexpr OptDesc(const char* nm, const char* ev, bool ContextHost::*m, Rule r = PLAIN)
+        : name(nm), env(ev), lo(0), hi(1), i(nullptr), b(m), rule(r) {}
 };
+typedef ContextHost H;
+const OptDesc kOptions[] = {
+    {"fused_row_mac", "HEGPU_FUSED_ROW_MAC", -1, 1, &H::fused_row_mac},
+    {"fused_moddown", "HEGPU_FUSED_MODDOWN", &H::fused_moddown},
+    {"col_multi", "HEGPU_COL_MULTI", -1, 1, &H::col_multi},
+    {"single_pass", "HEGPU_SINGLE_PASS", -1, 1, &H::single_pass},
+    {"ntt_galois", "HEGPU_NTT_GALOIS", &H::ntt_galois},
+    {"galois_scatter", "HEGPU_GALOIS_SCATTER", &H::galois_scatter},
+    {"fuse_inverse", "HEGPU_FUSE_INVERSE", &H::fuse_inverse},
+    {"copy_along", "HEGPU_COPY_ALONG", &H::copy_along},
+    {"digit_split", "HEGPU_DIGIT_SPLIT", -1, 4, &H::digit_split, OptDesc::NOT_1_OR_3},
+    {"fp_ntt", "HEGPU_FP_NTT", &H::fp_ntt, OptDesc::BEFORE_UPLOAD}, // decides the layout of the twiddle tables
+    {"behz_split", "HEGPU_BEHZ_SPLIT", -1, 1, &H::behz_split, OptDesc::MIRROR_BEHZ},
+    {"fused_tensor", "HEGPU_FUSED_TENSOR", &H::fused_tensor},
+    {"moddown_in_mac", "HEGPU_MODDOWN_IN_MAC", &H::moddown_in_mac},
+};
+const OptDesc* find_option(const char* name)
+{
+    for (const OptDesc& o : kOptions)
+        if (name && !strcmp(o.name, name)) return &o;
+    return nullptr;
+}
 } // namespace
 
 int Context::set_option(const char* name, int value)
 {
-    if (!name) return 1;
-    const OptDesc* d = nullptr;
-    for (const OptDesc& o : kOptions)
-        if (!strcmp(o.name, name)) d = &o;
+    const OptDesc* d = find_option(name);
     if (!d) return 1;
-    if (value < d->lo || value > d->hi) return 2;
-    const std::string nm(name);
-    if (nm == "fp_ntt") {
-        if (uploaded) return 3; // decides the layout of the twiddle tables
-        fp_ntt = value != 0;
-    } else if (nm == "fused_row_mac") fused_row_mac = value;
-    else if (nm == "fused_moddown") fused_moddown = value != 0;
-    else if (nm == "col_multi") col_multi = value;
-    else if (nm == "single_pass") single_pass = value;
-    else if (nm == "ntt_galois") ntt_galois = value != 0;
-    else if (nm == "galois_scatter") galois_scatter = value != 0;
-    else if (nm == "fuse_inverse") fuse_inverse = value != 0;
-    else if (nm == "copy_along") copy_along = value != 0;
-    else if (nm == "fused_tensor") fused_tensor = value != 0;
-    else if (nm == "moddown_in_mac") moddown_in_mac = value != 0;
-    else if (nm == "digit_split") {
-        if (value == 1 || value == 3) return 2;
-        digit_split = value;
-    } else if (nm == "behz_split") {
-        behz_split = value;
-        behz.split = value;
-    }
+    if (value < d->lo || value > d->hi || (d->rule == OptDesc::NOT_1_OR_3 && (value == 1 || value == 3))) return 2;
+    if (d->rule == OptDesc::BEFORE_UPLOAD && uploaded) return 3;
+    if (d->i) this->*d->i = value;
+    else this->*d->b = value != 0;
+    if (d->rule == OptDesc::MIRROR_BEHZ) behz.split = value;
     return 0;
 }
 
 int Context::get_option(const char* name, int* value) const
 {
-    if (!name || !value) return 1;
-    const std::string nm(name);
-    if (nm == "fp_ntt") *value = fp_ntt;
-    else if (nm == "fused_row_mac") *value = fused_row_mac;
-    else if (nm == "fused_moddown") *value = fused_moddown;
-    else if (nm == "col_multi") *value = col_multi;
-    else if (nm == "single_pass") *value = single_pass;
-    else if (nm == "ntt_galois") *value = ntt_galois;
-    else if (nm == "galois_scatter") *value = galois_scatter;
-    else if (nm == "fuse_inverse") *value = fuse_inverse;
-    else if (nm == "copy_along") *value = copy_along;
-    else if (nm == "fused_tensor") *value = fused_tensor;
-    else if (nm == "moddown_in_mac") *value = moddown_in_mac;
-    else if (nm == "digit_split") *value = digit_split;
-    else if (nm == "behz_split") *value = behz_split;
-    else return 1;
+    const OptDesc* d = find_option(name);
+    if (!d || !value) return 1;
+    *value = d->i ? this->*d->i : (int) (this->*d->b);
     return 0;
 }
 
@@ -857,17 +825,6 @@ void Context::release_device()
 Context::~Context()
 {
     if (uploaded) release_device();
-}
-
-const u64* Context::d64(const char* name) const
-{
-    auto it = dev.find(name);
-    return it == dev.end() ? nullptr : (const u64*) it->second;
-}
-const int* Context::d32(const char* name) const
-{
-    auto it = dev.find(name);
-    return it == dev.end() ? nullptr : (const int*) it->second;
 }
 
 NttArgs Context::ntt_args(int table_set) const

@@ -40,7 +40,27 @@ struct NttPlan {
     u64 lazy_q_max = 0;
 };
 
-struct Context {
+// Device copies of the host tables that upload() files under the same names (context.cpp, the row table in upload();
+// the BFV BEHZ tables go straight into BehzDev).  A member is null where build_host() makes no such table: the groups
+// say when it does, which is the check that an entry point (cabi.cpp) makes before a sequence reads the member.
+struct DevTables {
+    // every context
+    const u64 *psi_half, *last_q_modinv, *half, *half_mod, *factor;
+    // P_size > 1 (key-switching method II)
+    const u64 *m2_md_W0, *m2_md_G, *m2_md_C, *m2_Mi_inv, *m2_matrix, *m2_prod, *m2_matrix_mg, *m2_negprod_mg;
+    const int *m2_I_j, *m2_I_location;
+    // CKKS (rescaled_*: empty with a single ciphertext prime, which has no rescale)
+    const u64 *rescaled_last_q_modinv, *rescaled_half_mod, *rescaled_half;
+    const u64 *Mi, *Mi_inv, *upper_half_threshold, *decryption_modulus, *special_fft_roots_table, *special_ifft_roots_table;
+    const int *new_prime_locations, *new_input_locations, *reverse_order;
+    // BFV
+    const u64 *coeff_div_plain_modulus, *upper_halfincrement, *Qi_t, *Qi_gamma, *Qi_inverse;
+    // BFV with batching (plan_plain.count != 0)
+    const int* encoding_location;
+};
+
+// Everything hegpu_context_clone copies: the parameter set, the host tables and the options.
+struct ContextHost {
     int scheme = 0;
     int n_power = 0;
     u64 n = 0;
@@ -48,7 +68,16 @@ struct Context {
     int bsk_size = 0;
     u64 plain_modulus = 0;
     std::vector<u64> primes; // Q then P
-    std::map<std::string, std::vector<u64>> host; // named host tables
+    std::map<std::string, std::vector<u64>> host; // named host tables: read by build_host(), upload() and hegpu_context_get only
+    // the host values the operator sequences read on every call (build_host())
+    struct HostVals {
+        u64 half = 0;                         // half[0]
+        std::vector<u64> rescaled_half;       // CKKS, per depth
+        std::vector<u64> new_prime_locations; // CKKS: host copy of the device table (ops.cpp: fill_int_slots)
+        // BFV
+        u64 Q_mod_t = 0, upper_threshold = 0, gamma = 0, mulq_inv_t = 0, mulq_inv_gamma = 0, inv_gamma = 0;
+        u64 inv_prod_q_mod_m_tilde = 0, inv_prod_B_mod_m_sk = 0;
+    } hv;
     // key-switching method II (P_size > 1): per-depth digit partition + table
     // offsets into the flattened host/device arrays "m2_*"
     struct M2Level {
@@ -60,22 +89,24 @@ struct Context {
     };
     std::vector<M2Level> m2_levels;
     int m2_width = 0; // digit width m: 2 for BFV, P_size for CKKS
-    // use the fused "row pass + key-switch MAC" kernel (HEGPU_FUSED_ROW_MAC=0 disables)
-    int fused_row_mac = -1;    // HEGPU_FUSED_ROW_MAC: 1 / 0 force the fused / the reference's key-switch sequence, otherwise by launch size (ops.cpp: use_fused_row_mac)
-    bool fused_moddown = true; // HEGPU_FUSED_MODDOWN=0: separate stage-two kernel
-    int col_multi = -1;        // HEGPU_COL_MULTI: form of the decomposing column pass (NttArgs::col_multi)
-    int single_pass = -1;      // HEGPU_SINGLE_PASS: 1 / 0 force the single pass / the two passes for N <= 2^14, otherwise by launch size (NttArgs::single_pass)
-    bool ntt_galois = true;    // HEGPU_NTT_GALOIS=0: CKKS rotations in the reference's order (permutation in the coefficient domain)
-    bool galois_scatter = true; // HEGPU_GALOIS_SCATTER=0: the NTT-domain permutation as a kernel of its own (gather) instead of the mod-down epilogue's store
-    int digit_split = -1;      // HEGPU_DIGIT_SPLIT: 0 never, 2 / 4 always that many workgroups per fused key-switch unit, -1 by launch size
-    bool copy_along = true;    // HEGPU_COPY_ALONG=0: the rescale's copy of the kept limbs always has its own launch
-    bool fuse_inverse = true;  // HEGPU_FUSE_INVERSE=0: the INTT feeding a decomposing launch runs on its own
-    bool moddown_in_mac = true; // HEGPU_MODDOWN_IN_MAC=0: CKKS method I, fused key switch: the mod-down row pass as a launch of its own instead of the inner product's tail
+    // ---- options: one row each in context.cpp (kOptions: name, HEGPU_<NAME> variable that seeds the default when a
+    // context is created, range, rule); hegpu_context_set_option (include/hegpu.h) is the interface
+    int fused_row_mac = -1;    // 1 / 0 force the fused / the reference's key-switch sequence, otherwise by launch size (ops.cpp: use_fused_row_mac)
+    bool fused_moddown = true; // 0: separate stage-two kernel
+    int col_multi = -1;        // form of the decomposing column pass (NttArgs::col_multi)
+    int single_pass = -1;      // 1 / 0 force the single pass / the two passes for N <= 2^14, otherwise by launch size (NttArgs::single_pass)
+    bool ntt_galois = true;    // 0: CKKS rotations in the reference's order (permutation in the coefficient domain)
+    bool galois_scatter = true; // 0: the NTT-domain permutation as a kernel of its own (gather) instead of the mod-down epilogue's store
+    int digit_split = -1;      // 0 never, 2 / 4 always that many workgroups per fused key-switch unit, -1 by launch size
+    bool copy_along = true;    // 0: the rescale's copy of the kept limbs always has its own launch
+    bool fuse_inverse = true;  // 0: the INTT feeding a decomposing launch runs on its own
+    bool moddown_in_mac = true; // 0: CKKS method I, fused key switch: the mod-down row pass as a launch of its own instead of the inner product's tail
     bool fused_tensor = true;  // BFV multiply: the tensor product as the load transform of the inverse transform (0: its own kernel)
-    bool fp_ntt = true;        // fp_ntt = 0: every modulus on the integer butterflies (read when the tables are built)
+    bool fp_ntt = true;        // 0: every modulus on the integer butterflies (read when the tables are built)
     int behz_split = -1;       // BFV BEHZ kernels: rows over four wavefronts (1), one thread per coefficient (0), by launch size (-1)
-    // The fields above are options: hegpu_context_set_option (include/hegpu.h); the environment variables named in
-    // the comments only seed their defaults when a context is created (seed_options_from_env).
+};
+
+struct Context : ContextHost {
     void seed_options_from_env();
     // 0 ok, 1 unknown name, 2 value out of range, 3 too late (the tables are already on the device)
     int set_option(const char* name, int value);
@@ -88,8 +119,8 @@ struct Context {
     NttPlan plan_qp;    // tables for the Q' chain
     NttPlan plan_merge; // BFV: [q_0..q_{Q-1}, Bsk...]
     NttPlan plan_plain; // BFV batching: the plain modulus t alone (bfv/context.cu:489-499), when 2N | t-1
-    std::map<std::string, void*> dev; // named device arrays (u64 / int)
-    Mod* bsk_mods = nullptr;
+    std::map<std::string, void*> dev; // the device tables by name: owns them; read by hegpu_context_device_ptr only
+    DevTables tab{};
     BehzDev behz{};
 
     ~Context();
@@ -97,10 +128,6 @@ struct Context {
     hipError_t upload();         // allocate + copy device tables (current device)
     void release_device();
 
-    const u64* d64(const char* name) const;
-    // host copy of a named table (throws if absent)
-    const std::vector<u64>& h64(const char* name) const { return host.at(name); }
-    const int* d32(const char* name) const;
     NttArgs ntt_args(int table_set) const; // 0 = Q' chain, 1 = merged q|Bsk
 };
 

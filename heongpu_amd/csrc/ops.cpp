@@ -1,6 +1,9 @@
 // ops.cpp -- operator sequences (the reference's host orchestration), batched
-// over independent ciphertexts and free of allocation: all temporaries live in
-// a caller-provided workspace so the sequences can be captured in a hipGraph.
+// over independent ciphertexts and free of allocation, on the device and on the
+// host: all temporaries live in a caller-provided workspace and every table is a
+// typed member of the context (Context::tab / hv, no lookup by name), so the
+// sequences can be captured in a hipGraph.  The one exception is
+// op_gen_secret_key, which stages its index list in a host vector and waits.
 #include "ops.hpp"
 #include <vector>
 #include <utility>
@@ -226,8 +229,8 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     NttArgs dgt = c.ntt_args(0);
     dgt.in = temp2; dgt.out = temp1; dgt.mod_count = rc; dgt.polys_per_item = l * rc; dgt.decomp_mods = rc;
     dgt.in_item_stride = per; dgt.out_item_stride = per;
-    dgt.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
-    fill_int_slots(c, dgt, c.h64("new_prime_locations").data() + triangle_offset(Qp, depth));
+    dgt.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
+    fill_int_slots(c, dgt, c.hv.new_prime_locations.data() + triangle_offset(Qp, depth));
     // When the decomposing column pass is the multi-modulus kernel (one launch for the whole batch), it also
     // finishes the inverse transform of its source tiles: only the row stages of the INTT run on their own.
     const bool fuse_inv = use_fused_row_mac(c, rc, batch) && c.fuse_inverse && (long) l * rc * batch <= 65535 &&
@@ -255,7 +258,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     a = c.ntt_args(0);
     a.in = temp2; a.out = temp2; a.mod_count = 1; a.mod_offset = Q; a.polys_per_item = 2;
     a.in_item_stride = a.out_item_stride = per;
-    a.poly_order = c.d32("new_input_locations") + 2 * depth;
+    a.poly_order = c.tab.new_input_locations + 2 * depth;
     // the same fusion for the mod-down transform, whose source is the inverse transform of the P limbs
     NttArgs md = c.ntt_args(0);
     md.in = temp2; md.out = temp1; md.mod_count = l; md.polys_per_item = 2 * l;
@@ -273,7 +276,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
         if (phases & RELIN_PHASE_MODDOWN) {
             a = md;
             a.out = temp2; a.decomp_out_mul = l + 1; // T of part p, limb j: slot j of part p in temp2 [2][l+1][N]
-            a.half = c.h64("half")[0]; a.half_mod = c.d64("half_mod");
+            a.half = c.hv.half; a.half_mod = c.tab.half_mod;
             a.src_inv = fuse_inv_p ? 1 : 0;
             TRY(ntt_launch_fwd_col(a, 2 * l * batch, st));
         }
@@ -283,7 +286,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
         t.T = temp2; t.T_item_stride = per;
         t.ct = add; t.ct_item_stride = add_stride; t.ct_parts = add_parts;
         t.out = outp; t.out_item_stride = out_stride;
-        t.inv = c.d64("last_q_modinv");
+        t.inv = c.tab.last_q_modinv;
         t.limbs = l;
         t.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
         return keyswitch_ntt_mac(c, dgt_args, key, temp2, per, l, rc, l, depth, src, src_stride, batch, st, 2, 0, l, &t);
@@ -291,7 +294,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     if (!(phases & RELIN_PHASE_MODDOWN)) return hipSuccess;
     // stage one: P limb (+half) reduced into every q_j               (:1003)
     if (!c.fused_moddown)
-        TRY(rns_moddown_stage_one(temp2, per, temp1, per, mods, c.d64("half"), c.d64("half_mod"), np, Q, l, batch,
+        TRY(rns_moddown_stage_one(temp2, per, temp1, per, mods, c.tab.half, c.tab.half_mod, np, Q, l, batch,
                                   st));
     // forward NTT of that (:1011) with stage one as its load transform and stage two -- (x - last) * P^-1 + add, written to
     // out parts 0,1 (:1015) -- as the epilogue of its row pass
@@ -301,12 +304,12 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     if (c.fused_moddown) {
         // input: the P limb (slot l) of each of the two parts of temp2 [2][l+1][N]
         a.in = temp2; a.decomp_mods = l; a.decomp_in_mul = l + 1; a.decomp_in_add = l;
-        a.half_on = 1; a.half_src_mod = Q; a.half = c.h64("half")[0]; a.half_mod = c.d64("half_mod");
+        a.half_on = 1; a.half_src_mod = Q; a.half = c.hv.half; a.half_mod = c.tab.half_mod;
         a.epi.on = 1;
         a.epi.ks = temp2; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = l + 1;
         a.epi.ct = add; a.epi.ct_item_stride = add_stride; a.epi.ct_parts = add_parts;
         a.epi.out = outp; a.epi.out_item_stride = out_stride;
-        a.epi.inv = c.d64("last_q_modinv");
+        a.epi.inv = c.tab.last_q_modinv;
         a.epi.limbs = l;
         a.epi.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
         a.src_inv = fuse_inv_p ? 1 : 0;
@@ -317,7 +320,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     if (add_parts != 2 || galois_elt) return hipErrorInvalidValue; // the stand-alone stage two adds both parts (relinearize only)
     TRY(ntt_launch(a, 2 * l * batch, false, st));
     return rns_moddown_stage_two(temp1, per, temp2, per, l + 1, add, add_stride, outp, out_stride, mods,
-                                 c.d64("last_q_modinv"), np, l, 1, batch, st);
+                                 c.tab.last_q_modinv, np, l, 1, batch, st);
 }
 
 // ------------------------------------------------------------------ method II (P_size > 1)
@@ -326,9 +329,9 @@ static hipError_t dtoq(const Context& c, int lvl, const u64* in, u64 in_stride, 
 {
     const Context::M2Level& L = c.m2_levels[lvl];
     return rns_base_conversion_DtoQtilde(in, in_stride, out, out_stride, c.plan_qp.mods,
-                                         c.d64("m2_matrix_mg") + L.off_matrix, c.d64("m2_Mi_inv") + L.off_mi,
-                                         c.d64("m2_negprod_mg") + L.off_prod, c.d32("m2_I_j") + L.off_digits,
-                                         c.d32("m2_I_location") + L.off_digits, c.n_power, L.d, L.rc, l, level,
+                                         c.tab.m2_matrix_mg + L.off_matrix, c.tab.m2_Mi_inv + L.off_mi,
+                                         c.tab.m2_negprod_mg + L.off_prod, c.tab.m2_I_j + L.off_digits,
+                                         c.tab.m2_I_location + L.off_digits, c.n_power, L.d, L.rc, l, level,
                                          c.m2_width, batch, st);
 }
 
@@ -354,8 +357,8 @@ static hipError_t ckks_moddown_multi(const Context& c, u64* acc, u64* scratch, u
         a.in_item_stride = a.out_item_stride = per;
         TRY(ntt_launch(a, P * batch, true, st));
     }
-    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, rc, l, Qp, Q,
+    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                                    c.tab.last_q_modinv, c.tab.m2_md_G, c.tab.m2_md_C, c.n_power, rc, l, Qp, Q,
                                     P, batch, st));
     NttArgs a = c.ntt_args(0);
     a.in = a.out = scratch; a.mod_count = l; a.polys_per_item = 2 * l;
@@ -364,7 +367,7 @@ static hipError_t ckks_moddown_multi(const Context& c, u64* acc, u64* scratch, u
     a.epi.ks = acc; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = rc;
     a.epi.ct = ct; a.epi.ct_item_stride = cs; a.epi.ct_parts = add_parts;
     a.epi.out = out; a.epi.out_item_stride = so;
-    a.epi.inv = c.d64("m2_md_W0");
+    a.epi.inv = c.tab.m2_md_W0;
     a.epi.limbs = l;
     a.epi.galois_inv = galois_elt ? (unsigned) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0u;
     return ntt_launch(a, 2 * l * batch, false, st);
@@ -380,11 +383,11 @@ static hipError_t ckks_rotate_tail(const Context& c, u64* acc, const u64* coef, 
     const int l = Q - depth, rc = Qp - depth;
     NttArgs a = c.ntt_args(0);
     a.in = acc; a.out = acc; a.mod_count = rc; a.polys_per_item = 2 * rc;
-    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1524
-    TRY(rns_moddown_permute(acc, per, coef, per, out, so, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                            c.d64("last_q_modinv"), galois_elt, c.n_power, rc, l, Qp, Q, c.P_size, batch, st)); // :1530
+    TRY(rns_moddown_permute(acc, per, coef, per, out, so, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                            c.tab.last_q_modinv, galois_elt, c.n_power, rc, l, Qp, Q, c.P_size, batch, st)); // :1530
     a = c.ntt_args(0);
     a.in = out; a.out = out; a.mod_count = l; a.polys_per_item = 2 * l;
     a.in_item_stride = a.out_item_stride = so;
@@ -423,7 +426,7 @@ static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int
     TRY(dtoq(c, depth, coef + (u64) add_parts * l * n, coef_stride, digits, per, l, depth, batch, st)); // :1065
     a = c.ntt_args(0);
     a.in = digits; a.out = digits; a.mod_count = rc; a.polys_per_item = d * rc;
-    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     a.in_item_stride = a.out_item_stride = per;
     TRY(keyswitch_ntt_mac(c, a, key, acc, per, d, rc, l, depth, nullptr, 0, batch, st));  // :1095-1125
     // the front of the workspace (the digits of a relinearization, the coefficient-domain copy of a rotation) is free
@@ -433,8 +436,8 @@ static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int
     if (!relin) return ckks_rotate_tail(c, acc, ws, per, out, so, galois_elt, depth, batch, st);
     a.in = acc; a.out = acc; a.polys_per_item = 2 * rc;
     TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1131
-    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                             c.d64("last_q_modinv"), np, rc, l, Qp, Q, c.P_size, 0, batch, st)); // :1136
+    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                             c.tab.last_q_modinv, np, rc, l, Qp, Q, c.P_size, 0, batch, st)); // :1136
     a = c.ntt_args(0);
     a.in = ws; a.out = ws; a.mod_count = l; a.polys_per_item = 2 * l;
     a.in_item_stride = a.out_item_stride = per;
@@ -475,7 +478,7 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
     NttArgs a = c.ntt_args(0);
     a.in = ct; a.out = ct; a.mod_count = 1; a.mod_offset = l - 1; a.polys_per_item = 2;
     a.in_item_stride = a.out_item_stride = cs;
-    a.poly_order = c.d32("new_input_locations") + (depth + P) * 2;
+    a.poly_order = c.tab.new_input_locations + (depth + P) * 2;
     TRY(ntt_launch(a, 2 * batch, true, st));                                               // :1197
     if (c.fused_moddown) {
         // stage one (:1205) as the load transform and stage two (:1225) as the row-pass epilogue
@@ -485,8 +488,8 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         a.in = ct; a.out = temp1; a.mod_count = l - 1; a.polys_per_item = 2 * (l - 1);
         a.in_item_stride = cs; a.out_item_stride = per;
         a.decomp_mods = l - 1; a.decomp_in_mul = l; a.decomp_in_add = l - 1;
-        a.half_on = 1; a.half_src_mod = l - 1; a.half = c.h64("rescaled_half")[depth];
-        a.half_mod = c.d64("rescaled_half_mod") + location;
+        a.half_on = 1; a.half_src_mod = l - 1; a.half = c.hv.rescaled_half[depth];
+        a.half_mod = c.tab.rescaled_half_mod + location;
         // The copy rides on the column pass when that is the per-polynomial kernel (one workgroup per kept limb
         // and tile: C2, 4.7 us of launch less); the multi-modulus kernel keeps its own launch for it.
         if (c.copy_along && !ntt_decomp_uses_multi(a, 2 * (l - 1) * batch)) {
@@ -500,19 +503,19 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         a.epi.ks = temp2; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = l;
         a.epi.ct = nullptr; a.epi.ct_item_stride = 0;
         a.epi.out = ct; a.epi.out_item_stride = cs;
-        a.epi.inv = c.d64("rescaled_last_q_modinv") + location;
+        a.epi.inv = c.tab.rescaled_last_q_modinv + location;
         a.epi.limbs = l - 1;
         return ntt_launch(a, 2 * (l - 1) * batch, false, st);
     }
-    TRY(rns_moddown_stage_one(ct, cs, temp1, per, mods, c.d64("rescaled_half") + depth,
-                              c.d64("rescaled_half_mod") + location, np, l - 1, l - 1, batch, st)); // :1205
+    TRY(rns_moddown_stage_one(ct, cs, temp1, per, mods, c.tab.rescaled_half + depth,
+                              c.tab.rescaled_half_mod + location, np, l - 1, l - 1, batch, st)); // :1205
     a = c.ntt_args(0);
     a.in = temp1; a.out = temp1; a.mod_count = l - 1; a.polys_per_item = 2 * (l - 1);
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * (l - 1) * batch, false, st));                                    // :1214
     TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, per, np, l - 1, 2, batch, st)); // :1219
     return rns_moddown_stage_two(temp1, per, temp2, per, l, nullptr, 0, ct, cs, mods,
-                                 c.d64("rescaled_last_q_modinv") + location, np, l - 1, 0, batch, st); // :1225
+                                 c.tab.rescaled_last_q_modinv + location, np, l - 1, 0, batch, st); // :1225
 }
 
 // reference ckks/operator.cu:1422-1559
@@ -551,7 +554,7 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
     a = c.ntt_args(0); // ckks_duplicate_kernel fused into the NTT load          :1467-1494
     a.in = temp0 + (u64) l * n; a.out = temp2; a.mod_count = rc; a.polys_per_item = l * rc; a.decomp_mods = rc;
     a.in_item_stride = a.out_item_stride = per;
-    a.mod_order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     TRY(keyswitch_ntt_mac(c, a, key, temp3, per, l, rc, l, depth, ct + (u64) l * n, cs, batch, st)); // :1490-1520
     return ckks_rotate_tail(c, temp3, temp0, per, out, so, galois_elt, depth, batch, st);
 }
@@ -605,7 +608,7 @@ static hipError_t bfv_intt_moddown(const Context& c, u64* acc, u64 per, const u6
     a.in = a.out = acc; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
     a.in_item_stride = a.out_item_stride = per;
     a.iepi.on = 1; a.iepi.limbs = Q; a.iepi.add_parts = add_parts; a.iepi.p_mod = Q; a.iepi.galois_elt = galois_elt;
-    a.iepi.half = c.h64("half")[0]; a.iepi.half_mod = c.d64("half_mod"); a.iepi.inv = c.d64("last_q_modinv");
+    a.iepi.half = c.hv.half; a.iepi.half_mod = c.tab.half_mod; a.iepi.inv = c.tab.last_q_modinv;
     a.iepi.ct = ct; a.iepi.ct_item_stride = cs;
     a.iepi.out = out; a.iepi.out_item_stride = so;
     return ntt_launch(a, 2 * Qp * batch, true, st);
@@ -631,15 +634,15 @@ static hipError_t bfv_intt_moddown_multi(const Context& c, u64* acc, u64* scratc
         a.in_item_stride = a.out_item_stride = per;
         TRY(ntt_launch(a, P * batch, true, st));
     }
-    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.d64("half"), c.d64("half_mod"),
-                                    c.d64("last_q_modinv"), c.d64("m2_md_G"), c.d64("m2_md_C"), c.n_power, Qp, Q, Qp, Q, P,
+    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
+                                    c.tab.last_q_modinv, c.tab.m2_md_G, c.tab.m2_md_C, c.n_power, Qp, Q, Qp, Q, P,
                                     batch, st));
     NttArgs a = c.ntt_args(0);
     a.in = a.out = acc; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
     a.in_item_stride = a.out_item_stride = per;
     a.iepi.on = 1; a.iepi.limbs = Q; a.iepi.p_count = P; a.iepi.add_parts = add_parts; a.iepi.p_mod = Q;
     a.iepi.galois_elt = galois_elt;
-    a.iepi.inv = c.d64("m2_md_W0");
+    a.iepi.inv = c.tab.m2_md_W0;
     a.iepi.u = scratch; a.iepi.u_item_stride = per;
     a.iepi.ct = ct; a.iepi.ct_item_stride = cs;
     a.iepi.out = out; a.iepi.out_item_stride = so;
@@ -683,13 +686,13 @@ static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * Qp * batch, true, st));
     if (add_parts == 1)
-        return rns_moddown_permute(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                                   c.d64("last_q_modinv"), galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st);
+        return rns_moddown_permute(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
+                                   c.tab.last_q_modinv, galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st);
     if (m2)
-        return rns_moddown_extended(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                                    c.d64("last_q_modinv"), np, Qp, Q, Qp, Q, c.P_size, 1, batch, st);
-    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, mods, c.d64("half"), c.d64("half_mod"),
-                                  c.d64("last_q_modinv"), np, Q, 0, batch, st);
+        return rns_moddown_extended(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
+                                    c.tab.last_q_modinv, np, Qp, Q, Qp, Q, c.P_size, 1, batch, st);
+    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
+                                  c.tab.last_q_modinv, np, Q, 0, batch, st);
 }
 
 hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws, hipStream_t st)
@@ -731,7 +734,7 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     u64* temp2 = temp0 + (u64) 2 * l * n;  // [digits][rc][N] NTT-domain digits
     u64* temp3 = temp2 + (u64) l * rc * n; // [group][2][rc][N]
     const Mod* mods = c.plan_qp.mods;
-    const int* order = c.d32("new_prime_locations") + triangle_offset(Qp, depth);
+    const int* order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     const u64 ct_words = (u64) 2 * l * n;
     bool any = false;
     for (int i = 0; i < count; i++) {
@@ -867,7 +870,7 @@ hipError_t op_gen_switch_key(const Context& c, Rng& r, const u64* sk, int galois
     a.in = e; a.out = e; a.mod_count = Qp;
     TRY(ntt_launch(a, d * Qp, false, st));
     const int inv = galois_elt ? (int) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0; // keygenerator.cu:474
-    return kg_switchkey(key, sk, e, av, c.plan_qp.mods, c.d64("factor"), inv, old_sk, c.n_power, Qp, d, width, Q,
+    return kg_switchkey(key, sk, e, av, c.plan_qp.mods, c.tab.factor, inv, old_sk, c.n_power, Qp, d, width, Q,
                         c.P_size, st);
 }
 
@@ -889,8 +892,8 @@ static hipError_t encrypt_zero(const Context& c, Rng& r, const u64* pk, u64* ct,
     a.in = pku; a.out = pku;
     TRY(ntt_launch(a, 2 * Qp, true, st));
     TRY(rns_addition(pku, e, pku, mods, np, Qp, 2, 1, 0, st));
-    return rns_moddown_extended(pku, 0, nullptr, 0, ct, 0, mods, c.d64("half"), c.d64("half_mod"),
-                                c.d64("last_q_modinv"), np, Qp, Q, Qp, Q, c.P_size, 0, 1, st);
+    return rns_moddown_extended(pku, 0, nullptr, 0, ct, 0, mods, c.tab.half, c.tab.half_mod,
+                                c.tab.last_q_modinv, np, Qp, Q, Qp, Q, c.P_size, 0, 1, st);
 }
 
 hipError_t op_ckks_encrypt(const Context& c, Rng& r, const u64* pk, const u64* plain, u64* ct, u64* ws,
@@ -907,8 +910,8 @@ hipError_t op_bfv_encrypt(const Context& c, Rng& r, const u64* pk, const u64* pl
                           hipStream_t st)
 {
     TRY(encrypt_zero(c, r, pk, ct, ws, st));
-    return kg_bfv_message_add(ct, plain, c.plan_qp.mods, c.d64("coeff_div_plain_modulus"), c.h64("Q_mod_t")[0],
-                              c.h64("upper_threshold")[0], c.plain_modulus, c.n_power, c.Q_size, st);
+    return kg_bfv_message_add(ct, plain, c.plan_qp.mods, c.tab.coeff_div_plain_modulus, c.hv.Q_mod_t,
+                              c.hv.upper_threshold, c.plain_modulus, c.n_power, c.Q_size, st);
 }
 
 hipError_t op_bfv_decrypt(const Context& c, const u64* ct, const u64* sk, u64* plain, u64* ws, hipStream_t st)
@@ -924,11 +927,11 @@ hipError_t op_bfv_decrypt(const Context& c, const u64* ct, const u64* sk, u64* p
     TRY(ntt_launch(a, Q, true, st));                                                       // :101
     BfvDecryptDev d{};
     d.plain = make_mod(c.plain_modulus);
-    d.gamma = make_mod(c.h64("gamma")[0]);
-    d.Qi_t = c.d64("Qi_t"); d.Qi_gamma = c.d64("Qi_gamma"); d.Qi_inverse = c.d64("Qi_inverse");
-    d.mulq_inv_t = c.h64("mulq_inv_t")[0];
-    d.mulq_inv_gamma = c.h64("mulq_inv_gamma")[0];
-    d.inv_gamma = c.h64("inv_gamma")[0];
+    d.gamma = make_mod(c.hv.gamma);
+    d.Qi_t = c.tab.Qi_t; d.Qi_gamma = c.tab.Qi_gamma; d.Qi_inverse = c.tab.Qi_inverse;
+    d.mulq_inv_t = c.hv.mulq_inv_t;
+    d.mulq_inv_gamma = c.hv.mulq_inv_gamma;
+    d.inv_gamma = c.hv.inv_gamma;
     return kg_bfv_decryption(ct, t1, plain, c.plan_qp.mods, d, np, Q, st);                 // :107
 }
 
@@ -948,7 +951,7 @@ hipError_t op_bfv_encode(const Context& c, const long long* message, int message
 {
     if (!c.plan_plain.count) return hipErrorNotSupported;
     if (message_size < 0 || message_size > (int) c.n) return hipErrorInvalidValue;
-    TRY(kg_bfv_encode_scatter(plain, message, c.d32("encoding_location"), c.plain_modulus, message_size, c.n_power,
+    TRY(kg_bfv_encode_scatter(plain, message, c.tab.encoding_location, c.plain_modulus, message_size, c.n_power,
                               st));                                                        // :66
     NttArgs a = c.ntt_args(2);
     a.in = plain; a.out = plain; a.mod_count = 1;
@@ -961,14 +964,14 @@ hipError_t op_bfv_decode(const Context& c, const u64* plain, u64* message, u64* 
     NttArgs a = c.ntt_args(2);
     a.in = plain; a.out = ws; a.mod_count = 1;
     TRY(ntt_launch(a, 1, false, st));                                                      // :234
-    return kg_bfv_decode_gather(message, ws, c.d32("encoding_location"), c.n_power, st);   // :239
+    return kg_bfv_decode_gather(message, ws, c.tab.encoding_location, c.n_power, st);   // :239
 }
 
 hipError_t op_bfv_multiply_plain(const Context& c, const u64* ct, const u64* plain, u64* out, u64* ws, hipStream_t st)
 {
     const int np = c.n_power, Q = c.Q_size;
     u64* pl = ws; // [Q][N]
-    TRY(kg_bfv_threshold(plain, pl, c.plan_qp.mods, c.d64("upper_halfincrement"), c.h64("upper_threshold")[0], np, Q,
+    TRY(kg_bfv_threshold(plain, pl, c.plan_qp.mods, c.tab.upper_halfincrement, c.hv.upper_threshold, np, Q,
                          st));                                                             // :454
     NttArgs a = c.ntt_args(0);
     a.in = pl; a.out = pl; a.mod_count = Q;
@@ -983,7 +986,7 @@ hipError_t op_bfv_multiply_plain(const Context& c, const u64* ct, const u64* pla
 // HEOperator<BFV>::transform_to_ntt_bfv_plain (bfv/operator.cu:1398-1431): threshold lift mod every q_j, forward NTT
 hipError_t op_bfv_plain_to_ntt(const Context& c, const u64* plain, u64* out, hipStream_t st)
 {
-    TRY(kg_bfv_threshold(plain, out, c.plan_qp.mods, c.d64("upper_halfincrement"), c.h64("upper_threshold")[0],
+    TRY(kg_bfv_threshold(plain, out, c.plan_qp.mods, c.tab.upper_halfincrement, c.hv.upper_threshold,
                          c.n_power, c.Q_size, st));
     NttArgs a = c.ntt_args(0);
     a.in = out; a.out = out; a.mod_count = c.Q_size;
@@ -1016,8 +1019,8 @@ hipError_t op_ckks_encode(const Context& c, int mode, const double* message, int
     void* cbuf = ws; // slots complex doubles = N words
     const double fix = scale / (double) slots;                                             // :127
     // double -> complex (:120) in the transform's first load
-    TRY(en_special_fft(cbuf, c.d64("special_ifft_roots_table"), log2i(slots), true, fix, st, message, message_size, mode == 1));
-    TRY(en_conversion(plain, cbuf, c.plan_qp.mods, Q, c.d32("reverse_order"), c.n_power, st)); // :138
+    TRY(en_special_fft(cbuf, c.tab.special_ifft_roots_table, log2i(slots), true, fix, st, message, message_size, mode == 1));
+    TRY(en_conversion(plain, cbuf, c.plan_qp.mods, Q, c.tab.reverse_order, c.n_power, st)); // :138
     return ntt_launch(a, Q, false, st);                                                    // :153
 }
 
@@ -1035,14 +1038,14 @@ hipError_t op_ckks_decode(const Context& c, int mode, const u64* plain, int dept
     int counter = c.Q_size, loc1 = 0, loc2 = 0;                                            // :474-482
     for (int i = 0; i < depth; i++) { loc1 += counter; loc2 += counter * counter; counter--; }
     if (mode == 2)                                                                         // :586-635
-        return en_coeff_compose(message, coeff, c.plan_qp.mods, c.d64("Mi_inv") + loc1, c.d64("Mi") + loc2,
-                                c.d64("upper_half_threshold") + loc1, c.d64("decryption_modulus") + loc1, l, scale,
+        return en_coeff_compose(message, coeff, c.plan_qp.mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2,
+                                c.tab.upper_half_threshold + loc1, c.tab.decryption_modulus + loc1, l, scale,
                                 c.n_power, st);
-    TRY(en_compose(cbuf, coeff, c.plan_qp.mods, c.d64("Mi_inv") + loc1, c.d64("Mi") + loc2,
-                   c.d64("upper_half_threshold") + loc1, c.d64("decryption_modulus") + loc1, l, scale,
-                   c.d32("reverse_order"), c.n_power, st));                                // :485
+    TRY(en_compose(cbuf, coeff, c.plan_qp.mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2,
+                   c.tab.upper_half_threshold + loc1, c.tab.decryption_modulus + loc1, l, scale,
+                   c.tab.reverse_order, c.n_power, st));                                // :485
     // :502, complex -> double (:505) in the transform's last store
-    return en_special_fft(cbuf, c.d64("special_fft_roots_table"), log2i(slots), false, 1.0, st, nullptr, 0, 0, message, mode == 1);
+    return en_special_fft(cbuf, c.tab.special_fft_roots_table, log2i(slots), false, 1.0, st, nullptr, 0, 0, message, mode == 1);
 }
 
 hipError_t op_ckks_decrypt(const Context& c, const u64* ct, const u64* sk, int depth, u64* plain, hipStream_t st)
