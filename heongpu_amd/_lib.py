@@ -104,6 +104,18 @@ SIGNATURES = [
     ("hegpu_ckks_decrypt", c_int, [voidp, u64p, u64p, c_int, u64p, voidp]),
     ("hegpu_bfv_encrypt", c_int, [voidp, voidp, u64p, u64p, u64p, voidp, c_size_t, voidp]),
     ("hegpu_bfv_decrypt", c_int, [voidp, u64p, u64p, u64p, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_public_key_share", c_int, [voidp, voidp, voidp, u64p, u64p, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_relin_key_share_round1", c_int, [voidp, voidp, voidp, u64p, u64p, u64p, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_relin_key_share_round2", c_int, [voidp, voidp, u64p, u64p, u64p, u64p, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_galois_key_share", c_int, [voidp, voidp, voidp, u64p, c_int, u64p, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_accumulate", c_int, [voidp, ctypes.POINTER(ctypes.c_void_p), c_int, c_int, u64p, voidp]),
+    ("hegpu_mpc_relin_key_finish", c_int, [voidp, ctypes.POINTER(ctypes.c_void_p), c_int, u64p, u64p, voidp]),
+    ("hegpu_mpc_ckks_decrypt_share", c_int, [voidp, voidp, u64p, u64, u64p, c_int, u64p, c_int, voidp]),
+    ("hegpu_mpc_ckks_decrypt_merge", c_int,
+     [voidp, u64p, u64, ctypes.POINTER(ctypes.c_void_p), c_int, c_int, u64p, c_int, voidp]),
+    ("hegpu_mpc_bfv_decrypt_share", c_int, [voidp, voidp, u64p, u64, u64p, u64p, c_int, voidp]),
+    ("hegpu_mpc_bfv_decrypt_merge", c_int,
+     [voidp, u64p, u64, ctypes.POINTER(ctypes.c_void_p), c_int, u64p, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_noise_rns", c_int, [voidp, u64p, u64p, u64p, voidp]),
     ("hegpu_bfv_plain_to_ntt", c_int, [voidp, u64p, u64p, voidp]),
     ("hegpu_negacyclic_shift", c_int, [voidp, u64p, u64p, c_int, c_int, c_int, voidp]),

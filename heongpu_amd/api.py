@@ -20,6 +20,8 @@ OP_CKKS_ROTATE_HOISTED = 17
 OP_KEYGEN_SECRET, OP_KEYGEN_PUBLIC, OP_KEYGEN_SWITCH, OP_CKKS_ENCRYPT, OP_BFV_ENCRYPT, OP_BFV_DECRYPT, OP_BFV_DECODE = 7, 8, 9, 10, 11, 12, 13
 OP_CKKS_ENCODE, OP_CKKS_DECODE = 14, 15
 OP_BFV_MULTIPLY_PLAIN = 16
+OP_MPC_KEY_SHARE, OP_MPC_BFV_DECRYPT_MERGE = 18, 19
+MPC_PUBLIC_KEY, MPC_GALOIS_KEY, MPC_RELIN_ROUND1 = 0, 1, 2
 TABLES_PLAIN = 2
 
 E_INVALID, E_LOGIC, E_RUNTIME, E_NODEVICE = 10001, 10002, 10003, 10004
@@ -566,6 +568,97 @@ class Context:
                                             stream if stream is not None else _stream()))
         return plain
 
+    # ---- N-out-of-N multiparty protocol (hegpu_mpc_*): crs = the generator all parties seed alike, rng = the party's own
+    def _key_words(self, layout):
+        return (1 if layout == MPC_PUBLIC_KEY else self.switch_key_digits()) * 2 * self.Q_prime_size * self.n
+
+    @staticmethod
+    def _share_array(shares):
+        return (ctypes.c_void_p * max(len(shares), 1))(*[_ptr(s) for s in shares])
+
+    def mpc_public_key_share(self, crs, rng, sk, stream=None):
+        import torch
+        share = torch.empty(self._key_words(MPC_PUBLIC_KEY), dtype=torch.int64, device="cuda")
+        ws = self._kg_ws(OP_MPC_KEY_SHARE)
+        _check(self._lib.hegpu_mpc_public_key_share(self._h, crs._h, rng._h, _ptr(sk), _ptr(share), _ptr(ws),
+                                                    ws.numel() * ws.element_size(),
+                                                    stream if stream is not None else _stream()))
+        return share
+
+    def mpc_relin_key_share_round1(self, crs, rng, sk, stream=None):
+        """-> (u, share): u is the party's ephemeral secret, to be handed to round 2 and to nobody else"""
+        import torch
+        u = torch.empty(self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
+        share = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
+        ws = self._kg_ws(OP_MPC_KEY_SHARE)
+        _check(self._lib.hegpu_mpc_relin_key_share_round1(self._h, crs._h, rng._h, _ptr(sk), _ptr(u), _ptr(share),
+                                                          _ptr(ws), ws.numel() * ws.element_size(),
+                                                          stream if stream is not None else _stream()))
+        return u, share
+
+    def mpc_relin_key_share_round2(self, rng, sk, u, round1_sum, stream=None):
+        import torch
+        share = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
+        ws = self._kg_ws(OP_MPC_KEY_SHARE)
+        _check(self._lib.hegpu_mpc_relin_key_share_round2(self._h, rng._h, _ptr(sk), _ptr(u), _ptr(round1_sum),
+                                                          _ptr(share), _ptr(ws), ws.numel() * ws.element_size(),
+                                                          stream if stream is not None else _stream()))
+        return share
+
+    def mpc_galois_key_share(self, crs, rng, sk, galois_elt, stream=None):
+        import torch
+        share = torch.empty(self._key_words(MPC_GALOIS_KEY), dtype=torch.int64, device="cuda")
+        ws = self._kg_ws(OP_MPC_KEY_SHARE)
+        _check(self._lib.hegpu_mpc_galois_key_share(self._h, crs._h, rng._h, _ptr(sk), galois_elt, _ptr(share), _ptr(ws),
+                                                    ws.numel() * ws.element_size(),
+                                                    stream if stream is not None else _stream()))
+        return share
+
+    def mpc_accumulate(self, shares, layout, stream=None):
+        import torch
+        out = torch.empty(self._key_words(layout), dtype=torch.int64, device="cuda")
+        _check(self._lib.hegpu_mpc_accumulate(self._h, self._share_array(shares), len(shares), layout, _ptr(out),
+                                              stream if stream is not None else _stream()))
+        return out
+
+    def mpc_relin_key_finish(self, round2_shares, round1_sum, stream=None):
+        import torch
+        rk = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
+        _check(self._lib.hegpu_mpc_relin_key_finish(self._h, self._share_array(round2_shares), len(round2_shares),
+                                                    _ptr(round1_sum), _ptr(rk),
+                                                    stream if stream is not None else _stream()))
+        return rk
+
+    def mpc_ckks_decrypt_share(self, rng, ct, ct_stride, sk, depth=0, batch=1, stream=None):
+        import torch
+        share = torch.empty(batch * (self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
+        _check(self._lib.hegpu_mpc_ckks_decrypt_share(self._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), depth, _ptr(share),
+                                                      batch, stream if stream is not None else _stream()))
+        return share
+
+    def mpc_ckks_decrypt_merge(self, ct, ct_stride, shares, depth=0, batch=1, stream=None):
+        import torch
+        plain = torch.empty(batch * (self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
+        _check(self._lib.hegpu_mpc_ckks_decrypt_merge(self._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares),
+                                                      depth, _ptr(plain), batch,
+                                                      stream if stream is not None else _stream()))
+        return plain
+
+    def mpc_bfv_decrypt_share(self, rng, ct, ct_stride, sk, batch=1, stream=None):
+        import torch
+        share = torch.empty(batch * self.Q_size * self.n, dtype=torch.int64, device="cuda")
+        _check(self._lib.hegpu_mpc_bfv_decrypt_share(self._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share), batch,
+                                                     stream if stream is not None else _stream()))
+        return share
+
+    def mpc_bfv_decrypt_merge(self, ct, ct_stride, shares, batch=1, stream=None):
+        import torch
+        plain = torch.empty(batch * self.n, dtype=torch.int64, device="cuda")
+        ws = self.workspace(OP_MPC_BFV_DECRYPT_MERGE, 0, batch)
+        _check(self._lib.hegpu_mpc_bfv_decrypt_merge(self._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares),
+                                                     _ptr(plain), batch, _ptr(ws), ws.numel() * ws.element_size(),
+                                                     stream if stream is not None else _stream()))
+        return plain
 
 
 GATE_NAND, GATE_AND, GATE_AND_FIRST_NOT, GATE_NOR, GATE_OR, GATE_XNOR, GATE_XOR, GATE_NOT = range(8)

@@ -1076,6 +1076,148 @@ int hegpu_bfv_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* sk
     });
 }
 
+// ------------------------------------------------------------------ N-out-of-N multiparty protocol
+#define CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes)                                                                 \
+    do {                                                                                                          \
+        CHECK_KG(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes);                                                       \
+        if (!(crs)) return fail(HEGPU_E_INVALID, "null common random generator");                                 \
+        if ((crs) == (rng))                                                                                       \
+            return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's errors are private"); \
+    } while (0)
+
+static int check_shares(const uint64_t* const* shares, int k, const void* out)
+{
+    if (!shares || k < 1) return fail(HEGPU_E_INVALID, "at least one share is needed");
+    for (int i = 0; i < k; i++) {
+        if (!shares[i]) return fail(HEGPU_E_INVALID, "null share");
+        if (shares[i] == out) return fail(HEGPU_E_INVALID, "the result must not be one of the shares");
+    }
+    return 0;
+}
+
+int hegpu_mpc_public_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, uint64_t* share,
+                               void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
+    return hip_ret(op_mpc_public_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, (u64*) share, (u64*) ws,
+                                           (hipStream_t) stream),
+                   "hegpu_mpc_public_key_share");
+}
+
+int hegpu_mpc_relin_key_share_round1(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk,
+                                     uint64_t* u_out, uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (!sk || !share || !u_out) return fail(HEGPU_E_INVALID, "null argument");
+    return hip_ret(op_mpc_switch_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, 0, (u64*) u_out, (u64*) share,
+                                           (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_relin_key_share_round1");
+}
+
+int hegpu_mpc_relin_key_share_round2(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* sk, const uint64_t* u,
+                                     const uint64_t* round1_sum, uint64_t* share, void* ws, size_t ws_bytes,
+                                     hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_KG(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes);
+    if (!sk || !u || !round1_sum || !share) return fail(HEGPU_E_INVALID, "null argument");
+    if (share == round1_sum) return fail(HEGPU_E_INVALID, "the share must not overwrite the round-1 sum");
+    return hip_ret(op_mpc_relin_key_share_round2(ctx->c, rng->r, (const u64*) sk, (const u64*) u,
+                                                 (const u64*) round1_sum, (u64*) share, (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_relin_key_share_round2");
+}
+
+int hegpu_mpc_galois_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, int galois_elt,
+                               uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
+    if (!(galois_elt & 1) || galois_elt <= 0 || galois_elt >= (int) (2 * ctx->c.n))
+        return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
+    return hip_ret(op_mpc_switch_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, galois_elt, nullptr, (u64*) share,
+                                           (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_galois_key_share");
+}
+
+int hegpu_mpc_accumulate(hegpu_context* ctx, const uint64_t* const* shares, int k, int layout, uint64_t* out,
+                         hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (!out) return fail(HEGPU_E_INVALID, "null argument");
+    if (layout != HEGPU_MPC_PUBLIC_KEY && layout != HEGPU_MPC_GALOIS_KEY && layout != HEGPU_MPC_RELIN_ROUND1)
+        return fail(HEGPU_E_INVALID, "unknown share layout");
+    if (const int rc = check_shares(shares, k, out)) return rc;
+    return hip_ret(op_mpc_accumulate(ctx->c, (const u64* const*) shares, k, layout, nullptr, (u64*) out,
+                                     (hipStream_t) stream),
+                   "hegpu_mpc_accumulate");
+}
+
+int hegpu_mpc_relin_key_finish(hegpu_context* ctx, const uint64_t* const* round2_shares, int k,
+                               const uint64_t* round1_sum, uint64_t* rk, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (!rk || !round1_sum) return fail(HEGPU_E_INVALID, "null argument");
+    if (rk == round1_sum) return fail(HEGPU_E_INVALID, "the key must not overwrite the round-1 sum");
+    if (const int rc = check_shares(round2_shares, k, rk)) return rc;
+    return hip_ret(op_mpc_accumulate(ctx->c, (const u64* const*) round2_shares, k, MPC_LAYOUT_RELIN_FINISH,
+                                     (const u64*) round1_sum, (u64*) rk, (hipStream_t) stream),
+                   "hegpu_mpc_relin_key_finish");
+}
+
+int hegpu_mpc_ckks_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
+                                 const uint64_t* sk, int depth, uint64_t* share, int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
+    if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
+    return hip_ret(op_mpc_ckks_decrypt_share(ctx->c, rng->r, (const u64*) ct, cs, (const u64*) sk, depth, (u64*) share,
+                                             batch, (hipStream_t) stream),
+                   "hegpu_mpc_ckks_decrypt_share");
+}
+
+int hegpu_mpc_ckks_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, const uint64_t* const* shares,
+                                 int k, int depth, uint64_t* plain, int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (!ct || !plain) return fail(HEGPU_E_INVALID, "null argument");
+    if (const int rc = check_shares(shares, k, plain)) return rc;
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    return hip_ret(op_mpc_ckks_decrypt_merge(ctx->c, (const u64*) ct, cs, (const u64* const*) shares, k, depth,
+                                             (u64*) plain, batch, (hipStream_t) stream),
+                   "hegpu_mpc_ckks_decrypt_merge");
+}
+
+int hegpu_mpc_bfv_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
+                                const uint64_t* sk, uint64_t* share, int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_BFV, 0, 0, batch, nullptr, 0);
+    if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
+    if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
+    return hip_ret(op_mpc_bfv_decrypt_share(ctx->c, rng->r, (const u64*) ct, cs, (const u64*) sk, (u64*) share, batch,
+                                            (hipStream_t) stream),
+                   "hegpu_mpc_bfv_decrypt_share");
+}
+
+int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, const uint64_t* const* shares,
+                                int k, uint64_t* plain, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (!ct || !plain) return fail(HEGPU_E_INVALID, "null argument");
+    if (const int rc = check_shares(shares, k, plain)) return rc;
+    CHECK_OP(ctx, SCHEME_BFV, OP_MPC_BFV_DECRYPT_MERGE, 0, batch, ws, ws_bytes);
+    return hip_ret(op_mpc_bfv_decrypt_merge(ctx->c, (const u64*) ct, cs, (const u64* const*) shares, k, (u64*) plain,
+                                            batch, (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_bfv_decrypt_merge");
+}
+
 int hegpu_bfv_encode(hegpu_context* ctx, const int64_t* message, int message_size, uint64_t* plain,
                      hegpu_stream stream)
 {

@@ -119,19 +119,26 @@ __device__ __forceinline__ u32 ntt_permutation(u32 index, u32 galois_elt, int n_
 // Method I: digits = Q, digit_width = 1, P = the one special prime; method II: digits of
 // digit_width primes (Sk_pair = y / width; special limbs belong to no digit), P = product of the
 // special primes, multiplied in one factor at a time like the reference.
+// With u != nullptr the same body writes a party's round-1 share of the collective relinearisation key
+// (multi_party_relinkey_piece_method_I / _II_stage_I_kernel :190-278):
+//   ( -(u * a_i) + e_i + [limb y belongs to digit i] * s * P  ,  s * a_i + e1_i ),
+// u the party's ephemeral ternary secret (NTT domain), a_i the parties' common randomness.
 __global__ __launch_bounds__(KG_THREADS) void k_kg_switchkey(u64* __restrict__ key, const u64* __restrict__ sk,
                                                              const u64* __restrict__ e, const u64* __restrict__ a,
                                                              const Mod* __restrict__ mods,
                                                              const u64* __restrict__ factor, int galois_elt,
-                                                             const u64* __restrict__ old_sk, int n_power, int limbs,
-                                                             int digits, int digit_width, int q_size, int p_size)
+                                                             const u64* __restrict__ old_sk,
+                                                             const u64* __restrict__ u, const u64* __restrict__ e1,
+                                                             int n_power, int limbs, int digits, int digit_width,
+                                                             int q_size, int p_size)
 {
     const u32 idx = blockIdx.x * KG_THREADS + threadIdx.x;
     const int y = blockIdx.y;
     const Mod m = mods[y];
     const u64 s = sk[idx + ((u64) y << n_power)];
-    const u64 sp = galois_elt ? sk[((u64) y << n_power) + ntt_permutation(idx, (u32) galois_elt, n_power)] : s;
-    u64 carried = old_sk ? old_sk[idx + ((u64) y << n_power)] : (galois_elt ? s : mul_barrett(s, s, m));
+    const u64 sp = u ? u[idx + ((u64) y << n_power)]
+                     : galois_elt ? sk[((u64) y << n_power) + ntt_permutation(idx, (u32) galois_elt, n_power)] : s;
+    u64 carried = old_sk ? old_sk[idx + ((u64) y << n_power)] : ((galois_elt || u) ? s : mul_barrett(s, s, m));
     const int own = (y < q_size) ? y / digit_width : -1;
     if (own >= 0)
         for (int j = 0; j < p_size; j++) carried = mul_barrett(carried, factor[j * q_size + y], m);
@@ -139,21 +146,26 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_switchkey(u64* __restrict__ k
         const u64 src = idx + ((u64) y << n_power) + ((u64) (limbs * i) << n_power);
         const u64 av = a[src];
         u64 k0 = mul_barrett(sp, av, m);
-        k0 = add_mod(k0, e[src], m.q);
-        k0 = sub_mod(0, k0, m.q);
+        if (u) { // round 1: the error is added to -(u * a), not negated with it (:210-212)
+            k0 = sub_mod(0, k0, m.q);
+            k0 = add_mod(k0, e[src], m.q);
+        } else {
+            k0 = add_mod(k0, e[src], m.q);
+            k0 = sub_mod(0, k0, m.q);
+        }
         if (i == own) k0 = add_mod(k0, carried, m.q);
         const u64 dst = idx + ((u64) y << n_power) + ((u64) (limbs * i) << (n_power + 1));
         key[dst] = k0;
-        key[dst + ((u64) limbs << n_power)] = av;
+        key[dst + ((u64) limbs << n_power)] = u ? add_mod(mul_barrett(av, s, m), e1[src], m.q) : av;
     }
 }
 
 hipError_t kg_switchkey(u64* key, const u64* sk, const u64* e, const u64* a, const Mod* mods, const u64* factor,
                         int galois_elt, const u64* old_sk, int n_power, int limbs, int digits, int digit_width,
-                        int q_size, int p_size, hipStream_t st)
+                        int q_size, int p_size, hipStream_t st, const u64* u, const u64* e1)
 {
     hipLaunchKernelGGL(k_kg_switchkey, dim3((1u << n_power) / KG_THREADS, limbs), dim3(KG_THREADS), 0, st, key, sk, e,
-                       a, mods, factor, galois_elt, old_sk, n_power, limbs, digits, digit_width, q_size, p_size);
+                       a, mods, factor, galois_elt, old_sk, u, e1, n_power, limbs, digits, digit_width, q_size, p_size);
     return hipGetLastError();
 }
 
@@ -317,29 +329,25 @@ hipError_t kg_coeff_multadd(const u64* ct0, const u64* x, u64* out, u64 t, const
     return hipGetLastError();
 }
 
-__global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_decryption(const u64* __restrict__ ct0,
-                                                                  const u64* __restrict__ ct1,
-                                                                  u64* __restrict__ plain,
-                                                                  const Mod* __restrict__ mods, BfvDecryptDev d,
-                                                                  int n_power, int limbs)
+// decryption_kernel (decryption.cu:44-120) in two steps: one limb of c0 + c1*s folded into the sums mod t and
+// mod gamma, then the scale-and-round from the two sums
+__device__ __forceinline__ void bfv_round_limb(u64 mt, int i, const Mod& m, const BfvDecryptDev& d, u64& sum_t,
+                                               u64& sum_g)
 {
-    const u32 idx = blockIdx.x * KG_THREADS + threadIdx.x;
     const u64 t = d.plain.q, g = d.gamma.q;
-    u64 sum_t = 0, sum_g = 0;
-    for (int i = 0; i < limbs; i++) {
-        const Mod m = mods[i];
-        const u64 loc = idx + ((u64) i << n_power);
-        u64 mt = add_mod(ct0[loc], ct1[loc], m.q);
-        const u64 g_i = reduce64(g, m);
-        mt = mul_barrett(mt, t, m);
-        mt = mul_barrett(mt, g_i, m);
-        mt = mul_barrett(mt, d.Qi_inverse[i], m);
-        u64 in_t = reduce64(mt, d.plain), in_g = reduce64(mt, d.gamma);
-        in_t = mul_barrett(in_t, d.Qi_t[i], d.plain);
-        in_g = mul_barrett(in_g, d.Qi_gamma[i], d.gamma);
-        sum_t = add_mod(sum_t, in_t, t);
-        sum_g = add_mod(sum_g, in_g, g);
-    }
+    const u64 g_i = reduce64(g, m);
+    mt = mul_barrett(mt, t, m);
+    mt = mul_barrett(mt, g_i, m);
+    mt = mul_barrett(mt, d.Qi_inverse[i], m);
+    u64 in_t = reduce64(mt, d.plain), in_g = reduce64(mt, d.gamma);
+    in_t = mul_barrett(in_t, d.Qi_t[i], d.plain);
+    in_g = mul_barrett(in_g, d.Qi_gamma[i], d.gamma);
+    sum_t = add_mod(sum_t, in_t, t);
+    sum_g = add_mod(sum_g, in_g, g);
+}
+__device__ __forceinline__ u64 bfv_round_finish(u64 sum_t, u64 sum_g, const BfvDecryptDev& d)
+{
+    const u64 t = d.plain.q, g = d.gamma.q;
     sum_t = mul_barrett(sum_t, d.mulq_inv_t, d.plain);
     sum_g = mul_barrett(sum_g, d.mulq_inv_gamma, d.gamma);
     u64 result;
@@ -353,7 +361,23 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_decryption(const u64* __r
         result = sub_mod(st, sg_t, t);
         result = mul_barrett(result, d.inv_gamma, d.plain);
     }
-    plain[idx] = result;
+    return result;
+}
+
+__global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_decryption(const u64* __restrict__ ct0,
+                                                                  const u64* __restrict__ ct1,
+                                                                  u64* __restrict__ plain,
+                                                                  const Mod* __restrict__ mods, BfvDecryptDev d,
+                                                                  int n_power, int limbs)
+{
+    const u32 idx = blockIdx.x * KG_THREADS + threadIdx.x;
+    u64 sum_t = 0, sum_g = 0;
+    for (int i = 0; i < limbs; i++) {
+        const Mod m = mods[i];
+        const u64 loc = idx + ((u64) i << n_power);
+        bfv_round_limb(add_mod(ct0[loc], ct1[loc], m.q), i, m, d, sum_t, sum_g);
+    }
+    plain[idx] = bfv_round_finish(sum_t, sum_g, d);
 }
 
 hipError_t kg_bfv_decryption(const u64* ct0, const u64* ct1s, u64* plain, const Mod* mods, const BfvDecryptDev& d,
@@ -528,6 +552,201 @@ hipError_t kg_negacyclic_shift(const u64* in, u64* out, const Mod* mods, int shi
 {
     hipLaunchKernelGGL(k_kg_negacyclic_shift, dim3((1u << n_power) / KG_THREADS, limbs, parts), dim3(KG_THREADS), 0, st,
                        in, out, mods, shift, n_power);
+    return hipGetLastError();
+}
+
+// ---- N-out-of-N multiparty protocol (host/{ckks,bfv}/mpcmanager.cu; keygeneration.cu:118-462, 861-894).
+// The public-key and Galois-key shares are k_kg_publickey / k_kg_switchkey with the parties' common `a`, the round-1
+// relinearisation share is k_kg_switchkey with u; what follows is the round-2 share, the k-way sums and the two
+// kernels of collective decryption.  All of them are HBM streams: two coefficients (16 bytes) per lane per array.
+#define KG_VEC 2
+typedef ulonglong2 u64x2;
+
+__device__ __forceinline__ u64x2 ld2(const u64* p) { return *reinterpret_cast<const u64x2*>(p); }
+__device__ __forceinline__ void st2(u64* p, u64x2 v) { *reinterpret_cast<u64x2*>(p) = v; }
+__device__ __forceinline__ u64x2 add2(u64x2 a, u64x2 b, u64 q) { return u64x2{add_mod(a.x, b.x, q), add_mod(a.y, b.y, q)}; }
+__device__ __forceinline__ u64x2 sub2(u64x2 a, u64x2 b, u64 q) { return u64x2{sub_mod(a.x, b.x, q), sub_mod(a.y, b.y, q)}; }
+__device__ __forceinline__ u64x2 mul2(u64x2 a, u64x2 b, const Mod& m)
+{
+    return u64x2{mul_barrett(a.x, b.x, m), mul_barrett(a.y, b.y, m)};
+}
+static inline dim3 vec_grid(int n_power, int y, int z) { return dim3((1u << n_power) / (KG_THREADS * KG_VEC), y, z); }
+
+// multi_party_relinkey_piece_method_I_II_stage_II_kernel (:280-319): from the summed round-1 shares (h0_d, h1_d)
+//   share_d = ( s * h0_d + e2_d ,  (u - s) * h1_d + e3_d );   e = [2][digits][limbs][N], e2 first
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_relin_round2(u64* __restrict__ share, const u64* __restrict__ h,
+                                                                    const u64* __restrict__ sk, const u64* __restrict__ u,
+                                                                    const u64* __restrict__ e,
+                                                                    const Mod* __restrict__ mods, int n_power, int limbs)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, i = blockIdx.z, digits = gridDim.z;
+    const Mod m = mods[y];
+    const u64 lane = n + ((u64) y << n_power);
+    const u64x2 s = ld2(sk + lane), us = sub2(ld2(u + lane), s, m.q);
+    const u64 key = lane + ((u64) (limbs * i) << (n_power + 1)), part = (u64) limbs << n_power;
+    const u64 err = lane + ((u64) (limbs * i) << n_power);
+    st2(share + key, add2(mul2(ld2(h + key), s, m), ld2(e + err), m.q));
+    st2(share + key + part, add2(mul2(ld2(h + key + part), us, m), ld2(e + err + (part * digits)), m.q));
+}
+
+hipError_t kg_mpc_relin_round2(u64* share, const u64* round1_sum, const u64* sk, const u64* u, const u64* e,
+                               const Mod* mods, int n_power, int limbs, int digits, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_relin_round2, vec_grid(n_power, limbs, digits), dim3(KG_THREADS), 0, st, share,
+                       round1_sum, sk, u, e, mods, n_power, limbs);
+    return hipGetLastError();
+}
+
+// threshold_pk_addition (:118-140), multi_party_relinkey_method_I_stage_I / _II_kernel (:321-462),
+// multi_party_galoiskey_method_I_II_kernel (:861-894): the reference adds one share per launch; here one launch reads
+// each of k <= KG_MPC_MAX_SHARES shares once and writes the sum once.  A unit (blockIdx.z) is [2][limbs][N]: the public
+// key, or one digit of a switching key.  Part 0 = carry + sum of the shares' parts 0 (fold: parts 0 and 1, the last
+// step of the relinearisation key); part 1 = carry + sum of the parts 1 (sum_second), a copy of `second`'s part 1
+// (second != nullptr), or left alone.  carry (may be `out`): the sum of an earlier group of shares.
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_accumulate(u64* out, MpcShares sh, int k, const u64* carry,
+                                                                  const u64* second, int fold, int sum_second,
+                                                                  const Mod* __restrict__ mods, int n_power, int limbs)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y;
+    const u64 q = mods[y].q;
+    const u64 part = (u64) limbs << n_power;
+    const u64 loc = n + ((u64) y << n_power) + 2 * part * blockIdx.z;
+    u64x2 a0 = carry ? ld2(carry + loc) : u64x2{0, 0};
+    u64x2 a1 = (carry && sum_second) ? ld2(carry + loc + part) : u64x2{0, 0};
+    for (int j = 0; j < k; j++) {
+        const u64* p = sh.p[j];
+        a0 = add2(a0, ld2(p + loc), q);
+        if (fold) a0 = add2(a0, ld2(p + loc + part), q);
+        if (sum_second) a1 = add2(a1, ld2(p + loc + part), q);
+    }
+    st2(out + loc, a0);
+    if (sum_second) st2(out + loc + part, a1);
+    else if (second) st2(out + loc + part, ld2(second + loc + part));
+}
+
+hipError_t kg_mpc_accumulate(u64* out, const u64* const* shares, int k, const u64* second, int fold, int sum_second,
+                             const Mod* mods, int n_power, int limbs, int units, hipStream_t st)
+{
+    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
+        MpcShares sh{};
+        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
+        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+        hipLaunchKernelGGL(k_kg_mpc_accumulate, vec_grid(n_power, limbs, units), dim3(KG_THREADS), 0, st, out, sh, cnt,
+                           done ? out : nullptr, done ? nullptr : second, fold, sum_second, mods, n_power, limbs);
+    }
+    return hipGetLastError();
+}
+
+// A party's share of a collective decryption, one per ciphertext of the batch (partial_decrypt_stage_1,
+// ckks/mpcmanager.cu:1483-1540: sk_multiplication, the error's NTT, `addition`, and a copy of c0 -- here the share is
+// h alone): h[b][y] = c1[b][y] * s[y] + h[b][y], where h comes in holding the transformed error (add) or nothing
+// (c1 may then be h itself)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride,
+                                                                     const u64* __restrict__ sk,
+                                                                     const Mod* __restrict__ mods, int n_power, int add)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, b = blockIdx.z;
+    const Mod m = mods[y];
+    const u64 lane = n + ((u64) y << n_power);
+    const u64 dst = lane + (((u64) gridDim.y * b) << n_power);
+    u64x2 v = mul2(ld2(c1 + lane + c1_stride * b), ld2(sk + lane), m);
+    if (add) v = add2(v, ld2(h + dst), m.q);
+    st2(h + dst, v);
+}
+
+hipError_t kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
+                                int limbs, int batch, int add, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_decrypt_share, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, h, c1,
+                       c1_stride, sk, mods, n_power, add);
+    return hipGetLastError();
+}
+
+// BFV shares live in the coefficient domain (bfv/mpcmanager.cu:1440-1519), where the error needs no transform: it
+// is drawn here, one value per (ciphertext, coefficient), and added to every limb of h = INTT(NTT(c1) * s)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_add_gaussian(u64* __restrict__ h, const Mod* __restrict__ mods,
+                                                                    int n_power, int limbs, DrbgKey seed, u64 stream,
+                                                                    GaussCdt cdt)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int b = blockIdx.y;
+    const int v0 = drbg_gaussian(seed, stream, ((u64) b << n_power) + n, cdt);
+    const int v1 = drbg_gaussian(seed, stream, ((u64) b << n_power) + n + 1, cdt);
+    for (int j = 0; j < limbs; j++) {
+        const u64 q = mods[j].q;
+        u64* p = h + (((u64) b * limbs + j) << n_power) + n;
+        st2(p, add2(ld2(p), u64x2{lift_small(v0, q), lift_small(v1, q)}, q));
+    }
+}
+
+hipError_t kg_mpc_add_gaussian(u64* h, const Mod* mods, int n_power, int limbs, int batch, DrbgKey seed, u64 stream,
+                               const GaussCdt& cdt, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_add_gaussian, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, h, mods, n_power,
+                       limbs, seed, stream, cdt);
+    return hipGetLastError();
+}
+
+// Collective decryption, the merge (partial_decrypt_stage_2, ckks/mpcmanager.cu:1542-1573: k `addition` launches
+// over a temporary): m[b][y] = c0[b][y] + sum_j h_j[b][y] in one launch; shares [batch][limbs][N] each
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, MpcShares sh,
+                                                             int k, const Mod* __restrict__ mods, int n_power)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, b = blockIdx.z;
+    const u64 q = mods[y].q;
+    const u64 lane = n + ((u64) y << n_power);
+    const u64 dst = lane + (((u64) gridDim.y * b) << n_power);
+    u64x2 acc = ld2(c0 + lane + c0_stride * b);
+    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + dst), q);
+    st2(plain + dst, acc);
+}
+
+hipError_t kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
+                        int n_power, int limbs, int batch, hipStream_t st)
+{
+    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
+        MpcShares sh{};
+        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
+        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+        hipLaunchKernelGGL(k_kg_mpc_merge, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, plain,
+                           done ? plain : c0, done ? ((u64) limbs << n_power) : c0_stride, sh, cnt, mods, n_power);
+    }
+    return hipGetLastError();
+}
+
+// BFV: the same sum feeding the scale-and-round stage of k_kg_bfv_decryption (bfv/mpcmanager.cu:1521-1561 runs k
+// `addition` launches, then decryption_fusion_bfv_kernel); plain [batch][N] mod t
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_bfv_merge(u64* __restrict__ plain, const u64* __restrict__ c0,
+                                                                 u64 c0_stride, MpcShares sh, int k,
+                                                                 const Mod* __restrict__ mods, BfvDecryptDev d,
+                                                                 int n_power, int limbs)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int b = blockIdx.y;
+    u64 t0 = 0, g0 = 0, t1 = 0, g1 = 0;
+    for (int i = 0; i < limbs; i++) {
+        const Mod m = mods[i];
+        const u64 lane = n + ((u64) i << n_power);
+        const u64 src = lane + (((u64) limbs * b) << n_power);
+        u64x2 acc = ld2(c0 + lane + c0_stride * b);
+        for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + src), m.q);
+        bfv_round_limb(acc.x, i, m, d, t0, g0);
+        bfv_round_limb(acc.y, i, m, d, t1, g1);
+    }
+    st2(plain + ((u64) b << n_power) + n, u64x2{bfv_round_finish(t0, g0, d), bfv_round_finish(t1, g1, d)});
+}
+
+hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
+                            const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st)
+{
+    MpcShares sh{};
+    for (int j = 0; j < k; j++) sh.p[j] = shares[j];
+    hipLaunchKernelGGL(k_kg_mpc_bfv_merge, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0, c0_stride,
+                       sh, k, mods, d, n_power, limbs);
     return hipGetLastError();
 }
 

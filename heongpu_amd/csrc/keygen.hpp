@@ -24,9 +24,12 @@ hipError_t kg_publickey(u64* pk, const u64* sk, const u64* e, const u64* a, cons
 // relinkey_gen_kernel / galoiskey_gen_kernel (keygeneration.cu:145-185, 757-805), method I:
 // key[d][0][j] = -(s'_j * a_dj + e_dj) + (d == j) * factor_j * t_j,  key[d][1][j] = a_dj with
 // (s', t) = (s, s*s) for relinearisation, (sigma_g(s), s) for a Galois key (galois_elt != 0)
+// u != nullptr: a party's round-1 share of the collective relinearisation key instead
+// (multi_party_relinkey_piece_method_I / _II_stage_I_kernel, keygeneration.cu:190-278):
+// key[d][0][j] = -(u_j * a_dj) + e_dj + [j in digit d] * factor_j * s_j,  key[d][1][j] = s_j * a_dj + e1_dj
 hipError_t kg_switchkey(u64* key, const u64* sk, const u64* e, const u64* a, const Mod* mods, const u64* factor,
                         int galois_elt, const u64* old_sk, int n_power, int limbs, int digits, int digit_width,
-                        int q_size, int p_size, hipStream_t st);
+                        int q_size, int p_size, hipStream_t st, const u64* u = nullptr, const u64* e1 = nullptr);
 // pk_u_kernel (encryption.cu:10-26): out[z][j] = pk[z][j] * u[j]
 hipError_t kg_pk_u(const u64* pk, const u64* u, u64* out, const Mod* mods, int n_power, int limbs, hipStream_t st);
 // cipher_message_add_kernel (encryption.cu:254-267): ct[0][j] += plain[j]
@@ -61,6 +64,34 @@ struct BfvDecryptDev {
 // decryption_kernel (decryption.cu:44-120): plain [N] from c0 and c1*s, both [Q][N] coefficient domain
 hipError_t kg_bfv_decryption(const u64* ct0, const u64* ct1s, u64* plain, const Mod* mods, const BfvDecryptDev& d,
                              int n_power, int limbs, hipStream_t st);
+
+// ---- N-out-of-N multiparty protocol (host/{ckks,bfv}/mpcmanager.cu)
+// share pointers travel as a kernel argument; more shares than this take one launch per group
+#define KG_MPC_MAX_SHARES 16
+struct MpcShares {
+    const u64* p[KG_MPC_MAX_SHARES];
+};
+// multi_party_relinkey_piece_method_I_II_stage_II_kernel (keygeneration.cu:280-319): share [digits][2][limbs][N]
+// from the summed round-1 shares; e [2][digits][limbs][N] NTT domain
+hipError_t kg_mpc_relin_round2(u64* share, const u64* round1_sum, const u64* sk, const u64* u, const u64* e,
+                               const Mod* mods, int n_power, int limbs, int digits, hipStream_t st);
+// k-way modular sum of shares of `units` x [2][limbs][N] (HOST array of device pointers).  Part 0: sum of the parts 0
+// (fold: of parts 0 and 1); part 1: sum of the parts 1 (sum_second), else part 1 of `second` if given
+// (threshold_pk_addition :118-140, multi_party_relinkey_method_I_stage_I / _II_kernel :321-462)
+hipError_t kg_mpc_accumulate(u64* out, const u64* const* shares, int k, const u64* second, int fold, int sum_second,
+                             const Mod* mods, int n_power, int limbs, int units, hipStream_t st);
+// h[b] = c1[b] * s (+ h[b] when add: h holds the transformed error), h [batch][limbs][N], c1 of item b at c1 + b*stride
+hipError_t kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
+                                int limbs, int batch, int add, hipStream_t st);
+// h[b][j] += one rounded Gaussian per (b, coefficient), coefficient domain
+hipError_t kg_mpc_add_gaussian(u64* h, const Mod* mods, int n_power, int limbs, int batch, DrbgKey seed, u64 stream,
+                               const GaussCdt& cdt, hipStream_t st);
+// plain[b] = c0[b] + sum of the k shares' item b; plain and shares [batch][limbs][N]
+hipError_t kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
+                        int n_power, int limbs, int batch, hipStream_t st);
+// the same sum followed by decryption_kernel's scale-and-round; k <= KG_MPC_MAX_SHARES, plain [batch][N] mod t
+hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
+                            const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st);
 
 // encode_kernel_bfv / decode_kernel_bfv (encoding.cu:11-41): slot idx <-> position location[idx]
 hipError_t kg_bfv_encode_scatter(u64* out, const long long* message, const int* location, u64 t, int message_size,

@@ -190,6 +190,8 @@ size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
         case OP_BFV_MULTIPLY_PLAIN: per = (u64) Q * n; break;        // lifted + transformed plaintext
         case OP_CKKS_ENCODE: per = n; break;                         // N/2 complex doubles
         case OP_CKKS_DECODE: per = (u64) (l + 1) * n; break;         // coefficient-domain copy + complex
+        case OP_MPC_KEY_SHARE: per = (u64) 3 * Q * Qp * n; break;    // relin round 1: e0, e1, a per digit (the largest)
+        case OP_MPC_BFV_DECRYPT_MERGE: per = (u64) Q * n; break;     // c0 + the shares beyond the first group
         default: return 0;
     }
     return per * (u64) batch;
@@ -860,7 +862,7 @@ hipError_t op_gen_switch_key(const Context& c, Rng& r, const u64* sk, int galois
     const int Q = c.Q_size, Qp = c.Qp_size;
     // method I: one digit per ciphertext prime; method II: the depth-0 digit partition
     // (ckks/keygenerator.cu:326-414 uses d_leveled[0] and Sk_pair_leveled[0])
-    const int d = c.P_size == 1 ? Q : c.m2_levels[0].d;
+    const int d = switch_key_digits(c);
     const int width = c.P_size == 1 ? 1 : c.m2_width;
     u64* e = ws;
     u64* av = ws + (u64) d * Qp * c.n;
@@ -914,6 +916,18 @@ hipError_t op_bfv_encrypt(const Context& c, Rng& r, const u64* pk, const u64* pl
                               c.hv.upper_threshold, c.plain_modulus, c.n_power, c.Q_size, st);
 }
 
+static BfvDecryptDev bfv_decrypt_dev(const Context& c)
+{
+    BfvDecryptDev d{};
+    d.plain = make_mod(c.plain_modulus);
+    d.gamma = make_mod(c.hv.gamma);
+    d.Qi_t = c.tab.Qi_t; d.Qi_gamma = c.tab.Qi_gamma; d.Qi_inverse = c.tab.Qi_inverse;
+    d.mulq_inv_t = c.hv.mulq_inv_t;
+    d.mulq_inv_gamma = c.hv.mulq_inv_gamma;
+    d.inv_gamma = c.hv.inv_gamma;
+    return d;
+}
+
 hipError_t op_bfv_decrypt(const Context& c, const u64* ct, const u64* sk, u64* plain, u64* ws, hipStream_t st)
 {
     const int np = c.n_power, Q = c.Q_size;
@@ -925,14 +939,7 @@ hipError_t op_bfv_decrypt(const Context& c, const u64* ct, const u64* sk, u64* p
     TRY(kg_sk_multiplication(t1, sk, t1, c.plan_qp.mods, np, Q, st));                      // :65
     a.in = t1; a.out = t1;
     TRY(ntt_launch(a, Q, true, st));                                                       // :101
-    BfvDecryptDev d{};
-    d.plain = make_mod(c.plain_modulus);
-    d.gamma = make_mod(c.hv.gamma);
-    d.Qi_t = c.tab.Qi_t; d.Qi_gamma = c.tab.Qi_gamma; d.Qi_inverse = c.tab.Qi_inverse;
-    d.mulq_inv_t = c.hv.mulq_inv_t;
-    d.mulq_inv_gamma = c.hv.mulq_inv_gamma;
-    d.inv_gamma = c.hv.inv_gamma;
-    return kg_bfv_decryption(ct, t1, plain, c.plan_qp.mods, d, np, Q, st);                 // :107
+    return kg_bfv_decryption(ct, t1, plain, c.plan_qp.mods, bfv_decrypt_dev(c), np, Q, st); // :107
 }
 
 hipError_t op_bfv_noise_rns(const Context& c, const u64* ct, const u64* sk, u64* out, hipStream_t st)
@@ -1053,6 +1060,118 @@ hipError_t op_ckks_decrypt(const Context& c, const u64* ct, const u64* sk, int d
     const int l = c.Q_size - depth;
     if (l < 1) return hipErrorInvalidValue;
     return kg_sk_multiplication_ckks(ct, plain, sk, c.plan_qp.mods, c.n_power, l, st);
+}
+
+// ------------------------------------------------------------------ N-out-of-N multiparty protocol
+// `crs` is the generator every party seeds identically (the common `a` polynomials, public); `r` is the party's own.
+// Both advance by one stream id per sampling call, so parties that make the same calls in the same order draw the
+// same `a`.
+int switch_key_digits(const Context& c) { return c.P_size == 1 ? c.Q_size : c.m2_levels[0].d; }
+
+hipError_t op_mpc_public_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, u64* share, u64* ws,
+                                   hipStream_t st)
+{
+    const int Qp = c.Qp_size;
+    u64* e = ws;
+    u64* av = ws + (u64) Qp * c.n;
+    TRY(kg_uniform(av, c.plan_qp.mods, c.n_power, Qp, 1, crs.seed, crs.stream++, st));
+    TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 1, r.seed, r.stream++, c.gauss_cdt, st));
+    NttArgs a = c.ntt_args(0);
+    a.in = e; a.out = e; a.mod_count = Qp;
+    TRY(ntt_launch(a, Qp, false, st));
+    return kg_publickey(share, sk, e, av, c.plan_qp.mods, c.n_power, Qp, st);
+}
+
+hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, int galois_elt, u64* u_out,
+                                   u64* share, u64* ws, hipStream_t st)
+{
+    const int Q = c.Q_size, Qp = c.Qp_size, d = switch_key_digits(c);
+    const int width = c.P_size == 1 ? 1 : c.m2_width;
+    const int errs = u_out ? 2 : 1; // round 1 of the relinearisation key carries an error in both parts
+    u64* e = ws;                                  // [errs][d][Q'][N]
+    u64* av = ws + (u64) errs * d * Qp * c.n;     // [d][Q'][N]
+    const Mod* mods = c.plan_qp.mods;
+    TRY(kg_uniform(av, mods, c.n_power, Qp, d, crs.seed, crs.stream++, st));
+    TRY(kg_gaussian(e, mods, c.n_power, Qp, errs * d, r.seed, r.stream++, c.gauss_cdt, st));
+    NttArgs a = c.ntt_args(0);
+    a.in = e; a.out = e; a.mod_count = Qp;
+    TRY(ntt_launch(a, errs * d * Qp, false, st));
+    if (u_out) {
+        TRY(kg_ternary(u_out, mods, c.n_power, Qp, 1, r.seed, r.stream++, st));
+        a.in = u_out; a.out = u_out;
+        TRY(ntt_launch(a, Qp, false, st));
+    }
+    const int inv = galois_elt ? (int) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0;
+    return kg_switchkey(share, sk, e, av, mods, c.tab.factor, inv, nullptr, c.n_power, Qp, d, width, Q, c.P_size, st,
+                        u_out, u_out ? e + (u64) d * Qp * c.n : nullptr);
+}
+
+hipError_t op_mpc_relin_key_share_round2(const Context& c, Rng& r, const u64* sk, const u64* u, const u64* round1_sum,
+                                         u64* share, u64* ws, hipStream_t st)
+{
+    const int Qp = c.Qp_size, d = switch_key_digits(c);
+    u64* e = ws; // [2][d][Q'][N]
+    TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 2 * d, r.seed, r.stream++, c.gauss_cdt, st));
+    NttArgs a = c.ntt_args(0);
+    a.in = e; a.out = e; a.mod_count = Qp;
+    TRY(ntt_launch(a, 2 * d * Qp, false, st));
+    return kg_mpc_relin_round2(share, round1_sum, sk, u, e, c.plan_qp.mods, c.n_power, Qp, d, st);
+}
+
+hipError_t op_mpc_accumulate(const Context& c, const u64* const* shares, int k, int layout, const u64* round1_sum,
+                             u64* out, hipStream_t st)
+{
+    const int units = layout == MPC_LAYOUT_PUBLIC_KEY ? 1 : switch_key_digits(c);
+    const bool finish = layout == MPC_LAYOUT_RELIN_FINISH;
+    return kg_mpc_accumulate(out, shares, k, finish ? round1_sum : shares[0], finish, layout == MPC_LAYOUT_RELIN_ROUND1,
+                             c.plan_qp.mods, c.n_power, c.Qp_size, units, st);
+}
+
+hipError_t op_mpc_ckks_decrypt_share(const Context& c, Rng& r, const u64* ct, u64 cs, const u64* sk, int depth,
+                                     u64* share, int batch, hipStream_t st)
+{
+    const int l = c.Q_size - depth;
+    const Mod* mods = c.plan_qp.mods;
+    TRY(kg_gaussian(share, mods, c.n_power, l, batch, r.seed, r.stream++, c.gauss_cdt, st));   // :1510
+    NttArgs a = c.ntt_args(0);
+    a.in = share; a.out = share; a.mod_count = l;
+    TRY(ntt_launch(a, batch * l, false, st));                                                  // :1524
+    return kg_mpc_decrypt_share(share, ct + ((u64) l << c.n_power), cs, sk, mods, c.n_power, l, batch, 1, st);
+}
+
+hipError_t op_mpc_bfv_decrypt_share(const Context& c, Rng& r, const u64* ct, u64 cs, const u64* sk, u64* share,
+                                    int batch, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    NttArgs a = c.ntt_args(0);
+    a.in = ct + ((u64) Q << np); a.out = share; a.mod_count = Q;
+    a.polys_per_item = Q; a.in_item_stride = cs; a.out_item_stride = (u64) Q << np;
+    TRY(ntt_launch(a, batch * Q, false, st));                                                  // :1461
+    TRY(kg_mpc_decrypt_share(share, share, (u64) Q << np, sk, mods, np, Q, batch, 0, st));     // :1465
+    a.in = share; a.polys_per_item = 0;
+    TRY(ntt_launch(a, batch * Q, true, st));                                                   // :1492
+    return kg_mpc_add_gaussian(share, mods, np, Q, batch, r.seed, r.stream++, c.gauss_cdt, st); // :1499-1510
+}
+
+hipError_t op_mpc_ckks_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
+                                     int depth, u64* plain, int batch, hipStream_t st)
+{
+    return kg_mpc_merge(plain, ct, cs, shares, k, c.plan_qp.mods, c.n_power, c.Q_size - depth, batch, st);
+}
+
+hipError_t op_mpc_bfv_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
+                                    u64* plain, int batch, u64* ws, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    if (k > KG_MPC_MAX_SHARES) { // everything but the last group is summed into ws first
+        const int head = (k - 1) / KG_MPC_MAX_SHARES * KG_MPC_MAX_SHARES;
+        TRY(kg_mpc_merge(ws, ct, cs, shares, head, mods, np, Q, batch, st));
+        return kg_mpc_bfv_merge(plain, ws, (u64) Q << np, shares + head, k - head, mods, bfv_decrypt_dev(c), np, Q,
+                                batch, st);
+    }
+    return kg_mpc_bfv_merge(plain, ct, cs, shares, k, mods, bfv_decrypt_dev(c), np, Q, batch, st);
 }
 
 } // namespace hegpu

@@ -8,7 +8,8 @@ namespace hegpu {
 enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIPLY = 4, OP_BFV_RELIN = 5,
        OP_BFV_GALOIS = 6, OP_KEYGEN_SECRET = 7, OP_KEYGEN_PUBLIC = 8, OP_KEYGEN_SWITCH = 9, OP_CKKS_ENCRYPT = 10, OP_BFV_ENCRYPT = 11,
        OP_BFV_DECRYPT = 12, OP_BFV_DECODE = 13, OP_CKKS_ENCODE = 14,
-       OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17 };
+       OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17, OP_MPC_KEY_SHARE = 18,
+       OP_MPC_BFV_DECRYPT_MERGE = 19 };
 
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
@@ -89,5 +90,36 @@ hipError_t op_ckks_encode(const Context& c, int mode, const double* message, int
                           double scale, u64* plain, u64* ws, hipStream_t st);
 hipError_t op_ckks_decode(const Context& c, int mode, const u64* plain, int depth, double scale, double* message,
                           u64* ws, hipStream_t st);
+
+// ---- N-out-of-N multiparty protocol (host/{ckks,bfv}/mpcmanager.cu).  crs: the generator all parties seed alike
+// (draws the common `a`); r: the party's own (errors, u).  Shares have the layout of the key they sum to.
+enum { MPC_LAYOUT_PUBLIC_KEY = 0, MPC_LAYOUT_GALOIS_KEY = 1, MPC_LAYOUT_RELIN_ROUND1 = 2, MPC_LAYOUT_RELIN_FINISH = 3 };
+// digits of a key-switching key: Q (method I) or the depth-0 digit partition (method II)
+int switch_key_digits(const Context& c);
+// generate_public_key_stage1 (ckks/mpcmanager.cu:36-90): share [2][Q'][N] = (-(a*s_i + e_i), a)
+hipError_t op_mpc_public_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, u64* share, u64* ws,
+                                   hipStream_t st);
+// u_out == nullptr: generate_galois_key_method_I / _II_stage_1 (:751-1308), today's Galois key with the common a
+// (galois_elt != 0).  u_out != nullptr: generate_relin_key_method_I_stage_1 / _II_stage_1 (:121-229, :346-462), round 1 of the
+// relinearisation key; u_out [Q'][N] receives the party's ephemeral secret u_i (NTT domain), needed again in round 2
+hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, int galois_elt, u64* u_out,
+                                   u64* share, u64* ws, hipStream_t st);
+// generate_relin_key_method_I_stage_3 / _II_stage_3 (:231-344, :464-582)
+hipError_t op_mpc_relin_key_share_round2(const Context& c, Rng& r, const u64* sk, const u64* u, const u64* round1_sum,
+                                         u64* share, u64* ws, hipStream_t st);
+// generate_public_key_stage2, generate_relin_key_stage_2 / _stage_4, generate_galois_key_stage_2 (:92-119, :584-749,
+// :1310-1481); shares: HOST array of k device pointers; round1_sum only for MPC_LAYOUT_RELIN_FINISH
+hipError_t op_mpc_accumulate(const Context& c, const u64* const* shares, int k, int layout, const u64* round1_sum,
+                             u64* out, hipStream_t st);
+// partial_decrypt_stage_1 / _stage_2 (ckks/mpcmanager.cu:1483-1573, bfv/mpcmanager.cu:1440-1561); share
+// [batch][Q - depth][N] (the h_i alone), plain [batch][Q - depth][N] (CKKS) or [batch][N] (BFV)
+hipError_t op_mpc_ckks_decrypt_share(const Context& c, Rng& r, const u64* ct, u64 cs, const u64* sk, int depth,
+                                     u64* share, int batch, hipStream_t st);
+hipError_t op_mpc_bfv_decrypt_share(const Context& c, Rng& r, const u64* ct, u64 cs, const u64* sk, u64* share,
+                                    int batch, hipStream_t st);
+hipError_t op_mpc_ckks_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
+                                     int depth, u64* plain, int batch, hipStream_t st);
+hipError_t op_mpc_bfv_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
+                                    u64* plain, int batch, u64* ws, hipStream_t st);
 
 } // namespace hegpu

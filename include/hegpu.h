@@ -267,7 +267,9 @@ enum {
     HEGPU_OP_CKKS_ENCODE = 14,
     HEGPU_OP_CKKS_DECODE = 15, /* depth-dependent */
     HEGPU_OP_BFV_MULTIPLY_PLAIN = 16,
-    HEGPU_OP_CKKS_ROTATE_HOISTED = 17 /* hegpu_ckks_rotate_hoisted with room for four accumulators */
+    HEGPU_OP_CKKS_ROTATE_HOISTED = 17, /* hegpu_ckks_rotate_hoisted with room for four accumulators */
+    HEGPU_OP_MPC_KEY_SHARE = 18,        /* every hegpu_mpc_*_key_share* entry */
+    HEGPU_OP_MPC_BFV_DECRYPT_MERGE = 19 /* per ciphertext of the batch */
 };
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch);
 
@@ -372,6 +374,74 @@ int hegpu_bfv_encrypt(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* pk, co
  * coefficient-domain 2-part ciphertext, plain [N] mod t.  Workspace HEGPU_OP_BFV_DECRYPT. */
 int hegpu_bfv_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* sk, uint64_t* plain, void* ws,
                       size_t ws_bytes, hegpu_stream stream);
+
+/* ---- N-out-of-N multiparty protocol: collective key generation and decryption ----
+ * HEMultiPartyManager<CKKS|BFV> (src/lib/host/{ckks,bfv}/mpcmanager.cu, kernel/keygeneration.cu:118-462, 861-894).
+ * Every party i holds a secret key s_i; the collective keys are keys under s = sum of the s_i and have exactly the
+ * layout of hegpu_generate_public_key / _relin_key / _galois_key, so the evaluator takes them unchanged.  Nobody ever
+ * holds s.  Shares are plain device buffers; moving them between parties is the caller's business.
+ *   crs  the generator EVERY party seeds identically (public): it draws the common `a` polynomials.  Parties must
+ *        make the same crs calls in the same order.
+ *   rng  the party's PRIVATE generator: errors and the ephemeral secret u_i.
+ * crs and rng must be different objects (HEGPU_E_INVALID otherwise: a private error drawn from the public stream
+ * would hand s_i to everyone).  All polynomials NTT domain over Q' = Q u P unless said otherwise.
+ * SECURITY: as in the reference, a decryption share carries only a fresh sigma = 3.2 error and NO smudging noise;
+ * shares of many decryptions of related ciphertexts leak about s_i.  Key-share workspaces:
+ * hegpu_workspace_bytes(ctx, HEGPU_OP_MPC_KEY_SHARE, 0, 1). */
+/* generate_public_key_stage1 (ckks/mpcmanager.cu:36-90, bfv :21-75; publickey_gen_kernel with the common a):
+ * share [2][Q'][N] = (-(a * s_i + e_i), a) */
+int hegpu_mpc_public_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, uint64_t* share,
+                               void* ws, size_t ws_bytes, hegpu_stream stream);
+/* generate_relin_key_method_I_stage_1 / _II_stage_1 (ckks/mpcmanager.cu:121-229, 346-462, bfv :108-216, 334-443;
+ * multi_party_relinkey_piece_method_I / _II_stage_I_kernel keygeneration.cu:190-278).  Round 1, per digit d with
+ * gadget term w_d: share [d][2][Q'][N] = (-(u_i * a_d) + s_i * w_d + e0, s_i * a_d + e1).  u_out [Q'][N] receives
+ * the party's ephemeral ternary secret u_i: keep it private, hand it to round 2, then discard it. */
+int hegpu_mpc_relin_key_share_round1(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk,
+                                     uint64_t* u_out, uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream);
+/* generate_relin_key_method_I_stage_3 / _II_stage_3 (ckks/mpcmanager.cu:231-344, 464-582;
+ * multi_party_relinkey_piece_method_I_II_stage_II_kernel keygeneration.cu:280-319).  Round 2 from round1_sum =
+ * hegpu_mpc_accumulate(HEGPU_MPC_RELIN_ROUND1) = (h0_d, h1_d): share = (s_i * h0_d + e2, (u_i - s_i) * h1_d + e3) */
+int hegpu_mpc_relin_key_share_round2(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* sk, const uint64_t* u,
+                                     const uint64_t* round1_sum, uint64_t* share, void* ws, size_t ws_bytes,
+                                     hegpu_stream stream);
+/* generate_galois_key_method_I / _II_stage_1, one element (ckks/mpcmanager.cu:751-1308, bfv :724-1263):
+ * hegpu_generate_galois_key for s_i with the common a_d; share [d][2][Q'][N] */
+int hegpu_mpc_galois_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, int galois_elt,
+                               uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream);
+/* generate_public_key_stage2, generate_relin_key_stage_2, generate_galois_key_stage_2 (ckks/mpcmanager.cu:92-119,
+ * 584-657, 1310-1481; threshold_pk_addition, multi_party_relinkey_method_I_stage_I_kernel,
+ * multi_party_galoiskey_method_I_II_kernel keygeneration.cu:118-140, 321-403, 861-894 -- one launch per share
+ * there, one launch for up to 16 shares here).  shares: HOST array of k >= 1 DEVICE pointers; out must be none of them.
+ *   HEGPU_MPC_PUBLIC_KEY    pk = (sum share_i[0], a)               out [2][Q'][N]
+ *   HEGPU_MPC_GALOIS_KEY    gk_d = (sum share_i[d][0], a_d)        out [d][2][Q'][N]
+ *   HEGPU_MPC_RELIN_ROUND1  (h0_d, h1_d) = sums of both parts      out [d][2][Q'][N] */
+enum { HEGPU_MPC_PUBLIC_KEY = 0, HEGPU_MPC_GALOIS_KEY = 1, HEGPU_MPC_RELIN_ROUND1 = 2 };
+int hegpu_mpc_accumulate(hegpu_context* ctx, const uint64_t* const* shares, int k, int layout, uint64_t* out,
+                         hegpu_stream stream);
+/* generate_relin_key_stage_4 (ckks/mpcmanager.cu:659-749; multi_party_relinkey_method_I_stage_II_kernel
+ * keygeneration.cu:405-462): rk_d = (sum_i (share2_i[d][0] + share2_i[d][1]), h1_d), so that
+ * rk_d[0] + s * rk_d[1] = s^2 * w_d + noise, the relation hegpu_generate_relin_key's keys satisfy */
+int hegpu_mpc_relin_key_finish(hegpu_context* ctx, const uint64_t* const* round2_shares, int k,
+                               const uint64_t* round1_sum, uint64_t* rk, hegpu_stream stream);
+/* Collective decryption of 2-part ciphertexts, batched: item b of ct at ct + b * ct_stride.
+ * partial_decrypt_stage_1 (ckks/mpcmanager.cu:1483-1539: product, error, NTT, `addition`, copy of c0 -- five
+ * launches and a 2-part result): share [batch][Q - depth][N], item b = h_i = c1_b * s_i + NTT(e_b) ALONE (half the
+ * reference's share; c0 stays with the ciphertext), every item with an error of its own.
+ * partial_decrypt_stage_2 (:1541-1573: k `addition` launches over a temporary): plain [batch][Q - depth][N], item b =
+ * c0_b + sum_i share_i[b], one launch for up to 16 shares.  shares: HOST array of k >= 1 DEVICE pointers. */
+int hegpu_mpc_ckks_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t ct_stride,
+                                 const uint64_t* sk, int depth, uint64_t* share, int batch, hegpu_stream stream);
+int hegpu_mpc_ckks_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride,
+                                 const uint64_t* const* shares, int k, int depth, uint64_t* plain, int batch,
+                                 hegpu_stream stream);
+/* The same for BFV (bfv/mpcmanager.cu:1440-1519, 1521-1561), coefficient-domain ciphertexts: share [batch][Q][N],
+ * item b = INTT(NTT(c1_b) * s_i) + e_b; plain [batch][N] mod t = the scale-and-round of hegpu_bfv_decrypt applied
+ * to c0_b + sum_i share_i[b] in the same launch.  Workspace HEGPU_OP_MPC_BFV_DECRYPT_MERGE (used beyond 16 shares). */
+int hegpu_mpc_bfv_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t ct_stride,
+                                const uint64_t* sk, uint64_t* share, int batch, hegpu_stream stream);
+int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride,
+                                const uint64_t* const* shares, int k, uint64_t* plain, int batch, void* ws,
+                                size_t ws_bytes, hegpu_stream stream);
 
 /* HEEncoder<BFV>::encode_bfv / decode_bfv (src/lib/host/bfv/encoder.cu:21-95, 213-249,
  * kernel/encoding.cu:11-41): batching over the slots of Z_t[X]/(X^N+1).  message: device int64

@@ -25,6 +25,7 @@
 #if defined(HEONGPU_CUDA_NAMES)
 #include "cuda_names.hpp" // lets unmodified consumers of the reference (benchmark/*.cpp) use their cuda* calls
 #endif
+#include <cerrno>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -46,6 +47,7 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include <sys/random.h> // RNGSeed: getrandom
 
 // Names that the reference's public headers bring into the global namespace from GPU-NTT /
 // GPU-FFT (thirdparty, unvendored) and that its consumers use unqualified (test/test_bfv_*.cpp:
@@ -2716,6 +2718,334 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         out.memory_set(std::move(m));
     }
     HEContext<S> context_;
+};
+
+// ------------------------------------------------------------------ N-out-of-N multiparty protocol
+// host/{ckks,bfv}/mpcmanager.cuh, util/random.cuh:23-50.  Every party runs a manager of its own next to its secret key;
+// the shares travel between parties as the Multiparty* objects below (plain keys with the common seed attached).
+//
+// RNGSeed: the seed all parties agree on (public).  The reference feeds key / nonce / personalisation string to its
+// AES-CTR DRBG; here they are expanded into the 256-bit ChaCha20 key of hegpu_rng_create_seeded: the byte string
+//   label || len(key) || key || len(nonce) || nonce || len(pers) || pers        (lengths as 8 bytes, little endian)
+// is cut into 32-byte blocks B_0, B_1, ... (zero padded); K_0 = 0, and K_{j+1} = the first 256 bits of the ChaCha20
+// stream (hegpu_drbg_block, stream j, indices 0 and 1) under the key K_j xor B_j.  `label` names the kind of key
+// ("pk", "rk", "gk" + the Galois element), so that the `a` of one collective key is never reused for another although
+// the parties pass the same RNGSeed to all of them.  The result only has to be the same for every party and look
+// uniform: the `a` polynomials are public.
+struct RNGSeed {
+    std::vector<unsigned char> key_, nonce_, personalization_string_;
+    RNGSeed() : key_(16), nonce_(8) // 128 + 64 bits from the operating system
+    {
+        fill(key_);
+        fill(nonce_);
+    }
+    RNGSeed(const std::vector<unsigned char>& key, const std::vector<unsigned char>& nonce,
+            const std::vector<unsigned char>& personalization_string)
+        : key_(key), nonce_(nonce), personalization_string_(personalization_string)
+    {
+        if (key_.size() < 16) throw std::invalid_argument("Invalid key size!");
+    }
+    // the generator of the common polynomials for one kind of key (caller destroys it)
+    hegpu_rng* expand(const std::string& label) const
+    {
+        std::vector<unsigned char> in(label.begin(), label.end());
+        for (const auto* part : {&key_, &nonce_, &personalization_string_}) {
+            const std::uint64_t len = part->size();
+            for (int i = 0; i < 8; i++) in.push_back((unsigned char) (len >> (8 * i)));
+            in.insert(in.end(), part->begin(), part->end());
+        }
+        in.resize((in.size() + 31) / 32 * 32, 0);
+        std::uint8_t k[32] = {0};
+        for (size_t j = 0; j < in.size() / 32; j++) {
+            std::uint8_t x[32];
+            for (int i = 0; i < 32; i++) x[i] = k[i] ^ in[32 * j + i];
+            std::uint32_t w[8];
+            detail::check(hegpu_drbg_block(x, j, 0, w));
+            detail::check(hegpu_drbg_block(x, j, 1, w + 4));
+            for (int i = 0; i < 32; i++) k[i] = (std::uint8_t) (w[i / 4] >> (8 * (i % 4)));
+        }
+        hegpu_rng* r = nullptr;
+        detail::check(hegpu_rng_create_seeded(k, &r));
+        return r;
+    }
+
+  private:
+    static void fill(std::vector<unsigned char>& v)
+    {
+        size_t got = 0;
+        while (got < v.size()) {
+            const ssize_t r = getrandom(v.data() + got, v.size() - got, 0);
+            if (r < 0 && errno == EINTR) continue;
+            if (r < 0) throw std::runtime_error("getrandom failed");
+            got += (size_t) r;
+        }
+    }
+};
+
+template <Scheme S> class MultipartyPublickey : public Publickey<S> { // host/*/publickey.cuh
+  public:
+    MultipartyPublickey(HEContext<S> context, const RNGSeed seed) : Publickey<S>(std::move(context)), seed_(seed) {}
+    inline RNGSeed seed() const noexcept { return seed_; }
+
+  private:
+    RNGSeed seed_;
+};
+template <Scheme S> class MultipartyRelinkey : public Relinkey<S> { // host/*/evaluationkey.cuh
+  public:
+    MultipartyRelinkey(HEContext<S> context, const RNGSeed seed) : Relinkey<S>(std::move(context)), seed_(seed) {}
+    inline RNGSeed seed() const noexcept { return seed_; }
+
+  private:
+    RNGSeed seed_;
+};
+template <Scheme S> class MultipartyGaloiskey : public Galoiskey<S> {
+  public:
+    MultipartyGaloiskey(HEContext<S> context, const RNGSeed seed) : Galoiskey<S>(std::move(context)), seed_(seed) {}
+    MultipartyGaloiskey(HEContext<S> context, std::vector<int>& shift_vec, const RNGSeed seed)
+        : Galoiskey<S>(std::move(context), shift_vec), seed_(seed) {}
+    MultipartyGaloiskey(HEContext<S> context, std::vector<uint32_t>& galois_elts, const RNGSeed seed)
+        : Galoiskey<S>(std::move(context), galois_elts), seed_(seed) {}
+    inline RNGSeed seed() const noexcept { return seed_; }
+
+  private:
+    RNGSeed seed_;
+};
+
+namespace detail {
+// what HEMultiPartyManager<CKKS> and <BFV> share: everything but the constructor
+template <Scheme S> class MultiPartyManagerBase {
+  public:
+    ~MultiPartyManagerBase() { hegpu_rng_destroy(rng_); }
+    MultiPartyManagerBase(const MultiPartyManagerBase&) = delete;
+    MultiPartyManagerBase& operator=(const MultiPartyManagerBase&) = delete;
+
+    void generate_public_key_share(MultipartyPublickey<S>& pk, Secretkey<S>& sk, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        if (pk.public_key_generated_) throw std::logic_error("Publickey is already generated!");
+        Crs crs(pk.seed(), "pk");
+        DeviceVector<Data64> out((size_t) 2 * context_->Q_prime_size * context_->n, o.stream_), ws = key_ws(o);
+        check(hegpu_mpc_public_key_share(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(), (uint64_t*) out.data(),
+                                         ws.data(), ws.size() * sizeof(Data64), o.stream_));
+        pk.memory_set(std::move(out));
+        pk.public_key_generated_ = true;
+    }
+    void assemble_public_key_share(std::vector<MultipartyPublickey<S>>& all_pk, Publickey<S>& pk,
+                                   const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (all_pk.empty()) throw std::invalid_argument("No participant to generate common publickey!");
+        std::vector<const uint64_t*> shares;
+        for (auto& p : all_pk) {
+            if (!p.public_key_generated_) throw std::invalid_argument("MultipartyPublickey is not generated!");
+            shares.push_back((const uint64_t*) p.data());
+        }
+        DeviceVector<Data64> out((size_t) 2 * context_->Q_prime_size * context_->n, o.stream_);
+        check(hegpu_mpc_accumulate(context_->handle(), shares.data(), (int) shares.size(), HEGPU_MPC_PUBLIC_KEY,
+                                   (uint64_t*) out.data(), o.stream_));
+        pk.memory_set(std::move(out));
+        pk.public_key_generated_ = true;
+    }
+    // round 1; the ephemeral secret u stays inside this manager until generate_relin_key_share (the reference keeps
+    // the seed that regenerates it, new_seed_)
+    void generate_relin_key_init(MultipartyRelinkey<S>& rk, Secretkey<S>& sk, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        if (rk.relin_key_generated_) throw std::logic_error("Relinkey is already generated!");
+        Crs crs(rk.seed(), "rk");
+        u_ = DeviceVector<Data64>((size_t) context_->Q_prime_size * context_->n, o.stream_);
+        DeviceVector<Data64> out(rk.size(), o.stream_), ws = key_ws(o);
+        check(hegpu_mpc_relin_key_share_round1(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(),
+                                               (uint64_t*) u_.data(), (uint64_t*) out.data(), ws.data(),
+                                               ws.size() * sizeof(Data64), o.stream_));
+        rk.memory_set(std::move(out));
+        rk.relin_key_generated_ = true;
+    }
+    void assemble_relin_key_init(std::vector<MultipartyRelinkey<S>>& all_rk, MultipartyRelinkey<S>& rk,
+                                 const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        std::vector<const uint64_t*> shares = relin_shares(all_rk);
+        DeviceVector<Data64> out(rk.size(), o.stream_);
+        check(hegpu_mpc_accumulate(context_->handle(), shares.data(), (int) shares.size(), HEGPU_MPC_RELIN_ROUND1,
+                                   (uint64_t*) out.data(), o.stream_));
+        rk.memory_set(std::move(out));
+        rk.relin_key_generated_ = true;
+    }
+    void generate_relin_key_share(MultipartyRelinkey<S>& rk_s1_common, MultipartyRelinkey<S>& rk_new, Secretkey<S>& sk,
+                                  const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (rk_s1_common.key_type != rk_new.key_type) throw std::invalid_argument("Invalid relinkey parameters!");
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        if (!rk_s1_common.relin_key_generated_) throw std::logic_error("Common Relinkey is not generated!");
+        if (rk_new.relin_key_generated_) throw std::logic_error("Relinkey is already generated!");
+        if (!u_.size()) throw std::logic_error("generate_relin_key_init has to run first!");
+        DeviceVector<Data64> out(rk_new.size(), o.stream_), ws = key_ws(o);
+        check(hegpu_mpc_relin_key_share_round2(context_->handle(), rng_, (const uint64_t*) sk.data(),
+                                               (const uint64_t*) u_.data(), (const uint64_t*) rk_s1_common.data(),
+                                               (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+        rk_new.memory_set(std::move(out));
+        rk_new.relin_key_generated_ = true;
+    }
+    void assemble_relin_key_share(std::vector<MultipartyRelinkey<S>>& all_rk, MultipartyRelinkey<S>& rk_common_stage1,
+                                  Relinkey<S>& rk, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        std::vector<const uint64_t*> shares = relin_shares(all_rk);
+        if (!rk_common_stage1.relin_key_generated_) throw std::invalid_argument("MultipartyRelinkey is not generated!");
+        DeviceVector<Data64> out(rk.size(), o.stream_);
+        check(hegpu_mpc_relin_key_finish(context_->handle(), shares.data(), (int) shares.size(),
+                                         (const uint64_t*) rk_common_stage1.data(), (uint64_t*) out.data(), o.stream_));
+        rk.memory_set(std::move(out));
+        rk.relin_key_generated_ = true;
+    }
+    void generate_galois_key_share(MultipartyGaloiskey<S>& gk, Secretkey<S>& sk, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        if (gk.galois_key_generated_) throw std::logic_error("Galoiskey is already generated!");
+        DeviceVector<Data64> ws = key_ws(o);
+        for (int elt : elements(gk)) {
+            Crs crs(gk.seed(), "gk" + std::to_string(elt));
+            DeviceVector<Data64> out(gk.size(), o.stream_);
+            check(hegpu_mpc_galois_key_share(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(), elt,
+                                             (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+            gk.device_location_[elt] = std::move(out);
+        }
+        gk.galois_key_generated_ = true;
+    }
+    void assemble_galois_key_share(std::vector<MultipartyGaloiskey<S>>& all_gk, Galoiskey<S>& gk,
+                                   const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (all_gk.empty()) throw std::invalid_argument("No participant to generate common galois key!");
+        for (auto& g : all_gk)
+            if (!g.galois_key_generated_) throw std::invalid_argument("MultipartyGaloiskey is not generated!");
+        if (gk.galois_key_generated_) throw std::logic_error("Galoiskey is already generated!");
+        for (int elt : elements(gk)) {
+            std::vector<const uint64_t*> shares;
+            for (auto& g : all_gk) {
+                const auto it = g.device_location_.find(elt);
+                if (it == g.device_location_.end()) throw std::invalid_argument("MultipartyGaloiskey lacks an element!");
+                shares.push_back((const uint64_t*) it->second.data());
+            }
+            DeviceVector<Data64> out(gk.size(), o.stream_);
+            check(hegpu_mpc_accumulate(context_->handle(), shares.data(), (int) shares.size(), HEGPU_MPC_GALOIS_KEY,
+                                       (uint64_t*) out.data(), o.stream_));
+            gk.device_location_[elt] = std::move(out);
+        }
+        gk.galois_key_generated_ = true;
+    }
+    // The reference's shape: a 2-part ciphertext (c0, h_i).  The C ABI produces h_i alone; c0 is copied next to it
+    // because callers pass these objects to decrypt(), which reads c0 from the first of them.
+    void decrypt_partial(Ciphertext<S>& ciphertext, Secretkey<S>& sk, Ciphertext<S>& partial_ciphertext,
+                         const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        if (ciphertext.size() != 2) throw std::invalid_argument("Ciphertext should be relinearized first!");
+        const size_t half = (size_t) (context_->Q_size - ciphertext.depth()) * context_->n;
+        DeviceVector<Data64> out(2 * half, o.stream_);
+        hip(hipMemcpyAsync(out.data(), ciphertext.data(), half * sizeof(Data64), hipMemcpyDeviceToDevice, o.stream_));
+        if (S == Scheme::CKKS)
+            check(hegpu_mpc_ckks_decrypt_share(context_->handle(), rng_, (const uint64_t*) ciphertext.data(), 2 * half,
+                                               (const uint64_t*) sk.data(), ciphertext.depth(),
+                                               (uint64_t*) out.data() + half, 1, o.stream_));
+        else
+            check(hegpu_mpc_bfv_decrypt_share(context_->handle(), rng_, (const uint64_t*) ciphertext.data(), 2 * half,
+                                              (const uint64_t*) sk.data(), (uint64_t*) out.data() + half, 1, o.stream_));
+        partial_ciphertext.adopt(std::move(out), 2, ciphertext.depth(), ciphertext.scale());
+        partial_ciphertext.encoding_ = ciphertext.encoding_;
+    }
+    void decrypt(std::vector<Ciphertext<S>>& ciphertexts, Plaintext<S>& plaintext, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (ciphertexts.empty()) throw std::invalid_argument("No ciphertext to decrypt!");
+        const int depth = ciphertexts[0].depth();
+        for (auto& c : ciphertexts) {
+            if (c.depth() != depth) throw std::invalid_argument("Ciphertext levels should be same!");
+            if (c.scale() != ciphertexts[0].scale()) throw std::invalid_argument("Ciphertext scales should be same!");
+            if (c.encoding_ != ciphertexts[0].encoding_) throw std::invalid_argument("Ciphertext encoding types should be same!");
+        }
+        const size_t half = (size_t) (context_->Q_size - depth) * context_->n;
+        std::vector<const uint64_t*> shares;
+        for (auto& c : ciphertexts) shares.push_back((const uint64_t*) c.data() + half);
+        const uint64_t* c0 = (const uint64_t*) ciphertexts[0].data();
+        DeviceVector<Data64> out(S == Scheme::CKKS ? half : (size_t) context_->n, o.stream_);
+        if (S == Scheme::CKKS) {
+            check(hegpu_mpc_ckks_decrypt_merge(context_->handle(), c0, 2 * half, shares.data(), (int) shares.size(), depth,
+                                               (uint64_t*) out.data(), 1, o.stream_));
+        } else {
+            DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_BFV_DECRYPT_MERGE, 0, 1) + 7) / 8,
+                                    o.stream_);
+            check(hegpu_mpc_bfv_decrypt_merge(context_->handle(), c0, 2 * half, shares.data(), (int) shares.size(),
+                                              (uint64_t*) out.data(), 1, ws.data(), ws.size() * sizeof(Data64), o.stream_));
+        }
+        plaintext.memory_set(std::move(out));
+        plaintext.depth_ = depth;
+        plaintext.scale_ = ciphertexts[0].scale();
+        plaintext.encoding_ = ciphertexts[0].encoding_;
+        plaintext.plaintext_generated_ = true;
+    }
+
+  protected:
+    explicit MultiPartyManagerBase(HEContext<S> context) : context_(std::move(context))
+    {
+        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        check(hegpu_rng_create_from_entropy(&rng_)); // the party's private generator
+    }
+
+  private:
+    struct Crs { // the common generator of one key, from the seed the key carries
+        Crs(const RNGSeed& seed, const std::string& label) : r(seed.expand(label)) {}
+        ~Crs() { hegpu_rng_destroy(r); }
+        Crs(const Crs&) = delete;
+        Crs& operator=(const Crs&) = delete;
+        hegpu_rng* r;
+    };
+    DeviceVector<Data64> key_ws(const ExecutionOptions& o)
+    {
+        return DeviceVector<Data64>((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, 1) + 7) / 8, o.stream_);
+    }
+    static std::vector<const uint64_t*> relin_shares(std::vector<MultipartyRelinkey<S>>& all_rk)
+    {
+        if (all_rk.empty()) throw std::invalid_argument("No participant to generate common relinkey!");
+        std::vector<const uint64_t*> shares;
+        for (auto& r : all_rk) {
+            if (!r.relin_key_generated_) throw std::invalid_argument("MultipartyRelinkey is not generated!");
+            shares.push_back((const uint64_t*) r.data());
+        }
+        return shares;
+    }
+    static std::vector<int> elements(const Galoiskey<S>& gk) // the listed elements and the column-rotation key, each once
+    {
+        std::vector<int> e;
+        if (gk.customized) for (std::uint32_t x : gk.custom_galois_elt) e.push_back((int) x);
+        else for (const auto& g : gk.galois_elt) e.push_back(g.second);
+        e.push_back(gk.galois_elt_zero);
+        std::sort(e.begin(), e.end());
+        e.erase(std::unique(e.begin(), e.end()), e.end());
+        return e;
+    }
+    HEContext<S> context_;
+    hegpu_rng* rng_ = nullptr;
+    DeviceVector<Data64> u_; // round 1 -> round 2 of the relinearisation key
+};
+} // namespace detail
+
+template <Scheme S> class HEMultiPartyManager;
+template <> class HEMultiPartyManager<Scheme::CKKS> : public detail::MultiPartyManagerBase<Scheme::CKKS> {
+  public:
+    // encoder and scale serve the reference's collective bootstrapping, which is not part of this backend
+    HEMultiPartyManager(HEContext<Scheme::CKKS> context, HEEncoder<Scheme::CKKS>&, double&)
+        : detail::MultiPartyManagerBase<Scheme::CKKS>(std::move(context)) {}
+};
+template <> class HEMultiPartyManager<Scheme::BFV> : public detail::MultiPartyManagerBase<Scheme::BFV> {
+  public:
+    explicit HEMultiPartyManager(HEContext<Scheme::BFV> context) : detail::MultiPartyManagerBase<Scheme::BFV>(std::move(context)) {}
 };
 
 // ------------------------------------------------------------------ TFHE (host/tfhe/*.cuh)
