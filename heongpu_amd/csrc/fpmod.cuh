@@ -37,6 +37,7 @@ enum FpMetric { FPM_MUL_Y = 0, FPM_MUL_W = 1, FPM_MUL_T = 2, FPM_SUM = 3, FPM_RE
 #define FP_STAGE_SUMS 25    // the running sums of those products (+ digits since the last re-centring: 25, 26, 27)
 #define FP_STAGE_INPUT 29   // load transforms (decomposition, mod-down half)
 #define FP_STAGE_OUT 30     // what leaves the transform / the external product
+#define FP_STAGE_TAIL 31    // mod-down tail of the fused key switch: accumulator - T and its product by P^-1
 #define FP_STAGES 32
 
 #ifdef HEGPU_FP_AUDIT_HEADER

@@ -262,19 +262,56 @@ __device__ __forceinline__ u64 shoup_full(u64 y, ulonglong2 w, const QC& c)
     return csub(r, c.q);
 }
 
-// Harvey-style CT butterfly.  LAZY == false: x,y in [0,8q) -> [0,8q) (one
-// conditional subtraction per butterfly; needs only q < 2^61).  LAZY == true
-// (q <= NttArgs::lazy_q_max): no correction at all -- every stage adds at most 4q to the
-// bound, which stays below 2^64 over all log2 N stages; one exact reduction ends the transform.
-template <bool LAZY>
-__device__ __forceinline__ void ct_bfly(u64& x, u64& y, ulonglong2 w, const QC& c)
+// Harvey-style CT butterfly (ct_bfly_cs below).  Correcting: x,y in [0,8q) -> [0,8q) with one conditional subtraction
+// per butterfly (needs only q < 2^61), or fewer on a schedule.  Correction-free (q <= NttArgs::lazy_q_max): every stage
+// adds at most 4q to the bound, which stays below 2^64 over all log2 N stages; one exact reduction ends the transform.
+// Where the corrections of the correcting butterflies go.  shoup_lazy returns a value in [0, 4q) for ANY 64-bit y, so
+// only the upper input u has to be bounded, and all a stage needs is u + 4q < 2^64: from u < b q it leaves x, y below
+// (b + 4) q.  A modulus below 2^61 has room for 8 q -- a correction (csub by 4q: [0, 8q) -> [0, 4q)) in every butterfly
+// of every stage (NTT_CS_EVERY).  A modulus below 2^60 has room for 16 q: from the [0, 8q) a pass is
+// handed, two stages run without a correction (8 -> 12 -> 16 q), then one csub by 8q brings [0, 16q) (or [0, 12q)) back
+// to [0, 8q) and the next two stages run free again.  A pass hands over [0, 8q) as before (what the row pass, the
+// canonicalisation in front of the 128-bit inner product and the final csub chain of the row pass assume), so its LAST
+// stage needs u < 4q: csub by 8q and by 4q there.  Eight stages from [0, 8q): corrections before stages 2, 4, 6 (8q)
+// and 7 (8q, 4q) -- five per coefficient pair instead of eight; the bound chain is 8, 12, 16 | 8, 12, 16 | 8, 12, 16 |
+// 8, 12 | 4, 8.  The schedule is computed at compile time from the room (units of q) and the number of stages: bit s of
+// c8 / c4 = csub by 8q / by 4q (in that order) before local stage s.  The entry bound stays 8 q, not the q of a
+// canonical input: decomposing launches feed digits of other primes (up to 8 q, fwd_col_body) and the transform entry
+// points have always taken any input below 8 q.
+struct CsSched { unsigned c8, c4; };
+__host__ __device__ constexpr CsSched cs_sched(int stages, int room)
+{
+    CsSched r{0u, 0u};
+    int b = 8;
+    for (int s = 0; s < stages; s++) {
+        const int need = (s == stages - 1) ? 4 : room - 4; // u + 4q inside the room; the last stage hands over [0, 8q)
+        if (b > need && b > 8) {
+            r.c8 |= 1u << s;
+            b = 8; // [0, 16q) -> [0, 8q)
+        }
+        if (b > need) {
+            r.c4 |= 1u << s;
+            b = 4;
+        }
+        b += 4;
+    }
+    return r;
+}
+static_assert(cs_sched(8, 8).c8 == 0u && cs_sched(8, 8).c4 == 0xFFu, "61-bit moduli: a correction in every stage");
+static_assert(cs_sched(8, 16).c8 == 0xD4u && cs_sched(8, 16).c4 == 0x80u, "60-bit moduli: stages 2, 4, 6, 7 / 7");
+static_assert(cs_sched(5, 16).c8 == 0x14u && cs_sched(5, 16).c4 == 0x10u, "N = 2^13 column pass: stages 2, 4 / 4");
+// the butterfly with the corrections of one stage: cs bit 1 = csub by 8q, bit 0 = csub by 4q (a constant after unrolling)
+__device__ __forceinline__ void ct_bfly_cs(u64& x, u64& y, ulonglong2 w, const QC& c, int cs)
 {
     NTT_ABLATE_BFLY(x, y, w);
-    u64 u = LAZY ? x : csub(x, c.q4);
+    u64 u = x;
+    if (cs & 2) u = csub(u, 2 * c.q4);
+    if (cs & 1) u = csub(u, c.q4);
     u64 t = shoup_lazy(y, w, c);
     x = u + t;
     y = u + c.q4 - t;
 }
+#define NTT_CS_EVERY 0xFFFFFFFFu // (c8 = 0, c4 = this: csub by 4q in every stage)
 
 // GS butterfly, x,y in [0,4q) -> [0,4q)
 __device__ __forceinline__ void gs_bfly(u64& x, u64& y, ulonglong2 w, const QC& c)
@@ -288,37 +325,40 @@ __device__ __forceinline__ void gs_bfly(u64& x, u64& y, ulonglong2 w, const QC& 
 
 // LOGR Cooley-Tukey stages on 2^LOGR register-resident values.  Local stage
 // s, block b uses root index (root0 << s) + b.
-template <int LOGR, bool LAZY, typename TW>
+// C8 / C4: the correction schedule of these stages (CsSched, bit s = local stage s; nothing if LAZY).
+template <int LOGR, bool LAZY, unsigned C8 = 0u, unsigned C4 = NTT_CS_EVERY, typename TW>
 __device__ __forceinline__ void ct_radix(u64 (&x)[1 << LOGR], TW tw,
                                          u32 root0, const QC& c)
 {
 #pragma unroll
     for (int s = 0; s < LOGR; s++) {
         const int half = (1 << LOGR) >> (s + 1);
+        const int cs = LAZY ? 0 : (int) (((C8 >> s) & 1u) * 2u + ((C4 >> s) & 1u));
 #pragma unroll
         for (int b = 0; b < (1 << s); b++) {
             ulonglong2 w = NTT_ABLATE_TW(tw[(root0 << s) + b], root0, s);
 #pragma unroll
             for (int j = 0; j < half; j++)
-                ct_bfly<LAZY>(x[b * 2 * half + j], x[b * 2 * half + j + half], w, c);
+                ct_bfly_cs(x[b * 2 * half + j], x[b * 2 * half + j + half], w, c, cs);
         }
     }
 }
 
 // The last four CT stages of the row pass with the re-laid table: slot k of
 // this thread is tb[k * 16] (tb already points at [mod][row][0][lane]).
-template <bool LAZY>
+template <bool LAZY, unsigned C8 = 0u, unsigned C4 = NTT_CS_EVERY>
 __device__ __forceinline__ void ct_radix16_tb(u64 (&x)[16], const ulonglong2* __restrict__ tb, const QC& c)
 {
 #pragma unroll
     for (int s = 0; s < 4; s++) {
         const int half = 8 >> s;
+        const int cs = LAZY ? 0 : (int) (((C8 >> s) & 1u) * 2u + ((C4 >> s) & 1u));
 #pragma unroll
         for (int b = 0; b < (1 << s); b++) {
             ulonglong2 w = tb[((1 << s) - 1 + b) * 16];
 #pragma unroll
             for (int j = 0; j < half; j++)
-                ct_bfly<LAZY>(x[b * 2 * half + j], x[b * 2 * half + j + half], w, c);
+                ct_bfly_cs(x[b * 2 * half + j], x[b * 2 * half + j + half], w, c, cs);
         }
     }
 }
@@ -455,7 +495,7 @@ __device__ __forceinline__ void wave_lds_fence()
 #define ROW_LDS_ELEMS 4096
 
 // ------------------------------------------------------------------ forward
-// Moduli up to NttArgs::lazy_q_max take the correction-free butterflies in every stage (see ct_bfly): the bound of a
+// Moduli up to NttArgs::lazy_q_max take the correction-free butterflies in every stage (see ct_bfly_cs): the bound of a
 // value grows by at most 4q per stage, in + 4 log2(N) q < 2^64 (2^57 for N = 2^16 next to 61-bit primes; the 58/59-bit
 // default chains at N <= 2^15).
 __device__ __forceinline__ bool fwd_stages_lazy(const Mod& md, u64 lazy_q_max) { return md.q <= lazy_q_max; }
@@ -466,16 +506,19 @@ __device__ __forceinline__ bool fwd_stages_lazy(const Mod& md, u64 lazy_q_max) {
 // (or the 128-bit inner product of ks_row_mac: 64 digits * 40q * q < 2^128) takes any such value.
 #define NTT_ROW_LAZY_MAX_Q 0x0666666666666666ull
 __device__ __forceinline__ bool row_stages_lazy(const Mod& md, u64 lazy_q_max) { return md.q <= lazy_q_max || md.q <= NTT_ROW_LAZY_MAX_Q; }
+// The room (units of q) of the correcting butterflies' schedule (cs_sched): 16 q < 2^64 up to 60-bit moduli, else 8 q.
+__device__ __forceinline__ bool stages_room16(const Mod& md) { return md.bit <= 60; }
 
 // Column pass: stages 0..S1-1 (row stride 256).  grid = (256/CT, batch).
 // SREG: the 16 source coefficients of the thread are already in registers (`sreg`, in load order:
 // group g, slot k at sreg[g * RA + k]) -- the multi-modulus column pass (ntt_fwd_col_multi) loads a
 // digit tile once and runs this body for every target modulus; it also needs the tile free again
 // before the next iteration writes it, hence the second barrier right after the exchange reads.
-template <int S1, bool DECOMP, bool LAZY, bool SREG = false>
+template <int S1, bool DECOMP, bool LAZY, bool SREG = false, int ROOM = 8>
 __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps, const Mod& md, u64* lds,
                                              const u64* sreg = nullptr)
 {
+    constexpr CsSched CS = cs_sched(S1, ROOM); // over the S1 stages of the pass: round A takes the low bits
     constexpr int R = 1 << S1;
     constexpr int CT = 4096 / R;
     constexpr int NSA = S1 - 4;
@@ -529,7 +572,7 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
             // first: the correcting butterflies only need x < 8q (guarded above) and the
             // correction-free path x + 4 log2(N) q < 2^64 (lazy_q_max); congruence mod q is
             // kept and the row pass ends with an exact reduction.
-            ct_radix<NSA, LAZY>(y, tw, 1u, qc);
+            ct_radix<NSA, LAZY, CS.c8, CS.c4>(y, tw, 1u, qc);
 #pragma unroll
             for (int k = 0; k < RA; k++) lds[col_phys((rb + 16 * k) * CT + c)] = y[k];
         }
@@ -541,7 +584,7 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
 #pragma unroll
         for (int k = 0; k < 16; k++) x[k] = v[k];
     }
-    ct_radix<4, LAZY>(x, tw, (u32) (RA + r1), qc);
+    ct_radix<4, LAZY, (CS.c8 >> NSA), (CS.c4 >> NSA)>(x, tw, (u32) (RA + r1), qc);
 #pragma unroll
     for (int k = 0; k < 16; k++) gst(&dst[(u64) (16 * r1 + k) * 256 + col], x[k]);
 }
@@ -704,6 +747,9 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col(NttArgs a)
             fwd_col_body_fp<S1, DECOMP, true>(a, ps, md, lds, twl);
         else fwd_col_body_fp<S1, DECOMP, false>(a, ps, md, lds, twl);
     } else if (fwd_stages_lazy(md, a.lazy_q_max)) fwd_col_body<S1, DECOMP, true>(a, ps, md, lds);
+    // (not at N = 2^12: four stages save one correction, and a third integer body takes ntt_fwd_col<4, true> from 90 to
+    // 106 registers, five waves per SIMD to four)
+    else if (S1 > 4 && stages_room16(md)) fwd_col_body<S1, DECOMP, false, false, (S1 > 4 ? 16 : 8)>(a, ps, md, lds);
     else fwd_col_body<S1, DECOMP, false>(a, ps, md, lds);
 }
 
@@ -760,9 +806,10 @@ __device__ __forceinline__ void row_store_all(const NttArgs& a, const PolySel& p
     }
 }
 
-template <bool LAZY>
+template <bool LAZY, int ROOM = 8>
 __device__ __forceinline__ void fwd_row_body(const NttArgs& a, const PolySel& ps, const Mod& md, u64* lds)
 {
+    constexpr CsSched CS = cs_sched(8, ROOM);
     const int t = threadIdx.x;
     const QC qc = make_qc(md.q);
     const int s1 = a.n_power - 8;
@@ -774,7 +821,7 @@ __device__ __forceinline__ void fwd_row_body(const NttArgs& a, const PolySel& ps
     u64 x[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) x[k] = gld(&p[row * 256 + i0 + 16 * k]);
-    ct_radix<4, LAZY>(x, tw, (1u << s1) + crow, qc);
+    ct_radix<4, LAZY, CS.c8, CS.c4>(x, tw, (1u << s1) + crow, qc);
 #pragma unroll
     for (int k = 0; k < 16; k++) lds[row_phys(row * 256 + i0 + 16 * k)] = x[k];
     wave_lds_fence();
@@ -784,7 +831,7 @@ __device__ __forceinline__ void fwd_row_body(const NttArgs& a, const PolySel& ps
         x[2 * k] = v.x;
         x[2 * k + 1] = v.y;
     }
-    ct_radix16_tb<LAZY>(x, a.twB + ((u64) ps.mod * (15u << (a.n_power - 4))) + ((u64) crow * 15 * 16 + i0), qc);
+    ct_radix16_tb<LAZY, (CS.c8 >> 4), (CS.c4 >> 4)>(x, a.twB + ((u64) ps.mod * (15u << (a.n_power - 4))) + ((u64) crow * 15 * 16 + i0), qc);
     if (LAZY) {
         // x < 65q: one exact reduction (floor(2^64/q) quotient estimate)
 #pragma unroll
@@ -844,6 +891,7 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_row(NttArgs a)
     const Mod md = a.mods[ps.mod];
     if (md.fp) fwd_row_body_fp(a, ps, md, lds);
     else if (row_stages_lazy(md, a.lazy_q_max)) fwd_row_body<true>(a, ps, md, lds);
+    else if (stages_room16(md)) fwd_row_body<false, 16>(a, ps, md, lds);
     else fwd_row_body<false>(a, ps, md, lds);
 }
 
@@ -1070,22 +1118,24 @@ __device__ __forceinline__ void acc128(u64& hi, u64& lo, u64 a, u64 b)
     hi += h + (lo < l);
 }
 
-template <bool LAZY>
+template <bool LAZY, int ROOM = 8>
 __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict__ p, u64* lds,
                                              const ulonglong2* twa, const ulonglong2* __restrict__ tb,
                                              const QC& qc, const Mod& md, int row, int i0)
 {
+    constexpr CsSched CS = cs_sched(8, ROOM);
 #pragma unroll
     for (int k = 0; k < 16; k++) x[k] = gld(&p[row * 256 + i0 + 16 * k]);
     // first four stages: the row's 15 twiddles from LDS (slot (1 << s) - 1 + b at [slot][row])
 #pragma unroll
     for (int s = 0; s < 4; s++) {
         const int half = 8 >> s;
+        const int cs = LAZY ? 0 : (int) (((CS.c8 >> s) & 1u) * 2u + ((CS.c4 >> s) & 1u));
 #pragma unroll
         for (int b = 0; b < (1 << s); b++) {
             const ulonglong2 w = twa[((1 << s) - 1 + b) * 16 + row];
 #pragma unroll
-            for (int j = 0; j < half; j++) ct_bfly<LAZY>(x[b * 2 * half + j], x[b * 2 * half + j + half], w, qc);
+            for (int j = 0; j < half; j++) ct_bfly_cs(x[b * 2 * half + j], x[b * 2 * half + j + half], w, qc, cs);
         }
     }
 #pragma unroll
@@ -1097,7 +1147,7 @@ __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict
         x[2 * k] = v.x;
         x[2 * k + 1] = v.y;
     }
-    ct_radix16_tb<LAZY>(x, tb, qc);
+    ct_radix16_tb<LAZY, (CS.c8 >> 4), (CS.c4 >> 4)>(x, tb, qc);
     if (!LAZY) {
         // bring [0,8q) down to [0,q) so that 64 products stay below 2^128
 #pragma unroll
@@ -1168,21 +1218,12 @@ __device__ __forceinline__ KsIdx ks_index(const KsMacArgs& a)
     return r;
 }
 
-// Mod-down tail of the fused key switch (KsMacArgs::tail), part p of one (item, slot, tile): acc / tv = the thread's 16
-// canonical accumulated / transformed-P-limb residues at e0 + 16 k of the limb (e0 = tile * 4096 + row * 256 + i0), cv
-// the added term if with_ct.  The residues of row_store_all.
-__device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int slot, int p, u64 e0, const Mod& md, u64 inv,
-                                              const u64 (&acc)[16], const u64 (&tv)[16], bool with_ct, const u64 (&cv)[16])
+// Mod-down tail of the fused key switch (KsMacArgs::tail), part p of one (item, slot, tile): the thread's 16 results r
+// belong at e0 + 16 k of the limb (e0 = tile * 4096 + row * 256 + i0), or where the Galois automorphism sends them.
+__device__ __forceinline__ void ks_tail_scatter(const KsMacArgs& a, int item, int slot, int p, u64 e0, const u64 (&r)[16])
 {
     const KsMacArgs::Tail& e = a.tail;
     u64* out = e.out + e.out_item_stride * item + ((u64) (p * e.limbs + slot) << a.n_power);
-    u64 r[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) r[k] = mul_barrett(sub_mod(acc[k], tv[k], md.q), inv, md);
-    if (with_ct) {
-#pragma unroll
-        for (int k = 0; k < 16; k++) r[k] = add_mod(cv[k], r[k], md.q);
-    }
     if (e.galois_inv) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -1194,6 +1235,57 @@ __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int 
 #pragma unroll
         for (int k = 0; k < 16; k++) out[e0 + 16 * k] = r[k];
     }
+}
+// Integer moduli: acc / tv = the thread's 16 canonical accumulated / transformed-P-limb residues, cv the added term if
+// with_ct.  The residues of row_store_all.
+__device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int slot, int p, u64 e0, const Mod& md, u64 inv,
+                                              const u64 (&acc)[16], const u64 (&tv)[16], bool with_ct, const u64 (&cv)[16])
+{
+    u64 r[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) r[k] = mul_barrett(sub_mod(acc[k], tv[k], md.q), inv, md);
+    if (with_ct) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) r[k] = add_mod(cv[k], r[k], md.q);
+    }
+    ks_tail_scatter(a, item, slot, p, e0, r);
+}
+// FP64 moduli (q < 2^50): the same residues, (acc - T) P^-1 + ct mod q, without leaving the doubles -- everything is
+// exact integer arithmetic modulo q, so the canonical result is the integer form's, bit for bit.  acc = the running
+// sums as the digit loop left them (|acc| <= 7.88 q), tv = T straight from its row stages, un-reduced (|T| <= 5.22 q),
+// (inv, invq) = P^-1 mod q (canonical, < q) and its companion RN(inv RN(1/q)).
+//   d = fp_reduce(acc) - T: acc - T itself could pass 2^53 (13.1 q), so the sums are re-centred first; then
+//       |d| <= 0.5 q + 5.22 q = 5.72 q < 2^53, a difference of two integers below 2^53: exact.
+//   t = fp_mul(d, inv, invq): operand |y| = |d| <= 5.72 q, "twiddle" inv < q.  invq and the rounded product d invq are
+//       within |d inv / q| * 1.5 * 2^-52 <= 5.72 * 2^50 * 1.5 * 2^-52 = 2.15 of d inv / q, so |k - y x / q| <= 2.65; k < 2^53
+//       is an exact integer, h - k q = (y x - k q) - l with |l| <= ulp(h) / 2 <= 2^49 (|h| < 2^103) is an integer below
+//       2.65 q + 2^49 < 2^52: the FMA that forms it and the sum with l are exact, t = d inv - k q EXACTLY, |t| <= 2.65 q.
+//   t + ct: ct < 2^52 (fp_from_u64's precondition; the operators pass canonical residues, ct < q, and any value below
+//       2^52 still gives the canonical residue of the exact sum -- the integer add_mod returned a non-canonical sum for a
+//       non-canonical ct); |t + ct| < 2.65 q + 2^52 < 2^53, exact; fp_canon takes that to [0, q).
+// tests/test_fp_model_tail.py derives these bounds, tests/test_gpu_fp_tail.py measures them in the instrumented build.
+__device__ __forceinline__ void ks_tail_store_fp(const KsMacArgs& a, int item, int slot, int p, u64 e0, const FC& fc, double inv,
+                                                 double invq, const double (&acc)[16], const double (&tv)[16], bool with_ct,
+                                                 const u64 (&cv)[16])
+{
+    double m[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        FP_STAGE(fc, FP_STAGE_OUT);
+        const double d = fp_reduce(acc[k], fc) - tv[k];
+        FP_STAGE(fc, FP_STAGE_TAIL);
+        FP_AUDIT_VAL(fc, FPM_SUM, d);
+        m[k] = fp_mul(d, inv, invq, fc);
+    }
+    FP_STAGE(fc, FP_STAGE_OUT);
+    if (with_ct) {
+#pragma unroll
+        for (int k = 0; k < 16; k++) m[k] += fp_from_u64(cv[k]);
+    }
+    u64 r[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) r[k] = fp_to_u64(fp_canon(m[k], fc));
+    ks_tail_scatter(a, item, slot, p, e0, r);
 }
 // the tail's operands of part p: the column-pass output T (row stages still to do) and the added term
 __device__ __forceinline__ const u64* ks_tail_T(const KsMacArgs& a, int item, int slot, int tile, int p)
@@ -1231,6 +1323,7 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
     const u64 key_off1 = (u64) a.key_limbs << a.n_power, key_off2 = (u64) a.key_limbs << (a.n_power + 1);
     // the un-reduced output (any 64-bit value) times a key residue (< q) summed over the digits has to fit 128 bits
     const bool lazy = row_stages_lazy(md, a.lazy_q_max) && md.q <= ~0ull / (u64) a.digits;
+    const bool room16 = stages_room16(md);
     // digit-invariant twiddles of the first four stages, shared by the 16 lanes of a row (see
     // ks_row_mac_fp; the per-lane ones of the last four stages would need 61 KiB as pairs)
     ulonglong2* twa = reinterpret_cast<ulonglong2*>(twbuf); // [15 * 16]
@@ -1255,6 +1348,8 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
             for (int k = 0; k < 16; k++) x[k] = gld(&pi[row * 256 + i0 + 16 * k]);
         } else if (lazy) {
             ks_row_digit<true>(x, p, lds, twa, tb, qc, md, row, i0);
+        } else if (room16) {
+            ks_row_digit<false, 16>(x, p, lds, twa, tb, qc, md, row, i0);
         } else {
             ks_row_digit<false>(x, p, lds, twa, tb, qc, md, row, i0);
         }
@@ -1290,6 +1385,8 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
                 ks_row_digit<true>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
 #pragma unroll
                 for (int k = 0; k < 16; k++) x[k] = reduce64(x[k], md);
+            } else if (room16) {
+                ks_row_digit<false, 16>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
             } else {
                 ks_row_digit<false>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
             }
@@ -1576,15 +1673,16 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
         }
     }
     if constexpr (MD) {
-        // mod-down tail, one part at a time: T's row stages exactly as a digit's, then the integer epilogue on the
-        // canonical residues.  The lane's indices are formed anew from an opaque copy of the thread index: kept from
+        // mod-down tail, one part at a time: T's row stages exactly as a digit's, then the epilogue in FP64 on the
+        // un-reduced T and the sums as they are (ks_tail_store_fp).  The lane's indices are formed anew from an opaque copy of the thread index: kept from
         // before the digit loop, they and what the compiler derives from them sit in AGPRs across it (one wave per SIMD).
         int tt = threadIdx.x;
         asm volatile("" : "+v"(tt));
         const int trow = tt >> 4, ti0 = tt & 15;
         const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
-        const Mod mds = a.mods[midx_s];
-        const u64 inv = a.tail.inv[midx_s];
+        // P^-1 mod q_j and its companion, formed here as the key products form theirs: one multiply per workgroup.  A
+        // pair table uploaded by the context would hold the same two wave-uniform doubles in the same registers.
+        const double inv = fp_from_u64(a.tail.inv[midx_s]), invq = inv * fc.qi;
         auto part = [&](int p, const double (&acc)[16]) {
             const u64* pT = ks_tail_T(a, item_s, slot_s, tile_s, p);
             u64 tr[16], cv[16];
@@ -1593,14 +1691,7 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
             const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
             double x[16];
             ks_fp_row<false>(x, tr, twl, lds, fc, s1, trow, ti0, tt);
-            FP_STAGE(fc, FP_STAGE_OUT);
-            u64 av[16], tv[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                av[k] = fp_to_u64(fp_canon(acc[k], fc));
-                tv[k] = fp_to_u64(fp_canon(x[k], fc));
-            }
-            ks_tail_store(a, item_s, slot_s, p, e0, mds, inv, av, tv, with_ct, cv);
+            ks_tail_store_fp(a, item_s, slot_s, p, e0, fc, inv, invq, acc, x, with_ct, cv);
         };
         __builtin_amdgcn_sched_barrier(0); // (one part at a time: the loads of the second are not hoisted into the first)
         part(0, a0);
