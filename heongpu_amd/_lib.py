@@ -116,6 +116,13 @@ SIGNATURES = [
     ("hegpu_mpc_bfv_decrypt_share", c_int, [voidp, voidp, u64p, u64, u64p, u64p, c_int, voidp]),
     ("hegpu_mpc_bfv_decrypt_merge", c_int,
      [voidp, u64p, u64, ctypes.POINTER(ctypes.c_void_p), c_int, u64p, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_ckks_refresh_share", c_int,
+     [voidp, voidp, voidp, u64p, u64, u64p, c_int, c_int, u64p, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_ckks_refresh_merge", c_int,
+     [voidp, voidp, u64p, u64, ctypes.POINTER(ctypes.c_void_p), c_int, c_int, u64p, u64, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_bfv_refresh_share", c_int, [voidp, voidp, voidp, u64p, u64, u64p, u64p, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_mpc_bfv_refresh_merge", c_int,
+     [voidp, voidp, u64p, u64, ctypes.POINTER(ctypes.c_void_p), c_int, u64p, u64, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_noise_rns", c_int, [voidp, u64p, u64p, u64p, voidp]),
     ("hegpu_bfv_plain_to_ntt", c_int, [voidp, u64p, u64p, voidp]),
     ("hegpu_negacyclic_shift", c_int, [voidp, u64p, u64p, c_int, c_int, c_int, voidp]),

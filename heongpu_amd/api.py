@@ -21,6 +21,7 @@ OP_KEYGEN_SECRET, OP_KEYGEN_PUBLIC, OP_KEYGEN_SWITCH, OP_CKKS_ENCRYPT, OP_BFV_EN
 OP_CKKS_ENCODE, OP_CKKS_DECODE = 14, 15
 OP_BFV_MULTIPLY_PLAIN = 16
 OP_MPC_KEY_SHARE, OP_MPC_BFV_DECRYPT_MERGE = 18, 19
+OP_MPC_REFRESH_SHARE, OP_MPC_REFRESH_MERGE = 20, 21
 MPC_PUBLIC_KEY, MPC_GALOIS_KEY, MPC_RELIN_ROUND1 = 0, 1, 2
 TABLES_PLAIN = 2
 
@@ -659,6 +660,56 @@ class Context:
                                                      _ptr(plain), batch, _ptr(ws), ws.numel() * ws.element_size(),
                                                      stream if stream is not None else _stream()))
         return plain
+
+    # ---- collective refresh (hegpu_mpc_*_refresh_*): crs takes one stream per call, the parties and the coordinator
+    # must start from equally advanced generators
+    def mpc_ckks_refresh_share(self, crs, rng, ct, ct_stride, sk, depth, mask_bits, batch=1, stream=None):
+        """-> share [batch][(Q - depth) + Q][N]: (c1 s_i + NTT(e0 - M_i), -(a s_i) + NTT(e1 + M_i))"""
+        import torch
+        share = torch.empty(batch * (2 * self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
+        ws = self.workspace(OP_MPC_REFRESH_SHARE, depth, batch)
+        _check(self._lib.hegpu_mpc_ckks_refresh_share(self._h, crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), depth,
+                                                      mask_bits, _ptr(share), batch, _ptr(ws),
+                                                      ws.numel() * ws.element_size(),
+                                                      stream if stream is not None else _stream()))
+        return share
+
+    def mpc_ckks_refresh_merge(self, crs, ct, ct_stride, shares, depth, batch=1, out=None, out_stride=None, stream=None):
+        """-> [batch][2][Q][N] at depth 0 (items out_stride apart when `out` is given), the scale unchanged"""
+        import torch
+        words = 2 * self.Q_size * self.n
+        out_stride = words if out_stride is None else out_stride
+        if out is None:
+            out = torch.empty(max(batch - 1, 0) * out_stride + words, dtype=torch.int64, device="cuda")
+        ws = self.workspace(OP_MPC_REFRESH_MERGE, depth, batch)
+        _check(self._lib.hegpu_mpc_ckks_refresh_merge(self._h, crs._h, _ptr(ct), ct_stride, self._share_array(shares),
+                                                      len(shares), depth, _ptr(out), out_stride, batch, _ptr(ws),
+                                                      ws.numel() * ws.element_size(),
+                                                      stream if stream is not None else _stream()))
+        return out
+
+    def mpc_bfv_refresh_share(self, crs, rng, ct, ct_stride, sk, batch=1, stream=None):
+        """-> share [batch][2][Q][N], coefficient domain"""
+        import torch
+        share = torch.empty(batch * 2 * self.Q_size * self.n, dtype=torch.int64, device="cuda")
+        ws = self.workspace(OP_MPC_REFRESH_SHARE, 0, batch)
+        _check(self._lib.hegpu_mpc_bfv_refresh_share(self._h, crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share),
+                                                     batch, _ptr(ws), ws.numel() * ws.element_size(),
+                                                     stream if stream is not None else _stream()))
+        return share
+
+    def mpc_bfv_refresh_merge(self, crs, ct, ct_stride, shares, batch=1, out=None, out_stride=None, stream=None):
+        import torch
+        words = 2 * self.Q_size * self.n
+        out_stride = words if out_stride is None else out_stride
+        if out is None:
+            out = torch.empty(max(batch - 1, 0) * out_stride + words, dtype=torch.int64, device="cuda")
+        ws = self.workspace(OP_MPC_REFRESH_MERGE, 0, batch)
+        _check(self._lib.hegpu_mpc_bfv_refresh_merge(self._h, crs._h, _ptr(ct), ct_stride, self._share_array(shares),
+                                                     len(shares), _ptr(out), out_stride, batch, _ptr(ws),
+                                                     ws.numel() * ws.element_size(),
+                                                     stream if stream is not None else _stream()))
+        return out
 
 
 GATE_NAND, GATE_AND, GATE_AND_FIRST_NOT, GATE_NOR, GATE_OR, GATE_XNOR, GATE_XOR, GATE_NOT = range(8)

@@ -1218,6 +1218,106 @@ int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t
                    "hegpu_mpc_bfv_decrypt_merge");
 }
 
+// ---- collective refresh.  The checks every entry shares; the workspace row may be empty (a share needs none)
+#define CHECK_REFRESH(ctx, want_scheme, op, depth, batch, ws, ws_bytes)                                        \
+    do {                                                                                                       \
+        if ((ctx)->c.scheme != (want_scheme)) return fail(HEGPU_E_INVALID, "context scheme mismatch");         \
+        if ((batch) < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");                           \
+        if ((depth) < 0 || (depth) >= (ctx)->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");          \
+        if (!crs) return fail(HEGPU_E_INVALID, "null common random generator");                                \
+        if ((batch) == 0) return 0; /* an empty batch is a no-op */                                            \
+        {                                                                                                      \
+            const size_t need = hegpu_workspace_bytes(ctx, op, depth, batch);                                  \
+            if (need && (!(ws) || (ws_bytes) < need)) return fail(HEGPU_E_INVALID, "workspace too small");     \
+        }                                                                                                      \
+    } while (0)
+
+static int check_refresh_party(const hegpu_rng* crs, const hegpu_rng* rng, const void* ct, const void* sk,
+                               const void* share)
+{
+    if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
+    if (crs == rng)
+        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
+    if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
+    return 0;
+}
+
+// out [batch] items of 2 Q N words, out_stride apart, must share no word with the input batch or with a share
+static int check_refresh_out(const hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t ct_words,
+                             const uint64_t* const* shares, int k, uint64_t share_words, const uint64_t* out,
+                             uint64_t so, int batch)
+{
+    if (!ct || !out) return fail(HEGPU_E_INVALID, "null argument");
+    if (const int rc = check_shares(shares, k, out)) return rc;
+    const uint64_t out_words = (uint64_t) 2 * ctx->c.Q_size * ctx->c.n;
+    if (batch > 1 && (so < out_words || cs < ct_words))
+        return fail(HEGPU_E_INVALID, "the items of a batch overlap: stride below the size of an item");
+    if (spans_overlap(ct, cs, ct_words, out, so, out_words, batch))
+        return fail(HEGPU_E_INVALID, "the result overlaps the input ciphertexts");
+    for (int i = 0; i < k; i++)
+        if (spans_overlap(shares[i], share_words, share_words, out, so, out_words, batch))
+            return fail(HEGPU_E_INVALID, "the result overlaps a share");
+    return 0;
+}
+
+int hegpu_mpc_ckks_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
+                                 const uint64_t* sk, int depth, int mask_bits, uint64_t* share, int batch, void* ws,
+                                 size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (crs && crs == rng)
+        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
+    CHECK_REFRESH(ctx, SCHEME_CKKS, OP_MPC_REFRESH_SHARE, depth, batch, ws, ws_bytes);
+    if (const int rc = check_refresh_party(crs, rng, ct, sk, share)) return rc;
+    // 2^mask_bits >= Q_level / 2 can never be unmasked, whatever the message and the number of parties
+    if (mask_bits < 1 || mask_bits > 126 || mask_bits + 1 >= level_modulus_bits(ctx->c, ctx->c.Q_size - depth))
+        return fail(HEGPU_E_INVALID, "mask_bits must be in [1, 126] with 2^mask_bits below half the level's modulus");
+    return hip_ret(op_mpc_ckks_refresh_share(ctx->c, crs->r, rng->r, (const u64*) ct, cs, (const u64*) sk, depth,
+                                             mask_bits, (u64*) share, batch, (hipStream_t) stream),
+                   "hegpu_mpc_ckks_refresh_share");
+}
+
+int hegpu_mpc_ckks_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint64_t* ct, uint64_t cs,
+                                 const uint64_t* const* shares, int k, int depth, uint64_t* out, uint64_t so, int batch,
+                                 void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_REFRESH(ctx, SCHEME_CKKS, OP_MPC_REFRESH_MERGE, depth, batch, ws, ws_bytes);
+    const uint64_t l = (uint64_t) (ctx->c.Q_size - depth), Q = (uint64_t) ctx->c.Q_size;
+    if (const int rc = check_refresh_out(ctx, ct, cs, 2 * l * ctx->c.n, shares, k, (l + Q) * ctx->c.n, out, so, batch))
+        return rc;
+    return hip_ret(op_mpc_ckks_refresh_merge(ctx->c, crs->r, (const u64*) ct, cs, (const u64* const*) shares, k, depth,
+                                             (u64*) out, so, batch, (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_ckks_refresh_merge");
+}
+
+int hegpu_mpc_bfv_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
+                                const uint64_t* sk, uint64_t* share, int batch, void* ws, size_t ws_bytes,
+                                hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (crs && crs == rng)
+        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
+    CHECK_REFRESH(ctx, SCHEME_BFV, OP_MPC_REFRESH_SHARE, 0, batch, ws, ws_bytes);
+    if (const int rc = check_refresh_party(crs, rng, ct, sk, share)) return rc;
+    return hip_ret(op_mpc_bfv_refresh_share(ctx->c, crs->r, rng->r, (const u64*) ct, cs, (const u64*) sk, (u64*) share,
+                                            batch, (hipStream_t) stream),
+                   "hegpu_mpc_bfv_refresh_share");
+}
+
+int hegpu_mpc_bfv_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint64_t* ct, uint64_t cs,
+                                const uint64_t* const* shares, int k, uint64_t* out, uint64_t so, int batch, void* ws,
+                                size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_REFRESH(ctx, SCHEME_BFV, OP_MPC_REFRESH_MERGE, 0, batch, ws, ws_bytes);
+    const uint64_t words = (uint64_t) 2 * ctx->c.Q_size * ctx->c.n;
+    if (const int rc = check_refresh_out(ctx, ct, cs, words, shares, k, words, out, so, batch)) return rc;
+    return hip_ret(op_mpc_bfv_refresh_merge(ctx->c, crs->r, (const u64*) ct, cs, (const u64* const*) shares, k,
+                                            (u64*) out, so, batch, (u64*) ws, (hipStream_t) stream),
+                   "hegpu_mpc_bfv_refresh_merge");
+}
+
 int hegpu_bfv_encode(hegpu_context* ctx, const int64_t* message, int message_size, uint64_t* plain,
                      hegpu_stream stream)
 {

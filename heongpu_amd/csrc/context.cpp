@@ -177,6 +177,14 @@ void Context::build_host()
         host["new_prime_locations"] = ploc;
         hv.new_prime_locations = ploc;
         host["new_input_locations"] = iloc;
+        // collective refresh: the moduli of a party's share at depth d, [0 .. Q-d) then [0 .. Q) (one transform over both
+        // halves); row d starts at d * 2Q - d (d - 1) / 2
+        vec rloc;
+        for (int d = 0; d < Q; d++) {
+            for (int j = 0; j < Q - d; j++) rloc.push_back(j);
+            for (int j = 0; j < Q; j++) rloc.push_back(j);
+        }
+        host["mpc_refresh_order"] = rloc;
     }
 
     if (P > 1) {
@@ -686,7 +694,7 @@ hipError_t Context::upload()
         {"new_prime_locations", nullptr, &tab.new_prime_locations},
         {"new_input_locations", nullptr, &tab.new_input_locations}, {"m2_I_j", nullptr, &tab.m2_I_j},
         {"m2_I_location", nullptr, &tab.m2_I_location}, {"encoding_location", nullptr, &tab.encoding_location},
-        {"reverse_order", nullptr, &tab.reverse_order},
+        {"reverse_order", nullptr, &tab.reverse_order}, {"mpc_refresh_order", nullptr, &tab.mpc_refresh_order},
     };
     for (const auto& r : rows) {
         auto it = host.find(r.name);

@@ -52,7 +52,7 @@ struct DevTables {
     // CKKS (rescaled_*: empty with a single ciphertext prime, which has no rescale)
     const u64 *rescaled_last_q_modinv, *rescaled_half_mod, *rescaled_half;
     const u64 *Mi, *Mi_inv, *upper_half_threshold, *decryption_modulus, *special_fft_roots_table, *special_ifft_roots_table;
-    const int *new_prime_locations, *new_input_locations, *reverse_order;
+    const int *new_prime_locations, *new_input_locations, *reverse_order, *mpc_refresh_order;
     // BFV
     const u64 *coeff_div_plain_modulus, *upper_halfincrement, *Qi_t, *Qi_gamma, *Qi_inverse;
     // BFV with batching (plan_plain.count != 0)

@@ -3,6 +3,7 @@
 // [poly][limb][N] arrays (HBM-bound); the transforms between them are the NTT
 // kernels of the hot path.
 #include "keygen.hpp"
+#include "crt_compose.cuh"
 
 namespace hegpu {
 
@@ -747,6 +748,315 @@ hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64*
     for (int j = 0; j < k; j++) sh.p[j] = shares[j];
     hipLaunchKernelGGL(k_kg_mpc_bfv_merge, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0, c0_stride,
                        sh, k, mods, d, n_power, limbs);
+    return hipGetLastError();
+}
+
+// ---- collective refresh ("distributed bootstrapping", {ckks,bfv}/mpcmanager.cu:1575-1903 / 1563-1752; kernels
+// decryption.cu:480-667).  A share is two polynomials per ciphertext: h0 over the ciphertext's limbs and h1 over all
+// Q, both carrying the party's mask M with opposite signs.  The common `a` is never stored on the party's side: every
+// kernel that needs it draws it from the crs in place: item b takes stream id crs_stream + b (limb j, coefficient n at
+// index j N + n -- kg_uniform's order for one polynomial), and stream ids stream + 3 b .. + 3 b + 2 of the party's own
+// generator (e0, e1, mask; coefficient n at index n).  A batch of B items therefore draws what B calls of one item draw.
+
+// the `bits`-bit mask of one coefficient as the unsigned integer raw = M + 2^(bits - 1) in [0, 2^bits): the 128 bits of
+// one DRBG block, cut to size
+__device__ __forceinline__ void refresh_mask_raw(const DrbgKey& seed, u64 stream, u64 index, int bits, u64& hi, u64& lo)
+{
+    const DrbgOut o = drbg_block(seed, stream, index);
+    lo = (u64) o.w[0] | ((u64) o.w[1] << 32);
+    hi = (u64) o.w[2] | ((u64) o.w[3] << 32);
+    if (bits < 64) {
+        lo &= (1ull << bits) - 1;
+        hi = 0;
+    } else {
+        hi &= (1ull << (bits - 64)) - 1;
+    }
+}
+
+// CKKS sampler: share[b] = [ (e0 - M) mod q_j, j < l | (e1 + M) mod q_j, j < Q ], coefficient domain; e0, e1 rounded
+// Gaussians (streams +0, +1 of the item), M uniform in [-2^(bits-1), 2^(bits-1)) (stream +2).  One pass, no mask buffer.
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_noise(u64* __restrict__ share,
+                                                                     const Mod* __restrict__ mods, int n_power, int l,
+                                                                     int limbs, DrbgKey seed, u64 stream, GaussCdt cdt,
+                                                                     int bits)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int b = blockIdx.y;
+    const u64 at = n;
+    stream += 3 * (u64) b;
+    const int e00 = drbg_gaussian(seed, stream, at, cdt), e01 = drbg_gaussian(seed, stream, at + 1, cdt);
+    const int e10 = drbg_gaussian(seed, stream + 1, at, cdt), e11 = drbg_gaussian(seed, stream + 1, at + 1, cdt);
+    u64 h0, l0, h1, l1;
+    refresh_mask_raw(seed, stream + 2, at, bits, h0, l0);
+    refresh_mask_raw(seed, stream + 2, at + 1, bits, h1, l1);
+    const u64 half_hi = bits > 64 ? 1ull << (bits - 65) : 0, half_lo = bits > 64 ? 0 : 1ull << (bits - 1);
+    u64* item = share + (((u64) b * (l + limbs)) << n_power) + n;
+    for (int j = 0; j < limbs; j++) {
+        const Mod m = mods[j];
+        const u64 half = reduce128(half_hi, half_lo, m);
+        const u64x2 mask{sub_mod(reduce128(h0, l0, m), half, m.q), sub_mod(reduce128(h1, l1, m), half, m.q)};
+        st2(item + ((u64) (l + j) << n_power), add2(u64x2{lift_small(e10, m.q), lift_small(e11, m.q)}, mask, m.q));
+        if (j < l) st2(item + ((u64) j << n_power), sub2(u64x2{lift_small(e00, m.q), lift_small(e01, m.q)}, mask, m.q));
+    }
+}
+
+hipError_t kg_mpc_refresh_noise(u64* share, const Mod* mods, int n_power, int l, int limbs, int batch, DrbgKey seed,
+                                u64 stream, const GaussCdt& cdt, int mask_bits, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_refresh_noise, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, share, mods,
+                       n_power, l, limbs, seed, stream, cdt, mask_bits);
+    return hipGetLastError();
+}
+
+// Both halves of a share in one pass (the reference: sk_multiplication twice, `addition` twice, temporaries):
+//   y < l:   h0[y]     = c1[y] * s[y]                      (+ what h0 holds: the transformed e0 - M)
+//   y >= l:  h1[y - l] = -(a[y - l] * s[y - l])            (+ what h1 holds: the transformed e1 + M)
+// share [batch][l + limbs][N]; c1 of item b at c1 + b * c1_stride (BFV: the share's own first half, add = 0)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride,
+                                                                     const u64* __restrict__ sk,
+                                                                     const Mod* __restrict__ mods, int n_power, int l,
+                                                                     int limbs, DrbgKey crs, u64 crs_stream, int add)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, b = blockIdx.z;
+    const int j = y < l ? y : y - l;
+    const Mod m = mods[j];
+    const u64 lane = n + ((u64) j << n_power);
+    u64* dst = share + (((u64) b * (l + limbs) + y) << n_power) + n;
+    const u64x2 s = ld2(sk + lane);
+    u64x2 v;
+    if (y < l) {
+        v = mul2(ld2(c1 + lane + c1_stride * b), s, m);
+    } else {
+        const u64 at = ((u64) j << n_power) + n;
+        const u64x2 a{drbg_uniform(crs, crs_stream + b, at, m), drbg_uniform(crs, crs_stream + b, at + 1, m)};
+        v = sub2(u64x2{0, 0}, mul2(a, s, m), m.q);
+    }
+    if (add) v = add2(v, ld2(dst), m.q);
+    st2(dst, v);
+}
+
+hipError_t kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
+                                int l, int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_refresh_share, vec_grid(n_power, l + limbs, batch), dim3(KG_THREADS), 0, st, share, c1,
+                       c1_stride, sk, mods, n_power, l, limbs, crs, crs_stream, add);
+    return hipGetLastError();
+}
+
+// D(m): limb y of the scaled plaintext of k_kg_bfv_message_add (Delta * m + the rounding fix, encryption.cu:158-172)
+__device__ __forceinline__ u64 bfv_scaled_plain(u64 message, const Mod& m, u64 coeff_div, const BfvPlainScale& p)
+{
+    u64 fix = message * p.Q_mod_t;
+    fix = fix + p.upper_threshold;
+    fix = (u64) (long long) (int) (fix / p.t);
+    return add_mod(mul_barrett(message, coeff_div, m), fix, m.q);
+}
+
+// BFV shares live in the coefficient domain: after the inverse transform of both halves
+//   h0[b][j] += e0 - D(M),  h1[b][j] += e1 + D(M),   M uniform in [0, t)^N (stream +2), e0 / e1 streams +0 / +1
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_bfv_noise(u64* __restrict__ share,
+                                                                         const Mod* __restrict__ mods,
+                                                                         const u64* __restrict__ coeff_div,
+                                                                         BfvPlainScale p, Mod plain, int n_power,
+                                                                         int limbs, DrbgKey seed, u64 stream,
+                                                                         GaussCdt cdt)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int b = blockIdx.y;
+    const u64 at = n;
+    stream += 3 * (u64) b;
+    const int e00 = drbg_gaussian(seed, stream, at, cdt), e01 = drbg_gaussian(seed, stream, at + 1, cdt);
+    const int e10 = drbg_gaussian(seed, stream + 1, at, cdt), e11 = drbg_gaussian(seed, stream + 1, at + 1, cdt);
+    const u64 m0 = drbg_uniform(seed, stream + 2, at, plain), m1 = drbg_uniform(seed, stream + 2, at + 1, plain);
+    u64* item = share + (((u64) b * 2 * limbs) << n_power) + n;
+    for (int j = 0; j < limbs; j++) {
+        const Mod m = mods[j];
+        const u64 cd = coeff_div[j];
+        const u64x2 d{bfv_scaled_plain(m0, m, cd, p), bfv_scaled_plain(m1, m, cd, p)};
+        u64* p0 = item + ((u64) j << n_power);
+        u64* p1 = p0 + ((u64) limbs << n_power);
+        st2(p0, add2(ld2(p0), sub2(u64x2{lift_small(e00, m.q), lift_small(e01, m.q)}, d, m.q), m.q));
+        st2(p1, add2(ld2(p1), add2(u64x2{lift_small(e10, m.q), lift_small(e11, m.q)}, d, m.q), m.q));
+    }
+}
+
+hipError_t kg_mpc_refresh_bfv_noise(u64* share, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,
+                                    int n_power, int limbs, int batch, DrbgKey seed, u64 stream, const GaussCdt& cdt,
+                                    hipStream_t st)
+{
+    hipLaunchKernelGGL(k_kg_mpc_refresh_bfv_noise, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, share, mods,
+                       coeff_div, p, make_mod(p.t), n_power, limbs, seed, stream, cdt);
+    return hipGetLastError();
+}
+
+// The coordinator's k-way sums read one half of every share: item b, limb y of share j at
+// sh.p[j] + b * sh_stride + sh_off + y * N.  k_kg_mpc_merge's body with those strides:
+//   out[b][y] = base[b][y] + sum_j share_j[b][y]     (out items out_stride apart, base items base_stride apart)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base,
+                                                                   u64 base_stride, MpcShares sh, int k, u64 sh_stride,
+                                                                   u64 sh_off, const Mod* __restrict__ mods,
+                                                                   int n_power)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, b = blockIdx.z;
+    const u64 q = mods[y].q;
+    const u64 lane = n + ((u64) y << n_power);
+    u64x2 acc = ld2(base + lane + base_stride * b);
+    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + sh_off + lane), q);
+    st2(out + lane + out_stride * b, acc);
+}
+
+hipError_t kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares,
+                              int k, u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch,
+                              hipStream_t st)
+{
+    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
+        MpcShares sh{};
+        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
+        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+        hipLaunchKernelGGL(k_kg_mpc_refresh_sum, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, out,
+                           out_stride, done ? out : base, done ? out_stride : base_stride, sh, cnt, sh_stride, sh_off,
+                           mods, n_power);
+    }
+    return hipGetLastError();
+}
+
+// Exact centred lift of t [batch][l][N] (coefficient domain, basis q_0..q_{l-1}) into out [batch][limbs][N] (items
+// out_stride apart): with x the integer in (-M/2, M/2) that t stands for, M = q_0 ... q_{l-1}, limb j of the result is
+// x mod q_j.  Limbs below l are copies.  For the others the coefficient is composed into words (the CKKS decoder's
+// crt_compose_words: the canonical value in [0, M) and on which side of (M + 1) / 2 it lies), the words are reduced by
+// Horner's rule in base 2^64, and M mod q_j -- reduced the same way -- is subtracted when x is negative.  Integer
+// arithmetic throughout: the result is a function of t alone.  One thread per coefficient, one wavefront per workgroup,
+// LMAX as in encode.hip.
+template <int LMAX>
+__global__ __launch_bounds__(EN_COMPOSE_THREADS) void k_kg_mpc_refresh_lift(u64* __restrict__ out, u64 out_stride,
+                                                                            const u64* __restrict__ t,
+                                                                            const Mod* __restrict__ mods,
+                                                                            const u64* __restrict__ Mi_inv,
+                                                                            const u64* __restrict__ Mi,
+                                                                            const u64* __restrict__ upper_half,
+                                                                            const u64* __restrict__ M, int l, int limbs,
+                                                                            int n_power)
+{
+    const u64 idx = (u64) blockIdx.x * EN_COMPOSE_THREADS + threadIdx.x;
+    const int b = blockIdx.y;
+    const u64* src = t + (((u64) b * l) << n_power);
+    u64* dst = out + out_stride * b + idx;
+    __shared__ u64 tl[LMAX * EN_COMPOSE_THREADS];
+    u64 acc[LMAX];
+    const bool negative = crt_compose_words<LMAX>(acc, src, idx, mods, Mi_inv, Mi, upper_half, M, l, n_power, tl);
+    for (int j = 0; j < l; j++) dst[(u64) j << n_power] = src[idx + ((u64) j << n_power)];
+    // the words go back to the thread's own column of `tl` (free once the value is composed): the loops below index them
+    // by a run-time k, which registers cannot be
+#pragma unroll
+    for (int k = 0; k < LMAX; k++) {
+        if (k < l) tl[k * EN_COMPOSE_THREADS + threadIdx.x] = acc[k];
+    }
+    for (int j = l; j < limbs; j++) {
+        const Mod m = mods[j];
+        u64 r = 0, mr = 0;
+        for (int k = l - 1; k >= 0; k--) {
+            r = reduce128(r, tl[k * EN_COMPOSE_THREADS + threadIdx.x], m);
+            mr = reduce128(mr, M[k], m);
+        }
+        dst[(u64) j << n_power] = negative ? sub_mod(r, mr, m.q) : r;
+    }
+}
+
+hipError_t kg_mpc_refresh_lift(u64* out, u64 out_stride, const u64* t, const Mod* mods, const u64* Mi_inv,
+                               const u64* Mi, const u64* upper_half, const u64* M, int l, int limbs, int n_power,
+                               int batch, hipStream_t st)
+{
+    if (l > EN_MAX_WORDS) return hipErrorInvalidValue;
+    const dim3 grid((1u << n_power) / EN_COMPOSE_THREADS, batch), block(EN_COMPOSE_THREADS);
+#define KG_LIFT(LM) hipLaunchKernelGGL(k_kg_mpc_refresh_lift<LM>, grid, block, 0, st, out, out_stride, t, mods, Mi_inv, Mi, upper_half, M, l, limbs, n_power)
+    if (l <= 8) KG_LIFT(8);
+    else if (l <= 16) KG_LIFT(16);
+    else if (l <= 32) KG_LIFT(32);
+    else KG_LIFT(EN_MAX_WORDS);
+#undef KG_LIFT
+    return hipGetLastError();
+}
+
+// The refreshed ciphertext, out [batch][2][limbs][N] (items out_stride apart):
+//   part 0 = (add_out: what it holds -- the lifted polynomial, or an earlier group's sum) + sum_j h1_j
+//            (+ D(plain[b]), BFV: plain [batch][N] mod t);   part 1 = a, drawn from the crs as the parties drew it
+//            (write_a; NTT domain)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_finish(u64* out, u64 out_stride, MpcShares sh, int k,
+                                                                      u64 sh_stride, u64 sh_off, int add_out,
+                                                                      const u64* __restrict__ plain,
+                                                                      const u64* __restrict__ coeff_div,
+                                                                      BfvPlainScale p, const Mod* __restrict__ mods,
+                                                                      int n_power, DrbgKey crs, u64 crs_stream,
+                                                                      int write_a)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int y = blockIdx.y, b = blockIdx.z, limbs = gridDim.y;
+    const Mod m = mods[y];
+    const u64 lane = n + ((u64) y << n_power);
+    u64* dst = out + out_stride * b + lane;
+    u64x2 acc = add_out ? ld2(dst) : u64x2{0, 0};
+    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + sh_off + lane), m.q);
+    if (plain) {
+        const u64x2 v = ld2(plain + ((u64) b << n_power) + n);
+        const u64 cd = coeff_div[y];
+        acc = add2(acc, u64x2{bfv_scaled_plain(v.x, m, cd, p), bfv_scaled_plain(v.y, m, cd, p)}, m.q);
+    }
+    st2(dst, acc);
+    if (write_a) {
+        const u64 at = ((u64) y << n_power) + n;
+        st2(dst + ((u64) limbs << n_power),
+            u64x2{drbg_uniform(crs, crs_stream + b, at, m), drbg_uniform(crs, crs_stream + b, at + 1, m)});
+    }
+}
+
+hipError_t kg_mpc_refresh_finish(u64* out, u64 out_stride, const u64* const* shares, int k, u64 sh_stride, u64 sh_off,
+                                 int add_out, const u64* plain, const u64* coeff_div, const BfvPlainScale& p,
+                                 const Mod* mods, int n_power, int limbs, int batch, DrbgKey crs, u64 crs_stream,
+                                 hipStream_t st)
+{
+    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
+        MpcShares sh{};
+        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
+        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+        hipLaunchKernelGGL(k_kg_mpc_refresh_finish, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, out,
+                           out_stride, sh, cnt, sh_stride, sh_off, done ? 1 : add_out, done ? nullptr : plain,
+                           coeff_div, p, mods, n_power, crs, crs_stream, done ? 0 : 1);
+    }
+    return hipGetLastError();
+}
+
+// BFV coordinator, first step: k_kg_mpc_bfv_merge's sum and scale-and-round over the h0 halves of refresh shares;
+// plain [batch][N] mod t, k <= KG_MPC_MAX_SHARES
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_bfv_round(u64* __restrict__ plain,
+                                                                         const u64* __restrict__ c0, u64 c0_stride,
+                                                                         MpcShares sh, int k, u64 sh_stride,
+                                                                         const Mod* __restrict__ mods, BfvDecryptDev d,
+                                                                         int n_power, int limbs)
+{
+    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
+    const int b = blockIdx.y;
+    u64 t0 = 0, g0 = 0, t1 = 0, g1 = 0;
+    for (int i = 0; i < limbs; i++) {
+        const Mod m = mods[i];
+        const u64 lane = n + ((u64) i << n_power);
+        u64x2 acc = ld2(c0 + lane + c0_stride * b);
+        for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + lane), m.q);
+        bfv_round_limb(acc.x, i, m, d, t0, g0);
+        bfv_round_limb(acc.y, i, m, d, t1, g1);
+    }
+    st2(plain + ((u64) b << n_power) + n, u64x2{bfv_round_finish(t0, g0, d), bfv_round_finish(t1, g1, d)});
+}
+
+hipError_t kg_mpc_refresh_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k,
+                                    u64 sh_stride, const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs,
+                                    int batch, hipStream_t st)
+{
+    MpcShares sh{};
+    for (int j = 0; j < k; j++) sh.p[j] = shares[j];
+    hipLaunchKernelGGL(k_kg_mpc_refresh_bfv_round, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0,
+                       c0_stride, sh, k, sh_stride, mods, d, n_power, limbs);
     return hipGetLastError();
 }
 

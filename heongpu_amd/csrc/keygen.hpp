@@ -93,6 +93,40 @@ hipError_t kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* con
 hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
                             const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st);
 
+// ---- collective refresh (mpcmanager.cu distributed_bootstrapping_*; decryption.cu:480-667).  Shares: CKKS
+// [batch][l + limbs][N] (h0 over the l current limbs, h1 over all), BFV [batch][2][limbs][N].  `a` is drawn in place:
+// item b from stream crs_stream + b, limb j, coefficient n at index j * N + n (kg_uniform's order for one polynomial).
+struct BfvPlainScale {
+    u64 Q_mod_t, upper_threshold, t;
+};
+// share[b] = [(e0 - M) mod q_j, j < l | (e1 + M) mod q_j, j < limbs], coefficient domain; item b: streams stream + 3 b ..
+hipError_t kg_mpc_refresh_noise(u64* share, const Mod* mods, int n_power, int l, int limbs, int batch, DrbgKey seed,
+                                u64 stream, const GaussCdt& cdt, int mask_bits, hipStream_t st);
+// h0 = c1 * s (+ h0), h1 = -(a * s) (+ h1); add: the share holds the transformed noise
+hipError_t kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
+                                int l, int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st);
+// BFV, coefficient domain: h0 += e0 - D(M), h1 += e1 + D(M); item b: streams stream + 3 b ..
+hipError_t kg_mpc_refresh_bfv_noise(u64* share, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,
+                                    int n_power, int limbs, int batch, DrbgKey seed, u64 stream, const GaussCdt& cdt,
+                                    hipStream_t st);
+// out[b][y] = base[b][y] + sum_j share_j[b * sh_stride + sh_off + y * N], y < limbs; any k (groups of 16)
+hipError_t kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares,
+                              int k, u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch,
+                              hipStream_t st);
+// exact centred lift of t [batch][l][N] from q_0..q_{l-1} to q_0..q_{limbs-1}, coefficient domain
+hipError_t kg_mpc_refresh_lift(u64* out, u64 out_stride, const u64* t, const Mod* mods, const u64* Mi_inv,
+                               const u64* Mi, const u64* upper_half, const u64* M, int l, int limbs, int n_power,
+                               int batch, hipStream_t st);
+// out[b] = ((add_out ? out[b][0] : 0) + sum_j h1_j[b] (+ D(plain[b])), a); any k (groups of 16)
+hipError_t kg_mpc_refresh_finish(u64* out, u64 out_stride, const u64* const* shares, int k, u64 sh_stride, u64 sh_off,
+                                 int add_out, const u64* plain, const u64* coeff_div, const BfvPlainScale& p,
+                                 const Mod* mods, int n_power, int limbs, int batch, DrbgKey crs, u64 crs_stream,
+                                 hipStream_t st);
+// plain[b] = scale-and-round(c0[b] + sum_j h0_j[b]); k <= KG_MPC_MAX_SHARES
+hipError_t kg_mpc_refresh_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k,
+                                    u64 sh_stride, const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs,
+                                    int batch, hipStream_t st);
+
 // encode_kernel_bfv / decode_kernel_bfv (encoding.cu:11-41): slot idx <-> position location[idx]
 hipError_t kg_bfv_encode_scatter(u64* out, const long long* message, const int* location, u64 t, int message_size,
                                  int n_power, hipStream_t st);

@@ -192,6 +192,10 @@ size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
         case OP_CKKS_DECODE: per = (u64) (l + 1) * n; break;         // coefficient-domain copy + complex
         case OP_MPC_KEY_SHARE: per = (u64) 3 * Q * Qp * n; break;    // relin round 1: e0, e1, a per digit (the largest)
         case OP_MPC_BFV_DECRYPT_MERGE: per = (u64) Q * n; break;     // c0 + the shares beyond the first group
+        case OP_MPC_REFRESH_SHARE: per = 0; break;                   // the noise is sampled and transformed in the share itself
+        case OP_MPC_REFRESH_MERGE:                                   // CKKS: t = c0 + sum h0; BFV: m' and the h0 sum beyond 16 shares
+            per = c.scheme == SCHEME_CKKS ? (u64) l * n : (u64) (Q + 1) * n;
+            break;
         default: return 0;
     }
     return per * (u64) batch;
@@ -1172,6 +1176,117 @@ hipError_t op_mpc_bfv_decrypt_merge(const Context& c, const u64* ct, u64 cs, con
                                 batch, st);
     }
     return kg_mpc_bfv_merge(plain, ct, cs, shares, k, mods, bfv_decrypt_dev(c), np, Q, batch, st);
+}
+
+// ------------------------------------------------------------------ collective refresh
+int level_modulus_bits(const Context& c, int l)
+{
+    std::vector<u64> big{1};
+    for (int j = 0; j < l; j++) {
+        unsigned __int128 carry = 0;
+        for (u64& w : big) {
+            const unsigned __int128 v = (unsigned __int128) w * c.primes[j] + carry;
+            w = (u64) v;
+            carry = v >> 64;
+        }
+        if (carry) big.push_back((u64) carry);
+    }
+    return 64 * (int) (big.size() - 1) + (64 - __builtin_clzll(big.back()));
+}
+
+// the first of `count` stream ids, one per item of the batch
+static u64 take_streams(Rng& r, int count)
+{
+    const u64 first = r.stream;
+    r.stream += (u64) count;
+    return first;
+}
+
+static BfvPlainScale bfv_plain_scale(const Context& c)
+{
+    return BfvPlainScale{c.hv.Q_mod_t, c.hv.upper_threshold, c.plain_modulus};
+}
+
+hipError_t op_mpc_ckks_refresh_share(const Context& c, Rng& crs, Rng& r, const u64* ct, u64 cs, const u64* sk,
+                                     int depth, int mask_bits, u64* share, int batch, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size, l = Q - depth;
+    const Mod* mods = c.plan_qp.mods;
+    TRY(kg_mpc_refresh_noise(share, mods, np, l, Q, batch, r.seed, r.stream, c.gauss_cdt, mask_bits, st));
+    r.stream += 3 * (u64) batch;
+    NttArgs a = c.ntt_args(0); // one transform over both halves: moduli 0..l-1, then 0..Q-1
+    a.in = share; a.out = share; a.mod_count = l + Q;
+    a.mod_order = c.tab.mpc_refresh_order + (depth * 2 * Q - depth * (depth - 1) / 2);
+    a.polys_per_item = l + Q; a.in_item_stride = a.out_item_stride = (u64) (l + Q) << np;
+    TRY(ntt_launch(a, batch * (l + Q), false, st));
+    return kg_mpc_refresh_share(share, ct + ((u64) l << np), cs, sk, mods, np, l, Q, batch, crs.seed, take_streams(crs, batch), 1,
+                                st);
+}
+
+hipError_t op_mpc_ckks_refresh_merge(const Context& c, Rng& crs, const u64* ct, u64 cs, const u64* const* shares,
+                                     int k, int depth, u64* out, u64 so, int batch, u64* ws, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size, l = Q - depth;
+    const Mod* mods = c.plan_qp.mods;
+    const u64 sh_stride = (u64) (l + Q) << np, t_stride = (u64) l << np;
+    u64* t = ws; // [batch][l][N]
+    TRY(kg_mpc_refresh_sum(t, t_stride, ct, cs, shares, k, sh_stride, 0, mods, np, l, batch, st));
+    NttArgs a = c.ntt_args(0);
+    a.in = t; a.out = t; a.mod_count = l;
+    TRY(ntt_launch(a, batch * l, true, st));
+    const int loc1 = triangle_offset(Q, depth);
+    int loc2 = 0;
+    for (int i = 0; i < depth; i++) loc2 += (Q - i) * (Q - i);
+    TRY(kg_mpc_refresh_lift(out, so, t, mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2, c.tab.upper_half_threshold + loc1,
+                            c.tab.decryption_modulus + loc1, l, Q, np, batch, st));
+    a.in = out; a.out = out; a.mod_count = Q;
+    a.polys_per_item = Q; a.in_item_stride = a.out_item_stride = so;
+    TRY(ntt_launch(a, batch * Q, false, st));
+    return kg_mpc_refresh_finish(out, so, shares, k, sh_stride, t_stride, 1, nullptr, nullptr, BfvPlainScale{}, mods,
+                                 np, Q, batch, crs.seed, take_streams(crs, batch), st);
+}
+
+hipError_t op_mpc_bfv_refresh_share(const Context& c, Rng& crs, Rng& r, const u64* ct, u64 cs, const u64* sk,
+                                    u64* share, int batch, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    const u64 sh_stride = (u64) (2 * Q) << np;
+    NttArgs a = c.ntt_args(0);
+    a.in = ct + ((u64) Q << np); a.out = share; a.mod_count = Q;
+    a.polys_per_item = Q; a.in_item_stride = cs; a.out_item_stride = sh_stride;
+    TRY(ntt_launch(a, batch * Q, false, st));
+    TRY(kg_mpc_refresh_share(share, share, sh_stride, sk, mods, np, Q, Q, batch, crs.seed, take_streams(crs, batch), 0, st));
+    a.in = share; a.polys_per_item = 0;
+    TRY(ntt_launch(a, batch * 2 * Q, true, st));
+    TRY(kg_mpc_refresh_bfv_noise(share, mods, c.tab.coeff_div_plain_modulus, bfv_plain_scale(c), np, Q, batch, r.seed,
+                                 r.stream, c.gauss_cdt, st));
+    r.stream += 3 * (u64) batch;
+    return hipSuccess;
+}
+
+hipError_t op_mpc_bfv_refresh_merge(const Context& c, Rng& crs, const u64* ct, u64 cs, const u64* const* shares,
+                                    int k, u64* out, u64 so, int batch, u64* ws, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    const u64 sh_stride = (u64) (2 * Q) << np, part = (u64) Q << np;
+    u64* plain = ws;                          // [batch][N]
+    u64* head_sum = ws + ((u64) batch << np); // [batch][Q][N], beyond 16 shares
+    if (k > KG_MPC_MAX_SHARES) {
+        const int head = (k - 1) / KG_MPC_MAX_SHARES * KG_MPC_MAX_SHARES;
+        TRY(kg_mpc_refresh_sum(head_sum, part, ct, cs, shares, head, sh_stride, 0, mods, np, Q, batch, st));
+        TRY(kg_mpc_refresh_bfv_round(plain, head_sum, part, shares + head, k - head, sh_stride, mods,
+                                     bfv_decrypt_dev(c), np, Q, batch, st));
+    } else {
+        TRY(kg_mpc_refresh_bfv_round(plain, ct, cs, shares, k, sh_stride, mods, bfv_decrypt_dev(c), np, Q, batch, st));
+    }
+    TRY(kg_mpc_refresh_finish(out, so, shares, k, sh_stride, part, 0, plain, c.tab.coeff_div_plain_modulus,
+                              bfv_plain_scale(c), mods, np, Q, batch, crs.seed, take_streams(crs, batch), st));
+    NttArgs a = c.ntt_args(0); // c1' = INTT(a)
+    a.in = out + part; a.out = out + part; a.mod_count = Q;
+    a.polys_per_item = Q; a.in_item_stride = a.out_item_stride = so;
+    return ntt_launch(a, batch * Q, true, st);
 }
 
 } // namespace hegpu

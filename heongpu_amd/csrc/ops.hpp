@@ -9,7 +9,7 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
        OP_BFV_GALOIS = 6, OP_KEYGEN_SECRET = 7, OP_KEYGEN_PUBLIC = 8, OP_KEYGEN_SWITCH = 9, OP_CKKS_ENCRYPT = 10, OP_BFV_ENCRYPT = 11,
        OP_BFV_DECRYPT = 12, OP_BFV_DECODE = 13, OP_CKKS_ENCODE = 14,
        OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17, OP_MPC_KEY_SHARE = 18,
-       OP_MPC_BFV_DECRYPT_MERGE = 19 };
+       OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21 };
 
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
@@ -121,5 +121,20 @@ hipError_t op_mpc_ckks_decrypt_merge(const Context& c, const u64* ct, u64 cs, co
                                      int depth, u64* plain, int batch, hipStream_t st);
 hipError_t op_mpc_bfv_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
                                     u64* plain, int batch, u64* ws, hipStream_t st);
+
+// distributed_bootstrapping_participant / _coordinator (ckks/mpcmanager.cu:1575-1903, bfv/mpcmanager.cu:1563-1752).
+// Share: CKKS [batch][(Q - depth) + Q][N] NTT domain, BFV [batch][2][Q][N] coefficient domain; out [batch][2][Q][N]
+// (CKKS: depth 0).  crs advances by one stream id per item (the common a: item b = the b-th draw of Q limbs), r by
+// three per item (e0, e1, the mask): a batch draws what as many calls of one item draw.
+// bit length of q_0 ... q_{l-1}
+int level_modulus_bits(const Context& c, int l);
+hipError_t op_mpc_ckks_refresh_share(const Context& c, Rng& crs, Rng& r, const u64* ct, u64 cs, const u64* sk,
+                                     int depth, int mask_bits, u64* share, int batch, hipStream_t st);
+hipError_t op_mpc_ckks_refresh_merge(const Context& c, Rng& crs, const u64* ct, u64 cs, const u64* const* shares,
+                                     int k, int depth, u64* out, u64 so, int batch, u64* ws, hipStream_t st);
+hipError_t op_mpc_bfv_refresh_share(const Context& c, Rng& crs, Rng& r, const u64* ct, u64 cs, const u64* sk,
+                                    u64* share, int batch, hipStream_t st);
+hipError_t op_mpc_bfv_refresh_merge(const Context& c, Rng& crs, const u64* ct, u64 cs, const u64* const* shares,
+                                    int k, u64* out, u64 so, int batch, u64* ws, hipStream_t st);
 
 } // namespace hegpu

@@ -269,7 +269,9 @@ enum {
     HEGPU_OP_BFV_MULTIPLY_PLAIN = 16,
     HEGPU_OP_CKKS_ROTATE_HOISTED = 17, /* hegpu_ckks_rotate_hoisted with room for four accumulators */
     HEGPU_OP_MPC_KEY_SHARE = 18,        /* every hegpu_mpc_*_key_share* entry */
-    HEGPU_OP_MPC_BFV_DECRYPT_MERGE = 19 /* per ciphertext of the batch */
+    HEGPU_OP_MPC_BFV_DECRYPT_MERGE = 19, /* per ciphertext of the batch */
+    HEGPU_OP_MPC_REFRESH_SHARE = 20,     /* hegpu_mpc_*_refresh_share: 0 bytes, the share is built in place */
+    HEGPU_OP_MPC_REFRESH_MERGE = 21      /* hegpu_mpc_*_refresh_merge; per item: CKKS (Q - depth) N words, BFV (Q + 1) N */
 };
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch);
 
@@ -442,6 +444,47 @@ int hegpu_mpc_bfv_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64
 int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride,
                                 const uint64_t* const* shares, int k, uint64_t* plain, int batch, void* ws,
                                 size_t ws_bytes, hegpu_stream stream);
+
+/* ---- collective refresh ("distributed bootstrapping") ----
+ * HEMultiPartyManager::distributed_bootstrapping_participant / _coordinator (ckks/mpcmanager.cu:1575-1903,
+ * bfv/mpcmanager.cu:1563-1752; kernels decryption.cu:480-667): the parties re-encrypt a ciphertext they can only decrypt
+ * together, without anybody seeing the plaintext -- the one operation of this library that brings an exhausted
+ * ciphertext (CKKS: last level; BFV: noise budget spent) back.  Batched like collective decryption: item b of ct at
+ * ct + b * ct_stride, one `a`, one mask and one pair of errors per item.  crs and rng as above (the same object for
+ * both: HEGPU_E_INVALID).  DRAW ORDER: every item takes one stream of crs -- item b's `a` is the b-th draw of Q limbs --
+ * and three of rng (e0, e1, mask), so a batch of B items draws exactly what B calls of one item draw, in order; the
+ * parties and the coordinator must start from equally advanced crs generators.  Workspaces: HEGPU_OP_MPC_REFRESH_SHARE (zero bytes: ws may be NULL) / _MERGE.
+ * HEGPU_E_INVALID: crs == rng, null pointers with batch > 0, k < 1, wrong scheme, depth out of range, the mask rule
+ * below, `out` overlapping the input or a share.  batch == 0: no-op, returns 0.
+ * SECURITY: as for collective decryption, the errors are fresh sigma = 3.2 samples and there is NO smudging noise.
+ *
+ * CKKS (NTT domain; input [2][l][N] at `depth`, l = Q - depth; result [2][Q][N] at depth 0, scale unchanged):
+ *   share [batch][l + Q][N] = ( h0 = c1 * s_i + NTT(e0 - M_i) over the l current limbs,
+ *                               h1 = -(a * s_i) + NTT(e1 + M_i) over all Q limbs ),
+ *   M_i an integer polynomial with coefficients uniform in [-2^(mask_bits-1), 2^(mask_bits-1)), 1 <= mask_bits <= 126
+ *   (the reference: the encoding of N(0, 3.2) slot values, which hides nothing of a larger message).
+ *   merge: t = c0 + sum h0_i -> INTT -> exact centred lift from q_0..q_{l-1} to q_0..q_{Q-1} -> NTT ->
+ *   out = (lift + sum h1_i, a).  (The reference decodes t to doubles and encodes it again at the manager's scale:
+ *   53 bits, two FFTs, right only when the ciphertext's scale is the manager's.)  With m~ the centred value of
+ *   c0 + c1 s mod Q_level:  out[0] + out[1] * s = m~ + sum_i (e0_i + e1_i) in every limb.
+ *   CORRECTNESS needs  k * 2^(mask_bits-1) + |m~| + 2 k B < Q_level / 2  (B = 20, the clip of an error sample): the
+ *   entry knows neither k nor the message and refuses only what can never work, 2^mask_bits >= Q_level / 2.
+ * BFV (coefficient domain, Q limbs; D(.) the scaled plaintext of hegpu_bfv_encrypt):
+ *   share [batch][2][Q][N] = ( INTT(NTT(c1) * s_i) + e0 - D(M_i),  INTT(-(a * s_i)) + e1 + D(M_i) ), M_i uniform
+ *   in [0, t)^N;  merge: m' = scale-and-round(c0 + sum h0_i), out = (sum h1_i + D(m'), INTT(a)).
+ * shares: HOST array of k >= 1 DEVICE pointers; more than 16 go through in groups. */
+int hegpu_mpc_ckks_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* ct,
+                                 uint64_t ct_stride, const uint64_t* sk, int depth, int mask_bits, uint64_t* share,
+                                 int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+int hegpu_mpc_ckks_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint64_t* ct, uint64_t ct_stride,
+                                 const uint64_t* const* shares, int k, int depth, uint64_t* out, uint64_t out_stride,
+                                 int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+int hegpu_mpc_bfv_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* ct,
+                                uint64_t ct_stride, const uint64_t* sk, uint64_t* share, int batch, void* ws,
+                                size_t ws_bytes, hegpu_stream stream);
+int hegpu_mpc_bfv_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint64_t* ct, uint64_t ct_stride,
+                                const uint64_t* const* shares, int k, uint64_t* out, uint64_t out_stride, int batch,
+                                void* ws, size_t ws_bytes, hegpu_stream stream);
 
 /* HEEncoder<BFV>::encode_bfv / decode_bfv (src/lib/host/bfv/encoder.cu:21-95, 213-249,
  * kernel/encoding.cu:11-41): batching over the slots of Z_t[X]/(X^N+1).  message: device int64

@@ -2991,6 +2991,64 @@ template <Scheme S> class MultiPartyManagerBase {
         plaintext.plaintext_generated_ = true;
     }
 
+    // Collective refresh (distributed_bootstrapping_participant / _coordinator, ckks/mpcmanager.cuh:454-560,
+    // bfv/mpcmanager.cuh).  The share is a 2-part object as in the reference -- CKKS (h0 over the input's limbs, h1 over
+    // all Q), BFV (h0, h1) -- that carries the input's depth and scale; the result is a 2-part ciphertext at depth 0 whose
+    // scale and encoding are the input's (the coordinator raises the modulus by an exact integer lift, which changes
+    // neither).  The reference's signature has no mask width: bits(Q_level) - 8, capped at 126, leaves room for 64
+    // parties (64 * 2^(bits - 9) = Q_level / 8) next to a message below Q_level / 4.
+    void distributed_bootstrapping_participant(Ciphertext<S>& common, Ciphertext<S>& output, Secretkey<S>& sk,
+                                               const RNGSeed& seed, const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
+        const DeviceVector<Data64> moved = refresh_input(common, o);
+        const uint64_t* ct = moved.size() ? (const uint64_t*) moved.data() : (const uint64_t*) common.data();
+        const int Q = context_->Q_size, depth = S == Scheme::CKKS ? common.depth() : 0, l = Q - depth;
+        const size_t n = context_->n;
+        Crs crs(seed, "boot");
+        DeviceVector<Data64> out((size_t) (l + Q) * n, o.stream_);
+        if (S == Scheme::CKKS)
+            check(hegpu_mpc_ckks_refresh_share(context_->handle(), crs.r, rng_, ct, 2 * l * n, (const uint64_t*) sk.data(), depth,
+                                               refresh_mask_bits(l), (uint64_t*) out.data(), 1, nullptr, 0, o.stream_));
+        else
+            check(hegpu_mpc_bfv_refresh_share(context_->handle(), crs.r, rng_, ct, 2 * l * n, (const uint64_t*) sk.data(),
+                                              (uint64_t*) out.data(), 1, nullptr, 0, o.stream_));
+        output.adopt(std::move(out), 2, depth, common.scale());
+        output.encoding_ = common.encoding_;
+    }
+    void distributed_bootstrapping_coordinator(std::vector<Ciphertext<S>>& ciphertexts, Ciphertext<S>& common,
+                                               Ciphertext<S>& output, const RNGSeed& seed,
+                                               const ExecutionOptions& o = ExecutionOptions())
+    {
+        OpScope storage_scope(o);
+        if (ciphertexts.empty()) throw std::invalid_argument("No participant share to refresh with!");
+        const DeviceVector<Data64> moved = refresh_input(common, o);
+        const uint64_t* ct = moved.size() ? (const uint64_t*) moved.data() : (const uint64_t*) common.data();
+        const int Q = context_->Q_size, depth = S == Scheme::CKKS ? common.depth() : 0, l = Q - depth;
+        const size_t n = context_->n;
+        std::vector<const uint64_t*> shares;
+        for (auto& c : ciphertexts) {
+            if (c.depth() != depth) throw std::invalid_argument("Ciphertext levels should be same!");
+            shares.push_back((const uint64_t*) c.data());
+        }
+        Crs crs(seed, "boot");
+        DeviceVector<Data64> out((size_t) 2 * Q * n, o.stream_);
+        DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_REFRESH_MERGE, depth, 1) + 7) / 8, o.stream_);
+        if (S == Scheme::CKKS)
+            check(hegpu_mpc_ckks_refresh_merge(context_->handle(), crs.r, ct, 2 * l * n, shares.data(), (int) shares.size(), depth,
+                                               (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.size() * sizeof(Data64),
+                                               o.stream_));
+        else
+            check(hegpu_mpc_bfv_refresh_merge(context_->handle(), crs.r, ct, 2 * l * n, shares.data(), (int) shares.size(),
+                                              (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.size() * sizeof(Data64),
+                                              o.stream_));
+        const double scale = common.scale();
+        const auto encoding = common.encoding_;
+        output.adopt(std::move(out), 2, 0, scale);
+        output.encoding_ = encoding;
+    }
+
   protected:
     explicit MultiPartyManagerBase(HEContext<S> context) : context_(std::move(context))
     {
@@ -3006,6 +3064,26 @@ template <Scheme S> class MultiPartyManagerBase {
         Crs& operator=(const Crs&) = delete;
         hegpu_rng* r;
     };
+    // the checks of a refresh input (the evaluator's exception class for such inputs); a coefficient-domain CKKS
+    // ciphertext comes back transformed (an empty vector: use the ciphertext's own residues)
+    DeviceVector<Data64> refresh_input(Ciphertext<S>& ct, const ExecutionOptions& o)
+    {
+        if (ct.relinearization_required() || ct.size() != 2) throw std::invalid_argument("Ciphertext should be relinearized first!");
+        if (ct.rescale_required()) throw std::invalid_argument("Ciphertext should be rescaled first!");
+        if (S != Scheme::CKKS || ct.in_ntt_domain()) return DeviceVector<Data64>();
+        const int l = context_->Q_size - ct.depth();
+        DeviceVector<Data64> t((size_t) 2 * l * context_->n, o.stream_);
+        check(hegpu_ntt(context_->handle(), HEGPU_TABLES_QP, (const uint64_t*) ct.data(), (uint64_t*) t.data(), 0, 2 * l, l, 0,
+                        nullptr, nullptr, o.stream_));
+        return t;
+    }
+    int refresh_mask_bits(int l) const
+    {
+        // a product of l numbers of b_i bits has at least sum b_i - (l - 1) bits: the lower bound keeps the mask legal
+        int bits = -(l - 1);
+        for (int i = 0; i < l; i++) bits += (int) context_->prime_vector_[i].bit;
+        return bits - 8 > 126 ? 126 : bits - 8;
+    }
     DeviceVector<Data64> key_ws(const ExecutionOptions& o)
     {
         return DeviceVector<Data64>((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, 1) + 7) / 8, o.stream_);
@@ -3039,7 +3117,8 @@ template <Scheme S> class MultiPartyManagerBase {
 template <Scheme S> class HEMultiPartyManager;
 template <> class HEMultiPartyManager<Scheme::CKKS> : public detail::MultiPartyManagerBase<Scheme::CKKS> {
   public:
-    // encoder and scale serve the reference's collective bootstrapping, which is not part of this backend
+    // encoder and scale serve the reference's collective bootstrapping, which re-encodes at the manager's scale; here
+    // the refresh is an integer lift that keeps the ciphertext's own scale, and neither is needed
     HEMultiPartyManager(HEContext<Scheme::CKKS> context, HEEncoder<Scheme::CKKS>&, double&)
         : detail::MultiPartyManagerBase<Scheme::CKKS>(std::move(context)) {}
 };
