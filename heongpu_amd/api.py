@@ -5,6 +5,7 @@ libhegpu.so.  Polynomial data is held in torch.int64 tensors that carry the
 uint64 bit patterns (torch has no full uint64 support); `to_device`/`to_host`
 convert from/to numpy uint64.
 """
+import collections
 import contextlib
 import ctypes
 
@@ -353,6 +354,28 @@ class Context:
         _check(self._lib.hegpu_ckks_rotate_hoisted(self._h, _ptr(ct), cs, _ptr(out), so, kp, ge, cnt, depth, batch,
                                                    _ptr(ws), ws.numel() * 8,
                                                    stream if stream is not None else _stream()))
+
+    def ckks_diag_mac(self, rot, rot_stride, n1, diags, n_diag, index, n2, out, out_stride, depth=0, batch=1, stream=None):
+        """hegpu_ckks_diag_mac: index = n2 rows of n1 packed-diagonal numbers (-1: absent)"""
+        ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
+        _check(self._lib.hegpu_ckks_diag_mac(self._h, _ptr(rot), rot_stride, n1, _ptr(diags), n_diag, ix, n2, _ptr(out),
+                                             out_stride, depth, batch, stream if stream is not None else _stream()))
+
+    def linear_transform_workspace_bytes(self, n1, n2, depth, batch):
+        return int(self._lib.hegpu_ckks_linear_transform_workspace_bytes(self._h, n1, n2, depth, batch))
+
+    def ckks_linear_transform(self, ct, cs, out, so, diags, n_diag, index, baby_keys, baby_elts, giant_keys, giant_elts,
+                              depth, batch, ws, stream=None):
+        """hegpu_ckks_linear_transform: keys = lists of device tensors (None where the element is 0)"""
+        n1, n2 = len(baby_elts), len(giant_elts)
+        ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
+        bk = (ctypes.c_void_p * n1)(*[(_ptr(k) if k is not None else None) for k in baby_keys])
+        gk = (ctypes.c_void_p * n2)(*[(_ptr(k) if k is not None else None) for k in giant_keys])
+        be = (ctypes.c_int * n1)(*[int(g) for g in baby_elts])
+        ge = (ctypes.c_int * n2)(*[int(g) for g in giant_elts])
+        _check(self._lib.hegpu_ckks_linear_transform(self._h, _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2,
+                                                     bk, be, gk, ge, depth, batch, _ptr(ws), ws.numel() * 8,
+                                                     stream if stream is not None else _stream()))
 
     def bfv_multiply(self, ct1, s1, ct2, s2, out, so, batch, ws, stream=None):
         _check(self._lib.hegpu_bfv_multiply(self._h, _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws),
@@ -856,6 +879,42 @@ class TfheContext:
                                          _ptr(out_b), _ptr(prepared_bk), _ptr(ks_a), _ptr(ks_b), shape, _ptr(ws),
                                          ws.numel() * ws.element_size(),
                                          stream if stream is not None else _stream()))
+
+
+LinearTransformPlan = collections.namedtuple("LinearTransformPlan",
+                                             "n1 n2 index baby_shifts giant_shifts pre_rotation")
+
+
+def linear_transform_plan(diag_indices, slots, n1=None):
+    """Baby-step/giant-step plan of y = M v for a matrix given by its diagonals diag_k[s] = M[s][(s + k) mod slots]
+    (host only; the inputs of hegpu_ckks_linear_transform).  `n1` is the baby-step period: diagonal k = j * n1 + i is
+    baby step i of giant step j; by default the power of two nearest the square root of the number of diagonals (the
+    larger one on a tie), at most 16.  Only the baby steps i and giant steps j that occur are kept.  Returns
+      n1, n2         the number of baby / giant rotations (the entry's n1 and n2; n1 is at most the period)
+      index          n2 rows of n1 positions in the sorted diagonal list, -1 where the matrix has no such diagonal
+      baby_shifts    the occurring i, ascending: column c of index belongs to baby_shifts[c]
+      giant_shifts   the occurring j * period, ascending: row r of index belongs to giant_shifts[r]
+      pre_rotation   per sorted diagonal, the shift -j * period to rotate its slot vector by before encoding, so that
+                     rot(j * period, diag' * rot(i, v)) = diag_k * rot(k, v)
+    where a positive shift moves slot s + shift to slot s (rotate_rows; numpy.roll(x, -shift)).  A plan of more than
+    16 giant steps is refused: choose a larger period."""
+    ks = sorted({int(k) % slots for k in diag_indices})
+    if not ks:
+        raise ValueError("a linear transform needs at least one diagonal")
+    if n1 is None:
+        root = len(ks) ** 0.5
+        n1 = min((1, 2, 4, 8, 16), key=lambda p: (abs(p - root), -p))
+    if not 1 <= n1 <= 16:
+        raise ValueError("the baby-step period lies in [1, 16]")
+    baby = sorted({k % n1 for k in ks})
+    giant = sorted({k // n1 for k in ks})
+    if len(giant) > 16:
+        raise ValueError(f"{len(giant)} giant steps, at most 16 fit one transform: choose a larger period")
+    index = [[-1] * len(baby) for _ in giant]
+    for pos, k in enumerate(ks):
+        index[giant.index(k // n1)][baby.index(k % n1)] = pos
+    return LinearTransformPlan(len(baby), len(giant), index, baby, [j * n1 for j in giant],
+                               [-(k // n1) * n1 for k in ks])
 
 
 def steps_to_galois_elt(steps, n, group_order):

@@ -862,6 +862,74 @@ int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t c
                    "hegpu_ckks_rotate_hoisted");
 }
 
+// index [n2][n1]: every entry is a packed diagonal or -1
+static bool diag_index_ok(const int* index, int n1, int n2, int n_diag)
+{
+    for (int k = 0; k < n1 * n2; k++)
+        if (index[k] < -1 || index[k] >= n_diag) return false;
+    return true;
+}
+
+int hegpu_ckks_diag_mac(hegpu_context* ctx, const uint64_t* rot, uint64_t rot_stride, int n1, const uint64_t* diags,
+                        int n_diag, const int* index, int n2, uint64_t* out, uint64_t out_stride, int depth, int batch,
+                        hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16)
+        return fail(HEGPU_E_INVALID, "diag_mac: n1 and n2 lie in [1, 16] (16 products per 128-bit sum, 256 indices by value)");
+    if (!rot || !diags || !index || !out || n_diag < 1) return fail(HEGPU_E_INVALID, "diag_mac: null argument");
+    if (!diag_index_ok(index, n1, n2, n_diag)) return fail(HEGPU_E_INVALID, "diag_mac: index outside [-1, n_diag)");
+    if (batch > 65535) return fail(HEGPU_E_INVALID, "diag_mac: at most 65535 items per call");
+    const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    if (spans_overlap(rot, rot_stride, (uint64_t) n1 * words, out, out_stride, (uint64_t) n2 * words, batch))
+        return fail(HEGPU_E_INVALID, "diag_mac: out must not overlap rot");
+    return hip_ret(rns_ckks_diag_mac((const u64*) rot, rot_stride, n1, (const u64*) diags, n_diag, index, n2, (u64*) out,
+                                     out_stride, ctx->c.plan_qp.mods, ctx->c.n_power, ctx->c.Q_size - depth, batch,
+                                     (hipStream_t) stream),
+                   "hegpu_ckks_diag_mac");
+}
+
+size_t hegpu_ckks_linear_transform_workspace_bytes(const hegpu_context* ctx, int n1, int n2, int depth, int batch)
+{
+    if (!ctx || batch <= 0 || n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16 || depth < 0 || depth >= ctx->c.Q_size) return 0;
+    return ops_linear_transform_workspace_elems(ctx->c, n1, n2, depth, batch) * sizeof(u64);
+}
+
+int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
+                                const uint64_t* diags, int n_diag, const int* index, int n1, int n2,
+                                const uint64_t* const* baby_keys, const int* baby_elts,
+                                const uint64_t* const* giant_keys, const int* giant_elts, int depth, int batch, void* ws,
+                                size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16)
+        return fail(HEGPU_E_INVALID, "linear_transform: n1 and n2 lie in [1, 16]");
+    if (!ct || !out || !diags || !index || !baby_keys || !baby_elts || !giant_keys || !giant_elts || n_diag < 1)
+        return fail(HEGPU_E_INVALID, "linear_transform: null argument");
+    if (!diag_index_ok(index, n1, n2, n_diag)) return fail(HEGPU_E_INVALID, "linear_transform: index outside [-1, n_diag)");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "linear_transform: at most 32767 items per call");
+    for (int k = 0; k < n1 + n2; k++) {
+        const int e = k < n1 ? baby_elts[k] : giant_elts[k - n1];
+        if (e == 0) continue;
+        if (e < 0 || !(e & 1) || e >= 2 * (int) ctx->c.n)
+            return fail(HEGPU_E_INVALID, "linear_transform: Galois elements are odd and below 2N");
+        if (!(k < n1 ? baby_keys[k] : giant_keys[k - n1]))
+            return fail(HEGPU_E_INVALID, "linear_transform: Galois key not present!");
+    }
+    const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    if (spans_overlap(ct, cs, words, out, so, words, batch))
+        return fail(HEGPU_E_INVALID, "linear_transform: out must not overlap ct");
+    if (!ws || ws_bytes < hegpu_ckks_linear_transform_workspace_bytes(ctx, n1, n2, depth, batch))
+        return fail(HEGPU_E_INVALID, "workspace too small");
+    return hip_ret(op_ckks_linear_transform(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) diags, n_diag, index,
+                                            n1, n2, (const u64* const*) baby_keys, baby_elts,
+                                            (const u64* const*) giant_keys, giant_elts, depth, batch, (u64*) ws,
+                                            (hipStream_t) stream),
+                   "hegpu_ckks_linear_transform");
+}
+
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t s1, const uint64_t* ct2, uint64_t s2,
                        uint64_t* out, uint64_t so, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {

@@ -821,6 +821,65 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------ plaintext matrix x encrypted vector
+// Workspace, per batch: A = max(n1, n2) ciphertexts (the baby rotations; once the inner sums exist, the rotated inner
+// sums), B = n2 ciphertexts (the inner sums), then the key-switch workspace of the hoisted rotations with four
+// accumulators (which is also enough for every apply_galois).
+size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, int depth, int batch)
+{
+    const u64 ct_words = (u64) 2 * (c.Q_size - depth) * c.n;
+    return (u64) ((n1 > n2 ? n1 : n2) + n2) * ct_words * (u64) batch +
+           ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch);
+}
+
+hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* diags,
+                                    int n_diag, const int* index, int n1, int n2, const u64* const* baby_keys,
+                                    const int* baby_elts, const u64* const* giant_keys, const int* giant_elts, int depth,
+                                    int batch, u64* ws, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16) return hipErrorInvalidValue;
+    const int l = c.Q_size - depth;
+    const u64 ct_words = (u64) 2 * l * c.n;
+    const u64 a_stride = (u64) (n1 > n2 ? n1 : n2) * ct_words, b_stride = (u64) n2 * ct_words;
+    u64* A = ws;
+    u64* B = A + a_stride * batch;
+    u64* ks = B + b_stride * batch;
+    const Mod* mods = c.plan_qp.mods;
+    // 1. baby rotations (a single identity step reads the input itself)
+    const u64* rot = ct;
+    u64 rot_stride = cs;
+    if (!(n1 == 1 && baby_elts[0] == 0)) {
+        const int group = (c.fused_moddown && c.ntt_galois) ? 4 : 1;
+        TRY(op_ckks_rotate_hoisted(c, ct, cs, A, a_stride, baby_keys, baby_elts, n1, depth, batch, ks, st, group));
+        rot = A;
+        rot_stride = a_stride;
+    }
+    // 2. all inner sums; a single giant step without a rotation is the result
+    const bool direct = n2 == 1 && giant_elts[0] == 0;
+    TRY(rns_ckks_diag_mac(rot, rot_stride, n1, diags, n_diag, index, n2, direct ? out : B, direct ? so : b_stride, mods,
+                          c.n_power, l, batch, st));
+    if (direct) return hipSuccess;
+    // 3. giant rotations into A (the baby rotations are spent; apply_galois forbids out == in)
+    const u64* terms[16];
+    u64 strides[16];
+    for (int j = 0; j < n2; j++) {
+        const u64* inner = B + (u64) j * ct_words;
+        terms[j] = inner;
+        strides[j] = b_stride;
+        if (giant_elts[j] == 0) continue;
+        if (!giant_keys[j]) return hipErrorInvalidValue;
+        u64* rotated = n2 == 1 ? out : A + (u64) j * ct_words; // a single term is the result
+        const u64 rs = n2 == 1 ? so : a_stride;
+        TRY(op_ckks_apply_galois(c, inner, b_stride, rotated, rs, giant_keys[j], giant_elts[j], depth, batch, ks, st));
+        terms[j] = rotated;
+        strides[j] = rs;
+    }
+    if (n2 == 1) return hipSuccess;
+    // 4. one read of every term, one write
+    return rns_ckks_sum_terms(terms, strides, n2, out, so, mods, c.n_power, l, batch, st);
+}
+
 // ------------------------------------------------------------------ keygen / encrypt / decrypt
 hipError_t op_gen_secret_key(const Context& c, Rng& r, int hamming_weight, u64* sk, u64* ws, hipStream_t st)
 {

@@ -47,6 +47,18 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
                                   const int* galois_elts, int count, int depth, int batch, u64* ws, hipStream_t st,
                                   int group = 1 /* accumulators in ws: 1 (OP_CKKS_GALOIS) or 4 (OP_CKKS_ROTATE_HOISTED) */);
 
+// y = M v for a plaintext matrix given by its diagonals and an encrypted vector, baby-step/giant-step (the project's own
+// entry; the reference's multiply_matrix, ckks/operator.cu:2803-2895, is private to its bootstrapping):
+//   out = sum_j galois(giant_elts[j], sum_i diags[index[j][i]] (.) galois(baby_elts[i], ct))
+// hoisted baby rotations -> one rns_ckks_diag_mac launch for all n2 inner sums -> one apply_galois per giant step with a
+// non-zero element -> one k-way sum.  index / keys / elts: HOST arrays ([n2][n1], [n1], [n2]; element 0 = identity, its
+// key is ignored).  Not rescaled.  Workspace: ops_linear_transform_workspace_elems.
+size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, int depth, int batch);
+hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* diags,
+                                    int n_diag, const int* index, int n1, int n2, const u64* const* baby_keys,
+                                    const int* baby_elts, const u64* const* giant_keys, const int* giant_elts, int depth,
+                                    int batch, u64* ws, hipStream_t st);
+
 // ---- key generation / encryption / decryption, key-switch method I
 // The generator state: every sampling call consumes one stream id of the DRBG (drbg.hpp).
 struct Rng {

@@ -1238,4 +1238,133 @@ hipError_t rns_fast_floor(const u64* in, u64 si, u64* out, u64 so, const BehzDev
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- plaintext diagonals x rotated ciphertexts
+// The inner sums of a baby-step/giant-step matrix-vector product, all giant steps in one launch:
+//   out_j[p] = sum_i diags[index[j][i]] (.) rot_i[p],   p = 0, 1,   j < n2
+// (reference multiplication.cu cipherplain_multiply_accumulate_kernel, one launch per giant step, host/ckks/
+// operator.cu:2843, which reads the n1 rotated ciphertexts again for every j).  The thread that owns two adjacent
+// coefficients of a limb loads its 2 n1 rotated values once and keeps them in registers over the j loop; every
+// diagonal value is loaded once and multiplied into both parts.  The products of a row are summed as 128-bit
+// integers and reduced once per (j, part): at most 16 products of residues below 2^60 stay below 2^124, and the
+// one reduction gives the canonical residue that a chain of modular multiplies and additions gives.
+// N1: the row width the kernel is compiled for (every register index a constant); n1 <= N1 rotations exist, the
+// index rows are padded to N1 with -1 (absent), which is also what a diagonal the matrix does not have looks like.
+// Registers: 8 N1 for the rotated values and as many for the row's diagonals in flight; the 16-wide instance takes
+// all 256 plus accumulation registers (one wave per SIMD, 16 independent 16-byte loads each), none uses scratch.
+#define DIAG_MAC_MAX 16
+struct DiagIndex { int v[DIAG_MAC_MAX * DIAG_MAC_MAX]; }; // [n2][N1]
+template <int N1>
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_diag_mac(const u64* __restrict__ rot, u64 rot_stride,
+                                                               const u64* __restrict__ diags, DiagIndex index,
+                                                               u64* __restrict__ out, u64 out_stride,
+                                                               const Mod* __restrict__ mods, int n_power, int limbs,
+                                                               int n1, int n2)
+{
+    const Mod m = mods[blockIdx.y];
+    const u64 loc = coeff0() + ((u64) blockIdx.y << n_power);
+    const u64 part = (u64) limbs << n_power;
+    const u64* pr = rot + rot_stride * blockIdx.z + loc;
+    u64* po = out + out_stride * blockIdx.z + loc;
+    ulonglong2 r0[N1], r1[N1];
+#pragma unroll
+    for (int i = 0; i < N1; i++) {
+        r0[i] = r1[i] = ulonglong2{0, 0};
+        if (i < n1) {
+            r0[i] = ld2(pr + 2 * part * i);
+            r1[i] = ld2(pr + 2 * part * i + part);
+        }
+    }
+#pragma unroll 1
+    for (int j = 0; j < n2; j++) {
+        u64 h[4] = {0, 0, 0, 0}, l[4] = {0, 0, 0, 0};
+        int at[N1]; // the row, wave-uniform: read from the kernel arguments in one go
+#pragma unroll
+        for (int i = 0; i < N1; i++) at[i] = index.v[j * N1 + i];
+        ulonglong2 d[N1]; // all diagonal loads of the row are in flight before the first product
+#pragma unroll
+        for (int i = 0; i < N1; i++) {
+            d[i] = ulonglong2{0, 0};
+            if (at[i] >= 0) d[i] = ld2(diags + part * at[i] + loc);
+        }
+#pragma unroll
+        for (int i = 0; i < N1; i++) { // an absent entry adds zeros: no branch around the accumulators
+            acc_mad(h[0], l[0], d[i].x, r0[i].x);
+            acc_mad(h[1], l[1], d[i].y, r0[i].y);
+            acc_mad(h[2], l[2], d[i].x, r1[i].x);
+            acc_mad(h[3], l[3], d[i].y, r1[i].y);
+        }
+        ulonglong2 o0, o1;
+        o0.x = reduce128(h[0], l[0], m);
+        o0.y = reduce128(h[1], l[1], m);
+        o1.x = reduce128(h[2], l[2], m);
+        o1.y = reduce128(h[3], l[3], m);
+        st2(po + 2 * part * j, o0);
+        st2(po + 2 * part * j + part, o1);
+    }
+}
+
+hipError_t rns_ckks_diag_mac(const u64* rot, u64 rot_stride, int n1, const u64* diags, int n_diag, const int* index,
+                             int n2, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs, int batch,
+                             hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (n1 < 1 || n1 > DIAG_MAC_MAX || n2 < 1 || n2 > DIAG_MAC_MAX || batch > 65535) return hipErrorInvalidValue;
+    int w = 1;
+    while (w < n1) w *= 2;
+    DiagIndex ix{};
+    for (int j = 0; j < n2; j++)
+        for (int i = 0; i < w; i++) {
+            const int at = i < n1 ? index[j * n1 + i] : -1;
+            if (at < -1 || at >= n_diag) return hipErrorInvalidValue;
+            ix.v[j * w + i] = at;
+        }
+    const dim3 g = grid3(n_power, limbs, batch);
+#define LAUNCH(W)                                                                                                     \
+    hipLaunchKernelGGL(k_ckks_diag_mac<W>, g, dim3(RNS_THREADS), 0, st, rot, rot_stride, diags, ix, out, out_stride,  \
+                       mods, n_power, limbs, n1, n2)
+    switch (w) {
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        case 4: LAUNCH(4); break;
+        case 8: LAUNCH(8); break;
+        default: LAUNCH(16); break;
+    }
+#undef LAUNCH
+    return hipGetLastError();
+}
+
+// out = the modular sum of `count` <= 16 ciphertexts [2][limbs][N] per item, each with a stride of its own: one read
+// of every term and one write (the shape of keygen.hip's k-way share sum).  out may be none of the terms.
+struct SumTerms {
+    const u64* p[DIAG_MAC_MAX];
+    u64 stride[DIAG_MAC_MAX];
+};
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_sum_terms(SumTerms t, int count, u64* __restrict__ out,
+                                                                u64 out_stride, const Mod* __restrict__ mods,
+                                                                int n_power, int limbs)
+{
+    const u64 q = mods[blockIdx.y].q;
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 loc = coeff0() + ((u64) blockIdx.y << n_power) + (((u64) limbs * z) << n_power);
+    ulonglong2 a = ld2(t.p[0] + t.stride[0] * item + loc);
+    for (int k = 1; k < count; k++) {
+        const ulonglong2 x = ld2(t.p[k] + t.stride[k] * item + loc);
+        a.x = add_mod(a.x, x.x, q);
+        a.y = add_mod(a.y, x.y, q);
+    }
+    st2(out + out_stride * item + loc, a);
+}
+
+hipError_t rns_ckks_sum_terms(const u64* const* terms, const u64* strides, int count, u64* out, u64 out_stride,
+                              const Mod* mods, int n_power, int limbs, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (count < 1 || count > DIAG_MAC_MAX || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    SumTerms t{};
+    for (int k = 0; k < count; k++) { t.p[k] = terms[k]; t.stride[k] = strides[k]; }
+    hipLaunchKernelGGL(k_ckks_sum_terms, grid3(n_power, limbs, 2 * batch), dim3(RNS_THREADS), 0, st, t, count, out,
+                       out_stride, mods, n_power, limbs);
+    return hipGetLastError();
+}
+
 } // namespace hegpu

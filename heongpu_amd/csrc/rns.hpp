@@ -100,6 +100,19 @@ hipError_t rns_copy_limbs(const u64* in, u64 in_part_stride, u64 in_stride, u64*
 hipError_t rns_copy_diag(const u64* in, u64 in_stride, u64* out, u64 out_stride, int n_power, int limbs, int rc,
                          int batch, hipStream_t st);
 
+// reference multiplication.cu cipherplain_multiply_accumulate_kernel as used by host/ckks/operator.cu:2843, for all giant
+// steps of a baby-step/giant-step matrix-vector product in one launch: out entry j (at out + j * 2 limbs N, items
+// out_stride apart) = sum_i diags[index[j][i]] (.) rot entry i, both parts.  rot: n1 <= 16 ciphertexts per item, entry i
+// at rot + i * 2 limbs N (the layout of op_ckks_rotate_hoisted); diags: [n_diag][limbs][N]; index: HOST [n2][n1], -1 =
+// absent (a row of -1 writes zeros), travels in the kernel arguments.  out must not overlap rot.
+hipError_t rns_ckks_diag_mac(const u64* rot, u64 rot_stride, int n1, const u64* diags, int n_diag, const int* index,
+                             int n2, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs, int batch,
+                             hipStream_t st);
+// out[item] = sum of terms[k][item] over [2][limbs][N] (addition.cu:10-21, `count` <= 16 terms in one pass); terms /
+// strides: HOST arrays
+hipError_t rns_ckks_sum_terms(const u64* const* terms, const u64* strides, int count, u64* out, u64 out_stride,
+                              const Mod* mods, int n_power, int limbs, int batch, hipStream_t st);
+
 struct BehzDev {
     const Mod* ibase;       // q_0..q_{Q-1}
     const Mod* obase;       // Bsk

@@ -310,6 +310,35 @@ int hegpu_ckks_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_
 int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out,
                               uint64_t out_stride, const uint64_t* const* galois_keys, const int* galois_elts,
                               int count, int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+/* The inner sums of a baby-step/giant-step product of a plaintext matrix, given by its diagonals, with an encrypted
+ * vector: cipherplain_multiply_accumulate_kernel (src/lib/kernel/multiplication.cu), which the reference launches once
+ * per giant step (host/ckks/operator.cu:2843) -- here ONE launch computes all n2 sums: the n1 rotated ciphertexts are
+ * read once, every diagonal once, the products of a sum are added as 128-bit integers and reduced once.
+ *   out entry j [p] = sum_i diags[index[j][i]] (.) rot entry i [p]   mod q_limb,   p = 0, 1
+ * rot: n1 ciphertexts per item in the layout hegpu_ckks_rotate_hoisted writes (entry i at rot + i * 2 l N, items
+ * rot_stride apart), l = Q - depth; diags: DEVICE [n_diag][l][N] plaintext limbs (NTT domain, shared by the items);
+ * index: HOST [n2][n1], -1 = absent (a row of -1 gives zeros); out entry j at out + j * 2 l N, items out_stride apart.
+ * Every result is bit-identical to hegpu_cipherplain_multiplication + hegpu_addition per diagonal.
+ * HEGPU_E_INVALID: n1 or n2 outside [1, 16] (16 products of residues below 2^60 fit the 128-bit sum; the index table
+ * travels by value), an index >= n_diag or < -1, out overlapping rot. */
+int hegpu_ckks_diag_mac(hegpu_context* ctx, const uint64_t* rot, uint64_t rot_stride, int n1, const uint64_t* diags,
+                        int n_diag, const int* index, int n2, uint64_t* out, uint64_t out_stride, int depth, int batch,
+                        hegpu_stream stream);
+/* y = M v for a plaintext matrix M and an encrypted vector v (this backend's own entry: the reference's
+ * multiply_matrix, host/ckks/operator.cu:2803-2895, is private to its bootstrapping):
+ *   out = sum_j galois(giant_elts[j], sum_i diags[index[j][i]] (.) galois(baby_elts[i], ct))
+ * as hegpu_ckks_rotate_hoisted of the n1 baby steps, one hegpu_ckks_diag_mac, one hegpu_ckks_apply_galois per giant
+ * step with a non-zero element, and one sum of the n2 terms.  Element 0 = no rotation (its key is ignored); keys and
+ * elements are HOST arrays of DEVICE keys, [n1] and [n2].  The result has two parts at the same depth and is NOT
+ * rescaled: its scale is the product of the ciphertext's and the diagonals' scales.  Bit-identical to the same
+ * composition of the single entries.  out must not overlap ct.  Workspace: the size function below (it depends on n1
+ * and n2, so it is not a row of hegpu_workspace_bytes). */
+size_t hegpu_ckks_linear_transform_workspace_bytes(const hegpu_context* ctx, int n1, int n2, int depth, int batch);
+int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out,
+                                uint64_t out_stride, const uint64_t* diags, int n_diag, const int* index, int n1, int n2,
+                                const uint64_t* const* baby_keys, const int* baby_elts,
+                                const uint64_t* const* giant_keys, const int* giant_elts, int depth, int batch, void* ws,
+                                size_t ws_bytes, hegpu_stream stream);
 /* multiply_bfv (src/lib/host/bfv/operator.cu:336-430): coefficient domain,
  * ct [2][Q][N] x [2][Q][N] -> out [3][Q][N] */
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_stride, const uint64_t* ct2,

@@ -2163,6 +2163,112 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
     HEContext<S> context_;
 };
 
+// ------------------------------------------------------------------ plaintext matrix for HEArithmeticOperator::linear_transform
+// A matrix M over the N/2 slots, given by its non-zero diagonals diag_k[s] = M[s][(s + k) mod N/2], prepared for the
+// baby-step/giant-step evaluation of y = M v (hegpu_ckks_linear_transform).  This is the project's own addition: the
+// reference's multiply_matrix (ckks/operator.cu:2803-2895) is private to its bootstrapping and takes pre-baked index
+// tensors.  The plan (the same as heongpu_amd.api.linear_transform_plan): with the baby-step period n1, diagonal
+// k = j n1 + i is baby step i of giant step j; only the i and j that occur are kept; the slot vector of diagonal k is
+// rotated by -j n1 before it is encoded, so that rot(j n1, diag' * rot(i, v)) = diag_k * rot(k, v).
+template <Scheme S> class LinearTransform;
+template <> class LinearTransform<Scheme::CKKS> {
+    static constexpr Scheme S = Scheme::CKKS;
+
+  public:
+    // n1: the baby-step period; 0 = the power of two nearest the square root of the number of diagonals (the larger one
+    // on a tie), at most 16.  Diagonals shorter than N/2 are padded with zeros.
+    LinearTransform(HEContext<S> context, const std::map<int, std::vector<Complex64>>& diagonals, HEEncoder<S>& encoder,
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions())
+        : context_(std::move(context))
+    {
+        build(diagonals, encoder, scale, depth, n1, o);
+    }
+    LinearTransform(HEContext<S> context, const std::map<int, std::vector<double>>& diagonals, HEEncoder<S>& encoder,
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions())
+        : context_(std::move(context))
+    {
+        build(diagonals, encoder, scale, depth, n1, o);
+    }
+    // the rotations linear_transform needs a Galois key of their own for (no key chains there)
+    std::vector<int> required_shifts() const
+    {
+        std::vector<int> v;
+        for (int sh : baby_shifts_) if (sh) v.push_back(sh);
+        for (int sh : giant_shifts_) if (sh && std::find(v.begin(), v.end(), sh) == v.end()) v.push_back(sh);
+        return v;
+    }
+    double scale() const noexcept { return scale_; }
+    int depth() const noexcept { return depth_; }
+    int n1() const noexcept { return (int) baby_shifts_.size(); }
+    int n2() const noexcept { return (int) giant_shifts_.size(); }
+    int diagonal_count() const noexcept { return n_diag_; }
+    const std::vector<int>& index() const noexcept { return index_; }            // [n2][n1], -1 = no such diagonal
+    const std::vector<int>& baby_shifts() const noexcept { return baby_shifts_; }
+    const std::vector<int>& giant_shifts() const noexcept { return giant_shifts_; }
+    const Data64* data() const { return diags_.data(); }                          // [diagonal_count][Q - depth][N]
+
+  private:
+    template <typename T> void build(const std::map<int, std::vector<T>>& diagonals, HEEncoder<S>& encoder, double scale,
+                                     int depth, int n1, const ExecutionOptions& o)
+    {
+        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        if (depth < 0 || depth >= context_->Q_size) throw std::invalid_argument("Invalid depth!");
+        const int slots = (int) (context_->n >> 1);
+        std::map<int, const std::vector<T>*> by_k; // diagonal index mod slots, ascending
+        for (const auto& d : diagonals) {
+            if ((int) d.second.size() > slots) throw std::invalid_argument("Vector size can not be higher than slot count!");
+            if (!by_k.emplace(((d.first % slots) + slots) % slots, &d.second).second)
+                throw std::invalid_argument("Two diagonals with the same index modulo the slot count!");
+        }
+        if (by_k.empty()) throw std::invalid_argument("A linear transform needs at least one diagonal!");
+        if (n1 == 0) {
+            const double root = std::sqrt((double) by_k.size());
+            n1 = 1;
+            for (int p2 = 2; p2 <= 16; p2 *= 2)
+                if (std::fabs(p2 - root) <= std::fabs(n1 - root)) n1 = p2;
+        }
+        if (n1 < 1 || n1 > 16) throw std::invalid_argument("The baby-step period lies in [1, 16]!");
+        std::vector<int> babies, giants;
+        for (const auto& d : by_k) {
+            if (std::find(babies.begin(), babies.end(), d.first % n1) == babies.end()) babies.push_back(d.first % n1);
+            if (std::find(giants.begin(), giants.end(), d.first / n1) == giants.end()) giants.push_back(d.first / n1);
+        }
+        std::sort(babies.begin(), babies.end());
+        std::sort(giants.begin(), giants.end());
+        if (giants.size() > 16)
+            throw std::invalid_argument("More than 16 giant steps: choose a larger baby-step period!");
+        index_.assign(babies.size() * giants.size(), -1);
+        scale_ = scale;
+        depth_ = depth;
+        n_diag_ = (int) by_k.size();
+        const size_t n = context_->n, l = (size_t) (context_->Q_size - depth);
+        diags_ = DeviceVector<Data64>((size_t) n_diag_ * l * n, o.stream_);
+        int pos = 0;
+        for (const auto& d : by_k) {
+            const int i = d.first % n1, j = d.first / n1;
+            const size_t row = std::find(giants.begin(), giants.end(), j) - giants.begin();
+            const size_t col = std::find(babies.begin(), babies.end(), i) - babies.begin();
+            index_[row * babies.size() + col] = pos;
+            std::vector<T> rotated((size_t) slots, T(0)); // rotated by -j n1: slot t takes slot t - j n1
+            for (size_t t = 0; t < d.second->size(); t++) rotated[(t + (size_t) j * n1) % slots] = (*d.second)[t];
+            Plaintext<S> plain(context_);
+            encoder.encode(plain, rotated, scale, o);
+            detail::hip(hipMemcpyAsync(diags_.data() + (size_t) pos * l * n, plain.data(), l * n * sizeof(Data64),
+                                       hipMemcpyDeviceToDevice, o.stream_));
+            detail::hip(hipStreamSynchronize(o.stream_)); // `plain` is released at the end of this iteration
+            pos++;
+        }
+        baby_shifts_ = babies;
+        giant_shifts_.clear();
+        for (int j : giants) giant_shifts_.push_back(j * n1);
+    }
+    HEContext<S> context_;
+    DeviceVector<Data64> diags_;
+    std::vector<int> index_, baby_shifts_, giant_shifts_;
+    double scale_ = 0;
+    int depth_ = 0, n_diag_ = 0;
+};
+
 // ------------------------------------------------------------------ operator
 template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
   public:
@@ -2374,6 +2480,50 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             detail::hip(hipStreamSynchronize(stream)); // `rot` is released on return
         }
         return result;
+    }
+
+    // out = M in for the plaintext matrix of `lt` (hegpu_ckks_linear_transform: hoisted baby rotations, one pass over
+    // the diagonals for all inner sums, one rotation per giant step, one sum).  The project's own addition -- the
+    // reference's multiply_matrix (ckks/operator.cu:2803-2895) is private to its bootstrapping and takes pre-baked index
+    // tensors.  The result is not rescaled: scale_ = in.scale_ * lt.scale(), rescale_required_ = true.  Every shift of
+    // lt.required_shifts() needs a Galois key of its own: a power-of-two chain would silently multiply the key
+    // switches, so a missing key is std::invalid_argument here.
+    void linear_transform(Ciphertext<S>& in, LinearTransform<S>& lt, Galoiskey<S>& galois_key, Ciphertext<S>& out,
+                          const ExecutionOptions& o = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "linear transforms are a CKKS operation");
+        detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
+        if (in.relinearization_required_ || in.cipher_size_ != 2)
+            throw std::invalid_argument("Ciphertext should be relinearized first!");
+        if (in.rescale_required_) throw std::invalid_argument("Ciphertext should be rescaled first!");
+        if (in.depth_ != lt.depth()) throw std::invalid_argument("Ciphertext and LinearTransform levels are not equal");
+        const int l = limbs(in);
+        const size_t n = context_->n;
+        if (in.memory_size() < 2 * n * l) throw std::invalid_argument("Invalid Ciphertexts size!");
+        const int n1 = lt.n1(), n2 = lt.n2();
+        std::vector<const uint64_t*> keys(n1 + n2, nullptr);
+        std::vector<int> elts(n1 + n2, 0);
+        for (int k = 0; k < n1 + n2; k++) {
+            const int shift = k < n1 ? lt.baby_shifts()[k] : lt.giant_shifts()[k - n1];
+            if (shift == 0) continue;
+            elts[k] = hegpu_steps_to_galois_elt(shift, (int) n, galois_key.group_order_);
+            auto it = galois_key.device_location_.find(elts[k]);
+            if (it == galois_key.device_location_.end())
+                throw std::invalid_argument("Galois key not present! (build the Galoiskey from required_shifts())");
+            keys[k] = (const uint64_t*) it->second.data();
+        }
+        const size_t wsb = hegpu_ckks_linear_transform_workspace_bytes(context_->handle(), n1, n2, in.depth_, 1);
+        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        DeviceVector<Data64> m(2 * n * l, o.stream_);
+        detail::check(hegpu_ckks_linear_transform(context_->handle(), (const uint64_t*) in.data(), 0, (uint64_t*) m.data(), 0,
+                                                  (const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1,
+                                                  n2, keys.data(), elts.data(), keys.data() + n1, elts.data() + n1,
+                                                  in.depth_, 1, ws.data(), wsb, o.stream_));
+        const double sc = in.scale_ * lt.scale();
+        if (&in != &out) copy_meta(in, out);
+        out.memory_set(std::move(m));
+        out.scale_ = sc;
+        out.rescale_required_ = true;
     }
 
   private:
