@@ -1553,8 +1553,7 @@ int hegpu_bfv_plain_addsub(hegpu_context* ctx, const uint64_t* ct, const uint64_
     const Context& c = ctx->c;
     return guarded([&]() -> int {
         return hip_ret(kg_bfv_plain_addsub((const u64*) ct, (const u64*) plain, (u64*) out, c.plan_qp.mods,
-                                           c.tab.coeff_div_plain_modulus, c.hv.Q_mod_t,
-                                           c.hv.upper_threshold, c.plain_modulus, c.n_power, c.Q_size, sub,
+                                           c.tab.coeff_div_plain_modulus, bfv_plain_scale(c), c.n_power, c.Q_size, sub,
                                            (hipStream_t) stream),
                        "hegpu_bfv_plain_addsub");
     });

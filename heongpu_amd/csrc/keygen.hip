@@ -218,39 +218,41 @@ hipError_t kg_sk_multiplication_ckks(const u64* ct, u64* plain, const u64* sk, c
     return hipGetLastError();
 }
 
+// D(m): limb y of the scaled plaintext, Delta * m + the rounding fix (tail of enc_div_lastq_bfv_kernel,
+// encryption.cu:158-172).  The 64-bit wrap-around and the detour through `int` are the reference's (:160-163).
+__device__ __forceinline__ u64 bfv_scaled_plain(u64 message, const Mod& m, u64 coeff_div, const BfvPlainScale& p)
+{
+    u64 fix = message * p.Q_mod_t;
+    fix = fix + p.upper_threshold;
+    fix = (u64) (long long) (int) (fix / p.t);
+    return add_mod(mul_barrett(message, coeff_div, m), fix, m.q);
+}
+
 __global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_message_add(u64* __restrict__ ct, const u64* __restrict__ plain,
                                                                    const Mod* __restrict__ mods,
-                                                                   const u64* __restrict__ coeff_div, u64 Q_mod_t,
-                                                                   u64 upper_threshold, u64 t, int n_power)
+                                                                   const u64* __restrict__ coeff_div, BfvPlainScale p,
+                                                                   int n_power)
 {
     const u32 idx = blockIdx.x * KG_THREADS + threadIdx.x;
     const int y = blockIdx.y;
     const Mod m = mods[y];
-    const u64 message = plain[idx];
-    // 64-bit wrap-around and the detour through `int` are the reference's (encryption.cu:160-163)
-    u64 fix = message * Q_mod_t;
-    fix = fix + upper_threshold;
-    fix = (u64) (long long) (int) (fix / t);
-    u64 c0 = mul_barrett(message, coeff_div[y], m);
-    c0 = add_mod(c0, fix, m.q);
     const u64 loc = idx + ((u64) y << n_power);
-    ct[loc] = add_mod(ct[loc], c0, m.q);
+    ct[loc] = add_mod(ct[loc], bfv_scaled_plain(plain[idx], m, coeff_div[y], p), m.q);
 }
 
-hipError_t kg_bfv_message_add(u64* ct, const u64* plain, const Mod* mods, const u64* coeff_div, u64 Q_mod_t,
-                              u64 upper_threshold, u64 t, int n_power, int limbs, hipStream_t st)
+hipError_t kg_bfv_message_add(u64* ct, const u64* plain, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,
+                              int n_power, int limbs, hipStream_t st)
 {
     hipLaunchKernelGGL(k_kg_bfv_message_add, dim3((1u << n_power) / KG_THREADS, limbs), dim3(KG_THREADS), 0, st, ct,
-                       plain, mods, coeff_div, Q_mod_t, upper_threshold, t, n_power);
+                       plain, mods, coeff_div, p, n_power);
     return hipGetLastError();
 }
 
 __global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_plain_addsub(const u64* __restrict__ ct,
                                                                     const u64* __restrict__ plain, u64* __restrict__ out,
                                                                     const Mod* __restrict__ mods,
-                                                                    const u64* __restrict__ coeff_div, u64 Q_mod_t,
-                                                                    u64 upper_threshold, u64 t, int n_power, int limbs,
-                                                                    int sub)
+                                                                    const u64* __restrict__ coeff_div, BfvPlainScale p,
+                                                                    int n_power, int limbs, int sub)
 {
     const u32 idx = blockIdx.x * KG_THREADS + threadIdx.x;
     const int y = blockIdx.y, z = blockIdx.z;
@@ -258,23 +260,17 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_plain_addsub(const u64* _
     const u64 loc = idx + ((u64) y << n_power) + (((u64) limbs * z) << n_power);
     u64 c = ct[loc];
     if (z == 0) {
-        const u64 message = plain[idx];
-        u64 fix = message * Q_mod_t;
-        fix = fix + upper_threshold;
-        fix = (u64) (long long) (int) (fix / t);
-        u64 r = mul_barrett(message, coeff_div[y], m);
-        r = add_mod(r, fix, m.q);
+        const u64 r = bfv_scaled_plain(plain[idx], m, coeff_div[y], p);
         c = sub ? sub_mod(c, r, m.q) : add_mod(r, c, m.q);
     }
     out[loc] = c;
 }
 
 hipError_t kg_bfv_plain_addsub(const u64* ct, const u64* plain, u64* out, const Mod* mods, const u64* coeff_div,
-                               u64 Q_mod_t, u64 upper_threshold, u64 t, int n_power, int limbs, int sub,
-                               hipStream_t st)
+                               const BfvPlainScale& p, int n_power, int limbs, int sub, hipStream_t st)
 {
     hipLaunchKernelGGL(k_kg_bfv_plain_addsub, dim3((1u << n_power) / KG_THREADS, limbs, 2), dim3(KG_THREADS), 0, st,
-                       ct, plain, out, mods, coeff_div, Q_mod_t, upper_threshold, t, n_power, limbs, sub);
+                       ct, plain, out, mods, coeff_div, p, n_power, limbs, sub);
     return hipGetLastError();
 }
 
@@ -558,8 +554,9 @@ hipError_t kg_negacyclic_shift(const u64* in, u64* out, const Mod* mods, int shi
 
 // ---- N-out-of-N multiparty protocol (host/{ckks,bfv}/mpcmanager.cu; keygeneration.cu:118-462, 861-894).
 // The public-key and Galois-key shares are k_kg_publickey / k_kg_switchkey with the parties' common `a`, the round-1
-// relinearisation share is k_kg_switchkey with u; what follows is the round-2 share, the k-way sums and the two
-// kernels of collective decryption.  All of them are HBM streams: two coefficients (16 bytes) per lane per array.
+// relinearisation share is k_kg_switchkey with u; what follows is the round-2 share, the k-way sums and the kernels of
+// collective decryption, which the collective refresh below uses too: its share is the decryption share with a second
+// half, its sums read one half of a share.  All of them are HBM streams: two coefficients (16 bytes) per lane per array.
 #define KG_VEC 2
 typedef ulonglong2 u64x2;
 
@@ -599,6 +596,19 @@ hipError_t kg_mpc_relin_round2(u64* share, const u64* round1_sum, const u64* sk,
     return hipGetLastError();
 }
 
+// The share pointers (a HOST array of k device pointers) reach the kernels KG_MPC_MAX_SHARES at a time:
+// launch(group, count, first) once per group, in order.  What a later group reads as its base is the caller's rule.
+template <class F> static hipError_t each_share_group(const u64* const* shares, int k, F&& launch)
+{
+    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
+        MpcShares sh{};
+        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
+        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+        launch(sh, cnt, done == 0);
+    }
+    return hipGetLastError();
+}
+
 // threshold_pk_addition (:118-140), multi_party_relinkey_method_I_stage_I / _II_kernel (:321-462),
 // multi_party_galoiskey_method_I_II_kernel (:861-894): the reference adds one share per launch; here one launch reads
 // each of k <= KG_MPC_MAX_SHARES shares once and writes the sum once.  A unit (blockIdx.z) is [2][limbs][N]: the public
@@ -630,39 +640,49 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_accumulate(u64* out, MpcS
 hipError_t kg_mpc_accumulate(u64* out, const u64* const* shares, int k, const u64* second, int fold, int sum_second,
                              const Mod* mods, int n_power, int limbs, int units, hipStream_t st)
 {
-    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
-        MpcShares sh{};
-        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
-        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+    return each_share_group(shares, k, [&](const MpcShares& sh, int cnt, bool first) {
         hipLaunchKernelGGL(k_kg_mpc_accumulate, vec_grid(n_power, limbs, units), dim3(KG_THREADS), 0, st, out, sh, cnt,
-                           done ? out : nullptr, done ? nullptr : second, fold, sum_second, mods, n_power, limbs);
-    }
-    return hipGetLastError();
+                           first ? nullptr : out, first ? second : nullptr, fold, sum_second, mods, n_power, limbs);
+    });
 }
 
-// A party's share of a collective decryption, one per ciphertext of the batch (partial_decrypt_stage_1,
-// ckks/mpcmanager.cu:1483-1540: sk_multiplication, the error's NTT, `addition`, and a copy of c0 -- here the share is
-// h alone): h[b][y] = c1[b][y] * s[y] + h[b][y], where h comes in holding the transformed error (add) or nothing
-// (c1 may then be h itself)
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride,
-                                                                     const u64* __restrict__ sk,
-                                                                     const Mod* __restrict__ mods, int n_power, int add)
+// A party's share, one per ciphertext of the batch, both halves in one pass (the reference: sk_multiplication and
+// `addition` per half, temporaries; partial_decrypt_stage_1, ckks/mpcmanager.cu:1483-1540, also copies c0):
+//   y < l:   h0[y]     = c1[y] * s[y]                      (+ what h0 holds: the transformed error)
+//   y >= l:  h1[y - l] = -(a[y - l] * s[y - l])            (+ what h1 holds), a drawn from the crs: item b takes stream
+//            crs_stream + b, limb j, coefficient n at index j N + n -- kg_uniform's order for one polynomial
+// share [batch][l + limbs][N]; c1 of item b at c1 + b * c1_stride (may be the share's own first half, add = 0).  A
+// collective decryption's share is h0 alone (limbs = 0), a refresh share carries both.  y is blockIdx.y: the branch is
+// uniform per workgroup.
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_share(u64* share, const u64* c1, u64 c1_stride,
+                                                             const u64* __restrict__ sk, const Mod* __restrict__ mods,
+                                                             int n_power, int l, int limbs, DrbgKey crs, u64 crs_stream,
+                                                             int add)
 {
     const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
     const int y = blockIdx.y, b = blockIdx.z;
-    const Mod m = mods[y];
-    const u64 lane = n + ((u64) y << n_power);
-    const u64 dst = lane + (((u64) gridDim.y * b) << n_power);
-    u64x2 v = mul2(ld2(c1 + lane + c1_stride * b), ld2(sk + lane), m);
-    if (add) v = add2(v, ld2(h + dst), m.q);
-    st2(h + dst, v);
+    const int j = y < l ? y : y - l;
+    const Mod m = mods[j];
+    const u64 lane = n + ((u64) j << n_power);
+    u64* dst = share + (((u64) b * (l + limbs) + y) << n_power) + n;
+    const u64x2 s = ld2(sk + lane);
+    u64x2 v;
+    if (y < l) {
+        v = mul2(ld2(c1 + lane + c1_stride * b), s, m);
+    } else {
+        const u64 at = ((u64) j << n_power) + n;
+        const u64x2 a{drbg_uniform(crs, crs_stream + b, at, m), drbg_uniform(crs, crs_stream + b, at + 1, m)};
+        v = sub2(u64x2{0, 0}, mul2(a, s, m), m.q);
+    }
+    if (add) v = add2(v, ld2(dst), m.q);
+    st2(dst, v);
 }
 
-hipError_t kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
-                                int limbs, int batch, int add, hipStream_t st)
+hipError_t kg_mpc_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power, int l,
+                        int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_kg_mpc_decrypt_share, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, h, c1,
-                       c1_stride, sk, mods, n_power, add);
+    hipLaunchKernelGGL(k_kg_mpc_share, vec_grid(n_power, l + limbs, batch), dim3(KG_THREADS), 0, st, share, c1,
+                       c1_stride, sk, mods, n_power, l, limbs, crs, crs_stream, add);
     return hipGetLastError();
 }
 
@@ -691,38 +711,38 @@ hipError_t kg_mpc_add_gaussian(u64* h, const Mod* mods, int n_power, int limbs, 
     return hipGetLastError();
 }
 
-// Collective decryption, the merge (partial_decrypt_stage_2, ckks/mpcmanager.cu:1542-1573: k `addition` launches
-// over a temporary): m[b][y] = c0[b][y] + sum_j h_j[b][y] in one launch; shares [batch][limbs][N] each
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, MpcShares sh,
-                                                             int k, const Mod* __restrict__ mods, int n_power)
+// The coordinator's k-way sums (partial_decrypt_stage_2, ckks/mpcmanager.cu:1542-1573: k `addition` launches over a
+// temporary) in one launch.  Item b, limb y of share j at sh.p[j] + b * sh_stride + sh_off + y * N -- a refresh share is
+// read one half at a time:
+//   out[b][y] = base[b][y] + sum_j share_j[b][y]     (out items out_stride apart, base items base_stride apart)
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride,
+                                                           MpcShares sh, int k, u64 sh_stride, u64 sh_off,
+                                                           const Mod* __restrict__ mods, int n_power)
 {
     const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
     const int y = blockIdx.y, b = blockIdx.z;
     const u64 q = mods[y].q;
     const u64 lane = n + ((u64) y << n_power);
-    const u64 dst = lane + (((u64) gridDim.y * b) << n_power);
-    u64x2 acc = ld2(c0 + lane + c0_stride * b);
-    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + dst), q);
-    st2(plain + dst, acc);
+    u64x2 acc = ld2(base + lane + base_stride * b);
+    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + sh_off + lane), q);
+    st2(out + lane + out_stride * b, acc);
 }
 
-hipError_t kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
-                        int n_power, int limbs, int batch, hipStream_t st)
+hipError_t kg_mpc_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares, int k,
+                      u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch, hipStream_t st)
 {
-    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
-        MpcShares sh{};
-        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
-        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
-        hipLaunchKernelGGL(k_kg_mpc_merge, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, plain,
-                           done ? plain : c0, done ? ((u64) limbs << n_power) : c0_stride, sh, cnt, mods, n_power);
-    }
-    return hipGetLastError();
+    return each_share_group(shares, k, [&](const MpcShares& sh, int cnt, bool first) {
+        hipLaunchKernelGGL(k_kg_mpc_sum, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, out, out_stride,
+                           first ? base : out, first ? base_stride : out_stride, sh, cnt, sh_stride, sh_off, mods,
+                           n_power);
+    });
 }
 
 // BFV: the same sum feeding the scale-and-round stage of k_kg_bfv_decryption (bfv/mpcmanager.cu:1521-1561 runs k
-// `addition` launches, then decryption_fusion_bfv_kernel); plain [batch][N] mod t
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_bfv_merge(u64* __restrict__ plain, const u64* __restrict__ c0,
-                                                                 u64 c0_stride, MpcShares sh, int k,
+// `addition` launches, then decryption_fusion_bfv_kernel); item b of share j at sh.p[j] + b * sh_stride (a decryption
+// share, or the h0 half of a refresh share); plain [batch][N] mod t, k <= KG_MPC_MAX_SHARES
+__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_bfv_round(u64* __restrict__ plain, const u64* __restrict__ c0,
+                                                                 u64 c0_stride, MpcShares sh, int k, u64 sh_stride,
                                                                  const Mod* __restrict__ mods, BfvDecryptDev d,
                                                                  int n_power, int limbs)
 {
@@ -732,23 +752,21 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_bfv_merge(u64* __restrict
     for (int i = 0; i < limbs; i++) {
         const Mod m = mods[i];
         const u64 lane = n + ((u64) i << n_power);
-        const u64 src = lane + (((u64) limbs * b) << n_power);
         u64x2 acc = ld2(c0 + lane + c0_stride * b);
-        for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + src), m.q);
+        for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + lane), m.q);
         bfv_round_limb(acc.x, i, m, d, t0, g0);
         bfv_round_limb(acc.y, i, m, d, t1, g1);
     }
     st2(plain + ((u64) b << n_power) + n, u64x2{bfv_round_finish(t0, g0, d), bfv_round_finish(t1, g1, d)});
 }
 
-hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
-                            const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st)
+hipError_t kg_mpc_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, u64 sh_stride,
+                            const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st)
 {
-    MpcShares sh{};
-    for (int j = 0; j < k; j++) sh.p[j] = shares[j];
-    hipLaunchKernelGGL(k_kg_mpc_bfv_merge, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0, c0_stride,
-                       sh, k, mods, d, n_power, limbs);
-    return hipGetLastError();
+    return each_share_group(shares, k, [&](const MpcShares& sh, int cnt, bool) {
+        hipLaunchKernelGGL(k_kg_mpc_bfv_round, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0, c0_stride,
+                           sh, cnt, sh_stride, mods, d, n_power, limbs);
+    });
 }
 
 // ---- collective refresh ("distributed bootstrapping", {ckks,bfv}/mpcmanager.cu:1575-1903 / 1563-1752; kernels
@@ -808,51 +826,6 @@ hipError_t kg_mpc_refresh_noise(u64* share, const Mod* mods, int n_power, int l,
     return hipGetLastError();
 }
 
-// Both halves of a share in one pass (the reference: sk_multiplication twice, `addition` twice, temporaries):
-//   y < l:   h0[y]     = c1[y] * s[y]                      (+ what h0 holds: the transformed e0 - M)
-//   y >= l:  h1[y - l] = -(a[y - l] * s[y - l])            (+ what h1 holds: the transformed e1 + M)
-// share [batch][l + limbs][N]; c1 of item b at c1 + b * c1_stride (BFV: the share's own first half, add = 0)
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride,
-                                                                     const u64* __restrict__ sk,
-                                                                     const Mod* __restrict__ mods, int n_power, int l,
-                                                                     int limbs, DrbgKey crs, u64 crs_stream, int add)
-{
-    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
-    const int y = blockIdx.y, b = blockIdx.z;
-    const int j = y < l ? y : y - l;
-    const Mod m = mods[j];
-    const u64 lane = n + ((u64) j << n_power);
-    u64* dst = share + (((u64) b * (l + limbs) + y) << n_power) + n;
-    const u64x2 s = ld2(sk + lane);
-    u64x2 v;
-    if (y < l) {
-        v = mul2(ld2(c1 + lane + c1_stride * b), s, m);
-    } else {
-        const u64 at = ((u64) j << n_power) + n;
-        const u64x2 a{drbg_uniform(crs, crs_stream + b, at, m), drbg_uniform(crs, crs_stream + b, at + 1, m)};
-        v = sub2(u64x2{0, 0}, mul2(a, s, m), m.q);
-    }
-    if (add) v = add2(v, ld2(dst), m.q);
-    st2(dst, v);
-}
-
-hipError_t kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
-                                int l, int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_kg_mpc_refresh_share, vec_grid(n_power, l + limbs, batch), dim3(KG_THREADS), 0, st, share, c1,
-                       c1_stride, sk, mods, n_power, l, limbs, crs, crs_stream, add);
-    return hipGetLastError();
-}
-
-// D(m): limb y of the scaled plaintext of k_kg_bfv_message_add (Delta * m + the rounding fix, encryption.cu:158-172)
-__device__ __forceinline__ u64 bfv_scaled_plain(u64 message, const Mod& m, u64 coeff_div, const BfvPlainScale& p)
-{
-    u64 fix = message * p.Q_mod_t;
-    fix = fix + p.upper_threshold;
-    fix = (u64) (long long) (int) (fix / p.t);
-    return add_mod(mul_barrett(message, coeff_div, m), fix, m.q);
-}
-
 // BFV shares live in the coefficient domain: after the inverse transform of both halves
 //   h0[b][j] += e0 - D(M),  h1[b][j] += e1 + D(M),   M uniform in [0, t)^N (stream +2), e0 / e1 streams +0 / +1
 __global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_bfv_noise(u64* __restrict__ share,
@@ -887,38 +860,6 @@ hipError_t kg_mpc_refresh_bfv_noise(u64* share, const Mod* mods, const u64* coef
 {
     hipLaunchKernelGGL(k_kg_mpc_refresh_bfv_noise, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, share, mods,
                        coeff_div, p, make_mod(p.t), n_power, limbs, seed, stream, cdt);
-    return hipGetLastError();
-}
-
-// The coordinator's k-way sums read one half of every share: item b, limb y of share j at
-// sh.p[j] + b * sh_stride + sh_off + y * N.  k_kg_mpc_merge's body with those strides:
-//   out[b][y] = base[b][y] + sum_j share_j[b][y]     (out items out_stride apart, base items base_stride apart)
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base,
-                                                                   u64 base_stride, MpcShares sh, int k, u64 sh_stride,
-                                                                   u64 sh_off, const Mod* __restrict__ mods,
-                                                                   int n_power)
-{
-    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
-    const int y = blockIdx.y, b = blockIdx.z;
-    const u64 q = mods[y].q;
-    const u64 lane = n + ((u64) y << n_power);
-    u64x2 acc = ld2(base + lane + base_stride * b);
-    for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + sh_off + lane), q);
-    st2(out + lane + out_stride * b, acc);
-}
-
-hipError_t kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares,
-                              int k, u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch,
-                              hipStream_t st)
-{
-    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
-        MpcShares sh{};
-        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
-        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
-        hipLaunchKernelGGL(k_kg_mpc_refresh_sum, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, out,
-                           out_stride, done ? out : base, done ? out_stride : base_stride, sh, cnt, sh_stride, sh_off,
-                           mods, n_power);
-    }
     return hipGetLastError();
 }
 
@@ -1016,48 +957,11 @@ hipError_t kg_mpc_refresh_finish(u64* out, u64 out_stride, const u64* const* sha
                                  const Mod* mods, int n_power, int limbs, int batch, DrbgKey crs, u64 crs_stream,
                                  hipStream_t st)
 {
-    for (int done = 0; done < k; done += KG_MPC_MAX_SHARES) {
-        MpcShares sh{};
-        const int cnt = k - done < KG_MPC_MAX_SHARES ? k - done : KG_MPC_MAX_SHARES;
-        for (int j = 0; j < cnt; j++) sh.p[j] = shares[done + j];
+    return each_share_group(shares, k, [&](const MpcShares& sh, int cnt, bool first) {
         hipLaunchKernelGGL(k_kg_mpc_refresh_finish, vec_grid(n_power, limbs, batch), dim3(KG_THREADS), 0, st, out,
-                           out_stride, sh, cnt, sh_stride, sh_off, done ? 1 : add_out, done ? nullptr : plain,
-                           coeff_div, p, mods, n_power, crs, crs_stream, done ? 0 : 1);
-    }
-    return hipGetLastError();
-}
-
-// BFV coordinator, first step: k_kg_mpc_bfv_merge's sum and scale-and-round over the h0 halves of refresh shares;
-// plain [batch][N] mod t, k <= KG_MPC_MAX_SHARES
-__global__ __launch_bounds__(KG_THREADS) void k_kg_mpc_refresh_bfv_round(u64* __restrict__ plain,
-                                                                         const u64* __restrict__ c0, u64 c0_stride,
-                                                                         MpcShares sh, int k, u64 sh_stride,
-                                                                         const Mod* __restrict__ mods, BfvDecryptDev d,
-                                                                         int n_power, int limbs)
-{
-    const u64 n = ((u64) blockIdx.x * KG_THREADS + threadIdx.x) * KG_VEC;
-    const int b = blockIdx.y;
-    u64 t0 = 0, g0 = 0, t1 = 0, g1 = 0;
-    for (int i = 0; i < limbs; i++) {
-        const Mod m = mods[i];
-        const u64 lane = n + ((u64) i << n_power);
-        u64x2 acc = ld2(c0 + lane + c0_stride * b);
-        for (int j = 0; j < k; j++) acc = add2(acc, ld2(sh.p[j] + sh_stride * b + lane), m.q);
-        bfv_round_limb(acc.x, i, m, d, t0, g0);
-        bfv_round_limb(acc.y, i, m, d, t1, g1);
-    }
-    st2(plain + ((u64) b << n_power) + n, u64x2{bfv_round_finish(t0, g0, d), bfv_round_finish(t1, g1, d)});
-}
-
-hipError_t kg_mpc_refresh_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k,
-                                    u64 sh_stride, const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs,
-                                    int batch, hipStream_t st)
-{
-    MpcShares sh{};
-    for (int j = 0; j < k; j++) sh.p[j] = shares[j];
-    hipLaunchKernelGGL(k_kg_mpc_refresh_bfv_round, vec_grid(n_power, batch, 1), dim3(KG_THREADS), 0, st, plain, c0,
-                       c0_stride, sh, k, sh_stride, mods, d, n_power, limbs);
-    return hipGetLastError();
+                           out_stride, sh, cnt, sh_stride, sh_off, first ? add_out : 1, first ? plain : nullptr,
+                           coeff_div, p, mods, n_power, crs, crs_stream, first ? 1 : 0);
+    });
 }
 
 } // namespace hegpu

@@ -38,15 +38,18 @@ hipError_t kg_message_add(u64* ct, const u64* plain, const Mod* mods, int n_powe
 hipError_t kg_sk_multiplication_ckks(const u64* ct, u64* plain, const u64* sk, const Mod* mods, int n_power,
                                      int limbs, hipStream_t st);
 
-// BFV: part 0 of a fresh encryption gets Delta*m + the rounding fix (tail of
-// enc_div_lastq_bfv_kernel, encryption.cu:158-172); plain [N] mod t, ct [2][Q][N] coefficient domain
-hipError_t kg_bfv_message_add(u64* ct, const u64* plain, const Mod* mods, const u64* coeff_div, u64 Q_mod_t,
-                              u64 upper_threshold, u64 t, int n_power, int limbs, hipStream_t st);
-// addition_plain_bfv_poly / substraction_plain_bfv_poly (addition.cu:50-176): out = ct +- (Delta*m + fix)
-// on part 0, part 1 copied; sub != 0 subtracts
+// the scalars of the scaled plaintext D(m) = Delta * m + the rounding fix (ops.cpp: bfv_plain_scale)
+struct BfvPlainScale {
+    u64 Q_mod_t, upper_threshold, t;
+};
+// BFV: part 0 of a fresh encryption gets D(m) (tail of enc_div_lastq_bfv_kernel, encryption.cu:158-172); plain [N] mod t,
+// ct [2][Q][N] coefficient domain
+hipError_t kg_bfv_message_add(u64* ct, const u64* plain, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,
+                              int n_power, int limbs, hipStream_t st);
+// addition_plain_bfv_poly / substraction_plain_bfv_poly (addition.cu:50-176): out = ct +- D(m) on part 0, part 1 copied;
+// sub != 0 subtracts
 hipError_t kg_bfv_plain_addsub(const u64* ct, const u64* plain, u64* out, const Mod* mods, const u64* coeff_div,
-                               u64 Q_mod_t, u64 upper_threshold, u64 t, int n_power, int limbs, int sub,
-                               hipStream_t st);
+                               const BfvPlainScale& p, int n_power, int limbs, int sub, hipStream_t st);
 // threshold_kernel (multiplication.cu:274-296): plain [N] mod t -> [limbs][N] centred lift into each q_i
 hipError_t kg_bfv_threshold(const u64* plain, u64* out, const Mod* mods, const u64* upper_half_increment,
                             u64 upper_threshold, int n_power, int limbs, hipStream_t st);
@@ -80,39 +83,33 @@ hipError_t kg_mpc_relin_round2(u64* share, const u64* round1_sum, const u64* sk,
 // (threshold_pk_addition :118-140, multi_party_relinkey_method_I_stage_I / _II_kernel :321-462)
 hipError_t kg_mpc_accumulate(u64* out, const u64* const* shares, int k, const u64* second, int fold, int sum_second,
                              const Mod* mods, int n_power, int limbs, int units, hipStream_t st);
-// h[b] = c1[b] * s (+ h[b] when add: h holds the transformed error), h [batch][limbs][N], c1 of item b at c1 + b*stride
-hipError_t kg_mpc_decrypt_share(u64* h, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
-                                int limbs, int batch, int add, hipStream_t st);
+// A party's share, [batch][l + limbs][N]: h0 = c1 * s (+ h0) over l limbs, h1 = -(a * s) (+ h1) over `limbs`, a drawn from
+// the crs (below).  add: the share comes in holding the transformed noise.  c1 of item b at c1 + b * c1_stride (may be the
+// share itself).  limbs == 0: the share of a collective decryption, h = c1 * s (+ h) alone, no crs.
+hipError_t kg_mpc_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power, int l,
+                        int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st);
 // h[b][j] += one rounded Gaussian per (b, coefficient), coefficient domain
 hipError_t kg_mpc_add_gaussian(u64* h, const Mod* mods, int n_power, int limbs, int batch, DrbgKey seed, u64 stream,
                                const GaussCdt& cdt, hipStream_t st);
-// plain[b] = c0[b] + sum of the k shares' item b; plain and shares [batch][limbs][N]
-hipError_t kg_mpc_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
-                        int n_power, int limbs, int batch, hipStream_t st);
-// the same sum followed by decryption_kernel's scale-and-round; k <= KG_MPC_MAX_SHARES, plain [batch][N] mod t
-hipError_t kg_mpc_bfv_merge(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, const Mod* mods,
-                            const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st);
+// out[b][y] = base[b][y] + sum_j share_j[b * sh_stride + sh_off + y * N], y < limbs; items of out / base out_stride /
+// base_stride apart; any k (groups of 16, a later group's base is out)
+hipError_t kg_mpc_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares, int k,
+                      u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch, hipStream_t st);
+// plain[b] = decryption_kernel's scale-and-round of c0[b] + sum_j share_j[b * sh_stride]; k <= KG_MPC_MAX_SHARES,
+// plain [batch][N] mod t
+hipError_t kg_mpc_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k, u64 sh_stride,
+                            const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs, int batch, hipStream_t st);
 
 // ---- collective refresh (mpcmanager.cu distributed_bootstrapping_*; decryption.cu:480-667).  Shares: CKKS
 // [batch][l + limbs][N] (h0 over the l current limbs, h1 over all), BFV [batch][2][limbs][N].  `a` is drawn in place:
 // item b from stream crs_stream + b, limb j, coefficient n at index j * N + n (kg_uniform's order for one polynomial).
-struct BfvPlainScale {
-    u64 Q_mod_t, upper_threshold, t;
-};
 // share[b] = [(e0 - M) mod q_j, j < l | (e1 + M) mod q_j, j < limbs], coefficient domain; item b: streams stream + 3 b ..
 hipError_t kg_mpc_refresh_noise(u64* share, const Mod* mods, int n_power, int l, int limbs, int batch, DrbgKey seed,
                                 u64 stream, const GaussCdt& cdt, int mask_bits, hipStream_t st);
-// h0 = c1 * s (+ h0), h1 = -(a * s) (+ h1); add: the share holds the transformed noise
-hipError_t kg_mpc_refresh_share(u64* share, const u64* c1, u64 c1_stride, const u64* sk, const Mod* mods, int n_power,
-                                int l, int limbs, int batch, DrbgKey crs, u64 crs_stream, int add, hipStream_t st);
 // BFV, coefficient domain: h0 += e0 - D(M), h1 += e1 + D(M); item b: streams stream + 3 b ..
 hipError_t kg_mpc_refresh_bfv_noise(u64* share, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,
                                     int n_power, int limbs, int batch, DrbgKey seed, u64 stream, const GaussCdt& cdt,
                                     hipStream_t st);
-// out[b][y] = base[b][y] + sum_j share_j[b * sh_stride + sh_off + y * N], y < limbs; any k (groups of 16)
-hipError_t kg_mpc_refresh_sum(u64* out, u64 out_stride, const u64* base, u64 base_stride, const u64* const* shares,
-                              int k, u64 sh_stride, u64 sh_off, const Mod* mods, int n_power, int limbs, int batch,
-                              hipStream_t st);
 // exact centred lift of t [batch][l][N] from q_0..q_{l-1} to q_0..q_{limbs-1}, coefficient domain
 hipError_t kg_mpc_refresh_lift(u64* out, u64 out_stride, const u64* t, const Mod* mods, const u64* Mi_inv,
                                const u64* Mi, const u64* upper_half, const u64* M, int l, int limbs, int n_power,
@@ -122,10 +119,6 @@ hipError_t kg_mpc_refresh_finish(u64* out, u64 out_stride, const u64* const* sha
                                  int add_out, const u64* plain, const u64* coeff_div, const BfvPlainScale& p,
                                  const Mod* mods, int n_power, int limbs, int batch, DrbgKey crs, u64 crs_stream,
                                  hipStream_t st);
-// plain[b] = scale-and-round(c0[b] + sum_j h0_j[b]); k <= KG_MPC_MAX_SHARES
-hipError_t kg_mpc_refresh_bfv_round(u64* plain, const u64* c0, u64 c0_stride, const u64* const* shares, int k,
-                                    u64 sh_stride, const Mod* mods, const BfvDecryptDev& d, int n_power, int limbs,
-                                    int batch, hipStream_t st);
 
 // encode_kernel_bfv / decode_kernel_bfv (encoding.cu:11-41): slot idx <-> position location[idx]
 hipError_t kg_bfv_encode_scatter(u64* out, const long long* message, const int* location, u64 t, int message_size,

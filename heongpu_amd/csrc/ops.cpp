@@ -881,6 +881,26 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
 }
 
 // ------------------------------------------------------------------ keygen / encrypt / decrypt
+// The plain transforms of this half: `polys` contiguous polynomials, polynomial i under modulus i % mod_count of table
+// set `tables` (0: Q', 2: the plain modulus)
+static hipError_t transform(const Context& c, const u64* in, u64* out, int mod_count, int polys, bool inverse,
+                            hipStream_t st, int tables = 0)
+{
+    NttArgs a = c.ntt_args(tables);
+    a.in = in; a.out = out; a.mod_count = mod_count;
+    return ntt_launch(a, polys, inverse, st);
+}
+// ... and `batch` items of `limbs` polynomials each, item b at in + b * in_stride / out + b * out_stride; limb j under
+// modulus j, or mod_order[j]
+static hipError_t transform_items(const Context& c, const u64* in, u64 in_stride, u64* out, u64 out_stride, int limbs,
+                                  int batch, bool inverse, hipStream_t st, const int* mod_order = nullptr)
+{
+    NttArgs a = c.ntt_args(0);
+    a.in = in; a.out = out; a.mod_count = limbs; a.mod_order = mod_order;
+    a.polys_per_item = limbs; a.in_item_stride = in_stride; a.out_item_stride = out_stride;
+    return ntt_launch(a, batch * limbs, inverse, st);
+}
+
 hipError_t op_gen_secret_key(const Context& c, Rng& r, int hamming_weight, u64* sk, u64* ws, hipStream_t st)
 {
     const int n = (int) c.n;
@@ -901,42 +921,19 @@ hipError_t op_gen_secret_key(const Context& c, Rng& r, int hamming_weight, u64* 
     TRY(hipMemcpyAsync(dpos, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, st));
     TRY(hipStreamSynchronize(st)); // the staging vector dies with this call
     TRY(kg_secret_rns(dpos, dpos + hamming_weight, hamming_weight, sk, c.plan_qp.mods, c.n_power, c.Qp_size, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = sk; a.out = sk; a.mod_count = c.Qp_size;
-    return ntt_launch(a, c.Qp_size, false, st);
+    return transform(c, sk, sk, c.Qp_size, c.Qp_size, false, st);
 }
 
+// The single-party keys are the parties' shares with one generator in both roles: `a` first, then the errors
 hipError_t op_gen_public_key(const Context& c, Rng& r, const u64* sk, u64* pk, u64* ws, hipStream_t st)
 {
-    const int Qp = c.Qp_size;
-    u64* e = ws;
-    u64* av = ws + (u64) Qp * c.n;
-    TRY(kg_uniform(av, c.plan_qp.mods, c.n_power, Qp, 1, r.seed, r.stream++, st));
-    TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 1, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = e; a.out = e; a.mod_count = Qp;
-    TRY(ntt_launch(a, Qp, false, st));
-    return kg_publickey(pk, sk, e, av, c.plan_qp.mods, c.n_power, Qp, st);
+    return op_mpc_public_key_share(c, r, r, sk, pk, ws, st);
 }
 
 hipError_t op_gen_switch_key(const Context& c, Rng& r, const u64* sk, int galois_elt, const u64* old_sk, u64* key,
                              u64* ws, hipStream_t st)
 {
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    // method I: one digit per ciphertext prime; method II: the depth-0 digit partition
-    // (ckks/keygenerator.cu:326-414 uses d_leveled[0] and Sk_pair_leveled[0])
-    const int d = switch_key_digits(c);
-    const int width = c.P_size == 1 ? 1 : c.m2_width;
-    u64* e = ws;
-    u64* av = ws + (u64) d * Qp * c.n;
-    TRY(kg_uniform(av, c.plan_qp.mods, c.n_power, Qp, d, r.seed, r.stream++, st));
-    TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, d, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = e; a.out = e; a.mod_count = Qp;
-    TRY(ntt_launch(a, d * Qp, false, st));
-    const int inv = galois_elt ? (int) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0; // keygenerator.cu:474
-    return kg_switchkey(key, sk, e, av, c.plan_qp.mods, c.tab.factor, inv, old_sk, c.n_power, Qp, d, width, Q,
-                        c.P_size, st);
+    return op_mpc_switch_key_share(c, r, r, sk, galois_elt, nullptr, key, ws, st, old_sk);
 }
 
 // (pk*u + e) / P with rounding: the common front of both encryptions (encryptor.cu:52-100)
@@ -950,12 +947,9 @@ static hipError_t encrypt_zero(const Context& c, Rng& r, const u64* pk, u64* ct,
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_ternary(u, mods, np, Qp, 1, r.seed, r.stream++, st));
     TRY(kg_gaussian(e, mods, np, Qp, 2, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = u; a.out = u; a.mod_count = Qp;
-    TRY(ntt_launch(a, Qp, false, st));
+    TRY(transform(c, u, u, Qp, Qp, false, st));
     TRY(kg_pk_u(pk, u, pku, mods, np, Qp, st));
-    a.in = pku; a.out = pku;
-    TRY(ntt_launch(a, 2 * Qp, true, st));
+    TRY(transform(c, pku, pku, Qp, 2 * Qp, true, st));
     TRY(rns_addition(pku, e, pku, mods, np, Qp, 2, 1, 0, st));
     return rns_moddown_extended(pku, 0, nullptr, 0, ct, 0, mods, c.tab.half, c.tab.half_mod,
                                 c.tab.last_q_modinv, np, Qp, Q, Qp, Q, c.P_size, 0, 1, st);
@@ -965,18 +959,21 @@ hipError_t op_ckks_encrypt(const Context& c, Rng& r, const u64* pk, const u64* p
                            hipStream_t st)
 {
     TRY(encrypt_zero(c, r, pk, ct, ws, st));                                               // :52-100
-    NttArgs a = c.ntt_args(0);
-    a.in = ct; a.out = ct; a.mod_count = c.Q_size;
-    TRY(ntt_launch(a, 2 * c.Q_size, false, st));                                           // :103
+    TRY(transform(c, ct, ct, c.Q_size, 2 * c.Q_size, false, st));                          // :103
     return kg_message_add(ct, plain, c.plan_qp.mods, c.n_power, c.Q_size, st);             // :107
+}
+
+BfvPlainScale bfv_plain_scale(const Context& c)
+{
+    return BfvPlainScale{c.hv.Q_mod_t, c.hv.upper_threshold, c.plain_modulus};
 }
 
 hipError_t op_bfv_encrypt(const Context& c, Rng& r, const u64* pk, const u64* plain, u64* ct, u64* ws,
                           hipStream_t st)
 {
     TRY(encrypt_zero(c, r, pk, ct, ws, st));
-    return kg_bfv_message_add(ct, plain, c.plan_qp.mods, c.tab.coeff_div_plain_modulus, c.hv.Q_mod_t,
-                              c.hv.upper_threshold, c.plain_modulus, c.n_power, c.Q_size, st);
+    return kg_bfv_message_add(ct, plain, c.plan_qp.mods, c.tab.coeff_div_plain_modulus, bfv_plain_scale(c), c.n_power,
+                              c.Q_size, st);
 }
 
 static BfvDecryptDev bfv_decrypt_dev(const Context& c)
@@ -996,24 +993,18 @@ hipError_t op_bfv_decrypt(const Context& c, const u64* ct, const u64* sk, u64* p
     const int np = c.n_power, Q = c.Q_size;
     const u64* ct1 = ct + ((u64) Q << np);
     u64* t1 = ws; // [Q][N]
-    NttArgs a = c.ntt_args(0);
-    a.in = ct1; a.out = t1; a.mod_count = Q;
-    TRY(ntt_launch(a, Q, false, st));                                                      // :62
+    TRY(transform(c, ct1, t1, Q, Q, false, st));                                           // :62
     TRY(kg_sk_multiplication(t1, sk, t1, c.plan_qp.mods, np, Q, st));                      // :65
-    a.in = t1; a.out = t1;
-    TRY(ntt_launch(a, Q, true, st));                                                       // :101
+    TRY(transform(c, t1, t1, Q, Q, true, st));                                             // :101
     return kg_bfv_decryption(ct, t1, plain, c.plan_qp.mods, bfv_decrypt_dev(c), np, Q, st); // :107
 }
 
 hipError_t op_bfv_noise_rns(const Context& c, const u64* ct, const u64* sk, u64* out, hipStream_t st)
 {
     const int np = c.n_power, Q = c.Q_size;
-    NttArgs a = c.ntt_args(0);
-    a.in = ct + ((u64) Q << np); a.out = out; a.mod_count = Q;
-    TRY(ntt_launch(a, Q, false, st));
+    TRY(transform(c, ct + ((u64) Q << np), out, Q, Q, false, st));
     TRY(kg_sk_multiplication(out, sk, out, c.plan_qp.mods, np, Q, st));
-    a.in = out; a.out = out;
-    TRY(ntt_launch(a, Q, true, st));
+    TRY(transform(c, out, out, Q, Q, true, st));
     return kg_coeff_multadd(ct, out, out, c.plain_modulus, c.plan_qp.mods, np, Q, st);
 }
 
@@ -1023,17 +1014,13 @@ hipError_t op_bfv_encode(const Context& c, const long long* message, int message
     if (message_size < 0 || message_size > (int) c.n) return hipErrorInvalidValue;
     TRY(kg_bfv_encode_scatter(plain, message, c.tab.encoding_location, c.plain_modulus, message_size, c.n_power,
                               st));                                                        // :66
-    NttArgs a = c.ntt_args(2);
-    a.in = plain; a.out = plain; a.mod_count = 1;
-    return ntt_launch(a, 1, true, st);                                                     // :81
+    return transform(c, plain, plain, 1, 1, true, st, 2);                                  // :81
 }
 
 hipError_t op_bfv_decode(const Context& c, const u64* plain, u64* message, u64* ws, hipStream_t st)
 {
     if (!c.plan_plain.count) return hipErrorNotSupported;
-    NttArgs a = c.ntt_args(2);
-    a.in = plain; a.out = ws; a.mod_count = 1;
-    TRY(ntt_launch(a, 1, false, st));                                                      // :234
+    TRY(transform(c, plain, ws, 1, 1, false, st, 2));                                      // :234
     return kg_bfv_decode_gather(message, ws, c.tab.encoding_location, c.n_power, st);   // :239
 }
 
@@ -1043,14 +1030,10 @@ hipError_t op_bfv_multiply_plain(const Context& c, const u64* ct, const u64* pla
     u64* pl = ws; // [Q][N]
     TRY(kg_bfv_threshold(plain, pl, c.plan_qp.mods, c.tab.upper_halfincrement, c.hv.upper_threshold, np, Q,
                          st));                                                             // :454
-    NttArgs a = c.ntt_args(0);
-    a.in = pl; a.out = pl; a.mod_count = Q;
-    TRY(ntt_launch(a, Q, false, st));                                                      // :479
-    a.in = ct; a.out = out;
-    TRY(ntt_launch(a, 2 * Q, false, st));                                                  // :484
+    TRY(transform(c, pl, pl, Q, Q, false, st));                                            // :479
+    TRY(transform(c, ct, out, Q, 2 * Q, false, st));                                       // :484
     TRY(kg_pk_u(out, pl, out, c.plan_qp.mods, np, Q, st));                                 // :489 cipherplain_kernel
-    a.in = out; a.out = out;
-    return ntt_launch(a, 2 * Q, true, st);                                                 // :496
+    return transform(c, out, out, Q, 2 * Q, true, st);                                     // :496
 }
 
 // HEOperator<BFV>::transform_to_ntt_bfv_plain (bfv/operator.cu:1398-1431): threshold lift mod every q_j, forward NTT
@@ -1058,9 +1041,7 @@ hipError_t op_bfv_plain_to_ntt(const Context& c, const u64* plain, u64* out, hip
 {
     TRY(kg_bfv_threshold(plain, out, c.plan_qp.mods, c.tab.upper_halfincrement, c.hv.upper_threshold,
                          c.n_power, c.Q_size, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = out; a.out = out; a.mod_count = c.Q_size;
-    return ntt_launch(a, c.Q_size, false, st);
+    return transform(c, out, out, c.Q_size, c.Q_size, false, st);
 }
 
 static int log2i(u64 v)
@@ -1078,12 +1059,10 @@ hipError_t op_ckks_encode(const Context& c, int mode, const double* message, int
     const int slots = (int) (c.n >> 1), Q = c.Q_size;
     if (mode == 3)                                                                         // encoder.cu:412-446
         return en_coeff_conversion(plain, nullptr, 0, true, scalar * scale, c.plan_qp.mods, Q, c.n_power, st);
-    NttArgs a = c.ntt_args(0);
-    a.in = plain; a.out = plain; a.mod_count = Q;
     if (mode == 2) {                                                                       // :222-261
         if (message_size < 0 || message_size > (int) c.n) return hipErrorInvalidValue;
         TRY(en_coeff_conversion(plain, message, message_size, false, scale, c.plan_qp.mods, Q, c.n_power, st));
-        return ntt_launch(a, Q, false, st);
+        return transform(c, plain, plain, Q, Q, false, st);
     }
     if (message_size < 0 || message_size > slots) return hipErrorInvalidValue;
     void* cbuf = ws; // slots complex doubles = N words
@@ -1091,7 +1070,19 @@ hipError_t op_ckks_encode(const Context& c, int mode, const double* message, int
     // double -> complex (:120) in the transform's first load
     TRY(en_special_fft(cbuf, c.tab.special_ifft_roots_table, log2i(slots), true, fix, st, message, message_size, mode == 1));
     TRY(en_conversion(plain, cbuf, c.plan_qp.mods, Q, c.tab.reverse_order, c.n_power, st)); // :138
-    return ntt_launch(a, Q, false, st);                                                    // :153
+    return transform(c, plain, plain, Q, Q, false, st);                                    // :153
+}
+
+// The decoder's CRT tables at a depth (ckks/decoder.cu:474-482): rows of Q, Q - 1, ... entries, Mi rows of their squares
+struct DecoderTables {
+    const u64 *Mi_inv, *Mi, *upper_half, *M;
+};
+static DecoderTables decoder_tables(const Context& c, int depth)
+{
+    const int loc1 = triangle_offset(c.Q_size, depth);
+    int loc2 = 0;
+    for (int i = 0; i < depth; i++) loc2 += (c.Q_size - i) * (c.Q_size - i);
+    return {c.tab.Mi_inv + loc1, c.tab.Mi + loc2, c.tab.upper_half_threshold + loc1, c.tab.decryption_modulus + loc1};
 }
 
 // mode: 0 the N/2 real parts, 1 the N/2 complex slots, 2 the N coefficients
@@ -1102,18 +1093,13 @@ hipError_t op_ckks_decode(const Context& c, int mode, const u64* plain, int dept
     if (l < 1) return hipErrorInvalidValue;
     u64* coeff = ws;                      // [l][N]
     void* cbuf = ws + (u64) l * c.n;      // slots complex doubles
-    NttArgs a = c.ntt_args(0);
-    a.in = plain; a.out = coeff; a.mod_count = l;
-    TRY(ntt_launch(a, l, true, st));                                                       // :469
-    int counter = c.Q_size, loc1 = 0, loc2 = 0;                                            // :474-482
-    for (int i = 0; i < depth; i++) { loc1 += counter; loc2 += counter * counter; counter--; }
+    TRY(transform(c, plain, coeff, l, l, true, st));                                       // :469
+    const DecoderTables d = decoder_tables(c, depth);
     if (mode == 2)                                                                         // :586-635
-        return en_coeff_compose(message, coeff, c.plan_qp.mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2,
-                                c.tab.upper_half_threshold + loc1, c.tab.decryption_modulus + loc1, l, scale,
-                                c.n_power, st);
-    TRY(en_compose(cbuf, coeff, c.plan_qp.mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2,
-                   c.tab.upper_half_threshold + loc1, c.tab.decryption_modulus + loc1, l, scale,
-                   c.tab.reverse_order, c.n_power, st));                                // :485
+        return en_coeff_compose(message, coeff, c.plan_qp.mods, d.Mi_inv, d.Mi, d.upper_half, d.M, l, scale, c.n_power,
+                                st);
+    TRY(en_compose(cbuf, coeff, c.plan_qp.mods, d.Mi_inv, d.Mi, d.upper_half, d.M, l, scale, c.tab.reverse_order,
+                   c.n_power, st));                                                        // :485
     // :502, complex -> double (:505) in the transform's last store
     return en_special_fft(cbuf, c.tab.special_fft_roots_table, log2i(slots), false, 1.0, st, nullptr, 0, 0, message, mode == 1);
 }
@@ -1139,15 +1125,15 @@ hipError_t op_mpc_public_key_share(const Context& c, Rng& crs, Rng& r, const u64
     u64* av = ws + (u64) Qp * c.n;
     TRY(kg_uniform(av, c.plan_qp.mods, c.n_power, Qp, 1, crs.seed, crs.stream++, st));
     TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 1, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = e; a.out = e; a.mod_count = Qp;
-    TRY(ntt_launch(a, Qp, false, st));
+    TRY(transform(c, e, e, Qp, Qp, false, st));
     return kg_publickey(share, sk, e, av, c.plan_qp.mods, c.n_power, Qp, st);
 }
 
 hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, int galois_elt, u64* u_out,
-                                   u64* share, u64* ws, hipStream_t st)
+                                   u64* share, u64* ws, hipStream_t st, const u64* old_sk)
 {
+    // method I: one digit per ciphertext prime; method II: the depth-0 digit partition
+    // (ckks/keygenerator.cu:326-414 uses d_leveled[0] and Sk_pair_leveled[0])
     const int Q = c.Q_size, Qp = c.Qp_size, d = switch_key_digits(c);
     const int width = c.P_size == 1 ? 1 : c.m2_width;
     const int errs = u_out ? 2 : 1; // round 1 of the relinearisation key carries an error in both parts
@@ -1156,16 +1142,13 @@ hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_uniform(av, mods, c.n_power, Qp, d, crs.seed, crs.stream++, st));
     TRY(kg_gaussian(e, mods, c.n_power, Qp, errs * d, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = e; a.out = e; a.mod_count = Qp;
-    TRY(ntt_launch(a, errs * d * Qp, false, st));
+    TRY(transform(c, e, e, Qp, errs * d * Qp, false, st));
     if (u_out) {
         TRY(kg_ternary(u_out, mods, c.n_power, Qp, 1, r.seed, r.stream++, st));
-        a.in = u_out; a.out = u_out;
-        TRY(ntt_launch(a, Qp, false, st));
+        TRY(transform(c, u_out, u_out, Qp, Qp, false, st));
     }
-    const int inv = galois_elt ? (int) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0;
-    return kg_switchkey(share, sk, e, av, mods, c.tab.factor, inv, nullptr, c.n_power, Qp, d, width, Q, c.P_size, st,
+    const int inv = galois_elt ? (int) inv_mod_2n((u64) galois_elt, 2 * c.n) : 0; // keygenerator.cu:474
+    return kg_switchkey(share, sk, e, av, mods, c.tab.factor, inv, old_sk, c.n_power, Qp, d, width, Q, c.P_size, st,
                         u_out, u_out ? e + (u64) d * Qp * c.n : nullptr);
 }
 
@@ -1175,9 +1158,7 @@ hipError_t op_mpc_relin_key_share_round2(const Context& c, Rng& r, const u64* sk
     const int Qp = c.Qp_size, d = switch_key_digits(c);
     u64* e = ws; // [2][d][Q'][N]
     TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 2 * d, r.seed, r.stream++, c.gauss_cdt, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = e; a.out = e; a.mod_count = Qp;
-    TRY(ntt_launch(a, 2 * d * Qp, false, st));
+    TRY(transform(c, e, e, Qp, 2 * d * Qp, false, st));
     return kg_mpc_relin_round2(share, round1_sum, sk, u, e, c.plan_qp.mods, c.n_power, Qp, d, st);
 }
 
@@ -1196,10 +1177,8 @@ hipError_t op_mpc_ckks_decrypt_share(const Context& c, Rng& r, const u64* ct, u6
     const int l = c.Q_size - depth;
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_gaussian(share, mods, c.n_power, l, batch, r.seed, r.stream++, c.gauss_cdt, st));   // :1510
-    NttArgs a = c.ntt_args(0);
-    a.in = share; a.out = share; a.mod_count = l;
-    TRY(ntt_launch(a, batch * l, false, st));                                                  // :1524
-    return kg_mpc_decrypt_share(share, ct + ((u64) l << c.n_power), cs, sk, mods, c.n_power, l, batch, 1, st);
+    TRY(transform(c, share, share, l, batch * l, false, st));                                  // :1524
+    return kg_mpc_share(share, ct + ((u64) l << c.n_power), cs, sk, mods, c.n_power, l, 0, batch, DrbgKey{}, 0, 1, st);
 }
 
 hipError_t op_mpc_bfv_decrypt_share(const Context& c, Rng& r, const u64* ct, u64 cs, const u64* sk, u64* share,
@@ -1207,34 +1186,41 @@ hipError_t op_mpc_bfv_decrypt_share(const Context& c, Rng& r, const u64* ct, u64
 {
     const int np = c.n_power, Q = c.Q_size;
     const Mod* mods = c.plan_qp.mods;
-    NttArgs a = c.ntt_args(0);
-    a.in = ct + ((u64) Q << np); a.out = share; a.mod_count = Q;
-    a.polys_per_item = Q; a.in_item_stride = cs; a.out_item_stride = (u64) Q << np;
-    TRY(ntt_launch(a, batch * Q, false, st));                                                  // :1461
-    TRY(kg_mpc_decrypt_share(share, share, (u64) Q << np, sk, mods, np, Q, batch, 0, st));     // :1465
-    a.in = share; a.polys_per_item = 0;
-    TRY(ntt_launch(a, batch * Q, true, st));                                                   // :1492
+    TRY(transform_items(c, ct + ((u64) Q << np), cs, share, (u64) Q << np, Q, batch, false, st)); // :1461
+    TRY(kg_mpc_share(share, share, (u64) Q << np, sk, mods, np, Q, 0, batch, DrbgKey{}, 0, 0, st)); // :1465
+    TRY(transform(c, share, share, Q, batch * Q, true, st));                                   // :1492
     return kg_mpc_add_gaussian(share, mods, np, Q, batch, r.seed, r.stream++, c.gauss_cdt, st); // :1499-1510
 }
 
 hipError_t op_mpc_ckks_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
                                      int depth, u64* plain, int batch, hipStream_t st)
 {
-    return kg_mpc_merge(plain, ct, cs, shares, k, c.plan_qp.mods, c.n_power, c.Q_size - depth, batch, st);
+    const int l = c.Q_size - depth;
+    const u64 stride = (u64) l << c.n_power;
+    return kg_mpc_sum(plain, stride, ct, cs, shares, k, stride, 0, c.plan_qp.mods, c.n_power, l, batch, st);
+}
+
+// plain [batch][N] = scale-and-round(c0 + the sum of the k shares, items sh_stride apart).  The rounding kernel takes one
+// group of shares: everything but the last group is summed into head_sum [batch][Q][N] first.
+static hipError_t bfv_sum_and_round(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
+                                    u64 sh_stride, u64* plain, u64* head_sum, int batch, hipStream_t st)
+{
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    const int head = (k - 1) / KG_MPC_MAX_SHARES * KG_MPC_MAX_SHARES;
+    if (head) {
+        const u64 part = (u64) Q << np;
+        TRY(kg_mpc_sum(head_sum, part, ct, cs, shares, head, sh_stride, 0, mods, np, Q, batch, st));
+        ct = head_sum;
+        cs = part;
+    }
+    return kg_mpc_bfv_round(plain, ct, cs, shares + head, k - head, sh_stride, mods, bfv_decrypt_dev(c), np, Q, batch, st);
 }
 
 hipError_t op_mpc_bfv_decrypt_merge(const Context& c, const u64* ct, u64 cs, const u64* const* shares, int k,
                                     u64* plain, int batch, u64* ws, hipStream_t st)
 {
-    const int np = c.n_power, Q = c.Q_size;
-    const Mod* mods = c.plan_qp.mods;
-    if (k > KG_MPC_MAX_SHARES) { // everything but the last group is summed into ws first
-        const int head = (k - 1) / KG_MPC_MAX_SHARES * KG_MPC_MAX_SHARES;
-        TRY(kg_mpc_merge(ws, ct, cs, shares, head, mods, np, Q, batch, st));
-        return kg_mpc_bfv_merge(plain, ws, (u64) Q << np, shares + head, k - head, mods, bfv_decrypt_dev(c), np, Q,
-                                batch, st);
-    }
-    return kg_mpc_bfv_merge(plain, ct, cs, shares, k, mods, bfv_decrypt_dev(c), np, Q, batch, st);
+    return bfv_sum_and_round(c, ct, cs, shares, k, (u64) c.Q_size << c.n_power, plain, ws, batch, st);
 }
 
 // ------------------------------------------------------------------ collective refresh
@@ -1261,11 +1247,6 @@ static u64 take_streams(Rng& r, int count)
     return first;
 }
 
-static BfvPlainScale bfv_plain_scale(const Context& c)
-{
-    return BfvPlainScale{c.hv.Q_mod_t, c.hv.upper_threshold, c.plain_modulus};
-}
-
 hipError_t op_mpc_ckks_refresh_share(const Context& c, Rng& crs, Rng& r, const u64* ct, u64 cs, const u64* sk,
                                      int depth, int mask_bits, u64* share, int batch, hipStream_t st)
 {
@@ -1273,13 +1254,12 @@ hipError_t op_mpc_ckks_refresh_share(const Context& c, Rng& crs, Rng& r, const u
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_mpc_refresh_noise(share, mods, np, l, Q, batch, r.seed, r.stream, c.gauss_cdt, mask_bits, st));
     r.stream += 3 * (u64) batch;
-    NttArgs a = c.ntt_args(0); // one transform over both halves: moduli 0..l-1, then 0..Q-1
-    a.in = share; a.out = share; a.mod_count = l + Q;
-    a.mod_order = c.tab.mpc_refresh_order + (depth * 2 * Q - depth * (depth - 1) / 2);
-    a.polys_per_item = l + Q; a.in_item_stride = a.out_item_stride = (u64) (l + Q) << np;
-    TRY(ntt_launch(a, batch * (l + Q), false, st));
-    return kg_mpc_refresh_share(share, ct + ((u64) l << np), cs, sk, mods, np, l, Q, batch, crs.seed, take_streams(crs, batch), 1,
-                                st);
+    const u64 sh_stride = (u64) (l + Q) << np;
+    // one transform over both halves: moduli 0..l-1, then 0..Q-1
+    TRY(transform_items(c, share, sh_stride, share, sh_stride, l + Q, batch, false, st,
+                        c.tab.mpc_refresh_order + (depth * 2 * Q - depth * (depth - 1) / 2)));
+    return kg_mpc_share(share, ct + ((u64) l << np), cs, sk, mods, np, l, Q, batch, crs.seed, take_streams(crs, batch), 1,
+                        st);
 }
 
 hipError_t op_mpc_ckks_refresh_merge(const Context& c, Rng& crs, const u64* ct, u64 cs, const u64* const* shares,
@@ -1289,18 +1269,11 @@ hipError_t op_mpc_ckks_refresh_merge(const Context& c, Rng& crs, const u64* ct, 
     const Mod* mods = c.plan_qp.mods;
     const u64 sh_stride = (u64) (l + Q) << np, t_stride = (u64) l << np;
     u64* t = ws; // [batch][l][N]
-    TRY(kg_mpc_refresh_sum(t, t_stride, ct, cs, shares, k, sh_stride, 0, mods, np, l, batch, st));
-    NttArgs a = c.ntt_args(0);
-    a.in = t; a.out = t; a.mod_count = l;
-    TRY(ntt_launch(a, batch * l, true, st));
-    const int loc1 = triangle_offset(Q, depth);
-    int loc2 = 0;
-    for (int i = 0; i < depth; i++) loc2 += (Q - i) * (Q - i);
-    TRY(kg_mpc_refresh_lift(out, so, t, mods, c.tab.Mi_inv + loc1, c.tab.Mi + loc2, c.tab.upper_half_threshold + loc1,
-                            c.tab.decryption_modulus + loc1, l, Q, np, batch, st));
-    a.in = out; a.out = out; a.mod_count = Q;
-    a.polys_per_item = Q; a.in_item_stride = a.out_item_stride = so;
-    TRY(ntt_launch(a, batch * Q, false, st));
+    TRY(kg_mpc_sum(t, t_stride, ct, cs, shares, k, sh_stride, 0, mods, np, l, batch, st));
+    TRY(transform(c, t, t, l, batch * l, true, st));
+    const DecoderTables d = decoder_tables(c, depth);
+    TRY(kg_mpc_refresh_lift(out, so, t, mods, d.Mi_inv, d.Mi, d.upper_half, d.M, l, Q, np, batch, st));
+    TRY(transform_items(c, out, so, out, so, Q, batch, false, st));
     return kg_mpc_refresh_finish(out, so, shares, k, sh_stride, t_stride, 1, nullptr, nullptr, BfvPlainScale{}, mods,
                                  np, Q, batch, crs.seed, take_streams(crs, batch), st);
 }
@@ -1311,13 +1284,9 @@ hipError_t op_mpc_bfv_refresh_share(const Context& c, Rng& crs, Rng& r, const u6
     const int np = c.n_power, Q = c.Q_size;
     const Mod* mods = c.plan_qp.mods;
     const u64 sh_stride = (u64) (2 * Q) << np;
-    NttArgs a = c.ntt_args(0);
-    a.in = ct + ((u64) Q << np); a.out = share; a.mod_count = Q;
-    a.polys_per_item = Q; a.in_item_stride = cs; a.out_item_stride = sh_stride;
-    TRY(ntt_launch(a, batch * Q, false, st));
-    TRY(kg_mpc_refresh_share(share, share, sh_stride, sk, mods, np, Q, Q, batch, crs.seed, take_streams(crs, batch), 0, st));
-    a.in = share; a.polys_per_item = 0;
-    TRY(ntt_launch(a, batch * 2 * Q, true, st));
+    TRY(transform_items(c, ct + ((u64) Q << np), cs, share, sh_stride, Q, batch, false, st));
+    TRY(kg_mpc_share(share, share, sh_stride, sk, mods, np, Q, Q, batch, crs.seed, take_streams(crs, batch), 0, st));
+    TRY(transform(c, share, share, Q, batch * 2 * Q, true, st));
     TRY(kg_mpc_refresh_bfv_noise(share, mods, c.tab.coeff_div_plain_modulus, bfv_plain_scale(c), np, Q, batch, r.seed,
                                  r.stream, c.gauss_cdt, st));
     r.stream += 3 * (u64) batch;
@@ -1332,20 +1301,10 @@ hipError_t op_mpc_bfv_refresh_merge(const Context& c, Rng& crs, const u64* ct, u
     const u64 sh_stride = (u64) (2 * Q) << np, part = (u64) Q << np;
     u64* plain = ws;                          // [batch][N]
     u64* head_sum = ws + ((u64) batch << np); // [batch][Q][N], beyond 16 shares
-    if (k > KG_MPC_MAX_SHARES) {
-        const int head = (k - 1) / KG_MPC_MAX_SHARES * KG_MPC_MAX_SHARES;
-        TRY(kg_mpc_refresh_sum(head_sum, part, ct, cs, shares, head, sh_stride, 0, mods, np, Q, batch, st));
-        TRY(kg_mpc_refresh_bfv_round(plain, head_sum, part, shares + head, k - head, sh_stride, mods,
-                                     bfv_decrypt_dev(c), np, Q, batch, st));
-    } else {
-        TRY(kg_mpc_refresh_bfv_round(plain, ct, cs, shares, k, sh_stride, mods, bfv_decrypt_dev(c), np, Q, batch, st));
-    }
+    TRY(bfv_sum_and_round(c, ct, cs, shares, k, sh_stride, plain, head_sum, batch, st));
     TRY(kg_mpc_refresh_finish(out, so, shares, k, sh_stride, part, 0, plain, c.tab.coeff_div_plain_modulus,
                               bfv_plain_scale(c), mods, np, Q, batch, crs.seed, take_streams(crs, batch), st));
-    NttArgs a = c.ntt_args(0); // c1' = INTT(a)
-    a.in = out + part; a.out = out + part; a.mod_count = Q;
-    a.polys_per_item = Q; a.in_item_stride = a.out_item_stride = so;
-    return ntt_launch(a, batch * Q, true, st);
+    return transform_items(c, out + part, so, out + part, so, Q, batch, true, st); // c1' = INTT(a)
 }
 
 } // namespace hegpu

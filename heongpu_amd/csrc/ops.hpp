@@ -79,6 +79,8 @@ hipError_t op_ckks_encrypt(const Context& c, Rng& r, const u64* pk, const u64* p
                            hipStream_t st);
 // HEDecryptor<CKKS>::decrypt_ckks (ckks/decryptor.cu:38-58); plain [l][N], l = Q - depth
 hipError_t op_ckks_decrypt(const Context& c, const u64* ct, const u64* sk, int depth, u64* plain, hipStream_t st);
+// the scalars of the BFV scaled plaintext, for every kernel that forms it
+BfvPlainScale bfv_plain_scale(const Context& c);
 // HEEncryptor<BFV>::encrypt_bfv (bfv/encryptor.cu:39-108); plain [N] mod t, ct [2][Q][N] coefficient domain
 hipError_t op_bfv_encrypt(const Context& c, Rng& r, const u64* pk, const u64* plain, u64* ct, u64* ws,
                           hipStream_t st);
@@ -114,8 +116,9 @@ hipError_t op_mpc_public_key_share(const Context& c, Rng& crs, Rng& r, const u64
 // u_out == nullptr: generate_galois_key_method_I / _II_stage_1 (:751-1308), today's Galois key with the common a
 // (galois_elt != 0).  u_out != nullptr: generate_relin_key_method_I_stage_1 / _II_stage_1 (:121-229, :346-462), round 1 of the
 // relinearisation key; u_out [Q'][N] receives the party's ephemeral secret u_i (NTT domain), needed again in round 2
+// old_sk (single party only): the switching key that carries old_sk
 hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64* sk, int galois_elt, u64* u_out,
-                                   u64* share, u64* ws, hipStream_t st);
+                                   u64* share, u64* ws, hipStream_t st, const u64* old_sk = nullptr);
 // generate_relin_key_method_I_stage_3 / _II_stage_3 (:231-344, :464-582)
 hipError_t op_mpc_relin_key_share_round2(const Context& c, Rng& r, const u64* sk, const u64* u, const u64* round1_sum,
                                          u64* share, u64* ws, hipStream_t st);

@@ -447,3 +447,58 @@ def test_more_shares_than_one_launch_takes(hg, oracle, torch):
     cbt = cb.bfv_encrypt(hg.Rng(2), pr.public_key(), hg.to_device(m))
     merged, _ = pr.bfv_decrypt(cbt, 2 * Qb * N)
     assert np.array_equal(hg.to_host(merged), m)
+
+
+def test_second_share_group_and_strides_that_differ(hg, oracle, torch):
+    """17 shares (a second group of one), batch 3, ciphertexts 64 words further apart than they are long, CKKS at depth 1
+    of a three-prime chain: the second group must read the first group's sum at the OUTPUT's item stride, not the
+    ciphertext's, and the shares' item stride is neither of them.  The padding holds random words, so a read at the wrong
+    stride changes the result.  The decrypt share is checked on its own: share - c1 * s is the transform of one error
+    polynomial per item, every coefficient a rounded Gaussian clipped at 6 sigma (at most B)."""
+    k, batch, depth, pad = 17, 3, 1, 64
+    c = hg.Context.from_bit_sizes(hg.CKKS, N, [50, 30, 30], [50], sec=hg.SEC_NONE)
+    primes = [int(x) for x in c.table("modulus")]
+    c.upload()
+    l = c.Q_size - depth
+    words, g = 2 * l * N, np.random.default_rng(31)
+    stride = words + pad
+    q = np.array(primes[:l], dtype=np.uint64).reshape(1, l, 1)
+
+    def padded(items):
+        buf = g.integers(0, 1 << 62, (batch, stride), dtype=np.uint64)
+        buf[:, :words] = items.reshape(batch, words)
+        return hg.to_device(buf.reshape(-1))
+
+    def residues(parts):
+        return np.stack([g.integers(0, primes[j], (batch, parts, N), dtype=np.uint64) for j in range(l)], axis=2)
+
+    # ---- CKKS merge: c0 + the modular sum of the shares, item by item
+    ct = residues(2)  # [batch][2][l][N]
+    hs = [residues(1).reshape(batch, l, N) for _ in range(k)]
+    got = hg.to_host(c.mpc_ckks_decrypt_merge(padded(ct), stride, [hg.to_device(x.reshape(-1)) for x in hs], depth, batch))
+    want = ct[:, 0]
+    for x in hs:
+        want = (want + x) % q
+    assert np.array_equal(got.reshape(batch, l, N), want), "merge of 17 strided shares"
+    # ---- CKKS decrypt share: share - c1 * s = NTT(e), |e| <= B
+    rng = hg.Rng(311)
+    sk = c.generate_secret_key(rng)
+    s = hg.to_host(sk).reshape(c.Q_prime_size, N)[:l]
+    share = hg.to_host(c.mpc_ckks_decrypt_share(rng, padded(ct), stride, sk, depth, batch)).reshape(batch, l, N)
+    diff = np.stack([(share[b] + q[0] - _mul_mod(ct[b, 1], s, primes)) % q[0] for b in range(batch)])
+    dev = hg.to_device(diff.reshape(-1))
+    c.ntt(dev, dev, True, batch * l, l)
+    e = hg.to_host(dev).reshape(batch, l, N)
+    worst = max(int(np.abs(_centred_limbs(e[b], primes)).max()) for b in range(batch))
+    print(f"decrypt share at depth 1, batch 3, padded stride: max |e| = {worst} (bound {B})")
+    assert worst <= B
+    # ---- BFV merge: 17 real shares of three padded ciphertexts open to the messages
+    cb, _, _, t = _bfv(hg, oracle)
+    words = 2 * cb.Q_size * N
+    stride = words + pad
+    p = Parties(hg, cb, k)
+    pk, enc = p.public_key(), hg.Rng(312)
+    msgs = g.integers(0, t, (batch, N)).astype(np.uint64)
+    cts = np.stack([hg.to_host(cb.bfv_encrypt(enc, pk, hg.to_device(m))) for m in msgs])
+    merged, _ = p.bfv_decrypt(padded(cts), stride, batch=batch)
+    assert np.array_equal(hg.to_host(merged).reshape(batch, N), msgs), "BFV merge of 17 strided shares"

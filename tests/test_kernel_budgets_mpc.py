@@ -10,8 +10,10 @@ import pytest
 from test_kernel_budgets import HIPCC, _usage
 
 MPC_KERNELS = ["k_kg_switchkey",            # widened: also the round-1 share of the relinearisation key
-               "k_kg_mpc_relin_round2", "k_kg_mpc_accumulate", "k_kg_mpc_decrypt_share", "k_kg_mpc_add_gaussian",
-               "k_kg_mpc_merge", "k_kg_mpc_bfv_merge",
+               "k_kg_mpc_relin_round2", "k_kg_mpc_accumulate", "k_kg_mpc_add_gaussian",
+               "k_kg_mpc_share",            # the decrypt share; with a second half, the refresh share
+               "k_kg_mpc_sum",              # the CKKS merge; with a share stride and offset, the refresh sums
+               "k_kg_mpc_bfv_round",        # the BFV merge; with a share stride, the refresh's
                "k_kg_bfv_decryption"]       # shares its rounding stage with the BFV merge
 
 

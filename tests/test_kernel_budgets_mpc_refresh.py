@@ -13,8 +13,8 @@ from test_kernel_budgets import HIPCC, _usage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-REFRESH_KERNELS = ["k_kg_mpc_refresh_noiseE", "k_kg_mpc_refresh_shareE", "k_kg_mpc_refresh_bfv_noiseE",
-                   "k_kg_mpc_refresh_sumE", "k_kg_mpc_refresh_finishE", "k_kg_mpc_refresh_bfv_roundE",
+REFRESH_KERNELS = ["k_kg_mpc_refresh_noiseE", "k_kg_mpc_shareE", "k_kg_mpc_refresh_bfv_noiseE",
+                   "k_kg_mpc_sumE", "k_kg_mpc_refresh_finishE", "k_kg_mpc_bfv_roundE",
                    # one instance per bound on the word count, as the decoder's compose
                    "k_kg_mpc_refresh_liftILi8EE", "k_kg_mpc_refresh_liftILi16EE", "k_kg_mpc_refresh_liftILi32EE",
                    "k_kg_mpc_refresh_liftILi64EE"]
