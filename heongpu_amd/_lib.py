@@ -22,6 +22,15 @@ c_int = ctypes.c_int
 c_size_t = ctypes.c_size_t
 voidp = ctypes.c_void_p
 
+
+
+class LinearFactor(ctypes.Structure):
+    """hegpu_linear_factor: the matrix arguments of hegpu_ckks_linear_transform for one factor of a sequence"""
+    _fields_ = [("diags", ctypes.c_void_p), ("n_diag", c_int), ("index", ctypes.POINTER(c_int)), ("n1", c_int), ("n2", c_int),
+                ("baby_keys", ctypes.POINTER(ctypes.c_void_p)), ("baby_elts", ctypes.POINTER(c_int)),
+                ("giant_keys", ctypes.POINTER(ctypes.c_void_p)), ("giant_elts", ctypes.POINTER(c_int))]
+
+
 # (name, restype, argtypes) -- must list EVERY symbol of include/hegpu.h
 SIGNATURES = [
     ("hegpu_last_error", ctypes.c_char_p, []),
@@ -92,6 +101,16 @@ SIGNATURES = [
     ("hegpu_ckks_linear_transform", c_int,
      [voidp, u64p, u64, u64p, u64, u64p, c_int, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(ctypes.c_void_p),
       ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_int), c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_encoding_transform_shape", c_int,
+     [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    ("hegpu_encoding_transform_fill", c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), voidp]),
+    ("hegpu_ckks_conj_split", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64p, u64, c_int, c_int, c_int, voidp]),
+    ("hegpu_ckks_conj_merge", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64, c_int, c_int, c_int, voidp]),
+    ("hegpu_ckks_encoding_transform_workspace_bytes", c_size_t, [voidp, ctypes.POINTER(LinearFactor), c_int, c_int, c_int]),
+    ("hegpu_ckks_coeff_to_slot", c_int,
+     [voidp, u64p, u64, u64p, u64p, u64, ctypes.POINTER(LinearFactor), c_int, u64p, c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_ckks_slot_to_coeff", c_int,
+     [voidp, u64p, u64, u64p, u64, u64p, u64, ctypes.POINTER(LinearFactor), c_int, c_int, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_multiply", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_relinearize_inplace", c_int, [voidp, u64p, u64, u64p, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_apply_galois", c_int,

@@ -377,6 +377,52 @@ class Context:
                                                      bk, be, gk, ge, depth, batch, _ptr(ws), ws.numel() * 8,
                                                      stream if stream is not None else _stream()))
 
+    def ckks_conj_split(self, x, xs, xc, xcs, out0, out1, so, depth, out_depth, batch=1, stream=None):
+        """hegpu_ckks_conj_split: out0 = x + xc, out1 = div_i(x - xc) on the Q - out_depth kept limbs"""
+        _check(self._lib.hegpu_ckks_conj_split(self._h, _ptr(x), xs, _ptr(xc), xcs, _ptr(out0), _ptr(out1), so, depth,
+                                               out_depth, batch, stream if stream is not None else _stream()))
+
+    def ckks_conj_merge(self, c0, s0, c1, s1, out, so, depth, out_depth, batch=1, stream=None):
+        """hegpu_ckks_conj_merge: out = c0 + mult_i(c1) on the Q - out_depth kept limbs"""
+        _check(self._lib.hegpu_ckks_conj_merge(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, depth, out_depth, batch,
+                                               stream if stream is not None else _stream()))
+
+    @staticmethod
+    def linear_factors(factors):
+        """the hegpu_linear_factor array of a sequence entry.  factors: one (diags, n_diag, index, baby_keys, baby_elts,
+        giant_keys, giant_elts) per matrix, the arguments of ckks_linear_transform.  Returns (array, keep-alive)."""
+        arr = (_lib.LinearFactor * len(factors))()
+        keep = []
+        for f, (diags, n_diag, index, baby_keys, baby_elts, giant_keys, giant_elts) in zip(arr, factors):
+            n1, n2 = len(baby_elts), len(giant_elts)
+            ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
+            bk = (ctypes.c_void_p * n1)(*[(_ptr(k) if k is not None else None) for k in baby_keys])
+            gk = (ctypes.c_void_p * n2)(*[(_ptr(k) if k is not None else None) for k in giant_keys])
+            be = (ctypes.c_int * n1)(*[int(g) for g in baby_elts])
+            ge = (ctypes.c_int * n2)(*[int(g) for g in giant_elts])
+            f.diags, f.n_diag, f.index, f.n1, f.n2 = _ptr(diags), n_diag, ix, n1, n2
+            f.baby_keys, f.baby_elts, f.giant_keys, f.giant_elts = bk, be, gk, ge
+            keep += [ix, bk, gk, be, ge, diags, baby_keys, giant_keys]
+        return arr, keep
+
+    def encoding_transform_workspace_bytes(self, factors, depth, batch):
+        arr, _keep = self.linear_factors(factors)
+        return int(self._lib.hegpu_ckks_encoding_transform_workspace_bytes(self._h, arr, len(factors), depth, batch))
+
+    def ckks_coeff_to_slot(self, ct, cs, out0, out1, so, factors, conj_key, depth, batch, ws, stream=None):
+        """hegpu_ckks_coeff_to_slot: factors as for linear_factors, their diagonals encoded at depth + position"""
+        arr, _keep = self.linear_factors(factors)
+        _check(self._lib.hegpu_ckks_coeff_to_slot(self._h, _ptr(ct), cs, _ptr(out0), _ptr(out1), so, arr, len(factors),
+                                                  _ptr(conj_key), depth, batch, _ptr(ws), ws.numel() * 8,
+                                                  stream if stream is not None else _stream()))
+
+    def ckks_slot_to_coeff(self, c0, s0, c1, s1, out, so, factors, depth, batch, ws, stream=None):
+        """hegpu_ckks_slot_to_coeff: factors as for linear_factors, their diagonals encoded at depth + 1 + position"""
+        arr, _keep = self.linear_factors(factors)
+        _check(self._lib.hegpu_ckks_slot_to_coeff(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, arr, len(factors),
+                                                  depth, batch, _ptr(ws), ws.numel() * 8,
+                                                  stream if stream is not None else _stream()))
+
     def bfv_multiply(self, ct1, s1, ct2, s2, out, so, batch, ws, stream=None):
         _check(self._lib.hegpu_bfv_multiply(self._h, _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws),
                                             ws.numel() * 8, stream if stream is not None else _stream()))
@@ -885,7 +931,7 @@ LinearTransformPlan = collections.namedtuple("LinearTransformPlan",
                                              "n1 n2 index baby_shifts giant_shifts pre_rotation")
 
 
-def linear_transform_plan(diag_indices, slots, n1=None):
+def linear_transform_plan(diag_indices, slots, n1=None, stride=1):
     """Baby-step/giant-step plan of y = M v for a matrix given by its diagonals diag_k[s] = M[s][(s + k) mod slots]
     (host only; the inputs of hegpu_ckks_linear_transform).  `n1` is the baby-step period: diagonal k = j * n1 + i is
     baby step i of giant step j; by default the power of two nearest the square root of the number of diagonals (the
@@ -897,24 +943,54 @@ def linear_transform_plan(diag_indices, slots, n1=None):
       pre_rotation   per sorted diagonal, the shift -j * period to rotate its slot vector by before encoding, so that
                      rot(j * period, diag' * rot(i, v)) = diag_k * rot(k, v)
     where a positive shift moves slot s + shift to slot s (rotate_rows; numpy.roll(x, -shift)).  A plan of more than
-    16 giant steps is refused: choose a larger period."""
+    16 giant steps is refused: choose a larger period.
+    `stride`: every diagonal index is a multiple of it (a group of FFT stages, encoding_transform_factors) and the plan
+    is made over k / stride: diagonal k = stride * (j * n1 + i), baby shifts stride * i, giant shifts stride * j * n1,
+    all modulo slots.  Without it such a matrix has the single baby step 0 and one giant step per diagonal."""
     ks = sorted({int(k) % slots for k in diag_indices})
     if not ks:
         raise ValueError("a linear transform needs at least one diagonal")
+    if stride < 1 or any(k % stride for k in ks):
+        raise ValueError("every diagonal index is a multiple of the stride")
     if n1 is None:
         root = len(ks) ** 0.5
         n1 = min((1, 2, 4, 8, 16), key=lambda p: (abs(p - root), -p))
     if not 1 <= n1 <= 16:
         raise ValueError("the baby-step period lies in [1, 16]")
-    baby = sorted({k % n1 for k in ks})
-    giant = sorted({k // n1 for k in ks})
+    qs = [k // stride for k in ks]
+    baby = sorted({q % n1 for q in qs})
+    giant = sorted({q // n1 for q in qs})
     if len(giant) > 16:
         raise ValueError(f"{len(giant)} giant steps, at most 16 fit one transform: choose a larger period")
     index = [[-1] * len(baby) for _ in giant]
-    for pos, k in enumerate(ks):
-        index[giant.index(k // n1)][baby.index(k % n1)] = pos
-    return LinearTransformPlan(len(baby), len(giant), index, baby, [j * n1 for j in giant],
-                               [-(k // n1) * n1 for k in ks])
+    for pos, q in enumerate(qs):
+        index[giant.index(q // n1)][baby.index(q % n1)] = pos
+    return LinearTransformPlan(len(baby), len(giant), index, [stride * i for i in baby], [stride * j * n1 for j in giant],
+                               [-stride * (q // n1) * n1 for q in qs])
+
+
+EncodingTransformPiece = collections.namedtuple("EncodingTransformPiece", "stride stages offsets diagonals")
+
+
+def encoding_transform_factors(n, inverse, pieces):
+    """The factors of the CKKS encoder's special FFT in diagonal form (host only; hegpu_encoding_transform_shape /
+    _fill): `pieces` groups of consecutive radix-2 stages in the order they are applied.  inverse=False: the SlotToCoeff
+    factors, their product is U B (U[j][k] = zeta^(5^j k), B the bit reversal); inverse=True: the CoeffToSlot factors,
+    their product is 1/2 B U^-1.  Per group: the stride (every offset is a multiple of it), the number of stages, the
+    signed diagonal offsets and a complex array [len(offsets)][n / 2] with diagonals[d][t] = M[t][(t + offsets[d]) mod
+    n / 2]."""
+    import numpy as np
+    lib = _lib.load()
+    strides, stages, counts = ((ctypes.c_int * pieces)() for _ in range(3))
+    _check(lib.hegpu_encoding_transform_shape(n, int(bool(inverse)), pieces, strides, stages, counts))
+    out = []
+    for p in range(pieces):
+        offsets = (ctypes.c_int * counts[p])()
+        values = np.empty((counts[p], n // 2), dtype=np.complex128)
+        _check(lib.hegpu_encoding_transform_fill(n, int(bool(inverse)), pieces, p, counts[p], offsets,
+                                                 values.ctypes.data))
+        out.append(EncodingTransformPiece(strides[p], stages[p], list(offsets), values))
+    return out
 
 
 def steps_to_galois_elt(steps, n, group_order):

@@ -2,6 +2,7 @@
 #include "../../include/hegpu.h"
 #include "../../include/hegpu_bench.h"
 #include "context.hpp"
+#include "encoding_transform.hpp"
 #include "host_params.hpp"
 #include "ops.hpp"
 #include <cmath>
@@ -18,6 +19,12 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+
+// The instrumented test build (tests/audit) compiles a fixed list of this directory's sources and must export every
+// entry; it gets the host-only factorisation through this file instead of an object of its own.
+#ifdef HEGPU_FP_AUDIT_HEADER
+#include "encoding_transform.cpp"
+#endif
 
 using namespace hegpu;
 
@@ -454,6 +461,53 @@ int hegpu_steps_to_galois_elt(int steps, int coeff_count, int group_order)
         return 0;
     });
     return elt;
+}
+
+// host only: the factors of the encoder's special FFT in diagonal form (encoding_transform.hpp)
+static int log2_exact(int v)
+{
+    int p = 0;
+    while ((1 << p) < v && p < 30) p++;
+    return (v > 0 && (1 << p) == v) ? p : -1;
+}
+
+int hegpu_encoding_transform_shape(int coeff_count, int inverse, int pieces, int* strides, int* stages, int* n_diags)
+{
+    return guarded([&]() -> int {
+        if (!strides || !stages || !n_diags) return fail(HEGPU_E_INVALID, "encoding_transform_shape: null argument");
+        const int n_power = log2_exact(coeff_count);
+        if (n_power < 0) return fail(HEGPU_E_INVALID, "encoding_transform_shape: the degree is a power of two");
+        if (pieces < 1) return fail(HEGPU_E_INVALID, "encoding_transform_shape: the piece count lies in [2, 5]");
+        for (int p = 0; p < pieces; p++) {
+            const host::EncodingTransformPiece g = host::encoding_transform_piece(n_power, inverse != 0, pieces, p);
+            strides[p] = g.stride;
+            stages[p] = g.stages;
+            n_diags[p] = (int) g.offsets.size();
+        }
+        return 0;
+    });
+}
+
+int hegpu_encoding_transform_fill(int coeff_count, int inverse, int pieces, int piece, int n_diag, int* offsets,
+                                  double* values)
+{
+    return guarded([&]() -> int {
+        if (!offsets || !values) return fail(HEGPU_E_INVALID, "encoding_transform_fill: null argument");
+        const int n_power = log2_exact(coeff_count);
+        if (n_power < 0) return fail(HEGPU_E_INVALID, "encoding_transform_fill: the degree is a power of two");
+        const host::EncodingTransformPiece g = host::encoding_transform_piece(n_power, inverse != 0, pieces, piece);
+        if (n_diag != (int) g.offsets.size())
+            return fail(HEGPU_E_INVALID, "encoding_transform_fill: n_diag is not what hegpu_encoding_transform_shape gives");
+        const size_t n = (size_t) coeff_count >> 1;
+        for (size_t d = 0; d < g.offsets.size(); d++) {
+            offsets[d] = g.offsets[d];
+            for (size_t t = 0; t < n; t++) {
+                values[2 * (d * n + t)] = g.diags[d][t].real();
+                values[2 * (d * n + t) + 1] = g.diags[d][t].imag();
+            }
+        }
+        return 0;
+    });
 }
 
 #define NEED_CTX(ctx)                                                                      \
@@ -928,6 +982,154 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                             (const u64* const*) giant_keys, giant_elts, depth, batch, (u64*) ws,
                                             (hipStream_t) stream),
                    "hegpu_ckks_linear_transform");
+}
+
+// ---- the real / imaginary boundary passes and the CoeffToSlot / SlotToCoeff sequences
+static int conj_pass_check(const hegpu_context* ctx, int depth, int out_depth, int batch, const char* who)
+{
+    if (batch < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": batch must be at least 1");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, std::string(who) + ": at most 32767 items per call");
+    if (depth < 0 || out_depth < depth || out_depth >= ctx->c.Q_size)
+        return fail(HEGPU_E_INVALID, std::string(who) + ": depth <= out_depth < Q");
+    return 0;
+}
+
+int hegpu_ckks_conj_split(hegpu_context* ctx, const uint64_t* x, uint64_t x_stride, const uint64_t* xc,
+                          uint64_t xc_stride, uint64_t* out0, uint64_t* out1, uint64_t out_stride, int depth,
+                          int out_depth, int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = conj_pass_check(ctx, depth, out_depth, batch, "conj_split")) return r;
+    if (!x || !xc || !out0 || !out1) return fail(HEGPU_E_INVALID, "conj_split: null argument");
+    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - out_depth) * ctx->c.n;
+    for (const uint64_t* in : {x, xc})
+        for (uint64_t* out : {out0, out1})
+            if (spans_overlap(in, in == x ? x_stride : xc_stride, in_words, out, out_stride, out_words, batch))
+                return fail(HEGPU_E_INVALID, "conj_split: an output must not overlap an input");
+    if (spans_overlap(out0, out_stride, out_words, out1, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, "conj_split: the two outputs must not overlap");
+    return hip_ret(rns_ckks_conj_split((const u64*) x, x_stride, (const u64*) xc, xc_stride, (u64*) out0, (u64*) out1,
+                                       out_stride, ctx->c.tab.psi_half, ctx->c.plan_qp.mods, ctx->c.n_power,
+                                       ctx->c.Q_size - depth, ctx->c.Q_size - out_depth, batch, (hipStream_t) stream),
+                   "hegpu_ckks_conj_split");
+}
+
+int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
+                          uint64_t c1_stride, uint64_t* out, uint64_t out_stride, int depth, int out_depth, int batch,
+                          hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = conj_pass_check(ctx, depth, out_depth, batch, "conj_merge")) return r;
+    if (!c0 || !c1 || !out) return fail(HEGPU_E_INVALID, "conj_merge: null argument");
+    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - out_depth) * ctx->c.n;
+    if (spans_overlap(c0, c0_stride, in_words, out, out_stride, out_words, batch) ||
+        spans_overlap(c1, c1_stride, in_words, out, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, "conj_merge: the output must not overlap an input");
+    return hip_ret(rns_ckks_conj_merge((const u64*) c0, c0_stride, (const u64*) c1, c1_stride, (u64*) out, out_stride,
+                                       ctx->c.tab.psi_half, ctx->c.plan_qp.mods, ctx->c.n_power, ctx->c.Q_size - depth,
+                                       ctx->c.Q_size - out_depth, batch, (hipStream_t) stream),
+                   "hegpu_ckks_conj_merge");
+}
+
+// the factor array of a sequence entry: every factor as hegpu_ckks_linear_transform checks its arguments
+static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f, int count, int depth, const char* who)
+{
+    if (!f || count < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": at least one factor");
+    if (depth < 0 || depth + count + 1 >= ctx->c.Q_size)
+        return fail(HEGPU_E_INVALID, std::string(who) + ": depth + factors + 1 must stay below Q (one level per factor, one "
+                                                        "at the real / imaginary boundary)");
+    for (int k = 0; k < count; k++) {
+        const hegpu_linear_factor& a = f[k];
+        if (a.n1 < 1 || a.n1 > 16 || a.n2 < 1 || a.n2 > 16)
+            return fail(HEGPU_E_INVALID, std::string(who) + ": n1 and n2 lie in [1, 16]");
+        if (!a.diags || !a.index || !a.baby_keys || !a.baby_elts || !a.giant_keys || !a.giant_elts || a.n_diag < 1)
+            return fail(HEGPU_E_INVALID, std::string(who) + ": null argument in a factor");
+        if (!diag_index_ok(a.index, a.n1, a.n2, a.n_diag))
+            return fail(HEGPU_E_INVALID, std::string(who) + ": index outside [-1, n_diag)");
+        for (int i = 0; i < a.n1 + a.n2; i++) {
+            const int e = i < a.n1 ? a.baby_elts[i] : a.giant_elts[i - a.n1];
+            if (e == 0) continue;
+            if (e < 0 || !(e & 1) || e >= 2 * (int) ctx->c.n)
+                return fail(HEGPU_E_INVALID, std::string(who) + ": Galois elements are odd and below 2N");
+            if (!(i < a.n1 ? a.baby_keys[i] : a.giant_keys[i - a.n1]))
+                return fail(HEGPU_E_INVALID, std::string(who) + ": Galois key not present!");
+        }
+    }
+    return 0;
+}
+
+static std::vector<LinearFactor> factors_of(const hegpu_linear_factor* f, int count)
+{
+    std::vector<LinearFactor> v((size_t) count);
+    for (int k = 0; k < count; k++)
+        v[(size_t) k] = LinearFactor{(const u64*) f[k].diags, f[k].n_diag, f[k].index, f[k].n1, f[k].n2,
+                                     (const u64* const*) f[k].baby_keys, f[k].baby_elts,
+                                     (const u64* const*) f[k].giant_keys, f[k].giant_elts};
+    return v;
+}
+
+size_t hegpu_ckks_encoding_transform_workspace_bytes(const hegpu_context* ctx, const hegpu_linear_factor* factors,
+                                                     int count, int depth, int batch)
+{
+    if (!ctx || !factors || batch <= 0 || count < 1 || depth < 0 || depth >= ctx->c.Q_size) return 0;
+    for (int k = 0; k < count; k++)
+        if (factors[k].n1 < 1 || factors[k].n1 > 16 || factors[k].n2 < 1 || factors[k].n2 > 16) return 0;
+    return ops_encoding_transform_workspace_elems(ctx->c, factors_of(factors, count).data(), count, depth, batch) *
+           sizeof(u64);
+}
+
+int hegpu_ckks_coeff_to_slot(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out0, uint64_t* out1,
+                             uint64_t so, const hegpu_linear_factor* factors, int count, const uint64_t* conj_key,
+                             int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = factors_check(ctx, factors, count, depth, "coeff_to_slot")) return r;
+    if (!ct || !out0 || !out1 || !conj_key) return fail(HEGPU_E_INVALID, "coeff_to_slot: null argument");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "coeff_to_slot: at most 32767 items per call");
+    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - depth - count - 1) * ctx->c.n;
+    if (spans_overlap(ct, cs, in_words, out0, so, out_words, batch) ||
+        spans_overlap(ct, cs, in_words, out1, so, out_words, batch) ||
+        spans_overlap(out0, so, out_words, out1, so, out_words, batch))
+        return fail(HEGPU_E_INVALID, "coeff_to_slot: the outputs must overlap neither ct nor each other");
+    if (!ws || ws_bytes < hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch))
+        return fail(HEGPU_E_INVALID, "workspace too small");
+    return guarded([&]() -> int {
+        return hip_ret(op_ckks_coeff_to_slot(ctx->c, (const u64*) ct, cs, (u64*) out0, (u64*) out1, so,
+                                             factors_of(factors, count).data(), count, (const u64*) conj_key, depth,
+                                             batch, (u64*) ws, (hipStream_t) stream),
+                       "hegpu_ckks_coeff_to_slot");
+    });
+}
+
+int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
+                             uint64_t c1_stride, uint64_t* out, uint64_t so, const hegpu_linear_factor* factors,
+                             int count, int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = factors_check(ctx, factors, count, depth, "slot_to_coeff")) return r;
+    if (!c0 || !c1 || !out) return fail(HEGPU_E_INVALID, "slot_to_coeff: null argument");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "slot_to_coeff: at most 32767 items per call");
+    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - depth - count) * ctx->c.n; // before the last rescale
+    if (batch > 1 && so < out_words) return fail(HEGPU_E_INVALID, "slot_to_coeff: out_stride too small");
+    if (spans_overlap(c0, c0_stride, in_words, out, so, out_words, batch) ||
+        spans_overlap(c1, c1_stride, in_words, out, so, out_words, batch))
+        return fail(HEGPU_E_INVALID, "slot_to_coeff: out must not overlap an input");
+    if (!ws || ws_bytes < hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch))
+        return fail(HEGPU_E_INVALID, "workspace too small");
+    return guarded([&]() -> int {
+        return hip_ret(op_ckks_slot_to_coeff(ctx->c, (const u64*) c0, c0_stride, (const u64*) c1, c1_stride, (u64*) out, so,
+                                             factors_of(factors, count).data(), count, depth, batch, (u64*) ws,
+                                             (hipStream_t) stream),
+                       "hegpu_ckks_slot_to_coeff");
+    });
 }
 
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t s1, const uint64_t* ct2, uint64_t s2,

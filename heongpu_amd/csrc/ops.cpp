@@ -880,6 +880,79 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
     return rns_ckks_sum_terms(terms, strides, n2, out, so, mods, c.n_power, l, batch, st);
 }
 
+// ------------------------------------------------------------------ CoeffToSlot / SlotToCoeff
+// Workspace, per batch: T0 and T1, one ciphertext of the start depth each (the chain alternates between them: a linear
+// transform may not write over its input), then the largest workspace any step needs (the linear transforms'; it holds
+// the hoisted-rotation workspace, which is enough for apply_galois and larger than the rescale's).
+size_t ops_encoding_transform_workspace_elems(const Context& c, const LinearFactor* f, int count, int depth, int batch)
+{
+    size_t step = ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch);
+    for (int k = 0; k < count; k++) {
+        const size_t w = ops_linear_transform_workspace_elems(c, f[k].n1, f[k].n2, depth, batch);
+        if (w > step) step = w;
+    }
+    return (u64) 2 * 2 * (c.Q_size - depth) * c.n * (u64) batch + step;
+}
+
+// `count` x (linear transform, rescale) from cur at depth d0, alternating between the two buffers; the last product goes
+// to `last` (stride last_stride) if given.  Returns where the result is.
+static hipError_t encoding_transform_chain(const Context& c, const u64*& cur, u64& cur_stride, u64* T0, u64* T1,
+                                           u64 t_stride, u64* last, u64 last_stride, const LinearFactor* f, int count,
+                                           int d0, int batch, u64* step_ws, hipStream_t st)
+{
+    for (int k = 0; k < count; k++) {
+        u64* dst = (cur == T0) ? T1 : T0;
+        u64 ds = t_stride;
+        if (last && k == count - 1) {
+            dst = last;
+            ds = last_stride;
+        }
+        TRY(op_ckks_linear_transform(c, cur, cur_stride, dst, ds, f[k].diags, f[k].n_diag, f[k].index, f[k].n1, f[k].n2,
+                                     f[k].baby_keys, f[k].baby_elts, f[k].giant_keys, f[k].giant_elts, d0 + k, batch,
+                                     step_ws, st));
+        TRY(op_ckks_rescale(c, dst, ds, d0 + k, batch, step_ws, st));
+        cur = dst;
+        cur_stride = ds;
+    }
+    return hipSuccess;
+}
+
+hipError_t op_ckks_coeff_to_slot(const Context& c, const u64* ct, u64 cs, u64* out0, u64* out1, u64 so,
+                                 const LinearFactor* f, int count, const u64* conj_key, int depth, int batch, u64* ws,
+                                 hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (count < 1 || depth + count + 1 >= c.Q_size) return hipErrorInvalidValue;
+    const u64 t_stride = (u64) 2 * (c.Q_size - depth) * c.n;
+    u64* T0 = ws;
+    u64* T1 = T0 + t_stride * batch;
+    u64* step_ws = T1 + t_stride * batch;
+    const u64* cur = ct;
+    u64 cur_stride = cs;
+    TRY(encoding_transform_chain(c, cur, cur_stride, T0, T1, t_stride, nullptr, 0, f, count, depth, batch, step_ws, st));
+    const int d = depth + count;
+    u64* conj = (cur == T0) ? T1 : T0;
+    TRY(op_ckks_apply_galois(c, cur, cur_stride, conj, t_stride, conj_key, 2 * (int) c.n - 1, d, batch, step_ws, st));
+    return rns_ckks_conj_split(cur, cur_stride, conj, t_stride, out0, out1, so, c.tab.psi_half, c.plan_qp.mods, c.n_power,
+                               c.Q_size - d, c.Q_size - d - 1, batch, st);
+}
+
+hipError_t op_ckks_slot_to_coeff(const Context& c, const u64* c0, u64 s0, const u64* c1, u64 s1, u64* out, u64 so,
+                                 const LinearFactor* f, int count, int depth, int batch, u64* ws, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (count < 1 || depth + count + 1 >= c.Q_size) return hipErrorInvalidValue;
+    const u64 t_stride = (u64) 2 * (c.Q_size - depth) * c.n;
+    u64* T0 = ws;
+    u64* T1 = T0 + t_stride * batch;
+    u64* step_ws = T1 + t_stride * batch;
+    TRY(rns_ckks_conj_merge(c0, s0, c1, s1, T0, t_stride, c.tab.psi_half, c.plan_qp.mods, c.n_power, c.Q_size - depth,
+                            c.Q_size - depth - 1, batch, st));
+    const u64* cur = T0;
+    u64 cur_stride = t_stride;
+    return encoding_transform_chain(c, cur, cur_stride, T0, T1, t_stride, out, so, f, count, depth + 1, batch, step_ws, st);
+}
+
 // ------------------------------------------------------------------ keygen / encrypt / decrypt
 // The plain transforms of this half: `polys` contiguous polynomials, polynomial i under modulus i % mod_count of table
 // set `tables` (0: Q', 2: the plain modulus)

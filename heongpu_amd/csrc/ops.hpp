@@ -59,6 +59,32 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
                                     const int* baby_elts, const u64* const* giant_keys, const int* giant_elts, int depth,
                                     int batch, u64* ws, hipStream_t st);
 
+// ---- CoeffToSlot / SlotToCoeff (reference coeff_to_slot / slot_to_coeff, ckks/operator.cu:3566-3663,
+// :3809-3891): a chain of op_ckks_linear_transform + op_ckks_rescale over the factors of the encoder's special FFT, and
+// one pass at the real / imaginary boundary.  One factor = the arguments of op_ckks_linear_transform for one matrix, its
+// diagonals encoded at the depth the chain has reached (depth + position, SlotToCoeff: + 1).
+struct LinearFactor {
+    const u64* diags;
+    int n_diag;
+    const int* index;
+    int n1, n2;
+    const u64* const* baby_keys;
+    const int* baby_elts;
+    const u64* const* giant_keys;
+    const int* giant_elts;
+};
+// two ciphertexts of the start depth per item + the largest linear-transform workspace of the chain
+size_t ops_encoding_transform_workspace_elems(const Context& c, const LinearFactor* f, int count, int depth, int batch);
+// ct [2][l][N] -> count x (linear_transform, rescale) -> apply_galois(2N - 1) -> rns_ckks_conj_split into out0 / out1
+// [2][l - count - 1][N]
+hipError_t op_ckks_coeff_to_slot(const Context& c, const u64* ct, u64 cs, u64* out0, u64* out1, u64 so,
+                                 const LinearFactor* f, int count, const u64* conj_key, int depth, int batch, u64* ws,
+                                 hipStream_t st);
+// c0, c1 [2][l][N] -> rns_ckks_conj_merge to depth + 1 -> count x (linear_transform, rescale); the last product is
+// written to out and rescaled there: out holds [2][l - count][N] on the way, [2][l - count - 1][N] at the end
+hipError_t op_ckks_slot_to_coeff(const Context& c, const u64* c0, u64 s0, const u64* c1, u64 s1, u64* out, u64 so,
+                                 const LinearFactor* f, int count, int depth, int batch, u64* ws, hipStream_t st);
+
 // ---- key generation / encryption / decryption, key-switch method I
 // The generator state: every sampling call consumes one stream id of the DRBG (drbg.hpp).
 struct Rng {

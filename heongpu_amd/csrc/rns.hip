@@ -1367,4 +1367,77 @@ hipError_t rns_ckks_sum_terms(const u64* const* terms, const u64* strides, int c
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- real / imaginary boundary of the encoding transforms
+// CoeffToSlot ends with out0 = x + conj x, out1 = -i (x - conj x); SlotToCoeff starts with out = c0 + i c1.  As single
+// entries that is addition + subtraction + mult_i: 4 + 4 + 6 ciphertext passes for the split, 3 + 3 for the merge.
+// Here the thread that owns two adjacent coefficients of a limb reads each input once and writes each output once
+// (4 in + 4 out limb-vectors per kept limb for the split, 4 + 2 for the merge).  i is +-psi^(N/2) on the two halves of
+// the NTT positions (k_kg_ckks_mult_i); sums, differences and the one Barrett product are the ones the single kernels
+// compute, so the residues are the same.  Inputs have in_limbs limbs per part, outputs the first out_limbs of them (the
+// level the caller drops is neither read nor written).  blockIdx.z = 2 item + part.
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_conj_split(const u64* __restrict__ x, u64 x_stride,
+                                                                 const u64* __restrict__ xc, u64 xc_stride,
+                                                                 u64* __restrict__ out0, u64* __restrict__ out1,
+                                                                 u64 out_stride, const u64* __restrict__ psi_half,
+                                                                 const Mod* __restrict__ mods, int n_power, int in_limbs,
+                                                                 int out_limbs)
+{
+    const Mod m = mods[blockIdx.y];
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << n_power;
+    const u64 in = c + limb + (((u64) in_limbs * z) << n_power), out = c + limb + (((u64) out_limbs * z) << n_power);
+    const u64 psi = psi_half[blockIdx.y];
+    const u64 w = (c < (1ull << (n_power - 1))) ? sub_mod(0, psi, m.q) : psi; // 1 / i = -i
+    const ulonglong2 a = ld2(x + x_stride * item + in), b = ld2(xc + xc_stride * item + in);
+    ulonglong2 s, d;
+    s.x = add_mod(a.x, b.x, m.q);
+    s.y = add_mod(a.y, b.y, m.q);
+    d.x = mul_barrett(sub_mod(a.x, b.x, m.q), w, m);
+    d.y = mul_barrett(sub_mod(a.y, b.y, m.q), w, m);
+    st2(out0 + out_stride * item + out, s);
+    st2(out1 + out_stride * item + out, d);
+}
+
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_conj_merge(const u64* __restrict__ c0, u64 c0_stride,
+                                                                 const u64* __restrict__ c1, u64 c1_stride,
+                                                                 u64* __restrict__ out, u64 out_stride,
+                                                                 const u64* __restrict__ psi_half,
+                                                                 const Mod* __restrict__ mods, int n_power, int in_limbs,
+                                                                 int out_limbs)
+{
+    const Mod m = mods[blockIdx.y];
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << n_power;
+    const u64 in = c + limb + (((u64) in_limbs * z) << n_power), o = c + limb + (((u64) out_limbs * z) << n_power);
+    const u64 psi = psi_half[blockIdx.y];
+    const u64 w = (c < (1ull << (n_power - 1))) ? psi : sub_mod(0, psi, m.q);
+    const ulonglong2 a = ld2(c0 + c0_stride * item + in), b = ld2(c1 + c1_stride * item + in);
+    ulonglong2 r;
+    r.x = add_mod(a.x, mul_barrett(b.x, w, m), m.q);
+    r.y = add_mod(a.y, mul_barrett(b.y, w, m), m.q);
+    st2(out + out_stride * item + o, r);
+}
+
+hipError_t rns_ckks_conj_split(const u64* x, u64 x_stride, const u64* xc, u64 xc_stride, u64* out0, u64* out1,
+                               u64 out_stride, const u64* psi_half, const Mod* mods, int n_power, int in_limbs,
+                               int out_limbs, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (out_limbs < 1 || out_limbs > in_limbs || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ckks_conj_split, grid3(n_power, out_limbs, 2 * batch), dim3(RNS_THREADS), 0, st, x, x_stride, xc,
+                       xc_stride, out0, out1, out_stride, psi_half, mods, n_power, in_limbs, out_limbs);
+    return hipGetLastError();
+}
+
+hipError_t rns_ckks_conj_merge(const u64* c0, u64 c0_stride, const u64* c1, u64 c1_stride, u64* out, u64 out_stride,
+                               const u64* psi_half, const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch,
+                               hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (out_limbs < 1 || out_limbs > in_limbs || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ckks_conj_merge, grid3(n_power, out_limbs, 2 * batch), dim3(RNS_THREADS), 0, st, c0, c0_stride, c1,
+                       c1_stride, out, out_stride, psi_half, mods, n_power, in_limbs, out_limbs);
+    return hipGetLastError();
+}
+
 } // namespace hegpu

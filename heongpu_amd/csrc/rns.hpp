@@ -113,6 +113,18 @@ hipError_t rns_ckks_diag_mac(const u64* rot, u64 rot_stride, int n1, const u64* 
 hipError_t rns_ckks_sum_terms(const u64* const* terms, const u64* strides, int count, u64* out, u64 out_stride,
                               const Mod* mods, int n_power, int limbs, int batch, hipStream_t st);
 
+// The real / imaginary boundary of CoeffToSlot / SlotToCoeff, one read of each input and one write of each output.
+// x, xc, c0, c1: [2][in_limbs][N] per item; outputs [2][out_limbs][N], out_limbs <= in_limbs (the first out_limbs limbs of
+// each part are kept).  psi_half: DEVICE, psi^(N/2) per modulus (Context::tab).  Outputs may overlap no input.
+//   split: out0 = x + xc, out1 = div_i(x - xc)        (addition.cu:10-47 + cipher_div_by_i_kernel, multiplication.cu:469-495)
+//   merge: out = c0 + mult_i(c1)                      (cipher_mult_by_i_kernel :441-467 + addition)
+hipError_t rns_ckks_conj_split(const u64* x, u64 x_stride, const u64* xc, u64 xc_stride, u64* out0, u64* out1,
+                               u64 out_stride, const u64* psi_half, const Mod* mods, int n_power, int in_limbs,
+                               int out_limbs, int batch, hipStream_t st);
+hipError_t rns_ckks_conj_merge(const u64* c0, u64 c0_stride, const u64* c1, u64 c1_stride, u64* out, u64 out_stride,
+                               const u64* psi_half, const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch,
+                               hipStream_t st);
+
 struct BehzDev {
     const Mod* ibase;       // q_0..q_{Q-1}
     const Mod* obase;       // Bsk

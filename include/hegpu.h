@@ -339,6 +339,70 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                 const uint64_t* const* baby_keys, const int* baby_elts,
                                 const uint64_t* const* giant_keys, const int* giant_elts, int depth, int batch, void* ws,
                                 size_t ws_bytes, hegpu_stream stream);
+/* ---- CoeffToSlot / SlotToCoeff (HEArithmeticOperator<CKKS>::coeff_to_slot / slot_to_coeff, host/ckks/operator.cu:
+ * 3566-3663 and 3809-3891; the context of generate_encoding_transform_context, :6686-6800).
+ *
+ * With n = N/2, L = log2 n and zeta = exp(2 pi i / 2N), the slot vector of a polynomial with real coefficients a is
+ * z = U w, w_k = a_k + i a_{k+n}, U[j][k] = zeta^(5^j k) = F_L ... F_1 B: the radix-2 stages of the encoder's special
+ * FFT and the bit reversal B on L bits.  Neither transform applies B: CoeffToSlot leaves slot j holding coefficient
+ * bitrev_L(j) (out0) and n + bitrev_L(j) (out1), SlotToCoeff expects them so.
+ *
+ * hegpu_encoding_transform_shape / _fill (HOST ONLY, no device needed): the L stages in `pieces` in [2, 5] groups of
+ * floor(L / pieces) or ceil(L / pieces) consecutive stages, the larger groups first, in the order they are applied.
+ * inverse = 0 (SlotToCoeff): group 0 holds stage 1.  inverse = 1 (CoeffToSlot): group 0 holds stage L, every stage is
+ * inverted, and each group carries the factor 2^(-1/pieces), so that all groups together are 1/2 B U^-1.
+ * _shape writes, per group: the stride 2^s (every diagonal offset of the group is a multiple of it), the number of
+ * stages g and the number of non-zero diagonals (at most 2^(g+1) - 1).  _fill writes one group: its signed offsets in
+ * (-n/2, n/2], ascending, and values [n_diag][n] (re, im) pairs with diag_k[t] = M[t][(t + k) mod n].
+ * HEGPU_E_INVALID: a degree that is no power of two, pieces outside [2, 5] or above L, a wrong piece or n_diag. */
+int hegpu_encoding_transform_shape(int coeff_count, int inverse, int pieces, int* strides, int* stages, int* n_diags);
+int hegpu_encoding_transform_fill(int coeff_count, int inverse, int pieces, int piece, int n_diag, int* offsets,
+                                  double* values);
+/* The two passes at the real / imaginary boundary, each one read of every input and one write of every output, both
+ * parts, the Q - out_depth limbs that are kept (out_depth >= depth: the dropped limbs are neither read nor written):
+ *   conj_split: out0 = x + xc, out1 = div_i(x - xc)     (xc = the conjugate of x: out0 = 2 Re, out1 = 2 Im)
+ *   conj_merge: out = c0 + mult_i(c1)
+ * Inputs [2][Q - depth][N], outputs [2][Q - out_depth][N] per item.  Bit-identical to hegpu_addition (op 0 / 1) and
+ * hegpu_ckks_mult_i (divide = 1 / 0) on the kept limbs.  HEGPU_E_INVALID, outputs untouched: an output overlapping an
+ * input (or the other output), out_depth < depth or >= Q, batch < 1. */
+int hegpu_ckks_conj_split(hegpu_context* ctx, const uint64_t* x, uint64_t x_stride, const uint64_t* xc,
+                          uint64_t xc_stride, uint64_t* out0, uint64_t* out1, uint64_t out_stride, int depth,
+                          int out_depth, int batch, hegpu_stream stream);
+int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
+                          uint64_t c1_stride, uint64_t* out, uint64_t out_stride, int depth, int out_depth, int batch,
+                          hegpu_stream stream);
+/* One factor of a sequence: exactly the matrix arguments of hegpu_ckks_linear_transform (all arrays HOST, keys and
+ * diagonals DEVICE).  The diagonals of factor k are encoded at the depth the chain has reached: depth + k for
+ * CoeffToSlot, depth + 1 + k for SlotToCoeff. */
+typedef struct hegpu_linear_factor {
+    const uint64_t* diags;
+    int n_diag;
+    const int* index;
+    int n1, n2;
+    const uint64_t* const* baby_keys;
+    const int* baby_elts;
+    const uint64_t* const* giant_keys;
+    const int* giant_elts;
+} hegpu_linear_factor;
+/* coeff_to_slot: per factor hegpu_ckks_linear_transform + hegpu_ckks_rescale_inplace (depth -> depth + count), then
+ * hegpu_ckks_apply_galois with the element 2N - 1 and conj_key, then hegpu_ckks_conj_split to depth + count + 1 -- the
+ * depth at which the reference's outputs leave (it spends that level on a product with scale / 2; here the half is in
+ * the matrices).  out0, out1: [2][Q - depth - count - 1][N] per item, out_stride apart.
+ * slot_to_coeff: hegpu_ckks_conj_merge from depth to depth + 1 (the reference spends a level on its product with i),
+ * then count x (linear transform, rescale).  The last product is written to out and rescaled there: out needs room for
+ * [2][Q - depth - count][N] per item and holds [2][Q - depth - count - 1][N] on return.
+ * Both are bit-identical to the same chain of single entries.  HEGPU_E_INVALID, outputs untouched: count < 1,
+ * depth + count + 1 >= Q, an output overlapping an input, what hegpu_ckks_linear_transform refuses in a factor, a
+ * workspace below hegpu_ckks_encoding_transform_workspace_bytes (0 for arguments it cannot size). */
+size_t hegpu_ckks_encoding_transform_workspace_bytes(const hegpu_context* ctx, const hegpu_linear_factor* factors,
+                                                     int count, int depth, int batch);
+int hegpu_ckks_coeff_to_slot(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out0, uint64_t* out1,
+                             uint64_t out_stride, const hegpu_linear_factor* factors, int count,
+                             const uint64_t* conj_key, int depth, int batch, void* ws, size_t ws_bytes,
+                             hegpu_stream stream);
+int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
+                             uint64_t c1_stride, uint64_t* out, uint64_t out_stride, const hegpu_linear_factor* factors,
+                             int count, int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
 /* multiply_bfv (src/lib/host/bfv/operator.cu:336-430): coefficient domain,
  * ct [2][Q][N] x [2][Q][N] -> out [3][Q][N] */
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_stride, const uint64_t* ct2,

@@ -2169,7 +2169,9 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
 // reference's multiply_matrix (ckks/operator.cu:2803-2895) is private to its bootstrapping and takes pre-baked index
 // tensors.  The plan (the same as heongpu_amd.api.linear_transform_plan): with the baby-step period n1, diagonal
 // k = j n1 + i is baby step i of giant step j; only the i and j that occur are kept; the slot vector of diagonal k is
-// rotated by -j n1 before it is encoded, so that rot(j n1, diag' * rot(i, v)) = diag_k * rot(k, v).
+// rotated by -j n1 before it is encoded, so that rot(j n1, diag' * rot(i, v)) = diag_k * rot(k, v).  With a stride (a
+// group of FFT stages: every diagonal index is a multiple of it) the plan is made over k / stride: k = stride (j n1 + i),
+// baby shifts stride i, giant shifts stride j n1.
 template <Scheme S> class LinearTransform;
 template <> class LinearTransform<Scheme::CKKS> {
     static constexpr Scheme S = Scheme::CKKS;
@@ -2178,16 +2180,16 @@ template <> class LinearTransform<Scheme::CKKS> {
     // n1: the baby-step period; 0 = the power of two nearest the square root of the number of diagonals (the larger one
     // on a tie), at most 16.  Diagonals shorter than N/2 are padded with zeros.
     LinearTransform(HEContext<S> context, const std::map<int, std::vector<Complex64>>& diagonals, HEEncoder<S>& encoder,
-                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions())
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1)
         : context_(std::move(context))
     {
-        build(diagonals, encoder, scale, depth, n1, o);
+        build(diagonals, encoder, scale, depth, n1, o, stride);
     }
     LinearTransform(HEContext<S> context, const std::map<int, std::vector<double>>& diagonals, HEEncoder<S>& encoder,
-                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions())
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1)
         : context_(std::move(context))
     {
-        build(diagonals, encoder, scale, depth, n1, o);
+        build(diagonals, encoder, scale, depth, n1, o, stride);
     }
     // the rotations linear_transform needs a Galois key of their own for (no key chains there)
     std::vector<int> required_shifts() const
@@ -2209,10 +2211,11 @@ template <> class LinearTransform<Scheme::CKKS> {
 
   private:
     template <typename T> void build(const std::map<int, std::vector<T>>& diagonals, HEEncoder<S>& encoder, double scale,
-                                     int depth, int n1, const ExecutionOptions& o)
+                                     int depth, int n1, const ExecutionOptions& o, int stride)
     {
         if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
         if (depth < 0 || depth >= context_->Q_size) throw std::invalid_argument("Invalid depth!");
+        if (stride < 1) throw std::invalid_argument("The stride is at least 1!");
         const int slots = (int) (context_->n >> 1);
         std::map<int, const std::vector<T>*> by_k; // diagonal index mod slots, ascending
         for (const auto& d : diagonals) {
@@ -2221,6 +2224,8 @@ template <> class LinearTransform<Scheme::CKKS> {
                 throw std::invalid_argument("Two diagonals with the same index modulo the slot count!");
         }
         if (by_k.empty()) throw std::invalid_argument("A linear transform needs at least one diagonal!");
+        for (const auto& d : by_k)
+            if (d.first % stride) throw std::invalid_argument("Every diagonal index is a multiple of the stride!");
         if (n1 == 0) {
             const double root = std::sqrt((double) by_k.size());
             n1 = 1;
@@ -2230,8 +2235,9 @@ template <> class LinearTransform<Scheme::CKKS> {
         if (n1 < 1 || n1 > 16) throw std::invalid_argument("The baby-step period lies in [1, 16]!");
         std::vector<int> babies, giants;
         for (const auto& d : by_k) {
-            if (std::find(babies.begin(), babies.end(), d.first % n1) == babies.end()) babies.push_back(d.first % n1);
-            if (std::find(giants.begin(), giants.end(), d.first / n1) == giants.end()) giants.push_back(d.first / n1);
+            const int q = d.first / stride;
+            if (std::find(babies.begin(), babies.end(), q % n1) == babies.end()) babies.push_back(q % n1);
+            if (std::find(giants.begin(), giants.end(), q / n1) == giants.end()) giants.push_back(q / n1);
         }
         std::sort(babies.begin(), babies.end());
         std::sort(giants.begin(), giants.end());
@@ -2245,12 +2251,13 @@ template <> class LinearTransform<Scheme::CKKS> {
         diags_ = DeviceVector<Data64>((size_t) n_diag_ * l * n, o.stream_);
         int pos = 0;
         for (const auto& d : by_k) {
-            const int i = d.first % n1, j = d.first / n1;
+            const int i = (d.first / stride) % n1, j = (d.first / stride) / n1;
             const size_t row = std::find(giants.begin(), giants.end(), j) - giants.begin();
             const size_t col = std::find(babies.begin(), babies.end(), i) - babies.begin();
             index_[row * babies.size() + col] = pos;
-            std::vector<T> rotated((size_t) slots, T(0)); // rotated by -j n1: slot t takes slot t - j n1
-            for (size_t t = 0; t < d.second->size(); t++) rotated[(t + (size_t) j * n1) % slots] = (*d.second)[t];
+            std::vector<T> rotated((size_t) slots, T(0)); // rotated by -stride j n1: slot t takes slot t - stride j n1
+            for (size_t t = 0; t < d.second->size(); t++)
+                rotated[(t + (size_t) stride * j * n1) % slots] = (*d.second)[t];
             Plaintext<S> plain(context_);
             encoder.encode(plain, rotated, scale, o);
             detail::hip(hipMemcpyAsync(diags_.data() + (size_t) pos * l * n, plain.data(), l * n * sizeof(Data64),
@@ -2258,15 +2265,51 @@ template <> class LinearTransform<Scheme::CKKS> {
             detail::hip(hipStreamSynchronize(o.stream_)); // `plain` is released at the end of this iteration
             pos++;
         }
-        baby_shifts_ = babies;
+        baby_shifts_.clear();
         giant_shifts_.clear();
-        for (int j : giants) giant_shifts_.push_back(j * n1);
+        for (int i : babies) baby_shifts_.push_back(stride * i);
+        for (int j : giants) giant_shifts_.push_back(stride * j * n1);
     }
     HEContext<S> context_;
     DeviceVector<Data64> diags_;
     std::vector<int> index_, baby_shifts_, giant_shifts_;
     double scale_ = 0;
     int depth_ = 0, n_diag_ = 0;
+};
+
+// ------------------------------------------------------------------ CoeffToSlot / SlotToCoeff context
+// host/ckks/operator.cuh:29-82.  The reference keeps pre-baked index tensors of its Vandermonde generator; here the
+// factors are LinearTransform objects over the groups of hegpu_encoding_transform_shape / _fill.
+struct CKKSEncodingTransformConfig {
+    int CtoS_piece_;       // [2, 5]
+    int StoC_piece_;       // [2, 5]
+    int CtoS_start_level_; // ciphertext level where CoeffToSlot starts
+    int StoC_start_level_; // ciphertext level where SlotToCoeff starts
+    bool less_key_mode_;
+    CKKSEncodingTransformConfig(int CtoS_piece = 3, int StoC_piece = 3, bool less_key_mode = true)
+        : CtoS_piece_(CtoS_piece), StoC_piece_(StoC_piece), CtoS_start_level_(-1), StoC_start_level_(-1),
+          less_key_mode_(less_key_mode)
+    {
+    }
+    CKKSEncodingTransformConfig(int CtoS_piece, int StoC_piece, int CtoS_start_level, int StoC_start_level,
+                                bool less_key_mode = true)
+        : CtoS_piece_(CtoS_piece), StoC_piece_(StoC_piece), CtoS_start_level_(CtoS_start_level),
+          StoC_start_level_(StoC_start_level), less_key_mode_(less_key_mode)
+    {
+    }
+};
+struct CKKSEncodingTransformContext {
+    bool generated_ = false;
+    bool less_key_mode_ = false;
+    double scale_boot_ = 0.0;
+    int CtoS_piece_ = 0;
+    int StoC_piece_ = 0;
+    int CtoS_level_ = 0;
+    int StoC_level_ = 0;
+    std::vector<int> key_indexs_; // every rotation of every factor: Galoiskey(context, key_indexs_) is enough
+    // the factors in the order they are applied; factor k of CtoS is encoded at CtoS_level_ + k, of StoC at
+    // StoC_level_ + 1 + k
+    std::vector<std::shared_ptr<LinearTransform<Scheme::CKKS>>> CtoS_factors_, StoC_factors_;
 };
 
 // ------------------------------------------------------------------ operator
@@ -2526,7 +2569,184 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         out.rescale_required_ = true;
     }
 
+    // host/ckks/operator.cu:6686-6800.  The factors are the groups of the encoder's special FFT
+    // (hegpu_encoding_transform_fill), every diagonal encoded at `scale`; the half of CoeffToSlot's real / imaginary
+    // split is in its matrices.  The key-chain variant (less_key_mode) is not provided: std::invalid_argument.
+    void generate_encoding_transform_context(CKKSEncodingTransformContext& tc, const double scale,
+                                             const CKKSEncodingTransformConfig& config = CKKSEncodingTransformConfig())
+    {
+        static_assert(S == Scheme::CKKS, "encoding transforms are a CKKS operation");
+        if (scale == 0.0) throw std::invalid_argument("Scale can not be zero for CKKS encoding transform context.");
+        if (config.CtoS_piece_ < 2 || config.CtoS_piece_ > 5) throw std::out_of_range("CtoS_piece must be in range [2, 5]");
+        if (config.StoC_piece_ < 2 || config.StoC_piece_ > 5) throw std::out_of_range("StoC_piece must be in range [2, 5]");
+        if (config.less_key_mode_)
+            throw std::invalid_argument("less_key_mode is not supported: every rotation takes a Galois key of its own");
+        const int Q = context_->Q_size;
+        const int ctos = config.CtoS_start_level_ < 0 ? 0 : config.CtoS_start_level_;
+        const int stoc = config.StoC_start_level_ < 0 ? ctos + config.CtoS_piece_ + 1 : config.StoC_start_level_;
+        if (ctos < 0 || ctos >= Q) throw std::out_of_range("CtoS_start_level must be in range [0, Q_size - 1]");
+        if (stoc < 0 || stoc >= Q) throw std::out_of_range("StoC_start_level must be in range [0, Q_size - 1]");
+        if (stoc + 1 >= Q)
+            throw std::out_of_range("StoC_start_level is too deep: slot_to_coeff needs one extra level internally before "
+                                    "matrix multiplication.");
+        // every factor rescales and one modulus must remain (CoeffToSlot: one more level for the split), which is what
+        // hegpu_ckks_coeff_to_slot / _slot_to_coeff require
+        if (Q - ctos < config.CtoS_piece_ || ctos + config.CtoS_piece_ + 1 >= Q)
+            throw std::out_of_range("CtoS_start_level is too deep for selected CtoS_piece.");
+        if (Q - (stoc + 1) < config.StoC_piece_ || stoc + 1 + config.StoC_piece_ >= Q)
+            throw std::out_of_range("StoC_start_level is too deep for selected StoC_piece.");
+        tc = CKKSEncodingTransformContext();
+        tc.scale_boot_ = scale;
+        tc.CtoS_piece_ = config.CtoS_piece_;
+        tc.StoC_piece_ = config.StoC_piece_;
+        tc.less_key_mode_ = false;
+        tc.CtoS_level_ = ctos;
+        tc.StoC_level_ = stoc;
+        HEEncoder<S> encoder(context_);
+        const int n = (int) context_->n, slots = n >> 1;
+        for (int inverse = 1; inverse >= 0; inverse--) {
+            const int pieces = inverse ? tc.CtoS_piece_ : tc.StoC_piece_;
+            const int start = inverse ? ctos : stoc + 1;
+            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
+            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
+            for (int p = 0; p < pieces; p++) {
+                std::vector<int> offsets(counts[p]);
+                std::vector<double> values((size_t) 2 * counts[p] * slots);
+                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
+                std::map<int, std::vector<Complex64>> diag;
+                for (int d = 0; d < counts[p]; d++) {
+                    std::vector<Complex64> v((size_t) slots);
+                    for (int t = 0; t < slots; t++)
+                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
+                    diag[offsets[d]] = std::move(v);
+                }
+                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder, scale, start + p, 0,
+                                                               ExecutionOptions(), strides[p]);
+                for (int sh : lt->required_shifts())
+                    if (std::find(tc.key_indexs_.begin(), tc.key_indexs_.end(), sh) == tc.key_indexs_.end())
+                        tc.key_indexs_.push_back(sh);
+                (inverse ? tc.CtoS_factors_ : tc.StoC_factors_).push_back(std::move(lt));
+            }
+        }
+        tc.generated_ = true;
+    }
+
+    // host/ckks/operator.cu:3566-3663 (hegpu_ckks_coeff_to_slot): slot j of result 0 holds coefficient bitrev(j), of
+    // result 1 coefficient N/2 + bitrev(j); both leave at CtoS_level_ + CtoS_piece_ + 1.
+    std::vector<Ciphertext<S>> coeff_to_slot(Ciphertext<S>& cipher, Galoiskey<S>& galois_key,
+                                             CKKSEncodingTransformContext& tc,
+                                             const ExecutionOptions& o = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "encoding transforms are a CKKS operation");
+        detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
+        if (!tc.generated_) throw std::invalid_argument("Encoding transform context is not generated!");
+        if (cipher.encoding_ != encoding::COEFFICIENT)
+            throw std::invalid_argument("coeff_to_slot expects coefficient-encoded ciphertext.");
+        if (cipher.depth_ != tc.CtoS_level_)
+            throw std::logic_error("coeff_to_slot input level does not match transform_context.CtoS_start_level");
+        check_plain_two_part(cipher);
+        FactorArgs fa(*this, tc.CtoS_factors_, galois_key);
+        const int P = tc.CtoS_piece_, out_depth = cipher.depth_ + P + 1;
+        if (out_depth >= context_->Q_size) throw std::logic_error("coeff_to_slot: no modulus left for the results");
+        const size_t n = context_->n, words = 2 * n * (size_t) (context_->Q_size - out_depth);
+        const size_t wsb = hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher.depth_, 1);
+        DeviceVector<Data64> ws(wsb / 8, o.stream_), m0(words, o.stream_), m1(words, o.stream_);
+        detail::check(hegpu_ckks_coeff_to_slot(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m0.data(),
+                                               (uint64_t*) m1.data(), 0, fa.f.data(), P, conj_key(galois_key), cipher.depth_,
+                                               1, ws.data(), wsb, o.stream_));
+        double sc = cipher.scale_; // every factor multiplies by its scale and the rescale divides by the modulus it drops
+        for (int k = 0; k < P; k++)
+            sc = sc * tc.CtoS_factors_[k]->scale() / (double) context_->prime_vector_[limbs(cipher) - 1 - k].value;
+        std::vector<Ciphertext<S>> result(2, Ciphertext<S>(context_));
+        for (int r = 0; r < 2; r++) {
+            copy_meta(cipher, result[r]);
+            result[r].memory_set(std::move(r ? m1 : m0));
+            result[r].depth_ = out_depth;
+            result[r].scale_ = sc;
+            result[r].encoding_ = encoding::SLOT;
+        }
+        return result;
+    }
+
+    // host/ckks/operator.cu:3809-3891 (hegpu_ckks_slot_to_coeff): the inverse of coeff_to_slot on inputs in its
+    // bit-reversed order; the result leaves at StoC_level_ + 1 + StoC_piece_.
+    Ciphertext<S> slot_to_coeff(Ciphertext<S>& cipher0, Ciphertext<S>& cipher1, Galoiskey<S>& galois_key,
+                                CKKSEncodingTransformContext& tc, const ExecutionOptions& o = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "encoding transforms are a CKKS operation");
+        detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
+        if (!tc.generated_) throw std::invalid_argument("Encoding transform context is not generated!");
+        if (cipher0.encoding_ != encoding::SLOT || cipher1.encoding_ != encoding::SLOT)
+            throw std::invalid_argument("slot_to_coeff expects slot-encoded ciphertext inputs.");
+        if (cipher0.depth_ != cipher1.depth_)
+            throw std::logic_error("slot_to_coeff expects equal levels for both slot ciphertexts.");
+        if (cipher0.depth_ != tc.StoC_level_)
+            throw std::logic_error("slot_to_coeff input level does not match transform_context.StoC_start_level");
+        check_plain_two_part(cipher0);
+        check_plain_two_part(cipher1);
+        FactorArgs fa(*this, tc.StoC_factors_, galois_key);
+        const int P = tc.StoC_piece_, out_depth = cipher0.depth_ + 1 + P;
+        if (out_depth >= context_->Q_size) throw std::logic_error("slot_to_coeff: no modulus left for the result");
+        const size_t n = context_->n;
+        const size_t wsb = hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher0.depth_, 1);
+        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        DeviceVector<Data64> m(2 * n * (size_t) (context_->Q_size - out_depth + 1), o.stream_); // rescaled in place at the end
+        detail::check(hegpu_ckks_slot_to_coeff(context_->handle(), (const uint64_t*) cipher0.data(), 0,
+                                               (const uint64_t*) cipher1.data(), 0, (uint64_t*) m.data(), 0, fa.f.data(), P,
+                                               cipher0.depth_, 1, ws.data(), wsb, o.stream_));
+        double sc = cipher0.scale_;
+        for (int k = 0; k < P; k++)
+            sc = sc * tc.StoC_factors_[k]->scale() / (double) context_->prime_vector_[limbs(cipher0) - 2 - k].value;
+        Ciphertext<S> result(context_);
+        copy_meta(cipher0, result);
+        result.memory_set(std::move(m));
+        result.depth_ = out_depth;
+        result.scale_ = sc;
+        result.encoding_ = encoding::COEFFICIENT;
+        return result;
+    }
+
   private:
+    void check_plain_two_part(const Ciphertext<S>& a) const
+    {
+        if (a.relinearization_required_ || a.cipher_size_ != 2)
+            throw std::invalid_argument("Ciphertext should be relinearized first!");
+        if (a.rescale_required_) throw std::invalid_argument("Ciphertext should be rescaled first!");
+        if (a.memory_size() < 2 * context_->n * (size_t) limbs(a)) throw std::invalid_argument("Invalid Ciphertexts size!");
+    }
+    const uint64_t* conj_key(Galoiskey<S>& gk) const
+    {
+        auto it = gk.device_location_.find(gk.galois_elt_zero);
+        if (it == gk.device_location_.end()) throw std::invalid_argument("Galois key not present! (conjugation)");
+        return (const uint64_t*) it->second.data();
+    }
+    // the hegpu_linear_factor array of a chain of LinearTransform objects, with the key and element tables it points into
+    struct FactorArgs {
+        std::vector<std::vector<const uint64_t*>> keys;
+        std::vector<std::vector<int>> elts;
+        std::vector<hegpu_linear_factor> f;
+        FactorArgs(HEArithmeticOperator& op, const std::vector<std::shared_ptr<LinearTransform<S>>>& lts, Galoiskey<S>& gk)
+            : keys(lts.size()), elts(lts.size()), f(lts.size())
+        {
+            for (size_t k = 0; k < lts.size(); k++) {
+                const LinearTransform<S>& lt = *lts[k];
+                const int n1 = lt.n1(), n2 = lt.n2();
+                keys[k].assign(n1 + n2, nullptr);
+                elts[k].assign(n1 + n2, 0);
+                for (int i = 0; i < n1 + n2; i++) {
+                    const int shift = i < n1 ? lt.baby_shifts()[i] : lt.giant_shifts()[i - n1];
+                    if (shift == 0) continue;
+                    elts[k][i] = hegpu_steps_to_galois_elt(shift, (int) op.context_->n, gk.group_order_);
+                    auto it = gk.device_location_.find(elts[k][i]);
+                    if (it == gk.device_location_.end())
+                        throw std::invalid_argument("Galois key not present! (build the Galoiskey from key_indexs_)");
+                    keys[k][i] = (const uint64_t*) it->second.data();
+                }
+                f[k] = hegpu_linear_factor{(const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1, n2,
+                                           keys[k].data(), elts[k].data(), keys[k].data() + n1, elts[k].data() + n1};
+            }
+        }
+    };
     void apply_key(Ciphertext<S>& in, Ciphertext<S>& out, const Data64* key, int galois_elt, const ExecutionOptions& o)
     {
         if (in.relinearization_required_) throw std::invalid_argument("Ciphertext should be relinearized first!");
