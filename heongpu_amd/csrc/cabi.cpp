@@ -653,9 +653,7 @@ int hegpu_divide_round_lastq(hegpu_context* ctx, const uint64_t* in, uint64_t in
     const Context& c = ctx->c;
     if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "divide_round_lastq needs a single special prime (method I)");
     return hip_ret(rns_divide_round_lastq((const u64*) in, in_stride, (const u64*) ct, ct_stride, (u64*) out,
-                                          out_stride, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                                          c.tab.last_q_modinv, c.n_power, c.Q_size, switchkey, batch,
-                                          (hipStream_t) stream),
+                                          out_stride, c.moddown(0), switchkey, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq");
 }
 
@@ -668,10 +666,7 @@ int hegpu_divide_round_lastq_permute(hegpu_context* ctx, const uint64_t* in, uin
     const Context& c = ctx->c;
     if (c.scheme == SCHEME_BFV && depth != 0) return fail(HEGPU_E_INVALID, "BFV ciphertexts have no depth");
     return hip_ret(rns_moddown_permute((const u64*) in, in_stride, (const u64*) in2, in2_stride, (u64*) out,
-                                       out_stride, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                                       c.tab.last_q_modinv, galois_elt, c.n_power, c.Qp_size - depth,
-                                       c.Q_size - depth, c.Qp_size, c.Q_size, c.P_size, batch,
-                                       (hipStream_t) stream),
+                                       out_stride, c.moddown(depth), galois_elt, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_permute");
 }
 
@@ -690,16 +685,9 @@ int hegpu_divide_round_lastq_leveled_stage_one(hegpu_context* ctx, const uint64_
                                                hegpu_stream stream)
 {
     SEAM_CKKS(ctx, depth, batch, rescale ? 2 : 1);
-    if (rescale)
-        return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                             c.tab.rescaled_half + depth,
-                                             c.tab.rescaled_half_mod + triangle_offset(c.Q_size - 1, depth), c.n_power,
-                                             l - 1, l - 1, batch, (hipStream_t) stream),
-                       "hegpu_divide_round_lastq_leveled_stage_one");
-    if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
-    return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.tab.half, c.tab.half_mod, c.n_power, c.Q_size, l, batch,
-                                         (hipStream_t) stream),
+    if (!rescale && c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
+    return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.moddown(depth, rescale != 0),
+                                         batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_one");
 }
 
@@ -711,9 +699,8 @@ int hegpu_divide_round_lastq_leveled_stage_two(hegpu_context* ctx, const uint64_
     SEAM_CKKS(ctx, depth, batch, 1);
     if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
     if (!ct) return fail(HEGPU_E_INVALID, "ct must not be NULL");
-    return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, l + 1,
-                                         (const u64*) ct, ct_stride, (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.tab.last_q_modinv, c.n_power, l, switchkey ? 2 : 1, batch,
+    return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, (const u64*) ct,
+                                         ct_stride, (u64*) out, out_stride, c.moddown(depth), switchkey ? 2 : 1, batch,
                                          (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_two");
 }
@@ -732,10 +719,8 @@ int hegpu_divide_round_lastq_rescale(hegpu_context* ctx, const uint64_t* in_last
                                      int depth, int batch, hegpu_stream stream)
 {
     SEAM_CKKS(ctx, depth, batch, 2);
-    return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, l, nullptr, 0,
-                                         (u64*) out, out_stride, c.plan_qp.mods,
-                                         c.tab.rescaled_last_q_modinv + triangle_offset(c.Q_size - 1, depth), c.n_power,
-                                         l - 1, 0, batch, (hipStream_t) stream),
+    return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, nullptr, 0,
+                                         (u64*) out, out_stride, c.moddown(depth, true), 0, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_rescale");
 }
 
@@ -752,9 +737,7 @@ int hegpu_divide_round_lastq_extended(hegpu_context* ctx, const uint64_t* in, ui
     if (batch < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");
     if (batch == 0) return 0;
     return hip_ret(rns_moddown_extended((const u64*) in, in_stride, (const u64*) ct, ct_stride, (u64*) out, out_stride,
-                                        c.plan_qp.mods, c.tab.half, c.tab.half_mod, c.tab.last_q_modinv,
-                                        c.n_power, c.Qp_size - depth, c.Q_size - depth, c.Qp_size, c.Q_size, c.P_size,
-                                        mode, batch, (hipStream_t) stream),
+                                        c.moddown(depth), mode, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_extended");
 }
 

@@ -857,4 +857,16 @@ NttArgs Context::ntt_args(int table_set) const
     return a;
 }
 
+ModDown Context::moddown(int depth, bool rescale) const
+{
+    const int l = Q_size - depth;
+    if (!rescale)
+        return {plan_qp.mods, tab.half, tab.half_mod, tab.last_q_modinv, n_power, Qp_size - depth, l, Qp_size, Q_size,
+                P_size};
+    // the divisor is the last of the l live primes: entry / row `depth` of the per-depth tables (ckks/operator.cu:1181-1187)
+    const int row = triangle_offset(Q_size - 1, depth);
+    return {plan_qp.mods, tab.rescaled_half + depth, tab.rescaled_half_mod + row, tab.rescaled_last_q_modinv + row,
+            n_power, l, l - 1, l, l - 1, 1};
+}
+
 } // namespace hegpu

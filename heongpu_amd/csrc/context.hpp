@@ -23,6 +23,15 @@ bool env_long(const char* name, long* out);
 
 enum Scheme { SCHEME_BFV = 1, SCHEME_CKKS = 2 };
 
+// Offset of row `depth` in a triangular per-depth table whose rows hold first, first - 1, ... entries
+// (reference ckks/operator.cu:949-955, 1181-1187)
+inline int triangle_offset(int first, int depth)
+{
+    int location = 0;
+    for (int i = 0; i < depth; i++) location += first - i;
+    return location;
+}
+
 struct NttPlan {
     // device arrays, one entry / table per modulus
     Mod* mods = nullptr;
@@ -129,6 +138,8 @@ struct Context : ContextHost {
     void release_device();
 
     NttArgs ntt_args(int table_set) const; // 0 = Q' chain, 1 = merged q|Bsk
+    // the mod-down by the special primes of a ciphertext at `depth`; rescale (CKKS, depth < Q_size - 1): by its last prime
+    ModDown moddown(int depth, bool rescale = false) const;
 };
 
 } // namespace hegpu

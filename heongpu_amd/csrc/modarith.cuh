@@ -55,6 +55,15 @@ HG_HD void mul64wide(u64 a, u64 b, u64& hi, u64& lo)
     hi = p11;
 }
 
+// hi:lo += a * b (a, b < 2^61: the running sum of a few dozen such products stays below 2^128)
+HG_HD void acc128(u64& hi, u64& lo, u64 a, u64 b)
+{
+    u64 h, l;
+    mul64wide(a, b, h, l);
+    lo += l;
+    hi += h + (lo < l);
+}
+
 HG_HD u64 mulhi64(u64 a, u64 b)
 {
     u64 hi, lo;

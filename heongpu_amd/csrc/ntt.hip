@@ -1110,14 +1110,6 @@ __global__ __launch_bounds__(16 << S1, 4) void ntt_fwd_single(NttArgs a)
 }
 
 // ------------------------------------------------------------------ fused row pass + key-switch MAC
-__device__ __forceinline__ void acc128(u64& hi, u64& lo, u64 a, u64 b)
-{
-    u64 h, l;
-    mul64wide(a, b, h, l);
-    lo += l;
-    hi += h + (lo < l);
-}
-
 template <bool LAZY, int ROOM = 8>
 __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict__ p, u64* lds,
                                              const ulonglong2* twa, const ulonglong2* __restrict__ tb,

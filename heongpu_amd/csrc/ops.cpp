@@ -219,10 +219,8 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
                                       u64* temp1, u64* temp2, u64 per, hipStream_t st, unsigned phases,
                                       int galois_elt = 0)
 {
-    const int np = c.n_power;
     const int Q = c.Q_size, Qp = c.Qp_size;
     const int l = Q - depth, rc = Qp - depth;
-    const Mod* mods = c.plan_qp.mods;
 
     NttArgs a = c.ntt_args(0);
     // INTT(src), batch l per item (:919) -- out of place into the (not yet used)
@@ -300,8 +298,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     if (!(phases & RELIN_PHASE_MODDOWN)) return hipSuccess;
     // stage one: P limb (+half) reduced into every q_j               (:1003)
     if (!c.fused_moddown)
-        TRY(rns_moddown_stage_one(temp2, per, temp1, per, mods, c.tab.half, c.tab.half_mod, np, Q, l, batch,
-                                  st));
+        TRY(rns_moddown_stage_one(temp2, per, temp1, per, c.moddown(depth), batch, st));
     // forward NTT of that (:1011) with stage one as its load transform and stage two -- (x - last) * P^-1 + add, written to
     // out parts 0,1 (:1015) -- as the epilogue of its row pass
     a = c.ntt_args(0);
@@ -325,8 +322,7 @@ static hipError_t ckks_keyswitch_core(const Context& c, const u64* src, u64 src_
     }
     if (add_parts != 2 || galois_elt) return hipErrorInvalidValue; // the stand-alone stage two adds both parts (relinearize only)
     TRY(ntt_launch(a, 2 * l * batch, false, st));
-    return rns_moddown_stage_two(temp1, per, temp2, per, l + 1, add, add_stride, outp, out_stride, mods,
-                                 c.tab.last_q_modinv, np, l, 1, batch, st);
+    return rns_moddown_stage_two(temp1, per, temp2, per, add, add_stride, outp, out_stride, c.moddown(depth), 1, batch, st);
 }
 
 // ------------------------------------------------------------------ method II (P_size > 1)
@@ -363,9 +359,7 @@ static hipError_t ckks_moddown_multi(const Context& c, u64* acc, u64* scratch, u
         a.in_item_stride = a.out_item_stride = per;
         TRY(ntt_launch(a, P * batch, true, st));
     }
-    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                                    c.tab.last_q_modinv, c.tab.m2_md_G, c.tab.m2_md_C, c.n_power, rc, l, Qp, Q,
-                                    P, batch, st));
+    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.moddown(depth), c.tab.m2_md_G, c.tab.m2_md_C, batch, st));
     NttArgs a = c.ntt_args(0);
     a.in = a.out = scratch; a.mod_count = l; a.polys_per_item = 2 * l;
     a.in_item_stride = a.out_item_stride = per;
@@ -392,8 +386,7 @@ static hipError_t ckks_rotate_tail(const Context& c, u64* acc, const u64* coef, 
     a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1524
-    TRY(rns_moddown_permute(acc, per, coef, per, out, so, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                            c.tab.last_q_modinv, galois_elt, c.n_power, rc, l, Qp, Q, c.P_size, batch, st)); // :1530
+    TRY(rns_moddown_permute(acc, per, coef, per, out, so, c.moddown(depth), galois_elt, batch, st)); // :1530
     a = c.ntt_args(0);
     a.in = out; a.out = out; a.mod_count = l; a.polys_per_item = 2 * l;
     a.in_item_stride = a.out_item_stride = so;
@@ -442,8 +435,7 @@ static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int
     if (!relin) return ckks_rotate_tail(c, acc, ws, per, out, so, galois_elt, depth, batch, st);
     a.in = acc; a.out = acc; a.polys_per_item = 2 * rc;
     TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1131
-    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                             c.tab.last_q_modinv, np, rc, l, Qp, Q, c.P_size, 0, batch, st)); // :1136
+    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.moddown(depth), 0, batch, st)); // :1136
     a = c.ntt_args(0);
     a.in = ws; a.out = ws; a.mod_count = l; a.polys_per_item = 2 * l;
     a.in_item_stride = a.out_item_stride = per;
@@ -475,11 +467,10 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
     const u64 n = c.n;
     const int Q = c.Q_size, P = c.P_size;
     const int l = Q - depth;
-    const int location = triangle_offset(Q - 1, depth); // reference ckks/operator.cu:1181-1187
+    const ModDown md = c.moddown(depth, true);
     const u64 per = ((u64) 2 * (l - 1) + 2 * l) * n;
     u64* temp1 = ws;                         // [2][l-1][N]
     u64* temp2 = ws + (u64) 2 * (l - 1) * n; // copy of ct, part stride l
-    const Mod* mods = c.plan_qp.mods;
 
     NttArgs a = c.ntt_args(0);
     a.in = ct; a.out = ct; a.mod_count = 1; a.mod_offset = l - 1; a.polys_per_item = 2;
@@ -495,7 +486,7 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         a.in_item_stride = cs; a.out_item_stride = per;
         a.decomp_mods = l - 1; a.decomp_in_mul = l; a.decomp_in_add = l - 1;
         a.half_on = 1; a.half_src_mod = l - 1; a.half = c.hv.rescaled_half[depth];
-        a.half_mod = c.tab.rescaled_half_mod + location;
+        a.half_mod = md.half_mod;
         // The copy rides on the column pass when that is the per-polynomial kernel (one workgroup per kept limb
         // and tile: C2, 4.7 us of launch less); the multi-modulus kernel keeps its own launch for it.
         if (c.copy_along && !ntt_decomp_uses_multi(a, 2 * (l - 1) * batch)) {
@@ -509,19 +500,17 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         a.epi.ks = temp2; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = l;
         a.epi.ct = nullptr; a.epi.ct_item_stride = 0;
         a.epi.out = ct; a.epi.out_item_stride = cs;
-        a.epi.inv = c.tab.rescaled_last_q_modinv + location;
+        a.epi.inv = md.last_q_modinv;
         a.epi.limbs = l - 1;
         return ntt_launch(a, 2 * (l - 1) * batch, false, st);
     }
-    TRY(rns_moddown_stage_one(ct, cs, temp1, per, mods, c.tab.rescaled_half + depth,
-                              c.tab.rescaled_half_mod + location, np, l - 1, l - 1, batch, st)); // :1205
+    TRY(rns_moddown_stage_one(ct, cs, temp1, per, md, batch, st));                         // :1205
     a = c.ntt_args(0);
     a.in = temp1; a.out = temp1; a.mod_count = l - 1; a.polys_per_item = 2 * (l - 1);
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * (l - 1) * batch, false, st));                                    // :1214
     TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, per, np, l - 1, 2, batch, st)); // :1219
-    return rns_moddown_stage_two(temp1, per, temp2, per, l, nullptr, 0, ct, cs, mods,
-                                 c.tab.rescaled_last_q_modinv + location, np, l - 1, 0, batch, st); // :1225
+    return rns_moddown_stage_two(temp1, per, temp2, per, nullptr, 0, ct, cs, md, 0, batch, st); // :1225
 }
 
 // reference ckks/operator.cu:1422-1559
@@ -640,9 +629,7 @@ static hipError_t bfv_intt_moddown_multi(const Context& c, u64* acc, u64* scratc
         a.in_item_stride = a.out_item_stride = per;
         TRY(ntt_launch(a, P * batch, true, st));
     }
-    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.plan_qp.mods, c.tab.half, c.tab.half_mod,
-                                    c.tab.last_q_modinv, c.tab.m2_md_G, c.tab.m2_md_C, c.n_power, Qp, Q, Qp, Q, P,
-                                    batch, st));
+    TRY(rns_moddown_multi_stage_one(acc, per, scratch, per, c.moddown(0), c.tab.m2_md_G, c.tab.m2_md_C, batch, st));
     NttArgs a = c.ntt_args(0);
     a.in = a.out = acc; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
     a.in_item_stride = a.out_item_stride = per;
@@ -664,7 +651,6 @@ static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add
                                 const u64* key, int galois_elt, int batch, u64* ws, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    const int np = c.n_power;
     const u64 n = c.n;
     const int Q = c.Q_size, Qp = c.Qp_size;
     const bool m2 = c.P_size > 1;
@@ -672,7 +658,6 @@ static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add
     const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
     u64* temp1 = ws;                    // [digits][Q'][N]
     u64* temp2 = ws + (u64) Q * Qp * n; // [2][Q'][N]
-    const Mod* mods = c.plan_qp.mods;
     const u64* src = ct + (u64) add_parts * Q * n;
     NttArgs a = c.ntt_args(0);
     a.out = temp1; a.mod_count = Qp; a.polys_per_item = digits * Qp; a.out_item_stride = per;
@@ -692,13 +677,9 @@ static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add
     a.in_item_stride = a.out_item_stride = per;
     TRY(ntt_launch(a, 2 * Qp * batch, true, st));
     if (add_parts == 1)
-        return rns_moddown_permute(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
-                                   c.tab.last_q_modinv, galois_elt, np, Qp, Q, Qp, Q, c.P_size, batch, st);
-    if (m2)
-        return rns_moddown_extended(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
-                                    c.tab.last_q_modinv, np, Qp, Q, Qp, Q, c.P_size, 1, batch, st);
-    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, mods, c.tab.half, c.tab.half_mod,
-                                  c.tab.last_q_modinv, np, Q, 0, batch, st);
+        return rns_moddown_permute(temp2, per, ct, cs, out, so, c.moddown(0), galois_elt, batch, st);
+    if (m2) return rns_moddown_extended(temp2, per, ct, cs, out, so, c.moddown(0), 1, batch, st);
+    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, c.moddown(0), 0, batch, st);
 }
 
 hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws, hipStream_t st)
@@ -1012,7 +993,7 @@ hipError_t op_gen_switch_key(const Context& c, Rng& r, const u64* sk, int galois
 // (pk*u + e) / P with rounding: the common front of both encryptions (encryptor.cu:52-100)
 static hipError_t encrypt_zero(const Context& c, Rng& r, const u64* pk, u64* ct, u64* ws, hipStream_t st)
 {
-    const int np = c.n_power, Q = c.Q_size, Qp = c.Qp_size;
+    const int np = c.n_power, Qp = c.Qp_size;
     const u64 n = c.n;
     u64* u = ws;                       // [Q'][N]
     u64* e = u + (u64) Qp * n;         // [2][Q'][N]
@@ -1024,8 +1005,7 @@ static hipError_t encrypt_zero(const Context& c, Rng& r, const u64* pk, u64* ct,
     TRY(kg_pk_u(pk, u, pku, mods, np, Qp, st));
     TRY(transform(c, pku, pku, Qp, 2 * Qp, true, st));
     TRY(rns_addition(pku, e, pku, mods, np, Qp, 2, 1, 0, st));
-    return rns_moddown_extended(pku, 0, nullptr, 0, ct, 0, mods, c.tab.half, c.tab.half_mod,
-                                c.tab.last_q_modinv, np, Qp, Q, Qp, Q, c.P_size, 0, 1, st);
+    return rns_moddown_extended(pku, 0, nullptr, 0, ct, 0, c.moddown(0), 0, 1, st);
 }
 
 hipError_t op_ckks_encrypt(const Context& c, Rng& r, const u64* pk, const u64* plain, u64* ct, u64* ws,

@@ -13,15 +13,6 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
 
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
-// Offset of row `depth` in a triangular per-depth table whose rows hold first, first - 1, ... entries
-// (reference ckks/operator.cu:949-955, 1181-1187)
-inline int triangle_offset(int first, int depth)
-{
-    int location = 0;
-    for (int i = 0; i < depth; i++) location += first - i;
-    return location;
-}
-
 hipError_t op_ckks_multiply(const Context& c, const u64* ct1, u64 s1, const u64* ct2, u64 s2, u64* out, u64 so,
                             int depth, int batch, hipStream_t st);
 // Relinearize and apply_galois run key-switching method I with one special prime (P_size == 1), method II with several.

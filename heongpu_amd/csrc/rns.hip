@@ -10,6 +10,7 @@
 // outputs are the same canonical residues.
 #include "rns.hpp"
 #include <cstdlib>
+#include <type_traits>
 
 namespace hegpu {
 
@@ -21,6 +22,17 @@ __device__ __forceinline__ void st2(u64* p, ulonglong2 v) { *reinterpret_cast<ul
 __device__ __forceinline__ u64 coeff0() { return ((u64) blockIdx.x * RNS_THREADS + threadIdx.x) * 2; }
 
 static inline dim3 grid3(int n_power, int y, int z) { return dim3((1u << n_power) / RNS_PER_BLOCK, y, z); }
+
+// A run-time width picks the kernel instance compiled for it: f(width_c<W>{}) for the first W of the ascending list
+// Ws that holds w, the last one when none does.  f is a generic lambda; W() inside it is a constant expression.
+template <int W> using width_c = std::integral_constant<int, W>;
+template <int W, int... Ws, class F>
+static void dispatch_width(int w, F&& f)
+{
+    if constexpr (sizeof...(Ws) == 0) f(width_c<W>{});
+    else if (w <= W) f(width_c<W>{});
+    else dispatch_width<Ws...>(w, f);
+}
 
 // ---------------------------------------------------------------- add/sub/neg
 template <int OP>
@@ -193,14 +205,6 @@ hipError_t rns_sum_partials(const u64* buf, u64 buf_item_stride, u64* out, u64 o
 }
 
 // ---------------------------------------------------------------- key-switch inner product
-__device__ __forceinline__ void acc_mad(u64& hi, u64& lo, u64 a, u64 b)
-{
-    u64 h, l;
-    mul64wide(a, b, h, l);
-    lo += l;
-    hi += h + (lo < l);
-}
-
 // sum_j v[j] * row[j < valid ? j : 0] as a 128-bit integer, every operand below 2^61 (residues and table
 // entries of moduli of at most 61 bits; v[j] == 0 beyond `valid`).  A 128-bit multiply-accumulate per term
 // costs ~19 instructions, most of them carries and the shifted addends of the 4-multiply chain.  Here the four
@@ -280,10 +284,10 @@ __global__ __launch_bounds__(RNS_THREADS) void k_keyswitch_mac(const u64* __rest
 #pragma unroll
         for (int t = 0; t < ITEMS; t++) {
             const ulonglong2 d = ld2(pin + in_stride * t + dig_off * i);
-            acc_mad(h[t][0], l[t][0], d.x, k0.x);
-            acc_mad(h[t][1], l[t][1], d.y, k0.y);
-            acc_mad(h[t][2], l[t][2], d.x, k1.x);
-            acc_mad(h[t][3], l[t][3], d.y, k1.y);
+            acc128(h[t][0], l[t][0], d.x, k0.x);
+            acc128(h[t][1], l[t][1], d.y, k0.y);
+            acc128(h[t][2], l[t][2], d.x, k1.x);
+            acc128(h[t][3], l[t][3], d.y, k1.y);
         }
     }
 #pragma unroll
@@ -450,21 +454,20 @@ hipError_t rns_keyswitch_mac_keys(const u64* in, u64 in_stride, const u64* const
     while (zsplit * 2 * E <= batch && (unsigned long) tiles * nmods * zsplit < 2048) zsplit *= 2;
     const int per_wg = (batch + zsplit - 1) / zsplit;
     const size_t lds = (size_t) digits * 4096;
-#define LAUNCH(EE, KOFF)                                                                                                   \
-    do {                                                                                                                   \
-        KsmKeys k2 = kk;                                                                                                   \
-        for (int e = 0; e < KSM_KEYS; e++) k2.k[e] = kk.k[(KOFF) + e < KSM_KEYS ? (KOFF) + e : KSM_KEYS - 1];              \
-        hipLaunchKernelGGL(k_keyswitch_mac_keys<EE>, dim3((1u << n_power) / (RNS_THREADS / (EE)), nmods, (batch + per_wg - 1) / per_wg), \
-                           dim3(RNS_THREADS), lds, st, in, in_stride, k2, out + (u64) (KOFF) * out_key_stride, out_stride,     \
-                           out_key_stride, mods, n_power, digits, nmods, key_limbs, split, level, batch, per_wg);          \
-    } while (0)
+    auto launch = [&](auto EE, int koff) { // EE keys from key `koff` on
+        KsmKeys k2 = kk;
+        for (int e = 0; e < KSM_KEYS; e++) k2.k[e] = kk.k[koff + e < KSM_KEYS ? koff + e : KSM_KEYS - 1];
+        hipLaunchKernelGGL(k_keyswitch_mac_keys<EE()>,
+                           dim3((1u << n_power) / (RNS_THREADS / EE()), nmods, (batch + per_wg - 1) / per_wg),
+                           dim3(RNS_THREADS), lds, st, in, in_stride, k2, out + (u64) koff * out_key_stride, out_stride,
+                           out_key_stride, mods, n_power, digits, nmods, key_limbs, split, level, batch, per_wg);
+    };
     switch (key_count) {
-        case 1: LAUNCH(1, 0); break;
-        case 2: LAUNCH(2, 0); break;
-        case 3: LAUNCH(2, 0); LAUNCH(1, 2); break;
-        default: LAUNCH(4, 0); break;
+        case 1: launch(width_c<1>{}, 0); break;
+        case 2: launch(width_c<2>{}, 0); break;
+        case 3: launch(width_c<2>{}, 0); launch(width_c<1>{}, 2); break;
+        default: launch(width_c<4>{}, 0); break;
     }
-#undef LAUNCH
     return hipGetLastError();
 }
 
@@ -492,6 +495,16 @@ hipError_t rns_keyswitch_mac(const u64* in, u64 in_stride, const u64* key, u64* 
 }
 
 // ---------------------------------------------------------------- mod-down (BFV, single kernel)
+// One limb's step of the mod-down by one special prime: (x - ((lh mod q) - half_mod)) * inv mod q, with lh = the special
+// prime's limb + half (below 2^64, any size against q), half_mod = half mod q and inv = that prime's inverse mod q.
+__device__ __forceinline__ u64 moddown_step(u64 x, u64 lh, u64 half_mod, u64 inv, const Mod& m)
+{
+    u64 t = reduce64(lh, m);
+    t = sub_mod(t, half_mod, m.q);
+    t = sub_mod(x, t, m.q);
+    return mul_barrett(t, inv, m);
+}
+
 __global__ __launch_bounds__(RNS_THREADS) void k_divide_round_lastq(
     const u64* __restrict__ in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out, u64 out_stride,
     const Mod* __restrict__ mods, const u64* __restrict__ half, const u64* __restrict__ half_mod,
@@ -510,34 +523,18 @@ __global__ __launch_bounds__(RNS_THREADS) void k_divide_round_lastq(
     ulonglong2 cin = make_ulonglong2(0, 0);
     if (!(switchkey && z != 0)) cin = ld2(ct + ct_stride * b + loc);
     ulonglong2 r;
-    {
-        u64 l = add_mod(last.x, h, qP);
-        l = reduce64(l, m);
-        l = sub_mod(l, hm, m.q);
-        u64 v = sub_mod(x.x, l, m.q);
-        v = mul_barrett(v, inv, m);
-        r.x = add_mod(cin.x, v, m.q);
-    }
-    {
-        u64 l = add_mod(last.y, h, qP);
-        l = reduce64(l, m);
-        l = sub_mod(l, hm, m.q);
-        u64 v = sub_mod(x.y, l, m.q);
-        v = mul_barrett(v, inv, m);
-        r.y = add_mod(cin.y, v, m.q);
-    }
+    r.x = add_mod(cin.x, moddown_step(x.x, add_mod(last.x, h, qP), hm, inv, m), m.q);
+    r.y = add_mod(cin.y, moddown_step(x.y, add_mod(last.y, h, qP), hm, inv, m), m.q);
     st2(out + out_stride * b + loc, r);
 }
 
 hipError_t rns_divide_round_lastq(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out,
-                                  u64 out_stride, const Mod* mods, const u64* half, const u64* half_mod,
-                                  const u64* last_q_modinv, int n_power, int decomp, int switchkey, int batch,
-                                  hipStream_t st)
+                                  u64 out_stride, const ModDown& md, int switchkey, int batch, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    hipLaunchKernelGGL(k_divide_round_lastq, grid3(n_power, decomp, 2 * batch), dim3(RNS_THREADS), 0, st, in,
-                       in_stride, ct, ct_stride, out, out_stride, mods, half, half_mod, last_q_modinv, n_power,
-                       decomp, switchkey);
+    hipLaunchKernelGGL(k_divide_round_lastq, grid3(md.n_power, md.Q_cur, 2 * batch), dim3(RNS_THREADS), 0, st, in,
+                       in_stride, ct, ct_stride, out, out_stride, md.mods, md.half, md.half_mod, md.last_q_modinv,
+                       md.n_power, md.Q_cur, switchkey);
     return hipGetLastError();
 }
 
@@ -566,13 +563,12 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_stage_one(
     }
 }
 
-hipError_t rns_moddown_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods,
-                                 const u64* half, const u64* half_mod, int n_power, int first_decomp,
-                                 int cur_decomp, int batch, hipStream_t st)
+hipError_t rns_moddown_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const ModDown& md, int batch,
+                                 hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    hipLaunchKernelGGL(k_moddown_stage_one, grid3(n_power, 2, batch), dim3(RNS_THREADS), 0, st, in, in_stride, out,
-                       out_stride, mods, half, half_mod, n_power, first_decomp, cur_decomp);
+    hipLaunchKernelGGL(k_moddown_stage_one, grid3(md.n_power, 2, batch), dim3(RNS_THREADS), 0, st, in, in_stride, out,
+                       out_stride, md.mods, md.half, md.half_mod, md.n_power, md.first_Q, md.Q_cur);
     return hipGetLastError();
 }
 
@@ -604,24 +600,15 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_stage_two(
     st2(out + out_stride * b + loc, r);
 }
 
-hipError_t rns_moddown_stage_two(const u64* in_last, u64 last_stride, const u64* in, u64 in_stride, int in_limbs,
-                                 const u64* ct, u64 ct_stride, u64* out, u64 out_stride, const Mod* mods,
-                                 const u64* last_q_modinv, int n_power, int cur_decomp, int with_ct, int batch,
+hipError_t rns_moddown_stage_two(const u64* in_last, u64 last_stride, const u64* in, u64 in_stride, const u64* ct,
+                                 u64 ct_stride, u64* out, u64 out_stride, const ModDown& md, int with_ct, int batch,
                                  hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    hipLaunchKernelGGL(k_moddown_stage_two, grid3(n_power, cur_decomp, 2 * batch), dim3(RNS_THREADS), 0, st,
-                       in_last, last_stride, in, in_stride, in_limbs, ct, ct_stride, out, out_stride, mods,
-                       last_q_modinv, n_power, cur_decomp, with_ct);
+    hipLaunchKernelGGL(k_moddown_stage_two, grid3(md.n_power, md.Q_cur, 2 * batch), dim3(RNS_THREADS), 0, st,
+                       in_last, last_stride, in, in_stride, md.Qp_cur, ct, ct_stride, out, out_stride, md.mods,
+                       md.last_q_modinv, md.n_power, md.Q_cur, with_ct);
     return hipGetLastError();
-}
-
-__device__ __forceinline__ void acc128_rns(u64& hi, u64& lo, u64 a, u64 b)
-{
-    u64 h, l;
-    mul64wide(a, b, h, l);
-    lo += l;
-    hi += h + (lo < l);
 }
 
 // ---------------------------------------------------------------- method II: digit -> Q~ base conversion
@@ -665,7 +652,7 @@ __global__ __launch_bounds__(RNS_THREADS) void k_base_conversion_DtoQtilde(
         const Mod m = mods[(i < l) ? i : i + level];
         u64 hi, lo;
         dot128(partial, matrix + (u64) i * cnt + (u64) s0 * rc, cnt, hi, lo);
-        acc128_rns(hi, lo, r_, prod[i + g * rc]);
+        acc128(hi, lo, r_, prod[i + g * rc]);
         po[(u64) i << n_power] = redc128(hi, lo, m);
     }
 }
@@ -678,15 +665,10 @@ hipError_t rns_base_conversion_DtoQtilde(const u64* in, u64 in_stride, u64* out,
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (max_cnt < 1 || max_cnt > 32) return hipErrorInvalidValue;
     dim3 g((1u << n_power) / RNS_THREADS, d, batch);
-#define LAUNCH(M)                                                                                                  \
-    hipLaunchKernelGGL(k_base_conversion_DtoQtilde<M>, g, dim3(RNS_THREADS), 0, st, in, in_stride, out, out_stride, \
-                       mods, matrix, mi_inv, prod, I_j, I_location, n_power, rc, l, level)
-    if (max_cnt <= 2) LAUNCH(2);
-    else if (max_cnt <= 4) LAUNCH(4);
-    else if (max_cnt <= 8) LAUNCH(8);
-    else if (max_cnt <= 16) LAUNCH(16);
-    else LAUNCH(32);
-#undef LAUNCH
+    dispatch_width<2, 4, 8, 16, 32>(max_cnt, [&](auto M) {
+        hipLaunchKernelGGL(k_base_conversion_DtoQtilde<M()>, g, dim3(RNS_THREADS), 0, st, in, in_stride, out, out_stride,
+                           mods, matrix, mi_inv, prod, I_j, I_location, n_power, rc, l, level);
+    });
     return hipGetLastError();
 }
 
@@ -697,6 +679,42 @@ hipError_t rns_base_conversion_DtoQtilde(const u64* in, u64 in_stride, u64* out,
 // the mod-down chain AMONG the special primes -- P (P - 1) / 2 reductions that do not depend on the limb -- for
 // every one of the Q_cur limbs; here it runs once (r[k] = special prime P_size - 1 - k, static register indices)
 // and leaves the P_size values lh_i the limbs need.
+// pin: limb 0 of this thread's coefficient; loc[i]: where step i's row of half_mod / last_q_modinv starts.
+// ZERO_PAD: the slots from P_size on end up zero (operands of a sum over all PMAX slots) instead of unspecified.
+// (The pointers carry no __restrict__ of their own: the kernels' qualifiers reach the inlined body, and repeating them here
+// took k_moddown_multi_stage_one<8> from 51 to 65 registers, one wave per SIMD less.)
+template <int PMAX, bool ZERO_PAD>
+__device__ __forceinline__ void special_prime_chain(u64 (&r)[PMAX], int (&loc)[PMAX], const u64* pin, const Mod* mods,
+                                                    const u64* half, const u64* half_mod, const u64* last_q_modinv,
+                                                    int n_power, int Q_cur, int first_Qp, int first_Q, int P_size)
+{
+#pragma unroll
+    for (int k = 0; k < PMAX; k++) r[k] = pin[(u64) (Q_cur + (k < P_size ? P_size - 1 - k : 0)) << n_power];
+    int location_ = 0;
+#pragma unroll
+    for (int i = 0; i < PMAX; i++) {
+        loc[i] = location_;
+        location_ += first_Qp - 1 - i;
+    }
+#pragma unroll
+    for (int i = 0; i < PMAX; i++) {
+        if (i < P_size) {
+            r[i] = add_mod(r[i], half[i], mods[first_Qp - 1 - i].q); // lh_i
+#pragma unroll
+            for (int k = i + 1; k < PMAX; k++) {
+                if (k < P_size) {
+                    const int j = P_size - 1 - k;
+                    const Mod mj = mods[first_Q + j];
+                    r[k] = moddown_step(r[k], r[i], half_mod[loc[i] + first_Q + j], last_q_modinv[loc[i] + first_Q + j], mj);
+                }
+            }
+        } else if (ZERO_PAD) {
+            r[i] = 0;
+        }
+    }
+}
+
+// The chain, then its P_size steps on each of the Q_cur limbs.
 // galois_elt != 0: the result goes through the coefficient permutation out[(i g) mod N] = +-v
 // (divide_round_lastq_permute_*_kernel with P_size > 1, switchkey.cu:1621-1813).
 template <int PMAX>
@@ -710,34 +728,9 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_extended(
     const int z = blockIdx.z & 1, b = blockIdx.z >> 1;
     const u64* pin = in + in_stride * b + (((u64) Qp_cur << n_power) * z) + idx;
     u64 r[PMAX];
-#pragma unroll
-    for (int k = 0; k < PMAX; k++) r[k] = pin[(u64) (Q_cur + (k < P_size ? P_size - 1 - k : 0)) << n_power];
     int loc[PMAX];
-    {
-        int location_ = 0;
-#pragma unroll
-        for (int i = 0; i < PMAX; i++) {
-            loc[i] = location_;
-            location_ += first_Qp - 1 - i;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < PMAX; i++) {
-        if (i < P_size) {
-            r[i] = add_mod(r[i], half[i], mods[first_Qp - 1 - i].q); // lh_i
-#pragma unroll
-            for (int k = i + 1; k < PMAX; k++) {
-                if (k < P_size) {
-                    const int j = P_size - 1 - k;
-                    const Mod mj = mods[first_Q + j];
-                    u64 t1 = reduce64(r[i], mj);
-                    t1 = sub_mod(t1, half_mod[loc[i] + first_Q + j], mj.q);
-                    t1 = sub_mod(r[k], t1, mj.q);
-                    r[k] = mul_barrett(t1, last_q_modinv[loc[i] + first_Q + j], mj);
-                }
-            }
-        }
-    }
+    special_prime_chain<PMAX, false>(r, loc, pin, mods, half, half_mod, last_q_modinv, n_power, Q_cur, first_Qp, first_Q,
+                                     P_size);
     const u64 part = ((u64) Q_cur << n_power) * z;
     const bool add = with_ct == 1 || (with_ct == 2 && z == 0);
     const u64* pc = ct + (add ? ct_stride * b + part + idx : 0);
@@ -758,14 +751,8 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_extended(
             const Mod m = mods[y];
             u64 v = x[u];
 #pragma unroll
-            for (int i = 0; i < PMAX; i++) {
-                if (i < P_size) {
-                    u64 t1 = reduce64(r[i], m);
-                    t1 = sub_mod(t1, half_mod[loc[i] + y], m.q);
-                    t1 = sub_mod(v, t1, m.q);
-                    v = mul_barrett(t1, last_q_modinv[loc[i] + y], m);
-                }
-            }
+            for (int i = 0; i < PMAX; i++)
+                if (i < P_size) v = moddown_step(v, r[i], half_mod[loc[i] + y], last_q_modinv[loc[i] + y], m);
             v = add ? add_mod(c4[u], v, m.q) : v;
             x[u] = neg ? m.q - v : v; // no zero test on the negation: reference switchkey.cu:1694,1711
         }
@@ -790,36 +777,9 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_multi_stage_one(
     const int z = blockIdx.z & 1, b = blockIdx.z >> 1;
     const u64* pin = in + in_stride * b + (((u64) Qp_cur << n_power) * z) + idx;
     u64 r[PMAX];
-#pragma unroll
-    for (int k = 0; k < PMAX; k++) r[k] = pin[(u64) (Q_cur + (k < P_size ? P_size - 1 - k : 0)) << n_power];
     int loc[PMAX];
-    {
-        int location_ = 0;
-#pragma unroll
-        for (int i = 0; i < PMAX; i++) {
-            loc[i] = location_;
-            location_ += first_Qp - 1 - i;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < PMAX; i++) {
-        if (i < P_size) {
-            r[i] = add_mod(r[i], half[i], mods[first_Qp - 1 - i].q); // lh_i
-#pragma unroll
-            for (int k = i + 1; k < PMAX; k++) {
-                if (k < P_size) {
-                    const int j = P_size - 1 - k;
-                    const Mod mj = mods[first_Q + j];
-                    u64 t1 = reduce64(r[i], mj);
-                    t1 = sub_mod(t1, half_mod[loc[i] + first_Q + j], mj.q);
-                    t1 = sub_mod(r[k], t1, mj.q);
-                    r[k] = mul_barrett(t1, last_q_modinv[loc[i] + first_Q + j], mj);
-                }
-            }
-        } else {
-            r[i] = 0;
-        }
-    }
+    special_prime_chain<PMAX, true>(r, loc, pin, mods, half, half_mod, last_q_modinv, n_power, Q_cur, first_Qp, first_Q,
+                                    P_size);
     u64* po = out + out_stride * b + (((u64) Q_cur << n_power) * z) + idx;
 #pragma unroll 1
     for (int y = 0; y < Q_cur; y++) {
@@ -830,44 +790,37 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_multi_stage_one(
     }
 }
 
-hipError_t rns_moddown_multi_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods,
-                                       const u64* half, const u64* half_mod, const u64* last_q_modinv, const u64* G,
-                                       const u64* C, int n_power, int Qp_cur, int Q_cur, int first_Qp, int first_Q,
-                                       int P_size, int batch, hipStream_t st)
+hipError_t rns_moddown_multi_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const ModDown& md,
+                                       const u64* G, const u64* C, int batch, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess;
-    if (P_size > 15 || P_size < 2) return hipErrorInvalidValue;
-    dim3 g((1u << n_power) / RNS_THREADS, 1, 2 * batch);
-#define LAUNCH(M)                                                                                                  \
-    hipLaunchKernelGGL(k_moddown_multi_stage_one<M>, g, dim3(RNS_THREADS), 0, st, in, in_stride, out, out_stride, mods, \
-                       half, half_mod, last_q_modinv, G, C, n_power, Qp_cur, Q_cur, first_Qp, first_Q, P_size)
-    if (P_size <= 2) LAUNCH(2);
-    else if (P_size <= 4) LAUNCH(4);
-    else if (P_size <= 8) LAUNCH(8);
-    else LAUNCH(16);
-#undef LAUNCH
+    if (md.P_size > 15 || md.P_size < 2) return hipErrorInvalidValue;
+    dim3 g((1u << md.n_power) / RNS_THREADS, 1, 2 * batch);
+    dispatch_width<2, 4, 8, 16>(md.P_size, [&](auto M) {
+        hipLaunchKernelGGL(k_moddown_multi_stage_one<M()>, g, dim3(RNS_THREADS), 0, st, in, in_stride, out, out_stride,
+                           md.mods, md.half, md.half_mod, md.last_q_modinv, G, C, md.n_power, md.Qp_cur, md.Q_cur,
+                           md.first_Qp, md.first_Q, md.P_size);
+    });
     return hipGetLastError();
 }
 
-hipError_t rns_moddown_extended(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out,
-                                u64 out_stride, const Mod* mods, const u64* half, const u64* half_mod,
-                                const u64* last_q_modinv, int n_power, int Qp_cur, int Q_cur, int first_Qp,
-                                int first_Q, int P_size, int with_ct, int batch, hipStream_t st)
+static void launch_moddown_extended(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out, u64 out_stride,
+                                    const ModDown& md, int with_ct, int galois_elt, int batch, hipStream_t st)
+{
+    dim3 g((1u << md.n_power) / RNS_THREADS, 1, 2 * batch);
+    dispatch_width<2, 4, 8, 16>(md.P_size, [&](auto M) {
+        hipLaunchKernelGGL(k_moddown_extended<M()>, g, dim3(RNS_THREADS), 0, st, in, in_stride, ct, ct_stride, out,
+                           out_stride, md.mods, md.half, md.half_mod, md.last_q_modinv, md.n_power, md.Qp_cur, md.Q_cur,
+                           md.first_Qp, md.first_Q, md.P_size, with_ct, galois_elt);
+    });
+}
+
+hipError_t rns_moddown_extended(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out, u64 out_stride,
+                                const ModDown& md, int with_ct, int batch, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    if (P_size > 15 || P_size < 1) return hipErrorInvalidValue;
-    dim3 g((1u << n_power) / RNS_THREADS, 1, 2 * batch);
-#define LAUNCH(M)                                                                                                    \
-    hipLaunchKernelGGL(k_moddown_extended<M>, g, dim3(RNS_THREADS), 0, st, in, in_stride, ct, ct_stride, out, out_stride, \
-                       mods, half, half_mod, last_q_modinv, n_power, Qp_cur, Q_cur, first_Qp, first_Q, P_size, with_ct,    \
-                       galois_elt)
-#define MODDOWN_EXT_DISPATCH \
-    if (P_size <= 2) LAUNCH(2); \
-    else if (P_size <= 4) LAUNCH(4); \
-    else if (P_size <= 8) LAUNCH(8); \
-    else LAUNCH(16)
-    const int galois_elt = 0;
-    MODDOWN_EXT_DISPATCH;
+    if (md.P_size > 15 || md.P_size < 1) return hipErrorInvalidValue;
+    launch_moddown_extended(in, in_stride, ct, ct_stride, out, out_stride, md, with_ct, 0, batch, st);
     return hipGetLastError();
 }
 
@@ -898,14 +851,7 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_permute(
 #pragma unroll
     for (int r = 0; r < MDP_PER; r++) {
         const u32 idx = idx0 + RNS_THREADS * r;
-        u64 x = xs[r];
-        {
-            u64 l = add_mod(ls[r], half[0], mods[first_Qp - 1].q);
-            l = reduce64(l, m);
-            l = sub_mod(l, half_mod[y], m.q);
-            l = sub_mod(x, l, m.q);
-            x = mul_barrett(l, last_q_modinv[y], m);
-        }
+        u64 x = moddown_step(xs[r], add_mod(ls[r], half[0], mods[first_Qp - 1].q), half_mod[y], last_q_modinv[y], m);
         if (z == 0) x = add_mod(cs[r], x, m.q);
         const u32 raw = idx * (u32) galois_elt;
         const u32 dst = raw & ((1u << n_power) - 1);
@@ -914,31 +860,22 @@ __global__ __launch_bounds__(RNS_THREADS) void k_moddown_permute(
     }
 }
 
-hipError_t rns_moddown_permute(const u64* in, u64 in_stride, const u64* in2, u64 in2_stride, u64* out,
-                               u64 out_stride, const Mod* mods, const u64* half, const u64* half_mod,
-                               const u64* last_q_modinv, int galois_elt, int n_power, int Qp_cur, int Q_cur,
-                               int first_Qp, int first_Q, int P_size, int batch, hipStream_t st)
+hipError_t rns_moddown_permute(const u64* in, u64 in_stride, const u64* in2, u64 in2_stride, u64* out, u64 out_stride,
+                               const ModDown& md, int galois_elt, int batch, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
-    dim3 g((1u << n_power) / (RNS_THREADS * MDP_PER), Q_cur, 2 * batch);
-    if (P_size > 15) return hipErrorInvalidValue;
-    if (P_size == 1)
-        hipLaunchKernelGGL(k_moddown_permute, g, dim3(RNS_THREADS), 0, st, in, in_stride, in2, in2_stride, out,
-                           out_stride, mods, half, half_mod, last_q_modinv, galois_elt, n_power, Qp_cur, Q_cur,
-                           first_Qp, first_Q, P_size);
-    else {
+    if (md.P_size > 15) return hipErrorInvalidValue;
+    if (md.P_size == 1)
+        hipLaunchKernelGGL(k_moddown_permute, dim3((1u << md.n_power) / (RNS_THREADS * MDP_PER), md.Q_cur, 2 * batch),
+                           dim3(RNS_THREADS), 0, st, in, in_stride, in2, in2_stride, out, out_stride, md.mods, md.half,
+                           md.half_mod, md.last_q_modinv, galois_elt, md.n_power, md.Qp_cur, md.Q_cur, md.first_Qp,
+                           md.first_Q, md.P_size);
+    else
         // several special primes: all limbs of a coefficient per thread (k_moddown_extended), the sum with the
         // other ciphertext part (part 0 only) and the permutation on the way out
-        const u64* ct = in2;
-        const u64 ct_stride = in2_stride;
-        const int with_ct = 2;
-        dim3 g((1u << n_power) / RNS_THREADS, 1, 2 * batch);
-        MODDOWN_EXT_DISPATCH;
-    }
+        launch_moddown_extended(in, in_stride, in2, in2_stride, out, out_stride, md, 2, galois_elt, batch, st);
     return hipGetLastError();
 }
-#undef LAUNCH
-#undef MODDOWN_EXT_DISPATCH
 
 // ---------------------------------------------------------------- strided limb copy
 __global__ __launch_bounds__(RNS_THREADS) void k_copy_limbs(const u64* __restrict__ in, u64 in_part_stride,
@@ -1010,15 +947,6 @@ hipError_t rns_copy_diag(const u64* in, u64 in_stride, u64* out, u64 out_stride,
     return hipGetLastError();
 }
 
-// hi:lo += a * b (a, b < 2^61: the running sum of a few dozen such products stays below 2^128)
-__device__ __forceinline__ void acc128(u64& hi, u64& lo, u64 a, u64 b)
-{
-    u64 h, l;
-    mul64wide(a, b, h, l);
-    lo += l;
-    hi += h + (lo < l);
-}
-
 // ---------------------------------------------------------------- BFV BEHZ kernels
 // One thread per coefficient; the per-coefficient vectors (ibase / Bsk
 // residues) must stay in registers, so the kernels are instantiated for a
@@ -1032,7 +960,7 @@ __device__ __forceinline__ void acc128(u64& hi, u64& lo, u64 a, u64 b)
 // zeroed with a wave-uniform select, the inner products run over all MAXB slots (a zero operand adds
 // nothing).  Guarding every slot with `if (i < ib)` instead made the compiler carry the whole register
 // array through a chain of conditional blocks -- 236 registers and one wave per SIMD at MAXB = 16 -- so
-// MAXB is kept close to the real size (behz_slots) and the few wasted products are accepted.
+// MAXB is kept close to the real size (behz_dispatch) and the few wasted products are accepted.
 // SPLIT (launches that leave the chip mostly empty: one ciphertext pair at N = 2^16 is 1024 workgroups of 10 k
 // instructions per thread): the four wavefronts of a workgroup share 64 coefficients; every wavefront repeats the
 // short per-coefficient prologue and takes every fourth row of the base conversion -- four times the threads, a
@@ -1086,22 +1014,16 @@ __global__ __launch_bounds__(RNS_THREADS) void k_fast_convertion(const u64* __re
     }
 }
 
-// padded size for a base of m moduli: steps of 2 up to 16, of 4 up to 32, of 8 up to 64
-static int behz_slots(int m)
+// the kernel instance for a base of m moduli and the split choice: padded sizes in steps of 2 up to 16, of 4 up to 32,
+// of 8 up to 64; f(MAXB, SPLIT), both compile-time
+template <class F>
+static void behz_dispatch(int m, bool split, F&& f)
 {
-    if (m <= 16) return (m + 1) & ~1;
-    if (m <= 32) return (m + 3) & ~3;
-    return (m + 7) & ~7;
+    dispatch_width<2, 4, 6, 8, 10, 12, 14, 16, 20, 24, 28, 32, 40, 48, 56, 64>(m, [&](auto M) {
+        if (split) f(M, std::true_type{});
+        else f(M, std::false_type{});
+    });
 }
-#define BEHZ_DISPATCH(m)                                                                     \
-    switch (behz_slots(m)) {                                                                 \
-        case 2: LAUNCH(2); break;   case 4: LAUNCH(4); break;   case 6: LAUNCH(6); break;    \
-        case 8: LAUNCH(8); break;   case 10: LAUNCH(10); break; case 12: LAUNCH(12); break;  \
-        case 14: LAUNCH(14); break; case 16: LAUNCH(16); break; case 20: LAUNCH(20); break;  \
-        case 24: LAUNCH(24); break; case 28: LAUNCH(28); break; case 32: LAUNCH(32); break;  \
-        case 40: LAUNCH(40); break; case 48: LAUNCH(48); break; case 56: LAUNCH(56); break;  \
-        default: LAUNCH(64); break;                                                          \
-    }
 
 // The split forms when the plain launch has fewer than 320 workgroups (measured, one ciphertext pair, plain / split:
 // N = 2^14 fast_floor 20.2 / 15.3 us, fast_convertion 14.7 / 13.6; N = 2^15 55 / 58, 35 / 39; N = 2^16 288 / 395,
@@ -1118,17 +1040,11 @@ hipError_t rns_fast_convertion(const u64* in1, u64 s1, const u64* in2, u64 s2, u
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (b.ibase_size > BEHZ_MAX || b.obase_size > BEHZ_MAX || b.ibase_size < 1) return hipErrorInvalidValue;
-    if (behz_split(b, n_power, 4, batch)) {
-        dim3 g((1u << n_power) / 64, 4, batch);
-#define LAUNCH(M) hipLaunchKernelGGL((k_fast_convertion<M, true>), g, dim3(RNS_THREADS), 0, st, in1, s1, in2, s2, out, so, b, n_power)
-        BEHZ_DISPATCH(b.ibase_size)
-#undef LAUNCH
-        return hipGetLastError();
-    }
-    dim3 g((1u << n_power) / RNS_THREADS, 4, batch);
-#define LAUNCH(M) hipLaunchKernelGGL((k_fast_convertion<M, false>), g, dim3(RNS_THREADS), 0, st, in1, s1, in2, s2, out, so, b, n_power)
-    BEHZ_DISPATCH(b.ibase_size)
-#undef LAUNCH
+    const bool split = behz_split(b, n_power, 4, batch);
+    const dim3 g((1u << n_power) / (split ? 64 : RNS_THREADS), 4, batch);
+    behz_dispatch(b.ibase_size, split, [&](auto M, auto S) {
+        hipLaunchKernelGGL((k_fast_convertion<M(), S()>), g, dim3(RNS_THREADS), 0, st, in1, s1, in2, s2, out, so, b, n_power);
+    });
     return hipGetLastError();
 }
 
@@ -1221,20 +1137,13 @@ hipError_t rns_fast_floor(const u64* in, u64 si, u64* out, u64 so, const BehzDev
     if (b.ibase_size > BEHZ_MAX || b.obase_size > BEHZ_MAX || b.ibase_size < 1 || b.obase_size < 2)
         return hipErrorInvalidValue;
     const int m = b.ibase_size > b.obase_size - 1 ? b.ibase_size : b.obase_size - 1;
-    if (behz_split(b, n_power, 3, batch)) {
-        dim3 g((1u << n_power) / 64, 3, batch);
-#define LAUNCH(M) hipLaunchKernelGGL((k_fast_floor<M, true>), g, dim3(RNS_THREADS), 0, st, in, si, out, so, b, n_power)
-        BEHZ_DISPATCH(m)
-#undef LAUNCH
-        return hipGetLastError();
-    }
-    dim3 g((1u << n_power) / RNS_THREADS, 3, batch);
-    // the 28-slot instance comes out of the register allocator at 256 registers (one wave per SIMD), the 32-slot one
-    // at 250 (two): bases of 25..28 take the larger one (surplus slots hold zeros)
-    const int m_plain = (behz_slots(m) == 28) ? 29 : m;
-#define LAUNCH(M) hipLaunchKernelGGL((k_fast_floor<M, false>), g, dim3(RNS_THREADS), 0, st, in, si, out, so, b, n_power)
-    BEHZ_DISPATCH(m_plain)
-#undef LAUNCH
+    const bool split = behz_split(b, n_power, 3, batch);
+    const dim3 g((1u << n_power) / (split ? 64 : RNS_THREADS), 3, batch);
+    // plain form: the 28-slot instance comes out of the register allocator at 256 registers (one wave per SIMD), the
+    // 32-slot one at 250 (two): bases of 25..28 take the larger one (surplus slots hold zeros)
+    behz_dispatch(!split && m > 24 && m <= 28 ? 29 : m, split, [&](auto M, auto S) {
+        hipLaunchKernelGGL((k_fast_floor<M(), S()>), g, dim3(RNS_THREADS), 0, st, in, si, out, so, b, n_power);
+    });
     return hipGetLastError();
 }
 
@@ -1288,10 +1197,10 @@ __global__ __launch_bounds__(RNS_THREADS) void k_ckks_diag_mac(const u64* __rest
         }
 #pragma unroll
         for (int i = 0; i < N1; i++) { // an absent entry adds zeros: no branch around the accumulators
-            acc_mad(h[0], l[0], d[i].x, r0[i].x);
-            acc_mad(h[1], l[1], d[i].y, r0[i].y);
-            acc_mad(h[2], l[2], d[i].x, r1[i].x);
-            acc_mad(h[3], l[3], d[i].y, r1[i].y);
+            acc128(h[0], l[0], d[i].x, r0[i].x);
+            acc128(h[1], l[1], d[i].y, r0[i].y);
+            acc128(h[2], l[2], d[i].x, r1[i].x);
+            acc128(h[3], l[3], d[i].y, r1[i].y);
         }
         ulonglong2 o0, o1;
         o0.x = reduce128(h[0], l[0], m);
@@ -1319,17 +1228,10 @@ hipError_t rns_ckks_diag_mac(const u64* rot, u64 rot_stride, int n1, const u64* 
             ix.v[j * w + i] = at;
         }
     const dim3 g = grid3(n_power, limbs, batch);
-#define LAUNCH(W)                                                                                                     \
-    hipLaunchKernelGGL(k_ckks_diag_mac<W>, g, dim3(RNS_THREADS), 0, st, rot, rot_stride, diags, ix, out, out_stride,  \
-                       mods, n_power, limbs, n1, n2)
-    switch (w) {
-        case 1: LAUNCH(1); break;
-        case 2: LAUNCH(2); break;
-        case 4: LAUNCH(4); break;
-        case 8: LAUNCH(8); break;
-        default: LAUNCH(16); break;
-    }
-#undef LAUNCH
+    dispatch_width<1, 2, 4, 8, 16>(w, [&](auto W) {
+        hipLaunchKernelGGL(k_ckks_diag_mac<W()>, g, dim3(RNS_THREADS), 0, st, rot, rot_stride, diags, ix, out, out_stride,
+                           mods, n_power, limbs, n1, n2);
+    });
     return hipGetLastError();
 }
 

@@ -48,43 +48,43 @@ hipError_t rns_base_conversion_DtoQtilde(const u64* in, u64 in_stride, u64* out,
                                          const int* I_location, int n_power, int d, int rc, int l, int level,
                                          int max_cnt /* widest digit */, int batch, hipStream_t st);
 
+// One mod-down (division by the special primes, or by the last ciphertext prime in a rescale, with rounding) as the
+// launchers below take it; Context::moddown / Context::rescale_moddown build it for a depth.  Host only: the kernels
+// take the members as scalar arguments.
+struct ModDown {
+    const Mod* mods;                           // the Q' chain (DEVICE, like the three tables)
+    const u64 *half, *half_mod, *last_q_modinv; // per divisor: half of it, that modulo each remaining limb, its inverse there
+    int n_power;
+    int Qp_cur, Q_cur;     // limbs per part of the input / of the result
+    int first_Qp, first_Q; // the same at depth 0: the divisors are moduli first_Qp - 1, first_Qp - 2, ... (row widths of the tables)
+    int P_size;            // number of divisors
+};
+
 // first half of the multi-prime mod-down in its NTT-domain form (context.cpp m2_md_*; ops.cpp ckks_moddown_multi)
-hipError_t rns_moddown_multi_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods,
-                                       const u64* half, const u64* half_mod, const u64* last_q_modinv, const u64* G,
-                                       const u64* C, int n_power, int Qp_cur, int Q_cur, int first_Qp, int first_Q,
-                                       int P_size, int batch, hipStream_t st);
+hipError_t rns_moddown_multi_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const ModDown& md,
+                                       const u64* G, const u64* C, int batch, hipStream_t st);
 // reference switchkey.cu:480-611 / 1222-1282 (mod-down by P_size primes);
 // with_ct: 0 none, 1 both parts, 2 part 0 only
-hipError_t rns_moddown_extended(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out,
-                                u64 out_stride, const Mod* mods, const u64* half, const u64* half_mod,
-                                const u64* last_q_modinv, int n_power, int Qp_cur, int Q_cur, int first_Qp,
-                                int first_Q, int P_size, int with_ct, int batch, hipStream_t st);
+hipError_t rns_moddown_extended(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out, u64 out_stride,
+                                const ModDown& md, int with_ct, int batch, hipStream_t st);
 
 // reference switchkey.cu:400-478 (switchkey != 0: ct added to part 0 only)
-hipError_t rns_divide_round_lastq(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride,
-                                  u64* out, u64 out_stride, const Mod* mods, const u64* half,
-                                  const u64* half_mod, const u64* last_q_modinv, int n_power,
-                                  int decomp, int switchkey, int batch, hipStream_t st);
+hipError_t rns_divide_round_lastq(const u64* in, u64 in_stride, const u64* ct, u64 ct_stride, u64* out,
+                                  u64 out_stride, const ModDown& md, int switchkey, int batch, hipStream_t st);
 
 // reference switchkey.cu:678-705
-hipError_t rns_moddown_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride,
-                                 const Mod* mods, const u64* half, const u64* half_mod, int n_power,
-                                 int first_decomp, int cur_decomp, int batch, hipStream_t st);
+hipError_t rns_moddown_stage_one(const u64* in, u64 in_stride, u64* out, u64 out_stride, const ModDown& md, int batch,
+                                 hipStream_t st);
 
-// reference switchkey.cu:707-771 (ct may alias out); with_ct: 0 none (rescale,
+// reference switchkey.cu:707-771 (ct may alias out; in: Qp_cur limbs per part); with_ct: 0 none (rescale,
 // switchkey.cu:792-815), 1 both parts, 2 part 0 only (switchkey variant)
-hipError_t rns_moddown_stage_two(const u64* in_last, u64 last_stride, const u64* in, u64 in_stride,
-                                 int in_limbs, const u64* ct, u64 ct_stride, u64* out,
-                                 u64 out_stride, const Mod* mods, const u64* last_q_modinv,
-                                 int n_power, int cur_decomp, int with_ct, int batch,
+hipError_t rns_moddown_stage_two(const u64* in_last, u64 last_stride, const u64* in, u64 in_stride, const u64* ct,
+                                 u64 ct_stride, u64* out, u64 out_stride, const ModDown& md, int with_ct, int batch,
                                  hipStream_t st);
 
 // reference switchkey.cu:1621-1813 (mod-down by P_size primes + Galois permute)
-hipError_t rns_moddown_permute(const u64* in, u64 in_stride, const u64* in2, u64 in2_stride,
-                               u64* out, u64 out_stride, const Mod* mods, const u64* half,
-                               const u64* half_mod, const u64* last_q_modinv, int galois_elt,
-                               int n_power, int Qp_cur, int Q_cur, int first_Qp, int first_Q,
-                               int P_size, int batch, hipStream_t st);
+hipError_t rns_moddown_permute(const u64* in, u64 in_stride, const u64* in2, u64 in2_stride, u64* out, u64 out_stride,
+                               const ModDown& md, int galois_elt, int batch, hipStream_t st);
 
 // plain strided copy of `limbs` limbs x `parts` parts (switchkey.cu:776-790,
 // bfv_duplicate's c0 copy)

@@ -652,6 +652,69 @@ def test_kernel_base_conversion_DtoQtilde(hg, oracle, torch, depth):
             assert np.array_equal(got[b], w), (P, depth, b)
 
 
+@pytest.fixture(scope="module")
+def five_special_primes(hg, oracle, torch):
+    """CKKS N = 2^12, six ciphertext and five special primes of 36 bits: the widths between four and eight, which the
+    mod-down and base-conversion kernels serve with their 8-wide instances."""
+    return _ckks(hg, oracle, 4096, [36] * 6, [36] * 5, sec=hg.SEC_NONE)
+
+
+@pytest.mark.parametrize("depth", [0, 1])
+def test_kernel_divide_round_lastq_extended_five_special_primes(hg, oracle, torch, five_special_primes, depth):
+    """hegpu_divide_round_lastq_extended, modes 0 / 1 / 2, with five special primes (the 8-wide instance of the chain
+    among the special primes, three of its slots padding)."""
+    c, o, primes = five_special_primes
+    n, Q, Qp = 4096, c.Q_size, c.Q_prime_size
+    assert (Q, c.P_size) == (6, 5)
+    l, rc, batch = Q - depth, Qp - depth, 2
+    src = [_limbs(oracle, primes, (list(range(l)) + list(range(Q, Qp))) * 2, n, 33 + b) for b in range(batch)]
+    for s_ in src:
+        s_[:3] = [0, primes[0] - 1, primes[0] // 2]
+        for k in range(Q, Qp):  # every special limb at its corners
+            at = (l + k - Q) * n
+            s_[at:at + 3] = [0, primes[k] - 1, primes[k] // 2]
+    cts = [synth_ct(primes, range(l), 2, n, 44 + b) for b in range(batch)]
+    out = torch.empty(batch * 2 * l * n, dtype=torch.int64, device="cuda")
+    for mode in (0, 1, 2):
+        c.divide_round_lastq_extended(hg.to_device(np.concatenate(src)), 2 * rc * n, hg.to_device(np.concatenate(cts)),
+                                      2 * l * n, out, 2 * l * n, mode, depth, batch)
+        torch.cuda.synchronize()
+        got = hg.to_host(out).reshape(batch, -1)
+        for b in range(batch):
+            w = np.zeros(2 * l * n, dtype=np.uint64)
+            o.L.o_divide_round_lastq_extended(o.h, src[b].ctypes.data, cts[b].ctypes.data, w.ctypes.data, rc, l, mode)
+            assert np.array_equal(got[b], w), (depth, mode, b)
+
+
+@pytest.mark.parametrize("depth", [0, 1])
+def test_kernel_divide_round_lastq_permute_five_special_primes(hg, oracle, torch, five_special_primes, depth):
+    """hegpu_divide_round_lastq_permute with five special primes: the same 8-wide instance with the permutation and the
+    sum with part 0 on the way out."""
+    c, o, primes = five_special_primes
+    _permute_case(hg, oracle, torch, c, o, primes, 4096, depth, hg.steps_to_galois_elt(1, 4096, 5))
+
+
+@pytest.mark.parametrize("depth", [0, 1])
+def test_kernel_base_conversion_DtoQtilde_five_wide_digits(hg, oracle, torch, five_special_primes, depth):
+    """hegpu_base_conversion_DtoQtilde with digits of five primes (the 8-wide instance): a full digit and a digit of one
+    prime at depth 0, one full digit at depth 1."""
+    c, o, primes = five_special_primes
+    n, Q, P = 4096, c.Q_size, c.P_size
+    l, rc, batch = Q - depth, Q + P - depth, 2
+    d = -(-l // P)
+    src = [_limbs(oracle, primes, range(l), n, 21 + b) for b in range(batch)]
+    for s in src:
+        s[:3] = [0, primes[0] - 1, primes[0] // 2]
+    out = torch.empty(batch * d * rc * n, dtype=torch.int64, device="cuda")
+    c.base_conversion_DtoQtilde(hg.to_device(np.concatenate(src)), l * n, out, d * rc * n, depth, batch)
+    torch.cuda.synchronize()
+    got = hg.to_host(out).reshape(batch, -1)
+    for b in range(batch):
+        w = np.zeros(d * rc * n, dtype=np.uint64)
+        o.L.o_base_conversion_DtoQtilde(o.h, src[b].ctypes.data, w.ctypes.data, depth)
+        assert np.array_equal(got[b], w), (depth, b)
+
+
 def test_kernel_fast_convertion_and_fast_floor(hg, oracle, torch):
     """hegpu_fast_convertion / hegpu_fast_floor (BEHZ, multiplication.cu:10-100, 128-272) on their own,
     N=2^12 default chain (Bsk = 3 primes of 61 bits) and N=2^13 (Q=4)."""
