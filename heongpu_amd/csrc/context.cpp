@@ -622,6 +622,8 @@ static hipError_t build_plan(NttPlan& p, const vec& mods, const vec& fwd, const 
     for (int k = 0; k < cnt; k++) (hm[k].fp ? p.has_fp : p.has_int) = 1;
     p.fp.assign(cnt, 0);
     for (int k = 0; k < cnt; k++) p.fp[k] = hm[k].fp ? 1 : 0;
+    p.bits.assign(cnt, 0);
+    for (int k = 0; k < cnt; k++) p.bits[k] = (unsigned char) hm[k].bit;
     // Correction-free forward butterflies add at most 4q to the bound of a value per stage (ntt.hip: ct_bfly_cs), so a
     // modulus may skip every conditional subtraction when in + 4 * log2(N) * q stays below 2^64; `in` is at most twice
     // the largest modulus of the plan (canonical inputs, or digits that are residues of another prime of the plan).

@@ -55,7 +55,8 @@ HG_HD void mul64wide(u64 a, u64 b, u64& hi, u64& lo)
     hi = p11;
 }
 
-// hi:lo += a * b (a, b < 2^61: the running sum of a few dozen such products stays below 2^128)
+// hi:lo += a * b for any 64-bit a, b; the caller keeps the running sum below 2^128 (ks_row_mac: a digit below B q times
+// a key residue below q, digits * B * q * q < 2^128 -- ks_unreduced_exit in ntt.hpp; reduce128 takes any such sum)
 HG_HD void acc128(u64& hi, u64& lo, u64 a, u64 b)
 {
     u64 h, l;

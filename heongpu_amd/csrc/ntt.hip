@@ -270,21 +270,28 @@ __device__ __forceinline__ u64 shoup_full(u64 y, ulonglong2 w, const QC& c)
 // (b + 4) q.  A modulus below 2^61 has room for 8 q -- a correction (csub by 4q: [0, 8q) -> [0, 4q)) in every butterfly
 // of every stage (NTT_CS_EVERY).  A modulus below 2^60 has room for 16 q: from the [0, 8q) a pass is
 // handed, two stages run without a correction (8 -> 12 -> 16 q), then one csub by 8q brings [0, 16q) (or [0, 12q)) back
-// to [0, 8q) and the next two stages run free again.  A pass hands over [0, 8q) as before (what the row pass, the
-// canonicalisation in front of the 128-bit inner product and the final csub chain of the row pass assume), so its LAST
-// stage needs u < 4q: csub by 8q and by 4q there.  Eight stages from [0, 8q): corrections before stages 2, 4, 6 (8q)
-// and 7 (8q, 4q) -- five per coefficient pair instead of eight; the bound chain is 8, 12, 16 | 8, 12, 16 | 8, 12, 16 |
-// 8, 12 | 4, 8.  The schedule is computed at compile time from the room (units of q) and the number of stages: bit s of
-// c8 / c4 = csub by 8q / by 4q (in that order) before local stage s.  The entry bound stays 8 q, not the q of a
+// to [0, 8q) and the next two stages run free again.  What the LAST stage does depends on who takes the pass's output,
+// the exit bound `exit_b` (units of q): its upper input has to be below (exit_b - 4) q.
+//   exit_b = 8: the column pass (for the row pass), ntt_fwd_row, the transform entry points and the mod-down tail's T,
+//     whose csub chain (4q, 2q, q) to the canonical residue assumes [0, 8q).  The last stage needs u < 4q: csub by 8q
+//     and by 4q there.  Eight stages from [0, 8q): corrections before stages 2, 4, 6 (8q) and 7 (8q, 4q) -- five per
+//     coefficient pair instead of eight; the bound chain is 8, 12, 16 | 8, 12, 16 | 8, 12, 16 | 8, 12 | 4, 8.
+//   exit_b = 12 / 16: a key-switch digit that goes into the 128-bit inner product as it is (ks_row_digit's EXIT;
+//     ks_unreduced_exit decides on the host whether the sum has the room).  12: the csub by 4q before stage 7 goes,
+//     8, 12, 16 | 8, 12, 16 | 8, 12, 16 | 8, 12 | 8, 12.  16: stage 7 is a stage like any other, corrections before
+//     stages 2, 4, 6 only -- three per pair -- 8, 12, 16 | 8, 12, 16 | 8, 12, 16 | 8, 12, 16.
+// The schedule is computed at compile time from the room (units of q), the number of stages and the exit bound: bit s
+// of c8 / c4 = csub by 8q / by 4q (in that order) before local stage s.  The entry bound stays 8 q, not the q of a
 // canonical input: decomposing launches feed digits of other primes (up to 8 q, fwd_col_body) and the transform entry
 // points have always taken any input below 8 q.
 struct CsSched { unsigned c8, c4; };
-__host__ __device__ constexpr CsSched cs_sched(int stages, int room)
+__host__ __device__ constexpr CsSched cs_sched(int stages, int room, int exit_b = 8)
 {
     CsSched r{0u, 0u};
     int b = 8;
     for (int s = 0; s < stages; s++) {
-        const int need = (s == stages - 1) ? 4 : room - 4; // u + 4q inside the room; the last stage hands over [0, 8q)
+        // u + 4q inside the room; the last stage hands over [0, exit_b q) (never more than the room)
+        const int need = (s == stages - 1 && exit_b < room) ? exit_b - 4 : room - 4;
         if (b > need && b > 8) {
             r.c8 |= 1u << s;
             b = 8; // [0, 16q) -> [0, 8q)
@@ -300,6 +307,9 @@ __host__ __device__ constexpr CsSched cs_sched(int stages, int room)
 static_assert(cs_sched(8, 8).c8 == 0u && cs_sched(8, 8).c4 == 0xFFu, "61-bit moduli: a correction in every stage");
 static_assert(cs_sched(8, 16).c8 == 0xD4u && cs_sched(8, 16).c4 == 0x80u, "60-bit moduli: stages 2, 4, 6, 7 / 7");
 static_assert(cs_sched(5, 16).c8 == 0x14u && cs_sched(5, 16).c4 == 0x10u, "N = 2^13 column pass: stages 2, 4 / 4");
+static_assert(cs_sched(8, 16, 12).c8 == 0xD4u && cs_sched(8, 16, 12).c4 == 0u, "60-bit digit, exit 12 q: stages 2, 4, 6, 7 / none");
+static_assert(cs_sched(8, 16, 16).c8 == 0x54u && cs_sched(8, 16, 16).c4 == 0u, "60-bit digit, exit 16 q: stages 2, 4, 6 / none");
+static_assert(cs_sched(8, 8, 8).c8 == 0u && cs_sched(8, 8, 8).c4 == 0xFFu, "61-bit digit: the schedule has no slack, only the chain goes");
 // the butterfly with the corrections of one stage: cs bit 1 = csub by 8q, bit 0 = csub by 4q (a constant after unrolling)
 __device__ __forceinline__ void ct_bfly_cs(u64& x, u64& y, ulonglong2 w, const QC& c, int cs)
 {
@@ -1110,12 +1120,28 @@ __global__ __launch_bounds__(16 << S1, 4) void ntt_fwd_single(NttArgs a)
 }
 
 // ------------------------------------------------------------------ fused row pass + key-switch MAC
-template <bool LAZY, int ROOM = 8>
+// The 128-bit inner product of the integer moduli takes a digit's transform as the last stage leaves it -- reduce128
+// is exact for ANY 128-bit sum, and the residue of the sum does not depend on which representative of a digit went
+// in -- if the sum fits: digits * B * q * q < 2^128 for the exit bound B (units of q) of the row stages and canonical
+// key residues (< q).  Decided once per launch on the host (KsMacArgs::unreduced_exit, ops.cpp: keyswitch_ntt_mac) from
+// the largest number of digits a workgroup sums (all of them, or its share of a split launch) and the largest integer
+// modulus of the launch (ks_unreduced_exit, ntt.hpp): the largest B of 16, 12, 8 that fits, or 0 -- the digits are
+// then brought down to [0, q) as before (e.g. 9 or more digits of a 61-bit prime).  A 60-bit modulus (room 16) leaves
+// 16 q, 12 q or 8 q (cs_sched's exit bound), a 61-bit one 8 q.  The flag is wave-uniform; q * q is rounded up to a
+// power of two (the bit length of q).  Identity digits are canonical anyway.
+static_assert(ks_unreduced_exit(16, 60) == 16 && ks_unreduced_exit(17, 60) == 12 && ks_unreduced_exit(21, 60) == 12, "");
+static_assert(ks_unreduced_exit(22, 60) == 8 && ks_unreduced_exit(32, 60) == 8 && ks_unreduced_exit(33, 60) == 0, "");
+static_assert(ks_unreduced_exit(4, 61) == 16 && ks_unreduced_exit(8, 61) == 8 && ks_unreduced_exit(9, 61) == 0, "");
+
+// EXIT: 0 = the digit ends canonical (the mod-down tail's T: ks_tail_store's sub_mod needs that; digits whose sum
+// would not fit); 8 / 12 / 16 = it goes on un-reduced, below EXIT q (correcting branch only; 12 / 16 need ROOM 16).
+template <bool LAZY, int ROOM = 8, int EXIT = 0>
 __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict__ p, u64* lds,
                                              const ulonglong2* twa, const ulonglong2* __restrict__ tb,
                                              const QC& qc, const Mod& md, int row, int i0)
 {
-    constexpr CsSched CS = cs_sched(8, ROOM);
+    static_assert(EXIT == 0 || (!LAZY && (EXIT == 8 || ((EXIT == 12 || EXIT == 16) && ROOM == 16))), "exit bound");
+    constexpr CsSched CS = cs_sched(8, ROOM, EXIT ? EXIT : 8);
 #pragma unroll
     for (int k = 0; k < 16; k++) x[k] = gld(&p[row * 256 + i0 + 16 * k]);
     // first four stages: the row's 15 twiddles from LDS (slot (1 << s) - 1 + b at [slot][row])
@@ -1140,13 +1166,14 @@ __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict
         x[2 * k + 1] = v.y;
     }
     ct_radix16_tb<LAZY, (CS.c8 >> 4), (CS.c4 >> 4)>(x, tb, qc);
-    if (!LAZY) {
-        // bring [0,8q) down to [0,q) so that 64 products stay below 2^128
+    if (!LAZY && EXIT == 0) {
+        // bring [0,8q) down to [0,q): the tail's T, and digits whose sum would pass 2^128 un-reduced (ks_unreduced_exit)
 #pragma unroll
         for (int k = 0; k < 16; k++) x[k] = csub(csub(csub(x[k], qc.q4), 2 * qc.q), qc.q);
     }
     // LAZY: the transform output stays un-reduced (any 64-bit value); the caller checked that
     // digits * 2^64 * q fits the 128-bit accumulator, the one exact reduction happens on the sum.
+    // EXIT: un-reduced below EXIT q, the host checked digits * EXIT * q * q < 2^128.
     wave_lds_fence();
 #pragma unroll
     for (int k = 0; k < 8; k++)
@@ -1316,6 +1343,8 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
     // the un-reduced output (any 64-bit value) times a key residue (< q) summed over the digits has to fit 128 bits
     const bool lazy = row_stages_lazy(md, a.lazy_q_max) && md.q <= ~0ull / (u64) a.digits;
     const bool room16 = stages_room16(md);
+    // correcting digits un-reduced into the sum: the launch's bound (wave-uniform; see ks_unreduced_exit)
+    const int ex = a.unreduced_exit;
     // digit-invariant twiddles of the first four stages, shared by the 16 lanes of a row (see
     // ks_row_mac_fp; the per-lane ones of the last four stages would need 61 KiB as pairs)
     ulonglong2* twa = reinterpret_cast<ulonglong2*>(twbuf); // [15 * 16]
@@ -1341,9 +1370,13 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
         } else if (lazy) {
             ks_row_digit<true>(x, p, lds, twa, tb, qc, md, row, i0);
         } else if (room16) {
-            ks_row_digit<false, 16>(x, p, lds, twa, tb, qc, md, row, i0);
+            if (ex == 16) ks_row_digit<false, 16, 16>(x, p, lds, twa, tb, qc, md, row, i0);
+            else if (ex == 12) ks_row_digit<false, 16, 12>(x, p, lds, twa, tb, qc, md, row, i0);
+            else if (ex == 8) ks_row_digit<false, 16, 8>(x, p, lds, twa, tb, qc, md, row, i0);
+            else ks_row_digit<false, 16>(x, p, lds, twa, tb, qc, md, row, i0);
         } else {
-            ks_row_digit<false>(x, p, lds, twa, tb, qc, md, row, i0);
+            if (ex) ks_row_digit<false, 8, 8>(x, p, lds, twa, tb, qc, md, row, i0);
+            else ks_row_digit<false>(x, p, lds, twa, tb, qc, md, row, i0);
         }
         const u64* k0 = pk + key_off2 * i;
         const u64* k1 = k0 + key_off1;
@@ -1355,7 +1388,7 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
     }
     if constexpr (MD) {
         // mod-down tail (see ks_row_mac_fp_body); T comes from a column pass like the digits', its row stages end
-        // canonical as in ntt_fwd_row
+        // canonical as in ntt_fwd_row (EXIT 0: ks_tail_store subtracts T with sub_mod)
         u64 acc0[16], acc1[16];
 #pragma unroll
         for (int k = 0; k < 16; k++) {

@@ -221,6 +221,9 @@ struct KsMacArgs {
     // The grids run over the limb slots [slot_first, slot_first + slot_count) only (slot_count 0: all rc slots);
     // int_slots then lists only the integer slots of that range.
     int slot_first, slot_count;
+    // Integer moduli on the correcting butterflies: the digits' transforms enter the 128-bit sums un-reduced, below
+    // unreduced_exit * q (ks_unreduced_exit of the launch: 16, 12 or 8), or canonical (0).
+    int unreduced_exit;
     // Optional mod-down tail (method I, one special prime P; the counterpart of NttEpilogue): the accumulated limb acc
     // of part p, slot k (modulus q_k) is not stored; instead
     //     out = (acc - T) * inv[q_k] + ct   (ct for parts below ct_parts only; 0: every part)
@@ -242,5 +245,17 @@ struct KsMacArgs {
     } tail;
 };
 hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st);
+// The bound (units of q) below which the row stages of a correcting integer modulus may leave a key-switch digit for
+// the 128-bit inner product: the largest B of 16, 12, 8 with digits * B * q * q < 2^128 for every q < 2^q_bits (key
+// residues canonical), 0 if there is none.  `digits`: the most a workgroup sums; `q_bits`: bit length of the launch's
+// largest integer modulus (0: unknown).
+constexpr inline int ks_unreduced_exit(int digits, int q_bits)
+{
+    if (digits <= 0 || q_bits <= 0 || 2 * q_bits > 127) return 0;
+    const unsigned __int128 room = ((unsigned __int128) 1 << (128 - 2 * q_bits)); // digits * B <= room: sum < 2^128
+    for (int b = 16; b >= 8; b -= 4)
+        if ((unsigned __int128) digits * (unsigned) b <= room) return b;
+    return 0;
+}
 
 } // namespace hegpu

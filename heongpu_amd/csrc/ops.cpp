@@ -89,6 +89,28 @@ static void fill_int_slots(const Context& c, NttArgs& a, const u64* order)
     a.int_slot_count = cnt ? cnt : -1;
 }
 
+// Bit length of the largest modulus on the integer butterflies among the target slots [slot_first, slot_first +
+// slot_count) (0: all rc) of a key-switch launch at `depth`, 0 if it has none.  The slot order is read from the host
+// copy of the table `order` points into (CKKS: new_prime_locations; null: slot k is modulus k); an order this does not
+// know counts every integer modulus of the chain, which only makes the bound of ks_unreduced_exit more careful.
+static int launch_int_q_bits(const Context& c, const int* order, int rc, int depth, int slot_first, int slot_count)
+{
+    const NttPlan& p = c.plan_qp;
+    const u64* ho = nullptr;
+    const size_t off = (size_t) triangle_offset(c.Qp_size, depth);
+    if (order && order == c.tab.new_prime_locations + off && off + (size_t) rc <= c.hv.new_prime_locations.size())
+        ho = c.hv.new_prime_locations.data() + off;
+    int bits = 0;
+    auto take = [&](size_t m) { if (m < p.bits.size() && !p.fp[m] && p.bits[m] > bits) bits = p.bits[m]; };
+    if (order && !ho) {
+        for (size_t m = 0; m < p.bits.size(); m++) take(m);
+        return bits;
+    }
+    const int k0 = slot_count ? slot_first : 0, k1 = slot_count ? slot_first + slot_count : rc;
+    for (int k = k0; k < k1; k++) take(ho ? (size_t) ho[k] : (size_t) k);
+    return bits;
+}
+
 // Forward NTT of the key-switch digits followed by the inner product with the
 // key.  `a` is the fully configured forward transform (plain or decomposing)
 // whose output is [digits][rc][N] per ciphertext at a.out; the result
@@ -143,6 +165,9 @@ static hipError_t keyswitch_ntt_mac(const Context& c, NttArgs a, const u64* key,
         k.int_slot_count = a.int_slot_count > 0 ? a.int_slot_count : 0;
         for (int q = 0; q < 8; q++) k.int_slots[q] = a.int_slots[q];
         k.slot_first = slot_first; k.slot_count = slot_count;
+        // the most digits one workgroup sums: all of them, or the largest range of a split launch (ks_index: d0, d1)
+        k.unreduced_exit = ks_unreduced_exit(splits > 1 ? (digits + splits - 1) / splits : digits,
+                                             launch_int_q_bits(c, a.mod_order, rc, level, slot_first, slot_count));
         if (slot_count && a.int_slot_count > 0) { // the integer slots of the range
             int cnt = 0;
             for (int q = 0; q < a.int_slot_count; q++)
