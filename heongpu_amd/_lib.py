@@ -31,6 +31,15 @@ class LinearFactor(ctypes.Structure):
                 ("giant_keys", ctypes.POINTER(ctypes.c_void_p)), ("giant_elts", ctypes.POINTER(c_int))]
 
 
+class PolyStep(ctypes.Structure):
+    """hegpu_poly_step: one step of a polynomial-evaluation plan (hegpu_poly_eval_plan_fill)"""
+    _fields_ = [("kind", ctypes.c_int32), ("dst", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32),
+                ("c", ctypes.c_int32), ("level", ctypes.c_int32), ("mul_level", ctypes.c_int32),
+                ("rescale_first", ctypes.c_int32), ("rescale_after", ctypes.c_int32), ("n_terms", ctypes.c_int32),
+                ("term_reg", ctypes.c_int32 * 15), ("scale", ctypes.c_double), ("tail_const", ctypes.c_double),
+                ("w0", ctypes.c_double * 2), ("w", (ctypes.c_double * 2) * 15)]
+
+
 # (name, restype, argtypes) -- must list EVERY symbol of include/hegpu.h
 SIGNATURES = [
     ("hegpu_last_error", ctypes.c_char_p, []),
@@ -104,6 +113,20 @@ SIGNATURES = [
     ("hegpu_encoding_transform_shape", c_int,
      [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     ("hegpu_encoding_transform_fill", c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), voidp]),
+    ("hegpu_poly_eval_plan_size", c_int,
+     [c_int, voidp, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(u64), c_int,
+      ctypes.POINTER(c_int)]),
+    ("hegpu_poly_eval_plan_fill", c_int,
+     [c_int, voidp, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(u64), c_int,
+      ctypes.POINTER(PolyStep), c_int]),
+    ("hegpu_ckks_weighted_sum", c_int,
+     [voidp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double),
+      c_int, ctypes.c_double, ctypes.c_double, u64p, u64, c_int, c_int, voidp]),
+    ("hegpu_ckks_double_sub", c_int,
+     [voidp, u64p, u64, c_int, u64p, u64, c_int, ctypes.c_double, u64p, u64, c_int, c_int, voidp]),
+    ("hegpu_ckks_poly_eval_workspace_bytes", c_size_t, [voidp, ctypes.POINTER(PolyStep), c_int, c_int, c_int]),
+    ("hegpu_ckks_poly_eval", c_int,
+     [voidp, u64p, u64, u64p, u64, ctypes.POINTER(PolyStep), c_int, u64p, c_int, c_int, voidp, c_size_t, voidp]),
     ("hegpu_ckks_conj_split", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64p, u64, c_int, c_int, c_int, voidp]),
     ("hegpu_ckks_conj_merge", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64, c_int, c_int, c_int, voidp]),
     ("hegpu_ckks_encoding_transform_workspace_bytes", c_size_t, [voidp, ctypes.POINTER(LinearFactor), c_int, c_int, c_int]),

@@ -387,6 +387,32 @@ class Context:
         _check(self._lib.hegpu_ckks_conj_merge(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, depth, out_depth, batch,
                                                stream if stream is not None else _stream()))
 
+    def ckks_weighted_sum(self, terms, strides, term_limbs, weights, w0, out, so, limbs, batch=1, stream=None):
+        """hegpu_ckks_weighted_sum: out = w0 + sum_k weights[k] * terms[k] on the first `limbs` limbs.  terms: device tensors
+        [2][term_limbs[k]][N] per item; weights / w0: complex numbers whose parts are rounded to integers"""
+        k = len(terms)
+        tp = (ctypes.c_void_p * max(k, 1))(*[_ptr(t) for t in terms])
+        ts = (ctypes.c_uint64 * max(k, 1))(*[int(v) for v in strides])
+        tl = (ctypes.c_int * max(k, 1))(*[int(v) for v in term_limbs])
+        tw = (ctypes.c_double * max(2 * k, 1))(*[v for w in weights for v in (complex(w).real, complex(w).imag)])
+        _check(self._lib.hegpu_ckks_weighted_sum(self._h, tp, ts, tl, tw, k, complex(w0).real, complex(w0).imag, _ptr(out),
+                                                 so, limbs, batch, stream if stream is not None else _stream()))
+
+    def ckks_double_sub(self, a, a_stride, a_limbs, b, b_stride, b_limbs, value, out, so, limbs, batch=1, stream=None):
+        """hegpu_ckks_double_sub: out = 2 a - b on the first `limbs` limbs; b None: round(value) leaves part 0 instead"""
+        _check(self._lib.hegpu_ckks_double_sub(self._h, _ptr(a), a_stride, a_limbs, _ptr(b), b_stride, b_limbs, float(value),
+                                               _ptr(out), so, limbs, batch, stream if stream is not None else _stream()))
+
+    def poly_eval_workspace_bytes(self, plan, depth, batch):
+        return int(self._lib.hegpu_ckks_poly_eval_workspace_bytes(self._h, plan.steps, len(plan.steps), depth, batch))
+
+    def ckks_poly_eval(self, ct, cs, out, so, plan, relin_key, depth, batch, ws, stream=None):
+        """hegpu_ckks_poly_eval: executes a PolyEvalPlan (poly_eval_plan) made for the level Q - 1 - depth; the result is
+        at depth Q - 1 - plan.level and scale plan.scale"""
+        _check(self._lib.hegpu_ckks_poly_eval(self._h, _ptr(ct), cs, _ptr(out), so, plan.steps, len(plan.steps),
+                                              _ptr(relin_key), depth, batch, _ptr(ws), ws.numel() * 8,
+                                              stream if stream is not None else _stream()))
+
     @staticmethod
     def linear_factors(factors):
         """the hegpu_linear_factor array of a sequence entry.  factors: one (diags, n_diag, index, baby_keys, baby_elts,
@@ -991,6 +1017,38 @@ def encoding_transform_factors(n, inverse, pieces):
                                                  values.ctypes.data))
         out.append(EncodingTransformPiece(strides[p], stages[p], list(offsets), values))
     return out
+
+
+MONOMIAL, CHEBYSHEV = 0, 1
+POLY_POWER, POLY_LEAF, POLY_COMBINE = 0, 1, 2
+POLY_TAIL_NONE, POLY_TAIL_ONE = -1, -2
+PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "steps level scale out_limbs")
+
+
+def poly_eval_plan(basis, coeffs, level, scale, target_scale, primes, max_deg=None, lead=True):
+    """The evaluation order of sum_i coeffs[i] b_i(x) on a CKKS ciphertext (host only; hegpu_poly_eval_plan_size / _fill),
+    b_i = x^i (MONOMIAL) or T_i (CHEBYSHEV, x in [-1, 1]): the reference's baby-step/giant-step schedule.  level / scale:
+    of the input ciphertext (level = Q - 1 - depth); primes: the context's q_0 ...; max_deg / lead: the reference's
+    Polynomial::max_deg_ (default: the degree) and lead_.  Returns
+      steps      a ctypes array of hegpu_poly_step (include/hegpu.h): kind, dst, a, b, c, level, mul_level, rescale_first,
+                 rescale_after, n_terms, term_reg, scale, tail_const, w0, w
+      level      of the result (its depth is Q - 1 - level)
+      scale      of the result
+      out_limbs  limbs per part the output buffer of Context.ckks_poly_eval needs (one more than level + 1 when the last
+                 step rescales)"""
+    lib = _lib.load()
+    c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(-1))
+    pr = [int(p) for p in primes]
+    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    md = len(c) - 1 if max_deg is None else int(max_deg)
+    args = (int(basis), c.ctypes.data, len(c), md, int(bool(lead)), int(level), float(scale), float(target_scale), arr,
+            len(pr))
+    count = ctypes.c_int(0)
+    _check(lib.hegpu_poly_eval_plan_size(*args, ctypes.byref(count)))
+    steps = (_lib.PolyStep * count.value)()
+    _check(lib.hegpu_poly_eval_plan_fill(*args, steps, count.value))
+    last = steps[count.value - 1]
+    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
 
 
 def steps_to_galois_elt(steps, n, group_order):

@@ -4,8 +4,11 @@
 #include "context.hpp"
 #include "encoding_transform.hpp"
 #include "host_params.hpp"
+#include "poly_eval.hpp"
 #include "ops.hpp"
 #include <cmath>
+#include <complex>
+#include <cstddef>
 #include "tfhe.hpp"
 #include <algorithm>
 #include <cerrno>
@@ -24,6 +27,7 @@
 // entry; it gets the host-only factorisation through this file instead of an object of its own.
 #ifdef HEGPU_FP_AUDIT_HEADER
 #include "encoding_transform.cpp"
+#include "poly_eval.cpp"
 #endif
 
 using namespace hegpu;
@@ -510,6 +514,47 @@ int hegpu_encoding_transform_fill(int coeff_count, int inverse, int pieces, int 
     });
 }
 
+// host only: the evaluation order of a polynomial on a ciphertext (poly_eval.hpp)
+static_assert(sizeof(hegpu_poly_step) == sizeof(host::PolyStep) && offsetof(hegpu_poly_step, w) == offsetof(host::PolyStep, w) &&
+                  offsetof(hegpu_poly_step, scale) == offsetof(host::PolyStep, scale),
+              "hegpu_poly_step is host::PolyStep");
+static std::vector<host::PolyStep> poly_plan_of(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level,
+                                                double scale, double target_scale, const uint64_t* primes, int n_primes)
+{
+    if (!coeffs || !primes) throw std::invalid_argument("poly_eval_plan: null argument");
+    if (n_coeffs < 1 || n_primes < 1) throw std::invalid_argument("poly_eval_plan: the degree is at least 2");
+    std::vector<std::complex<double>> c((size_t) n_coeffs);
+    for (int i = 0; i < n_coeffs; i++) c[(size_t) i] = std::complex<double>(coeffs[2 * i], coeffs[2 * i + 1]);
+    return host::poly_eval_plan(basis, c, max_deg, lead != 0, level, scale, target_scale,
+                                std::vector<uint64_t>(primes, primes + n_primes));
+}
+
+int hegpu_poly_eval_plan_size(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
+                              double target_scale, const uint64_t* primes, int n_primes, int* n_steps)
+{
+    return guarded([&]() -> int {
+        if (!n_steps) return fail(HEGPU_E_INVALID, "poly_eval_plan_size: null argument");
+        const std::vector<host::PolyStep> plan =
+            poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes);
+        *n_steps = (int) plan.size();
+        return 0;
+    });
+}
+
+int hegpu_poly_eval_plan_fill(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
+                              double target_scale, const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps)
+{
+    return guarded([&]() -> int {
+        if (!steps) return fail(HEGPU_E_INVALID, "poly_eval_plan_fill: null argument");
+        const std::vector<host::PolyStep> plan =
+            poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes);
+        if (n_steps != (int) plan.size())
+            return fail(HEGPU_E_INVALID, "poly_eval_plan_fill: n_steps is not what hegpu_poly_eval_plan_size gives");
+        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
+        return 0;
+    });
+}
+
 #define NEED_CTX(ctx)                                                                      \
     if (!(ctx)) return fail(HEGPU_E_INVALID, "null context");                              \
     if (!(ctx)->c.uploaded) {                                                              \
@@ -965,6 +1010,108 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                             (const u64* const*) giant_keys, giant_elts, depth, batch, (u64*) ws,
                                             (hipStream_t) stream),
                    "hegpu_ckks_linear_transform");
+}
+
+// ---- polynomial evaluation: the two one-pass kernels and the sequence over a plan
+int hegpu_ckks_weighted_sum(hegpu_context* ctx, const uint64_t* const* terms, const uint64_t* term_strides,
+                            const int* term_limbs, const double* weights, int count, double w0_re, double w0_im,
+                            uint64_t* out, uint64_t out_stride, int limbs, int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "weighted_sum: batch must be at least 1");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "weighted_sum: at most 32767 items per call");
+    if (count < 0 || count > 15)
+        return fail(HEGPU_E_INVALID, "weighted_sum: at most 15 terms (15 products and a residue per 128-bit sum)");
+    if (limbs < 1 || limbs > ctx->c.Q_size) return fail(HEGPU_E_INVALID, "weighted_sum: bad limb count");
+    if (!out || (count && (!terms || !term_strides || !term_limbs || !weights)))
+        return fail(HEGPU_E_INVALID, "weighted_sum: null argument");
+    for (double v : {w0_re, w0_im})
+        if (!std::isfinite(v)) return fail(HEGPU_E_INVALID, "weighted_sum: a weight is not a finite number");
+    const uint64_t out_words = (uint64_t) 2 * limbs * ctx->c.n;
+    for (int k = 0; k < count; k++) {
+        if (!terms[k]) return fail(HEGPU_E_INVALID, "weighted_sum: null argument");
+        if (term_limbs[k] < limbs || term_limbs[k] > ctx->c.Q_size)
+            return fail(HEGPU_E_INVALID, "weighted_sum: a term has fewer limbs than the sum");
+        if (!std::isfinite(weights[2 * k]) || !std::isfinite(weights[2 * k + 1]))
+            return fail(HEGPU_E_INVALID, "weighted_sum: a weight is not a finite number");
+        if (spans_overlap(terms[k], term_strides[k], (uint64_t) 2 * term_limbs[k] * ctx->c.n, out, out_stride, out_words, batch))
+            return fail(HEGPU_E_INVALID, "weighted_sum: out must not overlap a term");
+    }
+    return hip_ret(rns_ckks_weighted_sum((const u64* const*) terms, (const u64*) term_strides, term_limbs, weights, count,
+                                         w0_re, w0_im, (u64*) out, out_stride, ctx->c.tab.psi_half, ctx->c.plan_qp.mods,
+                                         ctx->c.n_power, limbs, batch, (hipStream_t) stream),
+                   "hegpu_ckks_weighted_sum");
+}
+
+int hegpu_ckks_double_sub(hegpu_context* ctx, const uint64_t* a, uint64_t a_stride, int a_limbs, const uint64_t* b,
+                          uint64_t b_stride, int b_limbs, double value, uint64_t* out, uint64_t out_stride, int limbs,
+                          int batch, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "double_sub: batch must be at least 1");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "double_sub: at most 32767 items per call");
+    if (!a || !out) return fail(HEGPU_E_INVALID, "double_sub: null argument");
+    if (limbs < 1 || a_limbs < limbs || a_limbs > ctx->c.Q_size || (b && (b_limbs < limbs || b_limbs > ctx->c.Q_size)))
+        return fail(HEGPU_E_INVALID, "double_sub: bad limb count");
+    if (!b && (!(value == value) || value >= 3.4e38 || value <= -3.4e38))
+        return fail(HEGPU_E_INVALID, "double_sub: constant out of range");
+    const uint64_t n = ctx->c.n, out_words = (uint64_t) 2 * limbs * n;
+    const bool in_place = a == out && a_stride == out_stride && a_limbs == limbs;
+    if (!in_place && spans_overlap(a, a_stride, (uint64_t) 2 * a_limbs * n, out, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, "double_sub: out is a itself (equal strides and limb counts) or does not overlap it");
+    if (b && spans_overlap(b, b_stride, (uint64_t) 2 * b_limbs * n, out, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, "double_sub: out must not overlap b");
+    return hip_ret(rns_ckks_double_sub((const u64*) a, a_stride, a_limbs, (const u64*) b, b_stride, b_limbs, value, (u64*) out,
+                                       out_stride, ctx->c.plan_qp.mods, ctx->c.n_power, limbs, batch, (hipStream_t) stream),
+                   "hegpu_ckks_double_sub");
+}
+
+size_t hegpu_ckks_poly_eval_workspace_bytes(const hegpu_context* ctx, const hegpu_poly_step* plan, int n_steps, int depth,
+                                            int batch)
+{
+    if (!ctx || batch <= 0 || ctx->c.scheme != SCHEME_CKKS) return 0;
+    const host::PolyStep* p = reinterpret_cast<const host::PolyStep*>(plan);
+    size_t bytes = 0;
+    (void) guarded([&]() -> int { // no exception may cross the C boundary (the check keeps tables of n_steps entries)
+        if (!ops_poly_eval_check(ctx->c, p, n_steps, depth))
+            bytes = ops_poly_eval_workspace_elems(ctx->c, p, n_steps, depth, batch) * sizeof(u64);
+        return 0;
+    });
+    return bytes;
+}
+
+int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
+                         const hegpu_poly_step* plan, int n_steps, const uint64_t* relin_key, int depth, int batch,
+                         void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    NEED_CTX(ctx);
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "poly_eval: batch must be at least 1");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "poly_eval: at most 32767 items per call");
+    if (!ct || !out || !plan || !relin_key || !ws) return fail(HEGPU_E_INVALID, "poly_eval: null argument");
+    const host::PolyStep* p = reinterpret_cast<const host::PolyStep*>(plan);
+    return guarded([&]() -> int {
+        if (const char* why = ops_poly_eval_check(ctx->c, p, n_steps, depth))
+            return fail(HEGPU_E_INVALID, std::string("poly_eval: ") + why);
+        for (int k = 0; k < n_steps; k++) {
+            if (p[k].kind != host::POLY_STEP_LEAF) continue;
+            for (int i = 0; i <= p[k].n_terms; i++) {
+                const double* w = i < p[k].n_terms ? p[k].w[i] : p[k].w0;
+                if (!std::isfinite(w[0]) || !std::isfinite(w[1])) return fail(HEGPU_E_INVALID, "poly_eval: a weight is not a finite number");
+            }
+        }
+        const host::PolyStep& last = p[n_steps - 1];
+        const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+        const uint64_t out_words = (uint64_t) 2 * (last.level + 1 + (last.rescale_after ? 1 : 0)) * ctx->c.n;
+        if (spans_overlap(ct, cs, in_words, out, so, out_words, batch)) return fail(HEGPU_E_INVALID, "poly_eval: out must not overlap ct");
+        if (ws_bytes < hegpu_ckks_poly_eval_workspace_bytes(ctx, plan, n_steps, depth, batch))
+            return fail(HEGPU_E_INVALID, "workspace too small");
+        return hip_ret(op_ckks_poly_eval(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, n_steps, (const u64*) relin_key, depth,
+                                         batch, (u64*) ws, (hipStream_t) stream),
+                       "hegpu_ckks_poly_eval");
+    });
 }
 
 // ---- the real / imaginary boundary passes and the CoeffToSlot / SlotToCoeff sequences

@@ -4,6 +4,7 @@
 // kernels of the hot path.
 #include "keygen.hpp"
 #include "crt_compose.cuh"
+#include "ckks_const.cuh"
 
 namespace hegpu {
 
@@ -434,13 +435,7 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_ckks_constant(const u64* __re
     const u64 x = ct[loc];
     if (op != 2 && blockIdx.z != 0) { out[loc] = x; return; }
     const Mod m = mods[blockIdx.y];
-    double c = round(value);
-    const bool neg = signbit(c);
-    c = fabs(c);
-    const double two64 = 18446744073709551616.0;
-    const u64 lo = (u64) fmod(c, two64), hi = (u64) (c / two64);
-    u64 pt = reduce128(hi, lo, m);
-    if (neg) pt = sub_mod(m.q, pt, m.q); // sub(q, 0) == q is the reference's
+    const u64 pt = real_constant_residue(value, m);
     out[loc] = op == 0 ? add_mod(x, pt, m.q) : op == 1 ? sub_mod(x, pt, m.q) : mul_barrett(x, pt, m);
 }
 
@@ -459,30 +454,6 @@ hipError_t kg_ckks_constant(const u64* ct, double value, u64* out, const Mod* mo
 // rounded doubles into residues with NTL big integers (ckks/operator.cu:583-617) and accepts any magnitude; a
 // double is mant * 2^e: below 2^128 the residue comes from its two 64-bit halves, beyond that from
 // (mant mod q) * (2^e mod q) -- exact for every finite double.
-__device__ __forceinline__ u64 residue_of_rounded(double value, const Mod& m)
-{
-    double c = round(value);
-    const bool neg = signbit(c);
-    c = fabs(c);
-    const double two64 = 18446744073709551616.0;
-    u64 r;
-    if (c < two64 * two64) {
-        const u64 lo = (u64) fmod(c, two64), hi = (u64) (c / two64);
-        r = reduce128(hi, lo, m);
-    } else {
-        int e;
-        const double fr = frexp(c, &e);              // c = fr * 2^e, 0.5 <= fr < 1
-        const u64 mant = (u64) ldexp(fr, 53);        // the 53-bit integer mantissa, exact
-        r = reduce64(mant, m);
-        u64 p = reduce64(2, m), acc = reduce64(1, m); // 2^(e - 53) mod q by square and multiply
-        for (int sh = e - 53; sh; sh >>= 1) {
-            if (sh & 1) acc = reduce128(mulhi64(acc, p), acc * p, m);
-            p = reduce128(mulhi64(p, p), p * p, m);
-        }
-        r = reduce128(mulhi64(r, acc), r * acc, m);
-    }
-    return (neg && r) ? m.q - r : r; // NTL: (x % q) made non-negative
-}
 __global__ __launch_bounds__(KG_THREADS) void k_kg_ckks_gaussian(const u64* __restrict__ ct, double re, double im,
                                                                  u64* __restrict__ out, const u64* __restrict__ psi_half,
                                                                  const Mod* __restrict__ mods, int n_power, int op)
@@ -492,9 +463,7 @@ __global__ __launch_bounds__(KG_THREADS) void k_kg_ckks_gaussian(const u64* __re
     const u64 x = ct[loc];
     if (op == 0 && blockIdx.z != 0) { out[loc] = x; return; }
     const Mod m = mods[blockIdx.y];
-    const u64 c_real = residue_of_rounded(re, m), c_imag = residue_of_rounded(im, m);
-    const u64 const_imag = mul_barrett(c_imag, psi_half[blockIdx.y], m);
-    const u64 k = (idx < (1u << (n_power - 1))) ? add_mod(c_real, const_imag, m.q) : sub_mod(c_real, const_imag, m.q);
+    const u64 k = gaussian_slot_constant(re, im, psi_half[blockIdx.y], idx < (1u << (n_power - 1)), m);
     out[loc] = op == 0 ? add_mod(x, k, m.q) : mul_barrett(x, k, m);
 }
 

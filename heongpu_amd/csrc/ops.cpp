@@ -959,6 +959,161 @@ hipError_t op_ckks_slot_to_coeff(const Context& c, const u64* c0, u64 s0, const 
     return encoding_transform_chain(c, cur, cur_stride, T0, T1, t_stride, out, so, f, count, depth + 1, batch, step_ws, st);
 }
 
+// ------------------------------------------------------------------ polynomial evaluation
+const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, int n_steps, int depth)
+{
+    using namespace host;
+    if (!plan || n_steps < 1) return "empty plan";
+    if (n_steps > 4096) return "a plan of more than 4096 steps"; // degree 255, the largest the planner takes, has under 600
+    if (depth < 0 || depth >= c.Q_size) return "invalid depth";
+    const int top = c.Q_size - 1 - depth;
+    if (plan[n_steps - 1].kind == POLY_STEP_POWER) return "the last step is a leaf or a combination";
+    std::vector<int> level((size_t) n_steps + 1);
+    std::vector<char> spent((size_t) n_steps + 1, 0); // rescaled in place by the COMBINE that consumed it
+    level[0] = top;
+    auto reg_ok = [&](int r, int dst) { return r >= 0 && r < dst && !spent[(size_t) r]; };
+    for (int k = 0; k < n_steps; k++) {
+        const PolyStep& s = plan[k];
+        const int dst = k + 1;
+        if (s.dst != dst) return "a step does not write the register of its position";
+        if (s.level < 0 || s.level > top) return "a level outside the ciphertext's";
+        if (s.rescale_after && (k != n_steps - 1 || s.kind != POLY_STEP_COMBINE)) return "only a last COMBINE step rescales its result";
+        if (s.kind == POLY_STEP_POWER) {
+            if (!reg_ok(s.a, dst) || !reg_ok(s.b, dst)) return "a register number out of range";
+            if (s.c != POLY_TAIL_NONE && s.c != POLY_TAIL_ONE && !reg_ok(s.c, dst)) return "a register number out of range";
+            const int la = level[(size_t) s.a], lb = level[(size_t) s.b];
+            if (s.mul_level < 1 || s.mul_level != (la < lb ? la : lb)) return "a product not at the lower of its operands' levels";
+            if (s.level > s.mul_level - 1 || (s.c >= 0 && s.level > level[(size_t) s.c])) return "a power above its operands' levels";
+            if (s.c < 0 && s.level != s.mul_level - 1) return "a power without a register tail leaves one level below its product";
+            if (s.c == POLY_TAIL_ONE && !(s.tail_const > -3.4e38 && s.tail_const < 3.4e38)) return "a tail constant out of range";
+        } else if (s.kind == POLY_STEP_LEAF) {
+            if (s.n_terms < 0 || s.n_terms > POLY_LEAF_MAX) return "a leaf of more than 15 power terms";
+            for (int i = 0; i < s.n_terms; i++) {
+                if (!reg_ok(s.term_reg[i], dst)) return "a register number out of range";
+                if (level[(size_t) s.term_reg[i]] < s.level) return "a leaf above the level of a term";
+            }
+        } else if (s.kind == POLY_STEP_COMBINE) {
+            if (!reg_ok(s.a, dst) || !reg_ok(s.b, dst) || !reg_ok(s.c, dst)) return "a register number out of range";
+            if (s.a == 0) return "the input cannot be rescaled in place";
+            const int la = level[(size_t) s.a] - (s.rescale_first ? 1 : 0), lb = level[(size_t) s.b];
+            if (la < 0) return "no modulus left to rescale by";
+            if (s.mul_level < 0 || s.mul_level != (la < lb ? la : lb)) return "a product not at the lower of its operands' levels";
+            const int lr = level[(size_t) s.c];
+            const int sum = s.level + (s.rescale_after ? 1 : 0);
+            if (sum != (s.mul_level < lr ? s.mul_level : lr)) return "a sum not at the lower of its operands' levels";
+            if (s.rescale_first && (s.a == s.b || s.a == s.c)) return "a register rescaled in place is read once";
+            if (s.rescale_first) spent[(size_t) s.a] = 1;
+        } else {
+            return "unknown step kind";
+        }
+        level[(size_t) dst] = s.level;
+    }
+    return nullptr;
+}
+
+// words of register k + 1 per item
+static u64 poly_reg_words(const Context& c, const host::PolyStep& s)
+{
+    const bool product_in_place = s.kind == host::POLY_STEP_POWER && s.c == host::POLY_TAIL_NONE;
+    return (product_in_place ? (u64) 3 * (s.mul_level + 1) : (u64) 2 * (s.level + 1)) * c.n;
+}
+
+size_t ops_poly_eval_workspace_elems(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch)
+{
+    const u64 top_limbs = (u64) (c.Q_size - depth);
+    u64 per = (3 + 2) * top_limbs * c.n;
+    for (int k = 0; k + 1 < n_steps; k++) per += poly_reg_words(c, plan[k]); // the last step writes `out`
+    const size_t relin = ops_workspace_elems(c, OP_CKKS_RELIN, depth, batch), resc = ops_workspace_elems(c, OP_CKKS_RESCALE, depth, batch);
+    return per * (u64) batch + (relin > resc ? relin : resc);
+}
+
+hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::PolyStep* plan,
+                             int n_steps, const u64* relin_key, int depth, int batch, u64* ws, hipStream_t st)
+{
+    using namespace host;
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (ops_poly_eval_check(c, plan, n_steps, depth)) return hipErrorInvalidValue;
+    const int np = c.n_power, Q = c.Q_size;
+    const u64 n = c.n;
+    const Mod* mods = c.plan_qp.mods;
+    struct Reg { u64* p; u64 stride; int limbs; };
+    std::vector<Reg> reg((size_t) n_steps + 1);
+    reg[0] = {const_cast<u64*>(ct), cs, Q - depth}; // never written: ops_poly_eval_check keeps register 0 out of every dst
+    u64* at = ws;
+    for (int k = 0; k < n_steps; k++) {
+        const u64 words = poly_reg_words(c, plan[k]);
+        if (k == n_steps - 1) reg[(size_t) k + 1] = {out, so, plan[k].level + 1};
+        else {
+            reg[(size_t) k + 1] = {at, words, plan[k].level + 1};
+            at += words * batch;
+        }
+    }
+    const u64 t_stride = (u64) 3 * (Q - depth) * n, d_stride = (u64) 2 * (Q - depth) * n;
+    u64* T = at;                    // one three-part product per item
+    u64* D = T + t_stride * batch;  // one operand copied down to the product's level
+    u64* ks = D + d_stride * batch; // relinearize / rescale workspace
+
+    // reg[x] * reg[y] at level ml, relinearized, into dst ([3][ml + 1][N] per item, two parts on return)
+    auto product = [&](const Reg& x, const Reg& y, int ml, u64* dst, u64 dst_stride) -> hipError_t {
+        const int l = ml + 1;
+        Reg in[2] = {x, y};
+        for (Reg& r : in)
+            if (r.limbs != l) { // at most one of the two sits above the product's level
+                TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) l * n, d_stride, np, l, 2, batch, st));
+                r = {D, d_stride, l};
+            }
+        TRY(op_ckks_multiply(c, in[0].p, in[0].stride, in[1].p, in[1].stride, dst, dst_stride, Q - l, batch, st));
+        return op_ckks_relinearize(c, dst, dst_stride, relin_key, Q - l, batch, ks, st);
+    };
+
+    for (int k = 0; k < n_steps; k++) {
+        const PolyStep& s = plan[k];
+        const Reg& dst = reg[(size_t) k + 1];
+        if (s.kind == POLY_STEP_POWER) {
+            const bool in_place = s.c == POLY_TAIL_NONE;
+            u64* prod = in_place ? dst.p : T;
+            const u64 ps = in_place ? dst.stride : t_stride;
+            TRY(product(reg[(size_t) s.a], reg[(size_t) s.b], s.mul_level, prod, ps));
+            TRY(op_ckks_rescale(c, prod, ps, Q - (s.mul_level + 1), batch, ks, st));
+            if (in_place) continue;
+            const Reg* b = s.c >= 0 ? &reg[(size_t) s.c] : nullptr;
+            TRY(rns_ckks_double_sub(prod, ps, s.mul_level, b ? b->p : nullptr, b ? b->stride : 0, b ? b->limbs : 0,
+                                    s.tail_const, dst.p, dst.stride, mods, np, dst.limbs, batch, st));
+        } else if (s.kind == POLY_STEP_LEAF) {
+            const u64* terms[POLY_LEAF_MAX];
+            u64 strides[POLY_LEAF_MAX];
+            int limbs[POLY_LEAF_MAX];
+            for (int i = 0; i < s.n_terms; i++) {
+                const Reg& r = reg[(size_t) s.term_reg[i]];
+                terms[i] = r.p;
+                strides[i] = r.stride;
+                limbs[i] = r.limbs;
+            }
+            TRY(rns_ckks_weighted_sum(terms, strides, limbs, &s.w[0][0], s.n_terms, s.w0[0], s.w0[1], dst.p, dst.stride,
+                                      c.tab.psi_half, mods, np, dst.limbs, batch, st));
+        } else {
+            Reg q = reg[(size_t) s.a];
+            if (s.rescale_first) {
+                TRY(op_ckks_rescale(c, q.p, q.stride, Q - q.limbs, batch, ks, st));
+                q.limbs -= 1;
+            }
+            TRY(product(q, reg[(size_t) s.b], s.mul_level, T, t_stride));
+            const int sum_limbs = dst.limbs + (s.rescale_after ? 1 : 0);
+            Reg terms2[2] = {{T, t_stride, s.mul_level + 1}, reg[(size_t) s.c]};
+            for (Reg& r : terms2)
+                if (r.limbs != sum_limbs) { // the product is relinearized: D is free again
+                    TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) sum_limbs * n, d_stride, np, sum_limbs, 2, batch, st));
+                    r = {D, d_stride, sum_limbs};
+                }
+            const u64* tp[2] = {terms2[0].p, terms2[1].p};
+            const u64 tsd[2] = {terms2[0].stride, terms2[1].stride};
+            TRY(rns_ckks_sum_terms(tp, tsd, 2, dst.p, dst.stride, mods, np, sum_limbs, batch, st));
+            if (s.rescale_after) TRY(op_ckks_rescale(c, dst.p, dst.stride, Q - sum_limbs, batch, ks, st));
+        }
+    }
+    return hipSuccess;
+}
+
 // ------------------------------------------------------------------ keygen / encrypt / decrypt
 // The plain transforms of this half: `polys` contiguous polynomials, polynomial i under modulus i % mod_count of table
 // set `tables` (0: Q', 2: the plain modulus)

@@ -2,6 +2,7 @@
 #pragma once
 #include "context.hpp"
 #include "keygen.hpp"
+#include "poly_eval.hpp"
 
 namespace hegpu {
 
@@ -75,6 +76,20 @@ hipError_t op_ckks_coeff_to_slot(const Context& c, const u64* ct, u64 cs, u64* o
 // written to out and rescaled there: out holds [2][l - count][N] on the way, [2][l - count - 1][N] at the end
 hipError_t op_ckks_slot_to_coeff(const Context& c, const u64* c0, u64 s0, const u64* c1, u64 s1, u64* out, u64 so,
                                  const LinearFactor* f, int count, int depth, int batch, u64* ws, hipStream_t st);
+
+// ---- polynomial evaluation (reference evaluate_poly, ckks/operator.cu:4292-4671): executes a plan of
+// host::poly_eval_plan and nothing else.  POWER: drop copy of the higher operand if the levels differ, op_ckks_multiply,
+// op_ckks_relinearize, op_ckks_rescale, then (Chebyshev) one rns_ckks_double_sub.  LEAF: one rns_ckks_weighted_sum, every
+// power read at its own level.  COMBINE: op_ckks_rescale of q if the plan says so, multiply and relinearize as above, one
+// rns_ckks_sum_terms at the lower level, and the plan's final rescale.  Register 0 is ct at `depth`; the last step writes
+// `out`, which needs room for [2][level + 1 + rescale_after][N] per item and holds [2][level + 1][N] on return.
+// ops_poly_eval_check: nullptr, or what is wrong with the plan for this context and depth (registers, levels).
+const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, int n_steps, int depth);
+// per item: every register at the limb count the plan gives it (a product without a tail: three parts at its product's
+// level), one three-part product, one dropped copy, then the relinearize workspace at `depth`
+size_t ops_poly_eval_workspace_elems(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch);
+hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::PolyStep* plan,
+                             int n_steps, const u64* relin_key, int depth, int batch, u64* ws, hipStream_t st);
 
 // ---- key generation / encryption / decryption, key-switch method I
 // The generator state: every sampling call consumes one stream id of the DRBG (drbg.hpp).

@@ -1,0 +1,54 @@
+// poly_eval.hpp -- host only: the evaluation order of a polynomial on a CKKS ciphertext.  No device,
+// no context: integers and FP64 on the host.
+//
+// The schedule is the reference's (HEOperator<CKKS>::evaluate_poly, gen_power, evaluate_poly_recurse,
+// evaluate_poly_from_polynomial_basis and Polynomial::split_coeffs, ckks/operator.cu:4292-4671, :6633-6678): baby powers
+// 2^s - 1 .. 1 and giant powers 2^s .. 2^(D-1) with s = optimal_split(D), then the recursive split q * x^(2^j) + r down to
+// leaves of degree < 2^s.  A level is the index of a ciphertext's last prime (limbs = level + 1), a scale the factor its
+// slots carry.  The plan is a flat list of steps over numbered registers; register 0 is the input (power 1), every step
+// writes a new register, the last step's register is the result.
+//
+// Two departures, both where the reference reads a power it never made:
+//   * D = bit length of the degree (ceil(log2(degree + 1))).  The reference takes ceil(log2(degree)), which is the same
+//     number unless the degree is a power of two; there its first split needs x^degree and only x^(degree/2) exists.
+//   * the threshold of the conditional rescale of q (:4545) is target_scale / 2; the reference compares with the scale
+//     of its bootstrapping context, which is the scale it calls the evaluator with.
+#pragma once
+#include <complex>
+#include <cstdint>
+#include <vector>
+
+namespace hegpu {
+namespace host {
+
+enum { POLY_MONOMIAL = 0, POLY_CHEBYSHEV = 1 };
+enum { POLY_STEP_POWER = 0, POLY_STEP_LEAF = 1, POLY_STEP_COMBINE = 2 };
+enum { POLY_TAIL_NONE = -1, POLY_TAIL_ONE = -2 }; // PolyStep::c of a POWER step that subtracts no register
+constexpr int POLY_LEAF_MAX = 15;                 // power terms of one leaf: 15 products and w_0 fit the 128-bit sum
+
+// The layout is the C ABI's hegpu_poly_step (include/hegpu.h), field for field.
+struct PolyStep {
+    int32_t kind;  // POLY_STEP_*
+    int32_t dst;   // the register written (= 1 + the step's position)
+    int32_t a, b;  // POWER: dst = reg[a] * reg[b]; COMBINE: dst = reg[a] * reg[b] + reg[c] (a = q, b = the giant power)
+    int32_t c;     // POWER: POLY_TAIL_NONE (monomial), POLY_TAIL_ONE (2 dst - 1) or the register of 2 dst - reg[c]; COMBINE: r
+    int32_t level; // of dst
+    int32_t mul_level;      // POWER, COMBINE: the level of the product (the lower of its operands', after q's rescale)
+    int32_t rescale_first;  // COMBINE: 1 = reg[a] is rescaled before the product
+    int32_t rescale_after;  // the last step only: 1 = dst is rescaled once more; level and scale are those after it
+    int32_t n_terms;        // LEAF: number of power terms, <= POLY_LEAF_MAX
+    int32_t term_reg[POLY_LEAF_MAX];
+    double scale;           // of dst
+    double tail_const;      // POWER with POLY_TAIL_ONE: the real constant subtracted from part 0 (= scale: the one)
+    double w0[2];           // LEAF: round(c_0 * leaf_scale), (re, im)
+    double w[POLY_LEAF_MAX][2]; // LEAF: round(c_i * (leaf_scale / scale_i)) per term
+};
+
+// std::invalid_argument: degree < 2, basis not one of the two, max_deg < degree, a non-finite coefficient or scale, a
+// scale <= 0, a leaf of more than POLY_LEAF_MAX power terms, fewer levels than the schedule spends (a level below 0, or
+// a rescale at level 0), level >= the number of primes.
+std::vector<PolyStep> poly_eval_plan(int basis, const std::vector<std::complex<double>>& coeffs, int max_deg, bool lead,
+                                     int level, double scale, double target_scale, const std::vector<uint64_t>& primes);
+
+} // namespace host
+} // namespace hegpu

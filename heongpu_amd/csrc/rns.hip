@@ -9,6 +9,7 @@
 // lazily where it is exact (128-bit accumulation in the key-switch MAC), so
 // outputs are the same canonical residues.
 #include "rns.hpp"
+#include "ckks_const.cuh"
 #include <cstdlib>
 #include <type_traits>
 
@@ -1339,6 +1340,142 @@ hipError_t rns_ckks_conj_merge(const u64* c0, u64 c0_stride, const u64* c1, u64 
     if (out_limbs < 1 || out_limbs > in_limbs || 2 * (long) batch > 65535) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_ckks_conj_merge, grid3(n_power, out_limbs, 2 * batch), dim3(RNS_THREADS), 0, st, c0, c0_stride, c1,
                        c1_stride, out, out_stride, psi_half, mods, n_power, in_limbs, out_limbs);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- polynomial evaluation: leaves and the Chebyshev tail
+// A leaf of the polynomial evaluator: out[p] = (p == 0 ? w_0 : 0) + sum_i w_i * term_i[p], p = 0, 1, over
+// the first `limbs` limbs.  The reference (evaluate_poly_from_polynomial_basis, ckks/operator.cu:4429-4481) encodes every
+// constant into a plaintext, multiplies a copy of the power by it, copies the power down to the leaf's level and adds:
+// about 12 l N words per term.  Here the thread that owns two adjacent coefficients of a limb reads each term once, in place
+// at whatever level it sits (term i has limbs[i] >= limbs limbs per part), and writes the sum once: 2 l N words read per
+// term, 2 l N written per leaf.
+// A weight is a Gaussian integer given as two doubles; its slot constant re +- im psi^(N/2) mod q_j (ckks_const.cuh, the
+// code of k_kg_ckks_gaussian) depends on the limb and on the half of the NTT positions only, so lanes 0 .. count of a
+// workgroup compute the two constants of one weight each and leave them in LDS.
+// Bound of the lazy sum: WSUM_MAX products of two residues below 2^61 plus nothing else stay below 15 * 2^122 < 2^126; one
+// reduce128 (any 128-bit value, q < 2^62) gives the canonical residue that the chain of modular multiplies and additions
+// gives, and w_0 is added to it modularly.
+// K: the term count the instance is compiled for (every register index a constant, all loads in flight before the first
+// product); count <= K terms exist.
+#define WSUM_MAX 15
+#define WSUM_SLOTS 16
+static_assert(WSUM_MAX <= WSUM_SLOTS, "the widest instance holds every term");
+static_assert(((unsigned __int128) WSUM_MAX << 122) + ((unsigned __int128) 1 << 61) < ((unsigned __int128) 1 << 127),
+              "15 products of residues below 2^61, plus a residue, fit 128 bits");
+struct WeightedTerms {
+    const u64* p[WSUM_SLOTS];
+    u64 stride[WSUM_SLOTS];
+    int limbs[WSUM_SLOTS];
+    double re[WSUM_SLOTS + 1], im[WSUM_SLOTS + 1]; // entry `count` is w_0
+};
+template <int K>
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_weighted_sum(WeightedTerms t, int count, u64* __restrict__ out,
+                                                                   u64 out_stride, const u64* __restrict__ psi_half,
+                                                                   const Mod* __restrict__ mods, int n_power, int limbs)
+{
+    __shared__ u64 w_first[WSUM_SLOTS + 1], w_second[WSUM_SLOTS + 1];
+    const Mod m = mods[blockIdx.y];
+    if ((int) threadIdx.x <= count) {
+        const u64 psi = psi_half[blockIdx.y];
+        w_first[threadIdx.x] = gaussian_slot_constant(t.re[threadIdx.x], t.im[threadIdx.x], psi, true, m);
+        w_second[threadIdx.x] = gaussian_slot_constant(t.re[threadIdx.x], t.im[threadIdx.x], psi, false, m);
+    }
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << n_power;
+    ulonglong2 x[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        x[i] = ulonglong2{0, 0};
+        if (i < count) x[i] = ld2(t.p[i] + t.stride[i] * item + (((u64) t.limbs[i] * z) << n_power) + limb + c);
+    }
+    __syncthreads();
+    const u64* w = (c < (1ull << (n_power - 1))) ? w_first : w_second; // c is even: both coefficients lie in one half
+    u64 h0 = 0, l0 = 0, h1 = 0, l1 = 0;
+#pragma unroll
+    for (int i = 0; i < K; i++) { // an absent term adds zeros: no branch around the accumulators
+        const u64 k = i < count ? w[i] : 0;
+        acc128(h0, l0, x[i].x, k);
+        acc128(h1, l1, x[i].y, k);
+    }
+    ulonglong2 r;
+    r.x = reduce128(h0, l0, m);
+    r.y = reduce128(h1, l1, m);
+    if (z == 0) {
+        const u64 k0 = w[count];
+        r.x = add_mod(r.x, k0, m.q);
+        r.y = add_mod(r.y, k0, m.q);
+    }
+    st2(out + out_stride * item + (((u64) limbs * z) << n_power) + limb + c, r);
+}
+
+hipError_t rns_ckks_weighted_sum(const u64* const* terms, const u64* strides, const int* term_limbs, const double* weights,
+                                 int count, double w0_re, double w0_im, u64* out, u64 out_stride, const u64* psi_half,
+                                 const Mod* mods, int n_power, int limbs, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (count < 0 || count > WSUM_MAX || limbs < 1 || n_power < 9 || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    WeightedTerms t{};
+    for (int k = 0; k < count; k++) {
+        if (!terms[k] || term_limbs[k] < limbs) return hipErrorInvalidValue;
+        t.p[k] = terms[k];
+        t.stride[k] = strides[k];
+        t.limbs[k] = term_limbs[k];
+        t.re[k] = weights[2 * k];
+        t.im[k] = weights[2 * k + 1];
+    }
+    t.re[count] = w0_re;
+    t.im[count] = w0_im;
+    const dim3 g = grid3(n_power, limbs, 2 * batch);
+    dispatch_width<1, 2, 4, 8, 16>(count, [&](auto K) {
+        hipLaunchKernelGGL(k_ckks_weighted_sum<K()>, g, dim3(RNS_THREADS), 0, st, t, count, out, out_stride, psi_half, mods,
+                           n_power, limbs);
+    });
+    return hipGetLastError();
+}
+
+// The tail of a Chebyshev power, T_{a+b} = 2 T_a T_b - T_{|a-b|}: out = 2 a - b over the first `limbs` limbs, one read of
+// each input and one write.  The reference (gen_power, ckks/operator.cu:4355-4394) adds the product to itself in place,
+// then subtracts a copy of the other power dropped to the level, or adds the constant -1: two to four passes.  b == nullptr:
+// the real constant round(value) (ckks_const.cuh, the code of k_kg_ckks_constant) is subtracted from part 0 and part 1 is
+// doubled only; lane 0 of a workgroup computes its residue.  a and b sit at their own limb counts >= limbs.  Doubling and
+// subtraction are the modular ones of k_addition, so the residues are those of the two passes.
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_double_sub(const u64* a, u64 a_stride, int a_limbs,
+                                                                 const u64* __restrict__ b, u64 b_stride, int b_limbs,
+                                                                 double value, u64* out, u64 out_stride,
+                                                                 const Mod* __restrict__ mods, int n_power, int limbs)
+{
+    __shared__ u64 constant;
+    const Mod m = mods[blockIdx.y];
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << n_power;
+    const bool with_constant = !b && z == 0; // the same for the whole workgroup
+    if (with_constant && threadIdx.x == 0) constant = real_constant_residue(value, m);
+    const ulonglong2 x = ld2(a + a_stride * item + (((u64) a_limbs * z) << n_power) + limb + c);
+    ulonglong2 r;
+    r.x = add_mod(x.x, x.x, m.q);
+    r.y = add_mod(x.y, x.y, m.q);
+    if (b) {
+        const ulonglong2 y = ld2(b + b_stride * item + (((u64) b_limbs * z) << n_power) + limb + c);
+        r.x = sub_mod(r.x, y.x, m.q);
+        r.y = sub_mod(r.y, y.y, m.q);
+    }
+    if (with_constant) {
+        __syncthreads();
+        r.x = sub_mod(r.x, constant, m.q);
+        r.y = sub_mod(r.y, constant, m.q);
+    }
+    st2(out + out_stride * item + (((u64) limbs * z) << n_power) + limb + c, r);
+}
+
+hipError_t rns_ckks_double_sub(const u64* a, u64 a_stride, int a_limbs, const u64* b, u64 b_stride, int b_limbs,
+                               double value, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs, int batch,
+                               hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (limbs < 1 || a_limbs < limbs || (b && b_limbs < limbs) || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ckks_double_sub, grid3(n_power, limbs, 2 * batch), dim3(RNS_THREADS), 0, st, a, a_stride, a_limbs, b,
+                       b_stride, b_limbs, value, out, out_stride, mods, n_power, limbs);
     return hipGetLastError();
 }
 

@@ -125,6 +125,21 @@ hipError_t rns_ckks_conj_merge(const u64* c0, u64 c0_stride, const u64* c1, u64 
                                const u64* psi_half, const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch,
                                hipStream_t st);
 
+// A leaf of the polynomial evaluator (evaluate_poly_from_polynomial_basis, ckks/operator.cu:4400-4484, in one pass):
+// out[p] = (p == 0 ? w_0 : 0) + sum_k w_k * terms[k][p] over the first `limbs` limbs, p = 0, 1.  terms / strides /
+// term_limbs / weights: HOST arrays of `count` <= 15 entries (count 0: the constant alone); term k has term_limbs[k] >=
+// limbs limbs per part and is read in place.  weights: (re, im) pairs, the Gaussian integers round(re) + round(im) i.
+// psi_half: DEVICE, psi^(N/2) per modulus.  out may overlap no term.  N >= 512.
+hipError_t rns_ckks_weighted_sum(const u64* const* terms, const u64* strides, const int* term_limbs, const double* weights,
+                                 int count, double w0_re, double w0_im, u64* out, u64 out_stride, const u64* psi_half,
+                                 const Mod* mods, int n_power, int limbs, int batch, hipStream_t st);
+// The tail of a Chebyshev power (gen_power, ckks/operator.cu:4355-4394, in one pass): out = 2 a - b over the first `limbs`
+// limbs of both parts; b == nullptr: round(value) is subtracted from part 0 instead.  a / b have a_limbs / b_limbs >=
+// limbs limbs per part.  out == a is allowed when a_limbs == limbs; out may overlap neither otherwise.
+hipError_t rns_ckks_double_sub(const u64* a, u64 a_stride, int a_limbs, const u64* b, u64 b_stride, int b_limbs,
+                               double value, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs, int batch,
+                               hipStream_t st);
+
 struct BehzDev {
     const Mod* ibase;       // q_0..q_{Q-1}
     const Mod* obase;       // Bsk

@@ -403,6 +403,79 @@ int hegpu_ckks_coeff_to_slot(hegpu_context* ctx, const uint64_t* ct, uint64_t ct
 int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
                              uint64_t c1_stride, uint64_t* out, uint64_t out_stride, const hegpu_linear_factor* factors,
                              int count, int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+/* ------------------------------------------------------------------ polynomial evaluation on a CKKS ciphertext
+ * (this backend's own entries: the reference's evaluate_poly, host/ckks/operator.cu:4292-4671, is protected and reachable
+ * only through its bootstraps).  Three layers: a host-only plan, two one-pass kernels, one sequence that executes a plan.
+ *
+ * PLAN.  hegpu_poly_eval_plan_size / _fill are host only (no context, no device) and reproduce the reference's schedule:
+ * baby powers 2^s - 1 .. 1 and giant powers 2^s .. 2^(D-1) with s = optimal_split(D), the recursion of
+ * evaluate_poly_recurse with its lead_ / max_deg_ rules and split_coeffs, its target-scale bookkeeping and its two
+ * conditional rescales.  basis: HEGPU_POLY_MONOMIAL or HEGPU_POLY_CHEBYSHEV (on [-1, 1]); coeffs: n_coeffs = degree + 1
+ * (re, im) pairs c_0 .. c_d; max_deg / lead: Polynomial::max_deg_ / lead_ (max_deg = degree and lead = 1 for a polynomial
+ * of its own); level / scale: of the input ciphertext (level = index of its last prime = Q - 1 - depth); primes: the
+ * context's q_0 .. q_{n_primes - 1}.  D is the bit length of the degree (the reference's ceil(log2(degree)) but for a
+ * power of two, where its first split reads a power it never made); the rescale of q compares with target_scale / 2.
+ * The plan is a list of steps over numbered registers: register 0 is the input, step k writes register k + 1, the last
+ * step's register is the result, at the level and scale that step carries.
+ *   POWER    dst = reg[a] * reg[b] at mul_level (the lower of the two), relinearized, rescaled; then c = HEGPU_POLY_TAIL_NONE:
+ *            nothing (monomial); HEGPU_POLY_TAIL_ONE: dst = 2 dst - round(tail_const); c >= 0: dst = 2 dst - reg[c]
+ *   LEAF     dst = w0 + sum_i w[i] * reg[term_reg[i]] over level + 1 limbs; w[i] = round(c_i * (leaf_scale / scale_i)),
+ *            w0 = round(c_0 * leaf_scale), real and imaginary part separately; terms with w[i] == 0 are left out
+ *   COMBINE  dst = reg[a] * reg[b] + reg[c]: reg[a] rescaled first if rescale_first, product at mul_level, relinearized,
+ *            sum at the lower of mul_level and reg[c]'s level; rescale_after (last step only): the sum is rescaled
+ * HEGPU_E_INVALID, outputs untouched: degree < 2, a leaf of more than 15 power terms (degree > 255), too few levels for
+ * the polynomial's depth, a non-finite coefficient or scale, max_deg < degree, n_steps not what _size gives. */
+enum { HEGPU_POLY_MONOMIAL = 0, HEGPU_POLY_CHEBYSHEV = 1 };
+enum { HEGPU_POLY_POWER = 0, HEGPU_POLY_LEAF = 1, HEGPU_POLY_COMBINE = 2 };
+enum { HEGPU_POLY_TAIL_NONE = -1, HEGPU_POLY_TAIL_ONE = -2 };
+typedef struct hegpu_poly_step {
+    int32_t kind, dst, a, b, c;
+    int32_t level;         /* of dst */
+    int32_t mul_level;     /* POWER, COMBINE */
+    int32_t rescale_first; /* COMBINE */
+    int32_t rescale_after; /* last step */
+    int32_t n_terms;       /* LEAF, <= 15 */
+    int32_t term_reg[15];
+    double scale;          /* of dst */
+    double tail_const;     /* POWER with HEGPU_POLY_TAIL_ONE */
+    double w0[2];          /* LEAF (re, im) */
+    double w[15][2];
+} hegpu_poly_step;
+int hegpu_poly_eval_plan_size(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
+                              double target_scale, const uint64_t* primes, int n_primes, int* n_steps);
+int hegpu_poly_eval_plan_fill(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
+                              double target_scale, const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps);
+/* KERNELS.  weighted_sum: out[p] = (p == 0 ? w0 : 0) + sum_k w_k * terms[k][p] mod q_j over the first `limbs` limbs, p = 0, 1.
+ * terms / term_strides / term_limbs / weights are HOST arrays of count <= 15 entries: term k is a DEVICE ciphertext
+ * [2][term_limbs[k]][N] per item (term_limbs[k] >= limbs; read in place, its part 1 term_limbs[k] * N words after part 0),
+ * items term_strides[k] apart; weights: (re, im) pairs of finite doubles, the Gaussian integer round(re) + round(im) i in
+ * every slot.  15 products of residues below 2^61 and a residue fit the 128-bit sum that is reduced once.  Bit-identical to
+ * hegpu_ckks_gaussian_integer_op (multiply) per term + hegpu_addition + hegpu_ckks_gaussian_integer_op (add) for w0.
+ * double_sub: out = 2 a - b over the first `limbs` limbs of both parts; b == NULL: round(value) is subtracted from part 0
+ * instead (|value| < 3.4e38).  a / b: [2][a_limbs / b_limbs][N] per item, both >= limbs.  Bit-identical to
+ * hegpu_addition(a, a) + hegpu_addition (op 1) resp. hegpu_ckks_constant_op (HEGPU_CONST_SUB).
+ * HEGPU_E_INVALID, out untouched: count outside [0, 15], a limb count outside [limbs, Q], a non-finite weight, batch < 1,
+ * out overlapping a term or b; out overlapping a unless it is a itself with a_limbs == limbs (in place). */
+int hegpu_ckks_weighted_sum(hegpu_context* ctx, const uint64_t* const* terms, const uint64_t* term_strides,
+                            const int* term_limbs, const double* weights, int count, double w0_re, double w0_im,
+                            uint64_t* out, uint64_t out_stride, int limbs, int batch, hegpu_stream stream);
+int hegpu_ckks_double_sub(hegpu_context* ctx, const uint64_t* a, uint64_t a_stride, int a_limbs, const uint64_t* b,
+                          uint64_t b_stride, int b_limbs, double value, uint64_t* out, uint64_t out_stride, int limbs,
+                          int batch, hegpu_stream stream);
+/* SEQUENCE.  Executes a plan on ct ([2][Q - depth][N] per item, the plan's input level = Q - 1 - depth) and nothing else:
+ * POWER = hegpu_ckks_multiply + _relinearize_inplace + _rescale_inplace + one double_sub; LEAF = one weighted_sum;
+ * COMBINE = the rescale, multiply, relinearize + one sum at the lower level.  An operand above the level of a product or
+ * sum is copied down first.  One polynomial and one level serve the whole batch.  out receives the last step's register:
+ * it needs room for [2][level + 1 + rescale_after][N] per item and holds [2][level + 1][N] on return, at the depth
+ * Q - 1 - level and the scale of the plan's last step.  Bit-identical to the same plan executed with the single entries.
+ * HEGPU_E_INVALID before anything is queued: a workspace below hegpu_ckks_poly_eval_workspace_bytes (0 for a plan it cannot
+ * size), out overlapping ct, a register or level number out of range, more than 4096 steps, a tail constant that is not
+ * finite or not below 3.4e38, a non-finite weight, null pointers, batch < 1. */
+size_t hegpu_ckks_poly_eval_workspace_bytes(const hegpu_context* ctx, const hegpu_poly_step* plan, int n_steps, int depth,
+                                            int batch);
+int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out, uint64_t out_stride,
+                         const hegpu_poly_step* plan, int n_steps, const uint64_t* relin_key, int depth, int batch,
+                         void* ws, size_t ws_bytes, hegpu_stream stream);
 /* multiply_bfv (src/lib/host/bfv/operator.cu:336-430): coefficient domain,
  * ct [2][Q][N] x [2][Q][N] -> out [3][Q][N] */
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_stride, const uint64_t* ct2,

@@ -2277,6 +2277,31 @@ template <> class LinearTransform<Scheme::CKKS> {
     int depth_ = 0, n_diag_ = 0;
 };
 
+// ------------------------------------------------------------------ polynomials evaluated on ciphertexts
+// host/ckks/operator.cuh:1902-1937 (there a class nested in HEOperator<CKKS>) and PolyType.  coeffs_[i] multiplies x^i
+// (MONOMIAL) or T_i(x), x in [-1, 1] (CHEBYSHEV); max_deg_ / lead_ steer the split of evaluate_poly as in the reference
+// (a polynomial of its own: max_deg = its degree, lead = true); a_ / b_ record the interval a caller mapped to [-1, 1].
+enum class PolyType { MONOMIAL, CHEBYSHEV };
+class Polynomial {
+  public:
+    Polynomial() : type_(PolyType::CHEBYSHEV), max_deg_(0), lead_(false), a_(0.0), b_(0.0) {}
+    Polynomial(int max_deg, const std::vector<Complex64>& coeffs, bool lead = false, PolyType type = PolyType::CHEBYSHEV,
+               double a = 0.0, double b = 0.0)
+        : type_(type), max_deg_(max_deg), coeffs_(coeffs), lead_(lead), a_(a), b_(b)
+    {
+    }
+    int degree() const { return (int) coeffs_.size() - 1; }
+    // ceil(log2(degree + 1)), the bit length of the degree: the levels evaluate_poly spends.  The reference's depth() is
+    // ceil(log2(degree)); the two differ for a degree that is a power of two only, where the reference's first split reads a
+    // power it never made (the plan's first departure, hegpu.h)
+    int depth() const { return (int) std::ceil(std::log2((double) coeffs_.size())); }
+    PolyType type_;
+    int max_deg_;
+    std::vector<Complex64> coeffs_;
+    bool lead_;
+    double a_, b_;
+};
+
 // ------------------------------------------------------------------ CoeffToSlot / SlotToCoeff context
 // host/ckks/operator.cuh:29-82.  The reference keeps pre-baked index tensors of its Vandermonde generator; here the
 // factors are LinearTransform objects over the groups of hegpu_encoding_transform_shape / _fill.
@@ -2703,6 +2728,52 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         result.depth_ = out_depth;
         result.scale_ = sc;
         result.encoding_ = encoding::COEFFICIENT;
+        return result;
+    }
+
+    // pol(cipher) by the reference's baby-step/giant-step schedule (host/ckks/operator.cu:4629-4671 with gen_power,
+    // evaluate_poly_recurse, evaluate_poly_from_polynomial_basis): hegpu_poly_eval_plan_* + hegpu_ckks_poly_eval.  In the
+    // reference the evaluator is protected and reachable only through its bootstraps; making it public is this backend's
+    // own decision (sigmoid, comparison, inverse are what a user reaches for it for).  The result carries the plan's depth
+    // and scale, relinearized and rescaled.
+    Ciphertext<S> evaluate_poly(Ciphertext<S>& cipher, double target_scale, const Polynomial& pol, Relinkey<S>& relin_key,
+                                const ExecutionOptions& o = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "polynomial evaluation is a CKKS operation");
+        detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
+        check_plain_two_part(cipher);
+        if (!cipher.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
+        {
+            const int Q = context_->Q_size, Qp = context_->Q_prime_size, P = context_->P_size;
+            const size_t d = P == 1 ? (size_t) Q : (size_t) (Q + P - 1) / P;
+            if (!relin_key.relin_key_generated_ || relin_key.size() != 2 * d * (size_t) Qp * context_->n)
+                throw std::invalid_argument("Relinkey does not belong to this context!");
+        }
+        const int Q = context_->Q_size, level = Q - 1 - cipher.depth_;
+        std::vector<uint64_t> primes((size_t) Q);
+        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        const int basis = pol.type_ == PolyType::MONOMIAL ? HEGPU_POLY_MONOMIAL : HEGPU_POLY_CHEBYSHEV;
+        const double* cf = reinterpret_cast<const double*>(pol.coeffs_.data());
+        int n_steps = 0;
+        detail::check(hegpu_poly_eval_plan_size(basis, cf, (int) pol.coeffs_.size(), pol.max_deg_, pol.lead_ ? 1 : 0, level,
+                                                cipher.scale_, target_scale, primes.data(), Q, &n_steps)); // too few levels: invalid_argument
+        std::vector<hegpu_poly_step> plan((size_t) n_steps);
+        detail::check(hegpu_poly_eval_plan_fill(basis, cf, (int) pol.coeffs_.size(), pol.max_deg_, pol.lead_ ? 1 : 0, level,
+                                                cipher.scale_, target_scale, primes.data(), Q, plan.data(), n_steps));
+        const hegpu_poly_step& last = plan.back();
+        const size_t n = context_->n;
+        const size_t wsb = hegpu_ckks_poly_eval_workspace_bytes(context_->handle(), plan.data(), n_steps, cipher.depth_, 1);
+        DeviceVector<Data64> ws(wsb / 8, o.stream_), m(2 * n * (size_t) (last.level + 1 + last.rescale_after), o.stream_);
+        detail::check(hegpu_ckks_poly_eval(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m.data(), 0,
+                                           plan.data(), n_steps, (const uint64_t*) relin_key.data(), cipher.depth_, 1,
+                                           ws.data(), wsb, o.stream_));
+        Ciphertext<S> result(context_);
+        copy_meta(cipher, result);
+        result.memory_set(std::move(m));
+        result.depth_ = Q - 1 - last.level;
+        result.scale_ = last.scale;
+        result.rescale_required_ = false;
+        result.relinearization_required_ = false;
         return result;
     }
 
