@@ -134,6 +134,14 @@ SIGNATURES = [
      [voidp, u64p, u64, u64p, u64p, u64, ctypes.POINTER(LinearFactor), c_int, u64p, c_int, c_int, voidp, c_size_t, voidp]),
     ("hegpu_ckks_slot_to_coeff", c_int,
      [voidp, u64p, u64, u64p, u64, u64p, u64, ctypes.POINTER(LinearFactor), c_int, c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_ckks_gate_combine", c_int,
+     [voidp, c_int, u64p, u64, c_int, u64p, c_int, u64, c_int, u64p, u64, c_int, ctypes.c_double, u64p, u64, c_int, c_int,
+      voidp]),
+    ("hegpu_bfv_gate_combine", c_int, [voidp, c_int, u64p, u64, u64p, c_int, u64, u64p, u64, u64p, u64, c_int, voidp]),
+    ("hegpu_ckks_logic_gate", c_int,
+     [voidp, c_int, u64p, u64, u64p, c_int, u64, u64p, ctypes.c_double, u64p, u64, c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_bfv_logic_gate", c_int,
+     [voidp, c_int, u64p, u64, u64p, c_int, u64, u64p, u64p, u64, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_multiply", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_relinearize_inplace", c_int, [voidp, u64p, u64, u64p, c_int, voidp, c_size_t, voidp]),
     ("hegpu_bfv_apply_galois", c_int,

@@ -25,6 +25,10 @@ OP_MPC_KEY_SHARE, OP_MPC_BFV_DECRYPT_MERGE = 18, 19
 OP_MPC_REFRESH_SHARE, OP_MPC_REFRESH_MERGE = 20, 21
 MPC_PUBLIC_KEY, MPC_GALOIS_KEY, MPC_RELIN_ROUND1 = 0, 1, 2
 TABLES_PLAIN = 2
+OP_CKKS_LOGIC_GATE, OP_BFV_LOGIC_GATE = 22, 23
+# the gates of the BFV / CKKS logic layer (the TFHE gates keep their own numbering: GATE_*)
+LOGIC_AND, LOGIC_OR, LOGIC_XOR, LOGIC_NAND, LOGIC_NOR, LOGIC_XNOR, LOGIC_NOT = range(7)
+GATE_B_NONE, GATE_B_CIPHER, GATE_B_PLAIN = 0, 1, 2
 
 E_INVALID, E_LOGIC, E_RUNTIME, E_NODEVICE = 10001, 10002, 10003, 10004
 
@@ -402,6 +406,32 @@ class Context:
         """hegpu_ckks_double_sub: out = 2 a - b on the first `limbs` limbs; b None: round(value) leaves part 0 instead"""
         _check(self._lib.hegpu_ckks_double_sub(self._h, _ptr(a), a_stride, a_limbs, _ptr(b), b_stride, b_limbs, float(value),
                                                _ptr(out), so, limbs, batch, stream if stream is not None else _stream()))
+
+    def ckks_gate_combine(self, gate, a, a_stride, a_limbs, b, b_kind, b_stride, b_limbs, p, p_stride, p_limbs, scale_one,
+                          out, so, limbs, batch=1, stream=None):
+        """hegpu_ckks_gate_combine: out = c0 * one + c1 * (a + b) + c2 * p on the first `limbs` limbs, one pass"""
+        _check(self._lib.hegpu_ckks_gate_combine(self._h, gate, _ptr(a), a_stride, a_limbs, _ptr(b), b_kind, b_stride, b_limbs,
+                                                 _ptr(p), p_stride, p_limbs, float(scale_one), _ptr(out), so, limbs, batch,
+                                                 stream if stream is not None else _stream()))
+
+    def bfv_gate_combine(self, gate, a, a_stride, b, b_kind, b_stride, p, p_stride, out, so, batch=1, stream=None):
+        """hegpu_bfv_gate_combine: the same in the coefficient domain, every operand at Q limbs"""
+        _check(self._lib.hegpu_bfv_gate_combine(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(p), p_stride,
+                                                _ptr(out), so, batch, stream if stream is not None else _stream()))
+
+    def ckks_logic_gate(self, gate, a, a_stride, b, b_kind, b_stride, relin_key, scale_one, out, so, depth, batch, ws,
+                        stream=None):
+        """hegpu_ckks_logic_gate: product sequence + one combine pass; out at depth + 1 (NOT: depth)"""
+        _check(self._lib.hegpu_ckks_logic_gate(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key),
+                                               float(scale_one), _ptr(out), so, depth, batch, _ptr(ws),
+                                               ws.numel() * 8 if ws is not None else 0,
+                                               stream if stream is not None else _stream()))
+
+    def bfv_logic_gate(self, gate, a, a_stride, b, b_kind, b_stride, relin_key, out, so, batch, ws, stream=None):
+        """hegpu_bfv_logic_gate: product sequence + one combine pass, coefficient domain"""
+        _check(self._lib.hegpu_bfv_logic_gate(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key),
+                                              _ptr(out), so, batch, _ptr(ws), ws.numel() * 8 if ws is not None else 0,
+                                              stream if stream is not None else _stream()))
 
     def poly_eval_workspace_bytes(self, plan, depth, batch):
         return int(self._lib.hegpu_ckks_poly_eval_workspace_bytes(self._h, plan.steps, len(plan.steps), depth, batch))

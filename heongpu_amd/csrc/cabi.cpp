@@ -1927,6 +1927,158 @@ int hegpu_bfv_multiply_plain(hegpu_context* ctx, const uint64_t* ct, const uint6
     });
 }
 
+// ---- logic gates (HELogicOperator<CKKS / BFV>): the one-pass combine alone, and the whole gate.  Every argument check
+// comes before the context is uploaded: a refusal queues nothing and needs no device.
+static int gate_batch_check(int batch, const char* who)
+{
+    if (batch < 0) return fail(HEGPU_E_INVALID, std::string(who) + ": batch must not be negative");
+    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, std::string(who) + ": at most 32767 items per call");
+    return 0;
+}
+
+// out against one operand: the operand itself (same address and stride, `limbs` limbs per part) or no common word
+static bool gate_operand_clear(const uint64_t* in, uint64_t in_stride, uint64_t in_words, bool may_alias, const uint64_t* out,
+                               uint64_t out_stride, uint64_t out_words, int batch)
+{
+    if (may_alias && in == out && in_stride == out_stride && in_words == out_words && (batch == 1 || out_stride >= out_words))
+        return true;
+    return !spans_overlap(in, in_stride, in_words, out, out_stride, out_words, batch);
+}
+
+static int gate_combine_entry(hegpu_context* ctx, int scheme, int gate, const uint64_t* a, uint64_t a_stride, int a_limbs,
+                              const uint64_t* b, int b_kind, uint64_t b_stride, int b_limbs, const uint64_t* p,
+                              uint64_t p_stride, int p_limbs, double scale_one, uint64_t* out, uint64_t out_stride,
+                              int limbs, int batch, hegpu_stream stream, const char* who)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    const Context& c = ctx->c;
+    const std::string w = who;
+    if (c.scheme != scheme) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    int k[3];
+    if (!logic_gate_coefficients(gate, k)) return fail(HEGPU_E_INVALID, w + ": unknown gate");
+    if (int r = gate_batch_check(batch, who)) return r;
+    if (batch == 0) return 0;
+    const bool unary = gate == LOGIC_NOT;
+    if (unary ? (b_kind != GATE_B_NONE || b || p) : (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN))
+        return fail(HEGPU_E_INVALID, w + ": NOT takes no second operand and no product, every other gate takes both");
+    if (!a || !out || (!unary && (!b || !p))) return fail(HEGPU_E_INVALID, w + ": null argument");
+    if (limbs < 1 || limbs > c.Q_size) return fail(HEGPU_E_INVALID, w + ": bad limb count");
+    if (a_limbs < limbs || a_limbs > c.Q_size || (!unary && (p_limbs < limbs || p_limbs > c.Q_size)) ||
+        (!unary && !(scheme == SCHEME_BFV && b_kind == GATE_B_PLAIN) && (b_limbs < limbs || b_limbs > c.Q_size)))
+        return fail(HEGPU_E_INVALID, w + ": an operand has fewer limbs than the result");
+    if (scheme == SCHEME_CKKS && (!(scale_one > 0) || scale_one >= 3.4e38))
+        return fail(HEGPU_E_INVALID, w + ": the scale of the constant one is positive and below 3.4e38");
+    const uint64_t n = c.n, out_words = (uint64_t) 2 * limbs * n;
+    if (!gate_operand_clear(a, a_stride, (uint64_t) 2 * a_limbs * n, true, out, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+    if (!unary) {
+        const bool cipher = b_kind == GATE_B_CIPHER;
+        const uint64_t b_words = cipher ? (uint64_t) 2 * b_limbs * n : scheme == SCHEME_BFV ? n : (uint64_t) b_limbs * n;
+        if (!gate_operand_clear(b, b_stride, b_words, cipher, out, out_stride, out_words, batch))
+            return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+        if (spans_overlap(p, p_stride, (uint64_t) 2 * p_limbs * n, out, out_stride, out_words, batch))
+            return fail(HEGPU_E_INVALID, w + ": out must not overlap the product");
+    }
+    NEED_CTX(ctx);
+    const bool bfv = scheme == SCHEME_BFV;
+    return hip_ret(rns_gate_combine(bfv, k[0], k[1], k[2], (const u64*) a, a_stride, a_limbs, (const u64*) b, b_kind, b_stride,
+                                    b_limbs, (const u64*) p, p_stride, p_limbs, scale_one,
+                                    bfv ? c.tab.coeff_div_plain_modulus : nullptr, bfv ? bfv_plain_scale(c) : BfvPlainScale{},
+                                    (u64*) out, out_stride, c.plan_qp.mods, c.n_power, limbs, batch, (hipStream_t) stream),
+                   who);
+}
+
+int hegpu_ckks_gate_combine(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, int a_limbs,
+                            const uint64_t* b, int b_kind, uint64_t b_stride, int b_limbs, const uint64_t* p,
+                            uint64_t p_stride, int p_limbs, double scale_one, uint64_t* out, uint64_t out_stride, int limbs,
+                            int batch, hegpu_stream stream)
+{
+    return gate_combine_entry(ctx, SCHEME_CKKS, gate, a, a_stride, a_limbs, b, b_kind, b_stride, b_limbs, p, p_stride,
+                              p_limbs, scale_one, out, out_stride, limbs, batch, stream, "hegpu_ckks_gate_combine");
+}
+
+int hegpu_bfv_gate_combine(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b,
+                           int b_kind, uint64_t b_stride, const uint64_t* p, uint64_t p_stride, uint64_t* out,
+                           uint64_t out_stride, int batch, hegpu_stream stream)
+{
+    const int Q = ctx ? ctx->c.Q_size : 0;
+    return gate_combine_entry(ctx, SCHEME_BFV, gate, a, a_stride, Q, b, b_kind, b_stride, Q, p, p_stride, Q, 0.0, out,
+                              out_stride, Q, batch, stream, "hegpu_bfv_gate_combine");
+}
+
+static int logic_gate_entry(hegpu_context* ctx, int scheme, int gate, const uint64_t* a, uint64_t a_stride,
+                            const uint64_t* b, int b_kind, uint64_t b_stride, const uint64_t* relin_key, double scale_one,
+                            uint64_t* out, uint64_t out_stride, int depth, int batch, void* ws, size_t ws_bytes,
+                            hegpu_stream stream, const char* who)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    const Context& c = ctx->c;
+    const std::string w = who;
+    const bool bfv = scheme == SCHEME_BFV;
+    if (c.scheme != scheme) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    int k[3];
+    if (!logic_gate_coefficients(gate, k)) return fail(HEGPU_E_INVALID, w + ": unknown gate");
+    if (int r = gate_batch_check(batch, who)) return r;
+    if (batch == 0) return 0;
+    if (depth < 0 || depth >= c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    const bool unary = gate == LOGIC_NOT;
+    if (unary ? (b_kind != GATE_B_NONE || b) : (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN))
+        return fail(HEGPU_E_INVALID, w + ": NOT takes no second operand, every other gate a ciphertext or a plaintext");
+    if (!a || !out || (!unary && !b) || (b_kind == GATE_B_CIPHER && !relin_key))
+        return fail(HEGPU_E_INVALID, w + ": null argument");
+    const int l = c.Q_size - depth;
+    if (!bfv && !unary && l < 2) return fail(HEGPU_E_INVALID, w + ": no modulus left to rescale the product by");
+    if (!bfv && (!(scale_one > 0) || scale_one >= 3.4e38))
+        return fail(HEGPU_E_INVALID, w + ": the scale of the constant one is positive and below 3.4e38");
+    const int op = bfv ? OP_BFV_LOGIC_GATE : OP_CKKS_LOGIC_GATE;
+    if (!unary && (!ws || ws_bytes < hegpu_workspace_bytes(ctx, op, depth, batch)))
+        return fail(HEGPU_E_INVALID, "workspace too small");
+    const uint64_t n = c.n, in_words = (uint64_t) 2 * l * n;
+    const uint64_t out_words = (uint64_t) 2 * (bfv || unary ? l : l - 1) * n;
+    if (!gate_operand_clear(a, a_stride, in_words, true, out, out_stride, out_words, batch))
+        return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+    if (!unary) {
+        const bool cipher = b_kind == GATE_B_CIPHER;
+        const uint64_t b_words = cipher ? in_words : bfv ? n : (uint64_t) l * n;
+        if (!gate_operand_clear(b, b_stride, b_words, cipher, out, out_stride, out_words, batch))
+            return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+        const uint64_t* wsp = (const uint64_t*) ws;
+        const uint64_t ws_words = ws_bytes / sizeof(uint64_t);
+        if (spans_overlap(wsp, 0, ws_words, out, out_stride, out_words, batch) ||
+            spans_overlap(wsp, 0, ws_words, a, a_stride, in_words, batch) ||
+            spans_overlap(wsp, 0, ws_words, b, b_stride, b_words, batch))
+            return fail(HEGPU_E_INVALID, w + ": the workspace must overlap neither out nor an operand");
+    }
+    NEED_CTX(ctx);
+    return guarded([&]() -> int {
+        if (bfv)
+            return hip_ret(op_bfv_logic_gate(c, gate, (const u64*) a, a_stride, (const u64*) b, b_kind, b_stride,
+                                             (const u64*) relin_key, (u64*) out, out_stride, batch, (u64*) ws,
+                                             (hipStream_t) stream),
+                           who);
+        return hip_ret(op_ckks_logic_gate(c, gate, (const u64*) a, a_stride, (const u64*) b, b_kind, b_stride,
+                                          (const u64*) relin_key, scale_one, (u64*) out, out_stride, depth, batch, (u64*) ws,
+                                          (hipStream_t) stream),
+                       who);
+    });
+}
+
+int hegpu_ckks_logic_gate(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b, int b_kind,
+                          uint64_t b_stride, const uint64_t* relin_key, double scale_one, uint64_t* out, uint64_t out_stride,
+                          int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    return logic_gate_entry(ctx, SCHEME_CKKS, gate, a, a_stride, b, b_kind, b_stride, relin_key, scale_one, out, out_stride,
+                            depth, batch, ws, ws_bytes, stream, "hegpu_ckks_logic_gate");
+}
+
+int hegpu_bfv_logic_gate(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b, int b_kind,
+                         uint64_t b_stride, const uint64_t* relin_key, uint64_t* out, uint64_t out_stride, int batch, void* ws,
+                         size_t ws_bytes, hegpu_stream stream)
+{
+    return logic_gate_entry(ctx, SCHEME_BFV, gate, a, a_stride, b, b_kind, b_stride, relin_key, 0.0, out, out_stride, 0,
+                            batch, ws, ws_bytes, stream, "hegpu_bfv_logic_gate");
+}
+
 // ------------------------------------------------------------------ TFHE
 struct hegpu_tfhe_context {
     TfheDev p{};

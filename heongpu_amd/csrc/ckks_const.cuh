@@ -1,6 +1,6 @@
 // ckks_const.cuh -- a double in the kernel arguments -> the residue of its nearest integer, for the kernels that add or
 // multiply a constant into every slot of an NTT-domain CKKS ciphertext (keygen.hip k_kg_ckks_constant / k_kg_ckks_gaussian,
-// rns.hip k_ckks_weighted_sum / k_ckks_double_sub).  One definition, so that all of them give the same residues.
+// rns.hip k_ckks_weighted_sum / k_ckks_double_sub / k_gate_combine).  One definition, so that all of them give the same residues.
 #pragma once
 #include "modarith.cuh"
 

@@ -219,16 +219,7 @@ hipError_t kg_sk_multiplication_ckks(const u64* ct, u64* plain, const u64* sk, c
     return hipGetLastError();
 }
 
-// D(m): limb y of the scaled plaintext, Delta * m + the rounding fix (tail of enc_div_lastq_bfv_kernel,
-// encryption.cu:158-172).  The 64-bit wrap-around and the detour through `int` are the reference's (:160-163).
-__device__ __forceinline__ u64 bfv_scaled_plain(u64 message, const Mod& m, u64 coeff_div, const BfvPlainScale& p)
-{
-    u64 fix = message * p.Q_mod_t;
-    fix = fix + p.upper_threshold;
-    fix = (u64) (long long) (int) (fix / p.t);
-    return add_mod(mul_barrett(message, coeff_div, m), fix, m.q);
-}
-
+// D(m), the scaled plaintext: bfv_scaled_plain of bfv_plain.cuh (shared with rns.hip k_gate_combine)
 __global__ __launch_bounds__(KG_THREADS) void k_kg_bfv_message_add(u64* __restrict__ ct, const u64* __restrict__ plain,
                                                                    const Mod* __restrict__ mods,
                                                                    const u64* __restrict__ coeff_div, BfvPlainScale p,

@@ -2,6 +2,7 @@
 // encryption and decryption; internal C++.
 #pragma once
 #include "drbg.hpp"
+#include "bfv_plain.cuh"
 
 namespace hegpu {
 
@@ -38,10 +39,6 @@ hipError_t kg_message_add(u64* ct, const u64* plain, const Mod* mods, int n_powe
 hipError_t kg_sk_multiplication_ckks(const u64* ct, u64* plain, const u64* sk, const Mod* mods, int n_power,
                                      int limbs, hipStream_t st);
 
-// the scalars of the scaled plaintext D(m) = Delta * m + the rounding fix (ops.cpp: bfv_plain_scale)
-struct BfvPlainScale {
-    u64 Q_mod_t, upper_threshold, t;
-};
 // BFV: part 0 of a fresh encryption gets D(m) (tail of enc_div_lastq_bfv_kernel, encryption.cu:158-172); plain [N] mod t,
 // ct [2][Q][N] coefficient domain
 hipError_t kg_bfv_message_add(u64* ct, const u64* plain, const Mod* mods, const u64* coeff_div, const BfvPlainScale& p,

@@ -221,6 +221,17 @@ size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
         case OP_MPC_REFRESH_MERGE:                                   // CKKS: t = c0 + sum h0; BFV: m' and the h0 sum beyond 16 shares
             per = c.scheme == SCHEME_CKKS ? (u64) l * n : (u64) (Q + 1) * n;
             break;
+        case OP_CKKS_LOGIC_GATE: { // one three-part product per item + the larger of relinearize and rescale
+            const size_t relin = ops_workspace_elems(c, OP_CKKS_RELIN, depth, batch);
+            const size_t resc = ops_workspace_elems(c, OP_CKKS_RESCALE, depth, batch);
+            return (u64) 3 * l * n * (u64) batch + (relin > resc ? relin : resc);
+        }
+        case OP_BFV_LOGIC_GATE: { // one three-part product per item + the largest of multiply, relinearize, multiply-plain
+            size_t most = ops_workspace_elems(c, OP_BFV_MULTIPLY, 0, batch);
+            for (int o : {OP_BFV_RELIN, OP_BFV_MULTIPLY_PLAIN})
+                if (ops_workspace_elems(c, o, 0, batch) > most) most = ops_workspace_elems(c, o, 0, batch);
+            return (u64) 3 * Q * n * (u64) batch + most;
+        }
         default: return 0;
     }
     return per * (u64) batch;
@@ -1112,6 +1123,64 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
         }
     }
     return hipSuccess;
+}
+
+// ------------------------------------------------------------------ logic gates
+hipError_t op_ckks_logic_gate(const Context& c, int gate, const u64* a, u64 as, const u64* b, int b_kind, u64 bs,
+                              const u64* relin_key, double scale_one, u64* out, u64 so, int depth, int batch, u64* ws,
+                              hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    int k[3];
+    if (!logic_gate_coefficients(gate, k)) return hipErrorInvalidValue;
+    const int np = c.n_power, l = c.Q_size - depth;
+    const Mod* mods = c.plan_qp.mods;
+    const BfvPlainScale none{};
+    if (gate == LOGIC_NOT)
+        return rns_gate_combine(false, k[0], k[1], k[2], a, as, l, nullptr, GATE_B_NONE, 0, 0, nullptr, 0, 0, scale_one,
+                                nullptr, none, out, so, mods, np, l, batch, st);
+    if (l < 2 || (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN)) return hipErrorInvalidValue;
+    const u64 ps = (u64) 3 * l * c.n;
+    u64* prod = ws;
+    u64* ks = ws + ps * batch;
+    if (b_kind == GATE_B_CIPHER) {
+        TRY(op_ckks_multiply(c, a, as, b, bs, prod, ps, depth, batch, st));
+        TRY(op_ckks_relinearize(c, prod, ps, relin_key, depth, batch, ks, st));
+    } else {
+        for (int i = 0; i < batch; i++) // cipherplain_kernel takes one ciphertext
+            TRY(kg_pk_u(a + as * i, b + bs * i, prod + ps * i, mods, np, l, st));
+    }
+    TRY(op_ckks_rescale(c, prod, ps, depth, batch, ks, st));
+    return rns_gate_combine(false, k[0], k[1], k[2], a, as, l, b, b_kind, bs, l, prod, ps, l - 1, scale_one, nullptr, none,
+                            out, so, mods, np, l - 1, batch, st);
+}
+
+hipError_t op_bfv_logic_gate(const Context& c, int gate, const u64* a, u64 as, const u64* b, int b_kind, u64 bs,
+                             const u64* relin_key, u64* out, u64 so, int batch, u64* ws, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    int k[3];
+    if (!logic_gate_coefficients(gate, k)) return hipErrorInvalidValue;
+    const int np = c.n_power, Q = c.Q_size;
+    const Mod* mods = c.plan_qp.mods;
+    const u64* cd = c.tab.coeff_div_plain_modulus;
+    const BfvPlainScale scale = bfv_plain_scale(c);
+    if (gate == LOGIC_NOT)
+        return rns_gate_combine(true, k[0], k[1], k[2], a, as, Q, nullptr, GATE_B_NONE, 0, 0, nullptr, 0, 0, 0.0, cd, scale,
+                                out, so, mods, np, Q, batch, st);
+    if (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN) return hipErrorInvalidValue;
+    const u64 ps = (u64) 3 * Q * c.n;
+    u64* prod = ws;
+    u64* ks = ws + ps * batch;
+    if (b_kind == GATE_B_CIPHER) {
+        TRY(op_bfv_multiply(c, a, as, b, bs, prod, ps, batch, ks, st));
+        TRY(op_bfv_relinearize(c, prod, ps, relin_key, batch, ks, st));
+    } else {
+        for (int i = 0; i < batch; i++) // multiply_plain_bfv takes one ciphertext
+            TRY(op_bfv_multiply_plain(c, a + as * i, b + bs * i, prod + ps * i, ks, st));
+    }
+    return rns_gate_combine(true, k[0], k[1], k[2], a, as, Q, b, b_kind, bs, Q, prod, ps, Q, 0.0, cd, scale, out, so, mods,
+                            np, Q, batch, st);
 }
 
 // ------------------------------------------------------------------ keygen / encrypt / decrypt

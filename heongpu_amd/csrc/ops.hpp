@@ -10,7 +10,8 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
        OP_BFV_GALOIS = 6, OP_KEYGEN_SECRET = 7, OP_KEYGEN_PUBLIC = 8, OP_KEYGEN_SWITCH = 9, OP_CKKS_ENCRYPT = 10, OP_BFV_ENCRYPT = 11,
        OP_BFV_DECRYPT = 12, OP_BFV_DECODE = 13, OP_CKKS_ENCODE = 14,
        OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17, OP_MPC_KEY_SHARE = 18,
-       OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21 };
+       OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21, OP_CKKS_LOGIC_GATE = 22,
+       OP_BFV_LOGIC_GATE = 23 };
 
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
@@ -90,6 +91,21 @@ const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, in
 size_t ops_poly_eval_workspace_elems(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch);
 hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::PolyStep* plan,
                              int n_steps, const u64* relin_key, int depth, int batch, u64* ws, hipStream_t st);
+
+// ---- logic gates on bits held as 0 / 1 (HELogicOperator<CKKS / BFV>, host/ckks/operator.cuh:2333-3500,
+// host/bfv/operator.cuh:1324-2230): the product sequence of the arithmetic operator into the workspace, then ONE
+// rns_gate_combine pass that reads a, b and the product in place and writes out (AND: the pass is its copy out of the
+// workspace).  NOT is the pass alone.  b_kind: GATE_B_CIPHER (multiply, relinearize, CKKS: rescale) or GATE_B_PLAIN
+// (CKKS: cipherplain product with b [l][N] per item, rescale; BFV: op_bfv_multiply_plain with b [N] per item); a plaintext
+// shared by the batch has b_stride 0.  CKKS: a, b at `depth` (l = Q - depth limbs), out [2][l - 1][N] (NOT: [2][l][N]);
+// BFV: everything [2][Q][N], coefficient domain.  Workspace OP_CKKS_LOGIC_GATE / OP_BFV_LOGIC_GATE: one three-part product
+// per item and the largest workspace of the sequence.
+// gate: LOGIC_* (rns.hpp)
+hipError_t op_ckks_logic_gate(const Context& c, int gate, const u64* a, u64 as, const u64* b, int b_kind, u64 bs,
+                              const u64* relin_key, double scale_one, u64* out, u64 so, int depth, int batch, u64* ws,
+                              hipStream_t st);
+hipError_t op_bfv_logic_gate(const Context& c, int gate, const u64* a, u64 as, const u64* b, int b_kind, u64 bs,
+                             const u64* relin_key, u64* out, u64 so, int batch, u64* ws, hipStream_t st);
 
 // ---- key generation / encryption / decryption, key-switch method I
 // The generator state: every sampling call consumes one stream id of the DRBG (drbg.hpp).

@@ -1479,4 +1479,142 @@ hipError_t rns_ckks_double_sub(const u64* a, u64 a_stride, int a_limbs, const u6
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- logic gates: everything after the product in one pass
+// A gate on bits held as 0 / 1 is c0 * 1 + c1 * (a + b) + c2 * (a * b):
+//   AND (0, 0, 1)   OR (0, 1, -1)   XOR (0, 1, -2)   NAND (1, 0, -1)   NOR (1, -1, 1)   XNOR (1, -1, 2)   NOT (1, -1, -)
+// The reference's HELogicOperator<BFV / CKKS> (host/bfv/operator.cuh:1324-2230, host/ckks/operator.cuh:2333-3500) builds the
+// part after the product p = a * b from separate element-wise launches -- add(p, p), add(a, b), mod_drop copies, sub,
+// negate, the plaintext add of an encoded one: 13 to 17 reads and writes of a ciphertext.  Here the thread that owns two
+// adjacent coefficients of a limb reads a, b and p once, in place at whatever limb count they sit (only the first `limbs`
+// limbs of a part are read: in CKKS a and b are one level above p), and writes the result once.
+//   b: none, a ciphertext (both parts), or a plaintext (part 0 only; CKKS: [b_limbs][N] NTT-domain residues, BFV: [N]
+//   residues mod t that enter as D(m), bfv_plain.cuh -- the residues of k_kg_bfv_plain_addsub).
+//   The constant one: CKKS round(scale_one) in every NTT position of part 0 (ckks_const.cuh, lane 0 leaves its residue in
+//   LDS as in k_ckks_double_sub); BFV D(1) on coefficient 0 of part 0 (the polynomial 1: the reference's
+//   encoded_constant_one_ is the inverse transform of the all-ones vector).
+// Additions and subtractions are the modular ones of k_addition on canonical residues, so every word is the word that the
+// chain of single passes gives.  out may be a or b itself when that operand has `limbs` limbs per part and the stride of
+// out (each thread reads its two words of every operand before it writes them): no __restrict__ on these.
+struct GateCombineArgs {
+    const u64 *a, *b, *p;
+    u64 a_stride, b_stride, p_stride;
+    int a_limbs, b_limbs, p_limbs;
+    int b_kind;
+    int c0, c1, c2;
+    u64* out;
+    u64 out_stride;
+    const Mod* mods;
+    int n_power, limbs;
+    double scale_one;     // CKKS
+    const u64* coeff_div; // BFV: floor(Q / t) mod q_j
+    BfvPlainScale ps;     // BFV
+};
+
+template <bool BFV>
+__global__ __launch_bounds__(RNS_THREADS) void k_gate_combine(GateCombineArgs g)
+{
+    __shared__ u64 one;
+    const Mod m = g.mods[blockIdx.y];
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const int np = g.n_power;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << np;
+    const bool with_one = g.c0 && z == 0;                                   // the same for the whole workgroup
+    const bool b_cipher = g.c1 && g.b_kind == GATE_B_CIPHER;                // ...
+    const bool b_plain = g.c1 && g.b_kind == GATE_B_PLAIN && z == 0;        // ...
+    if (!BFV && with_one && threadIdx.x == 0) one = real_constant_residue(g.scale_one, m);
+    // at most three 16-byte loads in flight, all issued before the first use
+    ulonglong2 s{0, 0}, y{0, 0}, pp{0, 0};
+    if (g.c1) s = ld2(g.a + g.a_stride * item + (((u64) g.a_limbs * z) << np) + limb + c);
+    if (b_cipher) y = ld2(g.b + g.b_stride * item + (((u64) g.b_limbs * z) << np) + limb + c);
+    else if (b_plain) y = ld2(g.b + g.b_stride * item + (BFV ? 0 : limb) + c);
+    if (g.c2) pp = ld2(g.p + g.p_stride * item + (((u64) g.p_limbs * z) << np) + limb + c);
+    if (BFV && b_plain) {
+        const u64 cd = g.coeff_div[blockIdx.y];
+        y.x = bfv_scaled_plain(y.x, m, cd, g.ps);
+        y.y = bfv_scaled_plain(y.y, m, cd, g.ps);
+    }
+    if (b_cipher || b_plain) {
+        s.x = add_mod(s.x, y.x, m.q);
+        s.y = add_mod(s.y, y.y, m.q);
+    }
+    ulonglong2 r{0, 0};
+    if (with_one) {
+        if (BFV) {
+            if (c == 0) r.x = bfv_scaled_plain(1, m, g.coeff_div[blockIdx.y], g.ps);
+        } else {
+            __syncthreads();
+            r.x = r.y = one;
+        }
+    }
+    if (g.c1 > 0) {
+        r.x = add_mod(r.x, s.x, m.q);
+        r.y = add_mod(r.y, s.y, m.q);
+    } else if (g.c1 < 0) {
+        r.x = sub_mod(r.x, s.x, m.q);
+        r.y = sub_mod(r.y, s.y, m.q);
+    }
+    if (g.c2) {
+        if (g.c2 == 2 || g.c2 == -2) {
+            pp.x = add_mod(pp.x, pp.x, m.q);
+            pp.y = add_mod(pp.y, pp.y, m.q);
+        }
+        if (g.c2 > 0) {
+            r.x = add_mod(r.x, pp.x, m.q);
+            r.y = add_mod(r.y, pp.y, m.q);
+        } else {
+            r.x = sub_mod(r.x, pp.x, m.q);
+            r.y = sub_mod(r.y, pp.y, m.q);
+        }
+    }
+    st2(g.out + g.out_stride * item + (((u64) g.limbs * z) << np) + limb + c, r);
+}
+
+bool logic_gate_coefficients(int gate, int coeff[3])
+{
+    static const int rows[7][3] = {{0, 0, 1}, {0, 1, -1}, {0, 1, -2}, {1, 0, -1}, {1, -1, 1}, {1, -1, 2}, {1, -1, 0}};
+    if (gate < LOGIC_AND || gate > LOGIC_NOT) return false;
+    for (int i = 0; i < 3; i++) coeff[i] = rows[gate][i];
+    return true;
+}
+
+static bool gate_coefficients_ok(int c0, int c1, int c2)
+{
+    int r[3];
+    for (int gate = LOGIC_AND; logic_gate_coefficients(gate, r); gate++)
+        if (r[0] == c0 && r[1] == c1 && r[2] == c2) return true;
+    return false;
+}
+
+hipError_t rns_gate_combine(bool bfv, int c0, int c1, int c2, const u64* a, u64 a_stride, int a_limbs, const u64* b,
+                            int b_kind, u64 b_stride, int b_limbs, const u64* p, u64 p_stride, int p_limbs,
+                            double scale_one, const u64* coeff_div, const BfvPlainScale& ps, u64* out, u64 out_stride,
+                            const Mod* mods, int n_power, int limbs, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (!gate_coefficients_ok(c0, c1, c2) || limbs < 1 || n_power < 9 || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    if (!out || b_kind < GATE_B_NONE || b_kind > GATE_B_PLAIN) return hipErrorInvalidValue;
+    if (c2 == 0 && (p || b_kind != GATE_B_NONE)) return hipErrorInvalidValue; // NOT: no product, no second operand
+    if (c2 != 0 && (!p || p_limbs < limbs)) return hipErrorInvalidValue;
+    if (c1 != 0) {
+        if (!a || a_limbs < limbs) return hipErrorInvalidValue;
+        if (c2 != 0 && (b_kind == GATE_B_NONE || !b)) return hipErrorInvalidValue;
+        if (b_kind == GATE_B_CIPHER && b_limbs < limbs) return hipErrorInvalidValue;
+        if (b_kind == GATE_B_PLAIN && !bfv && b_limbs < limbs) return hipErrorInvalidValue;
+    }
+    if (bfv && !coeff_div) return hipErrorInvalidValue;
+    GateCombineArgs g{};
+    g.a = a; g.b = b; g.p = p;
+    g.a_stride = a_stride; g.b_stride = b_stride; g.p_stride = p_stride;
+    g.a_limbs = a_limbs; g.b_limbs = b_limbs; g.p_limbs = p_limbs;
+    g.b_kind = b_kind;
+    g.c0 = c0; g.c1 = c1; g.c2 = c2;
+    g.out = out; g.out_stride = out_stride;
+    g.mods = mods; g.n_power = n_power; g.limbs = limbs;
+    g.scale_one = scale_one; g.coeff_div = coeff_div; g.ps = ps;
+    const dim3 grid = grid3(n_power, limbs, 2 * batch);
+    if (bfv) hipLaunchKernelGGL(k_gate_combine<true>, grid, dim3(RNS_THREADS), 0, st, g);
+    else hipLaunchKernelGGL(k_gate_combine<false>, grid, dim3(RNS_THREADS), 0, st, g);
+    return hipGetLastError();
+}
+
 } // namespace hegpu

@@ -4,6 +4,7 @@
 // ciphertexts of a batch `*_stride` elements apart.
 #pragma once
 #include "modarith.cuh"
+#include "bfv_plain.cuh"
 
 namespace hegpu {
 
@@ -139,6 +140,26 @@ hipError_t rns_ckks_weighted_sum(const u64* const* terms, const u64* strides, co
 hipError_t rns_ckks_double_sub(const u64* a, u64 a_stride, int a_limbs, const u64* b, u64 b_stride, int b_limbs,
                                double value, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs, int batch,
                                hipStream_t st);
+
+// Everything after the product of a logic gate in one pass (HELogicOperator<BFV / CKKS>, host/bfv/operator.cuh:1324-2230,
+// host/ckks/operator.cuh:2333-3500: add, add, mod_drop copies, sub, negate and the plaintext add of an encoded one as
+// separate launches): out = c0 * one * [part 0] + c1 * (a + b) + c2 * p over the first `limbs` limbs of both parts, with
+// (c0, c1, c2) a row of AND (0,0,1) OR (0,1,-1) XOR (0,1,-2) NAND (1,0,-1) NOR (1,-1,1) XNOR (1,-1,2) NOT (1,-1,0).
+// a / b / p: [2][a_limbs / b_limbs / p_limbs][N] per item, each >= limbs, read in place; a is not read when c1 == 0, p is
+// nullptr exactly when c2 == 0 (NOT, which has no b either).  b_kind GATE_B_PLAIN: part 0 only; CKKS (bfv == false): NTT
+// domain, b = [b_limbs][N] residues, one = round(scale_one) in every position; BFV: coefficient domain, b = [N] residues
+// mod t entering as D(m) (bfv_plain.cuh, coeff_div = floor(Q / t) mod q_j on the DEVICE), one = D(1) on coefficient 0.
+// out may be a or b itself (same stride) when that operand has exactly `limbs` limbs; it may overlap nothing otherwise.
+// N >= 512.  hipErrorInvalidValue: limbs < 1, an input limb count below limbs, 2 * batch > 65535, coefficients that are
+// no row of the table, operands that do not fit the row.
+enum { GATE_B_NONE = 0, GATE_B_CIPHER = 1, GATE_B_PLAIN = 2 };
+enum { LOGIC_AND = 0, LOGIC_OR = 1, LOGIC_XOR = 2, LOGIC_NAND = 3, LOGIC_NOR = 4, LOGIC_XNOR = 5, LOGIC_NOT = 6 };
+// the row (c0, c1, c2) of a gate; false: no such gate
+bool logic_gate_coefficients(int gate, int coeff[3]);
+hipError_t rns_gate_combine(bool bfv, int c0, int c1, int c2, const u64* a, u64 a_stride, int a_limbs, const u64* b,
+                            int b_kind, u64 b_stride, int b_limbs, const u64* p, u64 p_stride, int p_limbs,
+                            double scale_one, const u64* coeff_div, const BfvPlainScale& ps, u64* out, u64 out_stride,
+                            const Mod* mods, int n_power, int limbs, int batch, hipStream_t st);
 
 struct BehzDev {
     const Mod* ibase;       // q_0..q_{Q-1}

@@ -271,7 +271,9 @@ enum {
     HEGPU_OP_MPC_KEY_SHARE = 18,        /* every hegpu_mpc_*_key_share* entry */
     HEGPU_OP_MPC_BFV_DECRYPT_MERGE = 19, /* per ciphertext of the batch */
     HEGPU_OP_MPC_REFRESH_SHARE = 20,     /* hegpu_mpc_*_refresh_share: 0 bytes, the share is built in place */
-    HEGPU_OP_MPC_REFRESH_MERGE = 21      /* hegpu_mpc_*_refresh_merge; per item: CKKS (Q - depth) N words, BFV (Q + 1) N */
+    HEGPU_OP_MPC_REFRESH_MERGE = 21,     /* hegpu_mpc_*_refresh_merge; per item: CKKS (Q - depth) N words, BFV (Q + 1) N */
+    HEGPU_OP_CKKS_LOGIC_GATE = 22,       /* hegpu_ckks_logic_gate: a three-part product per item + the larger of RELIN, RESCALE */
+    HEGPU_OP_BFV_LOGIC_GATE = 23         /* hegpu_bfv_logic_gate: the same + the largest of MULTIPLY, RELIN, MULTIPLY_PLAIN */
 };
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch);
 
@@ -734,6 +736,56 @@ int hegpu_negacyclic_shift(hegpu_context* ctx, const uint64_t* in, uint64_t* out
                            hegpu_stream stream);
 int hegpu_bfv_multiply_plain(hegpu_context* ctx, const uint64_t* ct, const uint64_t* plain, uint64_t* out, void* ws,
                              size_t ws_bytes, hegpu_stream stream);
+
+/* ------------------------------------------------------------------ logic gates on encrypted bits (BFV / CKKS)
+ * HELogicOperator<Scheme::BFV> (src/include/heongpu/host/bfv/operator.cuh:1324-2230, src/lib/host/bfv/operator.cu:1520-1575)
+ * and HELogicOperator<Scheme::CKKS> (host/ckks/operator.cuh:2333-3500, src/lib/host/ckks/operator.cu:7329-7346, :8195-8225):
+ * a bit is the value 0 or 1 in a slot, and every gate is  c0 * 1 + c1 * (a + b) + c2 * (a * b):
+ *   AND (0,0,1)  OR (0,1,-1)  XOR (0,1,-2)  NAND (1,0,-1)  NOR (1,-1,1)  XNOR (1,-1,2)  NOT (1,-1; no b, no product)
+ * The numbering is this enum's own (the TFHE gates below keep theirs: HEGPU_GATE_*). */
+enum {
+    HEGPU_LOGIC_AND = 0, HEGPU_LOGIC_OR = 1, HEGPU_LOGIC_XOR = 2, HEGPU_LOGIC_NAND = 3, HEGPU_LOGIC_NOR = 4,
+    HEGPU_LOGIC_XNOR = 5, HEGPU_LOGIC_NOT = 6
+};
+enum { HEGPU_GATE_B_NONE = 0, HEGPU_GATE_B_CIPHER = 1, HEGPU_GATE_B_PLAIN = 2 }; /* the second operand of a gate */
+/* The part of a gate after the product p = a * b, in ONE pass: reads a, b and p in place, writes out.  The reference
+ * chains add(p, p), add(a, b), mod_drop copies, sub, negate (one_minus_cipher, ckks/operator.cu:7329-7346) and the
+ * plaintext add of its encoded_constant_one_ as separate launches (host/ckks/operator.cuh:2528-3230, each "TODO: make it
+ * efficient").  out = c0 * one * [part 0] + c1 * (a + b) + c2 * p over the first `limbs` limbs of both parts, canonical.
+ *   a, p: [2][a_limbs / p_limbs][N] per item, each >= limbs, only the first `limbs` limbs of a part are read (CKKS: a and
+ *   b sit one level above p).  b: HEGPU_GATE_B_CIPHER [2][b_limbs][N]; HEGPU_GATE_B_PLAIN, added to part 0 only: CKKS
+ *   [b_limbs][N] NTT-domain residues, BFV [N] residues mod t that enter as floor(Q/t) m + fix, the residues of
+ *   hegpu_bfv_plain_addsub; a plaintext shared by all items has b_stride 0.  NOT: b_kind HEGPU_GATE_B_NONE, b and p NULL.
+ *   one: CKKS round(scale_one) in every NTT position (the residue hegpu_ckks_constant_op adds); BFV the scaled plaintext
+ *   of m = 1 on coefficient 0 (the polynomial 1).  BFV: coefficient domain, every limb count is Q.
+ * Bit-identical to the chain hegpu_addition / hegpu_ckks_constant_op / hegpu_bfv_plain_addsub on the kept limbs.
+ * out may be a, or a ciphertext b, itself (same address and stride) when that operand has exactly `limbs` limbs -- BFV
+ * always, a CKKS NOT.  HEGPU_E_INVALID before anything is queued (no device needed): any other overlap of out with an
+ * input, an unknown gate, operands that do not fit the gate, a limb count outside [limbs, Q], 2 * batch > 65535,
+ * batch < 0, scale_one not in (0, 3.4e38), the wrong scheme.  batch == 0: no-op. */
+int hegpu_ckks_gate_combine(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, int a_limbs,
+                            const uint64_t* b, int b_kind, uint64_t b_stride, int b_limbs, const uint64_t* p,
+                            uint64_t p_stride, int p_limbs, double scale_one, uint64_t* out, uint64_t out_stride, int limbs,
+                            int batch, hegpu_stream stream);
+int hegpu_bfv_gate_combine(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b,
+                           int b_kind, uint64_t b_stride, const uint64_t* p, uint64_t p_stride, uint64_t* out,
+                           uint64_t out_stride, int batch, hegpu_stream stream);
+/* The whole gate, batched (HELogicOperator::AND .. XNOR, NOT and their _inplace forms): the product sequence into the
+ * workspace, then the one combine pass (AND: the pass is its copy out of the workspace); NOT is the pass alone (ws unused).
+ *   b ciphertext: hegpu_ckks_multiply, _relinearize_inplace, _rescale_inplace  /  hegpu_bfv_multiply, _relinearize_inplace
+ *   b plaintext:  hegpu_cipherplain_multiplication per item, _rescale_inplace  /  hegpu_bfv_multiply_plain per item
+ * CKKS: a and b at `depth`, l = Q - depth limbs (a plaintext b: [l][N]); out [2][l - 1][N] per item at depth + 1 for a
+ * binary gate, [2][l][N] for NOT.  EVERY gate reads the sum a + b at the product's level: the reference's ciphertext OR,
+ * XOR, NOR and XNOR hand a depth-d sum and a depth-d+1 product to sub(), which throws.  BFV: everything [2][Q][N].
+ * Bit-identical to the chain of the single entries.  Workspace HEGPU_OP_CKKS_LOGIC_GATE / HEGPU_OP_BFV_LOGIC_GATE.
+ * HEGPU_E_INVALID before anything is queued: what the combine refuses, a short workspace, a missing key, out overlapping
+ * the workspace, a CKKS binary gate on the last level. */
+int hegpu_ckks_logic_gate(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b, int b_kind,
+                          uint64_t b_stride, const uint64_t* relin_key, double scale_one, uint64_t* out, uint64_t out_stride,
+                          int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+int hegpu_bfv_logic_gate(hegpu_context* ctx, int gate, const uint64_t* a, uint64_t a_stride, const uint64_t* b, int b_kind,
+                         uint64_t b_stride, const uint64_t* relin_key, uint64_t* out, uint64_t out_stride, int batch, void* ws,
+                         size_t ws_bytes, hegpu_stream stream);
 
 /* ------------------------------------------------------------------ TFHE
  * Gate bootstrapping on the reference's fixed STD128 set
