@@ -808,6 +808,15 @@ int hegpu_fast_floor(hegpu_context* ctx, const uint64_t* in, uint64_t si, uint64
                    "hegpu_fast_floor");
 }
 
+// include/hegpu.h and ops.hpp number the workspace rows separately
+#define SAME_OP(name) static_assert((int) HEGPU_OP_##name == (int) OP_##name, "HEGPU_OP_" #name " != OP_" #name)
+SAME_OP(CKKS_RELIN); SAME_OP(CKKS_RESCALE); SAME_OP(CKKS_GALOIS); SAME_OP(BFV_MULTIPLY); SAME_OP(BFV_RELIN);
+SAME_OP(BFV_GALOIS); SAME_OP(KEYGEN_SECRET); SAME_OP(KEYGEN_PUBLIC); SAME_OP(KEYGEN_SWITCH); SAME_OP(CKKS_ENCRYPT);
+SAME_OP(BFV_ENCRYPT); SAME_OP(BFV_DECRYPT); SAME_OP(BFV_DECODE); SAME_OP(CKKS_ENCODE); SAME_OP(CKKS_DECODE);
+SAME_OP(BFV_MULTIPLY_PLAIN); SAME_OP(CKKS_ROTATE_HOISTED); SAME_OP(MPC_KEY_SHARE); SAME_OP(MPC_BFV_DECRYPT_MERGE);
+SAME_OP(MPC_REFRESH_SHARE); SAME_OP(MPC_REFRESH_MERGE); SAME_OP(CKKS_LOGIC_GATE); SAME_OP(BFV_LOGIC_GATE);
+#undef SAME_OP
+
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch)
 {
     if (!ctx || batch <= 0) return 0;
@@ -935,12 +944,12 @@ int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t c
             return fail(HEGPU_E_INVALID, "rotate_hoisted: Galois elements are odd and below 2N");
         if (!keys[i]) return fail(HEGPU_E_INVALID, "rotate_hoisted: Galois key not present!");
     }
-    // a workspace of HEGPU_OP_CKKS_ROTATE_HOISTED size holds four accumulators: the inner products of four
-    // elements then share one read of the digits
-    const bool big = ws_bytes >= hegpu_workspace_bytes(ctx, OP_CKKS_ROTATE_HOISTED, depth, batch) && ctx->c.fused_moddown &&
-                     ctx->c.ntt_galois;
+    // with room for four accumulators (HEGPU_OP_CKKS_ROTATE_HOISTED) the inner products of four elements share one
+    // read of the digits
+    const int group = (ctx->c.fused_moddown && ctx->c.ntt_galois)
+                          ? ops_rotate_hoisted_accumulators(ctx->c, depth, batch, ws_bytes / sizeof(u64)) : 1;
     return hip_ret(op_ckks_rotate_hoisted(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64* const*) keys,
-                                          galois_elts, count, depth, batch, (u64*) ws, (hipStream_t) stream, big ? 4 : 1),
+                                          galois_elts, count, depth, batch, (u64*) ws, (hipStream_t) stream, group),
                    "hegpu_ckks_rotate_hoisted");
 }
 

@@ -5,6 +5,7 @@
 // sequences can be captured in a hipGraph.  The one exception is
 // op_gen_secret_key, which stages its index list in a host vector and waits.
 #include "ops.hpp"
+#include <algorithm>
 #include <vector>
 #include <utility>
 
@@ -190,48 +191,108 @@ static hipError_t keyswitch_ntt_mac(const Context& c, NttArgs a, const u64* key,
     return hipSuccess;
 }
 
+// ------------------------------------------------------------------ workspace layouts
+// Every workspace shape is stated once, here.  A layout holds the word offset of each region behind the first (which
+// starts the workspace) and `per`, the words per item: the regions of a batch are `per` apart.  Composite layouts, whose
+// regions are blocks of `batch` items, hold `total` instead.  The size queries return per * batch or total, the sequences
+// take their pointers and strides from the same struct.  The sizes are public (callers allocate by them): where a row is
+// larger than what its sequence touches, the slack stays and the layout says so.
+
+// Key switch: [copy [2][l][N]] digits [l][rc][N] acc [accs][2][rc][N].  Relinearize has no copy; a rotation keeps the
+// coefficient-domain ciphertext there; hoisted rotations take four accumulators when they have the room
+// (OP_CKKS_ROTATE_HOISTED); BFV: depth 0, no copy.  Slack: method II fills d <= l of the digits.
+struct KeySwitchWs { u64 digits, acc, acc_words, per; };
+static KeySwitchWs keyswitch_ws(const Context& c, int depth, bool copy, int accs)
+{
+    const u64 l = c.Q_size - depth, rc = c.Qp_size - depth;
+    const u64 digits = copy ? 2 * l * c.n : 0, acc = digits + l * rc * c.n, acc_words = 2 * rc * c.n;
+    return {digits, acc, acc_words, acc + accs * acc_words};
+}
+int ops_rotate_hoisted_accumulators(const Context& c, int depth, int batch, size_t ws_elems)
+{
+    return ws_elems >= keyswitch_ws(c, depth, true, 4).per * (u64) batch ? 4 : 1;
+}
+
+// Two regions per item: where the second starts, and the words of both
+struct PairWs { u64 second, per; };
+// rescale: the dropped limb at every kept modulus [2][l-1][N], copy of the kept limbs (part stride l) [2][l][N]
+static PairWs rescale_ws(const Context& c, int depth)
+{
+    const u64 l = c.Q_size - depth;
+    return {2 * (l - 1) * c.n, (2 * (l - 1) + 2 * l) * c.n};
+}
+// BFV multiply over the L = Q + bsk moduli: both operands extended [4][L][N], their tensor product [3][L][N]
+static PairWs bfv_multiply_ws(const Context& c)
+{
+    const u64 L = c.Q_size + c.bsk_size;
+    return {4 * L * c.n, (4 + 3) * L * c.n};
+}
+// CKKS decode: coefficient-domain copy [l][N], N/2 complex doubles [N]
+static PairWs ckks_decode_ws(const Context& c, int depth) { const u64 l = c.Q_size - depth; return {l * c.n, (l + 1) * c.n}; }
+// public key (share): e [Q'][N], a [Q'][N]
+static PairWs public_key_share_ws(const Context& c) { return {(u64) c.Qp_size * c.n, (u64) 2 * c.Qp_size * c.n}; }
+// switching key (share): e [errs][d][Q'][N], a [d][Q'][N]; errs = 2 in round 1 of the relinearisation key, whose round 2
+// has the e region alone.  Slack: sized for Q digits, method II has d <= Q.
+static PairWs switch_key_share_ws(const Context& c, int errs)
+{
+    return {(u64) errs * switch_key_digits(c) * c.Qp_size * c.n, (u64) (errs + 1) * c.Q_size * c.Qp_size * c.n};
+}
+// encryption of zero: u [Q'][N], e [2][Q'][N], pk * u [2][Q'][N]
+struct EncryptWs { u64 e, pku, per; };
+static EncryptWs encrypt_ws(const Context& c)
+{
+    const u64 limb = (u64) c.Qp_size * c.n;
+    return {limb, 3 * limb, 5 * limb};
+}
+// BFV refresh merge: the rounded plaintexts [batch][N], the h0 sum of the head groups beyond 16 shares [batch][Q][N]
+struct RefreshMergeWs { u64 head_sum, total; };
+static RefreshMergeWs bfv_refresh_merge_ws(const Context& c, int batch)
+{
+    return {(u64) batch * c.n, (u64) (c.Q_size + 1) * c.n * batch};
+}
+// Logic gates: one three-part product per item (`ps` apart), then the largest workspace of the sequence -- CKKS:
+// relinearize, rescale; BFV: multiply, relinearize, multiply-plain
+struct GateWs { u64 ps, ks, total; };
+static GateWs gate_ws(const Context& c, bool bfv, int depth, int batch)
+{
+    const auto row = [&](int op) { return ops_workspace_elems(c, op, bfv ? 0 : depth, batch); };
+    const size_t most = bfv ? std::max({row(OP_BFV_MULTIPLY), row(OP_BFV_RELIN), row(OP_BFV_MULTIPLY_PLAIN)})
+                            : std::max(row(OP_CKKS_RELIN), row(OP_CKKS_RESCALE));
+    const u64 ps = (u64) 3 * (bfv ? c.Q_size : c.Q_size - depth) * c.n, ks = ps * batch;
+    return {ps, ks, ks + most};
+}
+
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
 {
     const u64 n = c.n;
-    const int Q = c.Q_size, Qp = c.Qp_size;
-    const int l = Q - depth, rc = Qp - depth;
-    const int L = Q + c.bsk_size;
     u64 per = 0;
     switch (op) {
-        case OP_CKKS_RELIN: per = ((u64) l * rc + 2 * rc) * n; break;
-        case OP_CKKS_RESCALE: per = ((u64) 2 * (l - 1) + 2 * l) * n; break;
-        case OP_CKKS_GALOIS: per = ((u64) 2 * l + (u64) l * rc + 2 * rc) * n; break;
-        case OP_CKKS_ROTATE_HOISTED: per = ((u64) 2 * l + (u64) l * rc + 4 * 2 * rc) * n; break; // four accumulators
-        case OP_BFV_MULTIPLY: per = (u64) 7 * L * n; break;
-        case OP_BFV_RELIN: per = ((u64) Q * Qp + 2 * Qp) * n; break;
-        case OP_BFV_GALOIS: per = ((u64) Q * Qp + 2 * Qp) * n; break;
+        case OP_CKKS_RELIN: per = keyswitch_ws(c, depth, false, 1).per; break;
+        case OP_CKKS_RESCALE: per = rescale_ws(c, depth).per; break;
+        case OP_CKKS_GALOIS: per = keyswitch_ws(c, depth, true, 1).per; break;
+        case OP_CKKS_ROTATE_HOISTED: per = keyswitch_ws(c, depth, true, 4).per; break;
+        case OP_BFV_MULTIPLY: per = bfv_multiply_ws(c).per; break;
+        case OP_BFV_RELIN:
+        case OP_BFV_GALOIS: per = keyswitch_ws(c, 0, false, 1).per; break;
         case OP_KEYGEN_SECRET: per = n; break;                      // 2 x hamming weight ints
-        case OP_KEYGEN_PUBLIC: per = (u64) 2 * Qp * n; break;        // e, a
-        case OP_KEYGEN_SWITCH: per = (u64) 2 * Q * Qp * n; break;    // e, a per digit
+        case OP_KEYGEN_PUBLIC: per = public_key_share_ws(c).per; break;
+        case OP_KEYGEN_SWITCH: per = switch_key_share_ws(c, 1).per; break;
         case OP_CKKS_ENCRYPT:
-        case OP_BFV_ENCRYPT: per = (u64) 5 * Qp * n; break;          // u, e[2], pk*u[2]
-        case OP_BFV_DECRYPT: per = (u64) Q * n; break;               // c1*s
+        case OP_BFV_ENCRYPT: per = encrypt_ws(c).per; break;
+        case OP_BFV_DECRYPT: per = (u64) c.Q_size * n; break;        // c1*s
         case OP_BFV_DECODE: per = n; break;
-        case OP_BFV_MULTIPLY_PLAIN: per = (u64) Q * n; break;        // lifted + transformed plaintext
+        case OP_BFV_MULTIPLY_PLAIN: per = (u64) c.Q_size * n; break; // lifted + transformed plaintext
         case OP_CKKS_ENCODE: per = n; break;                         // N/2 complex doubles
-        case OP_CKKS_DECODE: per = (u64) (l + 1) * n; break;         // coefficient-domain copy + complex
-        case OP_MPC_KEY_SHARE: per = (u64) 3 * Q * Qp * n; break;    // relin round 1: e0, e1, a per digit (the largest)
-        case OP_MPC_BFV_DECRYPT_MERGE: per = (u64) Q * n; break;     // c0 + the shares beyond the first group
+        case OP_CKKS_DECODE: per = ckks_decode_ws(c, depth).per; break;
+        case OP_MPC_KEY_SHARE: per = switch_key_share_ws(c, 2).per; break; // round 1 of the relinearisation key, the largest
+        case OP_MPC_BFV_DECRYPT_MERGE: per = (u64) c.Q_size * n; break; // c0 + the shares beyond the first group
         case OP_MPC_REFRESH_SHARE: per = 0; break;                   // the noise is sampled and transformed in the share itself
-        case OP_MPC_REFRESH_MERGE:                                   // CKKS: t = c0 + sum h0; BFV: m' and the h0 sum beyond 16 shares
-            per = c.scheme == SCHEME_CKKS ? (u64) l * n : (u64) (Q + 1) * n;
+        case OP_MPC_REFRESH_MERGE:                                   // CKKS: t = c0 + sum h0, [l][N] per item
+            if (c.scheme != SCHEME_CKKS) return bfv_refresh_merge_ws(c, batch).total;
+            per = (u64) (c.Q_size - depth) * n;
             break;
-        case OP_CKKS_LOGIC_GATE: { // one three-part product per item + the larger of relinearize and rescale
-            const size_t relin = ops_workspace_elems(c, OP_CKKS_RELIN, depth, batch);
-            const size_t resc = ops_workspace_elems(c, OP_CKKS_RESCALE, depth, batch);
-            return (u64) 3 * l * n * (u64) batch + (relin > resc ? relin : resc);
-        }
-        case OP_BFV_LOGIC_GATE: { // one three-part product per item + the largest of multiply, relinearize, multiply-plain
-            size_t most = ops_workspace_elems(c, OP_BFV_MULTIPLY, 0, batch);
-            for (int o : {OP_BFV_RELIN, OP_BFV_MULTIPLY_PLAIN})
-                if (ops_workspace_elems(c, o, 0, batch) > most) most = ops_workspace_elems(c, o, 0, batch);
-            return (u64) 3 * Q * n * (u64) batch + most;
-        }
+        case OP_CKKS_LOGIC_GATE: return gate_ws(c, false, depth, batch).total;
+        case OP_BFV_LOGIC_GATE: return gate_ws(c, true, depth, batch).total;
         default: return 0;
     }
     return per * (u64) batch;
@@ -433,7 +494,7 @@ static hipError_t ckks_rotate_tail(const Context& c, u64* acc, const u64* coef, 
 // (add_parts 2, out == ct; reference ckks/operator.cu:1025-1154), c1 for apply_galois (add_parts 1, then the
 // automorphism galois_elt; :1561-1720).  Relinearize inverse-transforms c2 in place; a rotation inverse-transforms c1
 // into a [2][l][N] coefficient-domain copy at the front of its workspace, and c0 too when its tail runs in the
-// reference order.  Workspace: OP_CKKS_RELIN / OP_CKKS_GALOIS.
+// reference order.  Workspace: keyswitch_ws without (relinearize) or with the copy, one accumulator.
 static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int add_parts, u64* out, u64 so,
                                     const u64* key, int galois_elt, int depth, int batch, u64* ws, hipStream_t st)
 {
@@ -446,38 +507,37 @@ static hipError_t ckks_keyswitch_II(const Context& c, const u64* ct, u64 cs, int
     // the mod-down as the epilogue of its forward transform (ckks_moddown_multi); a rotation's c0 then stays in the NTT
     // domain (see op_ckks_apply_galois)
     const bool ntt_domain = c.fused_moddown && (relin || c.ntt_galois);
-    const u64 copy = relin ? 0 : (u64) 2 * l * n;
-    const u64 per = copy + ((u64) l * rc + 2 * rc) * n;
+    const KeySwitchWs w = keyswitch_ws(c, depth, !relin, 1);
     u64* coef = relin ? out : ws; // the coefficient-domain parts, coef_stride apart
-    const u64 coef_stride = relin ? so : per;
-    u64* digits = ws + copy;              // [d][rc][N]
-    u64* acc = digits + (u64) l * rc * n; // [2][rc][N]
+    const u64 coef_stride = relin ? so : w.per;
+    u64* digits = ws + w.digits; // [d][rc][N]
+    u64* acc = ws + w.acc;       // [2][rc][N]
     const int first = (relin || ntt_domain) ? add_parts : 0; // first part inverse-transformed
     NttArgs a = c.ntt_args(0);
     a.in = ct + (u64) first * l * n; a.out = coef + (u64) first * l * n; a.mod_count = l;
     a.polys_per_item = (add_parts + 1 - first) * l;
     a.in_item_stride = cs; a.out_item_stride = coef_stride;
     TRY(ntt_launch(a, a.polys_per_item * batch, true, st));                                // :1052
-    TRY(dtoq(c, depth, coef + (u64) add_parts * l * n, coef_stride, digits, per, l, depth, batch, st)); // :1065
+    TRY(dtoq(c, depth, coef + (u64) add_parts * l * n, coef_stride, digits, w.per, l, depth, batch, st)); // :1065
     a = c.ntt_args(0);
     a.in = digits; a.out = digits; a.mod_count = rc; a.polys_per_item = d * rc;
     a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
-    a.in_item_stride = a.out_item_stride = per;
-    TRY(keyswitch_ntt_mac(c, a, key, acc, per, d, rc, l, depth, nullptr, 0, batch, st));  // :1095-1125
+    a.in_item_stride = a.out_item_stride = w.per;
+    TRY(keyswitch_ntt_mac(c, a, key, acc, w.per, d, rc, l, depth, nullptr, 0, batch, st));  // :1095-1125
     // the front of the workspace (the digits of a relinearization, the coefficient-domain copy of a rotation) is free
     // again: scratch of the mod-down; ct_parts 0 adds both parts
     if (ntt_domain)
-        return ckks_moddown_multi(c, acc, ws, per, ct, cs, relin ? 0 : add_parts, out, so, depth, galois_elt, batch, st);
-    if (!relin) return ckks_rotate_tail(c, acc, ws, per, out, so, galois_elt, depth, batch, st);
+        return ckks_moddown_multi(c, acc, ws, w.per, ct, cs, relin ? 0 : add_parts, out, so, depth, galois_elt, batch, st);
+    if (!relin) return ckks_rotate_tail(c, acc, ws, w.per, out, so, galois_elt, depth, batch, st);
     a.in = acc; a.out = acc; a.polys_per_item = 2 * rc;
     TRY(ntt_launch(a, 2 * rc * batch, true, st));                                          // :1131
-    TRY(rns_moddown_extended(acc, per, nullptr, 0, ws, per, c.moddown(depth), 0, batch, st)); // :1136
+    TRY(rns_moddown_extended(acc, w.per, nullptr, 0, ws, w.per, c.moddown(depth), 0, batch, st)); // :1136
     a = c.ntt_args(0);
     a.in = ws; a.out = ws; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     TRY(ntt_launch(a, 2 * l * batch, false, st));                                          // :1145
     // addition(temp1, ct, ct): per-item strides differ, so one launch per item batch via copy-free add
-    return rns_addition_strided(ws, per, ct, cs, out, so, c.plan_qp.mods, np, l, 2, batch, st); // :1149
+    return rns_addition_strided(ws, w.per, ct, cs, out, so, c.plan_qp.mods, np, l, 2, batch, st); // :1149
 }
 
 // reference ckks/operator.cu:899-1023
@@ -486,13 +546,12 @@ hipError_t op_ckks_relinearize(const Context& c, u64* ct, u64 cs, const u64* key
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (c.P_size > 1) return ckks_keyswitch_II(c, ct, cs, 2, ct, cs, key, 0, depth, batch, ws, st);
-    const u64 n = c.n;
-    const int l = c.Q_size - depth, rc = c.Qp_size - depth;
-    const u64 per = ((u64) l * rc + 2 * rc) * n;
-    u64* temp1 = ws;                      // [l][rc][N] per item, later [2][l][N]
-    u64* temp2 = ws + (u64) l * rc * n;   // [2][rc][N] per item
+    const int l = c.Q_size - depth;
+    const KeySwitchWs w = keyswitch_ws(c, depth, false, 1);
+    u64* temp1 = ws + w.digits; // [l][rc][N] per item, later [2][l][N]
+    u64* temp2 = ws + w.acc;    // [2][rc][N] per item
     return ckks_keyswitch_core(c, ct + ((u64) l << (c.n_power + 1)), cs, ct, cs, 2, ct, cs, key, depth, batch, temp1,
-                               temp2, per, st, phases);
+                               temp2, w.per, st, phases);
 }
 
 // reference ckks/operator.cu:1156-1244
@@ -504,9 +563,9 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
     const int Q = c.Q_size, P = c.P_size;
     const int l = Q - depth;
     const ModDown md = c.moddown(depth, true);
-    const u64 per = ((u64) 2 * (l - 1) + 2 * l) * n;
-    u64* temp1 = ws;                         // [2][l-1][N]
-    u64* temp2 = ws + (u64) 2 * (l - 1) * n; // copy of ct, part stride l
+    const PairWs w = rescale_ws(c, depth);
+    u64* temp1 = ws;            // [2][l-1][N]
+    u64* temp2 = ws + w.second; // copy of ct, part stride l
 
     NttArgs a = c.ntt_args(0);
     a.in = ct; a.out = ct; a.mod_count = 1; a.mod_offset = l - 1; a.polys_per_item = 2;
@@ -519,7 +578,7 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         // epilogue writes the compacted ciphertext over them
         a = c.ntt_args(0);
         a.in = ct; a.out = temp1; a.mod_count = l - 1; a.polys_per_item = 2 * (l - 1);
-        a.in_item_stride = cs; a.out_item_stride = per;
+        a.in_item_stride = cs; a.out_item_stride = w.per;
         a.decomp_mods = l - 1; a.decomp_in_mul = l; a.decomp_in_add = l - 1;
         a.half_on = 1; a.half_src_mod = l - 1; a.half = c.hv.rescaled_half[depth];
         a.half_mod = md.half_mod;
@@ -527,26 +586,26 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
         // and tile: C2, 4.7 us of launch less); the multi-modulus kernel keeps its own launch for it.
         if (c.copy_along && !ntt_decomp_uses_multi(a, 2 * (l - 1) * batch)) {
             a.copy_src = ct; a.copy_src_item_stride = cs;
-            a.copy_dst = temp2; a.copy_dst_item_stride = per;
+            a.copy_dst = temp2; a.copy_dst_item_stride = w.per;
             a.copy_part_limbs = l;
         } else {
-            TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, per, np, l - 1, 2, batch, st));
+            TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, w.per, np, l - 1, 2, batch, st));
         }
         a.epi.on = 1;
-        a.epi.ks = temp2; a.epi.ks_item_stride = per; a.epi.ks_part_limbs = l;
+        a.epi.ks = temp2; a.epi.ks_item_stride = w.per; a.epi.ks_part_limbs = l;
         a.epi.ct = nullptr; a.epi.ct_item_stride = 0;
         a.epi.out = ct; a.epi.out_item_stride = cs;
         a.epi.inv = md.last_q_modinv;
         a.epi.limbs = l - 1;
         return ntt_launch(a, 2 * (l - 1) * batch, false, st);
     }
-    TRY(rns_moddown_stage_one(ct, cs, temp1, per, md, batch, st));                         // :1205
+    TRY(rns_moddown_stage_one(ct, cs, temp1, w.per, md, batch, st));                         // :1205
     a = c.ntt_args(0);
     a.in = temp1; a.out = temp1; a.mod_count = l - 1; a.polys_per_item = 2 * (l - 1);
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     TRY(ntt_launch(a, 2 * (l - 1) * batch, false, st));                                    // :1214
-    TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, per, np, l - 1, 2, batch, st)); // :1219
-    return rns_moddown_stage_two(temp1, per, temp2, per, nullptr, 0, ct, cs, md, 0, batch, st); // :1225
+    TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, w.per, np, l - 1, 2, batch, st)); // :1219
+    return rns_moddown_stage_two(temp1, w.per, temp2, w.per, nullptr, 0, ct, cs, md, 0, batch, st); // :1225
 }
 
 // reference ckks/operator.cu:1422-1559
@@ -559,10 +618,10 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
     const u64 n = c.n;
     const int Q = c.Q_size, Qp = c.Qp_size;
     const int l = Q - depth, rc = Qp - depth;
-    const u64 per = ((u64) 2 * l + (u64) l * rc + 2 * rc) * n;
-    u64* temp0 = ws;                       // [2][l][N] coefficient-domain copy of ct
-    u64* temp2 = temp0 + (u64) 2 * l * n;  // [l][rc][N]
-    u64* temp3 = temp2 + (u64) l * rc * n; // [2][rc][N]
+    const KeySwitchWs w = keyswitch_ws(c, depth, true, 1);
+    u64* temp0 = ws;            // [2][l][N] coefficient-domain copy of ct
+    u64* temp2 = ws + w.digits; // [l][rc][N]
+    u64* temp3 = ws + w.acc;    // [2][rc][N]
 
     if (c.fused_moddown && c.ntt_galois) {
         // The key switch of c1 exactly as relinearize does it (c0 added to part 0 by the mod-down epilogue), all
@@ -572,22 +631,22 @@ hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* ou
         // no scattered stores; the residues are the same (the permutation commutes with the transform, the
         // mod-down is the same exact integer function either way).
         if (c.galois_scatter)
-            return ckks_keyswitch_core(c, ct + (u64) l * n, cs, ct, cs, 1, out, so, key, depth, batch, temp2, temp3, per, st,
+            return ckks_keyswitch_core(c, ct + (u64) l * n, cs, ct, cs, 1, out, so, key, depth, batch, temp2, temp3, w.per, st,
                                        RELIN_PHASE_ALL, galois_elt);
-        TRY(ckks_keyswitch_core(c, ct + (u64) l * n, cs, ct, cs, 1, temp0, per, key, depth, batch, temp2, temp3, per, st,
+        TRY(ckks_keyswitch_core(c, ct + (u64) l * n, cs, ct, cs, 1, temp0, w.per, key, depth, batch, temp2, temp3, w.per, st,
                                 RELIN_PHASE_ALL));
-        return rns_permute_ntt(temp0, per, out, so, galois_elt, np, 2 * l, batch, st);
+        return rns_permute_ntt(temp0, w.per, out, so, galois_elt, np, 2 * l, batch, st);
     }
     NttArgs a = c.ntt_args(0);
     a.in = ct; a.out = temp0; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = cs; a.out_item_stride = per;
+    a.in_item_stride = cs; a.out_item_stride = w.per;
     TRY(ntt_launch(a, 2 * l * batch, true, st));                                           // :1461
     a = c.ntt_args(0); // ckks_duplicate_kernel fused into the NTT load          :1467-1494
     a.in = temp0 + (u64) l * n; a.out = temp2; a.mod_count = rc; a.polys_per_item = l * rc; a.decomp_mods = rc;
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     a.mod_order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
-    TRY(keyswitch_ntt_mac(c, a, key, temp3, per, l, rc, l, depth, ct + (u64) l * n, cs, batch, st)); // :1490-1520
-    return ckks_rotate_tail(c, temp3, temp0, per, out, so, galois_elt, depth, batch, st);
+    TRY(keyswitch_ntt_mac(c, a, key, temp3, w.per, l, rc, l, depth, ct + (u64) l * n, cs, batch, st)); // :1490-1520
+    return ckks_rotate_tail(c, temp3, temp0, w.per, out, so, galois_elt, depth, batch, st);
 }
 
 // reference bfv/operator.cu:336-430
@@ -598,24 +657,24 @@ hipError_t op_bfv_multiply(const Context& c, const u64* ct1, u64 s1, const u64* 
     const int np = c.n_power;
     const u64 n = c.n;
     const int L = c.Q_size + c.bsk_size;
-    const u64 per = (u64) 7 * L * n;
-    u64* temp1 = ws;                   // [4][L][N]
-    u64* temp2 = ws + (u64) 4 * L * n; // [3][L][N]
-    TRY(rns_fast_convertion(ct1, s1, ct2, s2, temp1, per, c.behz, np, batch, st));         // :364
+    const PairWs w = bfv_multiply_ws(c);
+    u64* temp1 = ws;            // [4][L][N]
+    u64* temp2 = ws + w.second; // [3][L][N]
+    TRY(rns_fast_convertion(ct1, s1, ct2, s2, temp1, w.per, c.behz, np, batch, st));         // :364
     NttArgs a = c.ntt_args(1);
     a.in = temp1; a.out = temp1; a.mod_count = L; a.polys_per_item = 4 * L;
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     TRY(ntt_launch(a, 4 * L * batch, false, st));                                          // :393
     a.in = temp2; a.out = temp2; a.polys_per_item = 3 * L;
     if (c.fused_tensor) {
         // the tensor product (:399) as the load transform of the inverse transform (:410): [3][L][N] is never stored
-        a.tensor_in = temp1; a.tensor_item_stride = per; a.tensor_limbs = L;
+        a.tensor_in = temp1; a.tensor_item_stride = w.per; a.tensor_limbs = L;
     } else {
-        TRY(rns_cross_multiplication(temp1, per, temp1 + (u64) 2 * L * n, per, temp2, per, c.plan_merge.mods, np, L,
+        TRY(rns_cross_multiplication(temp1, w.per, temp1 + (u64) 2 * L * n, w.per, temp2, w.per, c.plan_merge.mods, np, L,
                                      batch, st));                                          // :399
     }
     TRY(ntt_launch(a, 3 * L * batch, true, st));                                           // :410
-    return rns_fast_floor(temp2, per, out, so, c.behz, np, batch, st);                     // :416
+    return rns_fast_floor(temp2, w.per, out, so, c.behz, np, batch, st);                     // :416
 }
 
 // BFV key switching, tail: acc [2][Q'][N] (NTT domain, `per` apart) -> INTT -> divide by the special prime with
@@ -691,31 +750,31 @@ static hipError_t bfv_keyswitch(const Context& c, const u64* ct, u64 cs, int add
     const int Q = c.Q_size, Qp = c.Qp_size;
     const bool m2 = c.P_size > 1;
     const int digits = m2 ? c.m2_levels[0].d : Q;
-    const u64 per = ((u64) Q * Qp + 2 * Qp) * n;
-    u64* temp1 = ws;                    // [digits][Q'][N]
-    u64* temp2 = ws + (u64) Q * Qp * n; // [2][Q'][N]
+    const KeySwitchWs w = keyswitch_ws(c, 0, false, 1);
+    u64* temp1 = ws + w.digits; // [digits][Q'][N]
+    u64* temp2 = ws + w.acc;    // [2][Q'][N]
     const u64* src = ct + (u64) add_parts * Q * n;
     NttArgs a = c.ntt_args(0);
-    a.out = temp1; a.mod_count = Qp; a.polys_per_item = digits * Qp; a.out_item_stride = per;
+    a.out = temp1; a.mod_count = Qp; a.polys_per_item = digits * Qp; a.out_item_stride = w.per;
     if (m2) {
-        TRY(dtoq(c, 0, src, cs, temp1, per, Q, 0, batch, st));
-        a.in = temp1; a.in_item_stride = per;
+        TRY(dtoq(c, 0, src, cs, temp1, w.per, Q, 0, batch, st));
+        a.in = temp1; a.in_item_stride = w.per;
     } else {
         a.in = src; a.in_item_stride = cs; a.decomp_mods = Qp;
     }
-    TRY(keyswitch_ntt_mac(c, a, key, temp2, per, digits, Qp, Qp, 0, nullptr, 0, batch, st));
+    TRY(keyswitch_ntt_mac(c, a, key, temp2, w.per, digits, Qp, Qp, 0, nullptr, 0, batch, st));
     if (c.fused_moddown) { // temp1 (the digits) is free again: scratch of the multi-prime mod-down
-        if (m2) return bfv_intt_moddown_multi(c, temp2, temp1, per, ct, cs, add_parts, out, so, galois_elt, batch, st);
-        return bfv_intt_moddown(c, temp2, per, ct, cs, add_parts, out, so, galois_elt, batch, st);
+        if (m2) return bfv_intt_moddown_multi(c, temp2, temp1, w.per, ct, cs, add_parts, out, so, galois_elt, batch, st);
+        return bfv_intt_moddown(c, temp2, w.per, ct, cs, add_parts, out, so, galois_elt, batch, st);
     }
     a = c.ntt_args(0);
     a.in = temp2; a.out = temp2; a.mod_count = Qp; a.polys_per_item = 2 * Qp;
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     TRY(ntt_launch(a, 2 * Qp * batch, true, st));
     if (add_parts == 1)
-        return rns_moddown_permute(temp2, per, ct, cs, out, so, c.moddown(0), galois_elt, batch, st);
-    if (m2) return rns_moddown_extended(temp2, per, ct, cs, out, so, c.moddown(0), 1, batch, st);
-    return rns_divide_round_lastq(temp2, per, ct, cs, out, so, c.moddown(0), 0, batch, st);
+        return rns_moddown_permute(temp2, w.per, ct, cs, out, so, c.moddown(0), galois_elt, batch, st);
+    if (m2) return rns_moddown_extended(temp2, w.per, ct, cs, out, so, c.moddown(0), 1, batch, st);
+    return rns_divide_round_lastq(temp2, w.per, ct, cs, out, so, c.moddown(0), 0, batch, st);
 }
 
 hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws, hipStream_t st)
@@ -737,7 +796,8 @@ hipError_t op_bfv_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out
 // ciphertext and the NTT-domain digits stay in the workspace while the per-element part walks the keys, so every
 // output is bit-identical to the reference's (and to `count` separate hegpu_ckks_apply_galois calls).
 // out: [count][2][l][N] per ciphertext (`so` apart), entry i at i * 2 l N; galois_elts[i] == 0 copies the input
-// (global_memory_replace_kernel, :4708 / :5141).  Workspace: OP_CKKS_GALOIS.
+// (global_memory_replace_kernel, :4708 / :5141).  Workspace: keyswitch_ws with the copy and `group` accumulators, that is
+// OP_CKKS_GALOIS for group 1 and OP_CKKS_ROTATE_HOISTED for group 4 (ops_rotate_hoisted_accumulators tells which fits).
 hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* const* keys,
                                   const int* galois_elts, int count, int depth, int batch, u64* ws, hipStream_t st,
                                   int group)
@@ -751,11 +811,10 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     const int digits = m2 ? c.m2_levels[depth].d : l;
     if (group != 1 && group != 4) return hipErrorInvalidValue;
     if (digits > 16) group = 1; // rns_keyswitch_mac_keys keeps the digits of a coefficient in 16 registers
-    const u64 acc_words = (u64) 2 * rc * n;
-    const u64 per = ((u64) 2 * l + (u64) l * rc) * n + group * acc_words;
-    u64* temp0 = ws;                       // [2][l][N] coefficient-domain copy of ct
-    u64* temp2 = temp0 + (u64) 2 * l * n;  // [digits][rc][N] NTT-domain digits
-    u64* temp3 = temp2 + (u64) l * rc * n; // [group][2][rc][N]
+    const KeySwitchWs w = keyswitch_ws(c, depth, true, group);
+    u64* temp0 = ws;            // [2][l][N] coefficient-domain copy of ct
+    u64* temp2 = ws + w.digits; // [digits][rc][N] NTT-domain digits
+    u64* temp3 = ws + w.acc;    // [group][2][rc][N]
     const Mod* mods = c.plan_qp.mods;
     const int* order = c.tab.new_prime_locations + triangle_offset(Qp, depth);
     const u64 ct_words = (u64) 2 * l * n;
@@ -783,7 +842,7 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     // ---- shared: INTT of both parts (of c1 only: ntt_domain), digits, forward NTT of the digits
     NttArgs a = c.ntt_args(0);
     a.in = ct; a.out = temp0; a.mod_count = l; a.polys_per_item = 2 * l;
-    a.in_item_stride = cs; a.out_item_stride = per;
+    a.in_item_stride = cs; a.out_item_stride = w.per;
     if (ntt_domain) {
         a.in = ct + (u64) l * n; a.out = temp0 + (u64) l * n; a.polys_per_item = l;
         TRY(ntt_launch(a, l * batch, true, st));
@@ -792,14 +851,14 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
     }
     a = c.ntt_args(0);
     a.out = temp2; a.mod_count = rc; a.polys_per_item = digits * rc; a.mod_order = order;
-    a.in_item_stride = a.out_item_stride = per;
+    a.in_item_stride = a.out_item_stride = w.per;
     if (m2) {
-        TRY(dtoq(c, depth, temp0 + (u64) l * n, per, temp2, per, l, depth, batch, st));
+        TRY(dtoq(c, depth, temp0 + (u64) l * n, w.per, temp2, w.per, l, depth, batch, st));
         a.in = temp2;
     } else {
         // digit d at modulus d is the NTT-domain limb of c1 itself
         a.in = temp0 + (u64) l * n; a.decomp_mods = rc; a.skip_identity = 1;
-        TRY(rns_copy_diag(ct + (u64) l * n, cs, temp2, per, np, l, rc, batch, st));
+        TRY(rns_copy_diag(ct + (u64) l * n, cs, temp2, w.per, np, l, rc, batch, st));
     }
     TRY(ntt_launch(a, digits * rc * batch, false, st));
 
@@ -816,24 +875,24 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
                 const u64* gk[4];
                 for (int j = i; j < count && npend < group; j++)
                     if (galois_elts[j] != 0) { pending[npend] = j; gk[npend++] = keys[j]; }
-                TRY(rns_keyswitch_mac_keys(temp2, per, gk, npend, temp3, per, acc_words, mods, np, digits, rc, Qp, l, depth,
+                TRY(rns_keyswitch_mac_keys(temp2, w.per, gk, npend, temp3, w.per, w.acc_words, mods, np, digits, rc, Qp, l, depth,
                                            batch, st));
             }
-            acc = temp3 + (u64) next * acc_words; // pending[next] == i
+            acc = temp3 + (u64) next * w.acc_words; // pending[next] == i
             next++;
         } else {
-            TRY(rns_keyswitch_mac(temp2, per, keys[i], temp3, per, mods, np, digits, rc, Qp, l, depth, batch, st));
+            TRY(rns_keyswitch_mac(temp2, w.per, keys[i], temp3, w.per, mods, np, digits, rc, Qp, l, depth, batch, st));
         }
         if (ntt_domain) {
             // temp0 is free once the digits exist: scratch of the mod-down transform
-            if (m2) TRY(ckks_moddown_multi(c, acc, temp0, per, ct, cs, 1, oi, so, depth, galois_elts[i], batch, st));
+            if (m2) TRY(ckks_moddown_multi(c, acc, temp0, w.per, ct, cs, 1, oi, so, depth, galois_elts[i], batch, st));
             else
-                TRY(ckks_keyswitch_core(c, nullptr, 0, ct, cs, 1, oi, so, nullptr, depth, batch, temp0, acc, per, st,
+                TRY(ckks_keyswitch_core(c, nullptr, 0, ct, cs, 1, oi, so, nullptr, depth, batch, temp0, acc, w.per, st,
                                         RELIN_PHASE_INTT_P | RELIN_PHASE_MODDOWN, galois_elts[i]));
             continue;
         }
         if (group > 1) return hipErrorInvalidValue; // the reference-order tail works on one accumulator
-        TRY(ckks_rotate_tail(c, temp3, temp0, per, oi, so, galois_elts[i], depth, batch, st));
+        TRY(ckks_rotate_tail(c, temp3, temp0, w.per, oi, so, galois_elts[i], depth, batch, st));
     }
     return hipSuccess;
 }
@@ -842,11 +901,17 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
 // Workspace, per batch: A = max(n1, n2) ciphertexts (the baby rotations; once the inner sums exist, the rotated inner
 // sums), B = n2 ciphertexts (the inner sums), then the key-switch workspace of the hoisted rotations with four
 // accumulators (which is also enough for every apply_galois).
-size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, int depth, int batch)
+struct LinearTransformWs { u64 a_stride, b_stride, B, ks, total; };
+static LinearTransformWs linear_transform_ws(const Context& c, int n1, int n2, int depth, int batch)
 {
     const u64 ct_words = (u64) 2 * (c.Q_size - depth) * c.n;
-    return (u64) ((n1 > n2 ? n1 : n2) + n2) * ct_words * (u64) batch +
-           ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch);
+    const u64 a_stride = (u64) (n1 > n2 ? n1 : n2) * ct_words, b_stride = (u64) n2 * ct_words;
+    const u64 B = a_stride * batch, ks = B + b_stride * batch;
+    return {a_stride, b_stride, B, ks, ks + ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch)};
+}
+size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, int depth, int batch)
+{
+    return linear_transform_ws(c, n1, n2, depth, batch).total;
 }
 
 hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* diags,
@@ -858,23 +923,23 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
     if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16) return hipErrorInvalidValue;
     const int l = c.Q_size - depth;
     const u64 ct_words = (u64) 2 * l * c.n;
-    const u64 a_stride = (u64) (n1 > n2 ? n1 : n2) * ct_words, b_stride = (u64) n2 * ct_words;
+    const LinearTransformWs w = linear_transform_ws(c, n1, n2, depth, batch);
     u64* A = ws;
-    u64* B = A + a_stride * batch;
-    u64* ks = B + b_stride * batch;
+    u64* B = ws + w.B;
+    u64* ks = ws + w.ks;
     const Mod* mods = c.plan_qp.mods;
     // 1. baby rotations (a single identity step reads the input itself)
     const u64* rot = ct;
     u64 rot_stride = cs;
     if (!(n1 == 1 && baby_elts[0] == 0)) {
         const int group = (c.fused_moddown && c.ntt_galois) ? 4 : 1;
-        TRY(op_ckks_rotate_hoisted(c, ct, cs, A, a_stride, baby_keys, baby_elts, n1, depth, batch, ks, st, group));
+        TRY(op_ckks_rotate_hoisted(c, ct, cs, A, w.a_stride, baby_keys, baby_elts, n1, depth, batch, ks, st, group));
         rot = A;
-        rot_stride = a_stride;
+        rot_stride = w.a_stride;
     }
     // 2. all inner sums; a single giant step without a rotation is the result
     const bool direct = n2 == 1 && giant_elts[0] == 0;
-    TRY(rns_ckks_diag_mac(rot, rot_stride, n1, diags, n_diag, index, n2, direct ? out : B, direct ? so : b_stride, mods,
+    TRY(rns_ckks_diag_mac(rot, rot_stride, n1, diags, n_diag, index, n2, direct ? out : B, direct ? so : w.b_stride, mods,
                           c.n_power, l, batch, st));
     if (direct) return hipSuccess;
     // 3. giant rotations into A (the baby rotations are spent; apply_galois forbids out == in)
@@ -883,12 +948,12 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
     for (int j = 0; j < n2; j++) {
         const u64* inner = B + (u64) j * ct_words;
         terms[j] = inner;
-        strides[j] = b_stride;
+        strides[j] = w.b_stride;
         if (giant_elts[j] == 0) continue;
         if (!giant_keys[j]) return hipErrorInvalidValue;
         u64* rotated = n2 == 1 ? out : A + (u64) j * ct_words; // a single term is the result
-        const u64 rs = n2 == 1 ? so : a_stride;
-        TRY(op_ckks_apply_galois(c, inner, b_stride, rotated, rs, giant_keys[j], giant_elts[j], depth, batch, ks, st));
+        const u64 rs = n2 == 1 ? so : w.a_stride;
+        TRY(op_ckks_apply_galois(c, inner, w.b_stride, rotated, rs, giant_keys[j], giant_elts[j], depth, batch, ks, st));
         terms[j] = rotated;
         strides[j] = rs;
     }
@@ -901,14 +966,17 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
 // Workspace, per batch: T0 and T1, one ciphertext of the start depth each (the chain alternates between them: a linear
 // transform may not write over its input), then the largest workspace any step needs (the linear transforms'; it holds
 // the hoisted-rotation workspace, which is enough for apply_galois and larger than the rescale's).
+struct EncodingTransformWs { u64 t_stride, T1, step, total; };
+static EncodingTransformWs encoding_transform_ws(const Context& c, const LinearFactor* f, int count, int depth, int batch)
+{
+    u64 step = ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch);
+    for (int k = 0; k < count; k++) step = std::max(step, linear_transform_ws(c, f[k].n1, f[k].n2, depth, batch).total);
+    const u64 t_stride = (u64) 2 * (c.Q_size - depth) * c.n, T1 = t_stride * batch;
+    return {t_stride, T1, 2 * T1, 2 * T1 + step};
+}
 size_t ops_encoding_transform_workspace_elems(const Context& c, const LinearFactor* f, int count, int depth, int batch)
 {
-    size_t step = ops_workspace_elems(c, OP_CKKS_ROTATE_HOISTED, depth, batch);
-    for (int k = 0; k < count; k++) {
-        const size_t w = ops_linear_transform_workspace_elems(c, f[k].n1, f[k].n2, depth, batch);
-        if (w > step) step = w;
-    }
-    return (u64) 2 * 2 * (c.Q_size - depth) * c.n * (u64) batch + step;
+    return encoding_transform_ws(c, f, count, depth, batch).total;
 }
 
 // `count` x (linear transform, rescale) from cur at depth d0, alternating between the two buffers; the last product goes
@@ -940,17 +1008,17 @@ hipError_t op_ckks_coeff_to_slot(const Context& c, const u64* ct, u64 cs, u64* o
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (count < 1 || depth + count + 1 >= c.Q_size) return hipErrorInvalidValue;
-    const u64 t_stride = (u64) 2 * (c.Q_size - depth) * c.n;
+    const EncodingTransformWs w = encoding_transform_ws(c, f, count, depth, batch);
     u64* T0 = ws;
-    u64* T1 = T0 + t_stride * batch;
-    u64* step_ws = T1 + t_stride * batch;
+    u64* T1 = ws + w.T1;
+    u64* step_ws = ws + w.step;
     const u64* cur = ct;
     u64 cur_stride = cs;
-    TRY(encoding_transform_chain(c, cur, cur_stride, T0, T1, t_stride, nullptr, 0, f, count, depth, batch, step_ws, st));
+    TRY(encoding_transform_chain(c, cur, cur_stride, T0, T1, w.t_stride, nullptr, 0, f, count, depth, batch, step_ws, st));
     const int d = depth + count;
     u64* conj = (cur == T0) ? T1 : T0;
-    TRY(op_ckks_apply_galois(c, cur, cur_stride, conj, t_stride, conj_key, 2 * (int) c.n - 1, d, batch, step_ws, st));
-    return rns_ckks_conj_split(cur, cur_stride, conj, t_stride, out0, out1, so, c.tab.psi_half, c.plan_qp.mods, c.n_power,
+    TRY(op_ckks_apply_galois(c, cur, cur_stride, conj, w.t_stride, conj_key, 2 * (int) c.n - 1, d, batch, step_ws, st));
+    return rns_ckks_conj_split(cur, cur_stride, conj, w.t_stride, out0, out1, so, c.tab.psi_half, c.plan_qp.mods, c.n_power,
                                c.Q_size - d, c.Q_size - d - 1, batch, st);
 }
 
@@ -959,15 +1027,15 @@ hipError_t op_ckks_slot_to_coeff(const Context& c, const u64* c0, u64 s0, const 
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (count < 1 || depth + count + 1 >= c.Q_size) return hipErrorInvalidValue;
-    const u64 t_stride = (u64) 2 * (c.Q_size - depth) * c.n;
+    const EncodingTransformWs w = encoding_transform_ws(c, f, count, depth, batch);
     u64* T0 = ws;
-    u64* T1 = T0 + t_stride * batch;
-    u64* step_ws = T1 + t_stride * batch;
-    TRY(rns_ckks_conj_merge(c0, s0, c1, s1, T0, t_stride, c.tab.psi_half, c.plan_qp.mods, c.n_power, c.Q_size - depth,
+    u64* T1 = ws + w.T1;
+    u64* step_ws = ws + w.step;
+    TRY(rns_ckks_conj_merge(c0, s0, c1, s1, T0, w.t_stride, c.tab.psi_half, c.plan_qp.mods, c.n_power, c.Q_size - depth,
                             c.Q_size - depth - 1, batch, st));
     const u64* cur = T0;
-    u64 cur_stride = t_stride;
-    return encoding_transform_chain(c, cur, cur_stride, T0, T1, t_stride, out, so, f, count, depth + 1, batch, step_ws, st);
+    u64 cur_stride = w.t_stride;
+    return encoding_transform_chain(c, cur, cur_stride, T0, T1, w.t_stride, out, so, f, count, depth + 1, batch, step_ws, st);
 }
 
 // ------------------------------------------------------------------ polynomial evaluation
@@ -1029,13 +1097,28 @@ static u64 poly_reg_words(const Context& c, const host::PolyStep& s)
     return (product_in_place ? (u64) 3 * (s.mul_level + 1) : (u64) 2 * (s.level + 1)) * c.n;
 }
 
+// The registers of every step but the last (which writes `out`), each a block of `batch` items; T: one three-part product
+// per item; D: one operand copied down to a product's level; ks: the larger of the relinearize and rescale workspaces
+struct PolyEvalWs { u64 t_stride, d_stride, T, D, ks, total; };
+struct PolyReg { u64* p; u64 stride; int limbs; };
+// reg (with ws): reg[k + 1] becomes the register step k writes
+static PolyEvalWs poly_eval_ws(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch,
+                               u64* ws = nullptr, PolyReg* reg = nullptr)
+{
+    u64 at = 0;
+    for (int k = 0; k + 1 < n_steps; k++) {
+        const u64 words = poly_reg_words(c, plan[k]);
+        if (reg) reg[k + 1] = {ws + at, words, plan[k].level + 1};
+        at += words * batch;
+    }
+    const u64 t_stride = (u64) 3 * (c.Q_size - depth) * c.n, d_stride = (u64) 2 * (c.Q_size - depth) * c.n;
+    const u64 D = at + t_stride * batch, ks = D + d_stride * batch;
+    return {t_stride, d_stride, at, D, ks, ks + std::max(ops_workspace_elems(c, OP_CKKS_RELIN, depth, batch),
+                                                         ops_workspace_elems(c, OP_CKKS_RESCALE, depth, batch))};
+}
 size_t ops_poly_eval_workspace_elems(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch)
 {
-    const u64 top_limbs = (u64) (c.Q_size - depth);
-    u64 per = (3 + 2) * top_limbs * c.n;
-    for (int k = 0; k + 1 < n_steps; k++) per += poly_reg_words(c, plan[k]); // the last step writes `out`
-    const size_t relin = ops_workspace_elems(c, OP_CKKS_RELIN, depth, batch), resc = ops_workspace_elems(c, OP_CKKS_RESCALE, depth, batch);
-    return per * (u64) batch + (relin > resc ? relin : resc);
+    return poly_eval_ws(c, plan, n_steps, depth, batch).total;
 }
 
 hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::PolyStep* plan,
@@ -1047,22 +1130,14 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
     const int np = c.n_power, Q = c.Q_size;
     const u64 n = c.n;
     const Mod* mods = c.plan_qp.mods;
-    struct Reg { u64* p; u64 stride; int limbs; };
+    using Reg = PolyReg;
     std::vector<Reg> reg((size_t) n_steps + 1);
     reg[0] = {const_cast<u64*>(ct), cs, Q - depth}; // never written: ops_poly_eval_check keeps register 0 out of every dst
-    u64* at = ws;
-    for (int k = 0; k < n_steps; k++) {
-        const u64 words = poly_reg_words(c, plan[k]);
-        if (k == n_steps - 1) reg[(size_t) k + 1] = {out, so, plan[k].level + 1};
-        else {
-            reg[(size_t) k + 1] = {at, words, plan[k].level + 1};
-            at += words * batch;
-        }
-    }
-    const u64 t_stride = (u64) 3 * (Q - depth) * n, d_stride = (u64) 2 * (Q - depth) * n;
-    u64* T = at;                    // one three-part product per item
-    u64* D = T + t_stride * batch;  // one operand copied down to the product's level
-    u64* ks = D + d_stride * batch; // relinearize / rescale workspace
+    const PolyEvalWs w = poly_eval_ws(c, plan, n_steps, depth, batch, ws, reg.data());
+    reg[(size_t) n_steps] = {out, so, plan[n_steps - 1].level + 1};
+    u64* T = ws + w.T;   // one three-part product per item
+    u64* D = ws + w.D;   // one operand copied down to the product's level
+    u64* ks = ws + w.ks; // relinearize / rescale workspace
 
     // reg[x] * reg[y] at level ml, relinearized, into dst ([3][ml + 1][N] per item, two parts on return)
     auto product = [&](const Reg& x, const Reg& y, int ml, u64* dst, u64 dst_stride) -> hipError_t {
@@ -1070,8 +1145,8 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
         Reg in[2] = {x, y};
         for (Reg& r : in)
             if (r.limbs != l) { // at most one of the two sits above the product's level
-                TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) l * n, d_stride, np, l, 2, batch, st));
-                r = {D, d_stride, l};
+                TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) l * n, w.d_stride, np, l, 2, batch, st));
+                r = {D, w.d_stride, l};
             }
         TRY(op_ckks_multiply(c, in[0].p, in[0].stride, in[1].p, in[1].stride, dst, dst_stride, Q - l, batch, st));
         return op_ckks_relinearize(c, dst, dst_stride, relin_key, Q - l, batch, ks, st);
@@ -1083,7 +1158,7 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
         if (s.kind == POLY_STEP_POWER) {
             const bool in_place = s.c == POLY_TAIL_NONE;
             u64* prod = in_place ? dst.p : T;
-            const u64 ps = in_place ? dst.stride : t_stride;
+            const u64 ps = in_place ? dst.stride : w.t_stride;
             TRY(product(reg[(size_t) s.a], reg[(size_t) s.b], s.mul_level, prod, ps));
             TRY(op_ckks_rescale(c, prod, ps, Q - (s.mul_level + 1), batch, ks, st));
             if (in_place) continue;
@@ -1108,13 +1183,13 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
                 TRY(op_ckks_rescale(c, q.p, q.stride, Q - q.limbs, batch, ks, st));
                 q.limbs -= 1;
             }
-            TRY(product(q, reg[(size_t) s.b], s.mul_level, T, t_stride));
+            TRY(product(q, reg[(size_t) s.b], s.mul_level, T, w.t_stride));
             const int sum_limbs = dst.limbs + (s.rescale_after ? 1 : 0);
-            Reg terms2[2] = {{T, t_stride, s.mul_level + 1}, reg[(size_t) s.c]};
+            Reg terms2[2] = {{T, w.t_stride, s.mul_level + 1}, reg[(size_t) s.c]};
             for (Reg& r : terms2)
                 if (r.limbs != sum_limbs) { // the product is relinearized: D is free again
-                    TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) sum_limbs * n, d_stride, np, sum_limbs, 2, batch, st));
-                    r = {D, d_stride, sum_limbs};
+                    TRY(rns_copy_limbs(r.p, (u64) r.limbs * n, r.stride, D, (u64) sum_limbs * n, w.d_stride, np, sum_limbs, 2, batch, st));
+                    r = {D, w.d_stride, sum_limbs};
                 }
             const u64* tp[2] = {terms2[0].p, terms2[1].p};
             const u64 tsd[2] = {terms2[0].stride, terms2[1].stride};
@@ -1140,18 +1215,18 @@ hipError_t op_ckks_logic_gate(const Context& c, int gate, const u64* a, u64 as, 
         return rns_gate_combine(false, k[0], k[1], k[2], a, as, l, nullptr, GATE_B_NONE, 0, 0, nullptr, 0, 0, scale_one,
                                 nullptr, none, out, so, mods, np, l, batch, st);
     if (l < 2 || (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN)) return hipErrorInvalidValue;
-    const u64 ps = (u64) 3 * l * c.n;
+    const GateWs w = gate_ws(c, false, depth, batch);
     u64* prod = ws;
-    u64* ks = ws + ps * batch;
+    u64* ks = ws + w.ks;
     if (b_kind == GATE_B_CIPHER) {
-        TRY(op_ckks_multiply(c, a, as, b, bs, prod, ps, depth, batch, st));
-        TRY(op_ckks_relinearize(c, prod, ps, relin_key, depth, batch, ks, st));
+        TRY(op_ckks_multiply(c, a, as, b, bs, prod, w.ps, depth, batch, st));
+        TRY(op_ckks_relinearize(c, prod, w.ps, relin_key, depth, batch, ks, st));
     } else {
         for (int i = 0; i < batch; i++) // cipherplain_kernel takes one ciphertext
-            TRY(kg_pk_u(a + as * i, b + bs * i, prod + ps * i, mods, np, l, st));
+            TRY(kg_pk_u(a + as * i, b + bs * i, prod + w.ps * i, mods, np, l, st));
     }
-    TRY(op_ckks_rescale(c, prod, ps, depth, batch, ks, st));
-    return rns_gate_combine(false, k[0], k[1], k[2], a, as, l, b, b_kind, bs, l, prod, ps, l - 1, scale_one, nullptr, none,
+    TRY(op_ckks_rescale(c, prod, w.ps, depth, batch, ks, st));
+    return rns_gate_combine(false, k[0], k[1], k[2], a, as, l, b, b_kind, bs, l, prod, w.ps, l - 1, scale_one, nullptr, none,
                             out, so, mods, np, l - 1, batch, st);
 }
 
@@ -1169,17 +1244,17 @@ hipError_t op_bfv_logic_gate(const Context& c, int gate, const u64* a, u64 as, c
         return rns_gate_combine(true, k[0], k[1], k[2], a, as, Q, nullptr, GATE_B_NONE, 0, 0, nullptr, 0, 0, 0.0, cd, scale,
                                 out, so, mods, np, Q, batch, st);
     if (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN) return hipErrorInvalidValue;
-    const u64 ps = (u64) 3 * Q * c.n;
+    const GateWs w = gate_ws(c, true, 0, batch);
     u64* prod = ws;
-    u64* ks = ws + ps * batch;
+    u64* ks = ws + w.ks;
     if (b_kind == GATE_B_CIPHER) {
-        TRY(op_bfv_multiply(c, a, as, b, bs, prod, ps, batch, ks, st));
-        TRY(op_bfv_relinearize(c, prod, ps, relin_key, batch, ks, st));
+        TRY(op_bfv_multiply(c, a, as, b, bs, prod, w.ps, batch, ks, st));
+        TRY(op_bfv_relinearize(c, prod, w.ps, relin_key, batch, ks, st));
     } else {
         for (int i = 0; i < batch; i++) // multiply_plain_bfv takes one ciphertext
-            TRY(op_bfv_multiply_plain(c, a + as * i, b + bs * i, prod + ps * i, ks, st));
+            TRY(op_bfv_multiply_plain(c, a + as * i, b + bs * i, prod + w.ps * i, ks, st));
     }
-    return rns_gate_combine(true, k[0], k[1], k[2], a, as, Q, b, b_kind, bs, Q, prod, ps, Q, 0.0, cd, scale, out, so, mods,
+    return rns_gate_combine(true, k[0], k[1], k[2], a, as, Q, b, b_kind, bs, Q, prod, w.ps, Q, 0.0, cd, scale, out, so, mods,
                             np, Q, batch, st);
 }
 
@@ -1243,10 +1318,10 @@ hipError_t op_gen_switch_key(const Context& c, Rng& r, const u64* sk, int galois
 static hipError_t encrypt_zero(const Context& c, Rng& r, const u64* pk, u64* ct, u64* ws, hipStream_t st)
 {
     const int np = c.n_power, Qp = c.Qp_size;
-    const u64 n = c.n;
-    u64* u = ws;                       // [Q'][N]
-    u64* e = u + (u64) Qp * n;         // [2][Q'][N]
-    u64* pku = e + (u64) 2 * Qp * n;   // [2][Q'][N]
+    const EncryptWs w = encrypt_ws(c);
+    u64* u = ws;           // [Q'][N]
+    u64* e = ws + w.e;     // [2][Q'][N]
+    u64* pku = ws + w.pku; // [2][Q'][N]
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_ternary(u, mods, np, Qp, 1, r.seed, r.stream++, st));
     TRY(kg_gaussian(e, mods, np, Qp, 2, r.seed, r.stream++, c.gauss_cdt, st));
@@ -1393,8 +1468,8 @@ hipError_t op_ckks_decode(const Context& c, int mode, const u64* plain, int dept
 {
     const int slots = (int) (c.n >> 1), l = c.Q_size - depth;
     if (l < 1) return hipErrorInvalidValue;
-    u64* coeff = ws;                      // [l][N]
-    void* cbuf = ws + (u64) l * c.n;      // slots complex doubles
+    u64* coeff = ws;                                   // [l][N]
+    void* cbuf = ws + ckks_decode_ws(c, depth).second; // slots complex doubles
     TRY(transform(c, plain, coeff, l, l, true, st));                                       // :469
     const DecoderTables d = decoder_tables(c, depth);
     if (mode == 2)                                                                         // :586-635
@@ -1424,7 +1499,7 @@ hipError_t op_mpc_public_key_share(const Context& c, Rng& crs, Rng& r, const u64
 {
     const int Qp = c.Qp_size;
     u64* e = ws;
-    u64* av = ws + (u64) Qp * c.n;
+    u64* av = ws + public_key_share_ws(c).second;
     TRY(kg_uniform(av, c.plan_qp.mods, c.n_power, Qp, 1, crs.seed, crs.stream++, st));
     TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 1, r.seed, r.stream++, c.gauss_cdt, st));
     TRY(transform(c, e, e, Qp, Qp, false, st));
@@ -1439,8 +1514,8 @@ hipError_t op_mpc_switch_key_share(const Context& c, Rng& crs, Rng& r, const u64
     const int Q = c.Q_size, Qp = c.Qp_size, d = switch_key_digits(c);
     const int width = c.P_size == 1 ? 1 : c.m2_width;
     const int errs = u_out ? 2 : 1; // round 1 of the relinearisation key carries an error in both parts
-    u64* e = ws;                                  // [errs][d][Q'][N]
-    u64* av = ws + (u64) errs * d * Qp * c.n;     // [d][Q'][N]
+    u64* e = ws;                                        // [errs][d][Q'][N]
+    u64* av = ws + switch_key_share_ws(c, errs).second; // [d][Q'][N]
     const Mod* mods = c.plan_qp.mods;
     TRY(kg_uniform(av, mods, c.n_power, Qp, d, crs.seed, crs.stream++, st));
     TRY(kg_gaussian(e, mods, c.n_power, Qp, errs * d, r.seed, r.stream++, c.gauss_cdt, st));
@@ -1458,7 +1533,7 @@ hipError_t op_mpc_relin_key_share_round2(const Context& c, Rng& r, const u64* sk
                                          u64* share, u64* ws, hipStream_t st)
 {
     const int Qp = c.Qp_size, d = switch_key_digits(c);
-    u64* e = ws; // [2][d][Q'][N]
+    u64* e = ws; // [2][d][Q'][N], the first region of switch_key_share_ws(c, 2)
     TRY(kg_gaussian(e, c.plan_qp.mods, c.n_power, Qp, 2 * d, r.seed, r.stream++, c.gauss_cdt, st));
     TRY(transform(c, e, e, Qp, 2 * d * Qp, false, st));
     return kg_mpc_relin_round2(share, round1_sum, sk, u, e, c.plan_qp.mods, c.n_power, Qp, d, st);
@@ -1601,8 +1676,8 @@ hipError_t op_mpc_bfv_refresh_merge(const Context& c, Rng& crs, const u64* ct, u
     const int np = c.n_power, Q = c.Q_size;
     const Mod* mods = c.plan_qp.mods;
     const u64 sh_stride = (u64) (2 * Q) << np, part = (u64) Q << np;
-    u64* plain = ws;                          // [batch][N]
-    u64* head_sum = ws + ((u64) batch << np); // [batch][Q][N], beyond 16 shares
+    u64* plain = ws;                                              // [batch][N]
+    u64* head_sum = ws + bfv_refresh_merge_ws(c, batch).head_sum; // [batch][Q][N], beyond 16 shares
     TRY(bfv_sum_and_round(c, ct, cs, shares, k, sh_stride, plain, head_sum, batch, st));
     TRY(kg_mpc_refresh_finish(out, so, shares, k, sh_stride, part, 0, plain, c.tab.coeff_div_plain_modulus,
                               bfv_plain_scale(c), mods, np, Q, batch, crs.seed, take_streams(crs, batch), st));

@@ -13,6 +13,8 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
        OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21, OP_CKKS_LOGIC_GATE = 22,
        OP_BFV_LOGIC_GATE = 23 };
 
+// Words of the workspace row `op` for `batch` items at `depth`.  Every shape is stated once, by a layout function of
+// ops.cpp that this query and the sequence both read.
 size_t ops_workspace_elems(const Context& c, int op, int depth, int batch);
 
 hipError_t op_ckks_multiply(const Context& c, const u64* ct1, u64 s1, const u64* ct2, u64 s2, u64* out, u64 so,
@@ -35,10 +37,13 @@ hipError_t op_bfv_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out
                                int galois_elt, int batch, u64* ws, hipStream_t st);
 
 // fast_single_hoisting_rotation_ckks_method_I / _II (ckks/operator.cu:4674-5446): `count` rotations of one
-// ciphertext with the decomposition and the digit NTT shared; keys / galois_elts are HOST arrays
+// ciphertext with the decomposition and the digit NTT shared; keys / galois_elts are HOST arrays.  Workspace: the
+// key-switch layout with `group` accumulators, OP_CKKS_GALOIS (group 1) or OP_CKKS_ROTATE_HOISTED (group 4);
+// ops_rotate_hoisted_accumulators: the group a workspace of ws_elems words has room for.
+int ops_rotate_hoisted_accumulators(const Context& c, int depth, int batch, size_t ws_elems);
 hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* const* keys,
                                   const int* galois_elts, int count, int depth, int batch, u64* ws, hipStream_t st,
-                                  int group = 1 /* accumulators in ws: 1 (OP_CKKS_GALOIS) or 4 (OP_CKKS_ROTATE_HOISTED) */);
+                                  int group = 1);
 
 // y = M v for a plaintext matrix given by its diagonals and an encrypted vector, baby-step/giant-step (the project's own
 // entry; the reference's multiply_matrix, ckks/operator.cu:2803-2895, is private to its bootstrapping):
