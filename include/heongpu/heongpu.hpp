@@ -122,6 +122,14 @@ inline void hip(hipError_t e)
 {
     if (e != hipSuccess) throw HipException(hipGetErrorString(e));
 }
+// one field of the reference's wire format (util/serializer.h): the object's bytes as they lie in memory
+template <typename T> void put(std::ostream& os, const T& v) { os.write((const char*) &v, sizeof(T)); }
+template <typename T> void get(std::istream& is, T& v) { is.read((char*) &v, sizeof(T)); }
+// every class of this layer starts from a context whose device tables exist
+template <typename C> void require_generated(const C& context)
+{
+    if (!context || !context->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+}
 } // namespace detail
 
 // ------------------------------------------------------------------ memory pool
@@ -551,7 +559,8 @@ template <typename T> using HostVector = std::vector<T, PinnedAllocator<T>>;
 // An operator that touches a HOST-stored object stages it on use (an asynchronous copy on the operator's
 // stream); when the operator returns, inputs go back to where they were (keep_initial_condition_, with a
 // copy-back because the operators take non-const references) or stay on the device, and every object the
-// operator wrote is placed where ExecutionOptions::storage_ says.
+// operator wrote is placed where ExecutionOptions::storage_ says.  An object that is both -- the operand of an in-place
+// form -- goes back to the host if either rule says so.
 namespace detail {
 class StoredBuffer;
 struct OpScope {
@@ -714,8 +723,12 @@ inline OpScope::~OpScope() noexcept(false)
     // the operator is leaving through an exception: no copies, no synchronisation (a second throw from here would be
     // std::terminate); staged operands simply stay where they are
     if (std::uncaught_exceptions() > exceptions_) return;
-    for (StoredBuffer* b : written_)
-        if (o_.storage_ == storage_type::HOST) b->store_in_host(o_.stream_);
+    // what the operator wrote goes where storage_ says; an operand it staged from the host and then overwrote (an in-place
+    // form: add_inplace, multiply_inplace) is still an input, and keep_initial_condition_ sends it back to the host
+    for (StoredBuffer* b : written_) {
+        const bool host_input = std::find(staged_.begin(), staged_.end(), b) != staged_.end();
+        if (o_.storage_ == storage_type::HOST || (o_.keep_initial_condition_ && host_input)) b->store_in_host(o_.stream_);
+    }
     for (StoredBuffer* b : staged_) {
         if (std::find(written_.begin(), written_.end(), b) != written_.end()) continue;
         if (!b->staged()) continue;
@@ -853,18 +866,16 @@ template <Scheme S> class HEContextImpl { // BFV / CKKS; the TFHE specialisation
     {
         if (!poly_modulus_degree_specified_ || !coeff_modulus_specified_ || (S == Scheme::BFV && !plain_modulus_specified_))
             throw std::runtime_error("Context has no enough parameters to serialize!");
-        const scheme_type scheme = (S == Scheme::BFV) ? scheme_type::bfv : scheme_type::ckks;
-        os.write((const char*) &scheme, sizeof(scheme));
-        os.write((const char*) &sec_level_, sizeof(sec_level_));
-        os.write((const char*) &keyswitching_type_, sizeof(keyswitching_type_));
-        os.write((const char*) &n, sizeof(n));
-        os.write((const char*) &n_power, sizeof(n_power));
-        const int coeff_modulus = Q_prime_size;
-        os.write((const char*) &coeff_modulus, sizeof(int));
-        os.write((const char*) &total_coeff_bit_count, sizeof(int));
-        os.write((const char*) &Q_prime_size, sizeof(int));
-        os.write((const char*) &Q_size, sizeof(int));
-        os.write((const char*) &P_size, sizeof(int));
+        detail::put(os, (S == Scheme::BFV) ? scheme_type::bfv : scheme_type::ckks);
+        detail::put(os, sec_level_);
+        detail::put(os, keyswitching_type_);
+        detail::put(os, n);
+        detail::put(os, n_power);
+        detail::put(os, Q_prime_size); // coeff_modulus
+        detail::put(os, total_coeff_bit_count);
+        detail::put(os, Q_prime_size);
+        detail::put(os, Q_size);
+        detail::put(os, P_size);
         write_counted(os, prime_vector_);
         std::vector<Data64> base_q;
         for (const Modulus64& m : prime_vector_) base_q.push_back(m.value);
@@ -872,31 +883,31 @@ template <Scheme S> class HEContextImpl { // BFV / CKKS; the TFHE specialisation
         write_counted(os, Qprime_mod_bit_sizes_);
         write_counted(os, Q_mod_bit_sizes_);
         write_counted(os, P_mod_bit_sizes_);
-        if (S == Scheme::BFV) os.write((const char*) &plain_modulus_, sizeof(plain_modulus_));
+        if (S == Scheme::BFV) detail::put(os, plain_modulus_);
     }
     void load(std::istream& is)
     {
         if (context_generated_ || h_) throw std::runtime_error("Context has been already exist!");
         scheme_type scheme = scheme_type::none;
-        is.read((char*) &scheme, sizeof(scheme));
+        detail::get(is, scheme);
         if (scheme != ((S == Scheme::BFV) ? scheme_type::bfv : scheme_type::ckks)) throw std::runtime_error("Invalid scheme binary!");
-        is.read((char*) &sec_level_, sizeof(sec_level_));
-        is.read((char*) &keyswitching_type_, sizeof(keyswitching_type_));
-        is.read((char*) &n, sizeof(n));
-        is.read((char*) &n_power, sizeof(n_power));
         int coeff_modulus = 0;
-        is.read((char*) &coeff_modulus, sizeof(int));
-        is.read((char*) &total_coeff_bit_count, sizeof(int));
-        is.read((char*) &Q_prime_size, sizeof(int));
-        is.read((char*) &Q_size, sizeof(int));
-        is.read((char*) &P_size, sizeof(int));
+        detail::get(is, sec_level_);
+        detail::get(is, keyswitching_type_);
+        detail::get(is, n);
+        detail::get(is, n_power);
+        detail::get(is, coeff_modulus);
+        detail::get(is, total_coeff_bit_count);
+        detail::get(is, Q_prime_size);
+        detail::get(is, Q_size);
+        detail::get(is, P_size);
         std::vector<Data64> base_q;
         read_counted(is, prime_vector_);
         read_counted(is, base_q);
         read_counted(is, Qprime_mod_bit_sizes_);
         read_counted(is, Q_mod_bit_sizes_);
         read_counted(is, P_mod_bit_sizes_);
-        if (S == Scheme::BFV) is.read((char*) &plain_modulus_, sizeof(plain_modulus_));
+        if (S == Scheme::BFV) detail::get(is, plain_modulus_);
         if (!is || (int) prime_vector_.size() != Q_prime_size || Q_size + P_size != Q_prime_size || n != (1 << n_power))
             throw std::runtime_error("Context binary is not consistent!");
         poly_modulus_degree_specified_ = true;
@@ -957,13 +968,13 @@ template <Scheme S> class HEContextImpl { // BFV / CKKS; the TFHE specialisation
     template <typename T> static void write_counted(std::ostream& os, const std::vector<T>& v)
     {
         const std::uint32_t count = (std::uint32_t) v.size();
-        os.write((const char*) &count, sizeof(count));
+        detail::put(os, count);
         os.write((const char*) v.data(), sizeof(T) * count);
     }
     template <typename T> static void read_counted(std::istream& is, std::vector<T>& v)
     {
         std::uint32_t count = 0;
-        is.read((char*) &count, sizeof(count));
+        detail::get(is, count);
         if (!is || count > (1u << 20)) throw std::runtime_error("Context binary is not consistent!");
         v.resize(count);
         is.read((char*) v.data(), sizeof(T) * count);
@@ -981,13 +992,119 @@ template <Scheme S> HEContext<S> GenHEContext(sec_level_type sec = sec_level_typ
     return std::make_shared<HEContextImpl<S>>(sec);
 }
 
+// ------------------------------------------------------------------ what the stored objects share
+namespace detail {
+// One buffer of residues in HBM or pinned host memory, and the storage manager's public face for it
+// (ckks/ciphertext.cu:52-169 and its copies in every object): Ciphertext, Plaintext, Secretkey, Publickey, Relinkey
+// and Switchkey derive from this; Galoiskey keeps a map of StoredBuffer.
+class StoredObject {
+  public:
+    Data64* data() { return buf_.data(); }
+    const Data64* data() const { return buf_.data(); }
+    void memory_set(DeviceVector<Data64>&& m) { buf_ = std::move(m); }
+    void switch_stream(hipStream_t s) { buf_.set_stream(s); }
+    hipStream_t stream() const noexcept { return buf_.stream(); }
+    bool is_on_device() const noexcept { return buf_.is_on_device(); }
+    void store_in_device(hipStream_t s = nullptr) { buf_.store_in_device(s); }
+    void store_in_host(hipStream_t s = nullptr) { buf_.store_in_host(s); }
+    void copy_to_device(hipStream_t s = nullptr) { buf_.copy_to_device(s); }
+    void remove_from_device(hipStream_t s = nullptr) { buf_.remove_from_device(s); }
+    void remove_from_host() { buf_.remove_from_host(); }
+
+  protected:
+    void download(std::vector<Data64>& out, hipStream_t s) const // get_data, and save() of an object with a stream
+    {
+        out.resize(buf_.size());
+        hip(hipMemcpyAsync(out.data(), buf_.data(), out.size() * sizeof(Data64), hipMemcpyDeviceToHost, s));
+        hip(hipStreamSynchronize(s));
+    }
+    StoredBuffer buf_;
+};
+
+// ---- wire format (util/serializer.h): fields through put / get, residues through put_payload / read_payload
+inline std::vector<Data64> to_host(const Data64* dev, size_t count)
+{
+    std::vector<Data64> h(count);
+    if (count) hip(hipMemcpy(h.data(), dev, count * sizeof(Data64), hipMemcpyDeviceToHost));
+    return h;
+}
+template <Scheme S> constexpr scheme_type wire_scheme() { return S == Scheme::BFV ? scheme_type::bfv : scheme_type::ckks; }
+template <Scheme S> void check_scheme(std::istream& is)
+{
+    scheme_type sc = scheme_type::none;
+    get(is, sc);
+    if (sc != wire_scheme<S>()) throw std::runtime_error("Invalid scheme binary!");
+}
+inline void put_payload(std::ostream& os, const Data64* dev, size_t count)
+{
+    const std::vector<Data64> h = to_host(dev, count);
+    os.write((const char*) h.data(), sizeof(Data64) * count);
+}
+inline DeviceVector<Data64> read_payload(std::istream& is, size_t count, const char* what)
+{
+    std::vector<Data64> h(count);
+    is.read((char*) h.data(), sizeof(Data64) * count);
+    if (!is) throw std::runtime_error(std::string(what) + " binary is truncated!");
+    DeviceVector<Data64> d(h);
+    hip(hipStreamSynchronize(nullptr));
+    return d;
+}
+
+// The scratch memory of one C call: ceil(bytes / 8) words on the operator's stream; the call is handed the byte count
+// the size query reported.  No bytes, no allocation: data() is null then (a NOT gate).
+struct Workspace {
+    Workspace(size_t b, hipStream_t s) : bytes(b), words((b + 7) / 8, s) {}
+    Workspace(hegpu_context* h, int op, int depth, hipStream_t s) : Workspace(hegpu_workspace_bytes(h, op, depth, 1), s) {}
+    Data64* data() const { return words.data(); }
+    const size_t bytes;
+    DeviceVector<Data64> words;
+};
+
+// The shape of a key-switch key (*/evaluationkey.cu:30-36): d digits of 2 x Q' x N residues, with d = Q for one
+// special prime (method I) and ceil(Q / m) otherwise, m = 2 (BFV) or P_size (CKKS).  Relinkey, Switchkey and
+// Galoiskey derive from it; it also writes and reads the header their wire formats start with.
+class KeySwitchShape {
+  public:
+    KeySwitchShape() = default;
+    template <Scheme S> explicit KeySwitchShape(const std::shared_ptr<HEContextImpl<S>>& c)
+    {
+        require_generated(c);
+        const int m = (S == Scheme::BFV) ? 2 : c->P_size;
+        ring_size = c->n;
+        Q_prime_size_ = c->Q_prime_size;
+        Q_size_ = c->Q_size;
+        d_ = c->P_size == 1 ? c->Q_size : (c->Q_size + m - 1) / m;
+        key_size_ = (Data64) 2 * d_ * Q_prime_size_ * ring_size;
+        key_type = c->keyswitching_type_;
+    }
+    size_t size() const { return (size_t) key_size_; } // elements of one key
+    keyswitching_type key_type = keyswitching_type::KEYSWITCHING_METHOD_I;
+
+  protected:
+    template <Scheme S> void put_header(std::ostream& os) const // scheme, key type (u8), ring size, Q', Q, d (int)
+    {
+        put(os, wire_scheme<S>());
+        put(os, key_type);
+        put(os, ring_size); put(os, Q_prime_size_); put(os, Q_size_); put(os, d_);
+    }
+    template <Scheme S> void get_header(std::istream& is)
+    {
+        check_scheme<S>(is);
+        get(is, key_type);
+        get(is, ring_size); get(is, Q_prime_size_); get(is, Q_size_); get(is, d_);
+    }
+    int ring_size = 0, Q_prime_size_ = 0, Q_size_ = 0, d_ = 0;
+    Data64 key_size_ = 0;
+};
+} // namespace detail
+
 // ------------------------------------------------------------------ ciphertext
 template <Scheme S> class HEArithmeticOperator;
 namespace detail {
 template <Scheme S> class LogicOperatorBase;
 }
 
-template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
+template <Scheme S> class Ciphertext : public detail::StoredObject { // host/{ckks,bfv}/ciphertext.cuh
     friend class HEArithmeticOperator<S>;
     friend class detail::LogicOperatorBase<S>;
 
@@ -995,27 +1112,15 @@ template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
     Ciphertext() = default; // filled by load(std::istream&) or by an operator
     explicit Ciphertext(HEContext<S> context, const ExecutionOptions& options = ExecutionOptions())
     {
-        if (!context || !context->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context);
         ring_size_ = context->n;
         coeff_modulus_count_ = context->Q_size;
         cipher_size_ = 2;
         in_ntt_domain_ = (S == Scheme::CKKS); // CKKS ciphertexts live in the NTT domain (ckks/ciphertext.cu)
-        device_locations_.set_storage(options.storage_);
-        device_locations_.set_stream(options.stream_);
+        buf_.set_storage(options.storage_);
+        buf_.set_stream(options.stream_);
     }
-    Data64* data() { return device_locations_.data(); }
-    const Data64* data() const { return device_locations_.data(); }
-    size_t memory_size() const { return device_locations_.size(); }
-    void memory_set(DeviceVector<Data64>&& m) { device_locations_ = std::move(m); }
-    void switch_stream(hipStream_t s) { device_locations_.set_stream(s); }
-    hipStream_t stream() const noexcept { return device_locations_.stream(); }
-    // storage manager (ckks/ciphertext.cu:52-169): park the residues in pinned host memory / bring them back
-    bool is_on_device() const noexcept { return device_locations_.is_on_device(); }
-    void store_in_device(hipStream_t s = nullptr) { device_locations_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_locations_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_locations_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_locations_.remove_from_device(s); }
-    void remove_from_host() { device_locations_.remove_from_host(); }
+    size_t memory_size() const { return buf_.size(); }
     inline int ring_size() const noexcept { return ring_size_; }
     inline int coeff_modulus_count() const noexcept { return coeff_modulus_count_; }
     inline int size() const noexcept { return cipher_size_; }
@@ -1027,17 +1132,11 @@ template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
     inline bool relinearization_required() const noexcept { return relinearization_required_; }
     inline encoding encoding_type() const noexcept { return encoding_; } // CKKS: slots or coefficients
     encoding encoding_ = encoding::SLOT;
-    void get_data(std::vector<Data64>& out, hipStream_t s = nullptr) const
-    {
-        out.resize(device_locations_.size());
-        detail::hip(hipMemcpyAsync(out.data(), device_locations_.data(), out.size() * sizeof(Data64),
-                                   hipMemcpyDeviceToHost, s));
-        detail::hip(hipStreamSynchronize(s));
-    }
+    void get_data(std::vector<Data64>& out, hipStream_t s = nullptr) const { download(out, s); }
     // used by the encryptor: take ownership of freshly produced residues
     void adopt(DeviceVector<Data64>&& m, int cipher_size, int depth, double scale)
     {
-        device_locations_ = std::move(m);
+        buf_ = std::move(m);
         cipher_size_ = cipher_size;
         depth_ = depth;
         scale_ = scale;
@@ -1050,7 +1149,7 @@ template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
     {
         const size_t want = (size_t) cipher_size * (coeff_modulus_count_ - depth) * ring_size_;
         if (host.size() != want) throw std::invalid_argument("Invalid Ciphertexts size!");
-        device_locations_ = DeviceVector<Data64>(host, s);
+        buf_ = DeviceVector<Data64>(host, s);
         cipher_size_ = cipher_size;
         depth_ = depth;
         scale_ = scale;
@@ -1065,66 +1164,51 @@ template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
     void save(std::ostream& os) const
     {
         if (!ciphertext_generated_) throw std::runtime_error("Ciphertext is not generated so can not be serialized!");
-        const std::uint8_t scheme = (std::uint8_t) S, storage = (std::uint8_t) storage_type::DEVICE;
-        const std::uint8_t enc = (std::uint8_t) encoding_;
-        os.write((const char*) &scheme, 1);
-        os.write((const char*) &ring_size_, sizeof(int));
-        os.write((const char*) &coeff_modulus_count_, sizeof(int));
-        os.write((const char*) &cipher_size_, sizeof(int));
-        if (S == Scheme::CKKS) os.write((const char*) &depth_, sizeof(int));
-        os.write((const char*) &in_ntt_domain_, sizeof(bool));
-        os.write((const char*) &storage, 1);
-        if (S == Scheme::CKKS) {
-            os.write((const char*) &scale_, sizeof(double));
-            os.write((const char*) &enc, 1);
-            os.write((const char*) &rescale_required_, sizeof(bool));
-        }
-        os.write((const char*) &relinearization_required_, sizeof(bool));
-        os.write((const char*) &ciphertext_generated_, sizeof(bool));
+        detail::put(os, detail::wire_scheme<S>());
+        detail::put(os, ring_size_); detail::put(os, coeff_modulus_count_); detail::put(os, cipher_size_);
+        if (S == Scheme::CKKS) detail::put(os, depth_);
+        detail::put(os, in_ntt_domain_);
+        detail::put(os, storage_type::DEVICE);
+        if (S == Scheme::CKKS) { detail::put(os, scale_); detail::put(os, encoding_); detail::put(os, rescale_required_); }
+        detail::put(os, relinearization_required_);
+        detail::put(os, ciphertext_generated_);
         const std::uint32_t count = (std::uint32_t) ((size_t) cipher_size_ * (coeff_modulus_count_ - depth_) * ring_size_);
-        std::vector<Data64> host;
-        get_data(host, device_locations_.stream());
+        std::vector<Data64> host; // through the object's own stream: the residues may still be in flight there
+        download(host, buf_.stream());
         if (host.size() < count) throw std::runtime_error("Ciphertext memory is smaller than its description!");
-        os.write((const char*) &count, sizeof(count));
+        detail::put(os, count);
         os.write((const char*) host.data(), sizeof(Data64) * count);
     }
     void load(std::istream& is)
     {
         if (ciphertext_generated_) throw std::runtime_error("Ciphertext has been already exist!");
-        std::uint8_t scheme = 0, storage = 0, enc = 0;
-        is.read((char*) &scheme, 1);
-        if (scheme != (std::uint8_t) S) throw std::runtime_error("Invalid scheme binary!");
+        detail::check_scheme<S>(is);
         int ring = 0, count_mod = 0;
-        is.read((char*) &ring, sizeof(int));
-        is.read((char*) &count_mod, sizeof(int));
+        detail::get(is, ring); detail::get(is, count_mod);
         if (ring_size_ == 0) { ring_size_ = ring; coeff_modulus_count_ = count_mod; } // default-constructed
         if (ring != ring_size_ || count_mod != coeff_modulus_count_)
             throw std::runtime_error("Ciphertext binary does not match the context!");
-        is.read((char*) &cipher_size_, sizeof(int));
+        detail::get(is, cipher_size_);
         if (!is || cipher_size_ < 2 || cipher_size_ > 3) throw std::runtime_error("Ciphertext size is not correct!");
         depth_ = 0;
-        if (S == Scheme::CKKS) is.read((char*) &depth_, sizeof(int));
-        is.read((char*) &in_ntt_domain_, sizeof(bool));
-        is.read((char*) &storage, 1);
-        if (S == Scheme::CKKS) {
-            is.read((char*) &scale_, sizeof(double));
-            is.read((char*) &enc, 1);
-            encoding_ = (encoding) enc;
-            is.read((char*) &rescale_required_, sizeof(bool));
-        }
-        is.read((char*) &relinearization_required_, sizeof(bool));
+        storage_type st;
         bool generated = false;
-        is.read((char*) &generated, sizeof(bool));
         std::uint32_t count = 0;
-        is.read((char*) &count, sizeof(count));
+        if (S == Scheme::CKKS) detail::get(is, depth_);
+        detail::get(is, in_ntt_domain_);
+        detail::get(is, st);
+        if (S == Scheme::CKKS) { detail::get(is, scale_); detail::get(is, encoding_); detail::get(is, rescale_required_); }
+        detail::get(is, relinearization_required_);
+        detail::get(is, generated);
+        detail::get(is, count);
         if (!is || depth_ < 0 || depth_ >= coeff_modulus_count_ ||
             count != (std::uint32_t) ((size_t) cipher_size_ * ring_size_ * (coeff_modulus_count_ - depth_)))
             throw std::runtime_error("Ciphertext size is not correct!");
         std::vector<Data64> host(count);
         is.read((char*) host.data(), sizeof(Data64) * count);
         if (!is) throw std::runtime_error("Ciphertext binary is truncated!");
-        device_locations_ = DeviceVector<Data64>(host, device_locations_.stream());
-        detail::hip(hipStreamSynchronize(device_locations_.stream()));
+        buf_ = DeviceVector<Data64>(host, buf_.stream());
+        detail::hip(hipStreamSynchronize(buf_.stream()));
         ciphertext_generated_ = true;
     }
 
@@ -1133,170 +1217,87 @@ template <Scheme S> class Ciphertext { // host/{ckks,bfv}/ciphertext.cuh
     double scale_ = 0;
     bool in_ntt_domain_ = false, rescale_required_ = false, relinearization_required_ = false;
     bool ciphertext_generated_ = false;
-    detail::StoredBuffer device_locations_; // HBM or pinned host memory (storage manager)
 };
 
-namespace detail {
-inline std::vector<Data64> to_host(const Data64* dev, size_t count)
-{
-    std::vector<Data64> h(count);
-    if (count) hip(hipMemcpy(h.data(), dev, count * sizeof(Data64), hipMemcpyDeviceToHost));
-    return h;
-}
-template <typename T> void put(std::ostream& os, const T& v) { os.write((const char*) &v, sizeof(T)); }
-template <typename T> void get(std::istream& is, T& v) { is.read((char*) &v, sizeof(T)); }
-template <Scheme S> constexpr scheme_type wire_scheme() { return S == Scheme::BFV ? scheme_type::bfv : scheme_type::ckks; }
-template <Scheme S> void check_scheme(std::istream& is)
-{
-    scheme_type sc = scheme_type::none;
-    get(is, sc);
-    if (sc != wire_scheme<S>()) throw std::runtime_error("Invalid scheme binary!");
-}
-inline DeviceVector<Data64> read_payload(std::istream& is, size_t count, const char* what)
-{
-    std::vector<Data64> h(count);
-    is.read((char*) h.data(), sizeof(Data64) * count);
-    if (!is) throw std::runtime_error(std::string(what) + " binary is truncated!");
-    DeviceVector<Data64> d(h);
-    hip(hipStreamSynchronize(nullptr));
-    return d;
-}
-} // namespace detail
-
 // ------------------------------------------------------------------ keys
-template <Scheme S> class Relinkey { // host/*/evaluationkey.cuh; size 2*d*Q'*N (evaluationkey.cu:30-36)
+template <Scheme S> class Relinkey : public detail::StoredObject, public detail::KeySwitchShape { // host/*/evaluationkey.cuh
   public:
     Relinkey() = default;
-    explicit Relinkey(HEContext<S> context) : context_(std::move(context))
-    {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
-        const int m = (S == Scheme::BFV) ? 2 : context_->P_size;
-        ring_size = context_->n;
-        Q_prime_size_ = context_->Q_prime_size;
-        Q_size_ = context_->Q_size;
-        d_ = context_->P_size == 1 ? context_->Q_size : (context_->Q_size + m - 1) / m;
-        relinkey_size_ = (Data64) 2 * d_ * Q_prime_size_ * ring_size;
-        key_type = context_->keyswitching_type_;
-    }
-    Data64* data() { return device_location_.data(); }
-    size_t size() const { return (size_t) relinkey_size_; }
+    explicit Relinkey(HEContext<S> context) : detail::KeySwitchShape(context), context_(std::move(context)) {}
     void load(const std::vector<Data64>& host, hipStream_t s = nullptr) // a key produced elsewhere
     {
-        if (host.size() != relinkey_size_) throw std::invalid_argument("Invalid relinkey size!");
-        device_location_ = DeviceVector<Data64>(host, s);
+        if (host.size() != key_size_) throw std::invalid_argument("Invalid relinkey size!");
+        buf_ = DeviceVector<Data64>(host, s);
         relin_key_generated_ = true;
     }
-    void memory_set(DeviceVector<Data64>&& m) { device_location_ = std::move(m); }
     void set_context(HEContext<S> context) { context_ = std::move(context); }
-    bool is_on_device() const noexcept { return device_location_.is_on_device(); } // storage manager, see Ciphertext
-    void store_in_device(hipStream_t s = nullptr) { device_location_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_location_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_location_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_location_.remove_from_device(s); }
-    void remove_from_host() { device_location_.remove_from_host(); }
     // */evaluationkey.cu Relinkey::save/load (bfv :91-200): scheme, key type (u8), ring size, Q', Q,
     // d, d_tilda, r_prime (int), storage (u8), generated (bool), element count (u64), the key
     void save(std::ostream& os) const
     {
         if (!relin_key_generated_) throw std::runtime_error("Relinkey is not generated so can not be serialized!");
-        detail::put(os, detail::wire_scheme<S>());
-        detail::put(os, key_type);
-        detail::put(os, ring_size); detail::put(os, Q_prime_size_); detail::put(os, Q_size_);
-        detail::put(os, d_); detail::put(os, d_tilda_); detail::put(os, r_prime_);
+        put_header<S>(os);
+        detail::put(os, d_tilda_); detail::put(os, r_prime_);
         detail::put(os, storage_type::DEVICE);
         detail::put(os, relin_key_generated_);
-        detail::put(os, relinkey_size_);
-        const std::vector<Data64> h = detail::to_host(device_location_.data(), (size_t) relinkey_size_);
-        os.write((const char*) h.data(), sizeof(Data64) * h.size());
+        detail::put(os, key_size_);
+        detail::put_payload(os, buf_.data(), size());
     }
     void load(std::istream& is)
     {
         if (relin_key_generated_) throw std::runtime_error("Relinkey has been already exist!");
-        detail::check_scheme<S>(is);
         storage_type st;
-        detail::get(is, key_type);
-        detail::get(is, ring_size); detail::get(is, Q_prime_size_); detail::get(is, Q_size_);
-        detail::get(is, d_); detail::get(is, d_tilda_); detail::get(is, r_prime_);
+        get_header<S>(is);
+        detail::get(is, d_tilda_); detail::get(is, r_prime_);
         detail::get(is, st);
         detail::get(is, relin_key_generated_);
-        detail::get(is, relinkey_size_);
-        if (!is || relinkey_size_ > ((Data64) 1 << 36)) throw std::runtime_error("Invalid relinkey size!");
-        device_location_ = detail::read_payload(is, (size_t) relinkey_size_, "Relinkey");
+        detail::get(is, key_size_);
+        if (!is || key_size_ > ((Data64) 1 << 36)) throw std::runtime_error("Invalid relinkey size!");
+        buf_ = detail::read_payload(is, size(), "Relinkey");
         relin_key_generated_ = true;
     }
-    keyswitching_type key_type = keyswitching_type::KEYSWITCHING_METHOD_I;
     bool relin_key_generated_ = false;
 
   private:
     HEContext<S> context_;
-    int ring_size = 0, Q_prime_size_ = 0, Q_size_ = 0, d_ = 0, d_tilda_ = 0, r_prime_ = 0;
-    Data64 relinkey_size_ = 0;
-    detail::StoredBuffer device_location_; // HBM or pinned host memory (storage manager)
+    int d_tilda_ = 0, r_prime_ = 0;
 };
 
 // A key that moves a ciphertext from one secret key to another (host/*/evaluationkey.cuh
 // Switchkey; generated by HEKeyGenerator::generate_switch_key, used by keyswitch())
-template <Scheme S> class Switchkey {
+template <Scheme S> class Switchkey : public detail::StoredObject, public detail::KeySwitchShape {
   public:
     Switchkey() = default;
-    explicit Switchkey(HEContext<S> context) : context_(std::move(context))
-    {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
-        const int m = (S == Scheme::BFV) ? 2 : context_->P_size;
-        ring_size = context_->n;
-        Q_prime_size_ = context_->Q_prime_size;
-        Q_size_ = context_->Q_size;
-        d_ = context_->P_size == 1 ? context_->Q_size : (context_->Q_size + m - 1) / m;
-        switchkey_size_ = (Data64) 2 * d_ * Q_prime_size_ * ring_size;
-        key_type = context_->keyswitching_type_;
-    }
-    Data64* data() { return device_location_.data(); }
-    size_t size() const { return (size_t) switchkey_size_; }
-    void memory_set(DeviceVector<Data64>&& m) { device_location_ = std::move(m); }
+    explicit Switchkey(HEContext<S> context) : detail::KeySwitchShape(context), context_(std::move(context)) {}
     void set_context(HEContext<S> context) { context_ = std::move(context); }
-    bool is_on_device() const noexcept { return device_location_.is_on_device(); } // storage manager, see Ciphertext
-    void store_in_device(hipStream_t s = nullptr) { device_location_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_location_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_location_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_location_.remove_from_device(s); }
-    void remove_from_host() { device_location_.remove_from_host(); }
     void save(std::ostream& os) const // */evaluationkey.cu Switchkey::save (bfv :835-882)
     {
         if (!switch_key_generated_) throw std::runtime_error("Switchkey is not generated so can not be serialized!");
-        detail::put(os, detail::wire_scheme<S>());
-        detail::put(os, key_type);
-        detail::put(os, ring_size); detail::put(os, Q_prime_size_); detail::put(os, Q_size_); detail::put(os, d_);
+        put_header<S>(os);
         detail::put(os, storage_type::DEVICE);
         detail::put(os, switch_key_generated_);
-        detail::put(os, switchkey_size_);
-        const std::vector<Data64> h = detail::to_host(device_location_.data(), (size_t) switchkey_size_);
-        os.write((const char*) h.data(), sizeof(Data64) * h.size());
+        detail::put(os, key_size_);
+        detail::put_payload(os, buf_.data(), size());
     }
     void load(std::istream& is)
     {
         if (switch_key_generated_) throw std::runtime_error("Switchkey has been already exist!");
-        detail::check_scheme<S>(is);
         storage_type st;
-        detail::get(is, key_type);
-        detail::get(is, ring_size); detail::get(is, Q_prime_size_); detail::get(is, Q_size_); detail::get(is, d_);
+        get_header<S>(is);
         detail::get(is, st);
         detail::get(is, switch_key_generated_);
-        detail::get(is, switchkey_size_);
-        if (!is || switchkey_size_ > ((Data64) 1 << 36)) throw std::runtime_error("Invalid switchkey size!");
-        device_location_ = detail::read_payload(is, (size_t) switchkey_size_, "Switchkey");
+        detail::get(is, key_size_);
+        if (!is || key_size_ > ((Data64) 1 << 36)) throw std::runtime_error("Invalid switchkey size!");
+        buf_ = detail::read_payload(is, size(), "Switchkey");
         switch_key_generated_ = true;
     }
-    keyswitching_type key_type = keyswitching_type::KEYSWITCHING_METHOD_I;
     bool switch_key_generated_ = false;
 
   private:
     HEContext<S> context_;
-    int ring_size = 0, Q_prime_size_ = 0, Q_size_ = 0, d_ = 0;
-    Data64 switchkey_size_ = 0;
-    detail::StoredBuffer device_location_; // HBM or pinned host memory (storage manager)
 };
 
-template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration.cu:684-728
+template <Scheme S> class Galoiskey : public detail::KeySwitchShape { // host/*/evaluationkey.cuh; keygeneration.cu:684-728
   public:
     Galoiskey() = default;
     // power-of-two shifts in both directions (evaluationkey.cu:291-345, MAX_SHIFT = 8)
@@ -1307,31 +1308,28 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
         for (int i = 0; i < 8; i++) { v.push_back(1 << i); v.push_back(-(1 << i)); }
         return v;
     }
-    Galoiskey(HEContext<S> context, const std::vector<int>& shifts) : context_(std::move(context))
+    Galoiskey(HEContext<S> context, const std::vector<int>& shifts) : Galoiskey(std::move(context), false)
     {
-        init_sizes();
         for (int sh : shifts) galois_elt[sh] = hegpu_steps_to_galois_elt(sh, context_->n, group_order_);
     }
     // keys for explicit Galois elements (evaluationkey.cu:347-375)
-    Galoiskey(HEContext<S> context, const std::vector<uint32_t>& galois_elts) : context_(std::move(context))
+    Galoiskey(HEContext<S> context, const std::vector<uint32_t>& galois_elts) : Galoiskey(std::move(context), true)
     {
-        init_sizes();
-        customized = true;
         custom_galois_elt = galois_elts;
     }
-    size_t size() const { return (size_t) galoiskey_size_; }
     void load(int galois_element, const std::vector<Data64>& host, hipStream_t s = nullptr)
     {
-        if (host.size() != galoiskey_size_) throw std::invalid_argument("Invalid galoiskey size!");
+        if (host.size() != key_size_) throw std::invalid_argument("Invalid galoiskey size!");
         device_location_[galois_element] = DeviceVector<Data64>(host, s);
     }
     void set_context(HEContext<S> context) { context_ = std::move(context); }
+    // storage manager, every element
     bool is_on_device() const noexcept { for (const auto& k : device_location_) if (!k.second.is_on_device()) return false; return true; }
-    void store_in_device(hipStream_t s = nullptr) { for (auto& k : device_location_) k.second.store_in_device(s); } // storage manager, every element
-    void store_in_host(hipStream_t s = nullptr) { for (auto& k : device_location_) k.second.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { for (auto& k : device_location_) k.second.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { for (auto& k : device_location_) k.second.remove_from_device(s); }
-    void remove_from_host() { for (auto& k : device_location_) k.second.remove_from_host(); }
+    void store_in_device(hipStream_t s = nullptr) { each_key(&detail::StoredBuffer::store_in_device, s); }
+    void store_in_host(hipStream_t s = nullptr) { each_key(&detail::StoredBuffer::store_in_host, s); }
+    void copy_to_device(hipStream_t s = nullptr) { each_key(&detail::StoredBuffer::copy_to_device, s); }
+    void remove_from_device(hipStream_t s = nullptr) { each_key(&detail::StoredBuffer::remove_from_device, s); }
+    void remove_from_host() { each_key(&detail::StoredBuffer::remove_from_host); }
     // */evaluationkey.cu Galoiskey::save/load (bfv :540-760): header as Relinkey up to d, then
     // customized (bool), group order (int), storage (u8), generated (bool); the element table
     // (u32 list when customized, else (shift, element) int pairs); galois_elt_zero (int), key
@@ -1341,9 +1339,7 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
     void save(std::ostream& os) const
     {
         if (!galois_key_generated_) throw std::runtime_error("Galoiskey is not generated so can not be serialized!");
-        detail::put(os, detail::wire_scheme<S>());
-        detail::put(os, key_type);
-        detail::put(os, ring_size); detail::put(os, Q_prime_size_); detail::put(os, Q_size_); detail::put(os, d_);
+        put_header<S>(os);
         detail::put(os, customized);
         detail::put(os, group_order_);
         detail::put(os, storage_type::DEVICE);
@@ -1356,7 +1352,7 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
             for (const auto& g : galois_elt) { detail::put(os, g.first); detail::put(os, g.second); }
         }
         detail::put(os, galois_elt_zero);
-        detail::put(os, galoiskey_size_);
+        detail::put(os, key_size_);
         // a shift whose element equals galois_elt_zero cannot occur (the latter is 2N-1 / 2N-1)
         std::uint32_t key_count = 0;
         for (const auto& k : device_location_) if (k.first != galois_elt_zero) key_count++;
@@ -1364,21 +1360,17 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
         for (const auto& k : device_location_) {
             if (k.first == galois_elt_zero) continue;
             detail::put(os, k.first);
-            const std::vector<Data64> h = detail::to_host(k.second.data(), (size_t) galoiskey_size_);
-            os.write((const char*) h.data(), sizeof(Data64) * h.size());
+            detail::put_payload(os, k.second.data(), size());
         }
         const auto zero = device_location_.find(galois_elt_zero);
         if (zero == device_location_.end()) throw std::runtime_error("Galoiskey has no column-rotation key!");
-        const std::vector<Data64> h = detail::to_host(zero->second.data(), (size_t) galoiskey_size_);
-        os.write((const char*) h.data(), sizeof(Data64) * h.size());
+        detail::put_payload(os, zero->second.data(), size());
     }
     void load(std::istream& is)
     {
         if (galois_key_generated_) throw std::runtime_error("Galoiskey has been already exist!");
-        detail::check_scheme<S>(is);
         storage_type st;
-        detail::get(is, key_type);
-        detail::get(is, ring_size); detail::get(is, Q_prime_size_); detail::get(is, Q_size_); detail::get(is, d_);
+        get_header<S>(is);
         detail::get(is, customized);
         detail::get(is, group_order_);
         detail::get(is, st);
@@ -1399,17 +1391,17 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
             }
         }
         detail::get(is, galois_elt_zero);
-        detail::get(is, galoiskey_size_);
+        detail::get(is, key_size_);
         std::uint32_t key_count = 0;
         detail::get(is, key_count);
-        if (!is || galoiskey_size_ > ((Data64) 1 << 36) || key_count > (1u << 20)) throw std::runtime_error("Invalid galoiskey size!");
+        if (!is || key_size_ > ((Data64) 1 << 36) || key_count > (1u << 20)) throw std::runtime_error("Invalid galoiskey size!");
         device_location_.clear();
         for (std::uint32_t i = 0; i < key_count; i++) {
             int elt = 0;
             detail::get(is, elt);
-            device_location_[elt] = detail::read_payload(is, (size_t) galoiskey_size_, "Galoiskey");
+            device_location_[elt] = detail::read_payload(is, size(), "Galoiskey");
         }
-        device_location_[galois_elt_zero] = detail::read_payload(is, (size_t) galoiskey_size_, "Galoiskey");
+        device_location_[galois_elt_zero] = detail::read_payload(is, size(), "Galoiskey");
         galois_key_generated_ = true;
     }
     bool galois_key_generated_ = false;
@@ -1419,34 +1411,43 @@ template <Scheme S> class Galoiskey { // host/*/evaluationkey.cuh; keygeneration
     std::vector<std::uint32_t> custom_galois_elt;            // customized == true
     std::map<int, detail::StoredBuffer> device_location_;    // Galois element -> key (HBM or pinned host memory)
     int group_order_ = 5;
-    keyswitching_type key_type = keyswitching_type::KEYSWITCHING_METHOD_I;
 
   private:
-    void init_sizes()
+    Galoiskey(HEContext<S> context, bool custom)
+        : detail::KeySwitchShape(context), customized(custom), context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
         group_order_ = (S == Scheme::BFV) ? 3 : 5; // bfv/evaluationkey.cu:308, ckks/evaluationkey.cu:408
         galois_elt_zero = hegpu_steps_to_galois_elt(0, context_->n, group_order_); // column rotation / conjugation
-        const int m = (S == Scheme::BFV) ? 2 : context_->P_size;
-        ring_size = context_->n;
-        Q_prime_size_ = context_->Q_prime_size;
-        Q_size_ = context_->Q_size;
-        d_ = context_->P_size == 1 ? context_->Q_size : (context_->Q_size + m - 1) / m;
-        galoiskey_size_ = (Data64) 2 * d_ * Q_prime_size_ * ring_size;
-        key_type = context_->keyswitching_type_;
+    }
+    template <typename... A> void each_key(void (detail::StoredBuffer::*f)(A...), A... a)
+    {
+        for (auto& k : device_location_) (k.second.*f)(a...);
     }
     HEContext<S> context_;
-    int ring_size = 0, Q_prime_size_ = 0, Q_size_ = 0, d_ = 0;
-    Data64 galoiskey_size_ = 0;
 };
 
+namespace detail {
+// the device address of the key of a Galois element (a HOST-stored key is staged), null when the Galoiskey has none;
+// by shift: through the element the shift maps to, which is handed back as well
+template <Scheme S> const uint64_t* key_for(Galoiskey<S>& gk, int element)
+{
+    const auto it = gk.device_location_.find(element);
+    return it == gk.device_location_.end() ? nullptr : (const uint64_t*) it->second.data();
+}
+template <Scheme S> const uint64_t* key_for_shift(Galoiskey<S>& gk, int shift, int ring_size, int& element)
+{
+    element = hegpu_steps_to_galois_elt(shift, ring_size, gk.group_order_);
+    return key_for(gk, element);
+}
+} // namespace detail
+
 // ------------------------------------------------------------------ secret / public key, plaintext
-template <Scheme S> class Secretkey { // host/*/secretkey.cuh; [Q'][N], NTT domain
+template <Scheme S> class Secretkey : public detail::StoredObject { // host/*/secretkey.cuh; [Q'][N], NTT domain
   public:
     Secretkey() = default;
     explicit Secretkey(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         ring_size_ = context_->n;
         coeff_modulus_count_ = context_->Q_prime_size;
         n_power_ = context_->n_power;
@@ -1458,16 +1459,7 @@ template <Scheme S> class Secretkey { // host/*/secretkey.cuh; [Q'][N], NTT doma
             throw std::invalid_argument("hamming weight has to be in range 0 to ring size."); // secretkey.cu:43
         hamming_weight_ = hamming_weight;
     }
-    Data64* data() { return device_locations_.data(); }
-    const Data64* data() const { return device_locations_.data(); }
-    void memory_set(DeviceVector<Data64>&& m) { device_locations_ = std::move(m); }
     void set_context(HEContext<S> context) { context_ = std::move(context); }
-    bool is_on_device() const noexcept { return device_locations_.is_on_device(); } // storage manager, see Ciphertext
-    void store_in_device(hipStream_t s = nullptr) { device_locations_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_locations_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_locations_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_locations_.remove_from_device(s); }
-    void remove_from_host() { device_locations_.remove_from_host(); }
     inline int ring_size() const noexcept { return ring_size_; }
     inline int coeff_modulus_count() const noexcept { return coeff_modulus_count_; }
     // */secretkey.cu:235-345: scheme (u8), ring size, modulus count, n_power, hamming weight (int),
@@ -1484,8 +1476,7 @@ template <Scheme S> class Secretkey { // host/*/secretkey.cuh; [Q'][N], NTT doma
         detail::put(os, storage_type::DEVICE);
         const std::uint32_t count = (std::uint32_t) ((size_t) coeff_modulus_count_ * ring_size_);
         detail::put(os, count);
-        const std::vector<Data64> h = detail::to_host(device_locations_.data(), count);
-        os.write((const char*) h.data(), sizeof(Data64) * count);
+        detail::put_payload(os, buf_.data(), count);
     }
     void load(std::istream& is)
     {
@@ -1502,7 +1493,7 @@ template <Scheme S> class Secretkey { // host/*/secretkey.cuh; [Q'][N], NTT doma
         detail::get(is, count);
         if (!is || ring_size_ <= 0 || coeff_modulus_count_ <= 0 || count != (std::uint32_t) ((size_t) ring_size_ * coeff_modulus_count_))
             throw std::runtime_error("Invalid secretkey size!");
-        device_locations_ = detail::read_payload(is, count, "Secretkey");
+        buf_ = detail::read_payload(is, count, "Secretkey");
         secret_key_generated_ = true;
     }
     int hamming_weight_ = 0;
@@ -1511,28 +1502,18 @@ template <Scheme S> class Secretkey { // host/*/secretkey.cuh; [Q'][N], NTT doma
   private:
     HEContext<S> context_;
     int ring_size_ = 0, coeff_modulus_count_ = 0, n_power_ = 0;
-    detail::StoredBuffer device_locations_; // HBM or pinned host memory (storage manager)
 };
 
-template <Scheme S> class Publickey { // host/*/publickey.cuh; [2][Q'][N], NTT domain
+template <Scheme S> class Publickey : public detail::StoredObject { // host/*/publickey.cuh; [2][Q'][N], NTT domain
   public:
     Publickey() = default;
     explicit Publickey(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         ring_size_ = context_->n;
         coeff_modulus_count_ = context_->Q_prime_size;
     }
-    Data64* data() { return device_locations_.data(); }
-    const Data64* data() const { return device_locations_.data(); }
-    void memory_set(DeviceVector<Data64>&& m) { device_locations_ = std::move(m); }
     void set_context(HEContext<S> context) { context_ = std::move(context); }
-    bool is_on_device() const noexcept { return device_locations_.is_on_device(); } // storage manager, see Ciphertext
-    void store_in_device(hipStream_t s = nullptr) { device_locations_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_locations_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_locations_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_locations_.remove_from_device(s); }
-    void remove_from_host() { device_locations_.remove_from_host(); }
     inline int ring_size() const noexcept { return ring_size_; }
     inline int coeff_modulus_count() const noexcept { return coeff_modulus_count_; }
     // */publickey.cu:92-200: scheme (u8), ring size, modulus count (int), ntt flag, generated flag
@@ -1548,8 +1529,7 @@ template <Scheme S> class Publickey { // host/*/publickey.cuh; [2][Q'][N], NTT d
         detail::put(os, storage_type::DEVICE);
         const std::uint32_t count = (std::uint32_t) ((size_t) 2 * coeff_modulus_count_ * ring_size_);
         detail::put(os, count);
-        const std::vector<Data64> h = detail::to_host(device_locations_.data(), count);
-        os.write((const char*) h.data(), sizeof(Data64) * count);
+        detail::put_payload(os, buf_.data(), count);
     }
     void load(std::istream& is)
     {
@@ -1565,7 +1545,7 @@ template <Scheme S> class Publickey { // host/*/publickey.cuh; [2][Q'][N], NTT d
         detail::get(is, count);
         if (!is || ring_size_ <= 0 || coeff_modulus_count_ <= 0 || count != (std::uint32_t) ((size_t) 2 * ring_size_ * coeff_modulus_count_))
             throw std::runtime_error("Invalid publickey size!");
-        device_locations_ = detail::read_payload(is, count, "Publickey");
+        buf_ = detail::read_payload(is, count, "Publickey");
         public_key_generated_ = true;
     }
     bool public_key_generated_ = false;
@@ -1573,47 +1553,38 @@ template <Scheme S> class Publickey { // host/*/publickey.cuh; [2][Q'][N], NTT d
   private:
     HEContext<S> context_;
     int ring_size_ = 0, coeff_modulus_count_ = 0;
-    detail::StoredBuffer device_locations_; // HBM or pinned host memory (storage manager)
 };
 
-template <Scheme S> class Plaintext { // host/*/plaintext.cuh -- CKKS: [Q - depth][N] NTT domain (+ depth, scale); BFV: [N] mod t
+// host/*/plaintext.cuh -- CKKS: [Q - depth][N] NTT domain (+ depth, scale); BFV: [N] mod t
+template <Scheme S> class Plaintext : public detail::StoredObject {
   public:
     Plaintext() = default;
     explicit Plaintext(HEContext<S> context, const ExecutionOptions& options = ExecutionOptions())
         : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
-        device_locations_.set_stream(options.stream_);
+        detail::require_generated(context_);
+        buf_.set_stream(options.stream_);
     }
-    Data64* data() { return device_locations_.data(); }
-    const Data64* data() const { return device_locations_.data(); }
-    size_t size() const { return device_locations_.size(); }
-    void memory_set(DeviceVector<Data64>&& m) { device_locations_ = std::move(m); }
+    size_t size() const { return buf_.size(); }
     void set_context(HEContext<S> context) { context_ = std::move(context); }
     // residues produced elsewhere: [Q - depth][N] of the scaled message, NTT domain (CKKS) / [N] mod t (BFV)
     void load(const std::vector<Data64>& host, int depth, double scale, hipStream_t s = nullptr)
     {
         const size_t want = (S == Scheme::CKKS) ? (size_t) (context_->Q_size - depth) * context_->n : (size_t) context_->n;
         if (host.size() != want) throw std::invalid_argument("Invalid plaintext size!");
-        device_locations_ = DeviceVector<Data64>(host, s);
+        buf_ = DeviceVector<Data64>(host, s);
         depth_ = depth;
         scale_ = scale;
         plaintext_generated_ = true;
     }
-    void get_data(std::vector<Data64>& out, hipStream_t s = nullptr) const
-    {
-        out.resize(device_locations_.size());
-        detail::hip(hipMemcpyAsync(out.data(), device_locations_.data(), out.size() * sizeof(Data64),
-                                   hipMemcpyDeviceToHost, s));
-        detail::hip(hipStreamSynchronize(s));
-    }
+    void get_data(std::vector<Data64>& out, hipStream_t s = nullptr) const { download(out, s); }
     // */plaintext.cu (bfv :88-180, ckks :91-200): scheme (u8), size (int) [, depth (int), scale
     // (double)], ntt flag (bool) [, encoding (u8)], generated flag (bool), storage (u8), size again
     // (int), coefficients
     void save(std::ostream& os) const
     {
         if (!plaintext_generated_) throw std::runtime_error("Plaintext is not generated so can not be serialized!");
-        const int plain_size = (int) device_locations_.size();
+        const int plain_size = (int) buf_.size();
         const bool ntt = (S == Scheme::CKKS) || in_ntt_domain_;
         detail::put(os, detail::wire_scheme<S>());
         detail::put(os, plain_size);
@@ -1623,8 +1594,7 @@ template <Scheme S> class Plaintext { // host/*/plaintext.cuh -- CKKS: [Q - dept
         detail::put(os, plaintext_generated_);
         detail::put(os, storage_type::DEVICE);
         detail::put(os, plain_size);
-        const std::vector<Data64> h = detail::to_host(device_locations_.data(), (size_t) plain_size);
-        os.write((const char*) h.data(), sizeof(Data64) * h.size());
+        detail::put_payload(os, buf_.data(), (size_t) plain_size);
     }
     void load(std::istream& is)
     {
@@ -1642,15 +1612,9 @@ template <Scheme S> class Plaintext { // host/*/plaintext.cuh -- CKKS: [Q - dept
         detail::get(is, st);
         detail::get(is, again);
         if (!is || plain_size <= 0 || again != plain_size) throw std::runtime_error("Invalid plaintext size!");
-        device_locations_ = detail::read_payload(is, (size_t) plain_size, "Plaintext");
+        buf_ = detail::read_payload(is, (size_t) plain_size, "Plaintext");
         plaintext_generated_ = true;
     }
-    bool is_on_device() const noexcept { return device_locations_.is_on_device(); } // storage manager, see Ciphertext
-    void store_in_device(hipStream_t s = nullptr) { device_locations_.store_in_device(s); }
-    void store_in_host(hipStream_t s = nullptr) { device_locations_.store_in_host(s); }
-    void copy_to_device(hipStream_t s = nullptr) { device_locations_.copy_to_device(s); }
-    void remove_from_device(hipStream_t s = nullptr) { device_locations_.remove_from_device(s); }
-    void remove_from_host() { device_locations_.remove_from_host(); }
     inline int depth() const noexcept { return depth_; }
     inline double scale() const noexcept { return scale_; }
     inline encoding encoding_type() const noexcept { return encoding_; }
@@ -1662,7 +1626,6 @@ template <Scheme S> class Plaintext { // host/*/plaintext.cuh -- CKKS: [Q - dept
 
   private:
     HEContext<S> context_;
-    detail::StoredBuffer device_locations_; // HBM or pinned host memory (storage manager)
 };
 
 // ------------------------------------------------------------------ key generator / encryptor / decryptor
@@ -1674,13 +1637,13 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
     // 256 bits of operating-system entropy (getrandom) key the ChaCha20 DRBG
     explicit HEKeyGenerator(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         detail::check(hegpu_rng_create_from_entropy(&rng_));
     }
     // REPRODUCIBLE TESTS ONLY: a 64-bit seed can be searched exhaustively
     HEKeyGenerator(HEContext<S> context, std::uint64_t seed) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         detail::check(hegpu_rng_create(seed, &rng_));
     }
     ~HEKeyGenerator() { hegpu_rng_destroy(rng_); }
@@ -1692,9 +1655,9 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
         if (sk.secret_key_generated_) throw std::logic_error("Secretkey is already generated!");
         DeviceVector<Data64> out((size_t) context_->Q_prime_size * context_->n, o.stream_);
-        Workspace ws(context_, HEGPU_OP_KEYGEN_SECRET, o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_KEYGEN_SECRET, 0, o.stream_);
         detail::check(hegpu_generate_secret_key(context_->handle(), rng_, sk.hamming_weight_, (uint64_t*) out.data(),
-                                                ws.p(), ws.bytes(), o.stream_));
+                                                ws.data(), ws.bytes, o.stream_));
         sk.memory_set(std::move(out));
         sk.secret_key_generated_ = true;
     }
@@ -1704,9 +1667,9 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         if (pk.public_key_generated_) throw std::logic_error("Publickey is already generated!");
         DeviceVector<Data64> out((size_t) 2 * context_->Q_prime_size * context_->n, o.stream_);
-        Workspace ws(context_, HEGPU_OP_KEYGEN_PUBLIC, o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_KEYGEN_PUBLIC, 0, o.stream_);
         detail::check(hegpu_generate_public_key(context_->handle(), rng_, (const uint64_t*) sk.data(),
-                                                (uint64_t*) out.data(), ws.p(), ws.bytes(), o.stream_));
+                                                (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
         pk.memory_set(std::move(out));
         pk.public_key_generated_ = true;
     }
@@ -1716,9 +1679,9 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         if (rk.relin_key_generated_) throw std::logic_error("Relinkey is already generated!");
         DeviceVector<Data64> out(rk.size(), o.stream_);
-        Workspace ws(context_, HEGPU_OP_KEYGEN_SWITCH, o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_KEYGEN_SWITCH, 0, o.stream_);
         detail::check(hegpu_generate_relin_key(context_->handle(), rng_, (const uint64_t*) sk.data(),
-                                               (uint64_t*) out.data(), ws.p(), ws.bytes(), o.stream_));
+                                               (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
         rk.memory_set(std::move(out));
         rk.relin_key_generated_ = true;
     }
@@ -1731,10 +1694,10 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         if (!new_sk.secret_key_generated_) throw std::logic_error("Ner Secretkey is not generated!");
         if (swk.switch_key_generated_) throw std::logic_error("Switchkey is already generated!");
         DeviceVector<Data64> out(swk.size(), o.stream_);
-        Workspace ws(context_, HEGPU_OP_KEYGEN_SWITCH, o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_KEYGEN_SWITCH, 0, o.stream_);
         detail::check(hegpu_generate_switch_key(context_->handle(), rng_, (const uint64_t*) new_sk.data(),
-                                                (const uint64_t*) old_sk.data(), (uint64_t*) out.data(), ws.p(),
-                                                ws.bytes(), o.stream_));
+                                                (const uint64_t*) old_sk.data(), (uint64_t*) out.data(), ws.data(),
+                                                ws.bytes, o.stream_));
         swk.memory_set(std::move(out));
         swk.switch_key_generated_ = true;
     }
@@ -1743,37 +1706,22 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         if (gk.galois_key_generated_) throw std::logic_error("Galoiskey is already generated!");
-        Workspace ws(context_, HEGPU_OP_KEYGEN_SWITCH, o.stream_);
-        std::vector<int> elements;
+        detail::Workspace ws(context_->handle(), HEGPU_OP_KEYGEN_SWITCH, 0, o.stream_);
+        std::vector<int> elements; // in the key's own order, the "Columns Rotate" key last (keygenerator.cu:508-560)
         if (gk.customized) for (std::uint32_t e : gk.custom_galois_elt) elements.push_back((int) e);
         else for (auto& g : gk.galois_elt) elements.push_back(g.second);
+        elements.push_back(gk.galois_elt_zero);
         for (int elt : elements) {
             if (gk.device_location_.count(elt)) continue;
             DeviceVector<Data64> out(gk.size(), o.stream_);
             detail::check(hegpu_generate_galois_key(context_->handle(), rng_, (const uint64_t*) sk.data(), elt,
-                                                    (uint64_t*) out.data(), ws.p(), ws.bytes(), o.stream_));
+                                                    (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
             gk.device_location_[elt] = std::move(out);
-        }
-        if (!gk.device_location_.count(gk.galois_elt_zero)) { // "Columns Rotate" key (keygenerator.cu:508-560)
-            DeviceVector<Data64> out(gk.size(), o.stream_);
-            detail::check(hegpu_generate_galois_key(context_->handle(), rng_, (const uint64_t*) sk.data(),
-                                                    gk.galois_elt_zero, (uint64_t*) out.data(), ws.p(), ws.bytes(),
-                                                    o.stream_));
-            gk.device_location_[gk.galois_elt_zero] = std::move(out);
         }
         gk.galois_key_generated_ = true;
     }
 
   private:
-    struct Workspace {
-        Workspace(const HEContext<S>& c, int op, hipStream_t s)
-            : v((hegpu_workspace_bytes(c->handle(), op, 0, 1) + 7) / 8, s)
-        {
-        }
-        void* p() { return v.data(); }
-        size_t bytes() const { return v.size() * sizeof(Data64); }
-        DeviceVector<Data64> v;
-    };
     HEContext<S> context_;
     hegpu_rng* rng_ = nullptr;
 };
@@ -1782,14 +1730,14 @@ template <Scheme S> class HEEncryptor { // host/ckks/encryptor.cuh (public-key e
   public:
     HEEncryptor(HEContext<S> context, Publickey<S>& pk) : context_(std::move(context)), pk_(&pk)
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (!pk.public_key_generated_) throw std::logic_error("Publickey is not generated!");
         detail::check(hegpu_rng_create_from_entropy(&rng_));
     }
     // REPRODUCIBLE TESTS ONLY (64-bit seed)
     HEEncryptor(HEContext<S> context, Publickey<S>& pk, std::uint64_t seed) : context_(std::move(context)), pk_(&pk)
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (!pk.public_key_generated_) throw std::logic_error("Publickey is not generated!");
         detail::check(hegpu_rng_create(seed, &rng_));
     }
@@ -1803,15 +1751,10 @@ template <Scheme S> class HEEncryptor { // host/ckks/encryptor.cuh (public-key e
         if (!pt.plaintext_generated_ || pt.depth_ != 0) throw std::invalid_argument("Invalid plaintext size."); // encryptor.cuh:56
         DeviceVector<Data64> out((size_t) 2 * context_->Q_size * context_->n, o.stream_);
         const int opid = (S == Scheme::CKKS) ? HEGPU_OP_CKKS_ENCRYPT : HEGPU_OP_BFV_ENCRYPT;
-        DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), opid, 0, 1) + 7) / 8, o.stream_);
-        if (S == Scheme::CKKS)
-            detail::check(hegpu_ckks_encrypt(context_->handle(), rng_, (const uint64_t*) pk_->data(),
-                                             (const uint64_t*) pt.data(), (uint64_t*) out.data(), ws.data(),
-                                             ws.size() * sizeof(Data64), o.stream_));
-        else
-            detail::check(hegpu_bfv_encrypt(context_->handle(), rng_, (const uint64_t*) pk_->data(),
-                                            (const uint64_t*) pt.data(), (uint64_t*) out.data(), ws.data(),
-                                            ws.size() * sizeof(Data64), o.stream_));
+        detail::Workspace ws(context_->handle(), opid, 0, o.stream_);
+        detail::check((S == Scheme::CKKS ? hegpu_ckks_encrypt : hegpu_bfv_encrypt)(
+            context_->handle(), rng_, (const uint64_t*) pk_->data(), (const uint64_t*) pt.data(), (uint64_t*) out.data(),
+            ws.data(), ws.bytes, o.stream_));
         ct.adopt(std::move(out), 2, 0, pt.scale_);
         ct.encoding_ = pt.encoding_; // ckks/encryptor.cuh:84
     }
@@ -1826,7 +1769,7 @@ template <Scheme S> class HEDecryptor { // host/ckks/decryptor.cuh
   public:
     HEDecryptor(HEContext<S> context, Secretkey<S>& sk) : context_(std::move(context)), sk_(&sk)
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
     }
     void decrypt(Plaintext<S>& pt, Ciphertext<S>& ct, const ExecutionOptions& o = ExecutionOptions())
@@ -1840,11 +1783,10 @@ template <Scheme S> class HEDecryptor { // host/ckks/decryptor.cuh
                                              (const uint64_t*) sk_->data(), ct.depth(), (uint64_t*) out.data(),
                                              o.stream_));
         } else {
-            DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_BFV_DECRYPT, 0, 1) + 7) / 8,
-                                    o.stream_);
+            detail::Workspace ws(context_->handle(), HEGPU_OP_BFV_DECRYPT, 0, o.stream_);
             detail::check(hegpu_bfv_decrypt(context_->handle(), (const uint64_t*) ct.data(),
-                                            (const uint64_t*) sk_->data(), (uint64_t*) out.data(), ws.data(),
-                                            ws.size() * sizeof(Data64), o.stream_));
+                                            (const uint64_t*) sk_->data(), (uint64_t*) out.data(), ws.data(), ws.bytes,
+                                            o.stream_));
         }
         pt.memory_set(std::move(out));
         pt.depth_ = ct.depth();
@@ -1935,7 +1877,7 @@ template <> class HEEncoder<Scheme::BFV> { // host/bfv/encoder.cuh: batching ove
   public:
     explicit HEEncoder(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     inline int slot_count() const noexcept { return context_->n; }
 
@@ -2005,7 +1947,7 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
   public:
     explicit HEEncoder(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     inline int slot_count() const noexcept { return context_->n >> 1; }
 
@@ -2058,9 +2000,9 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
         const double* src = mapped ? message.data() : (const double*) msg.data();
         DeviceVector<Data64> out((size_t) context_->Q_size * context_->n, o.stream_);
         if (type == encoding::SLOT) {
-            DeviceVector<Data64> ws(ws_words(HEGPU_OP_CKKS_ENCODE, 0), o.stream_);
+            detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_ENCODE, 0, o.stream_);
             detail::check(hegpu_ckks_encode(context_->handle(), src, (int) message.size(), scale,
-                                            (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                            (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
         } else {
             detail::check(hegpu_ckks_encode_coeff(context_->handle(), src, (int) message.size(),
                                                   scale, (uint64_t*) out.data(), o.stream_));
@@ -2081,9 +2023,9 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
                                        hipMemcpyHostToDevice, o.stream_));
         const double* src = mapped ? (const double*) message.data() : (const double*) msg.data();
         DeviceVector<Data64> out((size_t) context_->Q_size * context_->n, o.stream_);
-        DeviceVector<Data64> ws(ws_words(HEGPU_OP_CKKS_ENCODE, 0), o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_ENCODE, 0, o.stream_);
         detail::check(hegpu_ckks_encode_complex(context_->handle(), src, (int) message.size(), scale,
-                                                (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                                (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
         finish(plain, std::move(out), scale, encoding::SLOT, o);
     }
 
@@ -2122,10 +2064,10 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
         const size_t count = coeff ? (size_t) context_->n : (size_t) slot_count();
         message.resize(count);
         DeviceVector<Data64> out(mapped ? 1 : count, o.stream_);
-        DeviceVector<Data64> ws(ws_words(HEGPU_OP_CKKS_DECODE, plain.depth_), o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_DECODE, plain.depth_, o.stream_);
         detail::check((coeff ? hegpu_ckks_decode_coeff : hegpu_ckks_decode)(
             context_->handle(), (const uint64_t*) plain.data(), plain.depth_, plain.scale_,
-            mapped ? message.data() : (double*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+            mapped ? message.data() : (double*) out.data(), ws.data(), ws.bytes, o.stream_));
         if (!mapped)
             detail::hip(hipMemcpyAsync(message.data(), out.data(), count * sizeof(double), hipMemcpyDeviceToHost, o.stream_));
         detail::hip(hipStreamSynchronize(o.stream_));
@@ -2138,10 +2080,10 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
             throw std::invalid_argument("Coefficient encoded CKKS plaintext can not be decoded to complex slots."); // :438
         message.resize(slot_count());
         DeviceVector<Data64> out(mapped ? 1 : (size_t) 2 * slot_count(), o.stream_);
-        DeviceVector<Data64> ws(ws_words(HEGPU_OP_CKKS_DECODE, plain.depth_), o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_DECODE, plain.depth_, o.stream_);
         detail::check(hegpu_ckks_decode_complex(context_->handle(), (const uint64_t*) plain.data(), plain.depth_,
                                                 plain.scale_, mapped ? (double*) message.data() : (double*) out.data(),
-                                                ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                                ws.data(), ws.bytes, o.stream_));
         if (!mapped)
             detail::hip(hipMemcpyAsync(message.data(), out.data(), message.size() * sizeof(Complex64), hipMemcpyDeviceToHost,
                                        o.stream_));
@@ -2154,7 +2096,6 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
         if (scale <= 0 || static_cast<int>(std::log2(scale)) >= context_->total_coeff_bit_count)
             throw std::invalid_argument("Scale out of bounds");
     }
-    size_t ws_words(int op, int depth) const { return (hegpu_workspace_bytes(context_->handle(), op, depth, 1) + 7) / 8; }
     void finish(Plaintext<S>& plain, DeviceVector<Data64>&& out, double scale, encoding type, const ExecutionOptions& o)
     {
         detail::hip(hipStreamSynchronize(o.stream_)); // the staging buffer of the message dies with the caller
@@ -2217,7 +2158,7 @@ template <> class LinearTransform<Scheme::CKKS> {
     template <typename T> void build(const std::map<int, std::vector<T>>& diagonals, HEEncoder<S>& encoder, double scale,
                                      int depth, int n1, const ExecutionOptions& o, int stride)
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (depth < 0 || depth >= context_->Q_size) throw std::invalid_argument("Invalid depth!");
         if (stride < 1) throw std::invalid_argument("The stride is at least 1!");
         const int slots = (int) (context_->n >> 1);
@@ -2343,10 +2284,12 @@ struct CKKSEncodingTransformContext {
 
 // ------------------------------------------------------------------ operator
 template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
+    friend class detail::LogicOperatorBase<S>; // emit, require_words
+
   public:
     explicit HEArithmeticOperator(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     // the reference's constructor takes the encoder (operator.cuh: used by its bootstrapping code only)
     HEArithmeticOperator(HEContext<S> context, HEEncoder<S>&) : HEArithmeticOperator(std::move(context)) {}
@@ -2368,8 +2311,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         DeviceVector<Data64> m((size_t) a.cipher_size_ * l * context_->n, o.stream_);
         detail::check(hegpu_addition(context_->handle(), (const uint64_t*) a.data(), nullptr, (uint64_t*) m.data(), l,
                                      a.cipher_size_, 1, 2, o.stream_));
-        copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
     }
 
     // host/ckks/operator.cuh:632-689, host/bfv/operator.cuh:348-391
@@ -2385,23 +2327,21 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (a.depth_ != b.depth_) throw std::logic_error("Ciphertexts leveled are not equal");
         const int l = limbs(a);
         const size_t n = context_->n;
-        if (a.memory_size() < 2 * n * l || b.memory_size() < 2 * n * l)
-            throw std::invalid_argument("Invalid Ciphertexts size!");
+        require_words(context_, a, 2);
+        require_words(context_, b, 2);
         DeviceVector<Data64> m(3 * n * l, o.stream_);
         if (S == Scheme::CKKS) {
             detail::check(hegpu_ckks_multiply(context_->handle(), (const uint64_t*) a.data(), 0,
                                               (const uint64_t*) b.data(), 0, (uint64_t*) m.data(), 0, a.depth_, 1,
                                               o.stream_));
         } else {
-            const size_t wsb = hegpu_workspace_bytes(context_->handle(), HEGPU_OP_BFV_MULTIPLY, 0, 1);
-            DeviceVector<Data64> ws(wsb / 8, o.stream_);
+            detail::Workspace ws(context_->handle(), HEGPU_OP_BFV_MULTIPLY, 0, o.stream_);
             detail::check(hegpu_bfv_multiply(context_->handle(), (const uint64_t*) a.data(), 0,
-                                             (const uint64_t*) b.data(), 0, (uint64_t*) m.data(), 0, 1, ws.data(), wsb,
-                                             o.stream_));
+                                             (const uint64_t*) b.data(), 0, (uint64_t*) m.data(), 0, 1, ws.data(),
+                                             ws.bytes, o.stream_));
         }
         const double sc = a.scale_ * b.scale_;
-        copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
         out.cipher_size_ = 3;
         out.scale_ = sc;
         out.relinearization_required_ = true;
@@ -2421,16 +2361,15 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             throw std::invalid_argument("Ciphertexts can not use relinearization, since no non-linear part!");
         const int l = limbs(a);
         const int op = (S == Scheme::CKKS) ? HEGPU_OP_CKKS_RELIN : HEGPU_OP_BFV_RELIN;
-        const size_t wsb = hegpu_workspace_bytes(context_->handle(), op, a.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        detail::Workspace ws(context_->handle(), op, a.depth_, o.stream_);
         if (S == Scheme::CKKS)
             detail::check(hegpu_ckks_relinearize_inplace(context_->handle(), (uint64_t*) a.data(),
                                                          (uint64_t) 3 * l * context_->n, (const uint64_t*) rk.data(),
-                                                         a.depth_, 1, ws.data(), wsb, o.stream_));
+                                                         a.depth_, 1, ws.data(), ws.bytes, o.stream_));
         else
             detail::check(hegpu_bfv_relinearize_inplace(context_->handle(), (uint64_t*) a.data(),
                                                         (uint64_t) 3 * l * context_->n, (const uint64_t*) rk.data(), 1,
-                                                        ws.data(), wsb, o.stream_));
+                                                        ws.data(), ws.bytes, o.stream_));
         a.relinearization_required_ = false;
         a.cipher_size_ = 2;
     }
@@ -2445,10 +2384,9 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                                         "or relinearization is required first!");
         const int l = limbs(a);
         if (l < 2) throw std::logic_error("Ciphertext modulus can not be reducible, since there is only one modulus");
-        const size_t wsb = hegpu_workspace_bytes(context_->handle(), HEGPU_OP_CKKS_RESCALE, a.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_RESCALE, a.depth_, o.stream_);
         detail::check(hegpu_ckks_rescale_inplace(context_->handle(), (uint64_t*) a.data(),
-                                                 (uint64_t) 2 * l * context_->n, a.depth_, 1, ws.data(), wsb,
+                                                 (uint64_t) 2 * l * context_->n, a.depth_, 1, ws.data(), ws.bytes,
                                                  o.stream_));
         a.scale_ = a.scale_ / (double) context_->prime_vector_[l - 1].value; // ckks/operator.cu:1235-1241
         a.depth_++;
@@ -2494,15 +2432,15 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
     {
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
         if (!swk.switch_key_generated_) throw std::logic_error("Switchkey is not generated!");
-        apply_key(in, out, swk.data(), 1, o);
+        apply_key(in, out, (const uint64_t*) swk.data(), 1, o);
     }
     void apply_galois(Ciphertext<S>& in, Ciphertext<S>& out, Galoiskey<S>& gk, int galois_elt,
                       const ExecutionOptions& o = ExecutionOptions())
     {
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
-        auto it = gk.device_location_.find(galois_elt);
-        if (it == gk.device_location_.end()) throw std::logic_error("Galois key not present!");
-        apply_key(in, out, it->second.data(), galois_elt, o);
+        const uint64_t* key = detail::key_for(gk, galois_elt);
+        if (!key) throw std::logic_error("Galois key not present!");
+        apply_key(in, out, key, galois_elt, o);
     }
 
     // host/ckks/operator.cuh:2133-2196 fast_single_hoisting_rotation_ckks (methods I and II by the key type):
@@ -2521,7 +2459,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             throw std::invalid_argument("Ciphertext can not be rotated!");
         const int l = limbs(input1);
         const size_t n = context_->n, words = 2 * n * l;
-        if (input1.memory_size() < words) throw std::invalid_argument("Invalid Ciphertexts size!");
+        require_words(context_, input1, 2);
         if (n1 < 1 || (size_t) n1 > bsgs_shift.size()) throw std::invalid_argument("Invalid rotation count!");
         DeviceVector<Data64> result(words * n1, stream);
         std::vector<const uint64_t*> keys(n1, nullptr);
@@ -2530,20 +2468,15 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             // the reference copies the input into entry 0 whatever bsgs_shift[0] is (method I, :4708) and treats
             // a zero shift as a copy (method II, :5138)
             if (i == 0 || bsgs_shift[i] == 0) continue;
-            const int g = hegpu_steps_to_galois_elt(bsgs_shift[i], (int) n, galois_key.group_order_);
-            auto it = galois_key.device_location_.find(g);
-            if (it != galois_key.device_location_.end()) {
-                elts[i] = g;
-                keys[i] = (const uint64_t*) it->second.data();
-            } else {
-                chained.push_back(i);
-            }
+            int g = 0;
+            keys[i] = detail::key_for_shift(galois_key, bsgs_shift[i], (int) n, g);
+            if (keys[i]) elts[i] = g;
+            else chained.push_back(i);
         }
-        const size_t wsb = hegpu_workspace_bytes(context_->handle(), HEGPU_OP_CKKS_ROTATE_HOISTED, input1.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, stream);
+        detail::Workspace ws(context_->handle(), HEGPU_OP_CKKS_ROTATE_HOISTED, input1.depth_, stream);
         detail::check(hegpu_ckks_rotate_hoisted(context_->handle(), (const uint64_t*) input1.data(), 0,
                                                 (uint64_t*) result.data(), 0, keys.data(), elts.data(), n1,
-                                                input1.depth_, 1, ws.data(), wsb, stream));
+                                                input1.depth_, 1, ws.data(), ws.bytes, stream));
         for (int i : chained) { // no key of its own: rotate_rows' chain of power-of-two keys
             Ciphertext<S> rot(input1);
             rotate_rows(input1, rot, galois_key, bsgs_shift[i], o);
@@ -2571,29 +2504,19 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (in.depth_ != lt.depth()) throw std::invalid_argument("Ciphertext and LinearTransform levels are not equal");
         const int l = limbs(in);
         const size_t n = context_->n;
-        if (in.memory_size() < 2 * n * l) throw std::invalid_argument("Invalid Ciphertexts size!");
+        require_words(context_, in, 2);
         const int n1 = lt.n1(), n2 = lt.n2();
-        std::vector<const uint64_t*> keys(n1 + n2, nullptr);
-        std::vector<int> elts(n1 + n2, 0);
-        for (int k = 0; k < n1 + n2; k++) {
-            const int shift = k < n1 ? lt.baby_shifts()[k] : lt.giant_shifts()[k - n1];
-            if (shift == 0) continue;
-            elts[k] = hegpu_steps_to_galois_elt(shift, (int) n, galois_key.group_order_);
-            auto it = galois_key.device_location_.find(elts[k]);
-            if (it == galois_key.device_location_.end())
-                throw std::invalid_argument("Galois key not present! (build the Galoiskey from required_shifts())");
-            keys[k] = (const uint64_t*) it->second.data();
-        }
-        const size_t wsb = hegpu_ckks_linear_transform_workspace_bytes(context_->handle(), n1, n2, in.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        std::vector<const uint64_t*> keys;
+        std::vector<int> elts;
+        keys_of(lt, galois_key, keys, elts, "Galois key not present! (build the Galoiskey from required_shifts())");
+        detail::Workspace ws(hegpu_ckks_linear_transform_workspace_bytes(context_->handle(), n1, n2, in.depth_, 1), o.stream_);
         DeviceVector<Data64> m(2 * n * l, o.stream_);
         detail::check(hegpu_ckks_linear_transform(context_->handle(), (const uint64_t*) in.data(), 0, (uint64_t*) m.data(), 0,
                                                   (const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1,
                                                   n2, keys.data(), elts.data(), keys.data() + n1, elts.data() + n1,
-                                                  in.depth_, 1, ws.data(), wsb, o.stream_));
+                                                  in.depth_, 1, ws.data(), ws.bytes, o.stream_));
         const double sc = in.scale_ * lt.scale();
-        if (&in != &out) copy_meta(in, out);
-        out.memory_set(std::move(m));
+        emit(in, out, std::move(m));
         out.scale_ = sc;
         out.rescale_required_ = true;
     }
@@ -2678,18 +2601,20 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         const int P = tc.CtoS_piece_, out_depth = cipher.depth_ + P + 1;
         if (out_depth >= context_->Q_size) throw std::logic_error("coeff_to_slot: no modulus left for the results");
         const size_t n = context_->n, words = 2 * n * (size_t) (context_->Q_size - out_depth);
-        const size_t wsb = hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_), m0(words, o.stream_), m1(words, o.stream_);
+        detail::Workspace ws(hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher.depth_, 1),
+                             o.stream_);
+        DeviceVector<Data64> m0(words, o.stream_), m1(words, o.stream_);
+        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
+        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
         detail::check(hegpu_ckks_coeff_to_slot(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m0.data(),
-                                               (uint64_t*) m1.data(), 0, fa.f.data(), P, conj_key(galois_key), cipher.depth_,
-                                               1, ws.data(), wsb, o.stream_));
+                                               (uint64_t*) m1.data(), 0, fa.f.data(), P, conj, cipher.depth_, 1, ws.data(),
+                                               ws.bytes, o.stream_));
         double sc = cipher.scale_; // every factor multiplies by its scale and the rescale divides by the modulus it drops
         for (int k = 0; k < P; k++)
             sc = sc * tc.CtoS_factors_[k]->scale() / (double) context_->prime_vector_[limbs(cipher) - 1 - k].value;
         std::vector<Ciphertext<S>> result(2, Ciphertext<S>(context_));
         for (int r = 0; r < 2; r++) {
-            copy_meta(cipher, result[r]);
-            result[r].memory_set(std::move(r ? m1 : m0));
+            emit(cipher, result[r], std::move(r ? m1 : m0));
             result[r].depth_ = out_depth;
             result[r].scale_ = sc;
             result[r].encoding_ = encoding::SLOT;
@@ -2717,18 +2642,17 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         const int P = tc.StoC_piece_, out_depth = cipher0.depth_ + 1 + P;
         if (out_depth >= context_->Q_size) throw std::logic_error("slot_to_coeff: no modulus left for the result");
         const size_t n = context_->n;
-        const size_t wsb = hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher0.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        detail::Workspace ws(hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher0.depth_, 1),
+                             o.stream_);
         DeviceVector<Data64> m(2 * n * (size_t) (context_->Q_size - out_depth + 1), o.stream_); // rescaled in place at the end
         detail::check(hegpu_ckks_slot_to_coeff(context_->handle(), (const uint64_t*) cipher0.data(), 0,
                                                (const uint64_t*) cipher1.data(), 0, (uint64_t*) m.data(), 0, fa.f.data(), P,
-                                               cipher0.depth_, 1, ws.data(), wsb, o.stream_));
+                                               cipher0.depth_, 1, ws.data(), ws.bytes, o.stream_));
         double sc = cipher0.scale_;
         for (int k = 0; k < P; k++)
             sc = sc * tc.StoC_factors_[k]->scale() / (double) context_->prime_vector_[limbs(cipher0) - 2 - k].value;
         Ciphertext<S> result(context_);
-        copy_meta(cipher0, result);
-        result.memory_set(std::move(m));
+        emit(cipher0, result, std::move(m));
         result.depth_ = out_depth;
         result.scale_ = sc;
         result.encoding_ = encoding::COEFFICIENT;
@@ -2747,12 +2671,8 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
         check_plain_two_part(cipher);
         if (!cipher.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
-        {
-            const int Q = context_->Q_size, Qp = context_->Q_prime_size, P = context_->P_size;
-            const size_t d = P == 1 ? (size_t) Q : (size_t) (Q + P - 1) / P;
-            if (!relin_key.relin_key_generated_ || relin_key.size() != 2 * d * (size_t) Qp * context_->n)
-                throw std::invalid_argument("Relinkey does not belong to this context!");
-        }
+        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
+            throw std::invalid_argument("Relinkey does not belong to this context!");
         const int Q = context_->Q_size, level = Q - 1 - cipher.depth_;
         std::vector<uint64_t> primes((size_t) Q);
         for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
@@ -2766,14 +2686,14 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                                                 cipher.scale_, target_scale, primes.data(), Q, plan.data(), n_steps));
         const hegpu_poly_step& last = plan.back();
         const size_t n = context_->n;
-        const size_t wsb = hegpu_ckks_poly_eval_workspace_bytes(context_->handle(), plan.data(), n_steps, cipher.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_), m(2 * n * (size_t) (last.level + 1 + last.rescale_after), o.stream_);
+        detail::Workspace ws(hegpu_ckks_poly_eval_workspace_bytes(context_->handle(), plan.data(), n_steps, cipher.depth_, 1),
+                             o.stream_);
+        DeviceVector<Data64> m(2 * n * (size_t) (last.level + 1 + last.rescale_after), o.stream_);
         detail::check(hegpu_ckks_poly_eval(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m.data(), 0,
                                            plan.data(), n_steps, (const uint64_t*) relin_key.data(), cipher.depth_, 1,
-                                           ws.data(), wsb, o.stream_));
+                                           ws.data(), ws.bytes, o.stream_));
         Ciphertext<S> result(context_);
-        copy_meta(cipher, result);
-        result.memory_set(std::move(m));
+        emit(cipher, result, std::move(m));
         result.depth_ = Q - 1 - last.level;
         result.scale_ = last.scale;
         result.rescale_required_ = false;
@@ -2787,13 +2707,22 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (a.relinearization_required_ || a.cipher_size_ != 2)
             throw std::invalid_argument("Ciphertext should be relinearized first!");
         if (a.rescale_required_) throw std::invalid_argument("Ciphertext should be rescaled first!");
-        if (a.memory_size() < 2 * context_->n * (size_t) limbs(a)) throw std::invalid_argument("Invalid Ciphertexts size!");
+        require_words(context_, a, 2);
     }
-    const uint64_t* conj_key(Galoiskey<S>& gk) const
+    // the keys and Galois elements of a LinearTransform's baby steps, then its giant steps (a zero shift takes none); a
+    // power-of-two chain would silently multiply the key switches, so a missing key is std::invalid_argument(`hint`)
+    void keys_of(const LinearTransform<S>& lt, Galoiskey<S>& gk, std::vector<const uint64_t*>& keys, std::vector<int>& elts,
+                 const char* hint) const
     {
-        auto it = gk.device_location_.find(gk.galois_elt_zero);
-        if (it == gk.device_location_.end()) throw std::invalid_argument("Galois key not present! (conjugation)");
-        return (const uint64_t*) it->second.data();
+        const int n1 = lt.n1(), n2 = lt.n2();
+        keys.assign(n1 + n2, nullptr);
+        elts.assign(n1 + n2, 0);
+        for (int i = 0; i < n1 + n2; i++) {
+            const int shift = i < n1 ? lt.baby_shifts()[i] : lt.giant_shifts()[i - n1];
+            if (shift == 0) continue;
+            keys[i] = detail::key_for_shift(gk, shift, (int) context_->n, elts[i]);
+            if (!keys[i]) throw std::invalid_argument(hint);
+        }
     }
     // the hegpu_linear_factor array of a chain of LinearTransform objects, with the key and element tables it points into
     struct FactorArgs {
@@ -2806,47 +2735,33 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             for (size_t k = 0; k < lts.size(); k++) {
                 const LinearTransform<S>& lt = *lts[k];
                 const int n1 = lt.n1(), n2 = lt.n2();
-                keys[k].assign(n1 + n2, nullptr);
-                elts[k].assign(n1 + n2, 0);
-                for (int i = 0; i < n1 + n2; i++) {
-                    const int shift = i < n1 ? lt.baby_shifts()[i] : lt.giant_shifts()[i - n1];
-                    if (shift == 0) continue;
-                    elts[k][i] = hegpu_steps_to_galois_elt(shift, (int) op.context_->n, gk.group_order_);
-                    auto it = gk.device_location_.find(elts[k][i]);
-                    if (it == gk.device_location_.end())
-                        throw std::invalid_argument("Galois key not present! (build the Galoiskey from key_indexs_)");
-                    keys[k][i] = (const uint64_t*) it->second.data();
-                }
+                op.keys_of(lt, gk, keys[k], elts[k], "Galois key not present! (build the Galoiskey from key_indexs_)");
                 f[k] = hegpu_linear_factor{(const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1, n2,
                                            keys[k].data(), elts[k].data(), keys[k].data() + n1, elts[k].data() + n1};
             }
         }
     };
-    void apply_key(Ciphertext<S>& in, Ciphertext<S>& out, const Data64* key, int galois_elt, const ExecutionOptions& o)
+    void apply_key(Ciphertext<S>& in, Ciphertext<S>& out, const uint64_t* key, int galois_elt, const ExecutionOptions& o)
     {
         if (in.relinearization_required_) throw std::invalid_argument("Ciphertext should be relinearized first!");
         const int l = limbs(in);
         const size_t n = context_->n;
         DeviceVector<Data64> m(2 * n * l, o.stream_);
         const int op = (S == Scheme::CKKS) ? HEGPU_OP_CKKS_GALOIS : HEGPU_OP_BFV_GALOIS;
-        const size_t wsb = hegpu_workspace_bytes(context_->handle(), op, in.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        detail::Workspace ws(context_->handle(), op, in.depth_, o.stream_);
         if (S == Scheme::CKKS)
-            detail::check(hegpu_ckks_apply_galois(context_->handle(), (const uint64_t*) in.data(), 0,
-                                                  (uint64_t*) m.data(), 0, (const uint64_t*) key, galois_elt,
-                                                  in.depth_, 1, ws.data(), wsb, o.stream_));
+            detail::check(hegpu_ckks_apply_galois(context_->handle(), (const uint64_t*) in.data(), 0, (uint64_t*) m.data(), 0,
+                                                  key, galois_elt, in.depth_, 1, ws.data(), ws.bytes, o.stream_));
         else
-            detail::check(hegpu_bfv_apply_galois(context_->handle(), (const uint64_t*) in.data(), 0,
-                                                 (uint64_t*) m.data(), 0, (const uint64_t*) key, galois_elt, 1,
-                                                 ws.data(), wsb, o.stream_));
-        if (&in != &out) copy_meta(in, out);
-        out.memory_set(std::move(m));
+            detail::check(hegpu_bfv_apply_galois(context_->handle(), (const uint64_t*) in.data(), 0, (uint64_t*) m.data(), 0,
+                                                 key, galois_elt, 1, ws.data(), ws.bytes, o.stream_));
+        emit(in, out, std::move(m));
     }
 
   public:
-
-    void add_inplace(Ciphertext<S>& a, Ciphertext<S>& b, const ExecutionOptions& o = ExecutionOptions()) { binary(a, b, a, 0, o); }
-    void sub_inplace(Ciphertext<S>& a, Ciphertext<S>& b, const ExecutionOptions& o = ExecutionOptions()) { binary(a, b, a, 1, o); }
+    // the in-place forms go through the out-of-place operators, so each of them runs inside a storage scope
+    void add_inplace(Ciphertext<S>& a, Ciphertext<S>& b, const ExecutionOptions& o = ExecutionOptions()) { add(a, b, a, o); }
+    void sub_inplace(Ciphertext<S>& a, Ciphertext<S>& b, const ExecutionOptions& o = ExecutionOptions()) { sub(a, b, a, o); }
     void negate_inplace(Ciphertext<S>& a, const ExecutionOptions& o = ExecutionOptions()) { negate(a, a, o); }
     // CKKS: drop the last limb without dividing (ckks/operator.cuh mod_drop*)
     void mod_drop(Ciphertext<S>& a, Ciphertext<S>& out, const ExecutionOptions& o = ExecutionOptions())
@@ -2861,8 +2776,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             detail::hip(hipMemcpyAsync(m.data() + (size_t) p * (l - 1) * n, a.data() + (size_t) p * l * n,
                                        (size_t) (l - 1) * n * sizeof(Data64), hipMemcpyDeviceToDevice, o.stream_));
         const int depth = a.depth_ + 1;
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
         out.depth_ = depth;
     }
     void mod_drop_inplace(Ciphertext<S>& a, const ExecutionOptions& o = ExecutionOptions()) { mod_drop(a, a, o); }
@@ -2920,15 +2834,13 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                                                            (const uint64_t*) p.data(), (uint64_t*) m.data(), l,
                                                            o.stream_));
         } else {
-            const size_t wsb = hegpu_workspace_bytes(context_->handle(), HEGPU_OP_BFV_MULTIPLY_PLAIN, 0, 1);
-            DeviceVector<Data64> ws(wsb / 8, o.stream_);
+            detail::Workspace ws(context_->handle(), HEGPU_OP_BFV_MULTIPLY_PLAIN, 0, o.stream_);
             detail::check(hegpu_bfv_multiply_plain(context_->handle(), (const uint64_t*) a.data(),
-                                                   (const uint64_t*) p.data(), (uint64_t*) m.data(), ws.data(), wsb,
+                                                   (const uint64_t*) p.data(), (uint64_t*) m.data(), ws.data(), ws.bytes,
                                                    o.stream_));
         }
         const double ps = p.scale_;
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
         if (S == Scheme::CKKS) {
             out.scale_ = a.scale_ * ps; // ckks/operator.cuh multiply_plain
             out.rescale_required_ = true;
@@ -2980,8 +2892,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         DeviceVector<Data64> m((size_t) 2 * context_->Q_size * context_->n, o.stream_);
         detail::check(hegpu_negacyclic_shift(context_->handle(), (const uint64_t*) a.data(), (uint64_t*) m.data(), index,
                                              context_->Q_size, 2, o.stream_));
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
     }
 
     // ---- CKKS: one real constant in every slot (ckks/operator.cuh:312-390, :507-585, :812-925), +-i, conjugation
@@ -3084,7 +2995,19 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         out.in_ntt_domain_ = a.in_ntt_domain_;
         out.rescale_required_ = a.rescale_required_;
         out.relinearization_required_ = a.relinearization_required_;
+    }
+    // the tail of an operator: `out` describes itself like `in` and owns the fresh residues; what the operator changes
+    // (depth, scale, flags) it sets afterwards
+    static void emit(const Ciphertext<S>& in, Ciphertext<S>& out, DeviceVector<Data64>&& m)
+    {
+        if (&in != &out) copy_meta(in, out);
+        out.memory_set(std::move(m));
         out.ciphertext_generated_ = true;
+    }
+    // `parts` polynomials at the ciphertext's own level have to be there before a kernel reads them
+    static void require_words(const HEContext<S>& c, const Ciphertext<S>& ct, int parts)
+    {
+        if (ct.memory_size() < (size_t) parts * (c->Q_size - ct.depth_) * c->n) throw std::invalid_argument("Invalid Ciphertexts size!");
     }
     void binary(Ciphertext<S>& a, Ciphertext<S>& b, Ciphertext<S>& out, int op, const ExecutionOptions& o)
     {
@@ -3094,8 +3017,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         DeviceVector<Data64> m((size_t) a.cipher_size_ * l * context_->n, o.stream_);
         detail::check(hegpu_addition(context_->handle(), (const uint64_t*) a.data(), (const uint64_t*) b.data(),
                                      (uint64_t*) m.data(), l, a.cipher_size_, 1, op, o.stream_));
-        copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
     }
     void change_domain(Ciphertext<S>& a, Ciphertext<S>& out, bool inverse, const ExecutionOptions& o)
     {
@@ -3105,42 +3027,36 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         DeviceVector<Data64> m((size_t) 2 * Q * context_->n, o.stream_);
         detail::check(hegpu_ntt(context_->handle(), HEGPU_TABLES_QP, (const uint64_t*) a.data(), (uint64_t*) m.data(),
                                 inverse ? 1 : 0, 2 * Q, Q, 0, nullptr, nullptr, o.stream_));
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
         out.in_ntt_domain_ = !inverse;
+    }
+    // out = call(a) on every polynomial a CKKS ciphertext has (three before relinearization): constants, +-i
+    template <typename Call> void elementwise(Ciphertext<S>& a, Ciphertext<S>& out, const ExecutionOptions& o, Call call)
+    {
+        static_assert(S == Scheme::CKKS, "constants and mult_i / div_i are CKKS operations");
+        const int l = limbs(a), parts = a.relinearization_required_ ? 3 : 2;
+        require_words(context_, a, parts);
+        DeviceVector<Data64> m((size_t) parts * l * context_->n, o.stream_);
+        detail::check(call((const uint64_t*) a.data(), (uint64_t*) m.data(), l, parts));
+        emit(a, out, std::move(m));
     }
     void constant_op(int op, Ciphertext<S>& a, double value, Ciphertext<S>& out, const ExecutionOptions& o)
     {
-        static_assert(S == Scheme::CKKS, "constants are CKKS operations");
-        const int l = limbs(a), parts = a.relinearization_required_ ? 3 : 2;
-        if (a.memory_size() < (size_t) parts * l * context_->n) throw std::invalid_argument("Invalid Ciphertexts size!");
-        DeviceVector<Data64> m((size_t) parts * l * context_->n, o.stream_);
-        detail::check(hegpu_ckks_constant_op(context_->handle(), op, (const uint64_t*) a.data(), value,
-                                             (uint64_t*) m.data(), l, parts, o.stream_));
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        elementwise(a, out, o, [&](const uint64_t* in, uint64_t* m, int l, int parts) {
+            return hegpu_ckks_constant_op(context_->handle(), op, in, value, m, l, parts, o.stream_);
+        });
     }
     void gaussian(Ciphertext<S>& a, Ciphertext<S>& out, int op, double re, double im, const ExecutionOptions& o)
     {
-        static_assert(S == Scheme::CKKS, "complex constants are a CKKS operation");
-        const int l = limbs(a), parts = a.relinearization_required_ ? 3 : 2;
-        if (a.memory_size() < (size_t) parts * l * context_->n) throw std::invalid_argument("Invalid Ciphertexts size!");
-        DeviceVector<Data64> m((size_t) parts * l * context_->n, o.stream_);
-        detail::check(hegpu_ckks_gaussian_integer_op(context_->handle(), op, (const uint64_t*) a.data(), re, im,
-                                                     (uint64_t*) m.data(), l, parts, o.stream_));
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        elementwise(a, out, o, [&](const uint64_t* in, uint64_t* m, int l, int parts) {
+            return hegpu_ckks_gaussian_integer_op(context_->handle(), op, in, re, im, m, l, parts, o.stream_);
+        });
     }
     void times_i(Ciphertext<S>& a, Ciphertext<S>& out, int divide, const ExecutionOptions& o)
     {
-        static_assert(S == Scheme::CKKS, "mult_i / div_i are CKKS operations");
-        const int l = limbs(a), parts = a.relinearization_required_ ? 3 : 2;
-        if (a.memory_size() < (size_t) parts * l * context_->n) throw std::invalid_argument("Invalid Ciphertexts size!");
-        DeviceVector<Data64> m((size_t) parts * l * context_->n, o.stream_);
-        detail::check(hegpu_ckks_mult_i(context_->handle(), (const uint64_t*) a.data(), (uint64_t*) m.data(), l, parts,
-                                        divide, o.stream_));
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        elementwise(a, out, o, [&](const uint64_t* in, uint64_t* m, int l, int parts) {
+            return hegpu_ckks_mult_i(context_->handle(), in, m, l, parts, divide, o.stream_);
+        });
     }
     void plain_addsub(Ciphertext<S>& a, Plaintext<S>& p, Ciphertext<S>& out, int sub, const ExecutionOptions& o)
     {
@@ -3159,8 +3075,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             detail::check(hegpu_bfv_plain_addsub(context_->handle(), (const uint64_t*) a.data(),
                                                  (const uint64_t*) p.data(), (uint64_t*) m.data(), sub, o.stream_));
         }
-        if (&a != &out) copy_meta(a, out);
-        out.memory_set(std::move(m));
+        emit(a, out, std::move(m));
     }
     HEContext<S> context_;
 };
@@ -3270,9 +3185,10 @@ template <Scheme S> class MultiPartyManagerBase {
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         if (pk.public_key_generated_) throw std::logic_error("Publickey is already generated!");
         Crs crs(pk.seed(), "pk");
-        DeviceVector<Data64> out((size_t) 2 * context_->Q_prime_size * context_->n, o.stream_), ws = key_ws(o);
+        DeviceVector<Data64> out((size_t) 2 * context_->Q_prime_size * context_->n, o.stream_);
+        Workspace ws(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, o.stream_);
         check(hegpu_mpc_public_key_share(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(), (uint64_t*) out.data(),
-                                         ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                         ws.data(), ws.bytes, o.stream_));
         pk.memory_set(std::move(out));
         pk.public_key_generated_ = true;
     }
@@ -3301,10 +3217,11 @@ template <Scheme S> class MultiPartyManagerBase {
         if (rk.relin_key_generated_) throw std::logic_error("Relinkey is already generated!");
         Crs crs(rk.seed(), "rk");
         u_ = DeviceVector<Data64>((size_t) context_->Q_prime_size * context_->n, o.stream_);
-        DeviceVector<Data64> out(rk.size(), o.stream_), ws = key_ws(o);
+        DeviceVector<Data64> out(rk.size(), o.stream_);
+        Workspace ws(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, o.stream_);
         check(hegpu_mpc_relin_key_share_round1(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(),
-                                               (uint64_t*) u_.data(), (uint64_t*) out.data(), ws.data(),
-                                               ws.size() * sizeof(Data64), o.stream_));
+                                               (uint64_t*) u_.data(), (uint64_t*) out.data(), ws.data(), ws.bytes,
+                                               o.stream_));
         rk.memory_set(std::move(out));
         rk.relin_key_generated_ = true;
     }
@@ -3328,10 +3245,11 @@ template <Scheme S> class MultiPartyManagerBase {
         if (!rk_s1_common.relin_key_generated_) throw std::logic_error("Common Relinkey is not generated!");
         if (rk_new.relin_key_generated_) throw std::logic_error("Relinkey is already generated!");
         if (!u_.size()) throw std::logic_error("generate_relin_key_init has to run first!");
-        DeviceVector<Data64> out(rk_new.size(), o.stream_), ws = key_ws(o);
+        DeviceVector<Data64> out(rk_new.size(), o.stream_);
+        Workspace ws(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, o.stream_);
         check(hegpu_mpc_relin_key_share_round2(context_->handle(), rng_, (const uint64_t*) sk.data(),
                                                (const uint64_t*) u_.data(), (const uint64_t*) rk_s1_common.data(),
-                                               (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                               (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
         rk_new.memory_set(std::move(out));
         rk_new.relin_key_generated_ = true;
     }
@@ -3352,12 +3270,12 @@ template <Scheme S> class MultiPartyManagerBase {
         OpScope storage_scope(o);
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         if (gk.galois_key_generated_) throw std::logic_error("Galoiskey is already generated!");
-        DeviceVector<Data64> ws = key_ws(o);
+        Workspace ws(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, o.stream_);
         for (int elt : elements(gk)) {
             Crs crs(gk.seed(), "gk" + std::to_string(elt));
             DeviceVector<Data64> out(gk.size(), o.stream_);
             check(hegpu_mpc_galois_key_share(context_->handle(), crs.r, rng_, (const uint64_t*) sk.data(), elt,
-                                             (uint64_t*) out.data(), ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                             (uint64_t*) out.data(), ws.data(), ws.bytes, o.stream_));
             gk.device_location_[elt] = std::move(out);
         }
         gk.galois_key_generated_ = true;
@@ -3373,9 +3291,8 @@ template <Scheme S> class MultiPartyManagerBase {
         for (int elt : elements(gk)) {
             std::vector<const uint64_t*> shares;
             for (auto& g : all_gk) {
-                const auto it = g.device_location_.find(elt);
-                if (it == g.device_location_.end()) throw std::invalid_argument("MultipartyGaloiskey lacks an element!");
-                shares.push_back((const uint64_t*) it->second.data());
+                shares.push_back(key_for(g, elt));
+                if (!shares.back()) throw std::invalid_argument("MultipartyGaloiskey lacks an element!");
             }
             DeviceVector<Data64> out(gk.size(), o.stream_);
             check(hegpu_mpc_accumulate(context_->handle(), shares.data(), (int) shares.size(), HEGPU_MPC_GALOIS_KEY,
@@ -3424,10 +3341,9 @@ template <Scheme S> class MultiPartyManagerBase {
             check(hegpu_mpc_ckks_decrypt_merge(context_->handle(), c0, 2 * half, shares.data(), (int) shares.size(), depth,
                                                (uint64_t*) out.data(), 1, o.stream_));
         } else {
-            DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_BFV_DECRYPT_MERGE, 0, 1) + 7) / 8,
-                                    o.stream_);
+            Workspace ws(context_->handle(), HEGPU_OP_MPC_BFV_DECRYPT_MERGE, 0, o.stream_);
             check(hegpu_mpc_bfv_decrypt_merge(context_->handle(), c0, 2 * half, shares.data(), (int) shares.size(),
-                                              (uint64_t*) out.data(), 1, ws.data(), ws.size() * sizeof(Data64), o.stream_));
+                                              (uint64_t*) out.data(), 1, ws.data(), ws.bytes, o.stream_));
         }
         plaintext.memory_set(std::move(out));
         plaintext.depth_ = depth;
@@ -3479,15 +3395,13 @@ template <Scheme S> class MultiPartyManagerBase {
         }
         Crs crs(seed, "boot");
         DeviceVector<Data64> out((size_t) 2 * Q * n, o.stream_);
-        DeviceVector<Data64> ws((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_REFRESH_MERGE, depth, 1) + 7) / 8, o.stream_);
+        Workspace ws(context_->handle(), HEGPU_OP_MPC_REFRESH_MERGE, depth, o.stream_);
         if (S == Scheme::CKKS)
             check(hegpu_mpc_ckks_refresh_merge(context_->handle(), crs.r, ct, 2 * l * n, shares.data(), (int) shares.size(), depth,
-                                               (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.size() * sizeof(Data64),
-                                               o.stream_));
+                                               (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.bytes, o.stream_));
         else
             check(hegpu_mpc_bfv_refresh_merge(context_->handle(), crs.r, ct, 2 * l * n, shares.data(), (int) shares.size(),
-                                              (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.size() * sizeof(Data64),
-                                              o.stream_));
+                                              (uint64_t*) out.data(), 2 * Q * n, 1, ws.data(), ws.bytes, o.stream_));
         const double scale = common.scale();
         const auto encoding = common.encoding_;
         output.adopt(std::move(out), 2, 0, scale);
@@ -3497,7 +3411,7 @@ template <Scheme S> class MultiPartyManagerBase {
   protected:
     explicit MultiPartyManagerBase(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         check(hegpu_rng_create_from_entropy(&rng_)); // the party's private generator
     }
 
@@ -3528,10 +3442,6 @@ template <Scheme S> class MultiPartyManagerBase {
         int bits = -(l - 1);
         for (int i = 0; i < l; i++) bits += (int) context_->prime_vector_[i].bit;
         return bits - 8 > 126 ? 126 : bits - 8;
-    }
-    DeviceVector<Data64> key_ws(const ExecutionOptions& o)
-    {
-        return DeviceVector<Data64>((hegpu_workspace_bytes(context_->handle(), HEGPU_OP_MPC_KEY_SHARE, 0, 1) + 7) / 8, o.stream_);
     }
     static std::vector<const uint64_t*> relin_shares(std::vector<MultipartyRelinkey<S>>& all_rk)
     {
@@ -3599,7 +3509,7 @@ template <> class Ciphertext<Scheme::TFHE> {
   public:
     explicit Ciphertext(HEContext<Scheme::TFHE> context, const ExecutionOptions& = ExecutionOptions())
     {
-        if (!context) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context);
         n_ = context->n_;
     }
     DeviceVector<int32_t> a_device_location_, b_device_location_;
@@ -3611,7 +3521,7 @@ template <> class Secretkey<Scheme::TFHE> {
   public:
     explicit Secretkey(HEContext<Scheme::TFHE> context) : context_(std::move(context))
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     DeviceVector<int32_t> lwe_key_device_location_, tlwe_key_device_location_;
     bool secret_key_generated_ = false;
@@ -3625,7 +3535,7 @@ template <> class Bootstrappingkey<Scheme::TFHE> { // boot key (prepared for the
   public:
     explicit Bootstrappingkey(HEContext<Scheme::TFHE> context) : context_(std::move(context))
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     DeviceVector<Data64> boot_key_device_location_;  // reference layout [n][k+1][l][k+1][N], NTT domain
     DeviceVector<Data64> prepared_;                  // hegpu_tfhe_prepare_bootkey
@@ -3642,13 +3552,13 @@ template <> class HEKeyGenerator<Scheme::TFHE> { // host/tfhe/keygenerator.cuh
   public:
     explicit HEKeyGenerator(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         detail::check(hegpu_rng_create_from_entropy(&rng_));
     }
     // REPRODUCIBLE TESTS ONLY (64-bit seed)
     HEKeyGenerator(HEContext<S> context, std::uint64_t seed) : context_(std::move(context))
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         detail::check(hegpu_rng_create(seed, &rng_));
     }
     ~HEKeyGenerator() { hegpu_rng_destroy(rng_); }
@@ -3696,7 +3606,7 @@ template <> class HEEncryptor<Scheme::TFHE> { // host/tfhe/encryptor.cuh: symmet
   public:
     HEEncryptor(HEContext<S> context, Secretkey<S>& sk) : context_(std::move(context)), sk_(&sk)
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
         detail::check(hegpu_rng_create_from_entropy(&rng_));
     }
@@ -3732,7 +3642,7 @@ template <> class HEDecryptor<Scheme::TFHE> { // host/tfhe/decryptor.cuh
   public:
     HEDecryptor(HEContext<S> context, Secretkey<S>& sk) : context_(std::move(context)), sk_(&sk)
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
         if (!sk.secret_key_generated_) throw std::logic_error("Secretkey is not generated!");
     }
     void decrypt(Ciphertext<S>& ct, std::vector<bool>& messages, const ExecutionOptions& o = ExecutionOptions())
@@ -3761,7 +3671,7 @@ template <> class HELogicOperator<Scheme::TFHE> { // host/tfhe/operator.cuh: boo
   public:
     explicit HELogicOperator(HEContext<S> context) : context_(std::move(context))
     {
-        if (!context_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
 #define HEONGPU_TFHE_GATE(NAME, ID)                                                                              \
     void NAME(Ciphertext<S>& in1, Ciphertext<S>& in2, Ciphertext<S>& out, Bootstrappingkey<S>& bk,               \
@@ -3895,14 +3805,14 @@ template <Scheme S> class LogicOperatorBase {
   protected:
     LogicOperatorBase(HEContext<S> context, double scale_one) : context_(std::move(context)), scale_one_(scale_one)
     {
-        if (!context_ || !context_->context_generated_) throw std::invalid_argument("HEContext is not generated!");
+        detail::require_generated(context_);
     }
     HEContext<S> context_;
     double scale_one_; // CKKS: the scale at which the constant one enters (the reference's encoded_constant_one_)
 
   private:
     // the checks and exception types of the arithmetic operator's multiply / multiply_plain / add
-    void check_cipher(const Ciphertext<S>& c, size_t words) const
+    void check_cipher(const Ciphertext<S>& c) const
     {
         if (c.relinearization_required_ || c.cipher_size_ != 2)
             throw std::invalid_argument("Ciphertexts can not be used because of the non-linear part! Please use "
@@ -3911,7 +3821,7 @@ template <Scheme S> class LogicOperatorBase {
             throw std::invalid_argument("Ciphertexts can not be used because of the noise! Please use rescale operation to "
                                         "get rid of additional noise!");
         if (S == Scheme::BFV && c.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in intt domain");
-        if (c.memory_size() < words) throw std::invalid_argument("Invalid Ciphertexts size!");
+        HEArithmeticOperator<S>::require_words(context_, c, 2);
     }
     void gate(int g, Ciphertext<S>& a, Ciphertext<S>* bc, Plaintext<S>* bp, Relinkey<S>* rk, Ciphertext<S>& out,
               const ExecutionOptions& o)
@@ -3920,10 +3830,10 @@ template <Scheme S> class LogicOperatorBase {
         const bool unary = g == HEGPU_LOGIC_NOT;
         const int l = context_->Q_size - a.depth_;
         const size_t n = context_->n;
-        check_cipher(a, 2 * n * l);
+        check_cipher(a);
         if (bc) {
             if (a.depth_ != bc->depth_) throw std::logic_error("Ciphertexts leveled are not equal");
-            check_cipher(*bc, 2 * n * l);
+            check_cipher(*bc); // at a's level: the depths are equal
         }
         if (bp) {
             if (ckks && bp->depth_ != a.depth_) throw std::logic_error("Ciphertext and Plaintext levels are not equal");
@@ -3940,34 +3850,24 @@ template <Scheme S> class LogicOperatorBase {
         // fresh memory for every result, in place too: the limb count of a CKKS binary gate changes
         DeviceVector<Data64> m((size_t) 2 * out_limbs * n, o.stream_);
         const int op = ckks ? HEGPU_OP_CKKS_LOGIC_GATE : HEGPU_OP_BFV_LOGIC_GATE;
-        const size_t wsb = unary ? 0 : hegpu_workspace_bytes(context_->handle(), op, a.depth_, 1);
-        DeviceVector<Data64> ws(wsb / 8, o.stream_);
+        detail::Workspace ws(unary ? 0 : hegpu_workspace_bytes(context_->handle(), op, a.depth_, 1), o.stream_); // NOT: none
         if (ckks)
             detail::check(hegpu_ckks_logic_gate(context_->handle(), g, (const uint64_t*) a.data(), 0, b, kind, 0, key,
-                                                scale_one_, (uint64_t*) m.data(), 0, a.depth_, 1, unary ? nullptr : ws.data(),
-                                                wsb, o.stream_));
+                                                scale_one_, (uint64_t*) m.data(), 0, a.depth_, 1, ws.data(), ws.bytes,
+                                                o.stream_));
         else
             detail::check(hegpu_bfv_logic_gate(context_->handle(), g, (const uint64_t*) a.data(), 0, b, kind, 0, key,
-                                               (uint64_t*) m.data(), 0, 1, unary ? nullptr : ws.data(), wsb, o.stream_));
+                                               (uint64_t*) m.data(), 0, 1, ws.data(), ws.bytes, o.stream_));
         // AND / NAND leave at the product's scale; the other gates at the first operand's, as the reference's last sub
         // leaves it.  (In place: a's fields are read before they are written.)
         double sc = a.scale_;
         if (ckks && (g == HEGPU_LOGIC_AND || g == HEGPU_LOGIC_NAND))
             sc = a.scale_ * (bc ? bc->scale_ : bp->scale_) / (double) context_->prime_vector_[l - 1].value;
         const int depth = a.depth_ + ((ckks && !unary) ? 1 : 0);
-        if (&a != &out) {
-            out.ring_size_ = a.ring_size_;
-            out.coeff_modulus_count_ = a.coeff_modulus_count_;
-            out.in_ntt_domain_ = a.in_ntt_domain_;
-            out.encoding_ = a.encoding_;
-        }
-        out.memory_set(std::move(m));
-        out.cipher_size_ = 2;
+        out.encoding_ = a.encoding_;
+        HEArithmeticOperator<S>::emit(a, out, std::move(m)); // two parts, no pending rescale or relinearization: check_cipher(a)
         out.depth_ = depth;
         out.scale_ = sc;
-        out.rescale_required_ = false;
-        out.relinearization_required_ = false;
-        out.ciphertext_generated_ = true;
     }
 };
 } // namespace detail

@@ -914,6 +914,24 @@ static void storage_manager()
     ok = true;
     for (size_t i = 0; ok && i < n; i++) ok = slots[i] == a[i];
     EXPECT(ok, "the copy decrypts to the same message");
+    // add_inplace / sub_inplace are add(a, b, a) / sub(a, b, a): they run inside a storage scope like every other
+    // operator, and a HOST-stored operand that the operator overwrites goes back to the host (keep_initial_condition_)
+    ca.store_in_host();
+    op.add_inplace(ca, cb);
+    EXPECT(!ca.is_on_device(), "add_inplace on a HOST-stored ciphertext leaves it on the host");
+    dec.decrypt(pr, ca);
+    encoder.decode(slots, pr);
+    ok = true;
+    for (size_t i = 0; ok && i < n; i++) ok = slots[i] == (a[i] + b[i]) % t;
+    EXPECT(ok, "add_inplace on a HOST-stored ciphertext gives a + b");
+    enc.encrypt(ca, pa);
+    op.add_inplace(ca, cb, ExecutionOptions().set_storage_type(storage_type::HOST));
+    EXPECT(!ca.is_on_device(), "add_inplace with storage_ = HOST parks the result in host memory");
+    dec.decrypt(pr, ca);
+    encoder.decode(slots, pr);
+    ok = true;
+    for (size_t i = 0; ok && i < n; i++) ok = slots[i] == (a[i] + b[i]) % t;
+    EXPECT(ok, "add_inplace with storage_ = HOST gives a + b");
 
     // ---- rotations through the storage manager: operator-local temporaries (rotate_rows_inplace's copy, the key
     // chain's intermediate ciphertexts) die before the operator's scope does; results assigned by copy / move (a zero

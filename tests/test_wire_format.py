@@ -65,6 +65,38 @@ def _payload(tmp_path, name):
     return open(tmp_path / (name + ".payload"), "rb").read()
 
 
+SKELETON = os.path.join(ROOT, "tests", "golden", "wire_skeleton.json")
+
+
+def _skeleton(kind, blob, d):
+    """The bytes of a blob outside its residue payloads, as hex strings: the header and, for a Galois key, the element
+    number in front of every key (the column-rotation key, written last, has none).  A context has no payload: the
+    whole blob."""
+    if kind == "context":
+        return [blob.hex()]
+    if kind != "galoiskey":
+        return [blob[:len(blob) - len(d["payload"])].hex()]
+    key = len(d["zero_key"])
+    head = len(blob) - (len(d["keys"]) * (4 + key) + key)
+    return [blob[:head].hex()] + [blob[off:off + 4].hex() for off in range(head, len(blob) - key, 4 + key)]
+
+
+@pytest.mark.gpu
+def test_bytes_outside_the_payloads_are_the_recorded_ones(tmp_path):
+    """wire_dump seeds its key generator and encryptor, so every blob is reproducible.  tests/golden/wire_skeleton.json
+    holds, per blob of the three parameter sets, the bytes outside the residue payloads as the class layer wrote them
+    before its writers were folded into detail::put / put_payload / KeySwitchShape::put_header: field order, field
+    widths, the plaintext size written twice, `storage` always DEVICE, the column-rotation key last.  (The payloads are
+    compared with the live objects in test_every_object_parses_and_matches_the_live_object.)"""
+    man = _run(tmp_path)
+    want = json.load(open(SKELETON))
+    assert sorted(man) == sorted(want)
+    for name, entry in man.items():
+        blob = open(tmp_path / (name + ".bin"), "rb").read()
+        d = None if entry["kind"] == "context" else wire.PARSERS[entry["kind"]](blob)
+        assert _skeleton(entry["kind"], blob, d) == want[name], name
+
+
 @pytest.mark.gpu
 def test_every_object_parses_and_matches_the_live_object(tmp_path, hg):
     man = _run(tmp_path)
