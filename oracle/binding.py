@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg -- never from heongpu_amd/.  See hegpu_oracle.h
-("parity unpinned" notice).
+(what is pinned to the reference's text and what rests on restatement).
 """
 import ctypes
 import os
@@ -116,6 +116,8 @@ def lib():
     L.o_drbg_block.argtypes = [ctypes.POINTER(ctypes.c_uint32), u64, u64, ctypes.POINTER(ctypes.c_uint32)]
     L.o_cipher_broadcast_leveled.argtypes = [vp, vp, vp, ci, ci, ci, ci]
     L.o_keyswitch_mac_leveled.argtypes = [vp, vp, vp, vp, ci, ci, ci]
+    L.o_keyswitch_mac_II.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci]
+    L.o_bfv_threshold_lift.argtypes = [vp, vp, vp]
     L.o_divide_round_lastq_permute.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci]
     L.o_base_conversion_DtoQtilde.argtypes = [vp, vp, vp, ci]
     L.o_divide_round_lastq_extended.argtypes = [vp, vp, vp, vp, ci, ci, ci]

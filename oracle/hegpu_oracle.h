@@ -6,17 +6,32 @@
  * bench.py's cpu_baseline leg use it, and only as the checker / timed CPU
  * baseline.
  *
- * PARITY UNPINNED at the limb level: the reference's arithmetic core
- * (github.com/Alisah-Ozcan/GPU-NTT, version unpinned, .gitmodules:4-6) is an
- * empty submodule in /root/reference, the reference is CUDA-only and cannot
- * be built or run in this pipeline, and its tests hold no golden vectors
- * (SURVEY.md 8c).  This restatement follows the in-tree call sites, table
- * generators and kernels line by line (each function cites file:line) and is
- * pinned by (a) deterministic parameter derivation checked against
- * tests/golden/ (python big-int restatement, oracle/pyref.py) and the
- * constants hard-coded in the reference (default moduli, TFHE psi), and
- * (b) semantic encrypt->op->decrypt round trips in tests/ (the shape of the
- * reference's own gtest suite).
+ * WHAT IS PINNED TO THE REFERENCE'S OWN TEXT, AND WHAT IS NOT.
+ * Pinned: the RNS kernels of src/lib/kernel/switchkey.cu, multiplication.cu and
+ * addition.cu (o_kernels.c, o_method2.c and the kernel-level parts of
+ * o_encode.c / o_keygen.c).  Those three files compile unchanged for gfx950
+ * against a stand-in for the one GPU-NTT header they include
+ * (oracle/ref_shim/, oracle/ref_build.py -> oracle/_ref/libref_kernels.so), and
+ * tests/test_gpu_reference_kernels.py runs them on the GPU next to this
+ * restatement and next to the product on the same inputs, every word compared:
+ * index arithmetic, loops, operand order, table use, launch geometry.
+ * Resting on restatement: (1) the GPU-NTT primitives themselves -- the
+ * reference's arithmetic core (github.com/Alisah-Ozcan/GPU-NTT, version
+ * unpinned, .gitmodules:4-6) is an empty submodule of the reference tree, so
+ * Modulus64 / add / sub / mult / reduce below and in oracle/ref_shim/ are the
+ * published algorithm restated ONCE and shared by both; inside the Barrett
+ * domain (a * b < 2^(2 bit)) the product is exact whatever the formula, outside
+ * it only the restated formula speaks (o_barrett_domain_violations counts
+ * those calls); (2) the NTT; (3) the kernels of encryption.cu, decryption.cu,
+ * keygeneration.cu, encoding.cu and bootstrapping.cu, which need PTX, the
+ * GPU-FFT headers or gpuntt/common/common.cuh and cannot be built here; the
+ * reference's tests hold no golden vectors for them.  Those
+ * parts follow the in-tree call sites, table generators and kernels line by
+ * line (each function cites file:line) and are pinned by (a) deterministic
+ * parameter derivation checked against tests/golden/ (python big-int
+ * restatement, oracle/pyref.py) and the constants hard-coded in the reference
+ * (default moduli, TFHE psi), and (b) semantic encrypt->op->decrypt round trips
+ * in tests/ (the shape of the reference's own gtest suite).
  */
 #ifndef HEGPU_ORACLE_H
 #define HEGPU_ORACLE_H
@@ -46,7 +61,7 @@ u64 o_mult(u64 a, u64 b, const omod_t* m);
 u64 o_reduce_forced(u64 a, const omod_t* m);
 u64 o_exp(u64 base, u64 e, const omod_t* m);
 u64 o_modinv(u64 a, const omod_t* m);
-/* counts Barrett calls with a*b >= 2^(2*bit): behaviour there is unpinned */
+/* counts Barrett calls with a*b >= 2^(2*bit): there the result rests on the restated formula alone */
 extern u64 o_barrett_domain_violations;
 
 /* ---- number theory / parameter derivation (util.cu:127-464) ---- */

@@ -1,8 +1,13 @@
 /*
  * o_arith.c -- modular arithmetic + number theory of the oracle.
- * TEST INFRASTRUCTURE ONLY (see hegpu_oracle.h).  PARITY UNPINNED for the
- * GPU-NTT primitives: their source is not in /root/reference; the Barrett
- * record below is the published GPU-NTT algorithm restated.
+ * TEST INFRASTRUCTURE ONLY (see hegpu_oracle.h).  The GPU-NTT primitives REST
+ * ON RESTATEMENT: their source is not in the reference tree (empty submodule);
+ * the Barrett record below is the published GPU-NTT algorithm restated
+ * (SURVEY.md 9).  oracle/ref_shim/gpuntt/common/modular_arith.cuh, under which
+ * the reference's own kernel files run, restates the same functions and is
+ * held equal to these by tests/test_reference_kernels_host.py -- so the
+ * kernels above them are pinned to the reference's text, these formulas are
+ * not (exact inside the Barrett domain whatever the formula).
  */
 #include "hegpu_oracle.h"
 #include <stdlib.h>

@@ -48,6 +48,9 @@ void o_divide_round_lastq_permute(const u64* input, const u64* input2,
                                   int n_power, int Q_prime_size, int Q_size,
                                   int first_Q_prime_size, int first_Q_size,
                                   int P_size);
+void o_keyswitch_mac_II(const u64* input, const u64* key, u64* output, const omod_t* mods, int first_rns, int l, int rc,
+                        int d, int level, int n_power);
+void o_bfv_threshold_lift(const octx_t* c, const u64* plain, u64* out);
 void o_fast_convertion(const octx_t* c, const u64* in1, const u64* in2,
                        u64* out1);
 void o_fast_floor(const octx_t* c, const u64* in_baseq_Bsk, u64* out1);

@@ -642,7 +642,7 @@ void o_tfhe_phase(const int32_t* lwe_key, const int32_t* a, const int32_t* b, in
  * threshold_kernel (multiplication.cu:274-296) with upper_halfincrement = q_j - t and
  * upper_threshold = (t + 1) >> 1 (bfv/context.cu:501-508), forward NTT:
  * HEOperator<BFV>::transform_to_ntt_bfv_plain (bfv/operator.cu:1398-1431); out [Q][N] */
-void o_bfv_plain_to_ntt(const octx_t* c, const u64* plain, u64* out)
+void o_bfv_threshold_lift(const octx_t* c, const u64* plain, u64* out)
 {
     const int Q = c->Q_size, np = c->n_power;
     const u64 t = c->plain_mod.value, thr = (t + 1) >> 1;
@@ -651,6 +651,11 @@ void o_bfv_plain_to_ntt(const octx_t* c, const u64* plain, u64* out)
             const u64 v = plain[i];
             out[i + ((u64) y << np)] = (v >= thr) ? o_add(v, c->mod[y].value - t, &c->mod[y]) : v;
         }
+}
+void o_bfv_plain_to_ntt(const octx_t* c, const u64* plain, u64* out)
+{
+    const int Q = c->Q_size, np = c->n_power;
+    o_bfv_threshold_lift(c, plain, out); /* the lift on its own: the parity test of threshold_kernel stops here */
     o_gpu_ntt(out, out, c->ntt_table, c->mod, np, Q, Q);
 }
 

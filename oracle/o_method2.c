@@ -1,6 +1,7 @@
 /*
  * o_method2.c -- key-switching method II (hybrid, P_size > 1) of the oracle.
- * TEST INFRASTRUCTURE ONLY (see hegpu_oracle.h; PARITY UNPINNED).  Follows
+ * TEST INFRASTRUCTURE ONLY (see hegpu_oracle.h: the kernels restated here are
+ * run against the reference's own in tests/test_gpu_reference_kernels.py).  Follows
  *   src/lib/kernel/contextpool.cpp:11-438 (digit partition + D->Q~ tables),
  *   src/lib/kernel/switchkey.cu:287-398,480-611,872-927,985-1046,1222-1282,
  *   src/lib/host/bfv/operator.cu:585-672,866-973, ckks/operator.cu:1025-1154,1561-1720.
@@ -149,6 +150,14 @@ static void keyswitch_mac_II(const u64* input, const u64* key, u64* output, cons
             output[x + ((u64) y << n_power) + ((u64) rc << n_power)] = s1;
         }
     }
+}
+
+/* exported form of the kernel above for the kernel-level parity test of hegpu_keyswitch_multiply_accumulate with
+ * method II chains: in [d][rc][N], key [>= d][2][first_rns][N], out [2][rc][N] */
+void o_keyswitch_mac_II(const u64* input, const u64* key, u64* output, const omod_t* mods, int first_rns, int l, int rc,
+                        int d, int level, int n_power)
+{
+    keyswitch_mac_II(input, key, output, mods, first_rns, l, rc, d, level, n_power);
 }
 
 /* switchkey.cu:480-545 (bfv: + ct) / 545-611 (switchkey: + ct on part 0) / 1222-1282 (leveled: no ct);
