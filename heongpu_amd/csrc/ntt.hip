@@ -524,9 +524,13 @@ __device__ __forceinline__ bool stages_room16(const Mod& md) { return md.bit <= 
 // group g, slot k at sreg[g * RA + k]) -- the multi-modulus column pass (ntt_fwd_col_multi) loads a
 // digit tile once and runs this body for every target modulus; it also needs the tile free again
 // before the next iteration writes it, hence the second barrier right after the exchange reads.
+// As for the FP64 body, `sreg` then holds canonical residues with the mod-down half already added, and the
+// lane-dependent twiddles of the second register round are handed over through `twl` (256 entries, free until the
+// barrier after the NEXT body's first round): requested up front as fifteen vector loads per lane they would hold 60
+// registers beside the source kept for the next modulus -- the third wave per SIMD of ntt_fwd_col_decomp_all.
 template <int S1, bool DECOMP, bool LAZY, bool SREG = false, int ROOM = 8>
 __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps, const Mod& md, u64* lds,
-                                             const u64* sreg = nullptr)
+                                             const u64* sreg = nullptr, ulonglong2* twl = nullptr)
 {
     constexpr CsSched CS = cs_sched(S1, ROOM); // over the S1 stages of the pass: round A takes the low bits
     constexpr int R = 1 << S1;
@@ -534,7 +538,10 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
     constexpr int NSA = S1 - 4;
     constexpr int RA = 1 << NSA;
     constexpr int G = 16 / RA;
-    const int t = threadIdx.x;
+    int t = threadIdx.x;
+    // (SREG: opaque per call, or the LDS and store offsets of all three integer bodies are hoisted out of the caller's
+    // modulus loop -- 29 registers held through it)
+    if constexpr (SREG) asm volatile("" : "+v"(t));
     const QC qc = make_qc(md.q);
     const ulonglong2* __restrict__ tw = a.tw + ((u64) ps.mod << a.n_power);
     const u64* __restrict__ src = a.in + ps.in_off + blockIdx.x * CT;
@@ -562,14 +569,17 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
         for (int k = 0; k < 16; k++) v[k] = SREG ? sreg[k] : gld(&src[(u64) k * 256 + col]);
     }
     if (DECOMP && a.half_on) {
+        // (SREG: the half is already added, as for the FP64 body)
 #pragma unroll
-        for (int k = 0; k < 16; k++) v[k] = sub_mod(reduce64(add_mod(v[k], a.half, half_qP), md), half_hm, md.q);
+        for (int k = 0; k < 16; k++) v[k] = sub_mod(reduce64(SREG ? v[k] : add_mod(v[k], a.half, half_qP), md), half_hm, md.q);
     } else if (DECOMP && !LAZY && a.mods[ps.digit].q > 8 * md.q) {
         // a digit of a much wider prime (61 bits next to 58): outside the [0, 8q) the correcting butterflies keep
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = reduce64(v[k], md);
     }
     if constexpr (NSA > 0) {
+        ulonglong2 mine;
+        if constexpr (SREG) mine = tw[t]; // tw[RA .. 16 RA): all the second round reads (see fwd_col_body_fp)
         // round A: G groups of radix RA, rows rbase + 16k
 #pragma unroll
         for (int g = 0; g < G; g++) {
@@ -582,10 +592,14 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
             // first: the correcting butterflies only need x < 8q (guarded above) and the
             // correction-free path x + 4 log2(N) q < 2^64 (lazy_q_max); congruence mod q is
             // kept and the row pass ends with an exact reduction.
-            ct_radix<NSA, LAZY, CS.c8, CS.c4>(y, tw, 1u, qc);
+            // (SREG = inside a modulus loop with stores in it: the wave-uniform twiddles through the constant address
+            // space -- see ConstTw)
+            if constexpr (SREG) ct_radix<NSA, LAZY, CS.c8, CS.c4>(y, const_tw(tw), 1u, qc);
+            else ct_radix<NSA, LAZY, CS.c8, CS.c4>(y, tw, 1u, qc);
 #pragma unroll
             for (int k = 0; k < RA; k++) lds[col_phys((rb + 16 * k) * CT + c)] = y[k];
         }
+        if constexpr (SREG) twl[t] = mine;
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 16; k++) x[k] = lds[col_phys((16 * r1 + k) * CT + col)];
@@ -594,7 +608,8 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
 #pragma unroll
         for (int k = 0; k < 16; k++) x[k] = v[k];
     }
-    ct_radix<4, LAZY, (CS.c8 >> NSA), (CS.c4 >> NSA)>(x, tw, (u32) (RA + r1), qc);
+    if constexpr (SREG && NSA > 0) ct_radix<4, LAZY, (CS.c8 >> NSA), (CS.c4 >> NSA)>(x, twl, (u32) (RA + r1), qc);
+    else ct_radix<4, LAZY, (CS.c8 >> NSA), (CS.c4 >> NSA)>(x, tw, (u32) (RA + r1), qc);
 #pragma unroll
     for (int k = 0; k < 16; k++) gst(&dst[(u64) (16 * r1 + k) * 256 + col], x[k]);
 }
@@ -2105,8 +2120,9 @@ __device__ __forceinline__ void inv_store(const InvEpi& epr, u64* __restrict__ p
 // Column stages of one column tile (R rows x CT columns), results to global memory.  FROM_LDS: the row
 // stages left their output in the LDS-resident limb (`buf` = the limb, positions single_pos); otherwise the
 // tile is read from `p` (global, in place) and `buf` is the tile's 4096-element exchange buffer.
-// KEEP: the results also stay in `keep` (slot gi * RA + k, the load order of the forward column stages)
-template <int S1, typename AR, bool FROM_LDS, bool KEEP = false, bool EPI = false>
+// KEEP: the results also stay in `keep` (slot gi * RA + k, the load order of the forward column stages); with STORE
+// off they stay there only
+template <int S1, typename AR, bool FROM_LDS, bool KEEP = false, bool EPI = false, bool STORE = true>
 __device__ __forceinline__ void inv_col_part(const AR& ar, const NttArgs& a, int mod, int tt, int g, u64* __restrict__ p,
                                              u64* buf, u64 (&keep)[16], const InvEpi& ep = InvEpi(), u32 e0 = 0)
 {
@@ -2141,7 +2157,8 @@ __device__ __forceinline__ void inv_col_part(const AR& ar, const NttArgs& a, int
 #pragma unroll
             for (int k = 0; k < RA; k++) y[k] = ar.from_bits(buf[pos(rb + 16 * k, c)]);
             ar.template radix_last<NSA>(y, tw, ninv, w1ninv, o);
-            if constexpr (RA == 16) {
+            if constexpr (!STORE) {
+            } else if constexpr (RA == 16) {
                 // two halves: sixteen elements' worth of epilogue operands would not fit the register budget
                 u64 oa[8], ob[8];
 #pragma unroll
@@ -2159,7 +2176,7 @@ __device__ __forceinline__ void inv_col_part(const AR& ar, const NttArgs& a, int
     } else {
         u64 o[16];
         ar.template radix_last<4>(x, tw, ninv, w1ninv, o);
-        {
+        if constexpr (STORE) {
             u64 oa[8], ob[8];
 #pragma unroll
             for (int k = 0; k < 8; k++) { oa[k] = o[k]; ob[k] = o[8 + k]; }
@@ -2277,16 +2294,15 @@ __global__ __launch_bounds__(16 << S1, 4) void ntt_inv_single(NttArgs a)
 // of its source tile (see below).  Two barriers per iteration (tile written -> read -> free again); the
 // second-round twiddles of the FP64 body are double-buffered by iteration parity, which the first
 // barrier of the following iteration makes safe.  grid = (256 / CT, items * digits).
-template <int S1>
-__global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
+// ALL: the integer target moduli of the digit as well, after the FP64 ones (ntt_fwd_col_decomp_all).
+template <int S1, bool ALL>
+__device__ __forceinline__ void fwd_col_multi_body(const NttArgs& a, u64* lds, ulonglong2* twl)
 {
     constexpr int R = 1 << S1;
     constexpr int CT = 4096 / R;
     constexpr int NSA = S1 - 4;
     constexpr int RA = 1 << NSA;
     constexpr int G = 16 / RA;
-    __shared__ u64 lds[(S1 > 4) ? COL_LDS_ELEMS : 1];
-    __shared__ ulonglong2 twl[(S1 > 4) ? 512 : 1];
     const int t = threadIdx.x;
     const int rc = a.decomp_mods;
     const int digits = udiv16(a.polys_per_item, a.mg_decomp_mods);
@@ -2299,12 +2315,13 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
         // The source limb is still half-way through its INVERSE transform (row stages done by ntt_inv_row):
         // the column tile its last stages produce is exactly the tile this workgroup decomposes, in the very
         // register layout (rows rb + 16 k of column c), so they run here -- ntt_inv_col's write of the
-        // coefficient-domain limb and the re-read disappear.  The tile is still stored (in place): the
-        // integer target moduli are transformed by the per-polynomial kernel, which reads it.  FP64 source
+        // coefficient-domain limb and the re-read disappear.  Without ALL the tile is still stored (in place): the
+        // integer target moduli are transformed by the per-polynomial kernel, which reads it; with ALL nobody does
+        // and the limb in memory stays as the row stages left it.  FP64 source
         // moduli only: with the integer inverse inlined as well the modulus loop below lost a wave per SIMD;
         // limbs of integer moduli get their column stages from ntt_inv_col (ntt_launch_inv_rows).
         const Mod im = a.mods[smod];
-        inv_col_part<S1, ArFp, false, true>(ArFp(im, a.n_power), a, smod, t, 0, const_cast<u64*>(src), lds, sreg);
+        inv_col_part<S1, ArFp, false, true, false, !ALL>(ArFp(im, a.n_power), a, smod, t, 0, const_cast<u64*>(src), lds, sreg);
         __syncthreads(); // the exchange tile is free again
     } else if constexpr (NSA > 0) {
 #pragma unroll
@@ -2328,8 +2345,8 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
 #pragma unroll
         for (int k = 0; k < 16; k++) sreg[k] = as_bits(fp_from_u64(sreg[k]));
     }
-    int done = 0; // executed iterations (parity of the twiddle buffer)
-    for (int k = 0; k < rc; k++) {
+    // target slot k of this digit
+    auto target = [&](int k) {
         PolySel ps;
         // (launch-constant tables read through the scalar cache: inside this loop plain loads of them are vector loads
         // with an s_waitcnt vmcnt(0) each -- round 5, see ConstTw)
@@ -2340,14 +2357,58 @@ __global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
         ps.in_off = 0;
         ps.out_off = (u64) item * a.out_item_stride +
                      ((u64) (a.decomp_out_mul ? digit * a.decomp_out_mul + k : ps.j) << a.n_power);
+        return ps;
+    };
+    int done = 0; // executed iterations (parity of the twiddle buffer)
+    for (int k = 0; k < rc; k++) {
+        const PolySel ps = target(k);
         if (a.skip_identity && ps.mod == digit) continue;
         const Mod md = ld_const_mod(a.mods + ps.mod);
-        if (!md.fp) continue; // integer target moduli: ntt_fwd_col<S1, true> with only_int
+        if (!md.fp) continue; // integer target moduli: below (ALL), or ntt_fwd_col<S1, true> with only_int
         ulonglong2* tl = twl + ((S1 > 4) ? 256 * (done & 1) : 0);
         done++;
         if (wide) fwd_col_body_fp<S1, true, true, true>(a, ps, md, lds, tl, sreg);
         else fwd_col_body_fp<S1, true, false, true>(a, ps, md, lds, tl, sreg);
     }
+    if constexpr (ALL) {
+        // The integer targets (NttArgs::int_slots) from the same registers, with the body and the choice of
+        // ntt_fwd_col<S1, true>.  The tile is free: every body above ends behind a barrier.  Workgroups of a CU drift
+        // apart, so this vector-ALU phase of one runs under the store-bound FP64 phases of the others.
+        if (!wide) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) sreg[k] = fp_to_u64(as_f64(sreg[k]));
+        }
+        for (int w = 0; w < a.int_slot_count; w++) {
+            const PolySel ps = target(a.int_slots[w]);
+            if (a.skip_identity && ps.mod == digit) continue;
+            const Mod md = ld_const_mod(a.mods + ps.mod);
+            ulonglong2* tl = twl + 256 * (done & 1); // the parity goes on from the FP64 bodies
+            done++;
+            if (fwd_stages_lazy(md, a.lazy_q_max)) fwd_col_body<S1, true, true, true>(a, ps, md, lds, sreg, tl);
+            else if (stages_room16(md)) fwd_col_body<S1, true, false, true, 16>(a, ps, md, lds, sreg, tl);
+            else fwd_col_body<S1, true, false, true>(a, ps, md, lds, sreg, tl);
+        }
+    }
+}
+
+template <int S1>
+__global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_multi(NttArgs a)
+{
+    __shared__ u64 lds[(S1 > 4) ? COL_LDS_ELEMS : 1];
+    __shared__ ulonglong2 twl[(S1 > 4) ? 512 : 1];
+    fwd_col_multi_body<S1, false>(a, lds, twl);
+}
+
+// The same pass with the integer target moduli in it (N = 2^16, launches that list their integer slots): one launch
+// instead of ntt_fwd_col_multi followed by ntt_fwd_col<S1, true> with only_int, no second read of the source limbs
+// and, with NttArgs::src_inv, no store of the finished inverse tile.  A kernel of its own: ntt_fwd_col_multi keeps its
+// code and its budget (tests/test_kernel_budgets.py, tests/test_kernel_budgets_decomp_all.py).
+template <int S1>
+__global__ __launch_bounds__(NTT_THREADS) void ntt_fwd_col_decomp_all(NttArgs a)
+{
+    __shared__ u64 lds[COL_LDS_ELEMS];
+    __shared__ ulonglong2 twl[512];
+    fwd_col_multi_body<S1, true>(a, lds, twl);
 }
 
 // ------------------------------------------------------------------ launch
@@ -2365,11 +2426,18 @@ static bool use_col_multi(const NttArgs& a, int batch)
 }
 
 // FP64 target moduli through the multi-modulus kernel, the integer ones (if the plan has any: the
-// 60-bit q0 and P of the C4 chain) through the per-polynomial kernel, which skips the rest
+// 60-bit q0 and P of the C4 chain) through the per-polynomial kernel, which skips the rest -- or, at N = 2^16 when the
+// caller lists the integer slots, both kinds in ONE launch of ntt_fwd_col_decomp_all
 template <int S1>
 static void launch_col_multi(const NttArgs& a, int batch, hipStream_t st)
 {
     constexpr int CT = 4096 >> S1;
+    if constexpr (S1 == 8) {
+        if (a.plan_has_fp && a.plan_has_int && a.int_slot_count > 0 && a.int_slot_count <= 8) {
+            hipLaunchKernelGGL((ntt_fwd_col_decomp_all<S1>), dim3(256 / CT, batch / a.decomp_mods), dim3(NTT_THREADS), 0, st, a);
+            return;
+        }
+    }
     if (a.plan_has_fp)
         hipLaunchKernelGGL((ntt_fwd_col_multi<S1>), dim3(256 / CT, batch / a.decomp_mods), dim3(NTT_THREADS), 0, st, a);
     if ((a.plan_has_int || !a.plan_has_fp) && !(a.plan_has_fp && a.int_slot_count < 0)) {

@@ -152,8 +152,10 @@ struct NttArgs {
     int int_slots[8];
     // Decomposing launch through the multi-modulus kernel only (ntt_decomp_uses_multi): the source limbs are
     // the output of ntt_launch_inv_rows -- for FP64 source moduli: inverse row stages done, column stages
-    // still to do -- and the kernel finishes their inverse transform itself (in place, the coefficient-domain
-    // limbs are stored too).
+    // still to do -- and the kernel finishes their inverse transform itself.  ntt_fwd_col_multi stores the
+    // coefficient-domain limbs too (in place: the per-polynomial kernel of the integer targets reads them);
+    // ntt_fwd_col_decomp_all keeps them in registers only, the limbs in memory stay half-way.  No caller reads them
+    // after the launch; one that did would need a flag here.
     int src_inv;
     // Decomposing launches through the per-polynomial column kernel only (not ntt_decomp_uses_multi): the workgroup
     // of polynomial (digit d, target slot k) also copies its column tile of limb d * copy_part_limbs + k from
