@@ -77,6 +77,13 @@ __device__ __forceinline__ double fp_from_u64(u64 v)
     FP_AUDIT_FROM_U64(v);
     return as_f64(v | 0x4330000000000000ull) - 4503599627370496.0;
 }
+// the same in ONE FP64 instruction (v_ldexp_f64): the raw bits of v < 2^52 are the denormal v * 2^-1074, and scaling by
+// 2^1074 gives v exactly.  Needs FP64 denormals on, as every kernel here is built (the compiler's default for gfx950).
+__device__ __forceinline__ double fp_from_u64_ldexp(u64 v)
+{
+    FP_AUDIT_FROM_U64(v);
+    return __builtin_ldexp(as_f64(v), 1074);
+}
 __device__ __forceinline__ double fp_from_u32(u32 v) { return fp_from_u64((u64) v); }
 // r an integer in [0, 2^52)
 __device__ __forceinline__ u64 fp_to_u64(double r)
@@ -107,6 +114,27 @@ __device__ __forceinline__ double fp_mul(double y, double wx, double wy, const F
     const double k = __builtin_rint(y * wy);
     const double t = __builtin_fma(-k, c.q, h) + l;
     FP_AUDIT_MUL(y, wx, wy, k, t, c);
+    return t;
+}
+// The same product WITHOUT a companion, for callers that hold only w (the fused key-switch row pass: no registers or
+// LDS for a second double per twiddle).  The quotient comes from the rounded product that is formed anyway:
+//   h = RN(y*w), l = y*w - h (exact, FMA), k = rint(RN(h * RN(1/q))), t = (h - k*q) + l.
+// Three roundings of relative size 2^-53 lie between h*RN(1/q) as computed and y*w/q (h, 1/q, their product) -- as
+// many as between RN(y * RN(w * RN(1/q))) and y*w/q, the form with a recomputed companion that this one replaces -- so
+// |k - y*w/q| <= 1/2 + 1.5 * 2^-52 * |y*w/q| either way.  With w < q < 2^50 that is 1/2 + 0.375 |y|/q: k < 2^53 is an
+// exact integer, h - k*q = (y*w - k*q) - l with |l| <= ulp(h)/2 <= 2^49 is an integer below 2^52 for every |y| <= 5.72 q
+// the callers pass, so the FMA and the final sum are exact: t == y*w - k*q EXACTLY, |t| <= (0.5 + 0.375 |y|/q) q.  A
+// butterfly takes |x| <= b q to at most (1.375 b + 0.5) q -- fp_mul with an exactly rounded companion gives 1.25 b +
+// 0.5, which is why the column passes keep theirs.  k may differ by one from the companion form's; t then moves by q
+// inside the same bound and every canonical residue stays what it was.  tests/test_fp_model_quotient.py searches the
+// bound in exact rational arithmetic.
+__device__ __forceinline__ double fp_mul_nc(double y, double w, const FC& c)
+{
+    const double h = y * w;
+    const double l = __builtin_fma(y, w, -h);
+    const double k = __builtin_rint(h * c.qi);
+    const double t = __builtin_fma(-k, c.q, h) + l;
+    FP_AUDIT_MUL(y, w, 0.0, k, t, c);
     return t;
 }
 

@@ -107,6 +107,15 @@ __device__ __forceinline__ void fp_ct_bfly(double& x, double& y, ulonglong2 w, c
     FP_AUDIT_VAL(c, FPM_SUM, x);
     FP_AUDIT_VAL(c, FPM_SUM, y);
 }
+// the same butterfly on a twiddle without a companion (fp_mul_nc: growth 1.375 b + 0.5)
+__device__ __forceinline__ void fp_ct_bfly(double& x, double& y, double w, const FC& c)
+{
+    const double t = fp_mul_nc(y, w, c);
+    y = x - t;
+    x = x + t;
+    FP_AUDIT_VAL(c, FPM_SUM, x);
+    FP_AUDIT_VAL(c, FPM_SUM, y);
+}
 // Where the centred reductions of the FP64 forward transform go (round 3).  A stage takes |x| <= b q to at most
 // (1.25 b + 0.5) q (fpmod.cuh, q < 2^50), and everything stays exact while |x| < 2^53 = 8 * 2^50: from b = 1/2 that is
 // SIX stages (1.125, 1.91, 2.88, 4.10, 5.63, 7.54), from an un-reduced input (b <= 1.05: a canonical residue, or a digit
@@ -114,7 +123,7 @@ __device__ __forceinline__ void fp_ct_bfly(double& x, double& y, ulonglong2 w, c
 // the input of a decomposing launch as well -- five times per 16 stages; three suffice.  The schedule is computed at
 // compile time from the bound: `before` bit s = reduce before local stage s, `at_end` = the hand-over bound would be
 // exceeded.  Contract between the passes: the column stages hand over centred residues (|x| <= q / 2) -- the row stages
-// of the fused key switch recompute their twiddle companions (growth 1.375 b + 0.5: five stages per reduction, not
+// of the fused key switch have no exact twiddle companions (fp_mul_nc, growth 1.375 b + 0.5: five stages per reduction, not
 // six), so a looser hand-over would cost that kernel the reduction the column pass saved.  What the schedule buys:
 // the input of a decomposing launch is not reduced (its digit is a residue of a prime of the same size), and the one
 // reduction inside the column stages sits after the fifth stage instead of the fourth.
@@ -1287,10 +1296,12 @@ __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int 
 // FP64 moduli (q < 2^50): the same residues, (acc - T) P^-1 + ct mod q, without leaving the doubles -- everything is
 // exact integer arithmetic modulo q, so the canonical result is the integer form's, bit for bit.  acc = the running
 // sums as the digit loop left them (|acc| <= 7.88 q), tv = T straight from its row stages, un-reduced (|T| <= 5.22 q),
-// (inv, invq) = P^-1 mod q (canonical, < q) and its companion RN(inv RN(1/q)).
+// inv = P^-1 mod q (canonical, < q); no companion (fp_mul_nc).
 //   d = fp_reduce(acc) - T: acc - T itself could pass 2^53 (13.1 q), so the sums are re-centred first; then
 //       |d| <= 0.5 q + 5.22 q = 5.72 q < 2^53, a difference of two integers below 2^53: exact.
-//   t = fp_mul(d, inv, invq): operand |y| = |d| <= 5.72 q, "twiddle" inv < q.  invq and the rounded product d invq are
+//   t = fp_mul_nc(d, inv): operand |y| = |d| <= 5.72 q, "twiddle" inv < q.  The quotient is taken from the rounded
+//       product h = RN(d inv): h, RN(1/q) and h RN(1/q) are three roundings, as inv RN(1/q), its product by d and RN(1/q)
+//       were when a companion was formed here, so the numbers stand: the rounded quotient is
 //       within |d inv / q| * 1.5 * 2^-52 <= 5.72 * 2^50 * 1.5 * 2^-52 = 2.15 of d inv / q, so |k - y x / q| <= 2.65; k < 2^53
 //       is an exact integer, h - k q = (y x - k q) - l with |l| <= ulp(h) / 2 <= 2^49 (|h| < 2^103) is an integer below
 //       2.65 q + 2^49 < 2^52: the FMA that forms it and the sum with l are exact, t = d inv - k q EXACTLY, |t| <= 2.65 q.
@@ -1299,7 +1310,7 @@ __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int 
 //       non-canonical ct); |t + ct| < 2.65 q + 2^52 < 2^53, exact; fp_canon takes that to [0, q).
 // tests/test_fp_model_tail.py derives these bounds, tests/test_gpu_fp_tail.py measures them in the instrumented build.
 __device__ __forceinline__ void ks_tail_store_fp(const KsMacArgs& a, int item, int slot, int p, u64 e0, const FC& fc, double inv,
-                                                 double invq, const double (&acc)[16], const double (&tv)[16], bool with_ct,
+                                                 const double (&acc)[16], const double (&tv)[16], bool with_ct,
                                                  const u64 (&cv)[16])
 {
     double m[16];
@@ -1309,7 +1320,7 @@ __device__ __forceinline__ void ks_tail_store_fp(const KsMacArgs& a, int item, i
         const double d = fp_reduce(acc[k], fc) - tv[k];
         FP_STAGE(fc, FP_STAGE_TAIL);
         FP_AUDIT_VAL(fc, FPM_SUM, d);
-        m[k] = fp_mul(d, inv, invq, fc);
+        m[k] = fp_mul_nc(d, inv, fc);
     }
     FP_STAGE(fc, FP_STAGE_OUT);
     if (with_ct) {
@@ -1480,9 +1491,8 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
 #pragma unroll
             for (int b = 0; b < (1 << s); b++) {
                 const double w = twl[15 * 256 + ((1 << s) - 1 + b) * 16 + row];
-                const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
 #pragma unroll
-                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
             }
         }
         FP_STAGE(fc, s1 + 4);
@@ -1504,8 +1514,7 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
             FP_STAGE(fc, s1 + 4 + s);
 #pragma unroll
             for (int b = 0; b < (1 << s); b++) {
-                const double wd = twl[((1 << s) - 1 + b) * 256 + t];
-                const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
+                const double w = twl[((1 << s) - 1 + b) * 256 + t];
 #pragma unroll
                 for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
             }
@@ -1549,9 +1558,8 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
 #pragma unroll
             for (int b = 0; b < (1 << s); b++) {
                 const double w = wc[b];
-                const ulonglong2 wp = make_ulonglong2(as_bits(w), as_bits(w * fc.qi));
 #pragma unroll
-                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], wp, fc);
+                for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
             }
         }
         FP_STAGE(fc, s1 + 4);
@@ -1580,8 +1588,7 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int b = 0; b < (1 << s); b++) {
-                const double wd = wc[b];
-                const ulonglong2 w = make_ulonglong2(as_bits(wd), as_bits(wd * fc.qi));
+                const double w = wc[b];
 #pragma unroll
                 for (int j = 0; j < half; j++) fp_ct_bfly(x[b * 2 * half + j], x[b * 2 * half + j + half], w, fc);
             }
@@ -1628,10 +1635,12 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
     // not fit the 32 KiB L1) and the SIMDs issued only 48 % of the time; 120 more registers are not
     // available.  So they are parked in LDS once per workgroup: the 15 of the last four stages are
     // private to the lane (slot k at [k][t]), the 15 of the first four are shared by the 16 lanes of
-    // a row ([k][row], written by lane i0 == k).  Only w is kept; its companion RN(w/q) is
-    // recomputed as w * RN(1/q) when the twiddle is used (one multiply per twiddle; a stage then takes |x| <= b q
+    // a row ([k][row], written by lane i0 == k).  Only w is kept, and no companion RN(w/q) is formed
+    // for it: the butterflies take their quotient from the rounded product (fp_mul_nc).  That carries the three
+    // roundings the recomputed companion w * RN(1/q) carried before, so a stage still takes |x| <= b q
     // to at most (1.375 b + 0.5) q: 0.5 -> 1.19, 2.13, 3.43, 5.22 q < 2^53 over the four stages of a round --
-    // tests/fp_model.py derives and searches these bounds, tests/test_gpu_fp_audit.py measures them on the device).
+    // tests/fp_model.py derives and searches these bounds, tests/test_gpu_fp_audit.py measures them on the device,
+    // tests/test_fp_model_quotient.py checks the companion-free product itself).
     double* twl = reinterpret_cast<double*>(twbuf); // [15 * 256 + 15 * 16]
 #pragma unroll
     for (int k = 0; k < 15; k++) twl[k * 256 + t] = tb8[k * 16];
@@ -1678,26 +1687,28 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
         if (ident) {
             FP_STAGE(fc, FP_STAGE_INPUT);
 #pragma unroll
-            for (int k = 0; k < 16; k++) x[k] = fp_reduce(fp_from_u64(xr[k]), fc);
+            for (int k = 0; k < 16; k++) x[k] = fp_reduce(fp_from_u64_ldexp(xr[k]), fc);
         } else {
             ks_fp_row<SPLIT>(x, xr, twl, lds, fc, s1, row, i0, t);
         }
 #pragma unroll
         for (int k = 0; k < 16; k++) {
-            // x plays the role of the "twiddle" (companion RN(x/q) ~ x * qi), the key (canonical, y < q < 2^50) is the
+            // x plays the role of the "twiddle", the key (canonical, y < q < 2^50) is the
             // operand.  Round 5: x arrives UN-reduced from the last four stages, |x| <= 5.22 q (0.5 q after the reduction
-            // in the middle, then b -> 1.375 b + 0.5 four times: the stages recompute their companions).  Exactness of
-            // fp_mul(y, x, xi): xi = RN(x RN(1/q)) and the rounded product y xi are within |y x / q| * 1.5 * 2^-52 <=
+            // in the middle, then b -> 1.375 b + 0.5 four times: the stages have no exact companions).  Exactness of
+            // fp_mul_nc(y, x): the quotient comes from h = RN(y x) -- h, RN(1/q) and their product are the three roundings
+            // that xi = RN(x RN(1/q)) and RN(y xi) were, so the numbers stand: RN(h RN(1/q)) is within |y x / q| * 1.5 * 2^-52 <=
             // 5.22 * 2^50 * 1.5 * 2^-52 = 1.96 of y x / q, so |k - y x / q| <= 2.46; k < 2^53 is an exact integer, h - k q
             // = (y x - k q) - l with |l| <= ulp(h) / 2 <= 2^49 is an integer below 2.46 q + 2^49 < 2^52 -- the FMA that
             // forms it and the sum with l are exact, t = y x - k q EXACTLY with |t| <= 2.46 q.  What the larger operand
             // costs is the accumulators' headroom: 0.5 q + 3 * 2.46 q = 7.88 q < 8 q <= 2^53, so they are re-centred after
             // every THIRD digit (round 4: x reduced to q / 2 first -- 48 instructions per digit and thread -- |t| <= 0.75 q,
-            // re-centred every fourth: 24; now 0 + 32).
-            const double xi = x[k] * fc.qi;
+            // re-centred every fourth: 24; now 0 + 32).  The key residues (and the identity limb above) become doubles in
+            // one v_ldexp_f64 each (fp_from_u64_ldexp): 32 instructions per digit fewer than OR + subtract, 7.24 -> 7.21 ms
+            // per C4 step in same-box A/Bs.
             FP_STAGE(fc, FP_STAGE_PRODUCT);
-            a0[k] += fp_mul(fp_from_u64(kv0[k]), x[k], xi, fc);
-            a1[k] += fp_mul(fp_from_u64(kv1[k]), x[k], xi, fc);
+            a0[k] += fp_mul_nc(fp_from_u64_ldexp(kv0[k]), x[k], fc);
+            a1[k] += fp_mul_nc(fp_from_u64_ldexp(kv1[k]), x[k], fc);
             FP_STAGE(fc, FP_STAGE_SUMS + since); // sums holding since + 1 products since they were last re-centred
             FP_AUDIT_VAL(fc, FPM_SUM, a0[k]);
             FP_AUDIT_VAL(fc, FPM_SUM, a1[k]);
@@ -1720,9 +1731,8 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
         asm volatile("" : "+v"(tt));
         const int trow = tt >> 4, ti0 = tt & 15;
         const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
-        // P^-1 mod q_j and its companion, formed here as the key products form theirs: one multiply per workgroup.  A
-        // pair table uploaded by the context would hold the same two wave-uniform doubles in the same registers.
-        const double inv = fp_from_u64(a.tail.inv[midx_s]), invq = inv * fc.qi;
+        // P^-1 mod q_j, wave-uniform; without a companion, as in the key products (fp_mul_nc)
+        const double inv = fp_from_u64(a.tail.inv[midx_s]);
         auto part = [&](int p, const double (&acc)[16]) {
             const u64* pT = ks_tail_T(a, item_s, slot_s, tile_s, p);
             u64 tr[16], cv[16];
@@ -1731,7 +1741,7 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
             const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
             double x[16];
             ks_fp_row<false>(x, tr, twl, lds, fc, s1, trow, ti0, tt);
-            ks_tail_store_fp(a, item_s, slot_s, p, e0, fc, inv, invq, acc, x, with_ct, cv);
+            ks_tail_store_fp(a, item_s, slot_s, p, e0, fc, inv, acc, x, with_ct, cv);
         };
         __builtin_amdgcn_sched_barrier(0); // (one part at a time: the loads of the second are not hoisted into the first)
         part(0, a0);

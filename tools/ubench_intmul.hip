@@ -59,6 +59,16 @@ __global__ __launch_bounds__(256) void k(u64* out, u32 a0, u32 b0)
                 acc[c] = (u32) (d * 0.5);
             } else if (KIND == 14) { // v_lshl_add_u64
                 acc[c] = (acc[c] << 1) + acc[(c + 1) % CH];
+            } else if (KIND == 15) { // v_ldexp_f64 (exponent +-3 by turns: the values stay finite and normal)
+                double d = __longlong_as_double(acc[c]);
+                d = __builtin_ldexp(d, (i & 1) ? -3 : 3);
+                acc[c] = __double_as_longlong(d);
+            } else if (KIND == 16) { // v_ldexp_f64 as fp_from_u64_ldexp uses it: a denormal input scaled by 2^1074
+                double d = __longlong_as_double(acc[c] & 0xFFFFFFFFFFFFFull);
+                d = __builtin_ldexp(d, 1074);
+                acc[c] = __double_as_longlong(d) >> 11;
+            } else if (KIND == 17) { // the frame of the line above without the ldexp (and + shift)
+                acc[c] = ((acc[c] & 0xFFFFFFFFFFFFFull) + x) >> 11;
             } else if (KIND == 6) { // v_mul_u32_u24 (full-rate 24-bit)
                 acc[c] = __umul24((u32) acc[c], x) + 1;
             }
@@ -105,5 +115,8 @@ int main()
     run<12>("rndne_f64+add", d);
     run<13>("cvt f64<->u32+mul", d);
     run<14>("v_lshl_add_u64", d);
+    run<15>("v_ldexp_f64", d);
+    run<16>("and+ldexp_dn+shr", d);
+    run<17>("and+add+shr", d);
     return 0;
 }
