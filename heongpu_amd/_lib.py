@@ -78,6 +78,8 @@ SIGNATURES = [
     ("hegpu_cross_multiplication", c_int,
      [voidp, c_int, u64p, u64, u64p, u64, u64p, u64, c_int, c_int, voidp]),
     ("hegpu_cipher_broadcast", c_int, [voidp, u64p, u64, u64p, u64, c_int, c_int, c_int, c_int, c_int, voidp]),
+    ("hegpu_mod_raise", c_int, [voidp, u64p, u64, u64p, u64, c_int, c_int, c_int, voidp]),
+    ("hegpu_ckks_mod_raise", c_int, [voidp, u64p, u64, u64p, u64, c_int, c_int, voidp, c_size_t, voidp]),
     ("hegpu_keyswitch_multiply_accumulate", c_int,
      [voidp, u64p, u64, u64p, u64p, u64, c_int, c_int, c_int, c_int, c_int, c_int, voidp]),
     ("hegpu_base_conversion_DtoQtilde", c_int, [voidp, u64p, u64, u64p, u64, c_int, c_int, voidp]),
@@ -119,6 +121,11 @@ SIGNATURES = [
     ("hegpu_poly_eval_plan_fill", c_int,
      [c_int, voidp, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(u64), c_int,
       ctypes.POINTER(PolyStep), c_int]),
+    ("hegpu_eval_mod_plan_size", c_int,
+     [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(u64), c_int, ctypes.POINTER(c_int)]),
+    ("hegpu_eval_mod_plan_fill", c_int,
+     [c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(u64), c_int, ctypes.POINTER(PolyStep),
+      c_int]),
     ("hegpu_ckks_weighted_sum", c_int,
      [voidp, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(u64), ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double),
       c_int, ctypes.c_double, ctypes.c_double, u64p, u64, c_int, c_int, voidp]),

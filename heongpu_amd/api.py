@@ -26,6 +26,7 @@ OP_MPC_REFRESH_SHARE, OP_MPC_REFRESH_MERGE = 20, 21
 MPC_PUBLIC_KEY, MPC_GALOIS_KEY, MPC_RELIN_ROUND1 = 0, 1, 2
 TABLES_PLAIN = 2
 OP_CKKS_LOGIC_GATE, OP_BFV_LOGIC_GATE = 22, 23
+OP_CKKS_MOD_RAISE = 25  # 24 stays unassigned
 # the gates of the BFV / CKKS logic layer (the TFHE gates keep their own numbering: GATE_*)
 LOGIC_AND, LOGIC_OR, LOGIC_XOR, LOGIC_NAND, LOGIC_NOR, LOGIC_XNOR, LOGIC_NOT = range(7)
 GATE_B_NONE, GATE_B_CIPHER, GATE_B_PLAIN = 0, 1, 2
@@ -349,6 +350,18 @@ class Context:
         _check(self._lib.hegpu_ckks_apply_galois(self._h, _ptr(ct), cs, _ptr(out), so, _ptr(key), galois_elt, depth,
                                                  batch, _ptr(ws), ws.numel() * 8,
                                                  stream if stream is not None else _stream()))
+
+    def mod_raise(self, src, s_in, out, s_out, limbs, parts=2, batch=1, stream=None):
+        """hegpu_mod_raise: src [parts][1][N] at q_0 (coefficient domain) -> out [parts][limbs][N], the centred lift"""
+        _check(self._lib.hegpu_mod_raise(self._h, _ptr(src), s_in, _ptr(out), s_out, limbs, parts, batch,
+                                         stream if stream is not None else _stream()))
+
+    def ckks_mod_raise(self, ct, cs, out, so, out_depth, batch, ws, ws_bytes=None, stream=None):
+        """hegpu_ckks_mod_raise: ct [2][1][N] at depth Q - 1 -> out [2][Q - out_depth][N], both in the NTT domain.
+        Workspace OP_CKKS_MOD_RAISE (ws_bytes: its size when ws is an address, not a tensor)"""
+        _check(self._lib.hegpu_ckks_mod_raise(self._h, _ptr(ct), cs, _ptr(out), so, out_depth, batch, _ptr(ws),
+                                              ws.numel() * 8 if ws_bytes is None else ws_bytes,
+                                              stream if stream is not None else _stream()))
 
     def ckks_rotate_hoisted(self, ct, cs, out, so, keys, galois_elts, depth, batch, ws, stream=None):
         """fast_single_hoisting_rotation_ckks: keys = list of device tensors (None where galois_elts[i] == 0)"""
@@ -1077,6 +1090,23 @@ def poly_eval_plan(basis, coeffs, level, scale, target_scale, primes, max_deg=No
     _check(lib.hegpu_poly_eval_plan_size(*args, ctypes.byref(count)))
     steps = (_lib.PolyStep * count.value)()
     _check(lib.hegpu_poly_eval_plan_fill(*args, steps, count.value))
+    last = steps[count.value - 1]
+    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+
+
+def eval_mod_plan(K, degree, double_angle, level, scale, target_scale, primes):
+    """EvalMod of CKKS bootstrapping as a plan for Context.ckks_poly_eval (host only; hegpu_eval_mod_plan_size / _fill).  The
+    input holds u in [-1, 1] with K u = I + eps, I an integer below K in magnitude; the plan evaluates the degree-`degree`
+    Chebyshev interpolant of (1 / 2 pi)^(1 / 2^r) cos(2 pi (K u - 1/4) / 2^r), r = double_angle, and then r double-angle
+    steps, which leaves sin(2 pi eps) / 2 pi at target_scale.  Returns a PolyEvalPlan like poly_eval_plan."""
+    lib = _lib.load()
+    pr = [int(p) for p in primes]
+    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    args = (int(K), int(degree), int(double_angle), int(level), float(scale), float(target_scale), arr, len(pr))
+    count = ctypes.c_int(0)
+    _check(lib.hegpu_eval_mod_plan_size(*args, ctypes.byref(count)))
+    steps = (_lib.PolyStep * count.value)()
+    _check(lib.hegpu_eval_mod_plan_fill(*args, steps, count.value))
     last = steps[count.value - 1]
     return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
 

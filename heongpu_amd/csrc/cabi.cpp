@@ -555,6 +555,41 @@ int hegpu_poly_eval_plan_fill(int basis, const double* coeffs, int n_coeffs, int
     });
 }
 
+// host only: EvalMod as a plan (poly_eval.hpp)
+static std::vector<host::PolyStep> eval_mod_plan_of(int K, int degree, int double_angle, int level, double scale,
+                                                    double target_scale, const uint64_t* primes, int n_primes)
+{
+    if (!primes || n_primes < 1) throw std::invalid_argument("eval_mod_plan: null argument");
+    return host::eval_mod_plan(K, degree, double_angle, level, scale, target_scale,
+                               std::vector<uint64_t>(primes, primes + n_primes));
+}
+
+int hegpu_eval_mod_plan_size(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                             const uint64_t* primes, int n_primes, int* n_steps)
+{
+    return guarded([&]() -> int {
+        if (!n_steps) return fail(HEGPU_E_INVALID, "eval_mod_plan_size: null argument");
+        const std::vector<host::PolyStep> plan =
+            eval_mod_plan_of(K, degree, double_angle, level, scale, target_scale, primes, n_primes);
+        *n_steps = (int) plan.size();
+        return 0;
+    });
+}
+
+int hegpu_eval_mod_plan_fill(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                             const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps)
+{
+    return guarded([&]() -> int {
+        if (!steps) return fail(HEGPU_E_INVALID, "eval_mod_plan_fill: null argument");
+        const std::vector<host::PolyStep> plan =
+            eval_mod_plan_of(K, degree, double_angle, level, scale, target_scale, primes, n_primes);
+        if (n_steps != (int) plan.size())
+            return fail(HEGPU_E_INVALID, "eval_mod_plan_fill: n_steps is not what hegpu_eval_mod_plan_size gives");
+        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
+        return 0;
+    });
+}
+
 #define NEED_CTX(ctx)                                                                      \
     if (!(ctx)) return fail(HEGPU_E_INVALID, "null context");                              \
     if (!(ctx)->c.uploaded) {                                                              \
@@ -814,7 +849,7 @@ SAME_OP(CKKS_RELIN); SAME_OP(CKKS_RESCALE); SAME_OP(CKKS_GALOIS); SAME_OP(BFV_MU
 SAME_OP(BFV_GALOIS); SAME_OP(KEYGEN_SECRET); SAME_OP(KEYGEN_PUBLIC); SAME_OP(KEYGEN_SWITCH); SAME_OP(CKKS_ENCRYPT);
 SAME_OP(BFV_ENCRYPT); SAME_OP(BFV_DECRYPT); SAME_OP(BFV_DECODE); SAME_OP(CKKS_ENCODE); SAME_OP(CKKS_DECODE);
 SAME_OP(BFV_MULTIPLY_PLAIN); SAME_OP(CKKS_ROTATE_HOISTED); SAME_OP(MPC_KEY_SHARE); SAME_OP(MPC_BFV_DECRYPT_MERGE);
-SAME_OP(MPC_REFRESH_SHARE); SAME_OP(MPC_REFRESH_MERGE); SAME_OP(CKKS_LOGIC_GATE); SAME_OP(BFV_LOGIC_GATE);
+SAME_OP(MPC_REFRESH_SHARE); SAME_OP(MPC_REFRESH_MERGE); SAME_OP(CKKS_LOGIC_GATE); SAME_OP(BFV_LOGIC_GATE); SAME_OP(CKKS_MOD_RAISE);
 #undef SAME_OP
 
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch)
@@ -925,6 +960,46 @@ int hegpu_ckks_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t cs,
     return hip_ret(op_ckks_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key, galois_elt, depth,
                                         batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_ckks_apply_galois");
+}
+
+// ---- the modulus raise.  Everything is checked on the host tables, before the context is uploaded: a refusal needs no device.
+int hegpu_mod_raise(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t out_stride,
+                    int limbs, int parts, int batch, hegpu_stream stream)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (!in || !out) return fail(HEGPU_E_INVALID, "mod_raise: null argument");
+    if (batch < 1 || batch > 65535) return fail(HEGPU_E_INVALID, "mod_raise: 1 to 65535 items per call");
+    if (parts < 1 || parts > 3) return fail(HEGPU_E_INVALID, "mod_raise: parts is 1, 2 or 3");
+    if (limbs < 1 || limbs > ctx->c.Q_size) return fail(HEGPU_E_INVALID, "mod_raise: 1 <= limbs <= Q");
+    if (spans_overlap(in, in_stride, (uint64_t) parts * ctx->c.n, out, out_stride, (uint64_t) parts * limbs * ctx->c.n, batch))
+        return fail(HEGPU_E_INVALID, "mod_raise: out must not overlap in");
+    NEED_CTX(ctx);
+    const Context& c = ctx->c;
+    return hip_ret(rns_mod_raise((const u64*) in, in_stride, (u64*) out, out_stride, c.plan_qp.mods, c.n_power, limbs, parts,
+                                 batch, (hipStream_t) stream),
+                   "hegpu_mod_raise");
+}
+
+int hegpu_ckks_mod_raise(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so, int out_depth,
+                         int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (!ct || !out || !ws) return fail(HEGPU_E_INVALID, "ckks_mod_raise: null argument");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "ckks_mod_raise: batch must be at least 1");
+    if (out_depth < 0 || out_depth >= ctx->c.Q_size) return fail(HEGPU_E_INVALID, "ckks_mod_raise: 0 <= out_depth < Q");
+    const uint64_t in_words = (uint64_t) 2 * ctx->c.n, out_words = in_words * (ctx->c.Q_size - out_depth);
+    const size_t need = ops_workspace_elems(ctx->c, OP_CKKS_MOD_RAISE, out_depth, batch) * sizeof(u64);
+    if (ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+    if (spans_overlap(ct, cs, in_words, out, so, out_words, batch))
+        return fail(HEGPU_E_INVALID, "ckks_mod_raise: out must not overlap ct");
+    if (spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), out, so, out_words, batch) ||
+        spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), ct, cs, in_words, batch))
+        return fail(HEGPU_E_INVALID, "ckks_mod_raise: the workspace must overlap neither out nor ct");
+    NEED_CTX(ctx);
+    return hip_ret(op_ckks_mod_raise(ctx->c, (const u64*) ct, cs, (u64*) out, so, out_depth, batch, (u64*) ws,
+                                     (hipStream_t) stream),
+                   "hegpu_ckks_mod_raise");
 }
 
 int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,

@@ -81,6 +81,14 @@ void Context::build_host()
         host["rescaled_half_mod"] = r_half_mod;
         host["rescaled_half"] = r_half;
         hv.rescaled_half = r_half;
+        // modulus raise (ops.cpp op_ckks_mod_raise): with half = (q_0 + 1) / 2 the mod-down load transform
+        // ((v + half) mod q_0) mod q_j - half mod q_j is the residue of the centred lift, negative from v = q_0 >> 1 on
+        {
+            vec mr;
+            hv.mod_raise_half = (primes[0] + 1) >> 1;
+            for (int j = 0; j < Q; j++) mr.push_back(hv.mod_raise_half % primes[j]);
+            host["mod_raise_half_mod"] = mr;
+        }
         // ---- decoding: CRT composition tables per level (ckks/context.cu:370-421, util.cu:772-888):
         // for l = Q - depth limbs, Mi[i] = prod_{j != i} q_j and M = prod q_j as l little-endian
         // 64-bit words, Mi_inv[i] = (Mi[i] mod q_i)^-1, upper_half_threshold = (M + 1) >> 1
@@ -672,7 +680,7 @@ hipError_t Context::upload()
         {"half_mod", &tab.half_mod}, {"factor", &tab.factor},
         {"m2_md_W0", &tab.m2_md_W0}, {"m2_md_G", &tab.m2_md_G}, {"m2_md_C", &tab.m2_md_C},
         {"rescaled_last_q_modinv", &tab.rescaled_last_q_modinv}, {"rescaled_half_mod", &tab.rescaled_half_mod},
-        {"rescaled_half", &tab.rescaled_half},
+        {"rescaled_half", &tab.rescaled_half}, {"mod_raise_half_mod", &tab.mod_raise_half_mod},
         {"base_change_matrix_Bsk", &behz.base_change_matrix_Bsk},
         {"inv_punctured_prod_mod_base_array", &behz.inv_punctured_prod_mod_base_array},
         {"base_change_matrix_m_tilde", &behz.base_change_matrix_m_tilde},

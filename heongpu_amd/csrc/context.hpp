@@ -61,6 +61,7 @@ struct DevTables {
     const int *m2_I_j, *m2_I_location;
     // CKKS (rescaled_*: empty with a single ciphertext prime, which has no rescale)
     const u64 *rescaled_last_q_modinv, *rescaled_half_mod, *rescaled_half;
+    const u64* mod_raise_half_mod; // (q_0 + 1) / 2 modulo q_j, j < Q: the modulus raise as a load transform (ops.cpp)
     const u64 *Mi, *Mi_inv, *upper_half_threshold, *decryption_modulus, *special_fft_roots_table, *special_ifft_roots_table;
     const int *new_prime_locations, *new_input_locations, *reverse_order, *mpc_refresh_order;
     // BFV
@@ -83,6 +84,7 @@ struct ContextHost {
     struct HostVals {
         u64 half = 0;                         // half[0]
         std::vector<u64> rescaled_half;       // CKKS, per depth
+        u64 mod_raise_half = 0;               // CKKS: (q_0 + 1) / 2
         std::vector<u64> new_prime_locations; // CKKS: host copy of the device table (ops.cpp: fill_int_slots)
         // BFV
         u64 Q_mod_t = 0, upper_threshold = 0, gamma = 0, mulq_inv_t = 0, mulq_inv_gamma = 0, inv_gamma = 0;

@@ -221,6 +221,8 @@ static PairWs rescale_ws(const Context& c, int depth)
     const u64 l = c.Q_size - depth;
     return {2 * (l - 1) * c.n, (2 * (l - 1) + 2 * l) * c.n};
 }
+// modulus raise: the two q_0 limbs in the coefficient domain [2][N]
+static u64 mod_raise_ws(const Context& c) { return 2 * c.n; }
 // BFV multiply over the L = Q + bsk moduli: both operands extended [4][L][N], their tensor product [3][L][N]
 static PairWs bfv_multiply_ws(const Context& c)
 {
@@ -291,6 +293,7 @@ size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
             if (c.scheme != SCHEME_CKKS) return bfv_refresh_merge_ws(c, batch).total;
             per = (u64) (c.Q_size - depth) * n;
             break;
+        case OP_CKKS_MOD_RAISE: per = mod_raise_ws(c); break;          // the same at every output depth
         case OP_CKKS_LOGIC_GATE: return gate_ws(c, false, depth, batch).total;
         case OP_BFV_LOGIC_GATE: return gate_ws(c, true, depth, batch).total;
         default: return 0;
@@ -606,6 +609,37 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
     TRY(ntt_launch(a, 2 * (l - 1) * batch, false, st));                                    // :1214
     TRY(rns_copy_limbs(ct, (u64) l * n, cs, temp2, (u64) l * n, w.per, np, l - 1, 2, batch, st)); // :1219
     return rns_moddown_stage_two(temp1, w.per, temp2, w.per, nullptr, 0, ct, cs, md, 0, batch, st); // :1225
+}
+
+// reference ckks/operator.cu:3963-4033 without its key switches (mod_up_from_q0: INTT of the two q_0 limbs, mod_raise_kernel
+// into [2][Q][N], NTT of all 2 Q limbs).  Here the lift is the load transform of the forward pass -- the mod-down's
+// "(v + half) mod q_0 mod q_j - half mod q_j" with half = (q_0 + 1) / 2 (context.cpp mod_raise_half_mod), which is the
+// residue of the centred representative -- and limb 0, whose transform would give the input back, is copied: no
+// coefficient-domain [2][L][N] is written or read.  Every degree and launch size is served this way.
+hipError_t op_ckks_mod_raise(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, int out_depth, int batch, u64* ws,
+                             hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    const u64 n = c.n, per = mod_raise_ws(c);
+    const int L = c.Q_size - out_depth, t = L - 1; // limbs of the result, of them lifted
+    TRY(rns_copy_limbs(ct, n, cs, out, (u64) L * n, so, c.n_power, 1, 2, batch, st));
+    if (t < 1) return hipSuccess;
+    NttArgs inv = c.ntt_args(0);
+    inv.in = ct; inv.out = ws; inv.mod_count = 1; inv.polys_per_item = 2;
+    inv.in_item_stride = cs; inv.out_item_stride = per;
+    NttArgs a = c.ntt_args(0);
+    a.in = ws; a.out = out + n; // digit p (part p), target slot k: limb 1 + k of part p
+    a.mod_count = t; a.mod_offset = 1; a.polys_per_item = 2 * t;
+    a.in_item_stride = per; a.out_item_stride = so;
+    a.decomp_mods = t; a.decomp_out_mul = L;
+    a.half_on = 1; a.half_src_mod = 0; a.half = c.hv.mod_raise_half; a.half_mod = c.tab.mod_raise_half_mod;
+    a.single_decomp_ok = 1; // ws -> out
+    fill_int_slots(c, a, nullptr);
+    const bool fuse_inv = c.fuse_inverse && (long) 2 * t * batch <= 65535 && ntt_decomp_uses_multi(a, 2 * t * batch);
+    if (fuse_inv) TRY(ntt_launch_inv_rows(inv, 2 * batch, st));
+    else TRY(ntt_launch(inv, 2 * batch, true, st));
+    a.src_inv = fuse_inv ? 1 : 0;
+    return ntt_launch(a, 2 * t * batch, false, st);
 }
 
 // reference ckks/operator.cu:1422-1559
@@ -1046,7 +1080,10 @@ const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, in
     if (n_steps > 4096) return "a plan of more than 4096 steps"; // degree 255, the largest the planner takes, has under 600
     if (depth < 0 || depth >= c.Q_size) return "invalid depth";
     const int top = c.Q_size - 1 - depth;
-    if (plan[n_steps - 1].kind == POLY_STEP_POWER) return "the last step is a leaf or a combination";
+    // (a product without a tail is three parts wide in its register; one with a tail -- the double-angle step that ends an
+    // EvalMod plan -- sits in the product region and its tail writes two parts)
+    if (plan[n_steps - 1].kind == POLY_STEP_POWER && plan[n_steps - 1].c == POLY_TAIL_NONE)
+        return "the last step is a leaf, a combination or a power with a tail";
     std::vector<int> level((size_t) n_steps + 1);
     std::vector<char> spent((size_t) n_steps + 1, 0); // rescaled in place by the COMBINE that consumed it
     level[0] = top;
@@ -1056,7 +1093,8 @@ const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, in
         const int dst = k + 1;
         if (s.dst != dst) return "a step does not write the register of its position";
         if (s.level < 0 || s.level > top) return "a level outside the ciphertext's";
-        if (s.rescale_after && (k != n_steps - 1 || s.kind != POLY_STEP_COMBINE)) return "only a last COMBINE step rescales its result";
+        // (the polynomial's last step; an EvalMod plan goes on from it, its register then has the sum's limbs: poly_reg_words)
+        if (s.rescale_after && s.kind != POLY_STEP_COMBINE) return "only a COMBINE step rescales its result";
         if (s.kind == POLY_STEP_POWER) {
             if (!reg_ok(s.a, dst) || !reg_ok(s.b, dst)) return "a register number out of range";
             if (s.c != POLY_TAIL_NONE && s.c != POLY_TAIL_ONE && !reg_ok(s.c, dst)) return "a register number out of range";
@@ -1094,7 +1132,7 @@ const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, in
 static u64 poly_reg_words(const Context& c, const host::PolyStep& s)
 {
     const bool product_in_place = s.kind == host::POLY_STEP_POWER && s.c == host::POLY_TAIL_NONE;
-    return (product_in_place ? (u64) 3 * (s.mul_level + 1) : (u64) 2 * (s.level + 1)) * c.n;
+    return (product_in_place ? (u64) 3 * (s.mul_level + 1) : (u64) 2 * (s.level + 1 + (s.rescale_after ? 1 : 0))) * c.n;
 }
 
 // The registers of every step but the last (which writes `out`), each a block of `batch` items; T: one three-part product

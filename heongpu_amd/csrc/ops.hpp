@@ -11,7 +11,7 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
        OP_BFV_DECRYPT = 12, OP_BFV_DECODE = 13, OP_CKKS_ENCODE = 14,
        OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17, OP_MPC_KEY_SHARE = 18,
        OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21, OP_CKKS_LOGIC_GATE = 22,
-       OP_BFV_LOGIC_GATE = 23 };
+       OP_BFV_LOGIC_GATE = 23, OP_CKKS_MOD_RAISE = 25 /* 24 stays unassigned: include/hegpu.h */ };
 
 // Words of the workspace row `op` for `batch` items at `depth`.  Every shape is stated once, by a layout function of
 // ops.cpp that this query and the sequence both read.
@@ -29,6 +29,11 @@ hipError_t op_ckks_relinearize(const Context& c, u64* ct, u64 cs, const u64* key
 hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int batch, u64* ws, hipStream_t st);
 hipError_t op_ckks_apply_galois(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* key,
                                 int galois_elt, int depth, int batch, u64* ws, hipStream_t st);
+// The modulus raise of bootstrapping (mod_up_from_q0, ckks/operator.cu:3963-4033, without its key switches): ct [2][1][N]
+// at q_0, NTT domain -> out [2][Q - out_depth][N], NTT domain, the centred lift of every coefficient.  out overlaps
+// neither ct nor ws.  Workspace OP_CKKS_MOD_RAISE.
+hipError_t op_ckks_mod_raise(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, int out_depth, int batch, u64* ws,
+                             hipStream_t st);
 hipError_t op_bfv_multiply(const Context& c, const u64* ct1, u64 s1, const u64* ct2, u64 s2, u64* out, u64 so,
                            int batch, u64* ws, hipStream_t st);
 hipError_t op_bfv_relinearize(const Context& c, u64* ct, u64 cs, const u64* key, int batch, u64* ws,

@@ -35,7 +35,7 @@ struct PolyStep {
     int32_t level; // of dst
     int32_t mul_level;      // POWER, COMBINE: the level of the product (the lower of its operands', after q's rescale)
     int32_t rescale_first;  // COMBINE: 1 = reg[a] is rescaled before the product
-    int32_t rescale_after;  // the last step only: 1 = dst is rescaled once more; level and scale are those after it
+    int32_t rescale_after;  // the polynomial's last step only: 1 = dst is rescaled once more; level and scale are those after it
     int32_t n_terms;        // LEAF: number of power terms, <= POLY_LEAF_MAX
     int32_t term_reg[POLY_LEAF_MAX];
     double scale;           // of dst
@@ -49,6 +49,19 @@ struct PolyStep {
 // a rescale at level 0), level >= the number of primes.
 std::vector<PolyStep> poly_eval_plan(int basis, const std::vector<std::complex<double>>& coeffs, int max_deg, bool lead,
                                      int level, double scale, double target_scale, const std::vector<uint64_t>& primes);
+
+// EvalMod of CKKS bootstrapping (eval_mod, ckks/operator.cu:4248-4290) as a plan the same executor runs.  The input
+// register holds u in [-1, 1] with K u = I + eps, I an integer below K in magnitude.  With c = (1 / 2 pi)^(1 / 2^r) the plan
+// evaluates p, the degree-`degree` Chebyshev interpolant (at the Chebyshev nodes, in doubles) of
+//     g(u) = c cos(2 pi (K u - 1/4) / 2^r),
+// and then r double-angle steps y <- 2 y^2 - c^(2^(i+1)), each a POWER step with a = b = the previous register,
+// POLY_TAIL_ONE and tail_const = c^(2^(i+1)) at the step's scale: y_r = sin(2 pi eps) / 2 pi.  p gets the target scale of
+// the reference's square-root chain (:4257-4265), so that the result carries target_scale (to the rounding of doubles).
+// The reference's change of variable by a constant addition (:4267-4271) is inside g.
+// std::invalid_argument: K < 1, double_angle outside [0, 8], a degree poly_eval_plan refuses, fewer levels than
+// bit_length(degree) + double_angle, a non-finite or non-positive scale.
+std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                                    const std::vector<uint64_t>& primes);
 
 } // namespace host
 } // namespace hegpu

@@ -169,6 +169,43 @@ hipError_t rns_decompose(const u64* in, u64 in_stride, u64* out, u64 out_stride,
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------- modulus raise
+// One load of the q_0 limb, `limbs` stores: (1 + limbs) W per part against the 2 limbs W of the reference's grid of one
+// thread per (coefficient, target modulus).  The coefficient is lifted to its centred representative c (v >= q_0 >> 1:
+// c = v - q_0) and |c| reduced into q_j with the forced reduction: a 60-bit q_0 is outside the Barrett domain of a
+// 30-bit q_j.  A negative c gives q_j - (|c| mod q_j), the WORD q_j when q_j divides |c| (the reference's words).
+__global__ __launch_bounds__(RNS_THREADS) void k_mod_raise(const u64* __restrict__ in, u64 in_stride,
+                                                           u64* __restrict__ out, u64 out_stride,
+                                                           const Mod* __restrict__ mods, int n_power, int limbs)
+{
+    const u64 c = coeff0();
+    const u64 q0 = mods[0].q, h = q0 >> 1;
+    const ulonglong2 x = ld2(in + in_stride * blockIdx.z + ((u64) blockIdx.y << n_power) + c);
+    u64* po = out + out_stride * blockIdx.z + (((u64) limbs * blockIdx.y) << n_power) + c;
+    st2(po, x);
+    const bool nx = x.x >= h, ny = x.y >= h;
+    const u64 ax = nx ? q0 - x.x : x.x, ay = ny ? q0 - x.y : x.y;
+    for (int j = 1; j < limbs; j++) {
+        const Mod m = mods[j];
+        ulonglong2 r;
+        r.x = reduce64(ax, m);
+        r.y = reduce64(ay, m);
+        if (nx) r.x = m.q - r.x;
+        if (ny) r.y = m.q - r.y;
+        st2(po + ((u64) j << n_power), r);
+    }
+}
+
+hipError_t rns_mod_raise(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs,
+                         int parts, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (limbs < 1 || parts < 1 || batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mod_raise, grid3(n_power, parts, batch), dim3(RNS_THREADS), 0, st, in, in_stride, out,
+                       out_stride, mods, n_power, limbs);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- partial sums of a digit-split key switch
 __global__ __launch_bounds__(RNS_THREADS) void k_sum_partials(const u64* __restrict__ buf, u64 buf_item_stride,
                                                               u64* __restrict__ out, u64 out_item_stride,

@@ -29,6 +29,13 @@ hipError_t rns_decompose(const u64* in, u64 in_stride, u64* out, u64 out_stride,
                          int n_power, int digits, int nmods, int split, int level, int batch,
                          hipStream_t st);
 
+// mod_raise_kernel (reference src/lib/kernel/bootstrapping.cu:339-376, restated: that file does not compile here): the
+// q_0 limb of each part, coefficient domain, lifted as a centred integer into q_0 .. q_{limbs-1}.  in [parts][1][N],
+// out [parts][limbs][N] per item; limb 0 is the input, limb j of a negative value q_j - (|c| mod q_j) (q_j itself
+// when that is 0).  out may not overlap in.
+hipError_t rns_mod_raise(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs,
+                         int parts, int batch, hipStream_t st);
+
 // reference switchkey.cu:61-285: out[c][y][n] = sum_i in[i][y][n]*key[i][c][kidx(y)][n].
 // key strides use key_limbs (= Q' at depth 0); kidx(y) = (y < split) ? y : y + level
 // (method I leveled: split = l, level = depth maps row l to the P limb; method II,

@@ -185,6 +185,14 @@ int hegpu_cross_multiplication(hegpu_context* ctx, int table_set, const uint64_t
 int hegpu_cipher_broadcast(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, uint64_t* out,
                            uint64_t out_stride, int digits, int nmods, int split, int level, int batch,
                            hegpu_stream stream);
+/* mod_raise_kernel (src/lib/kernel/bootstrapping.cu:339-376; restated, not compiled against): the q_0 limb of each part,
+ * coefficient domain, lifted to its centred representative c (v >= q_0 >> 1: c = v - q_0) and written into q_0 ..
+ * q_{limbs-1}.  in [parts][1][N], out [parts][limbs][N] per item; limb 0 is the input word, limb j > 0 is |c| mod q_j for
+ * c >= 0 and q_j - (|c| mod q_j) for c < 0 -- the word q_j itself when q_j divides |c|, as the reference writes it.
+ * HEGPU_E_INVALID, out untouched: a NULL pointer, batch < 1 or > 65535, parts outside [1, 3], limbs outside [1, Q], out
+ * overlapping in. */
+int hegpu_mod_raise(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t out_stride,
+                    int limbs, int parts, int batch, hegpu_stream stream);
 /* src/lib/kernel/switchkey.cu:61-398: out[c][y][n] = sum_i in[i][y][n] * key[i][c][kidx(y)][n],
  * kidx(y) = y < split ? y : y + level (non-leveled: split = nmods, level = 0;
  * method I leveled: split = l, level = depth; method II leveled: same) */
@@ -273,7 +281,9 @@ enum {
     HEGPU_OP_MPC_REFRESH_SHARE = 20,     /* hegpu_mpc_*_refresh_share: 0 bytes, the share is built in place */
     HEGPU_OP_MPC_REFRESH_MERGE = 21,     /* hegpu_mpc_*_refresh_merge; per item: CKKS (Q - depth) N words, BFV (Q + 1) N */
     HEGPU_OP_CKKS_LOGIC_GATE = 22,       /* hegpu_ckks_logic_gate: a three-part product per item + the larger of RELIN, RESCALE */
-    HEGPU_OP_BFV_LOGIC_GATE = 23         /* hegpu_bfv_logic_gate: the same + the largest of MULTIPLY, RELIN, MULTIPLY_PLAIN */
+    HEGPU_OP_BFV_LOGIC_GATE = 23,        /* hegpu_bfv_logic_gate: the same + the largest of MULTIPLY, RELIN, MULTIPLY_PLAIN */
+    /* 24 stays unassigned: tests/test_cabi_logic.py holds it as the number no row has (0 bytes) */
+    HEGPU_OP_CKKS_MOD_RAISE = 25         /* hegpu_ckks_mod_raise: 2 N words per item at every depth */
 };
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch);
 
@@ -290,6 +300,14 @@ int hegpu_ckks_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_st
 int hegpu_ckks_relinearize_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t ct_stride,
                                    const uint64_t* relin_key, int depth, int batch, void* ws, size_t ws_bytes,
                                    hegpu_stream stream);
+/* The modulus raise of bootstrapping (mod_up_from_q0, ckks/operator.cu:3963-4033, without its two key switches): ct
+ * [2][1][N] per item, a ciphertext at depth Q - 1 (NTT domain) -> out [2][Q - out_depth][N], NTT domain: every coefficient
+ * of the q_0 limbs lifted as hegpu_mod_raise lifts it.  One inverse transform of the two limbs, one forward transform whose
+ * first load is the lift, one copy of limb 0.  Canonical residues, bit-identical to hegpu_ntt (inverse) ->
+ * hegpu_mod_raise -> hegpu_ntt (forward).  HEGPU_E_INVALID before anything is queued: a NULL pointer, batch < 1, out_depth
+ * outside [0, Q - 1], a workspace below HEGPU_OP_CKKS_MOD_RAISE, out overlapping ct, the workspace overlapping either. */
+int hegpu_ckks_mod_raise(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out, uint64_t out_stride,
+                         int out_depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
 /* rescale_inplace_ckks_leveled (ckks/operator.cu:1156-1244):
  * ct [2][l][N] -> [2][l-1][N] in place (caller then uses depth+1) */
 int hegpu_ckks_rescale_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t ct_stride, int depth, int batch,
@@ -424,7 +442,8 @@ int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0
  *   LEAF     dst = w0 + sum_i w[i] * reg[term_reg[i]] over level + 1 limbs; w[i] = round(c_i * (leaf_scale / scale_i)),
  *            w0 = round(c_0 * leaf_scale), real and imaginary part separately; terms with w[i] == 0 are left out
  *   COMBINE  dst = reg[a] * reg[b] + reg[c]: reg[a] rescaled first if rescale_first, product at mul_level, relinearized,
- *            sum at the lower of mul_level and reg[c]'s level; rescale_after (last step only): the sum is rescaled
+ *            sum at the lower of mul_level and reg[c]'s level; rescale_after: the sum is rescaled (the planner sets it on
+ *            the polynomial's last step; an EvalMod plan goes on from there)
  * HEGPU_E_INVALID, outputs untouched: degree < 2, a leaf of more than 15 power terms (degree > 255), too few levels for
  * the polynomial's depth, a non-finite coefficient or scale, max_deg < degree, n_steps not what _size gives. */
 enum { HEGPU_POLY_MONOMIAL = 0, HEGPU_POLY_CHEBYSHEV = 1 };
@@ -435,7 +454,7 @@ typedef struct hegpu_poly_step {
     int32_t level;         /* of dst */
     int32_t mul_level;     /* POWER, COMBINE */
     int32_t rescale_first; /* COMBINE */
-    int32_t rescale_after; /* last step */
+    int32_t rescale_after; /* COMBINE: the polynomial's last step */
     int32_t n_terms;       /* LEAF, <= 15 */
     int32_t term_reg[15];
     double scale;          /* of dst */
@@ -447,6 +466,20 @@ int hegpu_poly_eval_plan_size(int basis, const double* coeffs, int n_coeffs, int
                               double target_scale, const uint64_t* primes, int n_primes, int* n_steps);
 int hegpu_poly_eval_plan_fill(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
                               double target_scale, const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps);
+/* EVALMOD of CKKS bootstrapping (eval_mod, host/ckks/operator.cu:4248-4290) as a plan for the same sequence; host only.
+ * The input holds u in [-1, 1] with K u = I + eps, I an integer, |I| < K.  With c = (1 / 2 pi)^(1 / 2^r), r = double_angle,
+ * the plan is the Chebyshev plan of p, the degree-`degree` interpolant (at the Chebyshev nodes, in doubles) of
+ * g(u) = c cos(2 pi (K u - 1/4) / 2^r), followed by r POWER steps y <- 2 y^2 - c^(2^(i+1)) (a = b = the previous register,
+ * HEGPU_POLY_TAIL_ONE, tail_const = c^(2^(i+1)) at the step's scale): the result is sin(2 pi eps) / 2 pi at target_scale
+ * (to the rounding of doubles), bit_length(degree) + r levels below `level`.  p carries the target scale of the reference's
+ * square-root chain (:4257-4265); its change of variable (:4267-4271) is inside g, its q_diff corrections have no
+ * counterpart (scales are exact labels here).  HEGPU_E_INVALID, outputs untouched: K < 1, double_angle outside [0, 8], a
+ * degree hegpu_poly_eval_plan_* refuses, too few levels, a scale that is not positive and finite, n_steps not what _size
+ * gives. */
+int hegpu_eval_mod_plan_size(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                             const uint64_t* primes, int n_primes, int* n_steps);
+int hegpu_eval_mod_plan_fill(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                             const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps);
 /* KERNELS.  weighted_sum: out[p] = (p == 0 ? w0 : 0) + sum_k w_k * terms[k][p] mod q_j over the first `limbs` limbs, p = 0, 1.
  * terms / term_strides / term_limbs / weights are HOST arrays of count <= 15 entries: term k is a DEVICE ciphertext
  * [2][term_limbs[k]][N] per item (term_limbs[k] >= limbs; read in place, its part 1 term_limbs[k] * N words after part 0),
@@ -472,7 +505,8 @@ int hegpu_ckks_double_sub(hegpu_context* ctx, const uint64_t* a, uint64_t a_stri
  * Q - 1 - level and the scale of the plan's last step.  Bit-identical to the same plan executed with the single entries.
  * HEGPU_E_INVALID before anything is queued: a workspace below hegpu_ckks_poly_eval_workspace_bytes (0 for a plan it cannot
  * size), out overlapping ct, a register or level number out of range, more than 4096 steps, a tail constant that is not
- * finite or not below 3.4e38, a non-finite weight, null pointers, batch < 1. */
+ * finite or not below 3.4e38, a non-finite weight, null pointers, batch < 1, a plan that ends with a POWER step without a
+ * tail (its register is three parts wide; one with a tail, as an EvalMod plan ends, writes out). */
 size_t hegpu_ckks_poly_eval_workspace_bytes(const hegpu_context* ctx, const hegpu_poly_step* plan, int n_steps, int depth,
                                             int batch);
 int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out, uint64_t out_stride,
