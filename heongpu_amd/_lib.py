@@ -40,6 +40,25 @@ class PolyStep(ctypes.Structure):
                 ("w0", ctypes.c_double * 2), ("w", (ctypes.c_double * 2) * 15)]
 
 
+class BootstrapConfig(ctypes.Structure):
+    """hegpu_bootstrap_config: the inputs of hegpu_bootstrap_plan_fill"""
+    _fields_ = [("scale", ctypes.c_double), ("message_ratio", ctypes.c_double), ("K", ctypes.c_int32),
+                ("sine_degree", ctypes.c_int32), ("double_angle", ctypes.c_int32), ("cts_level", ctypes.c_int32),
+                ("cts_pieces", ctypes.c_int32), ("eval_level", ctypes.c_int32), ("stc_level", ctypes.c_int32),
+                ("stc_pieces", ctypes.c_int32)]
+
+
+class BootstrapPlan(ctypes.Structure):
+    """hegpu_bootstrap_plan: every level and scale label of the CKKS refresh"""
+    _fields_ = [("k1", ctypes.c_uint64), ("cts_level", ctypes.c_int32), ("cts_pieces", ctypes.c_int32),
+                ("eval_level", ctypes.c_int32), ("stc_level", ctypes.c_int32), ("stc_pieces", ctypes.c_int32),
+                ("out_level", ctypes.c_int32), ("K", ctypes.c_int32), ("sine_degree", ctypes.c_int32),
+                ("double_angle", ctypes.c_int32), ("reserved", ctypes.c_int32), ("raise_scale", ctypes.c_double),
+                ("cts_scale", ctypes.c_double * 5), ("cts_label", ctypes.c_double * 5), ("eval_in_scale", ctypes.c_double),
+                ("eval_target_scale", ctypes.c_double), ("eval_out_scale", ctypes.c_double), ("stc_in_scale", ctypes.c_double),
+                ("stc_scale", ctypes.c_double * 5), ("stc_label", ctypes.c_double * 5), ("out_scale", ctypes.c_double)]
+
+
 # (name, restype, argtypes) -- must list EVERY symbol of include/hegpu.h
 SIGNATURES = [
     ("hegpu_last_error", ctypes.c_char_p, []),
@@ -141,6 +160,15 @@ SIGNATURES = [
      [voidp, u64p, u64, u64p, u64p, u64, ctypes.POINTER(LinearFactor), c_int, u64p, c_int, c_int, voidp, c_size_t, voidp]),
     ("hegpu_ckks_slot_to_coeff", c_int,
      [voidp, u64p, u64, u64p, u64, u64p, u64, ctypes.POINTER(LinearFactor), c_int, c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_bootstrap_plan_fill", c_int,
+     [ctypes.POINTER(BootstrapConfig), ctypes.POINTER(u64), c_int, ctypes.POINTER(BootstrapPlan)]),
+    ("hegpu_ckks_bootstrap_workspace_bytes", c_size_t,
+     [voidp, ctypes.POINTER(BootstrapPlan), ctypes.POINTER(PolyStep), c_int, ctypes.POINTER(LinearFactor), c_int,
+      ctypes.POINTER(LinearFactor), c_int, c_int, c_int]),
+    ("hegpu_ckks_bootstrap", c_int,
+     [voidp, u64p, u64, u64p, u64, ctypes.POINTER(BootstrapPlan), ctypes.POINTER(PolyStep), c_int,
+      ctypes.POINTER(LinearFactor), c_int, ctypes.POINTER(LinearFactor), c_int, u64p, u64p, u64p, u64p, c_int, voidp,
+      c_size_t, voidp]),
     ("hegpu_ckks_gate_combine", c_int,
      [voidp, c_int, u64p, u64, c_int, u64p, c_int, u64, c_int, u64p, u64, c_int, ctypes.c_double, u64p, u64, c_int, c_int,
       voidp]),

@@ -27,6 +27,7 @@ MPC_PUBLIC_KEY, MPC_GALOIS_KEY, MPC_RELIN_ROUND1 = 0, 1, 2
 TABLES_PLAIN = 2
 OP_CKKS_LOGIC_GATE, OP_BFV_LOGIC_GATE = 22, 23
 OP_CKKS_MOD_RAISE = 25  # 24 stays unassigned
+OP_CKKS_BOOTSTRAP = 26  # the head of the refresh's workspace; the whole: Context.bootstrap_workspace_bytes
 # the gates of the BFV / CKKS logic layer (the TFHE gates keep their own numbering: GATE_*)
 LOGIC_AND, LOGIC_OR, LOGIC_XOR, LOGIC_NAND, LOGIC_NOR, LOGIC_XNOR, LOGIC_NOT = range(7)
 GATE_B_NONE, GATE_B_CIPHER, GATE_B_PLAIN = 0, 1, 2
@@ -491,6 +492,64 @@ class Context:
         _check(self._lib.hegpu_ckks_slot_to_coeff(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, arr, len(factors),
                                                   depth, batch, _ptr(ws), ws.numel() * 8,
                                                   stream if stream is not None else _stream()))
+
+    def bootstrap_workspace_bytes(self, plan, cts, stc, switch_keys, batch):
+        """hegpu_ckks_bootstrap_workspace_bytes; plan: a BootstrapPlan (bootstrap_plan), cts / stc as for linear_factors"""
+        a, _ka = self.linear_factors(cts)
+        b, _kb = self.linear_factors(stc)
+        return int(self._lib.hegpu_ckks_bootstrap_workspace_bytes(self._h, ctypes.byref(plan.c), plan.eval_mod.steps,
+                                                                  len(plan.eval_mod.steps), a, len(cts), b, len(stc),
+                                                                  int(bool(switch_keys)), batch))
+
+    def ckks_bootstrap(self, ct, cs, out, so, plan, cts, stc, conj_key, relin_key, batch, ws, swk_dense_to_sparse=None,
+                       swk_sparse_to_dense=None, stream=None):
+        """hegpu_ckks_bootstrap: ct [2][1][N] per item at q_0 -> out [2][plan.out_level + 1][N] at plan.out_scale (room for
+        one limb more per part on the way).  cts / stc: as for linear_factors (bootstrap_factors builds them)"""
+        a, _ka = self.linear_factors(cts)
+        b, _kb = self.linear_factors(stc)
+        _check(self._lib.hegpu_ckks_bootstrap(self._h, _ptr(ct), cs, _ptr(out), so, ctypes.byref(plan.c), plan.eval_mod.steps,
+                                              len(plan.eval_mod.steps), a, len(cts), b, len(stc), _ptr(conj_key), _ptr(relin_key),
+                                              _ptr(swk_dense_to_sparse), _ptr(swk_sparse_to_dense), batch, _ptr(ws),
+                                              ws.numel() * 8 if ws is not None else 0,
+                                              stream if stream is not None else _stream()))
+
+    def bootstrap_factors(self, plan, galois_key, encode=None):
+        """The two factor lists of Context.ckks_bootstrap from a BootstrapPlan: the factorisation of the special FFT
+        (encoding_transform_factors), each factor's baby-step/giant-step plan (linear_transform_plan) and its diagonals
+        encoded at the level and scale the plan gives them.  galois_key(elt) -> device key of a Galois element;
+        encode(values, scale, limbs) -> packed residues [limbs][N] of one diagonal (default: ckks_encode_ex mode 1).
+        Returns (cts, stc, galois_elts): the lists and every element used, the conjugation 2N - 1 included."""
+        import torch
+        n, slots = self.n, self.n // 2
+        if encode is None:
+            def encode(values, scale, limbs):
+                return self.ckks_encode_ex(1, torch.from_numpy(np.ascontiguousarray(values)).cuda(), scale)[:limbs * n]
+        elts = set()
+
+        def key(shift):
+            if not shift:
+                return None, 0
+            e = steps_to_galois_elt(shift, n, 5)
+            elts.add(e)
+            return galois_key(e), e
+
+        def side(inverse, pieces, first_level, scales):
+            out = []
+            for f, g in enumerate(encoding_transform_factors(n, inverse, pieces)):
+                lp = linear_transform_plan(g.offsets, slots, stride=g.stride)
+                limbs = first_level - f + 1
+                order = np.argsort([k % slots for k in g.offsets])  # the plan numbers the diagonals by k mod slots
+                packed = torch.cat([encode(np.roll(g.diagonals[order[p]], -lp.pre_rotation[p]), scales[f], limbs)
+                                    for p in range(len(order))])
+                baby, giant = [key(s) for s in lp.baby_shifts], [key(s) for s in lp.giant_shifts]
+                out.append((packed, len(order), lp.index, [k for k, _ in baby], [e for _, e in baby], [k for k, _ in giant],
+                            [e for _, e in giant]))
+            return out
+
+        cts = side(True, plan.cts_pieces, plan.cts_level, plan.cts_scale)
+        stc = side(False, plan.stc_pieces, plan.stc_level - 1, plan.stc_scale)
+        elts.add(2 * n - 1)
+        return cts, stc, sorted(elts)
 
     def bfv_multiply(self, ct1, s1, ct2, s2, out, so, batch, ws, stream=None):
         _check(self._lib.hegpu_bfv_multiply(self._h, _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws),
@@ -1109,6 +1168,37 @@ def eval_mod_plan(K, degree, double_angle, level, scale, target_scale, primes):
     _check(lib.hegpu_eval_mod_plan_fill(*args, steps, count.value))
     last = steps[count.value - 1]
     return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+
+
+class BootstrapPlan:
+    """The plan of the CKKS refresh (bootstrap_plan): c is the hegpu_bootstrap_plan, eval_mod the EvalMod PolyEvalPlan it
+    names; the other attributes are c's fields, arrays cut to their piece counts."""
+
+    def __init__(self, c, eval_mod):
+        self.c, self.eval_mod = c, eval_mod
+        for name, _t in c._fields_:
+            setattr(self, name, getattr(c, name))
+        self.k1 = int(c.k1)
+        self.cts_scale, self.cts_label = list(c.cts_scale)[:c.cts_pieces], list(c.cts_label)[:c.cts_pieces]
+        self.stc_scale, self.stc_label = list(c.stc_scale)[:c.stc_pieces], list(c.stc_label)[:c.stc_pieces]
+
+
+def bootstrap_plan(primes, scale, cts_level, cts_pieces=3, stc_pieces=3, message_ratio=256.0, K=16, sine_degree=30,
+                   double_angle=3, eval_level=-1, stc_level=-1):
+    """Every level and scale label of the CKKS refresh (host only; hegpu_bootstrap_plan_fill) and the EvalMod plan that goes
+    with it.  primes: q_0 ...; scale: of the ciphertext to refresh; cts_level: the level the modulus raise goes to.  The
+    defaults are the reference's EvalModConfig(level_start).  Returns a BootstrapPlan: k1 (the integer the q_0 limbs are
+    multiplied by), raise_scale, cts_scale / stc_scale (what each factor's diagonals are encoded at), eval_level, stc_level,
+    out_level, out_scale, eval_mod."""
+    lib = _lib.load()
+    pr = [int(p) for p in primes]
+    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    cfg = _lib.BootstrapConfig(float(scale), float(message_ratio), int(K), int(sine_degree), int(double_angle), int(cts_level),
+                               int(cts_pieces), int(eval_level), int(stc_level), int(stc_pieces))
+    c = _lib.BootstrapPlan()
+    _check(lib.hegpu_bootstrap_plan_fill(ctypes.byref(cfg), arr, len(pr), ctypes.byref(c)))
+    return BootstrapPlan(c, eval_mod_plan(c.K, c.sine_degree, c.double_angle, c.eval_level, c.eval_in_scale,
+                                          c.eval_target_scale, pr))
 
 
 def steps_to_galois_elt(steps, n, group_order):

@@ -1,0 +1,61 @@
+// bootstrap_plan.hpp -- host only: every scale label of the CKKS refresh (reference
+// generate_bootstrapping_params_v2 / regular_bootstrapping_v2, ckks/operator.cu:6906-7000, :7147-7224).  No device, no
+// context: integers and FP64 on the host.  A level is the index of a ciphertext's last prime, a scale the exact label a
+// ciphertext carries (as in poly_eval.hpp); the plan states what the sequence op_ckks_bootstrap does at which level and
+// which scale the diagonals of every linear factor are encoded at.
+//
+//   input  [2][1][N] at q_0, scale D, coefficients a               integer D a + e
+//   x k1   k1 = max(1, round(q_0 / (ratio D))), D' = k1 D           D' a + e',  eps = D' a / q_0
+//   raise  to cts_level, labelled q_0 K                             u = (I + eps) / K in [-1, 1]
+//   CoeffToSlot, factor f encoded at cts_scale[f]                   label cts_label[f] after its rescale; the last is the
+//          = (S / (q_0 K))^(1/P) q_(cts_level - f), S = q_(eval_level)    sine scale S to the rounding of doubles
+//   split  drops one limb, label unchanged                          level eval_level
+//   EvalMod plan (eval_level, eval_in_scale, eval_target_scale = S) sin(2 pi eps) / 2 pi at eval_out_scale, stc_level
+//   relabel eval_out_scale D' / q_0 = stc_in_scale                  the value is (rho / 2 pi) sin(2 pi a / rho), rho = q_0 / D'
+//   merge  drops one limb; SlotToCoeff, factor g encoded at stc_scale[g]  label D at out_level
+//          = (D / stc_in_scale)^(1/P) q_(stc_level - 1 - g)
+#pragma once
+#include <cstdint>
+#include <vector>
+
+namespace hegpu {
+namespace host {
+
+constexpr int BOOTSTRAP_MAX_PIECES = 5; // the factorisation of the special FFT has 2 .. 5 pieces (encoding_transform.hpp)
+
+// The layouts are the C ABI's hegpu_bootstrap_config / hegpu_bootstrap_plan (include/hegpu.h), field for field.
+struct BootstrapConfig {
+    double scale;         // D, the caller's scale
+    double message_ratio; // q_0 / D' aimed at (EvalModConfig::message_ratio_, default 256)
+    int32_t K;            // the raise's overflow I stays below K in magnitude (EvalModConfig::K_, default 16)
+    int32_t sine_degree;  // EvalModConfig::sine_deg_, default 30
+    int32_t double_angle; // EvalModConfig::double_angle_, default 3
+    int32_t cts_level;    // EncodingMatrixConfig::level_start_ of CoeffToSlot: the level the raise goes to
+    int32_t cts_pieces;
+    int32_t eval_level;   // EvalModConfig::level_start_
+    int32_t stc_level;    // EncodingMatrixConfig::level_start_ of SlotToCoeff (the merge drops to stc_level - 1)
+    int32_t stc_pieces;
+};
+
+struct BootstrapPlan {
+    uint64_t k1;
+    int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces, out_level;
+    int32_t K, sine_degree, double_angle;
+    int32_t reserved;
+    double raise_scale;                      // q_0 K
+    double cts_scale[BOOTSTRAP_MAX_PIECES];  // the scale factor f's diagonals are encoded at (level cts_level - f)
+    double cts_label[BOOTSTRAP_MAX_PIECES];  // the ciphertext's label after factor f and its rescale
+    double eval_in_scale, eval_target_scale, eval_out_scale;
+    double stc_in_scale;                     // the relabelled result of EvalMod
+    double stc_scale[BOOTSTRAP_MAX_PIECES];  // factor g's diagonals (level stc_level - 1 - g)
+    double stc_label[BOOTSTRAP_MAX_PIECES];
+    double out_scale;                        // D to the rounding of doubles
+};
+
+// std::invalid_argument: fewer levels than P_cts + 1 + bit_length(degree) + r + 1 + P_stc and one limb left, start levels
+// that do not follow from one another, K < 1, ratio D > q_0, a scale or ratio that is not positive and finite, a piece
+// count outside [2, 5], what eval_mod_plan refuses.
+BootstrapPlan bootstrap_plan(const BootstrapConfig& cfg, const std::vector<uint64_t>& primes);
+
+} // namespace host
+} // namespace hegpu

@@ -28,6 +28,7 @@
 #ifdef HEGPU_FP_AUDIT_HEADER
 #include "encoding_transform.cpp"
 #include "poly_eval.cpp"
+#include "bootstrap_plan.cpp"
 #endif
 
 using namespace hegpu;
@@ -590,6 +591,25 @@ int hegpu_eval_mod_plan_fill(int K, int degree, int double_angle, int level, dou
     });
 }
 
+// host only: the scale labels of the CKKS refresh (bootstrap_plan.hpp)
+static_assert(sizeof(hegpu_bootstrap_config) == sizeof(host::BootstrapConfig) && sizeof(hegpu_bootstrap_plan) == sizeof(host::BootstrapPlan) &&
+                  offsetof(hegpu_bootstrap_config, cts_level) == offsetof(host::BootstrapConfig, cts_level) &&
+                  offsetof(hegpu_bootstrap_plan, raise_scale) == offsetof(host::BootstrapPlan, raise_scale) &&
+                  offsetof(hegpu_bootstrap_plan, eval_in_scale) == offsetof(host::BootstrapPlan, eval_in_scale) &&
+                  offsetof(hegpu_bootstrap_plan, out_scale) == offsetof(host::BootstrapPlan, out_scale),
+              "hegpu_bootstrap_config / _plan are host::BootstrapConfig / BootstrapPlan");
+int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64_t* primes, int n_primes, hegpu_bootstrap_plan* plan)
+{
+    return guarded([&]() -> int {
+        if (!config || !primes || !plan || n_primes < 1) return fail(HEGPU_E_INVALID, "bootstrap_plan_fill: null argument");
+        host::BootstrapConfig cfg;
+        std::memcpy(&cfg, config, sizeof(cfg));
+        const host::BootstrapPlan pl = host::bootstrap_plan(cfg, std::vector<uint64_t>(primes, primes + n_primes));
+        std::memcpy(plan, &pl, sizeof(pl));
+        return 0;
+    });
+}
+
 #define NEED_CTX(ctx)                                                                      \
     if (!(ctx)) return fail(HEGPU_E_INVALID, "null context");                              \
     if (!(ctx)->c.uploaded) {                                                              \
@@ -850,6 +870,7 @@ SAME_OP(BFV_GALOIS); SAME_OP(KEYGEN_SECRET); SAME_OP(KEYGEN_PUBLIC); SAME_OP(KEY
 SAME_OP(BFV_ENCRYPT); SAME_OP(BFV_DECRYPT); SAME_OP(BFV_DECODE); SAME_OP(CKKS_ENCODE); SAME_OP(CKKS_DECODE);
 SAME_OP(BFV_MULTIPLY_PLAIN); SAME_OP(CKKS_ROTATE_HOISTED); SAME_OP(MPC_KEY_SHARE); SAME_OP(MPC_BFV_DECRYPT_MERGE);
 SAME_OP(MPC_REFRESH_SHARE); SAME_OP(MPC_REFRESH_MERGE); SAME_OP(CKKS_LOGIC_GATE); SAME_OP(BFV_LOGIC_GATE); SAME_OP(CKKS_MOD_RAISE);
+SAME_OP(CKKS_BOOTSTRAP);
 #undef SAME_OP
 
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch)
@@ -1343,6 +1364,86 @@ int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0
                                              factors_of(factors, count).data(), count, depth, batch, (u64*) ws,
                                              (hipStream_t) stream),
                        "hegpu_ckks_slot_to_coeff");
+    });
+}
+
+// ---- the CKKS refresh.  Everything is checked on the host tables, before the context is uploaded: a refusal needs no device.
+static int bootstrap_check(const hegpu_context* ctx, const hegpu_bootstrap_plan* plan, const hegpu_poly_step* eval_mod,
+                           int n_steps, const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc,
+                           int stc_count, int batch)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (!plan || !eval_mod || !cts || !stc) return fail(HEGPU_E_INVALID, "bootstrap: null argument");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "bootstrap: batch must be at least 1");
+    if (4 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "bootstrap: at most 16383 items per call");
+    host::BootstrapPlan p;
+    std::memcpy(&p, plan, sizeof(p));
+    if (const char* why = ops_bootstrap_check(ctx->c, p, reinterpret_cast<const host::PolyStep*>(eval_mod), n_steps))
+        return fail(HEGPU_E_INVALID, std::string("bootstrap: ") + why);
+    if (cts_count != p.cts_pieces || stc_count != p.stc_pieces)
+        return fail(HEGPU_E_INVALID, "bootstrap: as many factors as the plan has pieces");
+    const int Q = ctx->c.Q_size;
+    if (int r = factors_check(ctx, cts, p.cts_pieces, Q - 1 - p.cts_level, "bootstrap (CoeffToSlot)")) return r;
+    if (int r = factors_check(ctx, stc, p.stc_pieces, Q - 1 - p.stc_level, "bootstrap (SlotToCoeff)")) return r;
+    return 0;
+}
+
+size_t hegpu_ckks_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_bootstrap_plan* plan,
+                                            const hegpu_poly_step* eval_mod, int n_steps, const hegpu_linear_factor* cts,
+                                            int cts_count, const hegpu_linear_factor* stc, int stc_count, int switch_keys,
+                                            int batch)
+{
+    size_t bytes = 0;
+    (void) guarded([&]() -> int { // no exception may cross the C boundary
+        if (bootstrap_check(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count, batch)) return 0;
+        host::BootstrapPlan p;
+        std::memcpy(&p, plan, sizeof(p));
+        bytes = ops_bootstrap_workspace_elems(ctx->c, p, reinterpret_cast<const host::PolyStep*>(eval_mod), n_steps,
+                                              factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
+                                              switch_keys != 0, batch) * sizeof(u64);
+        return 0;
+    });
+    return bytes;
+}
+
+int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
+                         const hegpu_bootstrap_plan* plan, const hegpu_poly_step* eval_mod, int n_steps,
+                         const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc, int stc_count,
+                         const uint64_t* conj_key, const uint64_t* relin_key, const uint64_t* swk_dense_to_sparse, const uint64_t* swk_sparse_to_dense,
+                         int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
+    return guarded([&]() -> int {
+        if (int r = bootstrap_check(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count, batch)) return r;
+        if (!ct || !out || !conj_key || !relin_key || !ws) return fail(HEGPU_E_INVALID, "bootstrap: null argument");
+        if (!swk_dense_to_sparse != !swk_sparse_to_dense)
+            return fail(HEGPU_E_INVALID, "bootstrap: both switch keys (dense to sparse, sparse to dense) or neither");
+        host::BootstrapPlan p;
+        std::memcpy(&p, plan, sizeof(p));
+        const host::PolyStep* steps = reinterpret_cast<const host::PolyStep*>(eval_mod);
+        for (int k = 0; k < n_steps; k++) {
+            if (steps[k].kind != host::POLY_STEP_LEAF) continue;
+            for (int i = 0; i <= steps[k].n_terms; i++) {
+                const double* w = i < steps[k].n_terms ? steps[k].w[i] : steps[k].w0;
+                if (!std::isfinite(w[0]) || !std::isfinite(w[1])) return fail(HEGPU_E_INVALID, "bootstrap: a weight is not a finite number");
+            }
+        }
+        const uint64_t in_words = (uint64_t) 2 * ctx->c.n, out_words = in_words * (p.out_level + 2); // before the last rescale
+        if (batch > 1 && so < out_words) return fail(HEGPU_E_INVALID, "bootstrap: out_stride too small");
+        const size_t need = hegpu_ckks_bootstrap_workspace_bytes(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count,
+                                                                 swk_dense_to_sparse != nullptr, batch);
+        if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+        if (spans_overlap(ct, cs, in_words, out, so, out_words, batch))
+            return fail(HEGPU_E_INVALID, "bootstrap: out must not overlap ct");
+        if (spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), out, so, out_words, batch) ||
+            spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), ct, cs, in_words, batch))
+            return fail(HEGPU_E_INVALID, "bootstrap: the workspace must overlap neither out nor ct");
+        NEED_CTX(ctx);
+        return hip_ret(op_ckks_bootstrap(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, steps, n_steps,
+                                         factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
+                                         (const u64*) conj_key, (const u64*) relin_key, (const u64*) swk_dense_to_sparse,
+                                         (const u64*) swk_sparse_to_dense, batch, (u64*) ws, (hipStream_t) stream),
+                       "hegpu_ckks_bootstrap");
     });
 }
 

@@ -294,6 +294,7 @@ size_t ops_workspace_elems(const Context& c, int op, int depth, int batch)
             per = (u64) (c.Q_size - depth) * n;
             break;
         case OP_CKKS_MOD_RAISE: per = mod_raise_ws(c); break;          // the same at every output depth
+        case OP_CKKS_BOOTSTRAP: per = 3 * mod_raise_ws(c); break;      // the head of the refresh's workspace (bootstrap_head_ws)
         case OP_CKKS_LOGIC_GATE: return gate_ws(c, false, depth, batch).total;
         case OP_BFV_LOGIC_GATE: return gate_ws(c, true, depth, batch).total;
         default: return 0;
@@ -616,17 +617,21 @@ hipError_t op_ckks_rescale(const Context& c, u64* ct, u64 cs, int depth, int bat
 // "(v + half) mod q_0 mod q_j - half mod q_j" with half = (q_0 + 1) / 2 (context.cpp mod_raise_half_mod), which is the
 // residue of the centred representative -- and limb 0, whose transform would give the input back, is copied: no
 // coefficient-domain [2][L][N] is written or read.  Every degree and launch size is served this way.
-hipError_t op_ckks_mod_raise(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, int out_depth, int batch, u64* ws,
-                             hipStream_t st)
+// k1 > 1 (the refresh's pre-multiplier, k1 < q_0): the raise of k1 * ct.  The copy of limb 0 becomes rns_scale_q0, which
+// leaves k1 v mod q_0 in the workspace too; the inverse transform then runs there in place.  k1 == 1: the launches below
+// are op_ckks_mod_raise's.
+static hipError_t mod_raise_scaled(const Context& c, const u64* ct, u64 cs, u64 k1, u64* out, u64 so, int out_depth,
+                                   int batch, u64* ws, hipStream_t st)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     const u64 n = c.n, per = mod_raise_ws(c);
     const int L = c.Q_size - out_depth, t = L - 1; // limbs of the result, of them lifted
-    TRY(rns_copy_limbs(ct, n, cs, out, (u64) L * n, so, c.n_power, 1, 2, batch, st));
+    if (k1 == 1) TRY(rns_copy_limbs(ct, n, cs, out, (u64) L * n, so, c.n_power, 1, 2, batch, st));
+    else TRY(rns_scale_q0(ct, cs, k1, out, (u64) L * n, so, t < 1 ? nullptr : ws, per, c.plan_qp.mods, c.n_power, batch, st));
     if (t < 1) return hipSuccess;
     NttArgs inv = c.ntt_args(0);
-    inv.in = ct; inv.out = ws; inv.mod_count = 1; inv.polys_per_item = 2;
-    inv.in_item_stride = cs; inv.out_item_stride = per;
+    inv.in = k1 == 1 ? ct : ws; inv.out = ws; inv.mod_count = 1; inv.polys_per_item = 2;
+    inv.in_item_stride = k1 == 1 ? cs : per; inv.out_item_stride = per;
     NttArgs a = c.ntt_args(0);
     a.in = ws; a.out = out + n; // digit p (part p), target slot k: limb 1 + k of part p
     a.mod_count = t; a.mod_offset = 1; a.polys_per_item = 2 * t;
@@ -640,6 +645,12 @@ hipError_t op_ckks_mod_raise(const Context& c, const u64* ct, u64 cs, u64* out, 
     else TRY(ntt_launch(inv, 2 * batch, true, st));
     a.src_inv = fuse_inv ? 1 : 0;
     return ntt_launch(a, 2 * t * batch, false, st);
+}
+
+hipError_t op_ckks_mod_raise(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, int out_depth, int batch, u64* ws,
+                             hipStream_t st)
+{
+    return mod_raise_scaled(c, ct, cs, 1, out, so, out_depth, batch, ws, st);
 }
 
 // reference ckks/operator.cu:1422-1559
@@ -1236,6 +1247,106 @@ hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, 
         }
     }
     return hipSuccess;
+}
+
+// ------------------------------------------------------------------ the CKKS refresh
+// Head (OP_CKKS_BOOTSTRAP, the part no plan or factor changes): per item k1 * ct [2][N], its dense -> sparse switch [2][N],
+// the raise's coefficient-domain pair [2][N].  Then the raised ciphertext [2][cts_level + 1][N] per item, with switch keys
+// a second one (a key switch does not write over its input), the two halves after CoeffToSlot as 2 * batch items
+// [2][eval_level + 1][N], EvalMod's result as 2 * batch items, and the largest workspace of the five sequences.
+struct BootstrapWs { u64 scaled, sparse, raise_ws, R, r_stride, R2, H, h_stride, E, e_stride, step, total; };
+static u64 bootstrap_head_ws(const Context& c) { return ops_workspace_elems(c, OP_CKKS_BOOTSTRAP, 0, 1); }
+static BootstrapWs bootstrap_ws(const Context& c, const host::BootstrapPlan& p, const host::PolyStep* eval_mod, int n_steps,
+                                const LinearFactor* cts, const LinearFactor* stc, bool switch_keys, int batch)
+{
+    const u64 n = c.n, B = (u64) batch;
+    const int Q = c.Q_size;
+    BootstrapWs w{};
+    w.scaled = 0;
+    w.sparse = 2 * n * B;
+    w.raise_ws = 4 * n * B;
+    w.R = bootstrap_head_ws(c) * B;
+    w.r_stride = (u64) 2 * (p.cts_level + 1) * n;
+    w.R2 = w.R + w.r_stride * B;
+    w.H = w.R2 + (switch_keys ? w.r_stride * B : 0);
+    w.h_stride = (u64) 2 * (p.eval_level + 1) * n;
+    w.E = w.H + w.h_stride * 2 * B;
+    const host::PolyStep& last = eval_mod[n_steps - 1];
+    w.e_stride = (u64) 2 * (last.level + 1 + (last.rescale_after ? 1 : 0)) * n;
+    w.step = w.E + w.e_stride * 2 * B;
+    u64 step = std::max(ops_encoding_transform_workspace_elems(c, cts, p.cts_pieces, Q - 1 - p.cts_level, batch),
+                        ops_encoding_transform_workspace_elems(c, stc, p.stc_pieces, Q - 1 - p.stc_level, batch));
+    step = std::max<u64>(step, ops_poly_eval_workspace_elems(c, eval_mod, n_steps, Q - 1 - p.eval_level, 2 * batch));
+    if (switch_keys)
+        step = std::max<u64>(step, std::max(ops_workspace_elems(c, OP_CKKS_GALOIS, Q - 1, batch),
+                                            ops_workspace_elems(c, OP_CKKS_GALOIS, Q - 1 - p.cts_level, batch)));
+    w.total = w.step + step;
+    return w;
+}
+
+const char* ops_bootstrap_check(const Context& c, const host::BootstrapPlan& p, const host::PolyStep* eval_mod, int n_steps)
+{
+    const int Q = c.Q_size;
+    if (c.scheme != SCHEME_CKKS) return "context scheme mismatch";
+    if (p.cts_pieces < 1 || p.cts_pieces > host::BOOTSTRAP_MAX_PIECES || p.stc_pieces < 1 ||
+        p.stc_pieces > host::BOOTSTRAP_MAX_PIECES)
+        return "a piece count outside [1, 5]";
+    if (p.cts_level < 1 || p.cts_level >= Q) return "the raise goes to a level the context has";
+    if (p.eval_level != p.cts_level - p.cts_pieces - 1 || p.eval_level < 1) return "EvalMod starts pieces + 1 levels below CoeffToSlot";
+    if (p.k1 < 1 || p.k1 >= c.primes[0]) return "the pre-multiplier lies in [1, q_0)";
+    if (const char* why = ops_poly_eval_check(c, eval_mod, n_steps, Q - 1 - p.eval_level)) return why;
+    const host::PolyStep& last = eval_mod[n_steps - 1];
+    if (last.level != p.stc_level || last.scale != p.eval_out_scale) return "the EvalMod plan is not the one of the bootstrap plan";
+    if (p.out_level != p.stc_level - 1 - p.stc_pieces || p.out_level < 0) return "SlotToCoeff needs pieces + 1 levels and one limb left";
+    return nullptr;
+}
+
+size_t ops_bootstrap_workspace_elems(const Context& c, const host::BootstrapPlan& p, const host::PolyStep* eval_mod,
+                                     int n_steps, const LinearFactor* cts, const LinearFactor* stc, bool switch_keys, int batch)
+{
+    return bootstrap_ws(c, p, eval_mod, n_steps, cts, stc, switch_keys, batch).total;
+}
+
+// x k1 -> [key switch to the sparse secret at depth Q - 1] -> raise -> [key switch back] -> CoeffToSlot -> ONE EvalMod over
+// the 2 * batch halves -> SlotToCoeff.  Every step is the existing sequence; the only launch of its own is rns_scale_q0,
+// and that only for k1 > 1: without switch keys it takes the place of the raise's copy of limb 0.
+hipError_t op_ckks_bootstrap(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::BootstrapPlan& p,
+                             const host::PolyStep* eval_mod, int n_steps, const LinearFactor* cts, const LinearFactor* stc,
+                             const u64* conj_key, const u64* relin_key, const u64* swk_dense_to_sparse,
+                             const u64* swk_sparse_to_dense, int batch, u64* ws, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (ops_bootstrap_check(c, p, eval_mod, n_steps) || !swk_dense_to_sparse != !swk_sparse_to_dense) return hipErrorInvalidValue;
+    const bool keys = swk_dense_to_sparse != nullptr;
+    const BootstrapWs w = bootstrap_ws(c, p, eval_mod, n_steps, cts, stc, keys, batch);
+    const int Q = c.Q_size, raise_depth = Q - 1 - p.cts_level;
+    const u64 n = c.n;
+    u64* step_ws = ws + w.step;
+    u64* R = ws + w.R;
+    const u64* raised = R;
+    if (!keys) {
+        TRY(mod_raise_scaled(c, ct, cs, p.k1, R, w.r_stride, raise_depth, batch, ws + w.raise_ws, st));
+    } else {
+        const u64* cur = ct;
+        u64 cur_stride = cs;
+        if (p.k1 != 1) {
+            TRY(rns_scale_q0(ct, cs, p.k1, ws + w.scaled, n, 2 * n, nullptr, 0, c.plan_qp.mods, c.n_power, batch, st));
+            cur = ws + w.scaled;
+            cur_stride = 2 * n;
+        }
+        TRY(op_ckks_apply_galois(c, cur, cur_stride, ws + w.sparse, 2 * n, swk_dense_to_sparse, 1, Q - 1, batch, step_ws, st));
+        TRY(op_ckks_mod_raise(c, ws + w.sparse, 2 * n, R, w.r_stride, raise_depth, batch, ws + w.raise_ws, st));
+        TRY(op_ckks_apply_galois(c, R, w.r_stride, ws + w.R2, w.r_stride, swk_sparse_to_dense, 1, raise_depth, batch, step_ws, st));
+        raised = ws + w.R2;
+    }
+    u64* H = ws + w.H; // items [0, batch): the first half of the coefficients, [batch, 2 batch): the second
+    TRY(op_ckks_coeff_to_slot(c, raised, w.r_stride, H, H + w.h_stride * batch, w.h_stride, cts, p.cts_pieces, conj_key,
+                              raise_depth, batch, step_ws, st));
+    u64* E = ws + w.E;
+    TRY(op_ckks_poly_eval(c, H, w.h_stride, E, w.e_stride, eval_mod, n_steps, relin_key, Q - 1 - p.eval_level, 2 * batch,
+                          step_ws, st));
+    return op_ckks_slot_to_coeff(c, E, w.e_stride, E + w.e_stride * batch, w.e_stride, out, so, stc, p.stc_pieces,
+                                 Q - 1 - p.stc_level, batch, step_ws, st);
 }
 
 // ------------------------------------------------------------------ logic gates

@@ -2,6 +2,7 @@
 #pragma once
 #include "context.hpp"
 #include "keygen.hpp"
+#include "bootstrap_plan.hpp"
 #include "poly_eval.hpp"
 
 namespace hegpu {
@@ -11,7 +12,7 @@ enum { OP_CKKS_RELIN = 1, OP_CKKS_RESCALE = 2, OP_CKKS_GALOIS = 3, OP_BFV_MULTIP
        OP_BFV_DECRYPT = 12, OP_BFV_DECODE = 13, OP_CKKS_ENCODE = 14,
        OP_CKKS_DECODE = 15, OP_BFV_MULTIPLY_PLAIN = 16, OP_CKKS_ROTATE_HOISTED = 17, OP_MPC_KEY_SHARE = 18,
        OP_MPC_BFV_DECRYPT_MERGE = 19, OP_MPC_REFRESH_SHARE = 20, OP_MPC_REFRESH_MERGE = 21, OP_CKKS_LOGIC_GATE = 22,
-       OP_BFV_LOGIC_GATE = 23, OP_CKKS_MOD_RAISE = 25 /* 24 stays unassigned: include/hegpu.h */ };
+       OP_BFV_LOGIC_GATE = 23, OP_CKKS_MOD_RAISE = 25 /* 24 stays unassigned: include/hegpu.h */, OP_CKKS_BOOTSTRAP = 26 };
 
 // Words of the workspace row `op` for `batch` items at `depth`.  Every shape is stated once, by a layout function of
 // ops.cpp that this query and the sequence both read.
@@ -101,6 +102,23 @@ const char* ops_poly_eval_check(const Context& c, const host::PolyStep* plan, in
 size_t ops_poly_eval_workspace_elems(const Context& c, const host::PolyStep* plan, int n_steps, int depth, int batch);
 hipError_t op_ckks_poly_eval(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::PolyStep* plan,
                              int n_steps, const u64* relin_key, int depth, int batch, u64* ws, hipStream_t st);
+
+// ---- the CKKS refresh (reference regular_bootstrapping_v2, ckks/operator.cu:7147-7224): ct [2][1][N] per
+// item at q_0 -> x k1 -> [apply_galois with the element 1 and swk_dense_to_sparse at depth Q - 1] -> op_ckks_mod_raise to
+// the plan's cts_level -> [the same with swk_sparse_to_dense there] -> op_ckks_coeff_to_slot, its two halves as items
+// [0, batch) and [batch, 2 batch) of one buffer -> ONE op_ckks_poly_eval of the EvalMod plan at batch 2 * batch ->
+// op_ckks_slot_to_coeff.  out needs room for [2][out_level + 2][N] per item and holds [2][out_level + 1][N] on return, at
+// the plan's out_scale.  Both switch keys or neither.  eval_mod: the steps of host::eval_mod_plan for the plan's
+// (K, sine_degree, double_angle, eval_level, eval_in_scale, eval_target_scale).  cts / stc: the plan's piece counts.
+// ops_bootstrap_check: nullptr, or what is wrong with the plan for this context.  Workspace: OP_CKKS_BOOTSTRAP is the head
+// that depends on nothing but the batch; ops_bootstrap_workspace_elems is the whole (check first).
+const char* ops_bootstrap_check(const Context& c, const host::BootstrapPlan& p, const host::PolyStep* eval_mod, int n_steps);
+size_t ops_bootstrap_workspace_elems(const Context& c, const host::BootstrapPlan& p, const host::PolyStep* eval_mod,
+                                     int n_steps, const LinearFactor* cts, const LinearFactor* stc, bool switch_keys, int batch);
+hipError_t op_ckks_bootstrap(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const host::BootstrapPlan& p,
+                             const host::PolyStep* eval_mod, int n_steps, const LinearFactor* cts, const LinearFactor* stc,
+                             const u64* conj_key, const u64* relin_key, const u64* swk_dense_to_sparse,
+                             const u64* swk_sparse_to_dense, int batch, u64* ws, hipStream_t st);
 
 // ---- logic gates on bits held as 0 / 1 (HELogicOperator<CKKS / BFV>, host/ckks/operator.cuh:2333-3500,
 // host/bfv/operator.cuh:1324-2230): the product sequence of the arithmetic operator into the workspace, then ONE

@@ -206,6 +206,34 @@ hipError_t rns_mod_raise(const u64* in, u64 in_stride, u64* out, u64 out_stride,
     return hipGetLastError();
 }
 
+// The pre-multiplier of the refresh on the two q_0 limbs of a ciphertext at depth Q - 1: k v mod q_0 (k below q_0), one
+// load and up to two stores -- `a` with its own part stride (limb 0 of the raised ciphertext, where the raise would copy
+// v) and, if given, `b` as [2][N] per item (the source of the raise's inverse transform).
+__global__ __launch_bounds__(RNS_THREADS) void k_scale_q0(const u64* __restrict__ in, u64 in_stride, u64 k,
+                                                          u64* __restrict__ a, u64 a_part_stride, u64 a_stride,
+                                                          u64* __restrict__ b, u64 b_stride,
+                                                          const Mod* __restrict__ mods, int n_power)
+{
+    const u64 c = coeff0();
+    const Mod m = mods[0];
+    const ulonglong2 x = ld2(in + in_stride * blockIdx.z + ((u64) blockIdx.y << n_power) + c);
+    ulonglong2 r;
+    r.x = mul_barrett(x.x, k, m);
+    r.y = mul_barrett(x.y, k, m);
+    st2(a + a_stride * blockIdx.z + a_part_stride * blockIdx.y + c, r);
+    if (b) st2(b + b_stride * blockIdx.z + ((u64) blockIdx.y << n_power) + c, r);
+}
+
+hipError_t rns_scale_q0(const u64* in, u64 in_stride, u64 k, u64* a, u64 a_part_stride, u64 a_stride, u64* b, u64 b_stride,
+                        const Mod* mods, int n_power, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scale_q0, grid3(n_power, 2, batch), dim3(RNS_THREADS), 0, st, in, in_stride, k, a, a_part_stride,
+                       a_stride, b, b_stride, mods, n_power);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- partial sums of a digit-split key switch
 __global__ __launch_bounds__(RNS_THREADS) void k_sum_partials(const u64* __restrict__ buf, u64 buf_item_stride,
                                                               u64* __restrict__ out, u64 out_item_stride,

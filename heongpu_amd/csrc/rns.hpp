@@ -36,6 +36,12 @@ hipError_t rns_decompose(const u64* in, u64 in_stride, u64* out, u64 out_stride,
 hipError_t rns_mod_raise(const u64* in, u64 in_stride, u64* out, u64 out_stride, const Mod* mods, int n_power, int limbs,
                          int parts, int batch, hipStream_t st);
 
+// The integer pre-multiplier of the CKKS refresh: in [2][1][N] per item at q_0 -> k * in mod q_0, k < q_0,
+// written to a (part p at a + p * a_part_stride) and, if b is given, to b [2][N] per item as well.  Canonical residues:
+// what hegpu_ckks_constant_op (HEGPU_CONST_MUL) gives on one limb.
+hipError_t rns_scale_q0(const u64* in, u64 in_stride, u64 k, u64* a, u64 a_part_stride, u64 a_stride, u64* b, u64 b_stride,
+                        const Mod* mods, int n_power, int batch, hipStream_t st);
+
 // reference switchkey.cu:61-285: out[c][y][n] = sum_i in[i][y][n]*key[i][c][kidx(y)][n].
 // key strides use key_limbs (= Q' at depth 0); kidx(y) = (y < split) ? y : y + level
 // (method I leveled: split = l, level = depth maps row l to the P limb; method II,

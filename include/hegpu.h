@@ -283,7 +283,9 @@ enum {
     HEGPU_OP_CKKS_LOGIC_GATE = 22,       /* hegpu_ckks_logic_gate: a three-part product per item + the larger of RELIN, RESCALE */
     HEGPU_OP_BFV_LOGIC_GATE = 23,        /* hegpu_bfv_logic_gate: the same + the largest of MULTIPLY, RELIN, MULTIPLY_PLAIN */
     /* 24 stays unassigned: tests/test_cabi_logic.py holds it as the number no row has (0 bytes) */
-    HEGPU_OP_CKKS_MOD_RAISE = 25         /* hegpu_ckks_mod_raise: 2 N words per item at every depth */
+    HEGPU_OP_CKKS_MOD_RAISE = 25,        /* hegpu_ckks_mod_raise: 2 N words per item at every depth */
+    HEGPU_OP_CKKS_BOOTSTRAP = 26         /* the head of hegpu_ckks_bootstrap's workspace, 6 N words per item at every depth; the
+                                          * whole is hegpu_ckks_bootstrap_workspace_bytes */
 };
 size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int batch);
 
@@ -512,6 +514,65 @@ size_t hegpu_ckks_poly_eval_workspace_bytes(const hegpu_context* ctx, const hegp
 int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out, uint64_t out_stride,
                          const hegpu_poly_step* plan, int n_steps, const uint64_t* relin_key, int depth, int batch,
                          void* ws, size_t ws_bytes, hegpu_stream stream);
+/* ------------------------------------------------------------------ the CKKS refresh (regular_bootstrapping_v2,
+ * generate_bootstrapping_params_v2 and mod_up_from_q0 with its two key switches, host/ckks/operator.cu:7147-7224, :6906-7000,
+ * :3963-4033): a host-only plan that holds every scale label, and one sequence over the entries above.
+ *
+ * PLAN.  hegpu_bootstrap_plan_fill is host only.  config: the fields of the reference's EvalModConfig / EncodingMatrixConfig
+ * with their defaults (ratio 256, K 16, degree 30, double_angle 3); levels are indices of a ciphertext's last prime;
+ * eval_level / stc_level may be -1 (they follow from cts_level: eval_level = cts_level - cts_pieces - 1, stc_level =
+ * eval_level - bit_length(sine_degree) - double_angle) and are refused if they are anything else.  With D = scale:
+ *   k1 = max(1, round(q_0 / (ratio D))), D' = k1 D: the q_0 limbs are multiplied by k1 before the raise;
+ *   the raised ciphertext is labelled raise_scale = q_0 K, its value is (I + eps) / K, eps = D' a / q_0;
+ *   factor f of CoeffToSlot is encoded at cts_scale[f] (level cts_level - f) and leaves the label cts_label[f]; the last
+ *   one is the sine scale q_(eval_level) to the rounding of doubles and the input scale eval_in_scale of the EvalMod plan
+ *   hegpu_eval_mod_plan_*(K, sine_degree, double_angle, eval_level, eval_in_scale, eval_target_scale), whose result
+ *   sin(2 pi eps) / 2 pi at eval_out_scale is relabelled stc_in_scale = eval_out_scale D' / q_0: the value is then
+ *   f(a) = (rho / 2 pi) sin(2 pi a / rho), rho = q_0 / D'; factor g of SlotToCoeff is encoded at stc_scale[g] (level
+ *   stc_level - 1 - g); the result is at out_level with the label out_scale = D to the rounding of doubles.
+ * HEGPU_E_INVALID, *plan untouched: fewer levels than cts_pieces + 1 + bit_length(sine_degree) + double_angle + 1 +
+ * stc_pieces and one limb left, K < 1, ratio D > q_0, a scale or ratio that is not positive and finite, piece counts
+ * outside [2, 5], start levels that do not follow from one another, what hegpu_eval_mod_plan_* refuses. */
+typedef struct hegpu_bootstrap_config {
+    double scale, message_ratio;
+    int32_t K, sine_degree, double_angle;
+    int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces;
+} hegpu_bootstrap_config;
+typedef struct hegpu_bootstrap_plan {
+    uint64_t k1;
+    int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces, out_level;
+    int32_t K, sine_degree, double_angle;
+    int32_t reserved;
+    double raise_scale;
+    double cts_scale[5], cts_label[5];
+    double eval_in_scale, eval_target_scale, eval_out_scale;
+    double stc_in_scale;
+    double stc_scale[5], stc_label[5];
+    double out_scale;
+} hegpu_bootstrap_plan;
+int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64_t* primes, int n_primes,
+                              hegpu_bootstrap_plan* plan);
+/* SEQUENCE.  ct: [2][1][N] per item, a ciphertext at depth Q - 1 (what hegpu_ckks_mod_raise takes).  The launches, all on
+ * `stream`, nothing allocated: the q_0 limbs times k1 (k1 > 1 only; without switch keys in the place of the raise's copy of
+ * limb 0) -> with switch keys hegpu_ckks_apply_galois with the element 1 and swk_dense_to_sparse at depth Q - 1 ->
+ * hegpu_ckks_mod_raise to plan->cts_level -> with switch keys the same key switch with swk_sparse_to_dense there ->
+ * hegpu_ckks_coeff_to_slot (cts: cts_count = plan->cts_pieces factors) -> ONE hegpu_ckks_poly_eval of eval_mod over the
+ * 2 * batch halves -> hegpu_ckks_slot_to_coeff (stc: stc_count = plan->stc_pieces factors).  Bit-identical to that chain of single entries
+ * (the multiplication: hegpu_ckks_constant_op, HEGPU_CONST_MUL).  out needs room for [2][out_level + 2][N] per item and
+ * holds [2][out_level + 1][N] on return, at depth Q - 1 - out_level and scale plan->out_scale.
+ * HEGPU_E_INVALID before anything is queued, out untouched: exactly one of the two switch keys, a plan, EvalMod plan or
+ * factor list that does not fit the context or one another, a workspace below hegpu_ckks_bootstrap_workspace_bytes (0 for
+ * arguments it cannot size; switch_keys: whether the call passes them), out overlapping ct or the workspace, null
+ * pointers, batch < 1. */
+size_t hegpu_ckks_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_bootstrap_plan* plan,
+                                            const hegpu_poly_step* eval_mod, int n_steps, const hegpu_linear_factor* cts,
+                                            int cts_count, const hegpu_linear_factor* stc, int stc_count, int switch_keys,
+                                            int batch);
+int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out, uint64_t out_stride,
+                         const hegpu_bootstrap_plan* plan, const hegpu_poly_step* eval_mod, int n_steps,
+                         const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc, int stc_count,
+                         const uint64_t* conj_key, const uint64_t* relin_key, const uint64_t* swk_dense_to_sparse, const uint64_t* swk_sparse_to_dense,
+                         int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
 /* multiply_bfv (src/lib/host/bfv/operator.cu:336-430): coefficient domain,
  * ct [2][Q][N] x [2][Q][N] -> out [3][Q][N] */
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_stride, const uint64_t* ct2,

@@ -1661,6 +1661,9 @@ template <Scheme S> class HEKeyGenerator { // host/*/keygenerator.cuh
         sk.memory_set(std::move(out));
         sk.secret_key_generated_ = true;
     }
+    // ckks/keygenerator.cu:85-160: the sampler hegpu_generate_secret_key restates is this one (exactly hamming_weight_
+    // non-zero coefficients), so the two names are one function here
+    void generate_secret_key_v2(Secretkey<S>& sk, const ExecutionOptions& o = ExecutionOptions()) { generate_secret_key(sk, o); }
     void generate_public_key(Publickey<S>& pk, Secretkey<S>& sk, const ExecutionOptions& o = ExecutionOptions())
     {
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
@@ -2282,6 +2285,170 @@ struct CKKSEncodingTransformContext {
     std::vector<std::shared_ptr<LinearTransform<Scheme::CKKS>>> CtoS_factors_, StoC_factors_;
 };
 
+// ------------------------------------------------------------------ configuration of the CKKS refresh
+// util/util.cuh:60-202: the names, fields and defaults of the reference.  level_start_ is a level (the index of a
+// ciphertext's last prime).  Read by HEArithmeticOperator<CKKS>::generate_bootstrapping_params_v2: Q_,
+// scaling_factor_, arcsine_deg_, sqrt2pi_, q_diff_ and bsgs_ratio_ are carried for the reference's callers and not used --
+// scales are exact labels here, the baby-step period is the linear transform's own rule.
+enum class SineType { COS1 };
+enum class LinearTransformType { COEFFS_TO_SLOTS, SLOTS_TO_COEFFS };
+struct EvalModConfig {
+    Data64 Q_ = 0;
+    int level_start_ = 0;
+    double message_ratio_ = 0.0;
+    int K_ = 0;
+    int sine_deg_ = 0;
+    int double_angle_ = 0;
+    int arcsine_deg_ = 0;
+    double scaling_factor_ = 0.0;
+    int piece_ = 0;
+    double sqrt2pi_ = 0.0;
+    double q_diff_ = 0.0;
+    SineType sine_type_ = SineType::COS1;
+    PolyType poly_type_ = PolyType::CHEBYSHEV;
+    EvalModConfig() {}
+    EvalModConfig(int level_start) : level_start_(level_start), message_ratio_(256.0), K_(16), sine_deg_(30), double_angle_(3) {}
+    EvalModConfig(Data64 Q, int level_start, double message_ratio, int K, int sine_deg, int double_angle, int arcsine_deg,
+                  double scaling_factor)
+        : Q_(Q), level_start_(level_start), message_ratio_(message_ratio), K_(K), sine_deg_(sine_deg),
+          double_angle_(double_angle), arcsine_deg_(arcsine_deg), scaling_factor_(scaling_factor)
+    {
+        if (Q != 0) q_diff_ = (double) Q / std::exp2(std::round(std::log2((double) Q)));
+        if (Q != 0 && scaling_factor != 0.0)
+            sqrt2pi_ = std::pow((double) Q * 0.5 / (scaling_factor * 3.14159265358979323846), 1.0 / std::exp2((double) double_angle));
+    }
+};
+struct EncodingMatrixConfig {
+    LinearTransformType lt_type_ = LinearTransformType::COEFFS_TO_SLOTS;
+    int level_start_ = 0;
+    double bsgs_ratio_ = 0.0;
+    int piece_ = 0;
+    EncodingMatrixConfig() {}
+    EncodingMatrixConfig(LinearTransformType lt_type, int level_start) : EncodingMatrixConfig(lt_type, level_start, 2.0) {}
+    EncodingMatrixConfig(LinearTransformType lt_type, int level_start, double bsgs_ratio)
+        : EncodingMatrixConfig(lt_type, level_start, bsgs_ratio, lt_type == LinearTransformType::COEFFS_TO_SLOTS ? 4 : 3)
+    {
+    }
+    EncodingMatrixConfig(LinearTransformType lt_type, int level_start, double bsgs_ratio, int piece)
+        : lt_type_(lt_type), level_start_(level_start), bsgs_ratio_(bsgs_ratio), piece_(piece)
+    {
+    }
+};
+struct BootstrappingConfigV2 {
+    int CtoS_piece_;
+    int StoC_piece_;
+    EncodingMatrixConfig cts_config_;
+    EncodingMatrixConfig stc_config_;
+    EvalModConfig eval_mod_config_;
+    BootstrappingConfigV2(EncodingMatrixConfig stc_config, EvalModConfig eval_mod_config, EncodingMatrixConfig cts_config)
+        : CtoS_piece_(cts_config.piece_), StoC_piece_(stc_config.piece_), cts_config_(cts_config), stc_config_(stc_config),
+          eval_mod_config_(eval_mod_config)
+    {
+    }
+};
+
+// ------------------------------------------------------------------ precision of decoded CKKS values
+// host/ckks/precision.cuh: per slot the distance of the real parts, of the imaginary parts and of the complex numbers
+// (l2); precision = log2(1 / delta).  The distributions (cdf_resol steps of 0.01 bit up to the best precision seen) count
+// the slots whose precision is at least that step.
+struct Stats {
+    double real, imag, l2;
+    Stats() : real(0.0), imag(0.0), l2(0.0) {}
+    Stats(double r, double i, double l2_val) : real(r), imag(i), l2(l2_val) {}
+};
+struct DistEntry {
+    double prec;
+    int count;
+    DistEntry() : prec(0.0), count(0) {}
+};
+inline Stats delta_to_precision(const Stats& d) { return Stats(std::log2(1.0 / d.real), std::log2(1.0 / d.imag), std::log2(1.0 / d.l2)); }
+inline Stats calc_median(std::vector<Stats>& values)
+{
+    if (values.empty()) return Stats();
+    std::vector<double> r, i, l;
+    for (const Stats& s : values) { r.push_back(s.real); i.push_back(s.imag); l.push_back(s.l2); }
+    auto mid = [](std::vector<double>& v) {
+        std::sort(v.begin(), v.end());
+        const size_t h = v.size() / 2;
+        return v.size() % 2 ? v[h] : 0.5 * (v[h - 1] + v[h]);
+    };
+    return Stats(mid(r), mid(i), mid(l));
+}
+inline void calc_cdf(const std::vector<double>& precs, std::vector<DistEntry>& res, int cdf_resol)
+{
+    res.assign((size_t) (cdf_resol > 0 ? cdf_resol : 0), DistEntry());
+    if (precs.empty() || cdf_resol < 1) return;
+    std::vector<double> sorted(precs);
+    std::sort(sorted.begin(), sorted.end());
+    const double lo = sorted.front(), hi = sorted.back();
+    for (int k = 0; k < cdf_resol; k++) {
+        const double p = lo + (hi - lo) * k / (double) cdf_resol;
+        res[(size_t) k].prec = p;
+        res[(size_t) k].count = (int) (sorted.end() - std::lower_bound(sorted.begin(), sorted.end(), p));
+    }
+}
+struct PrecisionStats {
+    Stats max_delta, min_delta, max_precision, min_precision, mean_delta, mean_precision, median_delta, median_precision;
+    std::vector<DistEntry> real_dist, imag_dist, l2_dist;
+    int cdf_resol;
+    PrecisionStats() : min_delta(1.0, 1.0, 1.0), cdf_resol(500) {}
+    std::string to_string() const
+    {
+        std::ostringstream os;
+        os << std::fixed << std::setprecision(2);
+        auto row = [&](const char* name, const Stats& s) {
+            os << name << " (real / imag / l2): " << s.real << " / " << s.imag << " / " << s.l2 << " bits\n";
+        };
+        row("MIN precision", min_precision);
+        row("MAX precision", max_precision);
+        row("AVG precision", mean_precision);
+        row("MED precision", median_precision);
+        os << std::scientific << "MAX delta (real / imag / l2): " << max_delta.real << " / " << max_delta.imag << " / "
+           << max_delta.l2 << "\n";
+        return os.str();
+    }
+};
+inline PrecisionStats get_precision_stats(const std::vector<Complex64>& values_want, const std::vector<Complex64>& values_test)
+{
+    PrecisionStats p;
+    const size_t slots = values_want.size() < values_test.size() ? values_want.size() : values_test.size();
+    if (slots == 0) return p;
+    std::vector<Stats> deltas(slots);
+    std::vector<double> pr(slots), pi(slots), pl(slots);
+    const double floor_delta = std::exp2(-1000.0); // an exact value has no finite precision: it counts as 1000 bits
+    for (size_t k = 0; k < slots; k++) {
+        const Complex64 d = values_test[k] - values_want[k];
+        Stats s(std::fabs(d.real()), std::fabs(d.imag()), std::abs(d));
+        for (double* v : {&s.real, &s.imag, &s.l2}) if (*v < floor_delta) *v = floor_delta;
+        deltas[k] = s;
+        p.mean_delta.real += s.real; p.mean_delta.imag += s.imag; p.mean_delta.l2 += s.l2;
+        if (k == 0) p.max_delta = p.min_delta = s;
+        p.max_delta = Stats(std::max(p.max_delta.real, s.real), std::max(p.max_delta.imag, s.imag), std::max(p.max_delta.l2, s.l2));
+        p.min_delta = Stats(std::min(p.min_delta.real, s.real), std::min(p.min_delta.imag, s.imag), std::min(p.min_delta.l2, s.l2));
+        const Stats b = delta_to_precision(s);
+        pr[k] = b.real; pi[k] = b.imag; pl[k] = b.l2;
+    }
+    p.mean_delta = Stats(p.mean_delta.real / slots, p.mean_delta.imag / slots, p.mean_delta.l2 / slots);
+    p.min_precision = delta_to_precision(p.max_delta);
+    p.max_precision = delta_to_precision(p.min_delta);
+    p.mean_precision = delta_to_precision(p.mean_delta);
+    p.median_delta = calc_median(deltas);
+    p.median_precision = delta_to_precision(p.median_delta);
+    calc_cdf(pr, p.real_dist, p.cdf_resol);
+    calc_cdf(pi, p.imag_dist, p.cdf_resol);
+    calc_cdf(pl, p.l2_dist, p.cdf_resol);
+    return p;
+}
+inline PrecisionStats get_precision_stats(const std::vector<double>& values_want, const std::vector<Complex64>& values_test)
+{
+    return get_precision_stats(std::vector<Complex64>(values_want.begin(), values_want.end()), values_test);
+}
+inline PrecisionStats get_precision_stats(const std::vector<double>& values_want, const std::vector<double>& values_test)
+{
+    return get_precision_stats(std::vector<Complex64>(values_want.begin(), values_want.end()),
+                               std::vector<Complex64>(values_test.begin(), values_test.end()));
+}
+
 // ------------------------------------------------------------------ operator
 template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
     friend class detail::LogicOperatorBase<S>; // emit, require_words
@@ -2701,7 +2868,136 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         return result;
     }
 
+    // host/ckks/operator.cu:6906-7000 (hegpu_bootstrap_plan_fill): the plan of the refresh for ciphertexts
+    // of `scale`, its EvalMod plan and the factors of both transforms, every diagonal encoded at the level and scale the
+    // plan gives it.  A transform of P pieces spends P + 1 levels here (its factors and the limb the boundary pass drops;
+    // the reference: P), so CoeffToSlot takes cts_config_.level_start_ - eval_mod_config_.level_start_ - 1 pieces
+    // whatever cts_config_.piece_ says, SlotToCoeff takes stc_config_.piece_ and the result leaves at
+    // stc_config_.level_start_ - 1 - piece_, one level below the reference's.  Locked after the first call.
+    void generate_bootstrapping_params_v2(const double scale, const BootstrappingConfigV2& config)
+    {
+        static_assert(S == Scheme::CKKS, "bootstrapping parameters are a CKKS matter");
+        if (boot_v2_.generated)
+            throw std::runtime_error("Bootstrapping parameters is locked after generation and cannot be modified.");
+        detail::require_generated(context_);
+        const EvalModConfig& em = config.eval_mod_config_;
+        if (em.sine_type_ != SineType::COS1) throw std::invalid_argument("Unsupported sine type!");
+        if (em.arcsine_deg_ != 0) throw std::invalid_argument("The arcsine correction is not supported!");
+        const int Q = context_->Q_size;
+        std::vector<uint64_t> primes((size_t) Q);
+        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        hegpu_bootstrap_config cfg{};
+        cfg.scale = scale;
+        cfg.message_ratio = em.message_ratio_;
+        cfg.K = em.K_;
+        cfg.sine_degree = em.sine_deg_;
+        cfg.double_angle = em.double_angle_;
+        cfg.cts_level = config.cts_config_.level_start_;
+        cfg.cts_pieces = config.cts_config_.level_start_ - em.level_start_ - 1;
+        cfg.eval_level = em.level_start_;
+        cfg.stc_level = config.stc_config_.level_start_;
+        cfg.stc_pieces = config.stc_config_.piece_;
+        BootV2 b;
+        detail::check(hegpu_bootstrap_plan_fill(&cfg, primes.data(), Q, &b.plan));
+        int n_steps = 0;
+        detail::check(hegpu_eval_mod_plan_size(b.plan.K, b.plan.sine_degree, b.plan.double_angle, b.plan.eval_level,
+                                               b.plan.eval_in_scale, b.plan.eval_target_scale, primes.data(), Q, &n_steps));
+        b.eval_mod.resize((size_t) n_steps);
+        detail::check(hegpu_eval_mod_plan_fill(b.plan.K, b.plan.sine_degree, b.plan.double_angle, b.plan.eval_level,
+                                               b.plan.eval_in_scale, b.plan.eval_target_scale, primes.data(), Q,
+                                               b.eval_mod.data(), n_steps));
+        HEEncoder<S> encoder(context_);
+        const int n = (int) context_->n, slots = n >> 1;
+        for (int inverse = 1; inverse >= 0; inverse--) {
+            const int pieces = inverse ? b.plan.cts_pieces : b.plan.stc_pieces;
+            const int first_level = inverse ? b.plan.cts_level : b.plan.stc_level - 1;
+            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
+            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
+            for (int p = 0; p < pieces; p++) {
+                std::vector<int> offsets(counts[p]);
+                std::vector<double> values((size_t) 2 * counts[p] * slots);
+                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
+                std::map<int, std::vector<Complex64>> diag;
+                for (int d = 0; d < counts[p]; d++) {
+                    std::vector<Complex64> v((size_t) slots);
+                    for (int t = 0; t < slots; t++)
+                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
+                    diag[offsets[d]] = std::move(v);
+                }
+                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder,
+                                                               inverse ? b.plan.cts_scale[p] : b.plan.stc_scale[p],
+                                                               Q - 1 - (first_level - p), 0, ExecutionOptions(), strides[p]);
+                for (int sh : lt->required_shifts())
+                    if (std::find(b.key_indexs.begin(), b.key_indexs.end(), sh) == b.key_indexs.end()) b.key_indexs.push_back(sh);
+                (inverse ? b.cts : b.stc).push_back(std::move(lt));
+            }
+        }
+        b.scale = scale;
+        b.generated = true;
+        boot_v2_ = std::move(b);
+    }
+    // every rotation of every factor: Galoiskey(context, bootstrapping_key_indexs()) is enough (the conjugation is in
+    // every Galoiskey)
+    std::vector<int> bootstrapping_key_indexs() const { return boot_v2_.key_indexs; }
+
+    // host/ckks/operator.cu:7147-7224 (hegpu_ckks_bootstrap): the refresh of a ciphertext at its last level.  The two switch
+    // keys of mod_up_from_q0 (to an ephemeral sparse secret before the raise and back after it) are both given or both
+    // null.  The result carries the scale the parameters were generated for, at the plan's level; its coefficients are
+    // (rho / 2 pi) sin(2 pi a / rho) of the input's, rho = q_0 / (k1 scale).
+    Ciphertext<S> regular_bootstrapping_v2(Ciphertext<S>& input1, Galoiskey<S>& galois_key, Relinkey<S>& relin_key,
+                                           Switchkey<S>* swk_dense_to_sparse = nullptr,
+                                           Switchkey<S>* swk_sparse_to_dense = nullptr,
+                                           const ExecutionOptions& options = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "regular bootstrapping is a CKKS operation");
+        if (!boot_v2_.generated)
+            throw std::invalid_argument("Bootstrapping operation can not be performed before generating Bootstrapping parameters!");
+        if (context_->Q_size - input1.depth_ != 1) throw std::logic_error("Ciphertexts leveled should be at max!");
+        detail::OpScope storage_scope(options); // storage manager: stage HOST-stored operands, place the results
+        check_plain_two_part(input1);
+        if (!input1.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
+        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
+            throw std::invalid_argument("Relinkey does not belong to this context!");
+        if (!swk_dense_to_sparse != !swk_sparse_to_dense)
+            throw std::invalid_argument("Both switch keys (dense to sparse, sparse to dense) or neither!");
+        for (Switchkey<S>* k : {swk_dense_to_sparse, swk_sparse_to_dense})
+            if (k && !k->switch_key_generated_) throw std::logic_error("Switchkey is not generated!");
+        FactorArgs fc(*this, boot_v2_.cts, galois_key), fs(*this, boot_v2_.stc, galois_key);
+        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
+        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        const hegpu_bootstrap_plan& p = boot_v2_.plan;
+        const int n_steps = (int) boot_v2_.eval_mod.size();
+        const uint64_t* down = swk_dense_to_sparse ? (const uint64_t*) swk_dense_to_sparse->data() : nullptr;
+        const uint64_t* up = swk_sparse_to_dense ? (const uint64_t*) swk_sparse_to_dense->data() : nullptr;
+        detail::Workspace ws(hegpu_ckks_bootstrap_workspace_bytes(context_->handle(), &p, boot_v2_.eval_mod.data(), n_steps,
+                                                                  fc.f.data(), p.cts_pieces, fs.f.data(), p.stc_pieces,
+                                                                  down ? 1 : 0, 1),
+                             options.stream_);
+        DeviceVector<Data64> m(2 * context_->n * (size_t) (p.out_level + 2), options.stream_); // rescaled in place at the end
+        detail::check(hegpu_ckks_bootstrap(context_->handle(), (const uint64_t*) input1.data(), 0, (uint64_t*) m.data(), 0, &p,
+                                           boot_v2_.eval_mod.data(), n_steps, fc.f.data(), p.cts_pieces, fs.f.data(),
+                                           p.stc_pieces, conj, (const uint64_t*) relin_key.data(), down, up, 1, ws.data(),
+                                           ws.bytes, options.stream_));
+        Ciphertext<S> result(context_);
+        emit(input1, result, std::move(m));
+        result.depth_ = context_->Q_size - 1 - p.out_level;
+        result.scale_ = p.out_scale;
+        result.rescale_required_ = false;
+        result.relinearization_required_ = false;
+        return result;
+    }
+
   private:
+    // what generate_bootstrapping_params_v2 leaves for regular_bootstrapping_v2
+    struct BootV2 {
+        bool generated = false;
+        double scale = 0.0;
+        hegpu_bootstrap_plan plan{};
+        std::vector<hegpu_poly_step> eval_mod;
+        std::vector<std::shared_ptr<LinearTransform<S>>> cts, stc;
+        std::vector<int> key_indexs;
+    };
+    BootV2 boot_v2_;
     void check_plain_two_part(const Ciphertext<S>& a) const
     {
         if (a.relinearization_required_ || a.cipher_size_ != 2)
