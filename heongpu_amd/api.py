@@ -1201,5 +1201,12 @@ def bootstrap_plan(primes, scale, cts_level, cts_pieces=3, stc_pieces=3, message
                                           c.eval_target_scale, pr))
 
 
+def ks_launch_forms():
+    """measurement seam: (natural, wide, split) launches of the fused row pass + inner product so far in this process"""
+    c = (ctypes.c_uint64 * 3)()
+    _lib.load().hegpu_probe_ks_launch_forms(c)
+    return tuple(int(x) for x in c)
+
+
 def steps_to_galois_elt(steps, n, group_order):
     return int(_lib.load().hegpu_steps_to_galois_elt(steps, n, group_order))

@@ -921,6 +921,13 @@ int hegpu_probe_ckks_relinearize(hegpu_context* ctx, uint64_t* ct, uint64_t cs, 
                    "hegpu_probe_ckks_relinearize");
 }
 
+void hegpu_probe_ks_launch_forms(uint64_t counts[3])
+{
+    unsigned long long c[3];
+    ks_row_mac_launch_counts(c);
+    for (int i = 0; i < 3; i++) counts[i] = c[i];
+}
+
 int hegpu_ckks_rescale_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs, int depth, int batch, void* ws,
                                size_t ws_bytes, hegpu_stream stream)
 {

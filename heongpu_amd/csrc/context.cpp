@@ -777,6 +777,7 @@ const OptDesc kOptions[] = {
     {"behz_split", "HEGPU_BEHZ_SPLIT", -1, 1, &H::behz_split, OptDesc::MIRROR_BEHZ},
     {"fused_tensor", "HEGPU_FUSED_TENSOR", &H::fused_tensor},
     {"moddown_in_mac", "HEGPU_MODDOWN_IN_MAC", &H::moddown_in_mac},
+    {"wide_access", "HEGPU_WIDE_ACCESS", &H::wide_access},
 };
 const OptDesc* find_option(const char* name)
 {

@@ -113,6 +113,7 @@ struct ContextHost {
     bool copy_along = true;    // 0: the rescale's copy of the kept limbs always has its own launch
     bool fuse_inverse = true;  // 0: the INTT feeding a decomposing launch runs on its own
     bool moddown_in_mac = true; // 0: CKKS method I, fused key switch: the mod-down row pass as a launch of its own instead of the inner product's tail
+    bool wide_access = true;   // 0: fused key switch without digit splits: the row pass + inner product in the natural ownership, 8-byte global accesses (KsMacArgs::wide)
     bool fused_tensor = true;  // BFV multiply: the tensor product as the load transform of the inverse transform (0: its own kernel)
     bool fp_ntt = true;        // 0: every modulus on the integer butterflies (read when the tables are built)
     int behz_split = -1;       // BFV BEHZ kernels: rows over four wavefronts (1), one thread per coefficient (0), by launch size (-1)

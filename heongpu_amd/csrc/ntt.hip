@@ -25,6 +25,7 @@
 //  * wave-uniform twiddles (column pass, first round) are fetched through
 //    the scalar cache; the rest are 16-byte (w, w') pairs read as dwordx4.
 #include "ntt.hpp"
+#include <atomic>
 #define HEGPU_FP_TU ntt // (names this file's table reader in the instrumented test build, see fpmod.cuh)
 #include "fpmod.cuh"
 
@@ -1157,9 +1158,76 @@ static_assert(ks_unreduced_exit(16, 60) == 16 && ks_unreduced_exit(17, 60) == 12
 static_assert(ks_unreduced_exit(22, 60) == 8 && ks_unreduced_exit(32, 60) == 8 && ks_unreduced_exit(33, 60) == 0, "");
 static_assert(ks_unreduced_exit(4, 61) == 16 && ks_unreduced_exit(8, 61) == 8 && ks_unreduced_exit(9, 61) == 0, "");
 
+// Ownership past the row stages.  Natural: thread (row, i0) holds the elements i0 + 16 k of its row, every global access
+// of the products and the tail is 8 bytes per lane.  PAIR (the wide kernels, KsMacArgs::wide): it holds the pairs
+// 2 i0 + 32 m + {0, 1}, value 2 m + s -- key tiles, identity limb, added ciphertext and results move 16 bytes per lane,
+// and the 16 lanes of a row cover 256 contiguous bytes per access.  The row stages leave positions 16 i0 + 0..15 in the
+// tile; the read-back row_phys(row * 256 + 2 i0 + 32 m) is pair slot i0 ^ m of the 32-element block m: the 16 lanes of a
+// row hit 16 distinct 16-byte slots, as the natural read-back's do (tests/test_wide_layout_model.py).
+template <bool PAIR> __device__ __forceinline__ int ks_own0(int i0) { return PAIR ? 2 * i0 : i0; }
+template <bool PAIR> __device__ __forceinline__ constexpr int ks_own(int k) { return PAIR ? 32 * (k >> 1) + (k & 1) : 16 * k; }
+// the thread's 16 values from / to p = the address of its first one; NT: with the non-temporal hint
+template <bool PAIR, bool NT = false>
+__device__ __forceinline__ void ks_ld16(u64 (&v)[16], const u64* p)
+{
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const u64x2_t* q = reinterpret_cast<const u64x2_t*>(p + 32 * m);
+            const u64x2_t w = NT ? __builtin_nontemporal_load(q) : *q;
+            v[2 * m] = w.x;
+            v[2 * m + 1] = w.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = NT ? __builtin_nontemporal_load(&p[16 * k]) : p[16 * k];
+    }
+}
+template <bool PAIR, bool NT = false>
+__device__ __forceinline__ void ks_st16(u64* p, const u64 (&v)[16])
+{
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            u64x2_t w;
+            w.x = v[2 * m];
+            w.y = v[2 * m + 1];
+            u64x2_t* q = reinterpret_cast<u64x2_t*>(p + 32 * m);
+            if constexpr (NT) __builtin_nontemporal_store(w, q);
+            else *q = w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            if constexpr (NT) __builtin_nontemporal_store(v[k], &p[16 * k]);
+            else p[16 * k] = v[k];
+        }
+    }
+}
+// read-back of the row tile in the ownership above (bits of the values)
+template <bool PAIR>
+__device__ __forceinline__ void ks_own_read(u64 (&v)[16], const u64* lds, int row, int i0)
+{
+    if constexpr (PAIR) {
+        // row_phys(b + 32 m) = (b ^ 2 m) + 32 m, formed per call from an opaque base: hoisted out of the digit loop the
+        // eight addresses sit in eight registers beside the natural tile's sixteen, past the 256 of two waves per SIMD
+        int b = row * 256 + 2 * i0;
+        asm volatile("" : "+v"(b));
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(&lds[(b ^ (2 * m)) + 32 * m]);
+            v[2 * m] = w.x;
+            v[2 * m + 1] = w.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) v[k] = lds[row_phys(row * 256 + i0 + 16 * k)];
+    }
+}
+
 // EXIT: 0 = the digit ends canonical (the mod-down tail's T: ks_tail_store's sub_mod needs that; digits whose sum
 // would not fit); 8 / 12 / 16 = it goes on un-reduced, below EXIT q (correcting branch only; 12 / 16 need ROOM 16).
-template <bool LAZY, int ROOM = 8, int EXIT = 0>
+template <bool LAZY, int ROOM = 8, int EXIT = 0, bool PAIR = false>
 __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict__ p, u64* lds,
                                              const ulonglong2* twa, const ulonglong2* __restrict__ tb,
                                              const QC& qc, const Mod& md, int row, int i0)
@@ -1204,8 +1272,7 @@ __device__ __forceinline__ void ks_row_digit(u64 (&x)[16], const u64* __restrict
         *reinterpret_cast<ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]) =
             make_ulonglong2(x[2 * k], x[2 * k + 1]);
     wave_lds_fence();
-#pragma unroll
-    for (int k = 0; k < 16; k++) x[k] = lds[row_phys(row * 256 + i0 + 16 * k)];
+    ks_own_read<PAIR>(x, lds, row, i0);
     wave_lds_fence();
 }
 
@@ -1263,6 +1330,8 @@ __device__ __forceinline__ KsIdx ks_index(const KsMacArgs& a)
 
 // Mod-down tail of the fused key switch (KsMacArgs::tail), part p of one (item, slot, tile): the thread's 16 results r
 // belong at e0 + 16 k of the limb (e0 = tile * 4096 + row * 256 + i0), or where the Galois automorphism sends them.
+// PAIR: at e0 + ks_own(k), e0 = tile * 4096 + row * 256 + 2 i0 (16-byte stores; the Galois scatter stays element-wise).
+template <bool PAIR = false>
 __device__ __forceinline__ void ks_tail_scatter(const KsMacArgs& a, int item, int slot, int p, u64 e0, const u64 (&r)[16])
 {
     const KsMacArgs::Tail& e = a.tail;
@@ -1270,17 +1339,17 @@ __device__ __forceinline__ void ks_tail_scatter(const KsMacArgs& a, int item, in
     if (e.galois_inv) {
 #pragma unroll
         for (int k = 0; k < 16; k++) {
-            const u32 el = (u32) e0 + 16 * k;
+            const u32 el = (u32) e0 + ks_own<PAIR>(k);
             const u32 ex = ((2u * (__brev(el) >> (32 - a.n_power)) + 1u) * e.galois_inv) & ((2u << a.n_power) - 1u);
             out[__brev((ex - 1u) >> 1) >> (32 - a.n_power)] = r[k];
         }
     } else {
-#pragma unroll
-        for (int k = 0; k < 16; k++) out[e0 + 16 * k] = r[k];
+        ks_st16<PAIR>(out + e0, r);
     }
 }
 // Integer moduli: acc / tv = the thread's 16 canonical accumulated / transformed-P-limb residues, cv the added term if
 // with_ct.  The residues of row_store_all.
+template <bool PAIR = false>
 __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int slot, int p, u64 e0, const Mod& md, u64 inv,
                                               const u64 (&acc)[16], const u64 (&tv)[16], bool with_ct, const u64 (&cv)[16])
 {
@@ -1291,7 +1360,7 @@ __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int 
 #pragma unroll
         for (int k = 0; k < 16; k++) r[k] = add_mod(cv[k], r[k], md.q);
     }
-    ks_tail_scatter(a, item, slot, p, e0, r);
+    ks_tail_scatter<PAIR>(a, item, slot, p, e0, r);
 }
 // FP64 moduli (q < 2^50): the same residues, (acc - T) P^-1 + ct mod q, without leaving the doubles -- everything is
 // exact integer arithmetic modulo q, so the canonical result is the integer form's, bit for bit.  acc = the running
@@ -1309,6 +1378,7 @@ __device__ __forceinline__ void ks_tail_store(const KsMacArgs& a, int item, int 
 //       2^52 still gives the canonical residue of the exact sum -- the integer add_mod returned a non-canonical sum for a
 //       non-canonical ct); |t + ct| < 2.65 q + 2^52 < 2^53, exact; fp_canon takes that to [0, q).
 // tests/test_fp_model_tail.py derives these bounds, tests/test_gpu_fp_tail.py measures them in the instrumented build.
+template <bool PAIR = false>
 __device__ __forceinline__ void ks_tail_store_fp(const KsMacArgs& a, int item, int slot, int p, u64 e0, const FC& fc, double inv,
                                                  const double (&acc)[16], const double (&tv)[16], bool with_ct,
                                                  const u64 (&cv)[16])
@@ -1330,26 +1400,26 @@ __device__ __forceinline__ void ks_tail_store_fp(const KsMacArgs& a, int item, i
     u64 r[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) r[k] = fp_to_u64(fp_canon(m[k], fc));
-    ks_tail_scatter(a, item, slot, p, e0, r);
+    ks_tail_scatter<PAIR>(a, item, slot, p, e0, r);
 }
 // the tail's operands of part p: the column-pass output T (row stages still to do) and the added term
 __device__ __forceinline__ const u64* ks_tail_T(const KsMacArgs& a, int item, int slot, int tile, int p)
 {
     return a.tail.T + a.tail.T_item_stride * item + ((u64) (p * a.rc + slot) << a.n_power) + (u64) tile * 4096;
 }
+template <bool PAIR = false>
 __device__ __forceinline__ bool ks_tail_ct(const KsMacArgs& a, int item, int slot, int p, u64 e0, u64 (&cv)[16])
 {
     const KsMacArgs::Tail& e = a.tail;
     if (!e.ct || (e.ct_parts && p >= e.ct_parts)) return false;
     const u64* c = e.ct + e.ct_item_stride * item + ((u64) (p * e.limbs + slot) << a.n_power) + e0; // may alias out
-#pragma unroll
-    for (int k = 0; k < 16; k++) cv[k] = c[16 * k];
+    ks_ld16<PAIR>(cv, c);
     return true;
 }
 
 // (bodies shared by the kernels below; `twbuf`: KS_TW_LDS_BYTES of LDS for the digit-invariant twiddles)
 #define KS_TW_LDS_BYTES ((15 * 256 + 15 * 16) * 8)
-template <bool SPLIT, bool MD = false>
+template <bool SPLIT, bool MD = false, bool PAIR = false>
 __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const KsIdx& ki, const Mod& md, int midx,
                                                     u64* lds, void* twbuf)
 {
@@ -1363,7 +1433,7 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
     const ulonglong2* __restrict__ tb = a.twB + ((u64) midx * (15u << (a.n_power - 4))) + ((u64) crow * 15 * 16 + i0);
     const u64 n = (u64) 1 << a.n_power;
     const u64* __restrict__ pin = a.in + a.in_item_stride * item + ((u64) slot << a.n_power) + (u64) tile * 4096;
-    const u64* __restrict__ pk = a.key + ((u64) midx << a.n_power) + (u64) tile * 4096 + row * 256 + i0;
+    const u64* __restrict__ pk = a.key + ((u64) midx << a.n_power) + (u64) tile * 4096 + row * 256 + ks_own0<PAIR>(i0);
     const u64 dig_off = (u64) a.rc << a.n_power;
     const u64 key_off1 = (u64) a.key_limbs << a.n_power, key_off2 = (u64) a.key_limbs << (a.n_power + 1);
     // the un-reduced output (any 64-bit value) times a key residue (< q) summed over the digits has to fit 128 bits
@@ -1391,25 +1461,41 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
         const u64* p = pin + dig_off * i;
         if (a.skip_identity && i == midx) {
             const u64* pi = a.ident + a.ident_item_stride * item + ((u64) i << a.n_power) + (u64) tile * 4096;
+            if constexpr (PAIR) {
+                ks_ld16<true>(x, pi + row * 256 + 2 * i0);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 16; k++) x[k] = gld(&pi[row * 256 + i0 + 16 * k]);
+                for (int k = 0; k < 16; k++) x[k] = gld(&pi[row * 256 + i0 + 16 * k]);
+            }
         } else if (lazy) {
-            ks_row_digit<true>(x, p, lds, twa, tb, qc, md, row, i0);
+            ks_row_digit<true, 8, 0, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
         } else if (room16) {
-            if (ex == 16) ks_row_digit<false, 16, 16>(x, p, lds, twa, tb, qc, md, row, i0);
-            else if (ex == 12) ks_row_digit<false, 16, 12>(x, p, lds, twa, tb, qc, md, row, i0);
-            else if (ex == 8) ks_row_digit<false, 16, 8>(x, p, lds, twa, tb, qc, md, row, i0);
-            else ks_row_digit<false, 16>(x, p, lds, twa, tb, qc, md, row, i0);
+            if (ex == 16) ks_row_digit<false, 16, 16, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
+            else if (ex == 12) ks_row_digit<false, 16, 12, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
+            else if (ex == 8) ks_row_digit<false, 16, 8, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
+            else ks_row_digit<false, 16, 0, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
         } else {
-            if (ex) ks_row_digit<false, 8, 8>(x, p, lds, twa, tb, qc, md, row, i0);
-            else ks_row_digit<false>(x, p, lds, twa, tb, qc, md, row, i0);
+            if (ex) ks_row_digit<false, 8, 8, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
+            else ks_row_digit<false, 8, 0, PAIR>(x, p, lds, twa, tb, qc, md, row, i0);
         }
         const u64* k0 = pk + key_off2 * i;
         const u64* k1 = k0 + key_off1;
+        if constexpr (PAIR) {
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-            acc128(h0[k], l0[k], x[k], k0[16 * k]);
-            acc128(h1[k], l1[k], x[k], k1[16 * k]);
+            for (int m = 0; m < 8; m++) {
+                const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(k0 + 32 * m);
+                const ulonglong2 v1 = *reinterpret_cast<const ulonglong2*>(k1 + 32 * m);
+                acc128(h0[2 * m], l0[2 * m], x[2 * m], v0.x);
+                acc128(h1[2 * m], l1[2 * m], x[2 * m], v1.x);
+                acc128(h0[2 * m + 1], l0[2 * m + 1], x[2 * m + 1], v0.y);
+                acc128(h1[2 * m + 1], l1[2 * m + 1], x[2 * m + 1], v1.y);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                acc128(h0[k], l0[k], x[k], k0[16 * k]);
+                acc128(h1[k], l1[k], x[k], k1[16 * k]);
+            }
         }
     }
     if constexpr (MD) {
@@ -1424,24 +1510,24 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
         int tt = threadIdx.x; // (see ks_row_mac_fp_body)
         asm volatile("" : "+v"(tt));
         const int trow = tt >> 4, ti0 = tt & 15;
-        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
+        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ks_own0<PAIR>(ti0);
         const u64 inv = a.tail.inv[midx_s];
         const bool lazy_t = row_stages_lazy(md, a.lazy_q_max);
         const ulonglong2* __restrict__ ttb = a.twB + ((u64) midx_s * (15u << (a.n_power - 4))) + ((u64) (tile_s * 16 + trow) * 15 * 16 + ti0);
         auto part = [&](int p, const u64 (&acc)[16]) {
             u64 cv[16], x[16];
-            const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
+            const bool with_ct = ks_tail_ct<PAIR>(a, item_s, slot_s, p, e0, cv);
             const u64* pT = ks_tail_T(a, item_s, slot_s, tile_s, p);
             if (lazy_t) {
-                ks_row_digit<true>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
+                ks_row_digit<true, 8, 0, PAIR>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
 #pragma unroll
                 for (int k = 0; k < 16; k++) x[k] = reduce64(x[k], md);
             } else if (room16) {
-                ks_row_digit<false, 16>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
+                ks_row_digit<false, 16, 0, PAIR>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
             } else {
-                ks_row_digit<false>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
+                ks_row_digit<false, 8, 0, PAIR>(x, pT, lds, twa, ttb, qc, md, trow, ti0);
             }
-            ks_tail_store(a, item_s, slot_s, p, e0, md, inv, acc, x, with_ct, cv);
+            ks_tail_store<PAIR>(a, item_s, slot_s, p, e0, md, inv, acc, x, with_ct, cv);
         };
         __builtin_amdgcn_sched_barrier(0);
         part(0, acc0);
@@ -1449,14 +1535,29 @@ __device__ __forceinline__ void ks_row_mac_int_body(const KsMacArgs& a, const Ks
         part(1, acc1);
         return;
     }
-    // split launches: the partial sums over the first two digits of this workgroup's own range (KsMacArgs::splits)
-    u64* po = (SPLIT ? const_cast<u64*>(pin) + dig_off * ki.d0 - (u64) tile * 4096
-                     : a.out + a.out_item_stride * item + ((u64) slot << a.n_power)) +
-              (u64) tile * 4096 + row * 256 + i0;
+    if constexpr (PAIR) {
+        // (no split launches) the lane's store address from an opaque copy of the thread index, as the tail forms its
+        // indices: kept from before the digit loop it is the one value that does not fit two waves per SIMD
+        int tt = threadIdx.x;
+        asm volatile("" : "+v"(tt));
+        u64* pw = a.out + a.out_item_stride * item + ((u64) slot << a.n_power) + (u64) tile * 4096 + (tt >> 4) * 256 + 2 * (tt & 15);
 #pragma unroll
-    for (int k = 0; k < 16; k++) {
-        po[16 * k] = reduce128(h0[k], l0[k], md);
-        po[dig_off + 16 * k] = reduce128(h1[k], l1[k], md);
+        for (int m = 0; m < 8; m++) {
+            *reinterpret_cast<ulonglong2*>(pw + 32 * m) =
+                make_ulonglong2(reduce128(h0[2 * m], l0[2 * m], md), reduce128(h0[2 * m + 1], l0[2 * m + 1], md));
+            *reinterpret_cast<ulonglong2*>(pw + dig_off + 32 * m) =
+                make_ulonglong2(reduce128(h1[2 * m], l1[2 * m], md), reduce128(h1[2 * m + 1], l1[2 * m + 1], md));
+        }
+    } else {
+        // split launches: the partial sums over the first two digits of this workgroup's own range (KsMacArgs::splits)
+        u64* po = (SPLIT ? const_cast<u64*>(pin) + dig_off * ki.d0 - (u64) tile * 4096
+                         : a.out + a.out_item_stride * item + ((u64) slot << a.n_power)) +
+                  (u64) tile * 4096 + row * 256 + i0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            po[16 * k] = reduce128(h0[k], l0[k], md);
+            po[dig_off + 16 * k] = reduce128(h1[k], l1[k], md);
+        }
     }
     (void) n;
 }
@@ -1477,7 +1578,7 @@ __global__ __launch_bounds__(NTT_THREADS, SPLIT ? 2 : 1) void ks_row_mac(KsMacAr
 // Row stages of one FP64 limb tile in a ks_row_mac_fp workgroup: xr = the thread's 16 column-pass outputs (raw
 // doubles, |x| <= q / 2) of row `row`, lanes i0 + 16 k; x = the transformed values at the same positions, un-reduced
 // (|x| <= 5.22 q).  `twl`: the parked twiddles (see ks_row_mac_fp_body).
-template <bool SPLIT>
+template <bool SPLIT, bool PAIR = false>
 __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], const double* twl, u64* lds, const FC& fc,
                                           int s1, int row, int i0, int t)
 {
@@ -1602,8 +1703,15 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
         *reinterpret_cast<ulonglong2*>(&lds[row_phys(row * 256 + 16 * i0 + 2 * k)]) =
             make_ulonglong2(as_bits(x[2 * k]), as_bits(x[2 * k + 1]));
     wave_lds_fence();
+    if constexpr (PAIR) {
+        u64 xb[16];
+        ks_own_read<true>(xb, lds, row, i0);
 #pragma unroll
-    for (int k = 0; k < 16; k++) x[k] = as_f64(lds[row_phys(row * 256 + i0 + 16 * k)]);
+        for (int k = 0; k < 16; k++) x[k] = as_f64(xb[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; k++) x[k] = as_f64(lds[row_phys(row * 256 + i0 + 16 * k)]);
+    }
     wave_lds_fence();
 }
 
@@ -1613,7 +1721,7 @@ __device__ __forceinline__ void ks_fp_row(double (&x)[16], const u64 (&xr)[16], 
 // re-centred after every third digit (|acc| <= 7.88 q < 2^53) and made canonical once at the end.
 // Two double accumulators per coefficient instead of two 128-bit integers
 // halve the register footprint (3 waves per SIMD instead of 2).
-template <bool SPLIT, bool MD = false>
+template <bool SPLIT, bool MD = false, bool PAIR = false>
 __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsIdx& ki, const Mod& md, int midx,
                                                    u64* lds, void* twbuf)
 {
@@ -1626,7 +1734,7 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
     const u32 crow = tile * 16 + row;
     const double* __restrict__ tb8 = a.twB8 + ((u64) midx * (15u << (a.n_power - 4))) + ((u64) crow * 15 * 16 + i0);
     const u64* __restrict__ pin = a.in + a.in_item_stride * item + ((u64) slot << a.n_power) + (u64) tile * 4096;
-    const u64* __restrict__ pk = a.key + ((u64) midx << a.n_power) + (u64) tile * 4096 + row * 256 + i0;
+    const u64* __restrict__ pk = a.key + ((u64) midx << a.n_power) + (u64) tile * 4096 + row * 256 + ks_own0<PAIR>(i0);
     const u64 dig_off = (u64) a.rc << a.n_power;
     const u64 key_off1 = (u64) a.key_limbs << a.n_power, key_off2 = (u64) a.key_limbs << (a.n_power + 1);
 
@@ -1669,27 +1777,44 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
         const bool ident = a.skip_identity && i == midx;
         const u64* px = ident ? a.ident + a.ident_item_stride * item + ((u64) i << a.n_power) + (u64) tile * 4096 : p;
         u64 xr[16];
+        if (PAIR && ident) {
+            // the identity limb is not transformed: read in the ownership the products use
+            ks_ld16<PAIR, true>(xr, px + row * 256 + 2 * i0);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-            // (large-launch form: the digits are read exactly once -- non-temporal; the key tile next to them is what the
-            // ciphertexts of a group share through L2.  With the stores below: 8.16 -> 8.03 ms per C4 step, same-box A/B)
-            if constexpr (!SPLIT) xr[k] = __builtin_nontemporal_load(&px[row * 256 + i0 + 16 * k]);
-            else xr[k] = px[row * 256 + i0 + 16 * k];
+            for (int k = 0; k < 16; k++) {
+                // (large-launch form: the digits are read exactly once -- non-temporal; the key tile next to them is what the
+                // ciphertexts of a group share through L2.  With the stores below: 8.16 -> 8.03 ms per C4 step, same-box A/B)
+                if constexpr (!SPLIT) xr[k] = __builtin_nontemporal_load(&px[row * 256 + i0 + 16 * k]);
+                else xr[k] = px[row * 256 + i0 + 16 * k];
+            }
         }
         const u64* k0 = pk + key_off2 * i;
         const u64* k1 = k0 + key_off1;
         u64 kv0[16], kv1[16];
+        if constexpr (PAIR) {
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-            kv0[k] = k0[16 * k];
-            kv1[k] = k1[16 * k];
+            for (int m = 0; m < 8; m++) {
+                const ulonglong2 v0 = *reinterpret_cast<const ulonglong2*>(k0 + 32 * m);
+                const ulonglong2 v1 = *reinterpret_cast<const ulonglong2*>(k1 + 32 * m);
+                kv0[2 * m] = v0.x;
+                kv0[2 * m + 1] = v0.y;
+                kv1[2 * m] = v1.x;
+                kv1[2 * m + 1] = v1.y;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                kv0[k] = k0[16 * k];
+                kv1[k] = k1[16 * k];
+            }
         }
         if (ident) {
             FP_STAGE(fc, FP_STAGE_INPUT);
 #pragma unroll
             for (int k = 0; k < 16; k++) x[k] = fp_reduce(fp_from_u64_ldexp(xr[k]), fc);
         } else {
-            ks_fp_row<SPLIT>(x, xr, twl, lds, fc, s1, row, i0, t);
+            ks_fp_row<SPLIT, PAIR>(x, xr, twl, lds, fc, s1, row, i0, t);
         }
 #pragma unroll
         for (int k = 0; k < 16; k++) {
@@ -1730,7 +1855,7 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
         int tt = threadIdx.x;
         asm volatile("" : "+v"(tt));
         const int trow = tt >> 4, ti0 = tt & 15;
-        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ti0;
+        const u64 e0 = (u64) tile_s * 4096 + trow * 256 + ks_own0<PAIR>(ti0);
         // P^-1 mod q_j, wave-uniform; without a companion, as in the key products (fp_mul_nc)
         const double inv = fp_from_u64(a.tail.inv[midx_s]);
         auto part = [&](int p, const double (&acc)[16]) {
@@ -1738,10 +1863,10 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
             u64 tr[16], cv[16];
 #pragma unroll
             for (int k = 0; k < 16; k++) tr[k] = __builtin_nontemporal_load(&pT[trow * 256 + ti0 + 16 * k]);
-            const bool with_ct = ks_tail_ct(a, item_s, slot_s, p, e0, cv);
+            const bool with_ct = ks_tail_ct<PAIR>(a, item_s, slot_s, p, e0, cv);
             double x[16];
-            ks_fp_row<false>(x, tr, twl, lds, fc, s1, trow, ti0, tt);
-            ks_tail_store_fp(a, item_s, slot_s, p, e0, fc, inv, acc, x, with_ct, cv);
+            ks_fp_row<false, PAIR>(x, tr, twl, lds, fc, s1, trow, ti0, tt);
+            ks_tail_store_fp<PAIR>(a, item_s, slot_s, p, e0, fc, inv, acc, x, with_ct, cv);
         };
         __builtin_amdgcn_sched_barrier(0); // (one part at a time: the loads of the second are not hoisted into the first)
         part(0, a0);
@@ -1751,8 +1876,19 @@ __device__ __forceinline__ void ks_row_mac_fp_body(const KsMacArgs& a, const KsI
     }
     u64* po = (SPLIT ? const_cast<u64*>(pin) + dig_off * ki.d0 - (u64) tile * 4096
                      : a.out + a.out_item_stride * item + ((u64) slot << a.n_power)) +
-              (u64) tile * 4096 + row * 256 + i0;
+              (u64) tile * 4096 + row * 256 + ks_own0<PAIR>(i0);
     FP_STAGE(fc, FP_STAGE_OUT);
+    if constexpr (PAIR) {
+        u64 r0[16], r1[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) {
+            r0[k] = fp_to_u64(fp_canon(a0[k], fc));
+            r1[k] = fp_to_u64(fp_canon(a1[k], fc));
+        }
+        ks_st16<true, !SPLIT>(po, r0);
+        ks_st16<true, !SPLIT>(po + dig_off, r1);
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         if constexpr (!SPLIT) {
@@ -1802,6 +1938,37 @@ __global__ __launch_bounds__(NTT_THREADS, 1) void ks_row_mac_moddown(KsMacArgs a
     ks_row_mac_int_body<false, true>(a, ki, md, midx, lds, twa);
 }
 
+// The wide forms of the four kernels above (KsMacArgs::wide): the same bodies in the pair ownership (ks_own), every
+// global access of the products, the tail and the stores 16 bytes per lane.  MD: with the mod-down tail.  Kernels of
+// their own, so that the natural forms keep their names, registers and launches when the option is off.
+// All four state two workgroups per CU (two waves per SIMD).  The natural integer kernels state one and come out at
+// two; so do the wide ones (250 / 256 registers with the bound at one or two), but at exactly 256 registers nothing is
+// left over: stated, a later change cannot trade the second wave for AGPRs unnoticed (tests/test_kernel_budgets_wide.py).
+template <bool MD>
+__global__ __launch_bounds__(NTT_THREADS, 2) void ks_pair_mac_fp(KsMacArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[ROW_LDS_ELEMS];
+    __shared__ double twl[15 * 256 + 15 * 16];
+    const KsIdx ki = ks_index<false, 2>(a);
+    if (!ki.valid) return;
+    const int midx = a.mod_order ? a.mod_order[ki.slot] : ki.slot;
+    const Mod md = a.mods[midx];
+    if (!md.fp) return;
+    ks_row_mac_fp_body<false, MD, true>(a, ki, md, midx, lds, twl);
+}
+template <bool MD>
+__global__ __launch_bounds__(NTT_THREADS, 2) void ks_pair_mac(KsMacArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[ROW_LDS_ELEMS];
+    __shared__ ulonglong2 twa[15 * 16];
+    const KsIdx ki = ks_index<false, 1>(a);
+    if (!ki.valid) return;
+    const int midx = a.mod_order ? a.mod_order[ki.slot] : ki.slot;
+    const Mod md = a.mods[midx];
+    if (md.fp) return;
+    ks_row_mac_int_body<false, MD, true>(a, ki, md, midx, lds, twa);
+}
+
 // Split launches are small launches (fewer workgroups than the chip holds, or barely more): the integer and the
 // FP64 moduli of a chain in ONE grid instead of two half-empty ones one after the other -- at N = 2^16, one
 // ciphertext, four pieces the two kernels took 87 + 58 us (the two integer moduli of the chain alone 58: 128
@@ -1818,6 +1985,12 @@ __global__ __launch_bounds__(NTT_THREADS, 2) void ks_row_mac_split(KsMacArgs a)
     else ks_row_mac_int_body<true>(a, ki, md, midx, lds, twl);
 }
 
+static std::atomic<unsigned long long> g_ks_forms[3];
+void ks_row_mac_launch_counts(unsigned long long out[3])
+{
+    for (int i = 0; i < 3; i++) out[i] = g_ks_forms[i].load(std::memory_order_relaxed);
+}
+
 hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st)
 {
     if (a.digits > 64 || items <= 0) return hipErrorInvalidValue;
@@ -1830,8 +2003,25 @@ hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st)
     if (k.int_slot_count < 0 || k.int_slot_count > 8) k.int_slot_count = 0;
     const unsigned tiles = (1u << a.n_power) / 4096, units = (unsigned) items * (a.splits > 1 ? (unsigned) a.splits : 1u);
     auto grid_of = [&](int kind) { return dim3(8u * ((ks_slots(k, kind) * tiles * units + 7u) / 8u)); };
+    // the wide forms move pairs: every operand they touch pairwise on a 16-byte boundary, every item stride even
+    // (offsets inside an item are multiples of N); anything else takes the natural forms -- same residues
+    auto pair_ok = [](const void* p, u64 stride) { return !(reinterpret_cast<uintptr_t>(p) & 15u) && !(stride & 1u); };
+    const bool wide = a.wide && a.splits <= 1 && pair_ok(a.key, 0) &&
+                      (a.tail.on ? pair_ok(a.tail.out, a.tail.out_item_stride) && pair_ok(a.tail.ct, a.tail.ct_item_stride)
+                                 : pair_ok(a.out, a.out_item_stride)) &&
+                      (!a.skip_identity || pair_ok(a.ident, a.ident_item_stride));
+    g_ks_forms[a.splits > 1 ? 2 : wide ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
     if (a.splits > 1) {
         hipLaunchKernelGGL(ks_row_mac_split, grid_of(0), dim3(NTT_THREADS), 0, st, k);
+    } else if (wide) {
+        if (!a.no_fp && ks_slots(k, 2) > 0) {
+            if (a.tail.on) hipLaunchKernelGGL(ks_pair_mac_fp<true>, grid_of(2), dim3(NTT_THREADS), 0, st, k);
+            else hipLaunchKernelGGL(ks_pair_mac_fp<false>, grid_of(2), dim3(NTT_THREADS), 0, st, k);
+        }
+        if (!a.no_int && ks_slots(k, 1) > 0) {
+            if (a.tail.on) hipLaunchKernelGGL(ks_pair_mac<true>, grid_of(1), dim3(NTT_THREADS), 0, st, k);
+            else hipLaunchKernelGGL(ks_pair_mac<false>, grid_of(1), dim3(NTT_THREADS), 0, st, k);
+        }
     } else {
         // each kernel over the slots of its kind where the caller named them, else over all (the other kind exits)
         if (!a.no_fp && ks_slots(k, 2) > 0) {

@@ -226,6 +226,12 @@ struct KsMacArgs {
     // Integer moduli on the correcting butterflies: the digits' transforms enter the 128-bit sums un-reduced, below
     // unreduced_exit * q (ks_unreduced_exit of the launch: 16, 12 or 8), or canonical (0).
     int unreduced_exit;
+    // 1: the wide row kernels (Context::wide_access; launches without digit splits only).  Past its row stages a thread
+    // owns the element pairs 2 i0 + 32 m + {0, 1} of its row instead of the elements i0 + 16 k, so the key tiles, the
+    // identity limb, the tail's added ciphertext and the results move in 16-byte accesses, 16 lanes covering two whole
+    // 128-byte lines.  Same residues at the same addresses; ks_row_mac_launch falls back to the natural ownership
+    // where a pointer or a stride is not 16-byte aligned.
+    int wide;
     // Optional mod-down tail (method I, one special prime P; the counterpart of NttEpilogue): the accumulated limb acc
     // of part p, slot k (modulus q_k) is not stored; instead
     //     out = (acc - T) * inv[q_k] + ct   (ct for parts below ct_parts only; 0: every part)
@@ -247,6 +253,8 @@ struct KsMacArgs {
     } tail;
 };
 hipError_t ks_row_mac_launch(const KsMacArgs& a, int items, hipStream_t st);
+// launches of ks_row_mac_launch in this process so far by the form it chose: [0] natural, [1] wide, [2] split
+void ks_row_mac_launch_counts(unsigned long long out[3]);
 // The bound (units of q) below which the row stages of a correcting integer modulus may leave a key-switch digit for
 // the 128-bit inner product: the largest B of 16, 12, 8 with digits * B * q * q < 2^128 for every q < 2^q_bits (key
 // residues canonical), 0 if there is none.  `digits`: the most a workgroup sums; `q_bits`: bit length of the launch's

@@ -161,6 +161,7 @@ static hipError_t keyswitch_ntt_mac(const Context& c, NttArgs a, const u64* key,
         k.lazy_q_max = a.lazy_q_max; k.n_power = c.n_power; k.digits = digits; k.rc = rc; k.key_limbs = c.Qp_size; k.skip_identity = skip_identity;
         k.ident = ident ? ident + (u64) b0 * ident_stride : nullptr; k.ident_item_stride = ident_stride;
         k.splits = splits;
+        k.wide = c.wide_access && splits <= 1;
         k.no_fp = !a.plan_has_fp;
         k.no_int = !a.plan_has_int || a.int_slot_count < 0;
         k.int_slot_count = a.int_slot_count > 0 ? a.int_slot_count : 0;

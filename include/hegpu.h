@@ -87,6 +87,9 @@ void hegpu_context_destroy(hegpu_context* ctx);
  *   "fused_tensor"   0/1     BFV multiply: the tensor product as the load transform of the inverse transform (1)
  *   "moddown_in_mac" 0/1     CKKS key switching with one special prime, fused path: the mod-down applied by the
  *                            inner-product kernels to their sums (1) / by the row pass of its own transform
+ *   "wide_access"    0/1     fused key switch without digit splits: the inner-product kernels read the key, the
+ *                            identity limb and the added ciphertext and write their results 16 bytes per lane (1) /
+ *                            8 bytes per lane, the launches of the releases before the option (0)
  * Every option but "fp_ntt" may be changed at any time, but not concurrently with calls on the same context.  The
  * environment variables HEGPU_<NAME IN CAPITALS> seed the defaults once, when a context is created; no call path
  * reads the environment.  Unknown name / value out of range: HEGPU_E_INVALID. */

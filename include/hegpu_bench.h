@@ -16,6 +16,10 @@ extern "C" {
 int hegpu_probe_ckks_relinearize(hegpu_context* ctx, uint64_t* ct, uint64_t ct_stride, const uint64_t* relin_key,
                                  int depth, int batch, void* ws, size_t ws_bytes, unsigned phases,
                                  hegpu_stream stream);
+/* How many launches of the fused row pass + inner product this process has made so far, by the form the launcher chose:
+ * counts[0] the natural kernels (8-byte accesses), counts[1] the wide kernels (context option "wide_access", every
+ * operand 16-byte aligned), counts[2] the split kernel.  Tests take the difference around a call. */
+void hegpu_probe_ks_launch_forms(uint64_t counts[3]);
 #ifdef __cplusplus
 }
 #endif
