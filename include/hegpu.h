@@ -14,6 +14,9 @@
  *    coeff + (limb << n_power) + part * (limbs << n_power);
  *  - batched calls take `batch` ciphertexts `*_stride` ELEMENTS apart (batch == 0: nothing is launched, the call
  *    succeeds; batch < 0: an error);
+ *  - operands (workspaces and keys included) need the alignment of their element type only, and any item stride not
+ *    smaller than the item works, odd ones included.  Alignment to 16 bytes and even strides select the faster
+ *    launch forms; results are identical either way;
  *  - every call is asynchronous on `stream`; return value 0 = success,
  *    otherwise a hipError_t code (or HEGPU_E_* below); hegpu_last_error()
  *    returns a message for the calling thread;

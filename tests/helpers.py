@@ -24,6 +24,48 @@ def synth_key(primes, Q, Qp, n, seed):
     return out.reshape(-1)
 
 
+SENTINEL = 0x5555555555555555
+# operand layouts (lead, pad) of laid_out: today's packed layout as the control, every item 8 bytes off a 16-byte
+# boundary, items that alternate between the two inside one launch, and that alternation starting misaligned
+LAYOUTS = {"packed": (0, 0), "off8": (1, 1000), "odd": (0, 1), "off8_odd": (1, 1001)}
+
+
+def laid_out(items, lead, pad, guard=2):
+    """One device buffer: `guard` sentinel words, `lead` (0 or 1) more, the items (equally long uint64 arrays)
+    len(item) + pad words apart with sentinels in the gaps, `guard` sentinel words behind the last item.
+    Returns (view from the first item on, item stride in words, intact): view.data_ptr() % 16 == 8 * lead, and intact()
+    is true while every sentinel word -- the one right in front of the first item included -- still holds."""
+    import torch
+    import heongpu_amd as hg
+    assert lead in (0, 1) and guard >= 2 and guard % 2 == 0 and pad >= 0
+    items = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in items]
+    words = len(items[0])
+    assert all(len(x) == words for x in items)
+    stride, front = words + pad, guard + lead
+    host = np.full(front + (len(items) - 1) * stride + words + guard, SENTINEL, dtype=np.uint64)
+    mask = np.ones(len(host), dtype=bool)
+    for i, x in enumerate(items):
+        host[front + i * stride:front + i * stride + words] = x
+        mask[front + i * stride:front + i * stride + words] = False
+    buf = hg.to_device(host)
+    assert buf.data_ptr() % 16 == 0
+    where = torch.from_numpy(np.flatnonzero(mask)).to(buf.device)
+    view = buf[front:len(host) - guard]
+    assert view.data_ptr() % 16 == 8 * lead
+
+    def intact():
+        return bool((buf[where] == SENTINEL).all())
+
+    return view, stride, intact
+
+
+def items_of(view, stride, words, count):
+    """the `count` items of a laid_out view back on the host: [count][words] uint64"""
+    import heongpu_amd as hg
+    got = hg.to_host(view)
+    return np.stack([got[i * stride:i * stride + words] for i in range(count)])
+
+
 import contextlib  # noqa: E402
 
 
