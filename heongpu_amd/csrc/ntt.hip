@@ -78,6 +78,13 @@ __device__ __forceinline__ int ld_const_i32(const int* p)
     return *(const int __attribute__((address_space(4)))*) p;
 #pragma clang diagnostic pop
 }
+__device__ __forceinline__ u64 ld_const_u64(const u64* p)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return *(const u64 __attribute__((address_space(4)))*) p;
+#pragma clang diagnostic pop
+}
 __device__ __forceinline__ Mod ld_const_mod(const Mod* p)
 {
 #pragma clang diagnostic push
@@ -559,8 +566,12 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
 
     // half_on (mod-down stage one as a load transform): exact residue, the butterflies' input
     // range does not cover v + q - half_mod for a 60-bit source modulus
-    const u64 half_qP = a.half_on ? a.mods[a.half_src_mod].q : 0;
-    const u64 half_hm = a.half_on ? a.half_mod[ps.mod] : 0;
+    // (SREG = inside a modulus loop with stores in it: the launch-constant words through the scalar cache.  As plain
+    // loads they are vector loads, and the s_waitcnt vmcnt(0) of each -- at the head of the body, right behind the
+    // sixteen stores of the previous target -- waits until every one of those stores has been acknowledged.)
+    const u64 half_qP = (a.half_on && !SREG) ? a.mods[a.half_src_mod].q : 0;
+    const u64 half_hm = a.half_on ? (SREG ? ld_const_u64(a.half_mod + ps.mod) : a.half_mod[ps.mod]) : 0;
+    auto digit_q = [&]() { return SREG ? ld_const_u64(&a.mods[ps.digit].q) : a.mods[ps.digit].q; };
     // all 16 loads in one block, then (uniform condition, one branch) the mod-down load transform: a branch per
     // element would serialise the loads -- one memory latency each
     u64 x[16];
@@ -582,7 +593,7 @@ __device__ __forceinline__ void fwd_col_body(const NttArgs& a, const PolySel& ps
         // (SREG: the half is already added, as for the FP64 body)
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = sub_mod(reduce64(SREG ? v[k] : add_mod(v[k], a.half, half_qP), md), half_hm, md.q);
-    } else if (DECOMP && !LAZY && a.mods[ps.digit].q > 8 * md.q) {
+    } else if (DECOMP && !LAZY && digit_q() > 8 * md.q) {
         // a digit of a much wider prime (61 bits next to 58): outside the [0, 8q) the correcting butterflies keep
 #pragma unroll
         for (int k = 0; k < 16; k++) v[k] = reduce64(v[k], md);
@@ -653,12 +664,15 @@ __device__ __forceinline__ void fwd_col_body_fp(const NttArgs& a, const PolySel&
         c32 = (double) reduce64(1ull << 32, md);
         c32i = c32 * fc.qi;
     }
-    const u64 half_qP = (DECOMP && a.half_on) ? a.mods[a.half_src_mod].q : 0;
-    const double half_hm = (DECOMP && a.half_on) ? fp_from_u64(a.half_mod[ps.mod]) : 0.0;
+    // (SREG: the launch-constant words of this body through the scalar cache, as in fwd_col_body)
+    const u64 half_qP = (DECOMP && a.half_on && !SREG) ? a.mods[a.half_src_mod].q : 0;
+    const double half_hm =
+        (DECOMP && a.half_on) ? fp_from_u64(SREG ? ld_const_u64(a.half_mod + ps.mod) : a.half_mod[ps.mod]) : 0.0;
+    auto digit_q = [&]() { return SREG ? ld_const_u64(&a.mods[ps.digit].q) : a.mods[ps.digit].q; };
     // plain decomposition of a digit whose prime is at most 1/64 above this modulus: no input reduction (FpSched)
     // (not at S1 = 7: the second form of the load loops costs ntt_fwd_col_multi<7> sixteen registers and with them its
     // fourth wave per SIMD, which the integer limbs of the same kernel use -- tests/test_kernel_budgets.py)
-    const bool in_small = S1 != 7 && DECOMP && !WIDE && !a.half_on && a.mods[ps.digit].q <= md.q + (md.q >> 6);
+    const bool in_small = S1 != 7 && DECOMP && !WIDE && !a.half_on && digit_q() <= md.q + (md.q >> 6);
     typedef FpColSched<S1> CS;
     // SREG: `sreg` holds the thread's 16 source coefficients, the mod-down half already added: for a
     // source modulus of at most 52 bits as the bits of the converted double, for a wider one as u64
@@ -2544,6 +2558,15 @@ __device__ __forceinline__ void fwd_col_multi_body(const NttArgs& a, u64* lds, u
     if (!wide) {
 #pragma unroll
         for (int k = 0; k < 16; k++) sreg[k] = as_bits(fp_from_u64(sreg[k]));
+    } else {
+        // The source has to have landed before the loop on this path too.  The compiler places the waits of the loop for
+        // all the ways into it: with loads still in flight on one of them, every iteration waits for "the source" where
+        // it first reads it -- with vmcnt(0) in the end, which from the second iteration on is a wait for the sixteen
+        // stores of the previous target.  (The empty asm only makes the compiler wait here.  Nothing tests what it buys:
+        // after a change of toolchain read the loop's s_waitcnt again from the ISA -- the one vmcnt wait of an iteration
+        // is the one in front of the ds_write_b128 of the twiddle slice.)
+#pragma unroll
+        for (int k = 0; k < 16; k++) asm volatile("" : "+v"(sreg[k]));
     }
     // target slot k of this digit
     auto target = [&](int k) {
