@@ -63,6 +63,19 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ws_bytes(ws):
+    """the size in bytes of a workspace tensor"""
+    return ws.numel() * ws.element_size()
+
+
+class _Handle:
+    """A handle of the C ABI (self._lib, self._h) and the one path of its stream-ordered calls."""
+
+    def _call(self, name, *args, stream=None):
+        """hegpu_<name>(handle, *args, stream), the code checked; stream None: torch's current stream"""
+        _check(getattr(self._lib, "hegpu_" + name)(self._h, *args, stream if stream is not None else _stream()))
+
+
 def to_device(arr, device="cuda"):
     import torch
     a = np.ascontiguousarray(arr, dtype=np.uint64)
@@ -129,7 +142,7 @@ def broadcast_bytes(devices, bufs, nbytes, streams=None):
     return int(path.value)
 
 
-class Context:
+class Context(_Handle):
     """HEContext<BFV|CKKS>: parameter set + device tables."""
 
     def __init__(self, handle):
@@ -256,128 +269,108 @@ class Context:
     # -- NTT seam --
     def ntt(self, src, dst, inverse, batch, mod_count, mod_offset=0, mod_order=None, poly_order=None,
             table_set=TABLES_QP, stream=None):
-        _check(self._lib.hegpu_ntt(self._h, table_set, _ptr(src), _ptr(dst), int(inverse), batch, mod_count,
-                                   mod_offset, _ptr(mod_order), _ptr(poly_order),
-                                   stream if stream is not None else _stream()))
+        self._call("ntt", table_set, _ptr(src), _ptr(dst), int(inverse), batch, mod_count, mod_offset, _ptr(mod_order),
+                   _ptr(poly_order), stream=stream)
 
     # -- kernels --
     def addition(self, a, b, out, limbs, parts, batch=1, op=0, stream=None):
-        _check(self._lib.hegpu_addition(self._h, _ptr(a), _ptr(b), _ptr(out), limbs, parts, batch, op,
-                                        stream if stream is not None else _stream()))
+        self._call("addition", _ptr(a), _ptr(b), _ptr(out), limbs, parts, batch, op, stream=stream)
 
     def cross_multiplication(self, in1, s1, in2, s2, out, so, decomp_size, batch=1, table_set=TABLES_QP,
                              stream=None):
-        _check(self._lib.hegpu_cross_multiplication(self._h, table_set, _ptr(in1), s1, _ptr(in2), s2, _ptr(out),
-                                                    so, decomp_size, batch,
-                                                    stream if stream is not None else _stream()))
+        self._call("cross_multiplication", table_set, _ptr(in1), s1, _ptr(in2), s2, _ptr(out), so, decomp_size, batch,
+                   stream=stream)
 
     def cipher_broadcast(self, src, s_in, out, s_out, digits, nmods, split, level, batch=1, stream=None):
-        _check(self._lib.hegpu_cipher_broadcast(self._h, _ptr(src), s_in, _ptr(out), s_out, digits, nmods, split,
-                                                level, batch, stream if stream is not None else _stream()))
+        self._call("cipher_broadcast", _ptr(src), s_in, _ptr(out), s_out, digits, nmods, split, level, batch,
+                   stream=stream)
 
     def keyswitch_multiply_accumulate(self, src, s_in, key, out, s_out, digits, nmods, key_limbs, split, level,
                                       batch=1, stream=None):
-        _check(self._lib.hegpu_keyswitch_multiply_accumulate(self._h, _ptr(src), s_in, _ptr(key), _ptr(out), s_out,
-                                                             digits, nmods, key_limbs, split, level, batch,
-                                                             stream if stream is not None else _stream()))
+        self._call("keyswitch_multiply_accumulate", _ptr(src), s_in, _ptr(key), _ptr(out), s_out, digits, nmods,
+                   key_limbs, split, level, batch, stream=stream)
 
     def base_conversion_DtoQtilde(self, src, s_in, out, s_out, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_base_conversion_DtoQtilde(self._h, _ptr(src), s_in, _ptr(out), s_out, depth, batch,
-                                                         stream if stream is not None else _stream()))
+        self._call("base_conversion_DtoQtilde", _ptr(src), s_in, _ptr(out), s_out, depth, batch, stream=stream)
 
     def divide_round_lastq(self, src, s_in, ct, s_ct, out, s_out, switchkey=0, batch=1, stream=None):
-        _check(self._lib.hegpu_divide_round_lastq(self._h, _ptr(src), s_in, _ptr(ct), s_ct, _ptr(out), s_out,
-                                                  switchkey, batch, stream if stream is not None else _stream()))
+        self._call("divide_round_lastq", _ptr(src), s_in, _ptr(ct), s_ct, _ptr(out), s_out, switchkey, batch,
+                   stream=stream)
 
     def divide_round_lastq_permute(self, src, s_in, in2, s_in2, out, s_out, galois_elt, depth=0, batch=1,
                                    stream=None):
-        _check(self._lib.hegpu_divide_round_lastq_permute(self._h, _ptr(src), s_in, _ptr(in2), s_in2, _ptr(out),
-                                                          s_out, galois_elt, depth, batch,
-                                                          stream if stream is not None else _stream()))
+        self._call("divide_round_lastq_permute", _ptr(src), s_in, _ptr(in2), s_in2, _ptr(out), s_out, galois_elt, depth,
+                   batch, stream=stream)
 
     def divide_round_lastq_leveled_stage_one(self, src, s_in, out, s_out, rescale=0, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_divide_round_lastq_leveled_stage_one(self._h, _ptr(src), s_in, _ptr(out), s_out, rescale,
-                                                                    depth, batch,
-                                                                    stream if stream is not None else _stream()))
+        self._call("divide_round_lastq_leveled_stage_one", _ptr(src), s_in, _ptr(out), s_out, rescale, depth, batch,
+                   stream=stream)
 
     def divide_round_lastq_leveled_stage_two(self, last, s_last, src, s_in, ct, s_ct, out, s_out, switchkey=0, depth=0,
                                              batch=1, stream=None):
-        _check(self._lib.hegpu_divide_round_lastq_leveled_stage_two(self._h, _ptr(last), s_last, _ptr(src), s_in,
-                                                                    _ptr(ct), s_ct, _ptr(out), s_out, switchkey, depth,
-                                                                    batch, stream if stream is not None else _stream()))
+        self._call("divide_round_lastq_leveled_stage_two", _ptr(last), s_last, _ptr(src), s_in, _ptr(ct), s_ct,
+                   _ptr(out), s_out, switchkey, depth, batch, stream=stream)
 
     def move_cipher_leveled(self, src, s_in, out, s_out, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_move_cipher_leveled(self._h, _ptr(src), s_in, _ptr(out), s_out, depth, batch,
-                                                   stream if stream is not None else _stream()))
+        self._call("move_cipher_leveled", _ptr(src), s_in, _ptr(out), s_out, depth, batch, stream=stream)
 
     def divide_round_lastq_rescale(self, last, s_last, src, s_in, out, s_out, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_divide_round_lastq_rescale(self._h, _ptr(last), s_last, _ptr(src), s_in, _ptr(out), s_out,
-                                                          depth, batch, stream if stream is not None else _stream()))
+        self._call("divide_round_lastq_rescale", _ptr(last), s_last, _ptr(src), s_in, _ptr(out), s_out, depth, batch,
+                   stream=stream)
 
     def divide_round_lastq_extended(self, src, s_in, ct, s_ct, out, s_out, mode=0, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_divide_round_lastq_extended(self._h, _ptr(src), s_in, _ptr(ct) if ct is not None else None,
-                                                           s_ct, _ptr(out), s_out, mode, depth, batch,
-                                                           stream if stream is not None else _stream()))
+        self._call("divide_round_lastq_extended", _ptr(src), s_in, _ptr(ct) if ct is not None else None, s_ct,
+                   _ptr(out), s_out, mode, depth, batch, stream=stream)
 
     def fast_convertion(self, in1, s1, in2, s2, out, so, batch=1, stream=None):
-        _check(self._lib.hegpu_fast_convertion(self._h, _ptr(in1), s1, _ptr(in2), s2, _ptr(out), so, batch,
-                                               stream if stream is not None else _stream()))
+        self._call("fast_convertion", _ptr(in1), s1, _ptr(in2), s2, _ptr(out), so, batch, stream=stream)
 
     def fast_floor(self, src, si, out, so, batch=1, stream=None):
-        _check(self._lib.hegpu_fast_floor(self._h, _ptr(src), si, _ptr(out), so, batch,
-                                          stream if stream is not None else _stream()))
+        self._call("fast_floor", _ptr(src), si, _ptr(out), so, batch, stream=stream)
 
     # -- operators (HEArithmeticOperator) --
     def ckks_multiply(self, ct1, s1, ct2, s2, out, so, depth=0, batch=1, stream=None):
-        _check(self._lib.hegpu_ckks_multiply(self._h, _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, depth, batch,
-                                             stream if stream is not None else _stream()))
+        self._call("ckks_multiply", _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, depth, batch, stream=stream)
 
     def ckks_relinearize_inplace(self, ct, cs, key, depth, batch, ws, stream=None):
-        _check(self._lib.hegpu_ckks_relinearize_inplace(self._h, _ptr(ct), cs, _ptr(key), depth, batch, _ptr(ws),
-                                                        ws.numel() * 8,
-                                                        stream if stream is not None else _stream()))
+        self._call("ckks_relinearize_inplace", _ptr(ct), cs, _ptr(key), depth, batch, _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
 
     def probe_ckks_relinearize(self, ct, cs, key, depth, batch, ws, phases, stream=None):
         """measurement seam: only the launches selected by `phases` (include/hegpu.h)"""
-        _check(self._lib.hegpu_probe_ckks_relinearize(self._h, _ptr(ct), cs, _ptr(key), depth, batch, _ptr(ws),
-                                                      ws.numel() * 8, phases,
-                                                      stream if stream is not None else _stream()))
+        self._call("probe_ckks_relinearize", _ptr(ct), cs, _ptr(key), depth, batch, _ptr(ws), _ws_bytes(ws), phases,
+                   stream=stream)
 
     def ckks_rescale_inplace(self, ct, cs, depth, batch, ws, stream=None):
-        _check(self._lib.hegpu_ckks_rescale_inplace(self._h, _ptr(ct), cs, depth, batch, _ptr(ws), ws.numel() * 8,
-                                                    stream if stream is not None else _stream()))
+        self._call("ckks_rescale_inplace", _ptr(ct), cs, depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def ckks_apply_galois(self, ct, cs, out, so, key, galois_elt, depth, batch, ws, stream=None):
-        _check(self._lib.hegpu_ckks_apply_galois(self._h, _ptr(ct), cs, _ptr(out), so, _ptr(key), galois_elt, depth,
-                                                 batch, _ptr(ws), ws.numel() * 8,
-                                                 stream if stream is not None else _stream()))
+        self._call("ckks_apply_galois", _ptr(ct), cs, _ptr(out), so, _ptr(key), galois_elt, depth, batch, _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
 
     def mod_raise(self, src, s_in, out, s_out, limbs, parts=2, batch=1, stream=None):
         """hegpu_mod_raise: src [parts][1][N] at q_0 (coefficient domain) -> out [parts][limbs][N], the centred lift"""
-        _check(self._lib.hegpu_mod_raise(self._h, _ptr(src), s_in, _ptr(out), s_out, limbs, parts, batch,
-                                         stream if stream is not None else _stream()))
+        self._call("mod_raise", _ptr(src), s_in, _ptr(out), s_out, limbs, parts, batch, stream=stream)
 
     def ckks_mod_raise(self, ct, cs, out, so, out_depth, batch, ws, ws_bytes=None, stream=None):
         """hegpu_ckks_mod_raise: ct [2][1][N] at depth Q - 1 -> out [2][Q - out_depth][N], both in the NTT domain.
         Workspace OP_CKKS_MOD_RAISE (ws_bytes: its size when ws is an address, not a tensor)"""
-        _check(self._lib.hegpu_ckks_mod_raise(self._h, _ptr(ct), cs, _ptr(out), so, out_depth, batch, _ptr(ws),
-                                              ws.numel() * 8 if ws_bytes is None else ws_bytes,
-                                              stream if stream is not None else _stream()))
+        self._call("ckks_mod_raise", _ptr(ct), cs, _ptr(out), so, out_depth, batch, _ptr(ws),
+                   _ws_bytes(ws) if ws_bytes is None else ws_bytes, stream=stream)
 
     def ckks_rotate_hoisted(self, ct, cs, out, so, keys, galois_elts, depth, batch, ws, stream=None):
         """fast_single_hoisting_rotation_ckks: keys = list of device tensors (None where galois_elts[i] == 0)"""
         cnt = len(galois_elts)
         kp = (ctypes.c_void_p * cnt)(*[(_ptr(k) if k is not None else None) for k in keys])
         ge = (ctypes.c_int * cnt)(*[int(g) for g in galois_elts])
-        _check(self._lib.hegpu_ckks_rotate_hoisted(self._h, _ptr(ct), cs, _ptr(out), so, kp, ge, cnt, depth, batch,
-                                                   _ptr(ws), ws.numel() * 8,
-                                                   stream if stream is not None else _stream()))
+        self._call("ckks_rotate_hoisted", _ptr(ct), cs, _ptr(out), so, kp, ge, cnt, depth, batch, _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
 
     def ckks_diag_mac(self, rot, rot_stride, n1, diags, n_diag, index, n2, out, out_stride, depth=0, batch=1, stream=None):
         """hegpu_ckks_diag_mac: index = n2 rows of n1 packed-diagonal numbers (-1: absent)"""
         ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
-        _check(self._lib.hegpu_ckks_diag_mac(self._h, _ptr(rot), rot_stride, n1, _ptr(diags), n_diag, ix, n2, _ptr(out),
-                                             out_stride, depth, batch, stream if stream is not None else _stream()))
+        self._call("ckks_diag_mac", _ptr(rot), rot_stride, n1, _ptr(diags), n_diag, ix, n2, _ptr(out), out_stride,
+                   depth, batch, stream=stream)
 
     def linear_transform_workspace_bytes(self, n1, n2, depth, batch):
         return int(self._lib.hegpu_ckks_linear_transform_workspace_bytes(self._h, n1, n2, depth, batch))
@@ -391,19 +384,17 @@ class Context:
         gk = (ctypes.c_void_p * n2)(*[(_ptr(k) if k is not None else None) for k in giant_keys])
         be = (ctypes.c_int * n1)(*[int(g) for g in baby_elts])
         ge = (ctypes.c_int * n2)(*[int(g) for g in giant_elts])
-        _check(self._lib.hegpu_ckks_linear_transform(self._h, _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2,
-                                                     bk, be, gk, ge, depth, batch, _ptr(ws), ws.numel() * 8,
-                                                     stream if stream is not None else _stream()))
+        self._call("ckks_linear_transform", _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2, bk, be, gk,
+                   ge, depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def ckks_conj_split(self, x, xs, xc, xcs, out0, out1, so, depth, out_depth, batch=1, stream=None):
         """hegpu_ckks_conj_split: out0 = x + xc, out1 = div_i(x - xc) on the Q - out_depth kept limbs"""
-        _check(self._lib.hegpu_ckks_conj_split(self._h, _ptr(x), xs, _ptr(xc), xcs, _ptr(out0), _ptr(out1), so, depth,
-                                               out_depth, batch, stream if stream is not None else _stream()))
+        self._call("ckks_conj_split", _ptr(x), xs, _ptr(xc), xcs, _ptr(out0), _ptr(out1), so, depth, out_depth, batch,
+                   stream=stream)
 
     def ckks_conj_merge(self, c0, s0, c1, s1, out, so, depth, out_depth, batch=1, stream=None):
         """hegpu_ckks_conj_merge: out = c0 + mult_i(c1) on the Q - out_depth kept limbs"""
-        _check(self._lib.hegpu_ckks_conj_merge(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, depth, out_depth, batch,
-                                               stream if stream is not None else _stream()))
+        self._call("ckks_conj_merge", _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, depth, out_depth, batch, stream=stream)
 
     def ckks_weighted_sum(self, terms, strides, term_limbs, weights, w0, out, so, limbs, batch=1, stream=None):
         """hegpu_ckks_weighted_sum: out = w0 + sum_k weights[k] * terms[k] on the first `limbs` limbs.  terms: device tensors
@@ -413,39 +404,36 @@ class Context:
         ts = (ctypes.c_uint64 * max(k, 1))(*[int(v) for v in strides])
         tl = (ctypes.c_int * max(k, 1))(*[int(v) for v in term_limbs])
         tw = (ctypes.c_double * max(2 * k, 1))(*[v for w in weights for v in (complex(w).real, complex(w).imag)])
-        _check(self._lib.hegpu_ckks_weighted_sum(self._h, tp, ts, tl, tw, k, complex(w0).real, complex(w0).imag, _ptr(out),
-                                                 so, limbs, batch, stream if stream is not None else _stream()))
+        self._call("ckks_weighted_sum", tp, ts, tl, tw, k, complex(w0).real, complex(w0).imag, _ptr(out), so, limbs,
+                   batch, stream=stream)
 
     def ckks_double_sub(self, a, a_stride, a_limbs, b, b_stride, b_limbs, value, out, so, limbs, batch=1, stream=None):
         """hegpu_ckks_double_sub: out = 2 a - b on the first `limbs` limbs; b None: round(value) leaves part 0 instead"""
-        _check(self._lib.hegpu_ckks_double_sub(self._h, _ptr(a), a_stride, a_limbs, _ptr(b), b_stride, b_limbs, float(value),
-                                               _ptr(out), so, limbs, batch, stream if stream is not None else _stream()))
+        self._call("ckks_double_sub", _ptr(a), a_stride, a_limbs, _ptr(b), b_stride, b_limbs, float(value), _ptr(out),
+                   so, limbs, batch, stream=stream)
 
     def ckks_gate_combine(self, gate, a, a_stride, a_limbs, b, b_kind, b_stride, b_limbs, p, p_stride, p_limbs, scale_one,
                           out, so, limbs, batch=1, stream=None):
         """hegpu_ckks_gate_combine: out = c0 * one + c1 * (a + b) + c2 * p on the first `limbs` limbs, one pass"""
-        _check(self._lib.hegpu_ckks_gate_combine(self._h, gate, _ptr(a), a_stride, a_limbs, _ptr(b), b_kind, b_stride, b_limbs,
-                                                 _ptr(p), p_stride, p_limbs, float(scale_one), _ptr(out), so, limbs, batch,
-                                                 stream if stream is not None else _stream()))
+        self._call("ckks_gate_combine", gate, _ptr(a), a_stride, a_limbs, _ptr(b), b_kind, b_stride, b_limbs, _ptr(p),
+                   p_stride, p_limbs, float(scale_one), _ptr(out), so, limbs, batch, stream=stream)
 
     def bfv_gate_combine(self, gate, a, a_stride, b, b_kind, b_stride, p, p_stride, out, so, batch=1, stream=None):
         """hegpu_bfv_gate_combine: the same in the coefficient domain, every operand at Q limbs"""
-        _check(self._lib.hegpu_bfv_gate_combine(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(p), p_stride,
-                                                _ptr(out), so, batch, stream if stream is not None else _stream()))
+        self._call("bfv_gate_combine", gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(p), p_stride, _ptr(out),
+                   so, batch, stream=stream)
 
     def ckks_logic_gate(self, gate, a, a_stride, b, b_kind, b_stride, relin_key, scale_one, out, so, depth, batch, ws,
                         stream=None):
         """hegpu_ckks_logic_gate: product sequence + one combine pass; out at depth + 1 (NOT: depth)"""
-        _check(self._lib.hegpu_ckks_logic_gate(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key),
-                                               float(scale_one), _ptr(out), so, depth, batch, _ptr(ws),
-                                               ws.numel() * 8 if ws is not None else 0,
-                                               stream if stream is not None else _stream()))
+        self._call("ckks_logic_gate", gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key),
+                   float(scale_one), _ptr(out), so, depth, batch, _ptr(ws), _ws_bytes(ws) if ws is not None else 0,
+                   stream=stream)
 
     def bfv_logic_gate(self, gate, a, a_stride, b, b_kind, b_stride, relin_key, out, so, batch, ws, stream=None):
         """hegpu_bfv_logic_gate: product sequence + one combine pass, coefficient domain"""
-        _check(self._lib.hegpu_bfv_logic_gate(self._h, gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key),
-                                              _ptr(out), so, batch, _ptr(ws), ws.numel() * 8 if ws is not None else 0,
-                                              stream if stream is not None else _stream()))
+        self._call("bfv_logic_gate", gate, _ptr(a), a_stride, _ptr(b), b_kind, b_stride, _ptr(relin_key), _ptr(out), so,
+                   batch, _ptr(ws), _ws_bytes(ws) if ws is not None else 0, stream=stream)
 
     def poly_eval_workspace_bytes(self, plan, depth, batch):
         return int(self._lib.hegpu_ckks_poly_eval_workspace_bytes(self._h, plan.steps, len(plan.steps), depth, batch))
@@ -453,9 +441,8 @@ class Context:
     def ckks_poly_eval(self, ct, cs, out, so, plan, relin_key, depth, batch, ws, stream=None):
         """hegpu_ckks_poly_eval: executes a PolyEvalPlan (poly_eval_plan) made for the level Q - 1 - depth; the result is
         at depth Q - 1 - plan.level and scale plan.scale"""
-        _check(self._lib.hegpu_ckks_poly_eval(self._h, _ptr(ct), cs, _ptr(out), so, plan.steps, len(plan.steps),
-                                              _ptr(relin_key), depth, batch, _ptr(ws), ws.numel() * 8,
-                                              stream if stream is not None else _stream()))
+        self._call("ckks_poly_eval", _ptr(ct), cs, _ptr(out), so, plan.steps, len(plan.steps), _ptr(relin_key), depth,
+                   batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     @staticmethod
     def linear_factors(factors):
@@ -482,16 +469,14 @@ class Context:
     def ckks_coeff_to_slot(self, ct, cs, out0, out1, so, factors, conj_key, depth, batch, ws, stream=None):
         """hegpu_ckks_coeff_to_slot: factors as for linear_factors, their diagonals encoded at depth + position"""
         arr, _keep = self.linear_factors(factors)
-        _check(self._lib.hegpu_ckks_coeff_to_slot(self._h, _ptr(ct), cs, _ptr(out0), _ptr(out1), so, arr, len(factors),
-                                                  _ptr(conj_key), depth, batch, _ptr(ws), ws.numel() * 8,
-                                                  stream if stream is not None else _stream()))
+        self._call("ckks_coeff_to_slot", _ptr(ct), cs, _ptr(out0), _ptr(out1), so, arr, len(factors), _ptr(conj_key),
+                   depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def ckks_slot_to_coeff(self, c0, s0, c1, s1, out, so, factors, depth, batch, ws, stream=None):
         """hegpu_ckks_slot_to_coeff: factors as for linear_factors, their diagonals encoded at depth + 1 + position"""
         arr, _keep = self.linear_factors(factors)
-        _check(self._lib.hegpu_ckks_slot_to_coeff(self._h, _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, arr, len(factors),
-                                                  depth, batch, _ptr(ws), ws.numel() * 8,
-                                                  stream if stream is not None else _stream()))
+        self._call("ckks_slot_to_coeff", _ptr(c0), s0, _ptr(c1), s1, _ptr(out), so, arr, len(factors), depth, batch,
+                   _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def bootstrap_workspace_bytes(self, plan, cts, stc, switch_keys, batch):
         """hegpu_ckks_bootstrap_workspace_bytes; plan: a BootstrapPlan (bootstrap_plan), cts / stc as for linear_factors"""
@@ -507,11 +492,10 @@ class Context:
         one limb more per part on the way).  cts / stc: as for linear_factors (bootstrap_factors builds them)"""
         a, _ka = self.linear_factors(cts)
         b, _kb = self.linear_factors(stc)
-        _check(self._lib.hegpu_ckks_bootstrap(self._h, _ptr(ct), cs, _ptr(out), so, ctypes.byref(plan.c), plan.eval_mod.steps,
-                                              len(plan.eval_mod.steps), a, len(cts), b, len(stc), _ptr(conj_key), _ptr(relin_key),
-                                              _ptr(swk_dense_to_sparse), _ptr(swk_sparse_to_dense), batch, _ptr(ws),
-                                              ws.numel() * 8 if ws is not None else 0,
-                                              stream if stream is not None else _stream()))
+        self._call("ckks_bootstrap", _ptr(ct), cs, _ptr(out), so, ctypes.byref(plan.c), plan.eval_mod.steps,
+                   len(plan.eval_mod.steps), a, len(cts), b, len(stc), _ptr(conj_key), _ptr(relin_key),
+                   _ptr(swk_dense_to_sparse), _ptr(swk_sparse_to_dense), batch, _ptr(ws),
+                   _ws_bytes(ws) if ws is not None else 0, stream=stream)
 
     def bootstrap_factors(self, plan, galois_key, encode=None):
         """The two factor lists of Context.ckks_bootstrap from a BootstrapPlan: the factorisation of the special FFT
@@ -552,18 +536,15 @@ class Context:
         return cts, stc, sorted(elts)
 
     def bfv_multiply(self, ct1, s1, ct2, s2, out, so, batch, ws, stream=None):
-        _check(self._lib.hegpu_bfv_multiply(self._h, _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws),
-                                            ws.numel() * 8, stream if stream is not None else _stream()))
+        self._call("bfv_multiply", _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
 
     def bfv_relinearize_inplace(self, ct, cs, key, batch, ws, stream=None):
-        _check(self._lib.hegpu_bfv_relinearize_inplace(self._h, _ptr(ct), cs, _ptr(key), batch, _ptr(ws),
-                                                       ws.numel() * 8,
-                                                       stream if stream is not None else _stream()))
+        self._call("bfv_relinearize_inplace", _ptr(ct), cs, _ptr(key), batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def bfv_apply_galois(self, ct, cs, out, so, key, galois_elt, batch, ws, stream=None):
-        _check(self._lib.hegpu_bfv_apply_galois(self._h, _ptr(ct), cs, _ptr(out), so, _ptr(key), galois_elt, batch,
-                                                _ptr(ws), ws.numel() * 8,
-                                                stream if stream is not None else _stream()))
+        self._call("bfv_apply_galois", _ptr(ct), cs, _ptr(out), so, _ptr(key), galois_elt, batch, _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
 
 
     # ---- key generation / encryption / decryption (method I keys)
@@ -576,18 +557,14 @@ class Context:
         sk = torch.empty(Qp * n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_KEYGEN_SECRET)
         hw = n // 2 if hamming_weight is None else hamming_weight  # secretkey.cu:23
-        _check(self._lib.hegpu_generate_secret_key(self._h, rng._h, hw, _ptr(sk), _ptr(ws),
-                                                   ws.numel() * ws.element_size(),
-                                                   stream if stream is not None else _stream()))
+        self._call("generate_secret_key", rng._h, hw, _ptr(sk), _ptr(ws), _ws_bytes(ws), stream=stream)
         return sk
 
     def generate_public_key(self, rng, sk, stream=None):
         import torch
         pk = torch.empty(2 * self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_KEYGEN_PUBLIC)
-        _check(self._lib.hegpu_generate_public_key(self._h, rng._h, _ptr(sk), _ptr(pk), _ptr(ws),
-                                                   ws.numel() * ws.element_size(),
-                                                   stream if stream is not None else _stream()))
+        self._call("generate_public_key", rng._h, _ptr(sk), _ptr(pk), _ptr(ws), _ws_bytes(ws), stream=stream)
         return pk
 
     def switch_key_digits(self):
@@ -602,9 +579,7 @@ class Context:
         import torch
         rk = torch.empty(self.switch_key_digits() * 2 * self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_KEYGEN_SWITCH)
-        _check(self._lib.hegpu_generate_relin_key(self._h, rng._h, _ptr(sk), _ptr(rk), _ptr(ws),
-                                                  ws.numel() * ws.element_size(),
-                                                  stream if stream is not None else _stream()))
+        self._call("generate_relin_key", rng._h, _ptr(sk), _ptr(rk), _ptr(ws), _ws_bytes(ws), stream=stream)
         return rk
 
     def generate_switch_key(self, rng, new_sk, old_sk, stream=None):
@@ -612,61 +587,51 @@ class Context:
         import torch
         swk = torch.empty(self.switch_key_digits() * 2 * self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_KEYGEN_SWITCH)
-        _check(self._lib.hegpu_generate_switch_key(self._h, rng._h, _ptr(new_sk), _ptr(old_sk), _ptr(swk), _ptr(ws),
-                                                   ws.numel() * ws.element_size(),
-                                                   stream if stream is not None else _stream()))
+        self._call("generate_switch_key", rng._h, _ptr(new_sk), _ptr(old_sk), _ptr(swk), _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
         return swk
 
     def generate_galois_key(self, rng, sk, galois_elt, stream=None):
         import torch
         gk = torch.empty(self.switch_key_digits() * 2 * self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_KEYGEN_SWITCH)
-        _check(self._lib.hegpu_generate_galois_key(self._h, rng._h, _ptr(sk), galois_elt, _ptr(gk), _ptr(ws),
-                                                   ws.numel() * ws.element_size(),
-                                                   stream if stream is not None else _stream()))
+        self._call("generate_galois_key", rng._h, _ptr(sk), galois_elt, _ptr(gk), _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
         return gk
 
     def ckks_encrypt(self, rng, pk, plain, stream=None):
         import torch
         ct = torch.empty(2 * self.Q_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_CKKS_ENCRYPT)
-        _check(self._lib.hegpu_ckks_encrypt(self._h, rng._h, _ptr(pk), _ptr(plain), _ptr(ct), _ptr(ws),
-                                            ws.numel() * ws.element_size(),
-                                            stream if stream is not None else _stream()))
+        self._call("ckks_encrypt", rng._h, _ptr(pk), _ptr(plain), _ptr(ct), _ptr(ws), _ws_bytes(ws), stream=stream)
         return ct
 
     def bfv_encrypt(self, rng, pk, plain, stream=None):
         import torch
         ct = torch.empty(2 * self.Q_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_BFV_ENCRYPT)
-        _check(self._lib.hegpu_bfv_encrypt(self._h, rng._h, _ptr(pk), _ptr(plain), _ptr(ct), _ptr(ws),
-                                           ws.numel() * ws.element_size(),
-                                           stream if stream is not None else _stream()))
+        self._call("bfv_encrypt", rng._h, _ptr(pk), _ptr(plain), _ptr(ct), _ptr(ws), _ws_bytes(ws), stream=stream)
         return ct
 
     def bfv_decrypt(self, ct, sk, stream=None):
         import torch
         plain = torch.empty(self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_BFV_DECRYPT)
-        _check(self._lib.hegpu_bfv_decrypt(self._h, _ptr(ct), _ptr(sk), _ptr(plain), _ptr(ws),
-                                           ws.numel() * ws.element_size(),
-                                           stream if stream is not None else _stream()))
+        self._call("bfv_decrypt", _ptr(ct), _ptr(sk), _ptr(plain), _ptr(ws), _ws_bytes(ws), stream=stream)
         return plain
 
     def bfv_encode(self, message, stream=None):
         """message: device int64 tensor with at most N entries"""
         import torch
         plain = torch.empty(self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_bfv_encode(self._h, _ptr(message), message.numel(), _ptr(plain),
-                                          stream if stream is not None else _stream()))
+        self._call("bfv_encode", _ptr(message), message.numel(), _ptr(plain), stream=stream)
         return plain
 
     def bfv_decode(self, plain, stream=None):
         import torch
         out = torch.empty(self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_BFV_DECODE)
-        _check(self._lib.hegpu_bfv_decode(self._h, _ptr(plain), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(),
-                                          stream if stream is not None else _stream()))
+        self._call("bfv_decode", _ptr(plain), _ptr(out), _ptr(ws), _ws_bytes(ws), stream=stream)
         return out
 
     def ckks_encode(self, message, scale, stream=None):
@@ -674,31 +639,27 @@ class Context:
         import torch
         plain = torch.empty(self.Q_size * self.n, dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_CKKS_ENCODE)
-        _check(self._lib.hegpu_ckks_encode(self._h, _ptr(message), message.numel(), float(scale), _ptr(plain),
-                                           _ptr(ws), ws.numel() * ws.element_size(),
-                                           stream if stream is not None else _stream()))
+        self._call("ckks_encode", _ptr(message), message.numel(), float(scale), _ptr(plain), _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
         return plain
 
     def ckks_decode(self, plain, scale, depth=0, stream=None):
         import torch
         out = torch.empty(self.n // 2, dtype=torch.float64, device="cuda")
         ws = self.workspace(OP_CKKS_DECODE, depth, 1)
-        _check(self._lib.hegpu_ckks_decode(self._h, _ptr(plain), depth, float(scale), _ptr(out), _ptr(ws),
-                                           ws.numel() * ws.element_size(),
-                                           stream if stream is not None else _stream()))
+        self._call("ckks_decode", _ptr(plain), depth, float(scale), _ptr(out), _ptr(ws), _ws_bytes(ws), stream=stream)
         return out
 
     def bfv_plain_to_ntt(self, plain, stream=None):
         import torch
         out = torch.empty(self.Q_size * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_bfv_plain_to_ntt(self._h, _ptr(plain), _ptr(out), stream if stream is not None else _stream()))
+        self._call("bfv_plain_to_ntt", _ptr(plain), _ptr(out), stream=stream)
         return out
 
     def negacyclic_shift(self, ct, shift, limbs, parts=2, stream=None):
         import torch
         out = torch.empty(parts * limbs * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_negacyclic_shift(self._h, _ptr(ct), _ptr(out), shift, limbs, parts,
-                                                stream if stream is not None else _stream()))
+        self._call("negacyclic_shift", _ptr(ct), _ptr(out), shift, limbs, parts, stream=stream)
         return out
 
     def ckks_constant_op(self, op, ct, value, limbs, parts=2, out=None, stream=None):
@@ -706,8 +667,7 @@ class Context:
         import torch
         if out is None:
             out = torch.empty(parts * limbs * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_ckks_constant_op(self._h, op, _ptr(ct), float(value), _ptr(out), limbs, parts,
-                                                stream if stream is not None else _stream()))
+        self._call("ckks_constant_op", op, _ptr(ct), float(value), _ptr(out), limbs, parts, stream=stream)
         return out
 
     def ckks_gaussian_integer_op(self, op, ct, re, im, limbs, parts=2, out=None, stream=None):
@@ -715,16 +675,15 @@ class Context:
         import torch
         if out is None:
             out = torch.empty(parts * limbs * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_ckks_gaussian_integer_op(self._h, op, _ptr(ct), float(re), float(im), _ptr(out), limbs,
-                                                        parts, stream if stream is not None else _stream()))
+        self._call("ckks_gaussian_integer_op", op, _ptr(ct), float(re), float(im), _ptr(out), limbs, parts,
+                   stream=stream)
         return out
 
     def ckks_mult_i(self, ct, limbs, parts=2, divide=False, out=None, stream=None):
         import torch
         if out is None:
             out = torch.empty(parts * limbs * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_ckks_mult_i(self._h, _ptr(ct), _ptr(out), limbs, parts, int(divide),
-                                           stream if stream is not None else _stream()))
+        self._call("ckks_mult_i", _ptr(ct), _ptr(out), limbs, parts, int(divide), stream=stream)
         return out
 
     def ckks_encode_ex(self, mode, message, scale, stream=None):
@@ -732,38 +691,34 @@ class Context:
         tensor (<= N/2) into the slots; mode 2: float64 device tensor (<= N) as polynomial coefficients;
         mode 3: `message` is one Python number placed in every slot."""
         import torch
-        st = stream if stream is not None else _stream()
         plain = torch.empty(self.Q_size * self.n, dtype=torch.int64, device="cuda")
         if mode == 3:
-            _check(self._lib.hegpu_ckks_encode_scalar(self._h, float(message), float(scale), _ptr(plain), st))
+            self._call("ckks_encode_scalar", float(message), float(scale), _ptr(plain), stream=stream)
         elif mode == 2:
-            _check(self._lib.hegpu_ckks_encode_coeff(self._h, _ptr(message), message.numel(), float(scale), _ptr(plain), st))
+            self._call("ckks_encode_coeff", _ptr(message), message.numel(), float(scale), _ptr(plain), stream=stream)
         else:
             assert mode == 1 and message.dtype == torch.complex128
             ws = self._kg_ws(OP_CKKS_ENCODE)
-            _check(self._lib.hegpu_ckks_encode_complex(self._h, _ptr(message), message.numel(), float(scale),
-                                                       _ptr(plain), _ptr(ws), ws.numel() * ws.element_size(), st))
+            self._call("ckks_encode_complex", _ptr(message), message.numel(), float(scale), _ptr(plain), _ptr(ws),
+                       _ws_bytes(ws), stream=stream)
         return plain
 
     def ckks_decode_ex(self, mode, plain, scale, depth=0, stream=None):
         """mode 1: the N/2 complex slots; mode 2: the N polynomial coefficients"""
         import torch
-        st = stream if stream is not None else _stream()
         ws = self.workspace(OP_CKKS_DECODE, depth, 1)
         if mode == 1:
             out = torch.empty(self.n // 2, dtype=torch.complex128, device="cuda")
-            fn = self._lib.hegpu_ckks_decode_complex
         else:
             out = torch.empty(self.n, dtype=torch.float64, device="cuda")
-            fn = self._lib.hegpu_ckks_decode_coeff
-        _check(fn(self._h, _ptr(plain), depth, float(scale), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), st))
+        self._call("ckks_decode_complex" if mode == 1 else "ckks_decode_coeff", _ptr(plain), depth, float(scale), _ptr(out),
+                   _ptr(ws), _ws_bytes(ws), stream=stream)
         return out
 
     def ckks_decrypt(self, ct, sk, depth=0, stream=None):
         import torch
         plain = torch.empty((self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_ckks_decrypt(self._h, _ptr(ct), _ptr(sk), depth, _ptr(plain),
-                                            stream if stream is not None else _stream()))
+        self._call("ckks_decrypt", _ptr(ct), _ptr(sk), depth, _ptr(plain), stream=stream)
         return plain
 
     # ---- N-out-of-N multiparty protocol (hegpu_mpc_*): crs = the generator all parties seed alike, rng = the party's own
@@ -778,9 +733,8 @@ class Context:
         import torch
         share = torch.empty(self._key_words(MPC_PUBLIC_KEY), dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_MPC_KEY_SHARE)
-        _check(self._lib.hegpu_mpc_public_key_share(self._h, crs._h, rng._h, _ptr(sk), _ptr(share), _ptr(ws),
-                                                    ws.numel() * ws.element_size(),
-                                                    stream if stream is not None else _stream()))
+        self._call("mpc_public_key_share", crs._h, rng._h, _ptr(sk), _ptr(share), _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
         return share
 
     def mpc_relin_key_share_round1(self, crs, rng, sk, stream=None):
@@ -789,73 +743,65 @@ class Context:
         u = torch.empty(self.Q_prime_size * self.n, dtype=torch.int64, device="cuda")
         share = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_MPC_KEY_SHARE)
-        _check(self._lib.hegpu_mpc_relin_key_share_round1(self._h, crs._h, rng._h, _ptr(sk), _ptr(u), _ptr(share),
-                                                          _ptr(ws), ws.numel() * ws.element_size(),
-                                                          stream if stream is not None else _stream()))
+        self._call("mpc_relin_key_share_round1", crs._h, rng._h, _ptr(sk), _ptr(u), _ptr(share), _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
         return u, share
 
     def mpc_relin_key_share_round2(self, rng, sk, u, round1_sum, stream=None):
         import torch
         share = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_MPC_KEY_SHARE)
-        _check(self._lib.hegpu_mpc_relin_key_share_round2(self._h, rng._h, _ptr(sk), _ptr(u), _ptr(round1_sum),
-                                                          _ptr(share), _ptr(ws), ws.numel() * ws.element_size(),
-                                                          stream if stream is not None else _stream()))
+        self._call("mpc_relin_key_share_round2", rng._h, _ptr(sk), _ptr(u), _ptr(round1_sum), _ptr(share), _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
         return share
 
     def mpc_galois_key_share(self, crs, rng, sk, galois_elt, stream=None):
         import torch
         share = torch.empty(self._key_words(MPC_GALOIS_KEY), dtype=torch.int64, device="cuda")
         ws = self._kg_ws(OP_MPC_KEY_SHARE)
-        _check(self._lib.hegpu_mpc_galois_key_share(self._h, crs._h, rng._h, _ptr(sk), galois_elt, _ptr(share), _ptr(ws),
-                                                    ws.numel() * ws.element_size(),
-                                                    stream if stream is not None else _stream()))
+        self._call("mpc_galois_key_share", crs._h, rng._h, _ptr(sk), galois_elt, _ptr(share), _ptr(ws), _ws_bytes(ws),
+                   stream=stream)
         return share
 
     def mpc_accumulate(self, shares, layout, stream=None):
         import torch
         out = torch.empty(self._key_words(layout), dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_mpc_accumulate(self._h, self._share_array(shares), len(shares), layout, _ptr(out),
-                                              stream if stream is not None else _stream()))
+        self._call("mpc_accumulate", self._share_array(shares), len(shares), layout, _ptr(out), stream=stream)
         return out
 
     def mpc_relin_key_finish(self, round2_shares, round1_sum, stream=None):
         import torch
         rk = torch.empty(self._key_words(MPC_RELIN_ROUND1), dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_mpc_relin_key_finish(self._h, self._share_array(round2_shares), len(round2_shares),
-                                                    _ptr(round1_sum), _ptr(rk),
-                                                    stream if stream is not None else _stream()))
+        self._call("mpc_relin_key_finish", self._share_array(round2_shares), len(round2_shares), _ptr(round1_sum),
+                   _ptr(rk), stream=stream)
         return rk
 
     def mpc_ckks_decrypt_share(self, rng, ct, ct_stride, sk, depth=0, batch=1, stream=None):
         import torch
         share = torch.empty(batch * (self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_mpc_ckks_decrypt_share(self._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), depth, _ptr(share),
-                                                      batch, stream if stream is not None else _stream()))
+        self._call("mpc_ckks_decrypt_share", rng._h, _ptr(ct), ct_stride, _ptr(sk), depth, _ptr(share), batch,
+                   stream=stream)
         return share
 
     def mpc_ckks_decrypt_merge(self, ct, ct_stride, shares, depth=0, batch=1, stream=None):
         import torch
         plain = torch.empty(batch * (self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_mpc_ckks_decrypt_merge(self._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares),
-                                                      depth, _ptr(plain), batch,
-                                                      stream if stream is not None else _stream()))
+        self._call("mpc_ckks_decrypt_merge", _ptr(ct), ct_stride, self._share_array(shares), len(shares), depth,
+                   _ptr(plain), batch, stream=stream)
         return plain
 
     def mpc_bfv_decrypt_share(self, rng, ct, ct_stride, sk, batch=1, stream=None):
         import torch
         share = torch.empty(batch * self.Q_size * self.n, dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_mpc_bfv_decrypt_share(self._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share), batch,
-                                                     stream if stream is not None else _stream()))
+        self._call("mpc_bfv_decrypt_share", rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share), batch, stream=stream)
         return share
 
     def mpc_bfv_decrypt_merge(self, ct, ct_stride, shares, batch=1, stream=None):
         import torch
         plain = torch.empty(batch * self.n, dtype=torch.int64, device="cuda")
         ws = self.workspace(OP_MPC_BFV_DECRYPT_MERGE, 0, batch)
-        _check(self._lib.hegpu_mpc_bfv_decrypt_merge(self._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares),
-                                                     _ptr(plain), batch, _ptr(ws), ws.numel() * ws.element_size(),
-                                                     stream if stream is not None else _stream()))
+        self._call("mpc_bfv_decrypt_merge", _ptr(ct), ct_stride, self._share_array(shares), len(shares), _ptr(plain),
+                   batch, _ptr(ws), _ws_bytes(ws), stream=stream)
         return plain
 
     # ---- collective refresh (hegpu_mpc_*_refresh_*): crs takes one stream per call, the parties and the coordinator
@@ -865,10 +811,8 @@ class Context:
         import torch
         share = torch.empty(batch * (2 * self.Q_size - depth) * self.n, dtype=torch.int64, device="cuda")
         ws = self.workspace(OP_MPC_REFRESH_SHARE, depth, batch)
-        _check(self._lib.hegpu_mpc_ckks_refresh_share(self._h, crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), depth,
-                                                      mask_bits, _ptr(share), batch, _ptr(ws),
-                                                      ws.numel() * ws.element_size(),
-                                                      stream if stream is not None else _stream()))
+        self._call("mpc_ckks_refresh_share", crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), depth, mask_bits,
+                   _ptr(share), batch, _ptr(ws), _ws_bytes(ws), stream=stream)
         return share
 
     def mpc_ckks_refresh_merge(self, crs, ct, ct_stride, shares, depth, batch=1, out=None, out_stride=None, stream=None):
@@ -879,10 +823,8 @@ class Context:
         if out is None:
             out = torch.empty(max(batch - 1, 0) * out_stride + words, dtype=torch.int64, device="cuda")
         ws = self.workspace(OP_MPC_REFRESH_MERGE, depth, batch)
-        _check(self._lib.hegpu_mpc_ckks_refresh_merge(self._h, crs._h, _ptr(ct), ct_stride, self._share_array(shares),
-                                                      len(shares), depth, _ptr(out), out_stride, batch, _ptr(ws),
-                                                      ws.numel() * ws.element_size(),
-                                                      stream if stream is not None else _stream()))
+        self._call("mpc_ckks_refresh_merge", crs._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares), depth,
+                   _ptr(out), out_stride, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
         return out
 
     def mpc_bfv_refresh_share(self, crs, rng, ct, ct_stride, sk, batch=1, stream=None):
@@ -890,9 +832,8 @@ class Context:
         import torch
         share = torch.empty(batch * 2 * self.Q_size * self.n, dtype=torch.int64, device="cuda")
         ws = self.workspace(OP_MPC_REFRESH_SHARE, 0, batch)
-        _check(self._lib.hegpu_mpc_bfv_refresh_share(self._h, crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share),
-                                                     batch, _ptr(ws), ws.numel() * ws.element_size(),
-                                                     stream if stream is not None else _stream()))
+        self._call("mpc_bfv_refresh_share", crs._h, rng._h, _ptr(ct), ct_stride, _ptr(sk), _ptr(share), batch, _ptr(ws),
+                   _ws_bytes(ws), stream=stream)
         return share
 
     def mpc_bfv_refresh_merge(self, crs, ct, ct_stride, shares, batch=1, out=None, out_stride=None, stream=None):
@@ -902,10 +843,8 @@ class Context:
         if out is None:
             out = torch.empty(max(batch - 1, 0) * out_stride + words, dtype=torch.int64, device="cuda")
         ws = self.workspace(OP_MPC_REFRESH_MERGE, 0, batch)
-        _check(self._lib.hegpu_mpc_bfv_refresh_merge(self._h, crs._h, _ptr(ct), ct_stride, self._share_array(shares),
-                                                     len(shares), _ptr(out), out_stride, batch, _ptr(ws),
-                                                     ws.numel() * ws.element_size(),
-                                                     stream if stream is not None else _stream()))
+        self._call("mpc_bfv_refresh_merge", crs._h, _ptr(ct), ct_stride, self._share_array(shares), len(shares),
+                   _ptr(out), out_stride, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
         return out
 
 
@@ -937,7 +876,7 @@ class Rng:
             pass
 
 
-class TfheContext:
+class TfheContext(_Handle):
     """HEContext<TFHE> + HELogicOperator<TFHE> over the C ABI (fixed STD128 set)."""
 
     def __init__(self):
@@ -970,8 +909,7 @@ class TfheContext:
     def prepare_bootkey(self, boot_key, stream=None):
         import torch
         out = torch.empty(self.int("prepared_bootkey_elems"), dtype=torch.int64, device=boot_key.device)
-        _check(self._lib.hegpu_tfhe_prepare_bootkey(self._h, _ptr(boot_key), _ptr(out),
-                                                    stream if stream is not None else _stream()))
+        self._call("tfhe_prepare_bootkey", _ptr(boot_key), _ptr(out), stream=stream)
         return out
 
     @staticmethod
@@ -988,30 +926,27 @@ class TfheContext:
         return f
 
     def gate_precompute(self, gate, out_a, out_b, a1, b1, a2, b2, shape, stream=None):
-        _check(self._lib.hegpu_tfhe_gate_precompute(self._h, gate, _ptr(out_a), _ptr(out_b), _ptr(a1), _ptr(b1),
-                                                    _ptr(a2), _ptr(b2), shape,
-                                                    stream if stream is not None else _stream()))
+        self._call("tfhe_gate_precompute", gate, _ptr(out_a), _ptr(out_b), _ptr(a1), _ptr(b1), _ptr(a2), _ptr(b2),
+                   shape, stream=stream)
 
     def bootstrapping(self, in_a, in_b, prepared_bk, out_a, out_b, shape, stream=None):
-        _check(self._lib.hegpu_tfhe_bootstrapping(self._h, _ptr(in_a), _ptr(in_b), _ptr(prepared_bk), _ptr(out_a),
-                                                  _ptr(out_b), shape, stream if stream is not None else _stream()))
+        self._call("tfhe_bootstrapping", _ptr(in_a), _ptr(in_b), _ptr(prepared_bk), _ptr(out_a), _ptr(out_b), shape,
+                   stream=stream)
 
     def status(self, stream=None):
         """drains the stream; raises HEError(E_INVALID) if a bootstrapping call was handed a buffer that is no prepared key"""
-        _check(self._lib.hegpu_tfhe_status(self._h, stream if stream is not None else _stream()))
+        self._call("tfhe_status", stream=stream)
 
     def key_switching(self, in_a, in_b, out_a, out_b, ks_a, ks_b, shape, stream=None):
-        _check(self._lib.hegpu_tfhe_key_switching(self._h, _ptr(in_a), _ptr(in_b), _ptr(out_a), _ptr(out_b),
-                                                  _ptr(ks_a), _ptr(ks_b), shape,
-                                                  stream if stream is not None else _stream()))
+        self._call("tfhe_key_switching", _ptr(in_a), _ptr(in_b), _ptr(out_a), _ptr(out_b), _ptr(ks_a), _ptr(ks_b),
+                   shape, stream=stream)
 
     # ---- front end: keys, bit encryption, decryption, MUX
     def generate_secret_key(self, rng, stream=None):
         import torch
         lwe = torch.empty(self.int("n"), dtype=torch.int32, device="cuda")
         tlwe = torch.empty(self.int("N") * self.int("k"), dtype=torch.int32, device="cuda")
-        _check(self._lib.hegpu_tfhe_generate_secret_key(self._h, rng._h, _ptr(lwe), _ptr(tlwe),
-                                                        stream if stream is not None else _stream()))
+        self._call("tfhe_generate_secret_key", rng._h, _ptr(lwe), _ptr(tlwe), stream=stream)
         return lwe, tlwe
 
     def generate_bootstrapping_key(self, rng, lwe, tlwe, stream=None):
@@ -1021,9 +956,8 @@ class TfheContext:
         ks_a = torch.empty(self.int("kskey_a_elems"), dtype=torch.int32, device="cuda")
         ks_b = torch.empty(self.int("kskey_b_elems"), dtype=torch.int32, device="cuda")
         ws = torch.empty(self.int("N"), dtype=torch.int64, device="cuda")
-        _check(self._lib.hegpu_tfhe_generate_bootstrapping_key(self._h, rng._h, _ptr(lwe), _ptr(tlwe), _ptr(bk),
-                                                               _ptr(ks_a), _ptr(ks_b), _ptr(ws), ws.numel() * 8,
-                                                               stream if stream is not None else _stream()))
+        self._call("tfhe_generate_bootstrapping_key", rng._h, _ptr(lwe), _ptr(tlwe), _ptr(bk), _ptr(ks_a), _ptr(ks_b),
+                   _ptr(ws), _ws_bytes(ws), stream=stream)
         return bk, ks_a, ks_b
 
     def encrypt(self, rng, lwe, messages, stream=None):
@@ -1031,28 +965,22 @@ class TfheContext:
         shape = messages.numel()
         a = torch.empty(shape * self.int("n"), dtype=torch.int32, device="cuda")
         b = torch.empty(shape, dtype=torch.int32, device="cuda")
-        _check(self._lib.hegpu_tfhe_encrypt(self._h, rng._h, _ptr(lwe), _ptr(messages), shape, _ptr(a), _ptr(b),
-                                            stream if stream is not None else _stream()))
+        self._call("tfhe_encrypt", rng._h, _ptr(lwe), _ptr(messages), shape, _ptr(a), _ptr(b), stream=stream)
         return a, b
 
     def decrypt_phase(self, lwe, a, b, stream=None):
         import torch
         out = torch.empty(b.numel(), dtype=torch.int32, device="cuda")
-        _check(self._lib.hegpu_tfhe_decrypt_phase(self._h, _ptr(lwe), _ptr(a), _ptr(b), b.numel(), _ptr(out),
-                                                  stream if stream is not None else _stream()))
+        self._call("tfhe_decrypt_phase", _ptr(lwe), _ptr(a), _ptr(b), b.numel(), _ptr(out), stream=stream)
         return out
 
     def mux(self, a1, b1, a2, b2, ca, cb, out_a, out_b, prepared_bk, ks_a, ks_b, shape, ws, stream=None):
-        _check(self._lib.hegpu_tfhe_mux(self._h, _ptr(a1), _ptr(b1), _ptr(a2), _ptr(b2), _ptr(ca), _ptr(cb),
-                                        _ptr(out_a), _ptr(out_b), _ptr(prepared_bk), _ptr(ks_a), _ptr(ks_b), shape,
-                                        _ptr(ws), ws.numel() * ws.element_size(),
-                                        stream if stream is not None else _stream()))
+        self._call("tfhe_mux", _ptr(a1), _ptr(b1), _ptr(a2), _ptr(b2), _ptr(ca), _ptr(cb), _ptr(out_a), _ptr(out_b),
+                   _ptr(prepared_bk), _ptr(ks_a), _ptr(ks_b), shape, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def gate(self, gate, a1, b1, a2, b2, out_a, out_b, prepared_bk, ks_a, ks_b, shape, ws, stream=None):
-        _check(self._lib.hegpu_tfhe_gate(self._h, gate, _ptr(a1), _ptr(b1), _ptr(a2), _ptr(b2), _ptr(out_a),
-                                         _ptr(out_b), _ptr(prepared_bk), _ptr(ks_a), _ptr(ks_b), shape, _ptr(ws),
-                                         ws.numel() * ws.element_size(),
-                                         stream if stream is not None else _stream()))
+        self._call("tfhe_gate", gate, _ptr(a1), _ptr(b1), _ptr(a2), _ptr(b2), _ptr(out_a), _ptr(out_b),
+                   _ptr(prepared_bk), _ptr(ks_a), _ptr(ks_b), shape, _ptr(ws), _ws_bytes(ws), stream=stream)
 
 
 LinearTransformPlan = collections.namedtuple("LinearTransformPlan",

@@ -120,6 +120,25 @@ static void check_degree(int n, int& n_power)
     n_power = 31 - __builtin_clz((unsigned) n);
 }
 
+// a modulus of at most 60 bits that admits a 2N-th root of unity
+static void check_prime(uint64_t p, int n)
+{
+    if (p >> 61) throw std::logic_error("invalid modulus bit size");
+    if ((p - 1) % (2 * (u64) n)) throw std::logic_error("no sufficient root unity");
+}
+
+// the total width of the chain against the security table (ckks/context.cu:94-119, secstdparams.h:25-79)
+static void check_security(int n, int total_bits, int sec_level)
+{
+    if (sec_level == HEGPU_SEC_128 || sec_level == HEGPU_SEC_192 || sec_level == HEGPU_SEC_256) {
+        if (host::max_logq((u64) n, sec_level) < total_bits)
+            throw std::runtime_error("Parameters do not align with the security recommendations "
+                                     "provided by the lattice-estimator");
+    } else if (sec_level != HEGPU_SEC_NONE) {
+        throw std::runtime_error("Invalid security level");
+    }
+}
+
 static int finish_create(std::unique_ptr<hegpu_context> h, int scheme, int n_power, uint64_t plain_modulus, int q_count,
                          int p_count, hegpu_context** out)
 {
@@ -151,13 +170,7 @@ int hegpu_context_create(int scheme, int n, const int* qb, int qn, const int* pb
         bits.insert(bits.end(), pb, pb + pn);
         int total = 0;
         for (int b : bits) total += b;
-        if (sec_level == HEGPU_SEC_128 || sec_level == HEGPU_SEC_192 || sec_level == HEGPU_SEC_256) {
-            if (host::max_logq((u64) n, sec_level) < total) // ckks/context.cu:94-119, secstdparams.h:25-79
-                throw std::runtime_error("Parameters do not align with the security recommendations "
-                                         "provided by the lattice-estimator");
-        } else if (sec_level != HEGPU_SEC_NONE) {
-            throw std::runtime_error("Invalid security level");
-        }
+        check_security(n, total, sec_level);
         std::unique_ptr<hegpu_context> h(new hegpu_context());
         h->c.primes = host::find_primes((u64) n, bits);
         return finish_create(std::move(h), scheme, n_power, plain_modulus, qn, pn, out);
@@ -192,10 +205,7 @@ int hegpu_context_create_from_primes(int scheme, int n, const uint64_t* primes, 
         int n_power;
         check_degree(n, n_power);
         if (pn <= 0 || qn <= 0) throw std::logic_error("log_P_bases_bit_sizes cannot be empty!");
-        for (int i = 0; i < qn + pn; i++) {
-            if (primes[i] >> 61) throw std::logic_error("invalid modulus bit size");
-            if ((primes[i] - 1) % (2 * (u64) n)) throw std::logic_error("no sufficient root unity");
-        }
+        for (int i = 0; i < qn + pn; i++) check_prime(primes[i], n);
         std::unique_ptr<hegpu_context> h(new hegpu_context());
         h->c.primes.assign(primes, primes + qn + pn);
         return finish_create(std::move(h), scheme, n_power, plain_modulus, qn, pn, out);
@@ -215,20 +225,14 @@ int hegpu_validate_coeff_modulus_values(int n, const uint64_t* primes, int qn, i
         std::vector<int> bits;
         int total = 0;
         for (int i = 0; i < qn + pn; i++) {
-            if (primes[i] < 2 || primes[i] >> 61) throw std::logic_error("invalid modulus bit size");
-            if ((primes[i] - 1) % (2 * (u64) n)) throw std::logic_error("no sufficient root unity");
+            if (primes[i] < 2) throw std::logic_error("invalid modulus bit size"); // (the constructor does not test this)
+            check_prime(primes[i], n);
             bits.push_back(64 - __builtin_clzll(primes[i]));
             total += bits.back();
         }
         if (!coefficient_validator(bits.data(), qn, bits.data() + qn, pn))
             throw std::logic_error("Invalid parameters, P should be bigger than Q pairs!");
-        if (sec_level == HEGPU_SEC_128 || sec_level == HEGPU_SEC_192 || sec_level == HEGPU_SEC_256) {
-            if (host::max_logq((u64) n, sec_level) < total)
-                throw std::runtime_error("Parameters do not align with the security recommendations "
-                                         "provided by the lattice-estimator");
-        } else if (sec_level != HEGPU_SEC_NONE) {
-            throw std::runtime_error("Invalid security level");
-        }
+        check_security(n, total, sec_level);
         return 0;
     });
 }
@@ -770,23 +774,89 @@ int hegpu_divide_round_lastq_permute(hegpu_context* ctx, const uint64_t* in, uin
                    "hegpu_divide_round_lastq_permute");
 }
 
-#define SEAM_CKKS(ctx, depth, batch, min_limbs)                                                                    \
-    NEED_CTX(ctx);                                                                                                 \
-    const Context& c = (ctx)->c;                                                                                   \
-    if (c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "CKKS context required");                            \
-    if ((depth) < 0 || c.Q_size - (depth) < (min_limbs)) return fail(HEGPU_E_INVALID, "invalid depth");            \
-    if ((batch) < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");                                   \
-    if ((batch) == 0) return 0;                                                                                    \
-    const int l = c.Q_size - (depth);                                                                              \
-    (void) l
+// ------------------------------------------------------------------ the argument rules the entry points share
+// Every check_* below returns 0 (go on), the code of a refusal whose message fail() has stored, or EMPTY_BATCH: the call
+// is a no-op and the entry returns 0 at once.  An entry uses them as `if (int r = check_x(...)) return leave(r);`, or
+// `return r;` where the check has no empty-batch exit.  EMPTY_BATCH is negative: no HEGPU_E_* code and no hipError_t is.
+static const int EMPTY_BATCH = -1;
+static int leave(int r) { return r == EMPTY_BATCH ? 0 : r; }
+static int require(bool ok, const std::string& msg) { return ok ? 0 : fail(HEGPU_E_INVALID, msg); }
+static int check_scheme(const Context& c, int want) { return require(c.scheme == want, "context scheme mismatch"); }
+static int check_batch(int batch) // its sign, and the empty batch: the entry returns leave(r)
+{
+    if (batch < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");
+    return batch == 0 ? EMPTY_BATCH : 0;
+}
+static int check_grid(int batch, int k, const char* who) // a grid dimension holds 65535 blocks, the entry launches k per item
+{
+    if (k * (long) batch <= 65535) return 0;
+    return fail(HEGPU_E_INVALID, std::string(who) + ": at most " + std::to_string(65535 / k) + " items per call");
+}
+static int check_items(int batch, int k, const char* who) // the entries for which an empty batch is a refusal
+{
+    if (batch < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": batch must be at least 1");
+    return check_grid(batch, k, who);
+}
+static int check_depth(const Context& c, int depth) { return require(depth >= 0 && depth < c.Q_size, "invalid depth"); }
+static int check_workspace(const void* ws, size_t have, size_t need) { return require(ws && have >= need, "workspace too small"); }
+// words of a ciphertext of `parts` polynomials at `limbs` limbs
+static uint64_t ct_words(const Context& c, int limbs, int parts = 2) { return (uint64_t) parts * limbs * c.n; }
+static uint64_t level_words(const Context& c, int depth) { return ct_words(c, c.Q_size - depth); } // two parts at `depth`
+static bool galois_elt_ok(const Context& c, int e) { return e > 0 && (e & 1) && e < 2 * (int) c.n; }
+// a list of rotations: element 0 is the identity and needs no key
+static int check_galois_list(const Context& c, const uint64_t* const* keys, const int* elts, int count, const char* who)
+{
+    for (int i = 0; i < count; i++) {
+        if (elts[i] == 0) continue;
+        if (!galois_elt_ok(c, elts[i]))
+            return fail(HEGPU_E_INVALID, std::string(who) + ": Galois elements are odd and below 2N");
+        if (!keys[i]) return fail(HEGPU_E_INVALID, std::string(who) + ": Galois key not present!");
+    }
+    return 0;
+}
+// the baby-step / giant-step shape: 16 products per 128-bit sum, 256 indices by value
+static bool bsgs_shape_ok(int n1, int n2) { return n1 >= 1 && n1 <= 16 && n2 >= 1 && n2 <= 16; }
+static int check_diag_index(const int* index, int n1, int n2, int n_diag, const char* who) // [n2][n1]: a packed diagonal or -1
+{
+    for (int k = 0; k < n1 * n2; k++)
+        if (index[k] < -1 || index[k] >= n_diag)
+            return fail(HEGPU_E_INVALID, std::string(who) + ": index outside [-1, n_diag)");
+    return 0;
+}
+static int check_leaf_weights(const host::PolyStep* p, int n_steps, const char* who) // the constant term included
+{
+    for (int k = 0; k < n_steps; k++) {
+        if (p[k].kind != host::POLY_STEP_LEAF) continue;
+        for (int i = 0; i <= p[k].n_terms; i++) {
+            const double* w = i < p[k].n_terms ? p[k].w[i] : p[k].w0;
+            if (!std::isfinite(w[0]) || !std::isfinite(w[1]))
+                return fail(HEGPU_E_INVALID, std::string(who) + ": a weight is not a finite number");
+        }
+    }
+    return 0;
+}
+// a constant the kernels round to an integer: a number, and inside the range of a float
+static bool constant_in_range(double v) { return v == v && v < 3.4e38 && v > -3.4e38; }
+static int check_shape(const Context& c, int limbs, int parts) // a ciphertext on the Q chain
+{
+    return require(limbs > 0 && limbs <= c.Q_size && parts >= 2 && parts <= 3, "bad ciphertext shape");
+}
+// the leveled seam entries: a CKKS context, at least min_limbs limbs left at `depth`, then the batch
+static int check_seam_ckks(const Context& c, int depth, int batch, int min_limbs)
+{
+    if (c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "CKKS context required");
+    if (depth < 0 || c.Q_size - depth < min_limbs) return fail(HEGPU_E_INVALID, "invalid depth");
+    return check_batch(batch);
+}
 
 int hegpu_divide_round_lastq_leveled_stage_one(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, uint64_t* out,
                                                uint64_t out_stride, int rescale, int depth, int batch,
                                                hegpu_stream stream)
 {
-    SEAM_CKKS(ctx, depth, batch, rescale ? 2 : 1);
-    if (!rescale && c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
-    return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, c.moddown(depth, rescale != 0),
+    NEED_CTX(ctx);
+    if (int r = check_seam_ckks(ctx->c, depth, batch, rescale ? 2 : 1)) return leave(r);
+    if (!rescale && ctx->c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
+    return hip_ret(rns_moddown_stage_one((const u64*) in, in_stride, (u64*) out, out_stride, ctx->c.moddown(depth, rescale != 0),
                                          batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_one");
 }
@@ -796,11 +866,12 @@ int hegpu_divide_round_lastq_leveled_stage_two(hegpu_context* ctx, const uint64_
                                                uint64_t ct_stride, uint64_t* out, uint64_t out_stride, int switchkey,
                                                int depth, int batch, hegpu_stream stream)
 {
-    SEAM_CKKS(ctx, depth, batch, 1);
-    if (c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
+    NEED_CTX(ctx);
+    if (int r = check_seam_ckks(ctx->c, depth, batch, 1)) return leave(r);
+    if (ctx->c.P_size != 1) return fail(HEGPU_E_LOGIC, "the leveled stages serve a single special prime (method I)");
     if (!ct) return fail(HEGPU_E_INVALID, "ct must not be NULL");
     return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, (const u64*) ct,
-                                         ct_stride, (u64*) out, out_stride, c.moddown(depth), switchkey ? 2 : 1, batch,
+                                         ct_stride, (u64*) out, out_stride, ctx->c.moddown(depth), switchkey ? 2 : 1, batch,
                                          (hipStream_t) stream),
                    "hegpu_divide_round_lastq_leveled_stage_two");
 }
@@ -808,9 +879,11 @@ int hegpu_divide_round_lastq_leveled_stage_two(hegpu_context* ctx, const uint64_
 int hegpu_move_cipher_leveled(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, uint64_t* out,
                               uint64_t out_stride, int depth, int batch, hegpu_stream stream)
 {
-    SEAM_CKKS(ctx, depth, batch, 2);
-    return hip_ret(rns_copy_limbs((const u64*) in, (u64) l * c.n, in_stride, (u64*) out, (u64) l * c.n, out_stride,
-                                  c.n_power, l - 1, 2, batch, (hipStream_t) stream),
+    NEED_CTX(ctx);
+    if (int r = check_seam_ckks(ctx->c, depth, batch, 2)) return leave(r);
+    const int l = ctx->c.Q_size - depth;
+    return hip_ret(rns_copy_limbs((const u64*) in, ct_words(ctx->c, l, 1), in_stride, (u64*) out, ct_words(ctx->c, l, 1),
+                                  out_stride, ctx->c.n_power, l - 1, 2, batch, (hipStream_t) stream),
                    "hegpu_move_cipher_leveled");
 }
 
@@ -818,9 +891,10 @@ int hegpu_divide_round_lastq_rescale(hegpu_context* ctx, const uint64_t* in_last
                                      const uint64_t* in, uint64_t in_stride, uint64_t* out, uint64_t out_stride,
                                      int depth, int batch, hegpu_stream stream)
 {
-    SEAM_CKKS(ctx, depth, batch, 2);
+    NEED_CTX(ctx);
+    if (int r = check_seam_ckks(ctx->c, depth, batch, 2)) return leave(r);
     return hip_ret(rns_moddown_stage_two((const u64*) in_last, last_stride, (const u64*) in, in_stride, nullptr, 0,
-                                         (u64*) out, out_stride, c.moddown(depth, true), 0, batch, (hipStream_t) stream),
+                                         (u64*) out, out_stride, ctx->c.moddown(depth, true), 0, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_rescale");
 }
 
@@ -832,10 +906,9 @@ int hegpu_divide_round_lastq_extended(hegpu_context* ctx, const uint64_t* in, ui
     const Context& c = ctx->c;
     if (mode < 0 || mode > 2) return fail(HEGPU_E_INVALID, "mode must be 0, 1 or 2");
     if (c.scheme == SCHEME_BFV && depth != 0) return fail(HEGPU_E_INVALID, "BFV ciphertexts have no depth");
-    if (depth < 0 || depth >= c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    if (int r = check_depth(c, depth)) return r;
     if (mode && !ct) return fail(HEGPU_E_INVALID, "ct must not be NULL");
-    if (batch < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");
-    if (batch == 0) return 0;
+    if (int r = check_batch(batch)) return leave(r);
     return hip_ret(rns_moddown_extended((const u64*) in, in_stride, (const u64*) ct, ct_stride, (u64*) out, out_stride,
                                         c.moddown(depth), mode, batch, (hipStream_t) stream),
                    "hegpu_divide_round_lastq_extended");
@@ -879,22 +952,22 @@ size_t hegpu_workspace_bytes(const hegpu_context* ctx, int op, int depth, int ba
     return ops_workspace_elems(ctx->c, op, depth, batch) * sizeof(u64);
 }
 
-#define CHECK_OP(ctx, want_scheme, op, depth, batch, ws, ws_bytes)                                            \
-    do {                                                                                                      \
-        if ((ctx)->c.scheme != (want_scheme)) return fail(HEGPU_E_INVALID, "context scheme mismatch");        \
-        if ((batch) < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");                          \
-        if ((batch) == 0) return 0; /* an empty batch is a no-op */                                           \
-        if ((depth) < 0 || (depth) >= (ctx)->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");         \
-        if ((op) && (!(ws) || (ws_bytes) < hegpu_workspace_bytes(ctx, op, depth, batch)))                     \
-            return fail(HEGPU_E_INVALID, "workspace too small");                                              \
-    } while (0)
+// the operators: scheme, batch (an empty batch is a no-op), depth, and the workspace row `op` (0: the entry has none, or
+// sizes its workspace itself)
+static int check_op(const hegpu_context* ctx, int want_scheme, int op, int depth, int batch, const void* ws, size_t ws_bytes)
+{
+    if (int r = check_scheme(ctx->c, want_scheme)) return r;
+    if (int r = check_batch(batch)) return r;
+    if (int r = check_depth(ctx->c, depth)) return r;
+    return op ? check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, op, depth, batch)) : 0;
+}
 
 int hegpu_ckks_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t s1, const uint64_t* ct2, uint64_t s2,
                         uint64_t* out, uint64_t so, int depth, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (depth < 0 || depth >= ctx->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_depth(ctx->c, depth)) return r;
     return hip_ret(op_ckks_multiply(ctx->c, (const u64*) ct1, s1, (const u64*) ct2, s2, (u64*) out, so, depth, batch,
                                     (hipStream_t) stream),
                    "hegpu_ckks_multiply");
@@ -904,7 +977,7 @@ int hegpu_ckks_relinearize_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs
                                    int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_RELIN, depth, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_CKKS, OP_CKKS_RELIN, depth, batch, ws, ws_bytes)) return leave(r);
     return hip_ret(op_ckks_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, depth, batch, (u64*) ws,
                                        (hipStream_t) stream),
                    "hegpu_ckks_relinearize_inplace");
@@ -914,7 +987,7 @@ int hegpu_probe_ckks_relinearize(hegpu_context* ctx, uint64_t* ct, uint64_t cs, 
                                  int batch, void* ws, size_t ws_bytes, unsigned phases, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_RELIN, depth, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_CKKS, OP_CKKS_RELIN, depth, batch, ws, ws_bytes)) return leave(r);
     if (ctx->c.P_size != 1) return fail(HEGPU_E_LOGIC, "the phase probe covers key-switching method I");
     return hip_ret(op_ckks_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, depth, batch, (u64*) ws,
                                        (hipStream_t) stream, phases),
@@ -932,7 +1005,7 @@ int hegpu_ckks_rescale_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs, in
                                size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_RESCALE, depth, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_CKKS, OP_CKKS_RESCALE, depth, batch, ws, ws_bytes)) return leave(r);
     if (depth >= ctx->c.Q_size - 1) return fail(HEGPU_E_LOGIC, "no modulus left to rescale by");
     return hip_ret(op_ckks_rescale(ctx->c, (u64*) ct, cs, depth, batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_ckks_rescale_inplace");
@@ -972,18 +1045,30 @@ static bool spans_overlap(const uint64_t* a, uint64_t a_stride, uint64_t a_item,
     return true; // beyond 1024 items with unequal strides: intersecting spans count as overlap (conservative)
 }
 
+// one batch of equally sized items: item i is [p + i * stride, + item)
+struct Span {
+    const uint64_t* p;
+    uint64_t stride, item;
+};
+
+// `out` shares a word with one of `ins`
+static bool overlaps_any(const Span& out, std::initializer_list<Span> ins, int batch)
+{
+    for (const Span& in : ins)
+        if (spans_overlap(in.p, in.stride, in.item, out.p, out.stride, out.item, batch)) return true;
+    return false;
+}
+
 int hegpu_ckks_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
                             const uint64_t* key, int galois_elt, int depth, int batch, void* ws, size_t ws_bytes,
                             hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_GALOIS, depth, batch, ws, ws_bytes);
-    {
-        const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-        if (spans_overlap(ct, cs, words, out, so, words, batch))
-            return fail(HEGPU_E_INVALID, "apply_galois: out must not alias ct (the result buffer must not contain the input)");
-    }
-    if (galois_elt <= 0 || !(galois_elt & 1) || galois_elt >= 2 * (int) ctx->c.n)
+    if (int r = check_op(ctx, SCHEME_CKKS, OP_CKKS_GALOIS, depth, batch, ws, ws_bytes)) return leave(r);
+    const uint64_t words = level_words(ctx->c, depth);
+    if (spans_overlap(ct, cs, words, out, so, words, batch))
+        return fail(HEGPU_E_INVALID, "apply_galois: out must not alias ct (the result buffer must not contain the input)");
+    if (!galois_elt_ok(ctx->c, galois_elt))
         return fail(HEGPU_E_INVALID, "apply_galois: Galois elements are odd and below 2N");
     return hip_ret(op_ckks_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key, galois_elt, depth,
                                         batch, (u64*) ws, (hipStream_t) stream),
@@ -999,7 +1084,7 @@ int hegpu_mod_raise(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride, 
     if (batch < 1 || batch > 65535) return fail(HEGPU_E_INVALID, "mod_raise: 1 to 65535 items per call");
     if (parts < 1 || parts > 3) return fail(HEGPU_E_INVALID, "mod_raise: parts is 1, 2 or 3");
     if (limbs < 1 || limbs > ctx->c.Q_size) return fail(HEGPU_E_INVALID, "mod_raise: 1 <= limbs <= Q");
-    if (spans_overlap(in, in_stride, (uint64_t) parts * ctx->c.n, out, out_stride, (uint64_t) parts * limbs * ctx->c.n, batch))
+    if (spans_overlap(in, in_stride, ct_words(ctx->c, 1, parts), out, out_stride, ct_words(ctx->c, limbs, parts), batch))
         return fail(HEGPU_E_INVALID, "mod_raise: out must not overlap in");
     NEED_CTX(ctx);
     const Context& c = ctx->c;
@@ -1012,17 +1097,15 @@ int hegpu_ckks_mod_raise(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
                          int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     if (!ctx) return fail(HEGPU_E_INVALID, "null context");
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (!ct || !out || !ws) return fail(HEGPU_E_INVALID, "ckks_mod_raise: null argument");
-    if (batch < 1) return fail(HEGPU_E_INVALID, "ckks_mod_raise: batch must be at least 1");
+    if (batch < 1) return fail(HEGPU_E_INVALID, "ckks_mod_raise: batch must be at least 1"); // (no grid limit here)
     if (out_depth < 0 || out_depth >= ctx->c.Q_size) return fail(HEGPU_E_INVALID, "ckks_mod_raise: 0 <= out_depth < Q");
-    const uint64_t in_words = (uint64_t) 2 * ctx->c.n, out_words = in_words * (ctx->c.Q_size - out_depth);
+    const Span in{ct, cs, ct_words(ctx->c, 1)}, res{out, so, level_words(ctx->c, out_depth)};
     const size_t need = ops_workspace_elems(ctx->c, OP_CKKS_MOD_RAISE, out_depth, batch) * sizeof(u64);
-    if (ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
-    if (spans_overlap(ct, cs, in_words, out, so, out_words, batch))
-        return fail(HEGPU_E_INVALID, "ckks_mod_raise: out must not overlap ct");
-    if (spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), out, so, out_words, batch) ||
-        spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), ct, cs, in_words, batch))
+    if (int r = check_workspace(ws, ws_bytes, need)) return r;
+    if (overlaps_any(res, {in}, batch)) return fail(HEGPU_E_INVALID, "ckks_mod_raise: out must not overlap ct");
+    if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in}, batch))
         return fail(HEGPU_E_INVALID, "ckks_mod_raise: the workspace must overlap neither out nor ct");
     NEED_CTX(ctx);
     return hip_ret(op_ckks_mod_raise(ctx->c, (const u64*) ct, cs, (u64*) out, so, out_depth, batch, (u64*) ws,
@@ -1035,18 +1118,13 @@ int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t c
                               void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, OP_CKKS_GALOIS, depth, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_CKKS, OP_CKKS_GALOIS, depth, batch, ws, ws_bytes)) return leave(r);
     if (count <= 0 || !keys || !galois_elts) return fail(HEGPU_E_INVALID, "rotate_hoisted: empty element list");
-    const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    const uint64_t words = level_words(ctx->c, depth);
     if (batch > 1 && so < (uint64_t) count * words) return fail(HEGPU_E_INVALID, "rotate_hoisted: out_stride too small");
     if (spans_overlap(ct, cs, words, out, so, (uint64_t) count * words, batch))
         return fail(HEGPU_E_INVALID, "rotate_hoisted: out must not alias ct (the result buffer must not contain the input)");
-    for (int i = 0; i < count; i++) {
-        if (galois_elts[i] == 0) continue;
-        if (galois_elts[i] < 0 || !(galois_elts[i] & 1) || galois_elts[i] >= 2 * (int) ctx->c.n)
-            return fail(HEGPU_E_INVALID, "rotate_hoisted: Galois elements are odd and below 2N");
-        if (!keys[i]) return fail(HEGPU_E_INVALID, "rotate_hoisted: Galois key not present!");
-    }
+    if (int r = check_galois_list(ctx->c, keys, galois_elts, count, "rotate_hoisted")) return r;
     // with room for four accumulators (HEGPU_OP_CKKS_ROTATE_HOISTED) the inner products of four elements share one
     // read of the digits
     const int group = (ctx->c.fused_moddown && ctx->c.ntt_galois)
@@ -1056,26 +1134,18 @@ int hegpu_ckks_rotate_hoisted(hegpu_context* ctx, const uint64_t* ct, uint64_t c
                    "hegpu_ckks_rotate_hoisted");
 }
 
-// index [n2][n1]: every entry is a packed diagonal or -1
-static bool diag_index_ok(const int* index, int n1, int n2, int n_diag)
-{
-    for (int k = 0; k < n1 * n2; k++)
-        if (index[k] < -1 || index[k] >= n_diag) return false;
-    return true;
-}
-
 int hegpu_ckks_diag_mac(hegpu_context* ctx, const uint64_t* rot, uint64_t rot_stride, int n1, const uint64_t* diags,
                         int n_diag, const int* index, int n2, uint64_t* out, uint64_t out_stride, int depth, int batch,
                         hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
-    if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16)
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
+    if (!bsgs_shape_ok(n1, n2))
         return fail(HEGPU_E_INVALID, "diag_mac: n1 and n2 lie in [1, 16] (16 products per 128-bit sum, 256 indices by value)");
     if (!rot || !diags || !index || !out || n_diag < 1) return fail(HEGPU_E_INVALID, "diag_mac: null argument");
-    if (!diag_index_ok(index, n1, n2, n_diag)) return fail(HEGPU_E_INVALID, "diag_mac: index outside [-1, n_diag)");
-    if (batch > 65535) return fail(HEGPU_E_INVALID, "diag_mac: at most 65535 items per call");
-    const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    if (int r = check_diag_index(index, n1, n2, n_diag, "diag_mac")) return r;
+    if (int r = check_grid(batch, 1, "diag_mac")) return r;
+    const uint64_t words = level_words(ctx->c, depth);
     if (spans_overlap(rot, rot_stride, (uint64_t) n1 * words, out, out_stride, (uint64_t) n2 * words, batch))
         return fail(HEGPU_E_INVALID, "diag_mac: out must not overlap rot");
     return hip_ret(rns_ckks_diag_mac((const u64*) rot, rot_stride, n1, (const u64*) diags, n_diag, index, n2, (u64*) out,
@@ -1086,7 +1156,7 @@ int hegpu_ckks_diag_mac(hegpu_context* ctx, const uint64_t* rot, uint64_t rot_st
 
 size_t hegpu_ckks_linear_transform_workspace_bytes(const hegpu_context* ctx, int n1, int n2, int depth, int batch)
 {
-    if (!ctx || batch <= 0 || n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16 || depth < 0 || depth >= ctx->c.Q_size) return 0;
+    if (!ctx || batch <= 0 || !bsgs_shape_ok(n1, n2) || depth < 0 || depth >= ctx->c.Q_size) return 0;
     return ops_linear_transform_workspace_elems(ctx->c, n1, n2, depth, batch) * sizeof(u64);
 }
 
@@ -1097,26 +1167,19 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                 size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
-    if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16)
-        return fail(HEGPU_E_INVALID, "linear_transform: n1 and n2 lie in [1, 16]");
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
+    if (!bsgs_shape_ok(n1, n2)) return fail(HEGPU_E_INVALID, "linear_transform: n1 and n2 lie in [1, 16]");
     if (!ct || !out || !diags || !index || !baby_keys || !baby_elts || !giant_keys || !giant_elts || n_diag < 1)
         return fail(HEGPU_E_INVALID, "linear_transform: null argument");
-    if (!diag_index_ok(index, n1, n2, n_diag)) return fail(HEGPU_E_INVALID, "linear_transform: index outside [-1, n_diag)");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "linear_transform: at most 32767 items per call");
-    for (int k = 0; k < n1 + n2; k++) {
-        const int e = k < n1 ? baby_elts[k] : giant_elts[k - n1];
-        if (e == 0) continue;
-        if (e < 0 || !(e & 1) || e >= 2 * (int) ctx->c.n)
-            return fail(HEGPU_E_INVALID, "linear_transform: Galois elements are odd and below 2N");
-        if (!(k < n1 ? baby_keys[k] : giant_keys[k - n1]))
-            return fail(HEGPU_E_INVALID, "linear_transform: Galois key not present!");
-    }
-    const uint64_t words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
+    if (int r = check_diag_index(index, n1, n2, n_diag, "linear_transform")) return r;
+    if (int r = check_grid(batch, 2, "linear_transform")) return r;
+    if (int r = check_galois_list(ctx->c, baby_keys, baby_elts, n1, "linear_transform")) return r;
+    if (int r = check_galois_list(ctx->c, giant_keys, giant_elts, n2, "linear_transform")) return r;
+    const uint64_t words = level_words(ctx->c, depth);
     if (spans_overlap(ct, cs, words, out, so, words, batch))
         return fail(HEGPU_E_INVALID, "linear_transform: out must not overlap ct");
-    if (!ws || ws_bytes < hegpu_ckks_linear_transform_workspace_bytes(ctx, n1, n2, depth, batch))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_workspace(ws, ws_bytes, hegpu_ckks_linear_transform_workspace_bytes(ctx, n1, n2, depth, batch)))
+        return r;
     return hip_ret(op_ckks_linear_transform(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) diags, n_diag, index,
                                             n1, n2, (const u64* const*) baby_keys, baby_elts,
                                             (const u64* const*) giant_keys, giant_elts, depth, batch, (u64*) ws,
@@ -1130,9 +1193,8 @@ int hegpu_ckks_weighted_sum(hegpu_context* ctx, const uint64_t* const* terms, co
                             uint64_t* out, uint64_t out_stride, int limbs, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (batch < 1) return fail(HEGPU_E_INVALID, "weighted_sum: batch must be at least 1");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "weighted_sum: at most 32767 items per call");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_items(batch, 2, "weighted_sum")) return r;
     if (count < 0 || count > 15)
         return fail(HEGPU_E_INVALID, "weighted_sum: at most 15 terms (15 products and a residue per 128-bit sum)");
     if (limbs < 1 || limbs > ctx->c.Q_size) return fail(HEGPU_E_INVALID, "weighted_sum: bad limb count");
@@ -1140,14 +1202,14 @@ int hegpu_ckks_weighted_sum(hegpu_context* ctx, const uint64_t* const* terms, co
         return fail(HEGPU_E_INVALID, "weighted_sum: null argument");
     for (double v : {w0_re, w0_im})
         if (!std::isfinite(v)) return fail(HEGPU_E_INVALID, "weighted_sum: a weight is not a finite number");
-    const uint64_t out_words = (uint64_t) 2 * limbs * ctx->c.n;
+    const Span res{out, out_stride, ct_words(ctx->c, limbs)};
     for (int k = 0; k < count; k++) {
         if (!terms[k]) return fail(HEGPU_E_INVALID, "weighted_sum: null argument");
         if (term_limbs[k] < limbs || term_limbs[k] > ctx->c.Q_size)
             return fail(HEGPU_E_INVALID, "weighted_sum: a term has fewer limbs than the sum");
         if (!std::isfinite(weights[2 * k]) || !std::isfinite(weights[2 * k + 1]))
             return fail(HEGPU_E_INVALID, "weighted_sum: a weight is not a finite number");
-        if (spans_overlap(terms[k], term_strides[k], (uint64_t) 2 * term_limbs[k] * ctx->c.n, out, out_stride, out_words, batch))
+        if (overlaps_any(res, {{terms[k], term_strides[k], ct_words(ctx->c, term_limbs[k])}}, batch))
             return fail(HEGPU_E_INVALID, "weighted_sum: out must not overlap a term");
     }
     return hip_ret(rns_ckks_weighted_sum((const u64* const*) terms, (const u64*) term_strides, term_limbs, weights, count,
@@ -1161,19 +1223,17 @@ int hegpu_ckks_double_sub(hegpu_context* ctx, const uint64_t* a, uint64_t a_stri
                           int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (batch < 1) return fail(HEGPU_E_INVALID, "double_sub: batch must be at least 1");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "double_sub: at most 32767 items per call");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_items(batch, 2, "double_sub")) return r;
     if (!a || !out) return fail(HEGPU_E_INVALID, "double_sub: null argument");
     if (limbs < 1 || a_limbs < limbs || a_limbs > ctx->c.Q_size || (b && (b_limbs < limbs || b_limbs > ctx->c.Q_size)))
         return fail(HEGPU_E_INVALID, "double_sub: bad limb count");
-    if (!b && (!(value == value) || value >= 3.4e38 || value <= -3.4e38))
-        return fail(HEGPU_E_INVALID, "double_sub: constant out of range");
-    const uint64_t n = ctx->c.n, out_words = (uint64_t) 2 * limbs * n;
+    if (!b && !constant_in_range(value)) return fail(HEGPU_E_INVALID, "double_sub: constant out of range");
+    const Span res{out, out_stride, ct_words(ctx->c, limbs)};
     const bool in_place = a == out && a_stride == out_stride && a_limbs == limbs;
-    if (!in_place && spans_overlap(a, a_stride, (uint64_t) 2 * a_limbs * n, out, out_stride, out_words, batch))
+    if (!in_place && overlaps_any(res, {{a, a_stride, ct_words(ctx->c, a_limbs)}}, batch))
         return fail(HEGPU_E_INVALID, "double_sub: out is a itself (equal strides and limb counts) or does not overlap it");
-    if (b && spans_overlap(b, b_stride, (uint64_t) 2 * b_limbs * n, out, out_stride, out_words, batch))
+    if (b && overlaps_any(res, {{b, b_stride, ct_words(ctx->c, b_limbs)}}, batch))
         return fail(HEGPU_E_INVALID, "double_sub: out must not overlap b");
     return hip_ret(rns_ckks_double_sub((const u64*) a, a_stride, a_limbs, (const u64*) b, b_stride, b_limbs, value, (u64*) out,
                                        out_stride, ctx->c.plan_qp.mods, ctx->c.n_power, limbs, batch, (hipStream_t) stream),
@@ -1199,27 +1259,20 @@ int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
                          void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (batch < 1) return fail(HEGPU_E_INVALID, "poly_eval: batch must be at least 1");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "poly_eval: at most 32767 items per call");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_items(batch, 2, "poly_eval")) return r;
     if (!ct || !out || !plan || !relin_key || !ws) return fail(HEGPU_E_INVALID, "poly_eval: null argument");
     const host::PolyStep* p = reinterpret_cast<const host::PolyStep*>(plan);
     return guarded([&]() -> int {
         if (const char* why = ops_poly_eval_check(ctx->c, p, n_steps, depth))
             return fail(HEGPU_E_INVALID, std::string("poly_eval: ") + why);
-        for (int k = 0; k < n_steps; k++) {
-            if (p[k].kind != host::POLY_STEP_LEAF) continue;
-            for (int i = 0; i <= p[k].n_terms; i++) {
-                const double* w = i < p[k].n_terms ? p[k].w[i] : p[k].w0;
-                if (!std::isfinite(w[0]) || !std::isfinite(w[1])) return fail(HEGPU_E_INVALID, "poly_eval: a weight is not a finite number");
-            }
-        }
+        if (int r = check_leaf_weights(p, n_steps, "poly_eval")) return r;
         const host::PolyStep& last = p[n_steps - 1];
-        const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-        const uint64_t out_words = (uint64_t) 2 * (last.level + 1 + (last.rescale_after ? 1 : 0)) * ctx->c.n;
-        if (spans_overlap(ct, cs, in_words, out, so, out_words, batch)) return fail(HEGPU_E_INVALID, "poly_eval: out must not overlap ct");
-        if (ws_bytes < hegpu_ckks_poly_eval_workspace_bytes(ctx, plan, n_steps, depth, batch))
-            return fail(HEGPU_E_INVALID, "workspace too small");
+        const uint64_t out_words = ct_words(ctx->c, last.level + 1 + (last.rescale_after ? 1 : 0));
+        if (spans_overlap(ct, cs, level_words(ctx->c, depth), out, so, out_words, batch))
+            return fail(HEGPU_E_INVALID, "poly_eval: out must not overlap ct");
+        if (int r = check_workspace(ws, ws_bytes, hegpu_ckks_poly_eval_workspace_bytes(ctx, plan, n_steps, depth, batch)))
+            return r;
         return hip_ret(op_ckks_poly_eval(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, n_steps, (const u64*) relin_key, depth,
                                          batch, (u64*) ws, (hipStream_t) stream),
                        "hegpu_ckks_poly_eval");
@@ -1229,11 +1282,8 @@ int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
 // ---- the real / imaginary boundary passes and the CoeffToSlot / SlotToCoeff sequences
 static int conj_pass_check(const hegpu_context* ctx, int depth, int out_depth, int batch, const char* who)
 {
-    if (batch < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": batch must be at least 1");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, std::string(who) + ": at most 32767 items per call");
-    if (depth < 0 || out_depth < depth || out_depth >= ctx->c.Q_size)
-        return fail(HEGPU_E_INVALID, std::string(who) + ": depth <= out_depth < Q");
-    return 0;
+    if (int r = check_items(batch, 2, who)) return r;
+    return require(depth >= 0 && out_depth >= depth && out_depth < ctx->c.Q_size, std::string(who) + ": depth <= out_depth < Q");
 }
 
 int hegpu_ckks_conj_split(hegpu_context* ctx, const uint64_t* x, uint64_t x_stride, const uint64_t* xc,
@@ -1241,17 +1291,14 @@ int hegpu_ckks_conj_split(hegpu_context* ctx, const uint64_t* x, uint64_t x_stri
                           int out_depth, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (int r = conj_pass_check(ctx, depth, out_depth, batch, "conj_split")) return r;
     if (!x || !xc || !out0 || !out1) return fail(HEGPU_E_INVALID, "conj_split: null argument");
-    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - out_depth) * ctx->c.n;
-    for (const uint64_t* in : {x, xc})
-        for (uint64_t* out : {out0, out1})
-            if (spans_overlap(in, in == x ? x_stride : xc_stride, in_words, out, out_stride, out_words, batch))
-                return fail(HEGPU_E_INVALID, "conj_split: an output must not overlap an input");
-    if (spans_overlap(out0, out_stride, out_words, out1, out_stride, out_words, batch))
-        return fail(HEGPU_E_INVALID, "conj_split: the two outputs must not overlap");
+    const Span a{x, x_stride, level_words(ctx->c, depth)}, b{xc, xc == x ? x_stride : xc_stride, a.item}; // (sic: one buffer, x's stride)
+    const Span res0{out0, out_stride, level_words(ctx->c, out_depth)}, res1{out1, out_stride, res0.item};
+    if (overlaps_any(res0, {a, b}, batch) || overlaps_any(res1, {a, b}, batch))
+        return fail(HEGPU_E_INVALID, "conj_split: an output must not overlap an input");
+    if (overlaps_any(res1, {res0}, batch)) return fail(HEGPU_E_INVALID, "conj_split: the two outputs must not overlap");
     return hip_ret(rns_ckks_conj_split((const u64*) x, x_stride, (const u64*) xc, xc_stride, (u64*) out0, (u64*) out1,
                                        out_stride, ctx->c.tab.psi_half, ctx->c.plan_qp.mods, ctx->c.n_power,
                                        ctx->c.Q_size - depth, ctx->c.Q_size - out_depth, batch, (hipStream_t) stream),
@@ -1263,13 +1310,12 @@ int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_st
                           hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (int r = conj_pass_check(ctx, depth, out_depth, batch, "conj_merge")) return r;
     if (!c0 || !c1 || !out) return fail(HEGPU_E_INVALID, "conj_merge: null argument");
-    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - out_depth) * ctx->c.n;
-    if (spans_overlap(c0, c0_stride, in_words, out, out_stride, out_words, batch) ||
-        spans_overlap(c1, c1_stride, in_words, out, out_stride, out_words, batch))
+    const uint64_t in_words = level_words(ctx->c, depth);
+    if (overlaps_any({out, out_stride, level_words(ctx->c, out_depth)},
+                     {{c0, c0_stride, in_words}, {c1, c1_stride, in_words}}, batch))
         return fail(HEGPU_E_INVALID, "conj_merge: the output must not overlap an input");
     return hip_ret(rns_ckks_conj_merge((const u64*) c0, c0_stride, (const u64*) c1, c1_stride, (u64*) out, out_stride,
                                        ctx->c.tab.psi_half, ctx->c.plan_qp.mods, ctx->c.n_power, ctx->c.Q_size - depth,
@@ -1277,7 +1323,7 @@ int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_st
                    "hegpu_ckks_conj_merge");
 }
 
-// the factor array of a sequence entry: every factor as hegpu_ckks_linear_transform checks its arguments
+// the factor array of a sequence entry: every factor through the checks of hegpu_ckks_linear_transform's matrix arguments
 static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f, int count, int depth, const char* who)
 {
     if (!f || count < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": at least one factor");
@@ -1286,20 +1332,12 @@ static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f,
                                                         "at the real / imaginary boundary)");
     for (int k = 0; k < count; k++) {
         const hegpu_linear_factor& a = f[k];
-        if (a.n1 < 1 || a.n1 > 16 || a.n2 < 1 || a.n2 > 16)
-            return fail(HEGPU_E_INVALID, std::string(who) + ": n1 and n2 lie in [1, 16]");
+        if (!bsgs_shape_ok(a.n1, a.n2)) return fail(HEGPU_E_INVALID, std::string(who) + ": n1 and n2 lie in [1, 16]");
         if (!a.diags || !a.index || !a.baby_keys || !a.baby_elts || !a.giant_keys || !a.giant_elts || a.n_diag < 1)
             return fail(HEGPU_E_INVALID, std::string(who) + ": null argument in a factor");
-        if (!diag_index_ok(a.index, a.n1, a.n2, a.n_diag))
-            return fail(HEGPU_E_INVALID, std::string(who) + ": index outside [-1, n_diag)");
-        for (int i = 0; i < a.n1 + a.n2; i++) {
-            const int e = i < a.n1 ? a.baby_elts[i] : a.giant_elts[i - a.n1];
-            if (e == 0) continue;
-            if (e < 0 || !(e & 1) || e >= 2 * (int) ctx->c.n)
-                return fail(HEGPU_E_INVALID, std::string(who) + ": Galois elements are odd and below 2N");
-            if (!(i < a.n1 ? a.baby_keys[i] : a.giant_keys[i - a.n1]))
-                return fail(HEGPU_E_INVALID, std::string(who) + ": Galois key not present!");
-        }
+        if (int r = check_diag_index(a.index, a.n1, a.n2, a.n_diag, who)) return r;
+        if (int r = check_galois_list(ctx->c, a.baby_keys, a.baby_elts, a.n1, who)) return r;
+        if (int r = check_galois_list(ctx->c, a.giant_keys, a.giant_elts, a.n2, who)) return r;
     }
     return 0;
 }
@@ -1319,7 +1357,7 @@ size_t hegpu_ckks_encoding_transform_workspace_bytes(const hegpu_context* ctx, c
 {
     if (!ctx || !factors || batch <= 0 || count < 1 || depth < 0 || depth >= ctx->c.Q_size) return 0;
     for (int k = 0; k < count; k++)
-        if (factors[k].n1 < 1 || factors[k].n1 > 16 || factors[k].n2 < 1 || factors[k].n2 > 16) return 0;
+        if (!bsgs_shape_ok(factors[k].n1, factors[k].n2)) return 0;
     return ops_encoding_transform_workspace_elems(ctx->c, factors_of(factors, count).data(), count, depth, batch) *
            sizeof(u64);
 }
@@ -1329,18 +1367,16 @@ int hegpu_ckks_coeff_to_slot(hegpu_context* ctx, const uint64_t* ct, uint64_t cs
                              int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     if (int r = factors_check(ctx, factors, count, depth, "coeff_to_slot")) return r;
     if (!ct || !out0 || !out1 || !conj_key) return fail(HEGPU_E_INVALID, "coeff_to_slot: null argument");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "coeff_to_slot: at most 32767 items per call");
-    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - depth - count - 1) * ctx->c.n;
-    if (spans_overlap(ct, cs, in_words, out0, so, out_words, batch) ||
-        spans_overlap(ct, cs, in_words, out1, so, out_words, batch) ||
-        spans_overlap(out0, so, out_words, out1, so, out_words, batch))
+    if (int r = check_grid(batch, 2, "coeff_to_slot")) return r;
+    const uint64_t out_words = level_words(ctx->c, depth + count + 1);
+    const Span in{ct, cs, level_words(ctx->c, depth)}, res0{out0, so, out_words}, res1{out1, so, out_words};
+    if (overlaps_any(res0, {in}, batch) || overlaps_any(res1, {in, res0}, batch))
         return fail(HEGPU_E_INVALID, "coeff_to_slot: the outputs must overlap neither ct nor each other");
-    if (!ws || ws_bytes < hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_workspace(ws, ws_bytes, hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch)))
+        return r;
     return guarded([&]() -> int {
         return hip_ret(op_ckks_coeff_to_slot(ctx->c, (const u64*) ct, cs, (u64*) out0, (u64*) out1, so,
                                              factors_of(factors, count).data(), count, (const u64*) conj_key, depth,
@@ -1354,18 +1390,17 @@ int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0
                              int count, int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     if (int r = factors_check(ctx, factors, count, depth, "slot_to_coeff")) return r;
     if (!c0 || !c1 || !out) return fail(HEGPU_E_INVALID, "slot_to_coeff: null argument");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "slot_to_coeff: at most 32767 items per call");
-    const uint64_t in_words = (uint64_t) 2 * (ctx->c.Q_size - depth) * ctx->c.n;
-    const uint64_t out_words = (uint64_t) 2 * (ctx->c.Q_size - depth - count) * ctx->c.n; // before the last rescale
+    if (int r = check_grid(batch, 2, "slot_to_coeff")) return r;
+    const uint64_t in_words = level_words(ctx->c, depth);
+    const uint64_t out_words = level_words(ctx->c, depth + count); // before the last rescale
     if (batch > 1 && so < out_words) return fail(HEGPU_E_INVALID, "slot_to_coeff: out_stride too small");
-    if (spans_overlap(c0, c0_stride, in_words, out, so, out_words, batch) ||
-        spans_overlap(c1, c1_stride, in_words, out, so, out_words, batch))
+    if (overlaps_any({out, so, out_words}, {{c0, c0_stride, in_words}, {c1, c1_stride, in_words}}, batch))
         return fail(HEGPU_E_INVALID, "slot_to_coeff: out must not overlap an input");
-    if (!ws || ws_bytes < hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_workspace(ws, ws_bytes, hegpu_ckks_encoding_transform_workspace_bytes(ctx, factors, count, depth, batch)))
+        return r;
     return guarded([&]() -> int {
         return hip_ret(op_ckks_slot_to_coeff(ctx->c, (const u64*) c0, c0_stride, (const u64*) c1, c1_stride, (u64*) out, so,
                                              factors_of(factors, count).data(), count, depth, batch, (u64*) ws,
@@ -1380,10 +1415,9 @@ static int bootstrap_check(const hegpu_context* ctx, const hegpu_bootstrap_plan*
                            int stc_count, int batch)
 {
     if (!ctx) return fail(HEGPU_E_INVALID, "null context");
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (!plan || !eval_mod || !cts || !stc) return fail(HEGPU_E_INVALID, "bootstrap: null argument");
-    if (batch < 1) return fail(HEGPU_E_INVALID, "bootstrap: batch must be at least 1");
-    if (4 * (long) batch > 65535) return fail(HEGPU_E_INVALID, "bootstrap: at most 16383 items per call");
+    if (int r = check_items(batch, 4, "bootstrap")) return r;
     host::BootstrapPlan p;
     std::memcpy(&p, plan, sizeof(p));
     if (const char* why = ops_bootstrap_check(ctx->c, p, reinterpret_cast<const host::PolyStep*>(eval_mod), n_steps))
@@ -1428,22 +1462,14 @@ int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
         host::BootstrapPlan p;
         std::memcpy(&p, plan, sizeof(p));
         const host::PolyStep* steps = reinterpret_cast<const host::PolyStep*>(eval_mod);
-        for (int k = 0; k < n_steps; k++) {
-            if (steps[k].kind != host::POLY_STEP_LEAF) continue;
-            for (int i = 0; i <= steps[k].n_terms; i++) {
-                const double* w = i < steps[k].n_terms ? steps[k].w[i] : steps[k].w0;
-                if (!std::isfinite(w[0]) || !std::isfinite(w[1])) return fail(HEGPU_E_INVALID, "bootstrap: a weight is not a finite number");
-            }
-        }
-        const uint64_t in_words = (uint64_t) 2 * ctx->c.n, out_words = in_words * (p.out_level + 2); // before the last rescale
-        if (batch > 1 && so < out_words) return fail(HEGPU_E_INVALID, "bootstrap: out_stride too small");
+        if (int r = check_leaf_weights(steps, n_steps, "bootstrap")) return r;
+        const Span in{ct, cs, ct_words(ctx->c, 1)}, res{out, so, ct_words(ctx->c, p.out_level + 2)}; // before the last rescale
+        if (batch > 1 && so < res.item) return fail(HEGPU_E_INVALID, "bootstrap: out_stride too small");
         const size_t need = hegpu_ckks_bootstrap_workspace_bytes(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count,
                                                                  swk_dense_to_sparse != nullptr, batch);
         if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
-        if (spans_overlap(ct, cs, in_words, out, so, out_words, batch))
-            return fail(HEGPU_E_INVALID, "bootstrap: out must not overlap ct");
-        if (spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), out, so, out_words, batch) ||
-            spans_overlap((const uint64_t*) ws, 0, need / sizeof(u64), ct, cs, in_words, batch))
+        if (overlaps_any(res, {in}, batch)) return fail(HEGPU_E_INVALID, "bootstrap: out must not overlap ct");
+        if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in}, batch))
             return fail(HEGPU_E_INVALID, "bootstrap: the workspace must overlap neither out nor ct");
         NEED_CTX(ctx);
         return hip_ret(op_ckks_bootstrap(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, steps, n_steps,
@@ -1458,11 +1484,9 @@ int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t s1, con
                        uint64_t* out, uint64_t so, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (batch < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");
-    if (batch == 0) return 0;
-    if (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_BFV_MULTIPLY, 0, batch))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
+    if (int r = check_batch(batch)) return leave(r);
+    if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_BFV_MULTIPLY, 0, batch))) return r;
     return hip_ret(op_bfv_multiply(ctx->c, (const u64*) ct1, s1, (const u64*) ct2, s2, (u64*) out, so, batch,
                                    (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_multiply");
@@ -1472,7 +1496,7 @@ int hegpu_bfv_relinearize_inplace(hegpu_context* ctx, uint64_t* ct, uint64_t cs,
                                   void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_BFV, OP_BFV_RELIN, 0, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_BFV, OP_BFV_RELIN, 0, batch, ws, ws_bytes)) return leave(r);
     return hip_ret(op_bfv_relinearize(ctx->c, (u64*) ct, cs, (const u64*) key, batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_relinearize_inplace");
 }
@@ -1482,12 +1506,10 @@ int hegpu_bfv_apply_galois(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, 
                            hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_BFV, OP_BFV_GALOIS, 0, batch, ws, ws_bytes);
-    {
-        const uint64_t words = (uint64_t) 2 * ctx->c.Q_size * ctx->c.n;
-        if (spans_overlap(ct, cs, words, out, so, words, batch))
-            return fail(HEGPU_E_INVALID, "apply_galois: out must not alias ct (the result buffer must not contain the input)");
-    }
+    if (int r = check_op(ctx, SCHEME_BFV, OP_BFV_GALOIS, 0, batch, ws, ws_bytes)) return leave(r);
+    const uint64_t words = level_words(ctx->c, 0);
+    if (spans_overlap(ct, cs, words, out, so, words, batch))
+        return fail(HEGPU_E_INVALID, "apply_galois: out must not alias ct (the result buffer must not contain the input)");
     return hip_ret(op_bfv_apply_galois(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) key, galois_elt, batch,
                                        (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_apply_galois");
@@ -1561,18 +1583,18 @@ void hegpu_rng_destroy(hegpu_rng* rng)
     delete rng;
 }
 
-#define CHECK_KG(ctx, rng, op, ws, ws_bytes)                                                          \
-    do {                                                                                              \
-        if (!(rng)) return fail(HEGPU_E_INVALID, "null random generator");                            \
-        if (!(ws) || (ws_bytes) < hegpu_workspace_bytes(ctx, op, 0, 1))                               \
-            return fail(HEGPU_E_INVALID, "workspace too small");                                      \
-    } while (0)
+// key generation and encryption: the party's generator and the workspace row `op` for one item
+static int check_kg(const hegpu_context* ctx, const hegpu_rng* rng, int op, const void* ws, size_t ws_bytes)
+{
+    if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
+    return check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, op, 0, 1));
+}
 
 int hegpu_generate_secret_key(hegpu_context* ctx, hegpu_rng* rng, int hamming_weight, uint64_t* sk, void* ws,
                               size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_KEYGEN_SECRET, ws, ws_bytes);
+    if (int r = check_kg(ctx, rng, OP_KEYGEN_SECRET, ws, ws_bytes)) return r;
     if (hamming_weight <= 0 || hamming_weight > (int) ctx->c.n)
         return fail(HEGPU_E_INVALID, "hamming weight has to be in range 0 to ring size"); // secretkey.cu:43
     return hip_ret(op_gen_secret_key(ctx->c, rng->r, hamming_weight, (u64*) sk, (u64*) ws, (hipStream_t) stream),
@@ -1583,7 +1605,7 @@ int hegpu_generate_public_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
                               size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_KEYGEN_PUBLIC, ws, ws_bytes);
+    if (int r = check_kg(ctx, rng, OP_KEYGEN_PUBLIC, ws, ws_bytes)) return r;
     return hip_ret(op_gen_public_key(ctx->c, rng->r, (const u64*) sk, (u64*) pk, (u64*) ws, (hipStream_t) stream),
                    "hegpu_generate_public_key");
 }
@@ -1592,7 +1614,7 @@ int hegpu_generate_relin_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t*
                              size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes);
+    if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
     return hip_ret(op_gen_switch_key(ctx->c, rng->r, (const u64*) sk, 0, nullptr, (u64*) rk, (u64*) ws,
                                      (hipStream_t) stream),
                    "hegpu_generate_relin_key");
@@ -1602,7 +1624,7 @@ int hegpu_generate_switch_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
                               uint64_t* swk, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes);
+    if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
     if (!old_sk) return fail(HEGPU_E_INVALID, "null old secret key");
     return hip_ret(op_gen_switch_key(ctx->c, rng->r, (const u64*) new_sk, 0, (const u64*) old_sk, (u64*) swk, (u64*) ws,
                                      (hipStream_t) stream),
@@ -1613,9 +1635,8 @@ int hegpu_generate_galois_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
                               void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes);
-    if (!(galois_elt & 1) || galois_elt <= 0 || galois_elt >= (int) (2 * ctx->c.n))
-        return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
+    if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
+    if (!galois_elt_ok(ctx->c, galois_elt)) return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
     return hip_ret(op_gen_switch_key(ctx->c, rng->r, (const u64*) sk, galois_elt, nullptr, (u64*) gk, (u64*) ws,
                                      (hipStream_t) stream),
                    "hegpu_generate_galois_key");
@@ -1625,8 +1646,8 @@ int hegpu_ckks_encrypt(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* pk, c
                        void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    CHECK_KG(ctx, rng, OP_CKKS_ENCRYPT, ws, ws_bytes);
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_kg(ctx, rng, OP_CKKS_ENCRYPT, ws, ws_bytes)) return r;
     return hip_ret(op_ckks_encrypt(ctx->c, rng->r, (const u64*) pk, (const u64*) plain, (u64*) ct, (u64*) ws,
                                    (hipStream_t) stream),
                    "hegpu_ckks_encrypt");
@@ -1636,8 +1657,8 @@ int hegpu_ckks_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* s
                        hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (depth < 0 || depth >= ctx->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_depth(ctx->c, depth)) return r;
     return hip_ret(op_ckks_decrypt(ctx->c, (const u64*) ct, (const u64*) sk, depth, (u64*) plain,
                                    (hipStream_t) stream),
                    "hegpu_ckks_decrypt");
@@ -1647,8 +1668,8 @@ int hegpu_bfv_encrypt(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* pk, co
                       void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    CHECK_KG(ctx, rng, OP_BFV_ENCRYPT, ws, ws_bytes);
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
+    if (int r = check_kg(ctx, rng, OP_BFV_ENCRYPT, ws, ws_bytes)) return r;
     return hip_ret(op_bfv_encrypt(ctx->c, rng->r, (const u64*) pk, (const u64*) plain, (u64*) ct, (u64*) ws,
                                   (hipStream_t) stream),
                    "hegpu_bfv_encrypt");
@@ -1658,9 +1679,8 @@ int hegpu_bfv_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* sk
                       size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_BFV_DECRYPT, 0, 1))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
+    if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_BFV_DECRYPT, 0, 1))) return r;
     return guarded([&]() -> int {
         return hip_ret(op_bfv_decrypt(ctx->c, (const u64*) ct, (const u64*) sk, (u64*) plain, (u64*) ws,
                                       (hipStream_t) stream),
@@ -1669,13 +1689,12 @@ int hegpu_bfv_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* sk
 }
 
 // ------------------------------------------------------------------ N-out-of-N multiparty protocol
-#define CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes)                                                                 \
-    do {                                                                                                          \
-        CHECK_KG(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes);                                                       \
-        if (!(crs)) return fail(HEGPU_E_INVALID, "null common random generator");                                 \
-        if ((crs) == (rng))                                                                                       \
-            return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's errors are private"); \
-    } while (0)
+static int check_mpc_kg(const hegpu_context* ctx, const hegpu_rng* crs, const hegpu_rng* rng, const void* ws, size_t ws_bytes)
+{
+    if (int r = check_kg(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes)) return r;
+    if (!crs) return fail(HEGPU_E_INVALID, "null common random generator");
+    return require(crs != rng, "crs and rng must be different generators: the party's errors are private");
+}
 
 static int check_shares(const uint64_t* const* shares, int k, const void* out)
 {
@@ -1691,7 +1710,7 @@ int hegpu_mpc_public_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rn
                                void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
     return hip_ret(op_mpc_public_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, (u64*) share, (u64*) ws,
                                            (hipStream_t) stream),
@@ -1702,7 +1721,7 @@ int hegpu_mpc_relin_key_share_round1(hegpu_context* ctx, hegpu_rng* crs, hegpu_r
                                      uint64_t* u_out, uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share || !u_out) return fail(HEGPU_E_INVALID, "null argument");
     return hip_ret(op_mpc_switch_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, 0, (u64*) u_out, (u64*) share,
                                            (u64*) ws, (hipStream_t) stream),
@@ -1714,7 +1733,7 @@ int hegpu_mpc_relin_key_share_round2(hegpu_context* ctx, hegpu_rng* rng, const u
                                      hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_KG(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes);
+    if (int r = check_kg(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes)) return r;
     if (!sk || !u || !round1_sum || !share) return fail(HEGPU_E_INVALID, "null argument");
     if (share == round1_sum) return fail(HEGPU_E_INVALID, "the share must not overwrite the round-1 sum");
     return hip_ret(op_mpc_relin_key_share_round2(ctx->c, rng->r, (const u64*) sk, (const u64*) u,
@@ -1726,10 +1745,9 @@ int hegpu_mpc_galois_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rn
                                uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_MPC_KG(ctx, crs, rng, ws, ws_bytes);
+    if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
-    if (!(galois_elt & 1) || galois_elt <= 0 || galois_elt >= (int) (2 * ctx->c.n))
-        return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
+    if (!galois_elt_ok(ctx->c, galois_elt)) return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
     return hip_ret(op_mpc_switch_key_share(ctx->c, crs->r, rng->r, (const u64*) sk, galois_elt, nullptr, (u64*) share,
                                            (u64*) ws, (hipStream_t) stream),
                    "hegpu_mpc_galois_key_share");
@@ -1764,7 +1782,7 @@ int hegpu_mpc_ckks_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint6
                                  const uint64_t* sk, int depth, uint64_t* share, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
     return hip_ret(op_mpc_ckks_decrypt_share(ctx->c, rng->r, (const u64*) ct, cs, (const u64*) sk, depth, (u64*) share,
@@ -1776,10 +1794,10 @@ int hegpu_mpc_ckks_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_
                                  int k, int depth, uint64_t* plain, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (!ct || !plain) return fail(HEGPU_E_INVALID, "null argument");
     if (const int rc = check_shares(shares, k, plain)) return rc;
-    CHECK_OP(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0);
+    if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     return hip_ret(op_mpc_ckks_decrypt_merge(ctx->c, (const u64*) ct, cs, (const u64* const*) shares, k, depth,
                                              (u64*) plain, batch, (hipStream_t) stream),
                    "hegpu_mpc_ckks_decrypt_merge");
@@ -1789,7 +1807,7 @@ int hegpu_mpc_bfv_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64
                                 const uint64_t* sk, uint64_t* share, int batch, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_OP(ctx, SCHEME_BFV, 0, 0, batch, nullptr, 0);
+    if (int r = check_op(ctx, SCHEME_BFV, 0, 0, batch, nullptr, 0)) return leave(r);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
     return hip_ret(op_mpc_bfv_decrypt_share(ctx->c, rng->r, (const u64*) ct, cs, (const u64*) sk, (u64*) share, batch,
@@ -1801,53 +1819,50 @@ int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                 int k, uint64_t* plain, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     if (!ct || !plain) return fail(HEGPU_E_INVALID, "null argument");
     if (const int rc = check_shares(shares, k, plain)) return rc;
-    CHECK_OP(ctx, SCHEME_BFV, OP_MPC_BFV_DECRYPT_MERGE, 0, batch, ws, ws_bytes);
+    if (int r = check_op(ctx, SCHEME_BFV, OP_MPC_BFV_DECRYPT_MERGE, 0, batch, ws, ws_bytes)) return leave(r);
     return hip_ret(op_mpc_bfv_decrypt_merge(ctx->c, (const u64*) ct, cs, (const u64* const*) shares, k, (u64*) plain,
                                             batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_mpc_bfv_decrypt_merge");
 }
 
 // ---- collective refresh.  The checks every entry shares; the workspace row may be empty (a share needs none)
-#define CHECK_REFRESH(ctx, want_scheme, op, depth, batch, ws, ws_bytes)                                        \
-    do {                                                                                                       \
-        if ((ctx)->c.scheme != (want_scheme)) return fail(HEGPU_E_INVALID, "context scheme mismatch");         \
-        if ((batch) < 0) return fail(HEGPU_E_INVALID, "batch must not be negative");                           \
-        if ((depth) < 0 || (depth) >= (ctx)->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");          \
-        if (!crs) return fail(HEGPU_E_INVALID, "null common random generator");                                \
-        if ((batch) == 0) return 0; /* an empty batch is a no-op */                                            \
-        {                                                                                                      \
-            const size_t need = hegpu_workspace_bytes(ctx, op, depth, batch);                                  \
-            if (need && (!(ws) || (ws_bytes) < need)) return fail(HEGPU_E_INVALID, "workspace too small");     \
-        }                                                                                                      \
-    } while (0)
+// Unlike the operators, the depth and the common generator are looked at before an empty batch leaves.
+static int check_refresh(const hegpu_context* ctx, int want_scheme, int op, int depth, int batch, const hegpu_rng* crs,
+                         const void* ws, size_t ws_bytes)
+{
+    if (int r = check_scheme(ctx->c, want_scheme)) return r;
+    const int b = check_batch(batch);
+    if (b > 0) return b;
+    if (int r = check_depth(ctx->c, depth)) return r;
+    if (!crs) return fail(HEGPU_E_INVALID, "null common random generator");
+    if (b) return b;
+    const size_t need = hegpu_workspace_bytes(ctx, op, depth, batch);
+    return need ? check_workspace(ws, ws_bytes, need) : 0;
+}
 
-static int check_refresh_party(const hegpu_rng* crs, const hegpu_rng* rng, const void* ct, const void* sk,
-                               const void* share)
+static int check_refresh_party(const hegpu_rng* rng, const void* ct, const void* sk, const void* share)
 {
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
-    if (crs == rng)
-        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
-    if (!ct || !sk || !share) return fail(HEGPU_E_INVALID, "null argument");
-    return 0;
+    return require(ct && sk && share, "null argument");
 }
 
 // out [batch] items of 2 Q N words, out_stride apart, must share no word with the input batch or with a share
-static int check_refresh_out(const hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t ct_words,
+static int check_refresh_out(const hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t in_words,
                              const uint64_t* const* shares, int k, uint64_t share_words, const uint64_t* out,
                              uint64_t so, int batch)
 {
     if (!ct || !out) return fail(HEGPU_E_INVALID, "null argument");
     if (const int rc = check_shares(shares, k, out)) return rc;
-    const uint64_t out_words = (uint64_t) 2 * ctx->c.Q_size * ctx->c.n;
-    if (batch > 1 && (so < out_words || cs < ct_words))
+    const Span res{out, so, level_words(ctx->c, 0)};
+    if (batch > 1 && (so < res.item || cs < in_words))
         return fail(HEGPU_E_INVALID, "the items of a batch overlap: stride below the size of an item");
-    if (spans_overlap(ct, cs, ct_words, out, so, out_words, batch))
+    if (overlaps_any(res, {{ct, cs, in_words}}, batch))
         return fail(HEGPU_E_INVALID, "the result overlaps the input ciphertexts");
     for (int i = 0; i < k; i++)
-        if (spans_overlap(shares[i], share_words, share_words, out, so, out_words, batch))
+        if (overlaps_any(res, {{shares[i], share_words, share_words}}, batch))
             return fail(HEGPU_E_INVALID, "the result overlaps a share");
     return 0;
 }
@@ -1857,10 +1872,10 @@ int hegpu_mpc_ckks_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* 
                                  size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (crs && crs == rng)
-        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
-    CHECK_REFRESH(ctx, SCHEME_CKKS, OP_MPC_REFRESH_SHARE, depth, batch, ws, ws_bytes);
-    if (const int rc = check_refresh_party(crs, rng, ct, sk, share)) return rc;
+    if (int r = require(!crs || crs != rng, "crs and rng must be different generators: the party's mask and errors are private"))
+        return r;
+    if (int r = check_refresh(ctx, SCHEME_CKKS, OP_MPC_REFRESH_SHARE, depth, batch, crs, ws, ws_bytes)) return leave(r);
+    if (const int rc = check_refresh_party(rng, ct, sk, share)) return rc;
     // 2^mask_bits >= Q_level / 2 can never be unmasked, whatever the message and the number of parties
     if (mask_bits < 1 || mask_bits > 126 || mask_bits + 1 >= level_modulus_bits(ctx->c, ctx->c.Q_size - depth))
         return fail(HEGPU_E_INVALID, "mask_bits must be in [1, 126] with 2^mask_bits below half the level's modulus");
@@ -1874,10 +1889,10 @@ int hegpu_mpc_ckks_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint6
                                  void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_REFRESH(ctx, SCHEME_CKKS, OP_MPC_REFRESH_MERGE, depth, batch, ws, ws_bytes);
-    const uint64_t l = (uint64_t) (ctx->c.Q_size - depth), Q = (uint64_t) ctx->c.Q_size;
-    if (const int rc = check_refresh_out(ctx, ct, cs, 2 * l * ctx->c.n, shares, k, (l + Q) * ctx->c.n, out, so, batch))
-        return rc;
+    if (int r = check_refresh(ctx, SCHEME_CKKS, OP_MPC_REFRESH_MERGE, depth, batch, crs, ws, ws_bytes)) return leave(r);
+    const int l = ctx->c.Q_size - depth;
+    const uint64_t share_words = ct_words(ctx->c, l + ctx->c.Q_size, 1);
+    if (const int rc = check_refresh_out(ctx, ct, cs, ct_words(ctx->c, l), shares, k, share_words, out, so, batch)) return rc;
     return hip_ret(op_mpc_ckks_refresh_merge(ctx->c, crs->r, (const u64*) ct, cs, (const u64* const*) shares, k, depth,
                                              (u64*) out, so, batch, (u64*) ws, (hipStream_t) stream),
                    "hegpu_mpc_ckks_refresh_merge");
@@ -1888,10 +1903,10 @@ int hegpu_mpc_bfv_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* r
                                 hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (crs && crs == rng)
-        return fail(HEGPU_E_INVALID, "crs and rng must be different generators: the party's mask and errors are private");
-    CHECK_REFRESH(ctx, SCHEME_BFV, OP_MPC_REFRESH_SHARE, 0, batch, ws, ws_bytes);
-    if (const int rc = check_refresh_party(crs, rng, ct, sk, share)) return rc;
+    if (int r = require(!crs || crs != rng, "crs and rng must be different generators: the party's mask and errors are private"))
+        return r;
+    if (int r = check_refresh(ctx, SCHEME_BFV, OP_MPC_REFRESH_SHARE, 0, batch, crs, ws, ws_bytes)) return leave(r);
+    if (const int rc = check_refresh_party(rng, ct, sk, share)) return rc;
     return hip_ret(op_mpc_bfv_refresh_share(ctx->c, crs->r, rng->r, (const u64*) ct, cs, (const u64*) sk, (u64*) share,
                                             batch, (hipStream_t) stream),
                    "hegpu_mpc_bfv_refresh_share");
@@ -1902,8 +1917,8 @@ int hegpu_mpc_bfv_refresh_merge(hegpu_context* ctx, hegpu_rng* crs, const uint64
                                 size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    CHECK_REFRESH(ctx, SCHEME_BFV, OP_MPC_REFRESH_MERGE, 0, batch, ws, ws_bytes);
-    const uint64_t words = (uint64_t) 2 * ctx->c.Q_size * ctx->c.n;
+    if (int r = check_refresh(ctx, SCHEME_BFV, OP_MPC_REFRESH_MERGE, 0, batch, crs, ws, ws_bytes)) return leave(r);
+    const uint64_t words = level_words(ctx->c, 0);
     if (const int rc = check_refresh_out(ctx, ct, cs, words, shares, k, words, out, so, batch)) return rc;
     return hip_ret(op_mpc_bfv_refresh_merge(ctx->c, crs->r, (const u64*) ct, cs, (const u64* const*) shares, k,
                                             (u64*) out, so, batch, (u64*) ws, (hipStream_t) stream),
@@ -1914,7 +1929,7 @@ int hegpu_bfv_encode(hegpu_context* ctx, const int64_t* message, int message_siz
                      hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     if (!ctx->c.plan_plain.count)
         return fail(HEGPU_E_LOGIC, "batching needs a prime plain modulus with 2N | t - 1");
     if (message_size < 0 || message_size > (int) ctx->c.n)
@@ -1929,11 +1944,10 @@ int hegpu_bfv_decode(hegpu_context* ctx, const uint64_t* plain, uint64_t* messag
                      hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     if (!ctx->c.plan_plain.count)
         return fail(HEGPU_E_LOGIC, "batching needs a prime plain modulus with 2N | t - 1");
-    if (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_BFV_DECODE, 0, 1))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_BFV_DECODE, 0, 1))) return r;
     return hip_ret(op_bfv_decode(ctx->c, (const u64*) plain, (u64*) message, (u64*) ws, (hipStream_t) stream),
                    "hegpu_bfv_decode");
 }
@@ -1942,7 +1956,7 @@ static int ckks_encode_any(hegpu_context* ctx, int mode, const double* message, 
                            double scale, uint64_t* plain, void* ws, size_t ws_bytes, hegpu_stream stream, const char* who)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (mode == 2) {
         if (message_size < 0 || message_size > (int) ctx->c.n)
             return fail(HEGPU_E_INVALID, "Vector size can not be higher than polynomial degree!"); // ckks/encoder.cuh:80
@@ -1951,8 +1965,8 @@ static int ckks_encode_any(hegpu_context* ctx, int mode, const double* message, 
     }
     if (mode != 3 && !message && message_size > 0) return fail(HEGPU_E_INVALID, "message is null");
     if (!(scale > 0.0)) return fail(HEGPU_E_INVALID, "Scale out of bounds");                       // :63
-    if (mode < 2 && (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_CKKS_ENCODE, 0, 1)))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (mode < 2)
+        if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_CKKS_ENCODE, 0, 1))) return r;
     return hip_ret(op_ckks_encode(ctx->c, mode, message, message_size, scalar, scale, (u64*) plain, (u64*) ws,
                                   (hipStream_t) stream), who);
 }
@@ -1983,11 +1997,10 @@ static int ckks_decode_any(hegpu_context* ctx, int mode, const uint64_t* plain, 
                            void* ws, size_t ws_bytes, hegpu_stream stream, const char* who)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (depth < 0 || depth >= ctx->c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_depth(ctx->c, depth)) return r;
     if (!(scale > 0.0)) return fail(HEGPU_E_INVALID, "scale must be positive");
-    if (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_CKKS_DECODE, depth, 1))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_CKKS_DECODE, depth, 1))) return r;
     return hip_ret(op_ckks_decode(ctx->c, mode, (const u64*) plain, depth, scale, message, (u64*) ws,
                                   (hipStream_t) stream), who);
 }
@@ -2011,7 +2024,7 @@ int hegpu_ckks_decode_coeff(hegpu_context* ctx, const uint64_t* plain, int depth
 int hegpu_bfv_noise_rns(hegpu_context* ctx, const uint64_t* ct, const uint64_t* sk, uint64_t* out, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     return hip_ret(op_bfv_noise_rns(ctx->c, (const u64*) ct, (const u64*) sk, (u64*) out, (hipStream_t) stream),
                    "hegpu_bfv_noise_rns");
 }
@@ -2031,10 +2044,10 @@ int hegpu_ckks_constant_op(hegpu_context* ctx, int op, const uint64_t* ct, doubl
                            int parts, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (op < 0 || op > 2) return fail(HEGPU_E_INVALID, "unknown constant operation");
-    if (limbs <= 0 || limbs > ctx->c.Q_size || parts < 2 || parts > 3) return fail(HEGPU_E_INVALID, "bad ciphertext shape");
-    if (!(value == value) || value >= 3.4e38 || value <= -3.4e38) return fail(HEGPU_E_INVALID, "constant out of range");
+    if (int r = check_shape(ctx->c, limbs, parts)) return r;
+    if (!constant_in_range(value)) return fail(HEGPU_E_INVALID, "constant out of range");
     return hip_ret(kg_ckks_constant((const u64*) ct, value, (u64*) out, ctx->c.plan_qp.mods, ctx->c.n_power, limbs, parts,
                                     op, (hipStream_t) stream),
                    "hegpu_ckks_constant_op");
@@ -2044,9 +2057,9 @@ int hegpu_ckks_gaussian_integer_op(hegpu_context* ctx, int op, const uint64_t* c
                                    int limbs, int parts, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (op < 0 || op > 1) return fail(HEGPU_E_INVALID, "unknown constant operation");
-    if (limbs <= 0 || limbs > ctx->c.Q_size || parts < 2 || parts > 3) return fail(HEGPU_E_INVALID, "bad ciphertext shape");
+    if (int r = check_shape(ctx->c, limbs, parts)) return r;
     for (double v : {re, im}) // any finite double, as the reference's NTL conversion (ckks/operator.cu:583-617)
         if (!std::isfinite(v)) return fail(HEGPU_E_INVALID, "constant is not a finite number");
     return guarded([&]() -> int {
@@ -2060,8 +2073,8 @@ int hegpu_ckks_mult_i(hegpu_context* ctx, const uint64_t* ct, uint64_t* out, int
                       hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_CKKS) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (limbs <= 0 || limbs > ctx->c.Q_size || parts < 2 || parts > 3) return fail(HEGPU_E_INVALID, "bad ciphertext shape");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = check_shape(ctx->c, limbs, parts)) return r;
     return guarded([&]() -> int {
         return hip_ret(kg_ckks_mult_i((const u64*) ct, (u64*) out, ctx->c.tab.psi_half, ctx->c.plan_qp.mods,
                                       ctx->c.n_power, limbs, parts, divide, (hipStream_t) stream),
@@ -2073,7 +2086,7 @@ int hegpu_bfv_plain_addsub(hegpu_context* ctx, const uint64_t* ct, const uint64_
                            hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     const Context& c = ctx->c;
     return guarded([&]() -> int {
         return hip_ret(kg_bfv_plain_addsub((const u64*) ct, (const u64*) plain, (u64*) out, c.plan_qp.mods,
@@ -2086,7 +2099,7 @@ int hegpu_bfv_plain_addsub(hegpu_context* ctx, const uint64_t* ct, const uint64_
 int hegpu_bfv_plain_to_ntt(hegpu_context* ctx, const uint64_t* plain, uint64_t* out, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     return guarded([&]() -> int {
         return hip_ret(op_bfv_plain_to_ntt(ctx->c, (const u64*) plain, (u64*) out, (hipStream_t) stream),
                        "hegpu_bfv_plain_to_ntt");
@@ -2109,9 +2122,8 @@ int hegpu_bfv_multiply_plain(hegpu_context* ctx, const uint64_t* ct, const uint6
                              size_t ws_bytes, hegpu_stream stream)
 {
     NEED_CTX(ctx);
-    if (ctx->c.scheme != SCHEME_BFV) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    if (!ws || ws_bytes < hegpu_workspace_bytes(ctx, OP_BFV_MULTIPLY_PLAIN, 0, 1))
-        return fail(HEGPU_E_INVALID, "workspace too small");
+    if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
+    if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, OP_BFV_MULTIPLY_PLAIN, 0, 1))) return r;
     return guarded([&]() -> int {
         return hip_ret(op_bfv_multiply_plain(ctx->c, (const u64*) ct, (const u64*) plain, (u64*) out, (u64*) ws,
                                              (hipStream_t) stream),
@@ -2121,20 +2133,24 @@ int hegpu_bfv_multiply_plain(hegpu_context* ctx, const uint64_t* ct, const uint6
 
 // ---- logic gates (HELogicOperator<CKKS / BFV>): the one-pass combine alone, and the whole gate.  Every argument check
 // comes before the context is uploaded: a refusal queues nothing and needs no device.
-static int gate_batch_check(int batch, const char* who)
+// what both gate entries look at first: the context, the gate (k: its coefficients), the batch (its sign under the entry's name)
+static int gate_head_check(const hegpu_context* ctx, int scheme, int gate, int k[3], int batch, const char* who)
 {
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (int r = check_scheme(ctx->c, scheme)) return r;
+    if (!logic_gate_coefficients(gate, k)) return fail(HEGPU_E_INVALID, std::string(who) + ": unknown gate");
     if (batch < 0) return fail(HEGPU_E_INVALID, std::string(who) + ": batch must not be negative");
-    if (2 * (long) batch > 65535) return fail(HEGPU_E_INVALID, std::string(who) + ": at most 32767 items per call");
-    return 0;
+    if (int r = check_grid(batch, 2, who)) return r;
+    return check_batch(batch);
 }
 
 // out against one operand: the operand itself (same address and stride, `limbs` limbs per part) or no common word
-static bool gate_operand_clear(const uint64_t* in, uint64_t in_stride, uint64_t in_words, bool may_alias, const uint64_t* out,
-                               uint64_t out_stride, uint64_t out_words, int batch)
+static int check_gate_operand(const Span& in, bool may_alias, const Span& out, int batch, const char* who)
 {
-    if (may_alias && in == out && in_stride == out_stride && in_words == out_words && (batch == 1 || out_stride >= out_words))
-        return true;
-    return !spans_overlap(in, in_stride, in_words, out, out_stride, out_words, batch);
+    if (may_alias && in.p == out.p && in.stride == out.stride && in.item == out.item && (batch == 1 || out.stride >= out.item))
+        return 0;
+    if (!overlaps_any(out, {in}, batch)) return 0;
+    return fail(HEGPU_E_INVALID, std::string(who) + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
 }
 
 static int gate_combine_entry(hegpu_context* ctx, int scheme, int gate, const uint64_t* a, uint64_t a_stride, int a_limbs,
@@ -2142,14 +2158,10 @@ static int gate_combine_entry(hegpu_context* ctx, int scheme, int gate, const ui
                               uint64_t p_stride, int p_limbs, double scale_one, uint64_t* out, uint64_t out_stride,
                               int limbs, int batch, hegpu_stream stream, const char* who)
 {
-    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    int k[3];
+    if (int r = gate_head_check(ctx, scheme, gate, k, batch, who)) return leave(r);
     const Context& c = ctx->c;
     const std::string w = who;
-    if (c.scheme != scheme) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    int k[3];
-    if (!logic_gate_coefficients(gate, k)) return fail(HEGPU_E_INVALID, w + ": unknown gate");
-    if (int r = gate_batch_check(batch, who)) return r;
-    if (batch == 0) return 0;
     const bool unary = gate == LOGIC_NOT;
     if (unary ? (b_kind != GATE_B_NONE || b || p) : (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN))
         return fail(HEGPU_E_INVALID, w + ": NOT takes no second operand and no product, every other gate takes both");
@@ -2158,17 +2170,15 @@ static int gate_combine_entry(hegpu_context* ctx, int scheme, int gate, const ui
     if (a_limbs < limbs || a_limbs > c.Q_size || (!unary && (p_limbs < limbs || p_limbs > c.Q_size)) ||
         (!unary && !(scheme == SCHEME_BFV && b_kind == GATE_B_PLAIN) && (b_limbs < limbs || b_limbs > c.Q_size)))
         return fail(HEGPU_E_INVALID, w + ": an operand has fewer limbs than the result");
-    if (scheme == SCHEME_CKKS && (!(scale_one > 0) || scale_one >= 3.4e38))
+    if (scheme == SCHEME_CKKS && !(scale_one > 0 && constant_in_range(scale_one)))
         return fail(HEGPU_E_INVALID, w + ": the scale of the constant one is positive and below 3.4e38");
-    const uint64_t n = c.n, out_words = (uint64_t) 2 * limbs * n;
-    if (!gate_operand_clear(a, a_stride, (uint64_t) 2 * a_limbs * n, true, out, out_stride, out_words, batch))
-        return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+    const Span res{out, out_stride, ct_words(c, limbs)};
+    if (int r = check_gate_operand({a, a_stride, ct_words(c, a_limbs)}, true, res, batch, who)) return r;
     if (!unary) {
         const bool cipher = b_kind == GATE_B_CIPHER;
-        const uint64_t b_words = cipher ? (uint64_t) 2 * b_limbs * n : scheme == SCHEME_BFV ? n : (uint64_t) b_limbs * n;
-        if (!gate_operand_clear(b, b_stride, b_words, cipher, out, out_stride, out_words, batch))
-            return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
-        if (spans_overlap(p, p_stride, (uint64_t) 2 * p_limbs * n, out, out_stride, out_words, batch))
+        const uint64_t b_words = cipher ? ct_words(c, b_limbs) : scheme == SCHEME_BFV ? c.n : ct_words(c, b_limbs, 1);
+        if (int r = check_gate_operand({b, b_stride, b_words}, cipher, res, batch, who)) return r;
+        if (overlaps_any(res, {{p, p_stride, ct_words(c, p_limbs)}}, batch))
             return fail(HEGPU_E_INVALID, w + ": out must not overlap the product");
     }
     NEED_CTX(ctx);
@@ -2203,16 +2213,12 @@ static int logic_gate_entry(hegpu_context* ctx, int scheme, int gate, const uint
                             uint64_t* out, uint64_t out_stride, int depth, int batch, void* ws, size_t ws_bytes,
                             hegpu_stream stream, const char* who)
 {
-    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    int k[3];
+    if (int r = gate_head_check(ctx, scheme, gate, k, batch, who)) return leave(r);
     const Context& c = ctx->c;
     const std::string w = who;
     const bool bfv = scheme == SCHEME_BFV;
-    if (c.scheme != scheme) return fail(HEGPU_E_INVALID, "context scheme mismatch");
-    int k[3];
-    if (!logic_gate_coefficients(gate, k)) return fail(HEGPU_E_INVALID, w + ": unknown gate");
-    if (int r = gate_batch_check(batch, who)) return r;
-    if (batch == 0) return 0;
-    if (depth < 0 || depth >= c.Q_size) return fail(HEGPU_E_INVALID, "invalid depth");
+    if (int r = check_depth(c, depth)) return r;
     const bool unary = gate == LOGIC_NOT;
     if (unary ? (b_kind != GATE_B_NONE || b) : (b_kind != GATE_B_CIPHER && b_kind != GATE_B_PLAIN))
         return fail(HEGPU_E_INVALID, w + ": NOT takes no second operand, every other gate a ciphertext or a plaintext");
@@ -2220,25 +2226,18 @@ static int logic_gate_entry(hegpu_context* ctx, int scheme, int gate, const uint
         return fail(HEGPU_E_INVALID, w + ": null argument");
     const int l = c.Q_size - depth;
     if (!bfv && !unary && l < 2) return fail(HEGPU_E_INVALID, w + ": no modulus left to rescale the product by");
-    if (!bfv && (!(scale_one > 0) || scale_one >= 3.4e38))
+    if (!bfv && !(scale_one > 0 && constant_in_range(scale_one)))
         return fail(HEGPU_E_INVALID, w + ": the scale of the constant one is positive and below 3.4e38");
     const int op = bfv ? OP_BFV_LOGIC_GATE : OP_CKKS_LOGIC_GATE;
-    if (!unary && (!ws || ws_bytes < hegpu_workspace_bytes(ctx, op, depth, batch)))
-        return fail(HEGPU_E_INVALID, "workspace too small");
-    const uint64_t n = c.n, in_words = (uint64_t) 2 * l * n;
-    const uint64_t out_words = (uint64_t) 2 * (bfv || unary ? l : l - 1) * n;
-    if (!gate_operand_clear(a, a_stride, in_words, true, out, out_stride, out_words, batch))
-        return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
+    if (!unary)
+        if (int r = check_workspace(ws, ws_bytes, hegpu_workspace_bytes(ctx, op, depth, batch))) return r;
+    const Span in_a{a, a_stride, ct_words(c, l)}, res{out, out_stride, ct_words(c, bfv || unary ? l : l - 1)};
+    if (int r = check_gate_operand(in_a, true, res, batch, who)) return r;
     if (!unary) {
         const bool cipher = b_kind == GATE_B_CIPHER;
-        const uint64_t b_words = cipher ? in_words : bfv ? n : (uint64_t) l * n;
-        if (!gate_operand_clear(b, b_stride, b_words, cipher, out, out_stride, out_words, batch))
-            return fail(HEGPU_E_INVALID, w + ": out is an operand itself (equal strides and limb counts) or does not overlap it");
-        const uint64_t* wsp = (const uint64_t*) ws;
-        const uint64_t ws_words = ws_bytes / sizeof(uint64_t);
-        if (spans_overlap(wsp, 0, ws_words, out, out_stride, out_words, batch) ||
-            spans_overlap(wsp, 0, ws_words, a, a_stride, in_words, batch) ||
-            spans_overlap(wsp, 0, ws_words, b, b_stride, b_words, batch))
+        const Span in_b{b, b_stride, cipher ? in_a.item : bfv ? c.n : ct_words(c, l, 1)};
+        if (int r = check_gate_operand(in_b, cipher, res, batch, who)) return r;
+        if (overlaps_any({(const uint64_t*) ws, 0, ws_bytes / sizeof(uint64_t)}, {res, in_a, in_b}, batch))
             return fail(HEGPU_E_INVALID, w + ": the workspace must overlap neither out nor an operand");
     }
     NEED_CTX(ctx);
@@ -2587,7 +2586,7 @@ int hegpu_tfhe_gate(hegpu_tfhe_context* ctx, int gate, const int32_t* in1_a, con
         return hegpu_tfhe_gate_precompute(ctx, gate, out_a, out_b, in1_a, in1_b, nullptr, nullptr, shape, stream);
     if ((r = tfhe_take_bad_key(ctx))) return r; // an earlier call's bad key, before anything of this gate is queued
     const size_t need = ((size_t) p.n + (size_t) p.k * p.N + 2) * shape * sizeof(int32_t);
-    if (!ws || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+    if ((r = check_workspace(ws, ws_bytes, need))) return r;
     int32_t* t_a = (int32_t*) ws;
     int32_t* t_b = t_a + (size_t) p.n * shape;
     int32_t* e_a = t_b + shape;
@@ -2619,7 +2618,7 @@ int hegpu_tfhe_generate_bootstrapping_key(hegpu_tfhe_context* ctx, hegpu_rng* rn
     TFHE_NEED(ctx);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     const TfheDev& p = ctx->p;
-    if (!ws || ws_bytes < (size_t) p.N * sizeof(u64)) return fail(HEGPU_E_INVALID, "workspace too small");
+    if ((r = check_workspace(ws, ws_bytes, (size_t) p.N * sizeof(u64)))) return r;
     const u64 s0 = rng->r.stream;
     rng->r.stream += 4;
     hipError_t e = tfhe_gen_bootkey(p, (u64*) boot_key, lwe_key, tlwe_key, (u64*) ws, ctx->bk_stdev / TFHE_IH,
@@ -2661,7 +2660,7 @@ int hegpu_tfhe_mux(hegpu_tfhe_context* ctx, const int32_t* in1_a, const int32_t*
     const TfheDev& p = ctx->p;
     const size_t kN = (size_t) p.k * p.N;
     const size_t need = ((size_t) p.n + 1 + 2 * (kN + 1)) * shape * sizeof(int32_t);
-    if (!ws || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+    if ((r = check_workspace(ws, ws_bytes, need))) return r;
     int32_t* t_a = (int32_t*) ws;
     int32_t* t_b = t_a + (size_t) p.n * shape;
     int32_t* e1_a = t_b + shape;

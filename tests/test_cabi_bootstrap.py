@@ -53,7 +53,7 @@ def test_refusals_need_no_device(setup):
     out = torch.full((room,), SENT, dtype=torch.int64)
     ws = torch.full((c.bootstrap_workspace_bytes(plan, cts, stc, True, 1) // 8,), SENT, dtype=torch.int64)
 
-    def refused(**kw):
+    def refused(text, **kw):
         args = dict(ct=ct, out=out, plan=plan, cts=cts, stc=stc, conj=key, relin=key, batch=1, ws=ws, d2s=key, s2d=key)
         args.update(kw)
         with pytest.raises(hg.HEError) as e:
@@ -61,27 +61,33 @@ def test_refusals_need_no_device(setup):
                              args["relin"], args["batch"], args["ws"], swk_dense_to_sparse=args["d2s"],
                              swk_sparse_to_dense=args["s2d"], stream=0)
         assert e.value.code == hg.E_INVALID, e.value
+        assert str(e.value) == f"[{hg.E_INVALID}] {text}"
         for t in (ct, out, ws):
             assert bool((t == SENT).all())
 
-    refused(d2s=None)
-    refused(s2d=None)
-    refused(batch=0)
-    refused(batch=-1)
-    refused(ws=ws[:ws.numel() - 1])
-    refused(ws=None)
-    refused(ct=None)
-    refused(out=None)
-    refused(conj=None)
-    refused(relin=None)
-    refused(cts=cts[:2])
-    refused(stc=stc + stc[:1])
-    refused(plan=hg.bootstrap_plan(primes[:Q] + [primes[Q - 1]], DELTA, Q, K=12))
-    refused(plan=hg.BootstrapPlan(plan.c, hg.eval_mod_plan(12, 30, 3, plan.eval_level, plan.eval_in_scale, 2.0 ** 49, primes[:Q])))
-    refused(plan=hg.BootstrapPlan(plan.c, hg.eval_mod_plan(12, 30, 2, plan.eval_level, plan.eval_in_scale, plan.eval_target_scale, primes[:Q])))
+    refused("bootstrap: both switch keys (dense to sparse, sparse to dense) or neither", d2s=None)
+    refused("bootstrap: both switch keys (dense to sparse, sparse to dense) or neither", s2d=None)
+    refused("bootstrap: batch must be at least 1", batch=0)
+    refused("bootstrap: batch must be at least 1", batch=-1)
+    refused("bootstrap: at most 16383 items per call", batch=16384)
+    refused("workspace too small", ws=ws[:ws.numel() - 1])
+    refused("bootstrap: null argument", ws=None)
+    refused("bootstrap: null argument", ct=None)
+    refused("bootstrap: null argument", out=None)
+    refused("bootstrap: null argument", conj=None)
+    refused("bootstrap: null argument", relin=None)
+    refused("bootstrap: as many factors as the plan has pieces", cts=cts[:2])
+    refused("bootstrap: as many factors as the plan has pieces", stc=stc + stc[:1])
+    refused("bootstrap: the raise goes to a level the context has", plan=hg.bootstrap_plan(primes[:Q] + [primes[Q - 1]], DELTA, Q, K=12))
+    not_the_plan = "bootstrap: the EvalMod plan is not the one of the bootstrap plan"
+    refused(not_the_plan, plan=hg.BootstrapPlan(plan.c, hg.eval_mod_plan(12, 30, 3, plan.eval_level, plan.eval_in_scale, 2.0 ** 49, primes[:Q])))
+    refused(not_the_plan, plan=hg.BootstrapPlan(plan.c, hg.eval_mod_plan(12, 30, 2, plan.eval_level, plan.eval_in_scale, plan.eval_target_scale, primes[:Q])))
+    # an earlier refusal wins: the factor count before the caller's pointers, those before the switch keys and the stride
+    refused("bootstrap: as many factors as the plan has pieces", cts=cts[:2], ct=None, d2s=None)
+    refused("bootstrap: null argument", ct=None, d2s=None, ws=ws[:1])
     both = torch.full((2 * N + room,), SENT, dtype=torch.int64)
-    refused(ct=both[:2 * N], out=both[2 * N - 1:2 * N - 1 + room])
-    refused(out=ws[:room])
+    refused("bootstrap: out must not overlap ct", ct=both[:2 * N], out=both[2 * N - 1:2 * N - 1 + room])
+    refused("bootstrap: the workspace must overlap neither out nor ct", out=ws[:room])
     bfv = hg.Context.from_bit_sizes(hg.BFV, N, [40, 40], [40], plain_modulus=65537, sec=hg.SEC_NONE)
     with pytest.raises(hg.HEError) as e:
         bfv.ckks_bootstrap(ct, 2 * N, out, room, plan, cts, stc, key, key, 1, ws, stream=0)

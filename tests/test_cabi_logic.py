@@ -53,9 +53,9 @@ def test_workspace_rows(hg):
     assert c.workspace_bytes(24, 0, 1) == 0
 
 
-def _refused(hg, c, rc):
+def _refused(hg, c, rc, text):
     assert rc == hg.E_INVALID, rc
-    assert c._lib.hegpu_last_error(), "a refusal carries a message"
+    assert c._lib.hegpu_last_error().decode() == text
 
 
 def test_refusals_need_no_device(hg):
@@ -78,33 +78,33 @@ def test_refusals_need_no_device(hg):
 
     # the baseline is refused by nothing but the missing device
     assert combine() == hg.E_NODEVICE
-    _refused(hg, c, combine(gate=7))
-    _refused(hg, c, combine(gate=-1))
-    _refused(hg, c, combine(a_limbs=1))
-    _refused(hg, c, combine(b_limbs=1))
-    _refused(hg, c, combine(p_limbs=1))
-    _refused(hg, c, combine(limbs=0))
-    _refused(hg, c, combine(a_limbs=4))
-    _refused(hg, c, combine(batch=32768))
-    _refused(hg, c, combine(batch=-1))
-    _refused(hg, c, combine(out=A))                          # a has 3 limbs, out 2: no in-place form
-    _refused(hg, c, combine(out=B + 8))
-    _refused(hg, c, combine(out=P))
-    _refused(hg, c, combine(scale_one=0.0))
-    _refused(hg, c, combine(scale_one=float("nan")))
-    _refused(hg, c, combine(gate=hg.LOGIC_NOT))              # NOT with a second operand
-    _refused(hg, c, combine(b_kind=hg.GATE_B_NONE))
-    _refused(hg, c, combine(p=None))
-    _refused(hg, c, combine(ctx=bfv))                        # wrong scheme
+    _refused(hg, c, combine(gate=7), "hegpu_ckks_gate_combine: unknown gate")
+    _refused(hg, c, combine(gate=-1), "hegpu_ckks_gate_combine: unknown gate")
+    _refused(hg, c, combine(a_limbs=1), "hegpu_ckks_gate_combine: an operand has fewer limbs than the result")
+    _refused(hg, c, combine(b_limbs=1), "hegpu_ckks_gate_combine: an operand has fewer limbs than the result")
+    _refused(hg, c, combine(p_limbs=1), "hegpu_ckks_gate_combine: an operand has fewer limbs than the result")
+    _refused(hg, c, combine(limbs=0), "hegpu_ckks_gate_combine: bad limb count")
+    _refused(hg, c, combine(a_limbs=4), "hegpu_ckks_gate_combine: an operand has fewer limbs than the result")
+    _refused(hg, c, combine(batch=32768), "hegpu_ckks_gate_combine: at most 32767 items per call")
+    _refused(hg, c, combine(batch=-1), "hegpu_ckks_gate_combine: batch must not be negative")
+    _refused(hg, c, combine(out=A), "hegpu_ckks_gate_combine: out is an operand itself (equal strides and limb counts) or does not overlap it")                          # a has 3 limbs, out 2: no in-place form
+    _refused(hg, c, combine(out=B + 8), "hegpu_ckks_gate_combine: out is an operand itself (equal strides and limb counts) or does not overlap it")
+    _refused(hg, c, combine(out=P), "hegpu_ckks_gate_combine: out must not overlap the product")
+    _refused(hg, c, combine(scale_one=0.0), "hegpu_ckks_gate_combine: the scale of the constant one is positive and below 3.4e38")
+    _refused(hg, c, combine(scale_one=float("nan")), "hegpu_ckks_gate_combine: the scale of the constant one is positive and below 3.4e38")
+    _refused(hg, c, combine(gate=hg.LOGIC_NOT), "hegpu_ckks_gate_combine: NOT takes no second operand and no product, every other gate takes both")              # NOT with a second operand
+    _refused(hg, c, combine(b_kind=hg.GATE_B_NONE), "hegpu_ckks_gate_combine: NOT takes no second operand and no product, every other gate takes both")
+    _refused(hg, c, combine(p=None), "hegpu_ckks_gate_combine: null argument")
+    _refused(hg, c, combine(ctx=bfv), "context scheme mismatch")                        # wrong scheme
     assert combine(batch=0) == 0
     # a CKKS NOT in place is allowed: refused by nothing but the missing device
     assert combine(gate=hg.LOGIC_NOT, b=None, b_kind=hg.GATE_B_NONE, p=None, out=A, out_stride=w3, limbs=3) == hg.E_NODEVICE
 
     wq = 2 * 3 * N
     assert lib.hegpu_bfv_gate_combine(bfv._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_CIPHER, wq, P, wq, A, wq, 2, None) == hg.E_NODEVICE
-    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(bfv._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_CIPHER, wq, P, wq, A + 8, wq, 2, None))
-    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(bfv._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_PLAIN, N, P, wq, B, wq, 2, None))
-    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(c._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_CIPHER, wq, P, wq, OUT, wq, 2, None))
+    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(bfv._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_CIPHER, wq, P, wq, A + 8, wq, 2, None), "hegpu_bfv_gate_combine: out is an operand itself (equal strides and limb counts) or does not overlap it")
+    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(bfv._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_PLAIN, N, P, wq, B, wq, 2, None), "hegpu_bfv_gate_combine: out is an operand itself (equal strides and limb counts) or does not overlap it")
+    _refused(hg, bfv, lib.hegpu_bfv_gate_combine(c._h, hg.LOGIC_OR, A, wq, B, hg.GATE_B_CIPHER, wq, P, wq, OUT, wq, 2, None), "context scheme mismatch")
 
     need = c.workspace_bytes(hg.OP_CKKS_LOGIC_GATE, 0, 2)
 
@@ -113,18 +113,18 @@ def test_refusals_need_no_device(hg):
         return lib.hegpu_ckks_logic_gate(ctx._h, gate, a, w3, b, kind, w3, key, scale, out, w2, depth, batch, ws, ws_bytes, None)
 
     assert gate() == hg.E_NODEVICE
-    _refused(hg, c, gate(gate=9))
-    _refused(hg, c, gate(ws_bytes=need - 8))
-    _refused(hg, c, gate(ws=None))
-    _refused(hg, c, gate(key=None))
-    _refused(hg, c, gate(out=A))
-    _refused(hg, c, gate(out=WS))
-    _refused(hg, c, gate(depth=2))                           # a binary gate on the last level
-    _refused(hg, c, gate(depth=3))
-    _refused(hg, c, gate(batch=40000))
-    _refused(hg, c, gate(ctx=bfv))
-    _refused(hg, c, gate(scale=0.0))
+    _refused(hg, c, gate(gate=9), "hegpu_ckks_logic_gate: unknown gate")
+    _refused(hg, c, gate(ws_bytes=need - 8), "workspace too small")
+    _refused(hg, c, gate(ws=None), "workspace too small")
+    _refused(hg, c, gate(key=None), "hegpu_ckks_logic_gate: null argument")
+    _refused(hg, c, gate(out=A), "hegpu_ckks_logic_gate: out is an operand itself (equal strides and limb counts) or does not overlap it")
+    _refused(hg, c, gate(out=WS), "hegpu_ckks_logic_gate: the workspace must overlap neither out nor an operand")
+    _refused(hg, c, gate(depth=2), "hegpu_ckks_logic_gate: no modulus left to rescale the product by")                           # a binary gate on the last level
+    _refused(hg, c, gate(depth=3), "invalid depth")
+    _refused(hg, c, gate(batch=40000), "hegpu_ckks_logic_gate: at most 32767 items per call")
+    _refused(hg, c, gate(ctx=bfv), "context scheme mismatch")
+    _refused(hg, c, gate(scale=0.0), "hegpu_ckks_logic_gate: the scale of the constant one is positive and below 3.4e38")
     needb = bfv.workspace_bytes(hg.OP_BFV_LOGIC_GATE, 0, 1)
     assert lib.hegpu_bfv_logic_gate(bfv._h, hg.LOGIC_AND, A, wq, B, hg.GATE_B_CIPHER, wq, KEY, A, wq, 1, WS, needb, None) == hg.E_NODEVICE
-    _refused(hg, bfv, lib.hegpu_bfv_logic_gate(bfv._h, hg.LOGIC_AND, A, wq, B, hg.GATE_B_CIPHER, wq, KEY, A, wq, 1, WS, needb - 8, None))
-    _refused(hg, bfv, lib.hegpu_bfv_logic_gate(c._h, hg.LOGIC_AND, A, wq, B, hg.GATE_B_CIPHER, wq, KEY, OUT, wq, 1, WS, needb, None))
+    _refused(hg, bfv, lib.hegpu_bfv_logic_gate(bfv._h, hg.LOGIC_AND, A, wq, B, hg.GATE_B_CIPHER, wq, KEY, A, wq, 1, WS, needb - 8, None), "workspace too small")
+    _refused(hg, bfv, lib.hegpu_bfv_logic_gate(c._h, hg.LOGIC_AND, A, wq, B, hg.GATE_B_CIPHER, wq, KEY, OUT, wq, 1, WS, needb, None), "context scheme mismatch")
