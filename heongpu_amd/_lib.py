@@ -59,6 +59,26 @@ class BootstrapPlan(ctypes.Structure):
                 ("stc_scale", ctypes.c_double * 5), ("stc_label", ctypes.c_double * 5), ("out_scale", ctypes.c_double)]
 
 
+class SlimBootstrapConfig(ctypes.Structure):
+    """hegpu_slim_bootstrap_config: the inputs of hegpu_slim_bootstrap_plan_fill"""
+    _fields_ = [("scale", ctypes.c_double), ("ratio", ctypes.c_double), ("phase", ctypes.c_double),
+                ("amplitude", ctypes.c_double), ("offset", ctypes.c_double), ("K", ctypes.c_int32), ("degree", ctypes.c_int32),
+                ("double_angle", ctypes.c_int32), ("cts_level", ctypes.c_int32), ("cts_pieces", ctypes.c_int32),
+                ("stc_pieces", ctypes.c_int32), ("arithmetic", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class SlimBootstrapPlan(ctypes.Structure):
+    """hegpu_slim_bootstrap_plan: every level and scale label of the slim, bit and gate refreshes"""
+    _fields_ = [("in_level", ctypes.c_int32), ("stc_pieces", ctypes.c_int32), ("cts_level", ctypes.c_int32),
+                ("cts_pieces", ctypes.c_int32), ("eval_level", ctypes.c_int32), ("out_level", ctypes.c_int32),
+                ("K", ctypes.c_int32), ("degree", ctypes.c_int32), ("double_angle", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("stc_scale", ctypes.c_double * 5), ("stc_label", ctypes.c_double * 5),
+                ("raise_scale", ctypes.c_double), ("cts_scale", ctypes.c_double * 5), ("cts_label", ctypes.c_double * 5),
+                ("ratio", ctypes.c_double), ("phase", ctypes.c_double), ("amplitude", ctypes.c_double),
+                ("offset", ctypes.c_double), ("eval_in_scale", ctypes.c_double), ("eval_target_scale", ctypes.c_double),
+                ("eval_out_scale", ctypes.c_double), ("out_scale", ctypes.c_double)]
+
+
 # (name, restype, argtypes) -- must list EVERY symbol of include/hegpu.h
 SIGNATURES = [
     ("hegpu_last_error", ctypes.c_char_p, []),
@@ -170,6 +190,21 @@ SIGNATURES = [
      [voidp, u64p, u64, u64p, u64, ctypes.POINTER(BootstrapPlan), ctypes.POINTER(PolyStep), c_int,
       ctypes.POINTER(LinearFactor), c_int, ctypes.POINTER(LinearFactor), c_int, u64p, u64p, u64p, u64p, c_int, voidp,
       c_size_t, voidp]),
+    ("hegpu_eval_trig_plan_size", c_int,
+     [c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.POINTER(u64), c_int, ctypes.POINTER(c_int)]),
+    ("hegpu_eval_trig_plan_fill", c_int,
+     [c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double,
+      ctypes.POINTER(u64), c_int, ctypes.POINTER(PolyStep), c_int]),
+    ("hegpu_slim_bootstrap_plan_fill", c_int,
+     [ctypes.POINTER(SlimBootstrapConfig), ctypes.POINTER(u64), c_int, ctypes.POINTER(SlimBootstrapPlan)]),
+    ("hegpu_ckks_conj_real", c_int, [voidp, u64p, u64, u64p, u64, u64p, u64, c_int, c_int, c_int, voidp]),
+    ("hegpu_ckks_slim_bootstrap_workspace_bytes", c_size_t,
+     [voidp, ctypes.POINTER(SlimBootstrapPlan), ctypes.POINTER(PolyStep), c_int, ctypes.POINTER(LinearFactor), c_int,
+      ctypes.POINTER(LinearFactor), c_int, c_int]),
+    ("hegpu_ckks_slim_bootstrap", c_int,
+     [voidp, u64p, u64, u64p, u64, u64p, u64, ctypes.POINTER(SlimBootstrapPlan), ctypes.POINTER(PolyStep), c_int,
+      ctypes.POINTER(LinearFactor), c_int, ctypes.POINTER(LinearFactor), c_int, u64p, u64p, c_int, voidp, c_size_t, voidp]),
     ("hegpu_ckks_gate_combine", c_int,
      [voidp, c_int, u64p, u64, c_int, u64p, c_int, u64, c_int, u64p, u64, c_int, ctypes.c_double, u64p, u64, c_int, c_int,
       voidp]),

@@ -530,10 +530,38 @@ class Context(_Handle):
                             [e for _, e in giant]))
             return out
 
+        # a SlimBootstrapPlan's SlotToCoeff starts at the input's own level: there is no merge below it
+        stc_first = plan.in_level if isinstance(plan, SlimBootstrapPlan) else plan.stc_level - 1
         cts = side(True, plan.cts_pieces, plan.cts_level, plan.cts_scale)
-        stc = side(False, plan.stc_pieces, plan.stc_level - 1, plan.stc_scale)
+        stc = side(False, plan.stc_pieces, stc_first, plan.stc_scale)
         elts.add(2 * n - 1)
         return cts, stc, sorted(elts)
+
+    def slim_bootstrap_factors(self, plan, galois_key, encode=None):
+        """bootstrap_factors for a SlimBootstrapPlan (slim_bootstrap_plan): the same factorisation and encoder, SlotToCoeff
+        factor g at level plan.in_level - g and scale plan.stc_scale[g].  Returns (cts, stc, galois_elts)."""
+        return self.bootstrap_factors(plan, galois_key, encode)
+
+    def slim_bootstrap_workspace_bytes(self, plan, cts, stc, batch):
+        """hegpu_ckks_slim_bootstrap_workspace_bytes; plan: a SlimBootstrapPlan, cts / stc as for linear_factors"""
+        a, _ka = self.linear_factors(cts)
+        b, _kb = self.linear_factors(stc)
+        return int(self._lib.hegpu_ckks_slim_bootstrap_workspace_bytes(self._h, ctypes.byref(plan.c), plan.trig.steps,
+                                                                       len(plan.trig.steps), a, len(cts), b, len(stc), batch))
+
+    def ckks_slim_bootstrap(self, ct, cs, out, so, plan, cts, stc, conj_key, relin_key, batch, ws, ct2=None, cs2=0,
+                            stream=None):
+        """hegpu_ckks_slim_bootstrap: ct (and ct2 for a gate) [2][plan.in_level + 1][N] per item -> out
+        [2][plan.out_level + 1][N] at plan.out_scale (room for plan.trig.out_limbs limbs per part on the way)"""
+        a, _ka = self.linear_factors(cts)
+        b, _kb = self.linear_factors(stc)
+        self._call("ckks_slim_bootstrap", _ptr(ct), cs, _ptr(ct2), cs2, _ptr(out), so, ctypes.byref(plan.c),
+                   plan.trig.steps, len(plan.trig.steps), a, len(cts), b, len(stc), _ptr(conj_key), _ptr(relin_key), batch,
+                   _ptr(ws), _ws_bytes(ws) if ws is not None else 0, stream=stream)
+
+    def ckks_conj_real(self, x, xs, xc, xcs, out, so, depth, out_depth, batch=1, stream=None):
+        """hegpu_ckks_conj_real: out = x + xc on the Q - out_depth kept limbs (conj_split's out0 alone)"""
+        self._call("ckks_conj_real", _ptr(x), xs, _ptr(xc), xcs, _ptr(out), so, depth, out_depth, batch, stream=stream)
 
     def bfv_multiply(self, ct1, s1, ct2, s2, out, so, batch, ws, stream=None):
         self._call("bfv_multiply", _ptr(ct1), s1, _ptr(ct2), s2, _ptr(out), so, batch, _ptr(ws), _ws_bytes(ws),
@@ -1127,6 +1155,69 @@ def bootstrap_plan(primes, scale, cts_level, cts_pieces=3, stc_pieces=3, message
     _check(lib.hegpu_bootstrap_plan_fill(ctypes.byref(cfg), arr, len(pr), ctypes.byref(c)))
     return BootstrapPlan(c, eval_mod_plan(c.K, c.sine_degree, c.double_angle, c.eval_level, c.eval_in_scale,
                                           c.eval_target_scale, pr))
+
+
+def eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes):
+    """offset + amplitude cos(2 pi (K u - phase)) as a plan for Context.ckks_poly_eval (host only; hegpu_eval_trig_plan_size /
+    _fill): the interpolant of amplitude^(1 / 2^r) cos(2 pi (K u - phase) / 2^r), r double-angle steps, the last one's tail
+    constant amplitude - offset.  eval_mod_plan is (1/4, 1 / 2 pi, 0).  Returns a PolyEvalPlan like poly_eval_plan."""
+    lib = _lib.load()
+    pr = [int(p) for p in primes]
+    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    args = (int(K), int(degree), int(double_angle), float(phase), float(amplitude), float(offset), int(level), float(scale),
+            float(target_scale), arr, len(pr))
+    count = ctypes.c_int(0)
+    _check(lib.hegpu_eval_trig_plan_size(*args, ctypes.byref(count)))
+    steps = (_lib.PolyStep * count.value)()
+    _check(lib.hegpu_eval_trig_plan_fill(*args, steps, count.value))
+    last = steps[count.value - 1]
+    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+
+
+# (ratio, phase, amplitude, offset) of the slim family: alpha + A cos(2 pi (a / ratio - phi)); ratio None: the caller's
+SLIM_FUNCTIONS = {
+    "slim": (None, 1 / 4, 1 / (2 * np.pi), 0.0),
+    "bit": (2.0, 1 / 2, 1 / 2, 1 / 2),
+    "and": (3.0, 2 / 3, 2 / 3, 1 / 3),
+    "or": (3.0, 1 / 2, 2 / 3, 2 / 3),
+    "xor": (3.0, 1 / 3, 2 / 3, 1 / 3),
+    "nand": (3.0, 1 / 6, 2 / 3, 2 / 3),
+    "nor": (3.0, 0.0, 2 / 3, 1 / 3),
+    "xnor": (3.0, 5 / 6, 2 / 3, 2 / 3),
+}
+
+
+class SlimBootstrapPlan:
+    """The plan of a slim, bit or gate refresh (slim_bootstrap_plan): c is the hegpu_slim_bootstrap_plan, trig the
+    PolyEvalPlan it names; the other attributes are c's fields, arrays cut to their piece counts."""
+
+    def __init__(self, c, trig):
+        self.c, self.trig = c, trig
+        for name, _t in c._fields_:
+            setattr(self, name, getattr(c, name))
+        self.cts_scale, self.cts_label = list(c.cts_scale)[:c.cts_pieces], list(c.cts_label)[:c.cts_pieces]
+        self.stc_scale, self.stc_label = list(c.stc_scale)[:c.stc_pieces], list(c.stc_label)[:c.stc_pieces]
+
+
+def slim_bootstrap_plan(primes, scale, cts_level, function="slim", cts_pieces=3, stc_pieces=3, ratio=256.0, K=12, degree=30,
+                        double_angle=3):
+    """Every level and scale label of a slim, bit or gate refresh (host only; hegpu_slim_bootstrap_plan_fill) and the trig
+    plan that goes with it.  primes: q_0 ...; scale: of the ciphertext to refresh, which sits at level stc_pieces;
+    cts_level: the level the modulus raise goes to; function: a key of SLIM_FUNCTIONS or a (ratio, phase, amplitude, offset)
+    tuple; ratio: for "slim" only.  Returns a SlimBootstrapPlan: in_level, stc_scale / cts_scale (what each factor's diagonals
+    are encoded at), raise_scale, eval_level, out_level, out_scale, trig."""
+    lib = _lib.load()
+    pr = [int(p) for p in primes]
+    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    arithmetic = function == "slim"
+    rho, phase, amplitude, offset = SLIM_FUNCTIONS[function] if isinstance(function, str) else function
+    cfg = _lib.SlimBootstrapConfig(float(scale), float(ratio if rho is None else rho), float(phase), float(amplitude),
+                                   float(offset), int(K), int(degree), int(double_angle), int(cts_level), int(cts_pieces),
+                                   int(stc_pieces), int(arithmetic), 0)
+    c = _lib.SlimBootstrapPlan()
+    _check(lib.hegpu_slim_bootstrap_plan_fill(ctypes.byref(cfg), arr, len(pr), ctypes.byref(c)))
+    return SlimBootstrapPlan(c, eval_trig_plan(c.K, c.degree, c.double_angle, c.phase, c.amplitude, c.offset, c.eval_level,
+                                               c.eval_in_scale, c.eval_target_scale, pr))
 
 
 def ks_launch_forms():

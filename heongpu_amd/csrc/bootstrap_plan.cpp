@@ -103,5 +103,80 @@ BootstrapPlan bootstrap_plan(const BootstrapConfig& cfg, const std::vector<uint6
     return pl;
 }
 
+SlimBootstrapPlan slim_bootstrap_plan(const SlimBootstrapConfig& cfg, const std::vector<uint64_t>& primes)
+{
+    const int Q = (int) primes.size();
+    if (Q < 1) throw std::invalid_argument("slim_bootstrap_plan: no primes");
+    for (uint64_t p : primes)
+        if (p < 2) throw std::invalid_argument("slim_bootstrap_plan: a prime below 2");
+    if (!bootstrap_scale_ok(cfg.scale)) throw std::invalid_argument("slim_bootstrap_plan: the scale is a positive finite number");
+    if (!std::isfinite(cfg.ratio) || !(cfg.ratio >= 2.0)) throw std::invalid_argument("slim_bootstrap_plan: the ratio is at least 2");
+    if (cfg.K < 1 || cfg.K > (1 << 20)) throw std::invalid_argument("slim_bootstrap_plan: K is at least 1");
+    if (cfg.degree < 2 || cfg.degree > 255) throw std::invalid_argument("slim_bootstrap_plan: the degree is 2 .. 255");
+    if (cfg.double_angle < 0 || cfg.double_angle > 8) throw std::invalid_argument("slim_bootstrap_plan: double_angle is 0 .. 8");
+    for (int p : {cfg.cts_pieces, cfg.stc_pieces})
+        if (p < 2 || p > BOOTSTRAP_MAX_PIECES) throw std::invalid_argument("slim_bootstrap_plan: the piece counts lie in [2, 5]");
+    if (Q < cfg.stc_pieces + 1) throw std::invalid_argument("slim_bootstrap_plan: SlotToCoeff needs a chain of pieces + 1 limbs");
+    const double q0 = static_cast<double>(primes[0]);
+
+    SlimBootstrapPlan pl{};
+    pl.K = cfg.K;
+    pl.degree = cfg.degree;
+    pl.double_angle = cfg.double_angle;
+    pl.cts_pieces = cfg.cts_pieces;
+    pl.stc_pieces = cfg.stc_pieces;
+    pl.in_level = cfg.stc_pieces;
+    pl.cts_level = cfg.cts_level;
+    pl.ratio = cfg.ratio;
+    pl.phase = cfg.phase;
+    pl.amplitude = cfg.amplitude;
+    pl.offset = cfg.offset;
+    if (pl.cts_level < 0 || pl.cts_level >= Q) throw std::invalid_argument("slim_bootstrap_plan: no such CoeffToSlot level");
+    // P factors and the limb the real part drops; the polynomial and the double angles
+    pl.eval_level = pl.cts_level - pl.cts_pieces - 1;
+    pl.out_level = pl.eval_level - bootstrap_bit_length(cfg.degree) - cfg.double_angle;
+    if (pl.out_level < 0)
+        throw std::invalid_argument("slim_bootstrap_plan: too few levels (CoeffToSlot pieces + 1 + bit length of the degree + "
+                                    "double angles, and one limb left)");
+    // 1. SlotToCoeff takes the label from D at level P_stc to q_0 / ratio at level 0: no pre-multiplier
+    const double back = std::pow(q0 / cfg.ratio / cfg.scale, 1.0 / pl.stc_pieces);
+    double label = cfg.scale;
+    for (int g = 0; g < pl.stc_pieces; g++) {
+        const double q = static_cast<double>(primes[(size_t) (pl.in_level - g)]);
+        pl.stc_scale[g] = back * q;
+        label = label * pl.stc_scale[g] / q; // the product's label, then the rescale: as the sequence's caller labels it
+        pl.stc_label[g] = label;
+    }
+    // 2. the raise
+    pl.raise_scale = q0 * static_cast<double>(cfg.K);
+    // 3. CoeffToSlot brings the label to the scale of the polynomial's input
+    const double S = static_cast<double>(primes[(size_t) pl.eval_level]);
+    const double share = std::pow(S / pl.raise_scale, 1.0 / pl.cts_pieces);
+    label = pl.raise_scale;
+    for (int f = 0; f < pl.cts_pieces; f++) {
+        const double q = static_cast<double>(primes[(size_t) (pl.cts_level - f)]);
+        pl.cts_scale[f] = share * q;
+        label = label * pl.cts_scale[f] / q;
+        pl.cts_label[f] = label;
+    }
+    // 4. one plan from the label as it comes out
+    pl.eval_in_scale = label;
+    pl.eval_target_scale = S;
+    const std::vector<PolyStep> steps = eval_trig_plan(cfg.K, cfg.degree, cfg.double_angle, cfg.phase, cfg.amplitude, cfg.offset,
+                                                       pl.eval_level, pl.eval_in_scale, pl.eval_target_scale, primes);
+    if (steps.back().level != pl.out_level) throw std::invalid_argument("slim_bootstrap_plan: the plan does not end at its level");
+    pl.eval_out_scale = steps.back().scale;
+    // 5. the arithmetic value sin(2 pi z / rho) / 2 pi becomes (rho / 2 pi) sin(2 pi z / rho) by its label alone
+    pl.out_scale = cfg.arithmetic ? pl.eval_out_scale / cfg.ratio : pl.eval_out_scale;
+    for (int i = 0; i < BOOTSTRAP_MAX_PIECES; i++) {
+        if (i < pl.cts_pieces && !(bootstrap_scale_ok(pl.cts_scale[i]) && pl.cts_scale[i] >= 1.0))
+            throw std::invalid_argument("slim_bootstrap_plan: a CoeffToSlot factor's scale is below one or not finite");
+        if (i < pl.stc_pieces && !(bootstrap_scale_ok(pl.stc_scale[i]) && pl.stc_scale[i] >= 1.0))
+            throw std::invalid_argument("slim_bootstrap_plan: a SlotToCoeff factor's scale is below one or not finite");
+    }
+    if (!bootstrap_scale_ok(pl.out_scale)) throw std::invalid_argument("slim_bootstrap_plan: a scale left the range of a double");
+    return pl;
+}
+
 } // namespace host
 } // namespace hegpu

@@ -57,5 +57,45 @@ struct BootstrapPlan {
 // count outside [2, 5], what eval_mod_plan refuses.
 BootstrapPlan bootstrap_plan(const BootstrapConfig& cfg, const std::vector<uint64_t>& primes);
 
+// ---- the slim family (reference slim_bootstrapping, bit_bootstrapping, gate_bootstrapping): SlotToCoeff
+// first, one EvalMod-like plan on the real parts.
+//
+//   input  [2][P_stc + 1][N], slots z at scale D, level in_level = P_stc
+//   SlotToCoeff, factor g encoded at stc_scale[g]                   label stc_label[g] after its rescale; the last is
+//          = (q_0 / (ratio D))^(1/P) q_(P_stc - g)                   q_0 / ratio to the rounding of doubles, at level 0
+//   raise  to cts_level, labelled q_0 K                             t = (q_0 / ratio) a + q_0 I + e,  u = t / (q_0 K)
+//   CoeffToSlot as above, then conj, then x + conj x dropping a limb    slot j holds u_j (real), level eval_level
+//   trig plan (K, degree, r, phase, amplitude, offset)              offset + amplitude cos(2 pi (a / ratio - phase))
+//   out    at out_level = eval_level - bit_length(degree) - r, labelled eval_out_scale (/ ratio if `arithmetic`)
+// The layouts are the C ABI's hegpu_slim_bootstrap_config / hegpu_slim_bootstrap_plan, field for field.
+struct SlimBootstrapConfig {
+    double scale;      // D, the caller's scale
+    double ratio;      // q_0 / (the scale of the coefficients at the raise): 256 by default for slim, 2 for bits, 3 for gates
+    double phase, amplitude, offset;
+    int32_t K, degree, double_angle;
+    int32_t cts_level, cts_pieces, stc_pieces;
+    int32_t arithmetic; // 1: the result is relabelled by 1 / ratio (slim); 0: it is the function's value (bit, gates)
+    int32_t reserved;
+};
+
+struct SlimBootstrapPlan {
+    int32_t in_level, stc_pieces, cts_level, cts_pieces, eval_level, out_level;
+    int32_t K, degree, double_angle;
+    int32_t reserved;
+    double stc_scale[BOOTSTRAP_MAX_PIECES]; // factor g's diagonals (level in_level - g)
+    double stc_label[BOOTSTRAP_MAX_PIECES];
+    double raise_scale;                     // q_0 K
+    double cts_scale[BOOTSTRAP_MAX_PIECES];
+    double cts_label[BOOTSTRAP_MAX_PIECES];
+    double ratio, phase, amplitude, offset;
+    double eval_in_scale, eval_target_scale, eval_out_scale;
+    double out_scale;
+};
+
+// std::invalid_argument: fewer levels than P_cts + 1 + bit_length(degree) + r and one limb left, a chain of fewer than
+// P_stc + 1 limbs, ratio < 2, a piece count outside [2, 5], a factor scale below 1, a scale that is not positive and
+// finite, what eval_trig_plan refuses.
+SlimBootstrapPlan slim_bootstrap_plan(const SlimBootstrapConfig& cfg, const std::vector<uint64_t>& primes);
+
 } // namespace host
 } // namespace hegpu

@@ -614,6 +614,65 @@ int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64
     });
 }
 
+// host only: the cosine with a phase and an offset (poly_eval.hpp) and the plan of the slim refreshes (bootstrap_plan.hpp)
+static std::vector<host::PolyStep> eval_trig_plan_of(int K, int degree, int double_angle, double phase, double amplitude,
+                                                     double offset, int level, double scale, double target_scale,
+                                                     const uint64_t* primes, int n_primes)
+{
+    if (!primes || n_primes < 1) throw std::invalid_argument("eval_trig_plan: null argument");
+    return host::eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale,
+                                std::vector<uint64_t>(primes, primes + n_primes));
+}
+
+int hegpu_eval_trig_plan_size(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
+                              double scale, double target_scale, const uint64_t* primes, int n_primes, int* n_steps)
+{
+    return guarded([&]() -> int {
+        if (!n_steps) return fail(HEGPU_E_INVALID, "eval_trig_plan_size: null argument");
+        const std::vector<host::PolyStep> plan =
+            eval_trig_plan_of(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes, n_primes);
+        *n_steps = (int) plan.size();
+        return 0;
+    });
+}
+
+int hegpu_eval_trig_plan_fill(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
+                              double scale, double target_scale, const uint64_t* primes, int n_primes,
+                              hegpu_poly_step* steps, int n_steps)
+{
+    return guarded([&]() -> int {
+        if (!steps) return fail(HEGPU_E_INVALID, "eval_trig_plan_fill: null argument");
+        const std::vector<host::PolyStep> plan =
+            eval_trig_plan_of(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes, n_primes);
+        if (n_steps != (int) plan.size())
+            return fail(HEGPU_E_INVALID, "eval_trig_plan_fill: n_steps is not what hegpu_eval_trig_plan_size gives");
+        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
+        return 0;
+    });
+}
+
+static_assert(sizeof(hegpu_slim_bootstrap_config) == sizeof(host::SlimBootstrapConfig) &&
+                  sizeof(hegpu_slim_bootstrap_plan) == sizeof(host::SlimBootstrapPlan) &&
+                  offsetof(hegpu_slim_bootstrap_config, cts_level) == offsetof(host::SlimBootstrapConfig, cts_level) &&
+                  offsetof(hegpu_slim_bootstrap_config, arithmetic) == offsetof(host::SlimBootstrapConfig, arithmetic) &&
+                  offsetof(hegpu_slim_bootstrap_plan, raise_scale) == offsetof(host::SlimBootstrapPlan, raise_scale) &&
+                  offsetof(hegpu_slim_bootstrap_plan, ratio) == offsetof(host::SlimBootstrapPlan, ratio) &&
+                  offsetof(hegpu_slim_bootstrap_plan, eval_in_scale) == offsetof(host::SlimBootstrapPlan, eval_in_scale) &&
+                  offsetof(hegpu_slim_bootstrap_plan, out_scale) == offsetof(host::SlimBootstrapPlan, out_scale),
+              "hegpu_slim_bootstrap_config / _plan are host::SlimBootstrapConfig / SlimBootstrapPlan");
+int hegpu_slim_bootstrap_plan_fill(const hegpu_slim_bootstrap_config* config, const uint64_t* primes, int n_primes,
+                                   hegpu_slim_bootstrap_plan* plan)
+{
+    return guarded([&]() -> int {
+        if (!config || !primes || !plan || n_primes < 1) return fail(HEGPU_E_INVALID, "slim_bootstrap_plan_fill: null argument");
+        host::SlimBootstrapConfig cfg;
+        std::memcpy(&cfg, config, sizeof(cfg));
+        const host::SlimBootstrapPlan pl = host::slim_bootstrap_plan(cfg, std::vector<uint64_t>(primes, primes + n_primes));
+        std::memcpy(plan, &pl, sizeof(pl));
+        return 0;
+    });
+}
+
 #define NEED_CTX(ctx)                                                                      \
     if (!(ctx)) return fail(HEGPU_E_INVALID, "null context");                              \
     if (!(ctx)->c.uploaded) {                                                              \
@@ -1323,11 +1382,35 @@ int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_st
                    "hegpu_ckks_conj_merge");
 }
 
-// the factor array of a sequence entry: every factor through the checks of hegpu_ckks_linear_transform's matrix arguments
-static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f, int count, int depth, const char* who)
+// Everything is checked on the host tables, before the context is uploaded: a refusal needs no device.
+int hegpu_ckks_conj_real(hegpu_context* ctx, const uint64_t* x, uint64_t x_stride, const uint64_t* xc, uint64_t xc_stride,
+                         uint64_t* out, uint64_t out_stride, int depth, int out_depth, int batch, hegpu_stream stream)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (int r = conj_pass_check(ctx, depth, out_depth, batch, "conj_real")) return r;
+    if (!x || !xc || !out) return fail(HEGPU_E_INVALID, "conj_real: null argument");
+    const Span a{x, x_stride, level_words(ctx->c, depth)}, b{xc, xc_stride, a.item}, res{out, out_stride, level_words(ctx->c, out_depth)};
+    if (overlaps_any(res, {b}, batch)) return fail(HEGPU_E_INVALID, "conj_real: out must not overlap xc");
+    const bool in_place = out == x && out_stride == x_stride && out_depth == depth;
+    if (!in_place && overlaps_any(res, {a}, batch))
+        return fail(HEGPU_E_INVALID, "conj_real: out is x itself (equal strides and depths) or does not overlap it");
+    NEED_CTX(ctx);
+    return hip_ret(rns_ckks_conj_real((const u64*) x, x_stride, (const u64*) xc, xc_stride, (u64*) out, out_stride,
+                                      ctx->c.plan_qp.mods, ctx->c.n_power, ctx->c.Q_size - depth, ctx->c.Q_size - out_depth,
+                                      batch, (hipStream_t) stream),
+                   "hegpu_ckks_conj_real");
+}
+
+// the factor array of a sequence entry: every factor through the checks of hegpu_ckks_linear_transform's matrix arguments;
+// boundary: the levels the sequence spends besides one per factor (the real / imaginary pass; the slim SlotToCoeff has none)
+static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f, int count, int depth, const char* who,
+                         int boundary = 1)
 {
     if (!f || count < 1) return fail(HEGPU_E_INVALID, std::string(who) + ": at least one factor");
-    if (depth < 0 || depth + count + 1 >= ctx->c.Q_size)
+    if (boundary == 0 && (depth < 0 || depth + count >= ctx->c.Q_size))
+        return fail(HEGPU_E_INVALID, std::string(who) + ": depth + factors must stay below Q (one level per factor)");
+    if (boundary != 0 && (depth < 0 || depth + count + 1 >= ctx->c.Q_size))
         return fail(HEGPU_E_INVALID, std::string(who) + ": depth + factors + 1 must stay below Q (one level per factor, one "
                                                         "at the real / imaginary boundary)");
     for (int k = 0; k < count; k++) {
@@ -1477,6 +1560,76 @@ int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
                                          (const u64*) conj_key, (const u64*) relin_key, (const u64*) swk_dense_to_sparse,
                                          (const u64*) swk_sparse_to_dense, batch, (u64*) ws, (hipStream_t) stream),
                        "hegpu_ckks_bootstrap");
+    });
+}
+
+// ---- the slim family of refreshes, checked like the refresh above
+static int slim_bootstrap_check(const hegpu_context* ctx, const hegpu_slim_bootstrap_plan* plan, const hegpu_poly_step* trig,
+                                int n_steps, const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc,
+                                int stc_count, int batch)
+{
+    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
+    if (!plan || !trig || !cts || !stc) return fail(HEGPU_E_INVALID, "slim_bootstrap: null argument");
+    if (int r = check_items(batch, 4, "slim_bootstrap")) return r;
+    host::SlimBootstrapPlan p;
+    std::memcpy(&p, plan, sizeof(p));
+    if (const char* why = ops_slim_bootstrap_check(ctx->c, p, reinterpret_cast<const host::PolyStep*>(trig), n_steps))
+        return fail(HEGPU_E_INVALID, std::string("slim_bootstrap: ") + why);
+    if (cts_count != p.cts_pieces || stc_count != p.stc_pieces)
+        return fail(HEGPU_E_INVALID, "slim_bootstrap: as many factors as the plan has pieces");
+    const int Q = ctx->c.Q_size;
+    if (int r = factors_check(ctx, cts, p.cts_pieces, Q - 1 - p.cts_level, "slim_bootstrap (CoeffToSlot)")) return r;
+    if (int r = factors_check(ctx, stc, p.stc_pieces, Q - 1 - p.in_level, "slim_bootstrap (SlotToCoeff)", 0)) return r;
+    return 0;
+}
+
+size_t hegpu_ckks_slim_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_slim_bootstrap_plan* plan,
+                                                 const hegpu_poly_step* trig, int n_steps, const hegpu_linear_factor* cts,
+                                                 int cts_count, const hegpu_linear_factor* stc, int stc_count, int batch)
+{
+    size_t bytes = 0;
+    (void) guarded([&]() -> int { // no exception may cross the C boundary
+        if (slim_bootstrap_check(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch)) return 0;
+        host::SlimBootstrapPlan p;
+        std::memcpy(&p, plan, sizeof(p));
+        bytes = ops_slim_bootstrap_workspace_elems(ctx->c, p, reinterpret_cast<const host::PolyStep*>(trig), n_steps,
+                                                   factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
+                                                   batch) * sizeof(u64);
+        return 0;
+    });
+    return bytes;
+}
+
+int hegpu_ckks_slim_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, const uint64_t* ct2, uint64_t cs2,
+                              uint64_t* out, uint64_t so, const hegpu_slim_bootstrap_plan* plan, const hegpu_poly_step* trig,
+                              int n_steps, const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc,
+                              int stc_count, const uint64_t* conj_key, const uint64_t* relin_key, int batch, void* ws,
+                              size_t ws_bytes, hegpu_stream stream)
+{
+    return guarded([&]() -> int {
+        if (int r = slim_bootstrap_check(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch)) return r;
+        if (!ct || !out || !conj_key || !relin_key || !ws) return fail(HEGPU_E_INVALID, "slim_bootstrap: null argument");
+        host::SlimBootstrapPlan p;
+        std::memcpy(&p, plan, sizeof(p));
+        const host::PolyStep* steps = reinterpret_cast<const host::PolyStep*>(trig);
+        if (int r = check_leaf_weights(steps, n_steps, "slim_bootstrap")) return r;
+        const host::PolyStep& last = steps[n_steps - 1];
+        const uint64_t in_words = ct_words(ctx->c, p.in_level + 1);
+        const Span in{ct, cs, in_words}, in2{ct2 ? ct2 : ct, ct2 ? cs2 : cs, in_words};
+        const Span res{out, so, ct_words(ctx->c, p.out_level + 1 + (last.rescale_after ? 1 : 0))};
+        if (batch > 1 && so < res.item) return fail(HEGPU_E_INVALID, "slim_bootstrap: out_stride too small");
+        const size_t need = hegpu_ckks_slim_bootstrap_workspace_bytes(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch);
+        if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+        if (overlaps_any(res, {in, in2}, batch)) return fail(HEGPU_E_INVALID, "slim_bootstrap: out must overlap neither ct nor ct2");
+        if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in, in2}, batch))
+            return fail(HEGPU_E_INVALID, "slim_bootstrap: the workspace must overlap neither out nor ct nor ct2");
+        NEED_CTX(ctx);
+        return hip_ret(op_ckks_slim_bootstrap(ctx->c, (const u64*) ct, cs, (const u64*) ct2, cs2, (u64*) out, so, p, steps, n_steps,
+                                              factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
+                                              (const u64*) conj_key, (const u64*) relin_key, batch, (u64*) ws,
+                                              (hipStream_t) stream),
+                       "hegpu_ckks_slim_bootstrap");
     });
 }
 

@@ -1350,6 +1350,98 @@ hipError_t op_ckks_bootstrap(const Context& c, const u64* ct, u64 cs, u64* out, 
                                  Q - 1 - p.stc_level, batch, step_ws, st);
 }
 
+// ------------------------------------------------------------------ the slim family of refreshes
+// Per batch: the raise's coefficient-domain pair [2][N], the raised ciphertext [2][cts_level + 1][N], the real parts
+// [2][eval_level + 1][N], then one region the three sequences use in turn: the two alternating ciphertexts and the step
+// workspace of an encoding transform (SlotToCoeff at the input's depth, CoeffToSlot at the raise's) or the polynomial
+// evaluator's workspace.  The SlotToCoeff result stays in that region until the raise has read it.
+struct SlimBootstrapWs { u64 raise_ws, R, r_stride, H, h_stride, step, total; };
+static SlimBootstrapWs slim_bootstrap_ws(const Context& c, const host::SlimBootstrapPlan& p, const host::PolyStep* trig,
+                                         int n_steps, const LinearFactor* cts, const LinearFactor* stc, int batch)
+{
+    const u64 n = c.n, B = (u64) batch;
+    const int Q = c.Q_size;
+    SlimBootstrapWs w{};
+    w.raise_ws = 0;
+    w.R = mod_raise_ws(c) * B;
+    w.r_stride = (u64) 2 * (p.cts_level + 1) * n;
+    w.H = w.R + w.r_stride * B;
+    w.h_stride = (u64) 2 * (p.eval_level + 1) * n;
+    w.step = w.H + w.h_stride * B;
+    u64 step = std::max(ops_encoding_transform_workspace_elems(c, cts, p.cts_pieces, Q - 1 - p.cts_level, batch),
+                        ops_encoding_transform_workspace_elems(c, stc, p.stc_pieces, Q - 1 - p.in_level, batch));
+    step = std::max<u64>(step, ops_poly_eval_workspace_elems(c, trig, n_steps, Q - 1 - p.eval_level, batch));
+    w.total = w.step + step;
+    return w;
+}
+
+const char* ops_slim_bootstrap_check(const Context& c, const host::SlimBootstrapPlan& p, const host::PolyStep* trig, int n_steps)
+{
+    const int Q = c.Q_size;
+    if (c.scheme != SCHEME_CKKS) return "context scheme mismatch";
+    if (p.cts_pieces < 1 || p.cts_pieces > host::BOOTSTRAP_MAX_PIECES || p.stc_pieces < 1 ||
+        p.stc_pieces > host::BOOTSTRAP_MAX_PIECES)
+        return "a piece count outside [1, 5]";
+    if (p.in_level != p.stc_pieces || p.in_level >= Q) return "SlotToCoeff starts at the level of its piece count";
+    if (p.cts_level < 1 || p.cts_level >= Q) return "the raise goes to a level the context has";
+    if (p.eval_level != p.cts_level - p.cts_pieces - 1 || p.eval_level < 1) return "the polynomial starts pieces + 1 levels below CoeffToSlot";
+    if (const char* why = ops_poly_eval_check(c, trig, n_steps, Q - 1 - p.eval_level)) return why;
+    const host::PolyStep& last = trig[n_steps - 1];
+    if (last.level != p.out_level || last.scale != p.eval_out_scale) return "the polynomial plan is not the one of the bootstrap plan";
+    return nullptr;
+}
+
+size_t ops_slim_bootstrap_workspace_elems(const Context& c, const host::SlimBootstrapPlan& p, const host::PolyStep* trig,
+                                          int n_steps, const LinearFactor* cts, const LinearFactor* stc, int batch)
+{
+    return slim_bootstrap_ws(c, p, trig, n_steps, cts, stc, batch).total;
+}
+
+// [ct + ct2] -> SlotToCoeff down to q_0 -> raise -> CoeffToSlot, conjugate, real part -> ONE polynomial at batch B into out.
+// Every step is the existing sequence; the only kernel of its own is rns_ckks_conj_real.
+hipError_t op_ckks_slim_bootstrap(const Context& c, const u64* ct, u64 cs, const u64* ct2, u64 cs2, u64* out, u64 so,
+                                  const host::SlimBootstrapPlan& p, const host::PolyStep* trig, int n_steps,
+                                  const LinearFactor* cts, const LinearFactor* stc, const u64* conj_key, const u64* relin_key,
+                                  int batch, u64* ws, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (ops_slim_bootstrap_check(c, p, trig, n_steps)) return hipErrorInvalidValue;
+    const SlimBootstrapWs w = slim_bootstrap_ws(c, p, trig, n_steps, cts, stc, batch);
+    const int Q = c.Q_size, in_depth = Q - 1 - p.in_level, raise_depth = Q - 1 - p.cts_level;
+    u64* region = ws + w.step;
+    // 1. SlotToCoeff on the one input, P_stc levels, no merge
+    const EncodingTransformWs ws_stc = encoding_transform_ws(c, stc, p.stc_pieces, in_depth, batch);
+    const u64* cur = ct;
+    u64 cur_stride = cs;
+    if (ct2) { // a gate: the modular sum of its two inputs
+        TRY(rns_addition_strided(ct, cs, ct2, cs2, region, ws_stc.t_stride, c.plan_qp.mods, c.n_power, Q - in_depth, 2, batch, st));
+        cur = region;
+        cur_stride = ws_stc.t_stride;
+    }
+    TRY(encoding_transform_chain(c, cur, cur_stride, region, region + ws_stc.T1, ws_stc.t_stride, nullptr, 0, stc,
+                                 p.stc_pieces, in_depth, batch, region + ws_stc.step, st));
+    // 2. the raise of its q_0 limbs ([2][1][N] per item after the last rescale)
+    u64* R = ws + w.R;
+    TRY(op_ckks_mod_raise(c, cur, cur_stride, R, w.r_stride, raise_depth, batch, ws + w.raise_ws, st));
+    // 3. CoeffToSlot, the conjugate, and the real part alone
+    const EncodingTransformWs ws_cts = encoding_transform_ws(c, cts, p.cts_pieces, raise_depth, batch);
+    u64* T0 = region;
+    u64* T1 = region + ws_cts.T1;
+    cur = R;
+    cur_stride = w.r_stride;
+    TRY(encoding_transform_chain(c, cur, cur_stride, T0, T1, ws_cts.t_stride, nullptr, 0, cts, p.cts_pieces, raise_depth,
+                                 batch, region + ws_cts.step, st));
+    const int d = raise_depth + p.cts_pieces;
+    u64* conj = (cur == T0) ? T1 : T0;
+    TRY(op_ckks_apply_galois(c, cur, cur_stride, conj, ws_cts.t_stride, conj_key, 2 * (int) c.n - 1, d, batch,
+                             region + ws_cts.step, st));
+    u64* H = ws + w.H;
+    TRY(rns_ckks_conj_real(cur, cur_stride, conj, ws_cts.t_stride, H, w.h_stride, c.plan_qp.mods, c.n_power, Q - d, Q - d - 1,
+                           batch, st));
+    // 4. one plan, batch items
+    return op_ckks_poly_eval(c, H, w.h_stride, out, so, trig, n_steps, relin_key, Q - 1 - p.eval_level, batch, region, st);
+}
+
 // ------------------------------------------------------------------ logic gates
 hipError_t op_ckks_logic_gate(const Context& c, int gate, const u64* a, u64 as, const u64* b, int b_kind, u64 bs,
                               const u64* relin_key, double scale_one, u64* out, u64 so, int depth, int batch, u64* ws,

@@ -120,6 +120,22 @@ hipError_t op_ckks_bootstrap(const Context& c, const u64* ct, u64 cs, u64* out, 
                              const u64* conj_key, const u64* relin_key, const u64* swk_dense_to_sparse,
                              const u64* swk_sparse_to_dense, int batch, u64* ws, hipStream_t st);
 
+// ---- the slim family of refreshes (reference slim_bootstrapping, bit_bootstrapping, gate_bootstrapping):
+// ct (and ct2 for a gate: their modular sum first, one addition launch into the workspace) [2][P_stc + 1][N] per item ->
+// per SlotToCoeff factor op_ckks_linear_transform + op_ckks_rescale, down to q_0, no merge -> op_ckks_mod_raise to the
+// plan's cts_level -> per CoeffToSlot factor the same -> op_ckks_apply_galois (2N - 1) -> rns_ckks_conj_real dropping one
+// limb -> ONE op_ckks_poly_eval of the trig plan at batch `batch` into out ([2][out_level + 1 + rescale_after][N] of room).
+// No switch keys.  trig: the steps of host::eval_trig_plan for the plan's (K, degree, double_angle, phase, amplitude, offset,
+// eval_level, eval_in_scale, eval_target_scale).  The workspace has no row in the OP_* table: ops_slim_bootstrap_workspace_elems
+// sizes all of it (check first).
+const char* ops_slim_bootstrap_check(const Context& c, const host::SlimBootstrapPlan& p, const host::PolyStep* trig, int n_steps);
+size_t ops_slim_bootstrap_workspace_elems(const Context& c, const host::SlimBootstrapPlan& p, const host::PolyStep* trig,
+                                          int n_steps, const LinearFactor* cts, const LinearFactor* stc, int batch);
+hipError_t op_ckks_slim_bootstrap(const Context& c, const u64* ct, u64 cs, const u64* ct2, u64 cs2, u64* out, u64 so,
+                                  const host::SlimBootstrapPlan& p, const host::PolyStep* trig, int n_steps,
+                                  const LinearFactor* cts, const LinearFactor* stc, const u64* conj_key, const u64* relin_key,
+                                  int batch, u64* ws, hipStream_t st);
+
 // ---- logic gates on bits held as 0 / 1 (HELogicOperator<CKKS / BFV>, host/ckks/operator.cuh:2333-3500,
 // host/bfv/operator.cuh:1324-2230): the product sequence of the arithmetic operator into the workspace, then ONE
 // rns_gate_combine pass that reads a, b and the product in place and writes out (AND: the pass is its copy out of the

@@ -246,9 +246,10 @@ std::vector<PolyStep> poly_eval_plan(int basis, const std::vector<cplx>& coeffs,
     return pl.steps;
 }
 
-// eval_mod, ckks/operator.cu:4248-4290: the polynomial, then r times (square, relinearize, double, subtract, rescale)
-std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int level, double scale, double target_scale,
-                                    const std::vector<uint64_t>& primes)
+// eval_mod, ckks/operator.cu:4248-4290: the polynomial, then r times (square, relinearize, double, subtract, rescale).
+// One cosine with a phase, an amplitude and an offset; EvalMod is (1/4, 1 / 2 pi, 0).
+std::vector<PolyStep> eval_trig_plan(int K, int degree, int double_angle, double phase, double amplitude, double offset,
+                                     int level, double scale, double target_scale, const std::vector<uint64_t>& primes)
 {
     const int r = double_angle;
     if (K < 1 || K > (1 << 20)) throw std::invalid_argument("eval_mod_plan: K is at least 1");
@@ -256,6 +257,8 @@ std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int lev
     if (degree < 2 || degree > 255) throw std::invalid_argument("eval_mod_plan: the degree is 2 .. 255");
     if (!std::isfinite(scale) || !std::isfinite(target_scale) || scale <= 0 || target_scale <= 0)
         throw std::invalid_argument("eval_mod_plan: a scale is not a positive finite number");
+    if (!std::isfinite(phase) || !std::isfinite(amplitude) || !std::isfinite(offset) || !(amplitude > 0))
+        throw std::invalid_argument("eval_trig_plan: phase and offset are finite, the amplitude is positive and finite");
     if (level < 0 || level >= (int) primes.size()) throw std::invalid_argument("eval_mod_plan: no such level");
     for (uint64_t p : primes)
         if (p < 2) throw std::invalid_argument("eval_mod_plan: a prime below 2");
@@ -264,14 +267,14 @@ std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int lev
     // the square-root chain (:4257-4265): the scale p must have for the r squarings to end at target_scale
     double target_p = target_scale;
     for (int i = 0; i < r; i++) target_p = std::sqrt(target_p * static_cast<double>(primes[(size_t) (level_p - r + i + 1)]));
-    // Chebyshev interpolant of g(u) = c cos(2 pi (K u - 1/4) / 2^r) at the degree + 1 Chebyshev nodes
+    // Chebyshev interpolant of g(u) = c cos(2 pi (K u - phase) / 2^r) at the degree + 1 Chebyshev nodes
     const double pi = 3.14159265358979323846;
-    const double c = std::pow(1.0 / (2.0 * pi), 1.0 / static_cast<double>(1 << r));
+    const double c = std::pow(amplitude, 1.0 / static_cast<double>(1 << r));
     const int m = degree + 1;
     std::vector<double> g((size_t) m);
     for (int j = 0; j < m; j++) {
         const double u = std::cos(pi * (j + 0.5) / m);
-        g[(size_t) j] = c * std::cos(2.0 * pi * (K * u - 0.25) / static_cast<double>(1 << r));
+        g[(size_t) j] = c * std::cos(2.0 * pi * (K * u - phase) / static_cast<double>(1 << r));
     }
     std::vector<cplx> coeffs((size_t) m);
     for (int k = 0; k < m; k++) {
@@ -279,9 +282,10 @@ std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int lev
         for (int j = 0; j < m; j++) s += g[(size_t) j] * std::cos(pi * k * (j + 0.5) / m);
         coeffs[(size_t) k] = cplx(s * (k ? 2.0 : 1.0) / m, 0.0);
     }
+    if (r == 0 && offset != 0) coeffs[0] += offset; // no double angle to carry it: the offset is the polynomial's
     std::vector<PolyStep> steps = poly_eval_plan(POLY_CHEBYSHEV, coeffs, degree, true, level, scale, target_p, primes);
     if (steps.back().level != level_p) throw std::invalid_argument("eval_mod_plan: the interpolant does not end at its level");
-    // y <- 2 y^2 - c^(2^(i+1)): a POWER step whose tail is the constant at the step's scale
+    // y <- 2 y^2 - c^(2^(i+1)): a POWER step whose tail is the constant at the step's scale; the last one leaves the offset
     double cc = c;
     for (int i = 0; i < r; i++) {
         const PolyStep prev = steps.back();
@@ -294,13 +298,20 @@ std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int lev
         s.mul_level = prev.level;
         s.level = prev.level - 1;
         s.scale = prev.scale * prev.scale / static_cast<double>(primes[(size_t) prev.level]);
-        s.tail_const = cc * s.scale;
+        s.tail_const = ((i == r - 1 && offset != 0) ? cc - offset : cc) * s.scale;
         for (int& t : s.term_reg) t = -1;
         if (!std::isfinite(s.scale) || !(std::fabs(s.tail_const) < 3.4e38))
             throw std::invalid_argument("eval_mod_plan: a scale left the range of the evaluator");
         steps.push_back(s);
     }
     return steps;
+}
+
+std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int level, double scale, double target_scale,
+                                    const std::vector<uint64_t>& primes)
+{
+    const double pi = 3.14159265358979323846;
+    return eval_trig_plan(K, degree, double_angle, 0.25, 1.0 / (2.0 * pi), 0.0, level, scale, target_scale, primes);
 }
 
 } // namespace host

@@ -63,5 +63,12 @@ std::vector<PolyStep> poly_eval_plan(int basis, const std::vector<std::complex<d
 std::vector<PolyStep> eval_mod_plan(int K, int degree, int double_angle, int level, double scale, double target_scale,
                                     const std::vector<uint64_t>& primes);
 
+// The same plan for alpha + A cos(2 pi (K u - phase)): the interpolant of g(u) = c cos(2 pi (K u - phase) /
+// 2^r) with c = A^(1 / 2^r), then the r double-angle steps; the last tail constant is A - alpha in place of A (any sign, or
+// zero), and without a double angle alpha is added to Chebyshev coefficient 0.  eval_mod_plan is (1/4, 1 / 2 pi, 0), step for
+// step.  std::invalid_argument: what eval_mod_plan refuses, an amplitude <= 0, a non-finite phase, amplitude or offset.
+std::vector<PolyStep> eval_trig_plan(int K, int degree, int double_angle, double phase, double amplitude, double offset,
+                                     int level, double scale, double target_scale, const std::vector<uint64_t>& primes);
+
 } // namespace host
 } // namespace hegpu

@@ -1386,6 +1386,35 @@ __global__ __launch_bounds__(RNS_THREADS) void k_ckks_conj_merge(const u64* __re
     st2(out + out_stride * item + o, r);
 }
 
+// The real half of the split alone (the slim refresh keeps no imaginary part): out = x + conj x.  4 in + 2
+// out limb-vectors per kept limb, no Barrett product, no psi_half; the words are k_ckks_conj_split's out0.  out may be x
+// itself when out_limbs == in_limbs (every thread reads its two words before it writes them), hence no __restrict__ there.
+__global__ __launch_bounds__(RNS_THREADS) void k_ckks_conj_real(const u64* x, u64 x_stride,
+                                                                const u64* __restrict__ xc, u64 xc_stride, u64* out,
+                                                                u64 out_stride, const Mod* __restrict__ mods, int n_power,
+                                                                int in_limbs, int out_limbs)
+{
+    const u64 q = mods[blockIdx.y].q;
+    const int z = blockIdx.z & 1, item = blockIdx.z >> 1;
+    const u64 c = coeff0(), limb = (u64) blockIdx.y << n_power;
+    const u64 in = c + limb + (((u64) in_limbs * z) << n_power), o = c + limb + (((u64) out_limbs * z) << n_power);
+    const ulonglong2 a = ld2(x + x_stride * item + in), b = ld2(xc + xc_stride * item + in);
+    ulonglong2 s;
+    s.x = add_mod(a.x, b.x, q);
+    s.y = add_mod(a.y, b.y, q);
+    st2(out + out_stride * item + o, s);
+}
+
+hipError_t rns_ckks_conj_real(const u64* x, u64 x_stride, const u64* xc, u64 xc_stride, u64* out, u64 out_stride,
+                              const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch, hipStream_t st)
+{
+    if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
+    if (out_limbs < 1 || out_limbs > in_limbs || 2 * (long) batch > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ckks_conj_real, grid3(n_power, out_limbs, 2 * batch), dim3(RNS_THREADS), 0, st, x, x_stride, xc,
+                       xc_stride, out, out_stride, mods, n_power, in_limbs, out_limbs);
+    return hipGetLastError();
+}
+
 hipError_t rns_ckks_conj_split(const u64* x, u64 x_stride, const u64* xc, u64 xc_stride, u64* out0, u64* out1,
                                u64 out_stride, const u64* psi_half, const Mod* mods, int n_power, int in_limbs,
                                int out_limbs, int batch, hipStream_t st)

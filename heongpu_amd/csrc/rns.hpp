@@ -138,6 +138,9 @@ hipError_t rns_ckks_conj_split(const u64* x, u64 x_stride, const u64* xc, u64 xc
 hipError_t rns_ckks_conj_merge(const u64* c0, u64 c0_stride, const u64* c1, u64 c1_stride, u64* out, u64 out_stride,
                                const u64* psi_half, const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch,
                                hipStream_t st);
+//   real:  out = x + xc, the split's out0 alone; out may be x itself (same stride, out_limbs == in_limbs), never xc
+hipError_t rns_ckks_conj_real(const u64* x, u64 x_stride, const u64* xc, u64 xc_stride, u64* out, u64 out_stride,
+                              const Mod* mods, int n_power, int in_limbs, int out_limbs, int batch, hipStream_t st);
 
 // A leaf of the polynomial evaluator (evaluate_poly_from_polynomial_basis, ckks/operator.cu:4400-4484, in one pass):
 // out[p] = (p == 0 ? w_0 : 0) + sum_k w_k * terms[k][p] over the first `limbs` limbs, p = 0, 1.  terms / strides /

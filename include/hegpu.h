@@ -579,6 +579,91 @@ int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_str
                          const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc, int stc_count,
                          const uint64_t* conj_key, const uint64_t* relin_key, const uint64_t* swk_dense_to_sparse, const uint64_t* swk_sparse_to_dense,
                          int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
+/* ------------------------------------------------------------------ the slim family of CKKS refreshes (slim_bootstrapping,
+ * HELogicOperator<CKKS>::bit_bootstrapping and the *_bootstrapping gates, eprint 2024/767): SlotToCoeff FIRST at the bottom of
+ * the chain, the raise, CoeffToSlot, the REAL parts only, ONE EvalMod-like polynomial.  One function family:
+ *   alpha + A cos(2 pi (K u - phi)),  K u = I + a / ratio
+ *   function   ratio        phi    A        alpha
+ *   slim       config (256) 1/4    1 / 2 pi 0       sin(2 pi z / rho) / 2 pi, relabelled by 1 / rho (rho = ratio): f(z) of the
+ *                                                   regular refresh
+ *   bit        2            1/2    1/2      1/2     b for b in {0, 1}
+ *   AND        3            2/3    2/3      1/3     with s = a + b in {0, 1, 2}: the gate's value
+ *   OR         3            1/2    2/3      2/3
+ *   XOR        3            1/3    2/3      1/3
+ *   NAND       3            1/6    2/3      2/3
+ *   NOR        3            0      2/3      1/3
+ *   XNOR       3            5/6    2/3      2/3
+ *
+ * TRIG PLAN.  hegpu_eval_trig_plan_* is hegpu_eval_mod_plan_* with the phase, the amplitude and the offset as arguments
+ * (host only): the interpolant of g(u) = c cos(2 pi (K u - phase) / 2^r), c = amplitude^(1 / 2^r), then r double-angle
+ * steps; the last tail constant is (amplitude - offset) at the step's scale (any sign, or zero); with double_angle == 0 the
+ * offset is added to Chebyshev coefficient 0.  (1/4, 1 / 2 pi, 0) is hegpu_eval_mod_plan_*, step for step.
+ * HEGPU_E_INVALID: what hegpu_eval_mod_plan_* refuses, amplitude <= 0, a non-finite phase, amplitude or offset.
+ *
+ * PLAN.  hegpu_slim_bootstrap_plan_fill is host only.  The input has P_stc + 1 limbs (in_level = stc_pieces) and scale D:
+ *   factor g of SlotToCoeff is encoded at stc_scale[g] (level in_level - g) and leaves the label stc_label[g]; the last is
+ *   q_0 / ratio to the rounding of doubles, at level 0: no pre-multiplier;
+ *   the raised ciphertext (level cts_level) is labelled raise_scale = q_0 K;
+ *   factor f of CoeffToSlot is encoded at cts_scale[f] (level cts_level - f); cts_label[last] = eval_in_scale is
+ *   q_(eval_level) to the rounding of doubles, eval_level = cts_level - cts_pieces - 1 (the real part drops a limb);
+ *   the trig plan hegpu_eval_trig_plan_*(K, degree, double_angle, phase, amplitude, offset, eval_level, eval_in_scale,
+ *   eval_target_scale) ends at out_level = eval_level - bit_length(degree) - double_angle with eval_out_scale;
+ *   out_scale = eval_out_scale / ratio if config->arithmetic, else eval_out_scale.
+ * HEGPU_E_INVALID, *plan untouched: fewer levels than cts_pieces + 1 + bit_length(degree) + double_angle and one limb left,
+ * a chain of fewer than stc_pieces + 1 limbs, ratio < 2, piece counts outside [2, 5], a factor scale below 1, what
+ * hegpu_eval_trig_plan_* refuses. */
+int hegpu_eval_trig_plan_size(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
+                              double scale, double target_scale, const uint64_t* primes, int n_primes, int* n_steps);
+int hegpu_eval_trig_plan_fill(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
+                              double scale, double target_scale, const uint64_t* primes, int n_primes,
+                              hegpu_poly_step* steps, int n_steps);
+typedef struct hegpu_slim_bootstrap_config {
+    double scale, ratio;
+    double phase, amplitude, offset;
+    int32_t K, degree, double_angle;
+    int32_t cts_level, cts_pieces, stc_pieces;
+    int32_t arithmetic; /* 1: out_scale = eval_out_scale / ratio (slim); 0: bit and gates */
+    int32_t reserved;
+} hegpu_slim_bootstrap_config;
+typedef struct hegpu_slim_bootstrap_plan {
+    int32_t in_level, stc_pieces, cts_level, cts_pieces, eval_level, out_level;
+    int32_t K, degree, double_angle;
+    int32_t reserved;
+    double stc_scale[5], stc_label[5];
+    double raise_scale;
+    double cts_scale[5], cts_label[5];
+    double ratio, phase, amplitude, offset;
+    double eval_in_scale, eval_target_scale, eval_out_scale;
+    double out_scale;
+} hegpu_slim_bootstrap_plan;
+int hegpu_slim_bootstrap_plan_fill(const hegpu_slim_bootstrap_config* config, const uint64_t* primes, int n_primes,
+                                   hegpu_slim_bootstrap_plan* plan);
+/* The real half of hegpu_ckks_conj_split alone: out = x + xc on the Q - out_depth kept limbs, both parts, one read of each
+ * input and one write.  Bit-identical to conj_split's out0 and to hegpu_addition on the kept limbs.  out may be x itself
+ * when out_depth == depth and out_stride == x_stride (in place).  Every refusal comes before the device is touched.
+ * HEGPU_E_INVALID, out untouched: out overlapping xc, or x in any other way; out_depth < depth or >= Q; batch < 1. */
+int hegpu_ckks_conj_real(hegpu_context* ctx, const uint64_t* x, uint64_t x_stride, const uint64_t* xc, uint64_t xc_stride,
+                         uint64_t* out, uint64_t out_stride, int depth, int out_depth, int batch, hegpu_stream stream);
+/* SEQUENCE.  ct (and ct2 for a gate, else NULL): [2][stc_pieces + 1][N] per item.  The launches, all on `stream`, nothing
+ * allocated: with ct2 one addition of the two into the workspace -> per SlotToCoeff factor hegpu_ckks_linear_transform +
+ * hegpu_ckks_rescale_inplace, down to level 0 -> hegpu_ckks_mod_raise to plan->cts_level -> per CoeffToSlot factor the same
+ * pair -> hegpu_ckks_apply_galois (2N - 1, conj_key) -> hegpu_ckks_conj_real dropping one limb -> ONE hegpu_ckks_poly_eval
+ * of trig at batch `batch` into out.  Bit-identical to that chain of single entries (the sum: hegpu_addition).  No switch
+ * keys: a sparse secret is the caller's business.  out needs room for [2][out_level + 1 + rescale_after of trig's last
+ * step][N] per item and holds [2][out_level + 1][N] on return, at depth Q - 1 - out_level and scale plan->out_scale.
+ * HEGPU_E_INVALID before anything is queued, out untouched: a plan, trig plan or factor list that does not fit the context
+ * or one another, a workspace below hegpu_ckks_slim_bootstrap_workspace_bytes (0 for arguments it cannot size; it has no row
+ * in the HEGPU_OP_* table), out overlapping ct, ct2 or the workspace, ct2 overlapping the workspace, null pointers,
+ * batch < 1. */
+size_t hegpu_ckks_slim_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_slim_bootstrap_plan* plan,
+                                                 const hegpu_poly_step* trig, int n_steps, const hegpu_linear_factor* cts,
+                                                 int cts_count, const hegpu_linear_factor* stc, int stc_count, int batch);
+int hegpu_ckks_slim_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, const uint64_t* ct2,
+                              uint64_t ct2_stride, uint64_t* out, uint64_t out_stride,
+                              const hegpu_slim_bootstrap_plan* plan, const hegpu_poly_step* trig, int n_steps,
+                              const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc, int stc_count,
+                              const uint64_t* conj_key, const uint64_t* relin_key, int batch, void* ws, size_t ws_bytes,
+                              hegpu_stream stream);
 /* multiply_bfv (src/lib/host/bfv/operator.cu:336-430): coefficient domain,
  * ct [2][Q][N] x [2][Q][N] -> out [3][Q][N] */
 int hegpu_bfv_multiply(hegpu_context* ctx, const uint64_t* ct1, uint64_t ct1_stride, const uint64_t* ct2,

@@ -2347,6 +2347,30 @@ struct BootstrappingConfigV2 {
     }
 };
 
+// util/util.cuh:176-188, util/schemes.h:113-127: the configuration and the kinds of the reference's first bootstrapping
+// family.  Here slim, bit and gate bootstrapping run on the parts of the regular refresh: taylor_number_
+// and less_key_mode_ are validated and carried as the reference does, and not used -- EvalMod is the Chebyshev cosine
+// with K = 12, degree 30 and three double angles, and the rotations are the linear transforms' own.
+struct BootstrappingConfig {
+    int CtoS_piece_;      // Default: 3
+    int StoC_piece_;      // Default: 3
+    int taylor_number_;   // Default: 11
+    bool less_key_mode_;  // Default: false
+    BootstrappingConfig(int CtoS = 3, int StoC = 3, int taylor = 11, bool less_key_mode = false)
+        : CtoS_piece_(CtoS), StoC_piece_(StoC), taylor_number_(taylor), less_key_mode_(less_key_mode)
+    {
+        if (CtoS_piece_ < 2 || CtoS_piece_ > 5) throw std::out_of_range("CtoS_piece must be in range [2, 5]");
+        if (StoC_piece_ < 2 || StoC_piece_ > 5) throw std::out_of_range("StoC_piece must be in range [2, 5]");
+        if (taylor_number_ < 6 || taylor_number_ > 15) throw std::out_of_range("taylor_number must be in range [6, 15]");
+    }
+};
+enum class arithmetic_bootstrapping_type : std::uint8_t { NONE = 0x0, REGULAR_BOOTSTRAPPING = 0x1, SLIM_BOOTSTRAPPING = 0x2 };
+enum class logic_bootstrapping_type : std::uint8_t {
+    NONE = 0x0,
+    BIT_BOOTSTRAPPING = 0x1,  // scale = q0 / 2 (eprint 2024/767)
+    GATE_BOOTSTRAPPING = 0x2, // scale = q0 / 3
+};
+
 // ------------------------------------------------------------------ precision of decoded CKKS values
 // host/ckks/precision.cuh: per slot the distance of the real parts, of the imaginary parts and of the complex numbers
 // (l2); precision = log2(1 / delta).  The distributions (cdf_resol steps of 0.01 bit up to the best precision seen) count
@@ -2877,7 +2901,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
     void generate_bootstrapping_params_v2(const double scale, const BootstrappingConfigV2& config)
     {
         static_assert(S == Scheme::CKKS, "bootstrapping parameters are a CKKS matter");
-        if (boot_v2_.generated)
+        if (boot_v2_.generated || slim_.generated)
             throw std::runtime_error("Bootstrapping parameters is locked after generation and cannot be modified.");
         detail::require_generated(context_);
         const EvalModConfig& em = config.eval_mod_config_;
@@ -2937,8 +2961,8 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         boot_v2_ = std::move(b);
     }
     // every rotation of every factor: Galoiskey(context, bootstrapping_key_indexs()) is enough (the conjugation is in
-    // every Galoiskey)
-    std::vector<int> bootstrapping_key_indexs() const { return boot_v2_.key_indexs; }
+    // every Galoiskey); serves both parameter sets, of which one is generated
+    std::vector<int> bootstrapping_key_indexs() const { return slim_.generated ? slim_.key_indexs : boot_v2_.key_indexs; }
 
     // host/ckks/operator.cu:7147-7224 (hegpu_ckks_bootstrap): the refresh of a ciphertext at its last level.  The two switch
     // keys of mod_up_from_q0 (to an ephemeral sparse secret before the raise and back after it) are both given or both
@@ -2987,7 +3011,163 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         return result;
     }
 
+    // ---- the slim family (host/ckks/operator.cu:6800-6900, :7226-7330): SlotToCoeff first at the bottom
+    // of the chain, the raise, CoeffToSlot, the real parts, ONE polynomial alpha + A cos(2 pi (K u - phi)).
+    // Departures from the reference, which builds this family on its Taylor exp_scaled and v1 Vandermonde machinery:
+    //  * taylor_number_ and less_key_mode_ are carried and unused: the polynomial is the Chebyshev cosine with K = 12,
+    //    degree 30 and three double angles, the plan of hegpu_slim_bootstrap_plan_fill;
+    //  * the result's scale_ is the plan's out_scale (for slim: q_(eval level) / 256 to the rounding of doubles), not the
+    //    scale the parameters were generated for; its slots are (rho / 2 pi) sin(2 pi z / rho), rho = 256;
+    //  * CoeffToSlot spends CtoS_piece_ + 1 levels (its factors and the limb the real part drops), as in 4.5f;
+    //  * REGULAR_BOOTSTRAPPING through this call is not built (std::invalid_argument): the regular refresh is
+    //    generate_bootstrapping_params_v2 / regular_bootstrapping_v2.
+    // Locked after the first call, together with generate_bootstrapping_params_v2, as the reference's one flag does.
+    void generate_bootstrapping_params(const double scale, const BootstrappingConfig& config,
+                                       const arithmetic_bootstrapping_type& boot_type)
+    {
+        static_assert(S == Scheme::CKKS, "bootstrapping parameters are a CKKS matter");
+        if (boot_type == arithmetic_bootstrapping_type::REGULAR_BOOTSTRAPPING)
+            throw std::invalid_argument("REGULAR_BOOTSTRAPPING is not built on this parameter set: use "
+                                        "generate_bootstrapping_params_v2 and regular_bootstrapping_v2!");
+        if (boot_type != arithmetic_bootstrapping_type::SLIM_BOOTSTRAPPING) throw std::invalid_argument("Invalid Bootstrapping Type");
+        generate_slim_family_params(scale, config, 256.0, true);
+    }
+    Ciphertext<S> slim_bootstrapping(Ciphertext<S>& input1, Galoiskey<S>& galois_key, Relinkey<S>& relin_key,
+                                     const ExecutionOptions& options = ExecutionOptions())
+    {
+        return slim_family_bootstrapping(SLIM_FUNCTION, input1, nullptr, galois_key, relin_key, options);
+    }
+    // This backend's seam under slim_bootstrapping and HELogicOperator<CKKS>'s bit and gate bootstrapping: one parameter
+    // set per ratio q_0 / (scale of the raised coefficients) -- 256 slim, 2 bit, 3 gates -- and one plan per function.
+    enum { SLIM_FUNCTION = 0, BIT_FUNCTION, AND_FUNCTION, OR_FUNCTION, XOR_FUNCTION, NAND_FUNCTION, NOR_FUNCTION, XNOR_FUNCTION,
+           SLIM_FAMILY_SIZE };
+    void generate_slim_family_params(const double scale, const BootstrappingConfig& config, double ratio, bool arithmetic)
+    {
+        static_assert(S == Scheme::CKKS, "bootstrapping parameters are a CKKS matter");
+        if (boot_v2_.generated || slim_.generated)
+            throw std::runtime_error("Bootstrapping parameters is locked after generation and cannot be modified.");
+        detail::require_generated(context_);
+        const int Q = context_->Q_size;
+        std::vector<uint64_t> primes((size_t) Q);
+        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        // (phi, A, alpha) of alpha + A cos(2 pi (a / ratio - phi)), include/hegpu.h
+        static const double family[SLIM_FAMILY_SIZE][3] = {
+            {0.25, 1.0 / (2.0 * 3.14159265358979323846), 0.0}, {1.0 / 2, 1.0 / 2, 1.0 / 2},
+            {2.0 / 3, 2.0 / 3, 1.0 / 3}, {1.0 / 2, 2.0 / 3, 2.0 / 3}, {1.0 / 3, 2.0 / 3, 1.0 / 3},
+            {1.0 / 6, 2.0 / 3, 2.0 / 3}, {0.0, 2.0 / 3, 1.0 / 3},     {5.0 / 6, 2.0 / 3, 2.0 / 3}};
+        SlimBoot b;
+        for (int fn = 0; fn < SLIM_FAMILY_SIZE; fn++) {
+            const bool wanted = arithmetic ? fn == SLIM_FUNCTION : ratio == 2.0 ? fn == BIT_FUNCTION : fn >= AND_FUNCTION;
+            if (!wanted) continue;
+            hegpu_slim_bootstrap_config cfg{};
+            cfg.scale = scale;
+            cfg.ratio = ratio;
+            cfg.phase = family[fn][0];
+            cfg.amplitude = family[fn][1];
+            cfg.offset = family[fn][2];
+            cfg.K = 12;
+            cfg.degree = 30;
+            cfg.double_angle = 3;
+            cfg.cts_level = Q - 1;
+            cfg.cts_pieces = config.CtoS_piece_;
+            cfg.stc_pieces = config.StoC_piece_;
+            cfg.arithmetic = arithmetic ? 1 : 0;
+            hegpu_slim_bootstrap_plan& p = b.plan[fn];
+            detail::check(hegpu_slim_bootstrap_plan_fill(&cfg, primes.data(), Q, &p));
+            int n_steps = 0;
+            detail::check(hegpu_eval_trig_plan_size(p.K, p.degree, p.double_angle, p.phase, p.amplitude, p.offset, p.eval_level,
+                                                    p.eval_in_scale, p.eval_target_scale, primes.data(), Q, &n_steps));
+            b.trig[fn].resize((size_t) n_steps);
+            detail::check(hegpu_eval_trig_plan_fill(p.K, p.degree, p.double_angle, p.phase, p.amplitude, p.offset, p.eval_level,
+                                                    p.eval_in_scale, p.eval_target_scale, primes.data(), Q, b.trig[fn].data(),
+                                                    n_steps));
+            b.first = b.first < 0 ? fn : b.first;
+        }
+        // the factors depend on the function through its ratio alone: one set serves every plan of the set
+        const hegpu_slim_bootstrap_plan& p0 = b.plan[b.first];
+        HEEncoder<S> encoder(context_);
+        const int n = (int) context_->n, slots = n >> 1;
+        for (int inverse = 1; inverse >= 0; inverse--) {
+            const int pieces = inverse ? p0.cts_pieces : p0.stc_pieces;
+            const int first_level = inverse ? p0.cts_level : p0.in_level;
+            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
+            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
+            for (int p = 0; p < pieces; p++) {
+                std::vector<int> offsets(counts[p]);
+                std::vector<double> values((size_t) 2 * counts[p] * slots);
+                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
+                std::map<int, std::vector<Complex64>> diag;
+                for (int d = 0; d < counts[p]; d++) {
+                    std::vector<Complex64> v((size_t) slots);
+                    for (int t = 0; t < slots; t++)
+                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
+                    diag[offsets[d]] = std::move(v);
+                }
+                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder,
+                                                               inverse ? p0.cts_scale[p] : p0.stc_scale[p],
+                                                               Q - 1 - (first_level - p), 0, ExecutionOptions(), strides[p]);
+                for (int sh : lt->required_shifts())
+                    if (std::find(b.key_indexs.begin(), b.key_indexs.end(), sh) == b.key_indexs.end()) b.key_indexs.push_back(sh);
+                (inverse ? b.cts : b.stc).push_back(std::move(lt));
+            }
+        }
+        b.generated = true;
+        slim_ = std::move(b);
+    }
+    bool slim_family_generated() const { return slim_.generated; }
+    // input1 (and input2 for a gate) at level StoC_piece_: the reference's "Ciphertexts leveled should be at max!"
+    Ciphertext<S> slim_family_bootstrapping(int function, Ciphertext<S>& input1, Ciphertext<S>* input2, Galoiskey<S>& galois_key,
+                                            Relinkey<S>& relin_key, const ExecutionOptions& options = ExecutionOptions())
+    {
+        static_assert(S == Scheme::CKKS, "bootstrapping is a CKKS operation");
+        if (!slim_.generated || function < 0 || function >= SLIM_FAMILY_SIZE || slim_.trig[function].empty())
+            throw std::invalid_argument("Bootstrapping operation can not be performed before generating Bootstrapping parameters!");
+        const hegpu_slim_bootstrap_plan& p = slim_.plan[function];
+        for (Ciphertext<S>* in : {&input1, input2})
+            if (in && context_->Q_size - in->depth_ != 1 + p.stc_pieces) throw std::logic_error("Ciphertexts leveled should be at max!");
+        detail::OpScope storage_scope(options); // storage manager: stage HOST-stored operands, place the results
+        for (Ciphertext<S>* in : {&input1, input2}) {
+            if (!in) continue;
+            check_plain_two_part(*in);
+            if (!in->in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
+        }
+        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
+            throw std::invalid_argument("Relinkey does not belong to this context!");
+        FactorArgs fc(*this, slim_.cts, galois_key), fs(*this, slim_.stc, galois_key);
+        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
+        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        const std::vector<hegpu_poly_step>& trig = slim_.trig[function];
+        const int n_steps = (int) trig.size();
+        const hegpu_poly_step& last = trig.back();
+        detail::Workspace ws(hegpu_ckks_slim_bootstrap_workspace_bytes(context_->handle(), &p, trig.data(), n_steps, fc.f.data(),
+                                                                       p.cts_pieces, fs.f.data(), p.stc_pieces, 1),
+                             options.stream_);
+        DeviceVector<Data64> m(2 * context_->n * (size_t) (p.out_level + 1 + (last.rescale_after ? 1 : 0)), options.stream_);
+        detail::check(hegpu_ckks_slim_bootstrap(context_->handle(), (const uint64_t*) input1.data(), 0,
+                                                input2 ? (const uint64_t*) input2->data() : nullptr, 0, (uint64_t*) m.data(), 0,
+                                                &p, trig.data(), n_steps, fc.f.data(), p.cts_pieces, fs.f.data(), p.stc_pieces,
+                                                conj, (const uint64_t*) relin_key.data(), 1, ws.data(), ws.bytes,
+                                                options.stream_));
+        Ciphertext<S> result(context_);
+        emit(input1, result, std::move(m));
+        result.depth_ = context_->Q_size - 1 - p.out_level;
+        result.scale_ = p.out_scale;
+        result.rescale_required_ = false;
+        result.relinearization_required_ = false;
+        return result;
+    }
+
   private:
+    // what generate_slim_family_params leaves for slim_family_bootstrapping: a plan per function of the set, one set of factors
+    struct SlimBoot {
+        bool generated = false;
+        int first = -1;
+        hegpu_slim_bootstrap_plan plan[SLIM_FAMILY_SIZE]{};
+        std::vector<hegpu_poly_step> trig[SLIM_FAMILY_SIZE];
+        std::vector<std::shared_ptr<LinearTransform<S>>> cts, stc;
+        std::vector<int> key_indexs;
+    };
+    SlimBoot slim_;
     // what generate_bootstrapping_params_v2 leaves for regular_bootstrapping_v2
     struct BootV2 {
         bool generated = false;
@@ -4052,8 +4232,9 @@ template <> class HELogicOperator<Scheme::TFHE> { // host/tfhe/operator.cuh: boo
 //     sum at the product's level, so all of them work and leave at depth + 1.
 //  2. Its out-of-place one_minus_cipher (ckks/operator.cu:7329-7346, bfv/operator.cu:1520-1575) negates its INPUT in
 //     place.  Here inputs are never modified.
-//  3. The bootstrapped members (generate_bootstrapping_params, bit_bootstrapping, gate_bootstrapping and the
-//     *_approximation gates) are not provided, and not declared.
+//  3. Of the bootstrapped members, generate_bootstrapping_params, bootstrapping_key_indexs, bit_bootstrapping,
+//     gate_bootstrapping and the six *_bootstrapping gates are provided on the parts of the regular refresh (DESIGN.md
+//     4.5g).  The *_approximation gates are not declared: they take a mid-pipeline ciphertext that does not exist here.
 namespace detail {
 template <Scheme S> class LogicOperatorBase {
   public:
@@ -4189,8 +4370,74 @@ template <> class HELogicOperator<Scheme::CKKS> : public detail::LogicOperatorBa
     void mod_drop(Plaintext<S>& p, Plaintext<S>& out, const ExecutionOptions& o = ExecutionOptions()) { arithmetic_.mod_drop(p, out, o); }
     void mod_drop_inplace(Plaintext<S>& p, const ExecutionOptions& o = ExecutionOptions()) { arithmetic_.mod_drop_inplace(p, o); }
 
+
+    // ---- bit and gate bootstrapping (host/ckks/operator.cuh:3255-3449, eprint 2024/767): the slim
+    // sequence of the arithmetic operator with ratio 2 (bit) or 3 (gates) and the function's cosine.  The reference's
+    // checks and texts are kept; its departures are HEArithmeticOperator::generate_bootstrapping_params's.  The
+    // *_approximation members stay undeclared: they take a mid-pipeline ciphertext that does not exist here.
+    void generate_bootstrapping_params(const double scale, const BootstrappingConfig& config,
+                                       const logic_bootstrapping_type& boot_type)
+    {
+        if (arithmetic_.slim_family_generated())
+            throw std::runtime_error("Bootstrapping parameters is locked after generation and cannot be modified.");
+        const int division = static_cast<int>(std::round(static_cast<double>(context_->prime_vector_[0].value) / scale));
+        switch (static_cast<int>(boot_type)) {
+            case 1: // BIT_BOOTSTRAPPING
+                if (division != 2)
+                    throw std::invalid_argument("Bootstrapping parameters can not be generated, because of context is not "
+                                                "suitable for Bit Bootstrapping. Last modulus should be 2*scale!");
+                break;
+            case 2: // GATE_BOOTSTRAPPING
+                if (division != 3)
+                    throw std::invalid_argument("Bootstrapping parameters can not be generated, because of context is not "
+                                                "suitable for Gate Bootstrapping. Last modulus should be 3*scale!");
+                break;
+            default:
+                throw std::invalid_argument("Invalid Bootstrapping Type");
+        }
+        arithmetic_.generate_slim_family_params(scale, config, (double) division, false);
+        boot_type_ = boot_type;
+    }
+    std::vector<int> bootstrapping_key_indexs()
+    {
+        if (!arithmetic_.slim_family_generated())
+            throw std::invalid_argument("Bootstrapping key indexs can not be returned before generating Bootstrapping parameters!");
+        return arithmetic_.bootstrapping_key_indexs();
+    }
+    Ciphertext<S> bit_bootstrapping(Ciphertext<S>& input1, Galoiskey<S>& galois_key, Relinkey<S>& relin_key,
+                                    const ExecutionOptions& options = ExecutionOptions())
+    {
+        if (boot_type_ != logic_bootstrapping_type::BIT_BOOTSTRAPPING)
+            throw std::invalid_argument("Bootstrapping operation can not be performed before generating Bootstrapping parameters!");
+        return arithmetic_.slim_family_bootstrapping(HEArithmeticOperator<S>::BIT_FUNCTION, input1, nullptr, galois_key, relin_key,
+                                                     options);
+    }
+#define HEONGPU_GATE_BOOTSTRAPPING(NAME)                                                                                   \
+    Ciphertext<S> NAME##_bootstrapping(Ciphertext<S>& input1, Ciphertext<S>& input2, Galoiskey<S>& galois_key,             \
+                                       Relinkey<S>& relin_key, const ExecutionOptions& options = ExecutionOptions())       \
+    {                                                                                                                      \
+        return gate_bootstrapping(logic_gate::NAME, input1, input2, galois_key, relin_key, options);                      \
+    }
+    HEONGPU_GATE_BOOTSTRAPPING(AND)
+    HEONGPU_GATE_BOOTSTRAPPING(OR)
+    HEONGPU_GATE_BOOTSTRAPPING(XOR)
+    HEONGPU_GATE_BOOTSTRAPPING(NAND)
+    HEONGPU_GATE_BOOTSTRAPPING(NOR)
+    HEONGPU_GATE_BOOTSTRAPPING(XNOR)
+#undef HEONGPU_GATE_BOOTSTRAPPING
+
   private:
+    enum class logic_gate { AND, OR, XOR, NAND, NOR, XNOR };
+    Ciphertext<S> gate_bootstrapping(logic_gate gate_type, Ciphertext<S>& input1, Ciphertext<S>& input2, Galoiskey<S>& galois_key,
+                                     Relinkey<S>& relin_key, const ExecutionOptions& options = ExecutionOptions())
+    {
+        if (boot_type_ != logic_bootstrapping_type::GATE_BOOTSTRAPPING)
+            throw std::invalid_argument("Bootstrapping operation can not be performed before generating Bootstrapping parameters!");
+        return arithmetic_.slim_family_bootstrapping(HEArithmeticOperator<S>::AND_FUNCTION + static_cast<int>(gate_type), input1,
+                                                     &input2, galois_key, relin_key, options);
+    }
     HEArithmeticOperator<S> arithmetic_;
+    logic_bootstrapping_type boot_type_ = logic_bootstrapping_type::NONE;
 };
 
 // ------------------------------------------------------------------ serializer (util/serializer.h:20-131)
