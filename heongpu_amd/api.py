@@ -1083,6 +1083,22 @@ POLY_TAIL_NONE, POLY_TAIL_ONE = -1, -2
 PolyEvalPlan = collections.namedtuple("PolyEvalPlan", "steps level scale out_limbs")
 
 
+def _primes_array(primes):
+    """primes as the (uint64 array, count) pair the host-only planners end their arguments with"""
+    pr = [int(p) for p in primes]
+    return (ctypes.c_uint64 * max(len(pr), 1))(*pr), len(pr)
+
+
+def _step_plan(size, fill, *args):
+    """One _size / _fill pair of the C ABI over the arguments the two share, as a PolyEvalPlan."""
+    count = ctypes.c_int(0)
+    _check(size(*args, ctypes.byref(count)))
+    steps = (_lib.PolyStep * count.value)()
+    _check(fill(*args, steps, count.value))
+    last = steps[count.value - 1]
+    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+
+
 def poly_eval_plan(basis, coeffs, level, scale, target_scale, primes, max_deg=None, lead=True):
     """The evaluation order of sum_i coeffs[i] b_i(x) on a CKKS ciphertext (host only; hegpu_poly_eval_plan_size / _fill),
     b_i = x^i (MONOMIAL) or T_i (CHEBYSHEV, x in [-1, 1]): the reference's baby-step/giant-step schedule.  level / scale:
@@ -1096,17 +1112,10 @@ def poly_eval_plan(basis, coeffs, level, scale, target_scale, primes, max_deg=No
                  step rescales)"""
     lib = _lib.load()
     c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.complex128).reshape(-1))
-    pr = [int(p) for p in primes]
-    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    arr, n_primes = _primes_array(primes)
     md = len(c) - 1 if max_deg is None else int(max_deg)
-    args = (int(basis), c.ctypes.data, len(c), md, int(bool(lead)), int(level), float(scale), float(target_scale), arr,
-            len(pr))
-    count = ctypes.c_int(0)
-    _check(lib.hegpu_poly_eval_plan_size(*args, ctypes.byref(count)))
-    steps = (_lib.PolyStep * count.value)()
-    _check(lib.hegpu_poly_eval_plan_fill(*args, steps, count.value))
-    last = steps[count.value - 1]
-    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+    return _step_plan(lib.hegpu_poly_eval_plan_size, lib.hegpu_poly_eval_plan_fill, int(basis), c.ctypes.data, len(c), md,
+                      int(bool(lead)), int(level), float(scale), float(target_scale), arr, n_primes)
 
 
 def eval_mod_plan(K, degree, double_angle, level, scale, target_scale, primes):
@@ -1115,28 +1124,30 @@ def eval_mod_plan(K, degree, double_angle, level, scale, target_scale, primes):
     Chebyshev interpolant of (1 / 2 pi)^(1 / 2^r) cos(2 pi (K u - 1/4) / 2^r), r = double_angle, and then r double-angle
     steps, which leaves sin(2 pi eps) / 2 pi at target_scale.  Returns a PolyEvalPlan like poly_eval_plan."""
     lib = _lib.load()
-    pr = [int(p) for p in primes]
-    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
-    args = (int(K), int(degree), int(double_angle), int(level), float(scale), float(target_scale), arr, len(pr))
-    count = ctypes.c_int(0)
-    _check(lib.hegpu_eval_mod_plan_size(*args, ctypes.byref(count)))
-    steps = (_lib.PolyStep * count.value)()
-    _check(lib.hegpu_eval_mod_plan_fill(*args, steps, count.value))
-    last = steps[count.value - 1]
-    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+    arr, n_primes = _primes_array(primes)
+    return _step_plan(lib.hegpu_eval_mod_plan_size, lib.hegpu_eval_mod_plan_fill, int(K), int(degree), int(double_angle),
+                      int(level), float(scale), float(target_scale), arr, n_primes)
 
 
-class BootstrapPlan:
+class _RefreshPlan:
+    """What the plans of the refreshes share: c is the C struct; the other attributes are c's fields, arrays cut to their
+    piece counts."""
+
+    def __init__(self, c):
+        self.c = c
+        for name, _t in c._fields_:
+            setattr(self, name, getattr(c, name))
+        self.cts_scale, self.cts_label = list(c.cts_scale)[:c.cts_pieces], list(c.cts_label)[:c.cts_pieces]
+        self.stc_scale, self.stc_label = list(c.stc_scale)[:c.stc_pieces], list(c.stc_label)[:c.stc_pieces]
+
+
+class BootstrapPlan(_RefreshPlan):
     """The plan of the CKKS refresh (bootstrap_plan): c is the hegpu_bootstrap_plan, eval_mod the EvalMod PolyEvalPlan it
     names; the other attributes are c's fields, arrays cut to their piece counts."""
 
     def __init__(self, c, eval_mod):
-        self.c, self.eval_mod = c, eval_mod
-        for name, _t in c._fields_:
-            setattr(self, name, getattr(c, name))
-        self.k1 = int(c.k1)
-        self.cts_scale, self.cts_label = list(c.cts_scale)[:c.cts_pieces], list(c.cts_label)[:c.cts_pieces]
-        self.stc_scale, self.stc_label = list(c.stc_scale)[:c.stc_pieces], list(c.stc_label)[:c.stc_pieces]
+        super().__init__(c)
+        self.eval_mod, self.k1 = eval_mod, int(c.k1)
 
 
 def bootstrap_plan(primes, scale, cts_level, cts_pieces=3, stc_pieces=3, message_ratio=256.0, K=16, sine_degree=30,
@@ -1147,14 +1158,13 @@ def bootstrap_plan(primes, scale, cts_level, cts_pieces=3, stc_pieces=3, message
     multiplied by), raise_scale, cts_scale / stc_scale (what each factor's diagonals are encoded at), eval_level, stc_level,
     out_level, out_scale, eval_mod."""
     lib = _lib.load()
-    pr = [int(p) for p in primes]
-    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    arr, n_primes = _primes_array(primes)
     cfg = _lib.BootstrapConfig(float(scale), float(message_ratio), int(K), int(sine_degree), int(double_angle), int(cts_level),
                                int(cts_pieces), int(eval_level), int(stc_level), int(stc_pieces))
     c = _lib.BootstrapPlan()
-    _check(lib.hegpu_bootstrap_plan_fill(ctypes.byref(cfg), arr, len(pr), ctypes.byref(c)))
+    _check(lib.hegpu_bootstrap_plan_fill(ctypes.byref(cfg), arr, n_primes, ctypes.byref(c)))
     return BootstrapPlan(c, eval_mod_plan(c.K, c.sine_degree, c.double_angle, c.eval_level, c.eval_in_scale,
-                                          c.eval_target_scale, pr))
+                                          c.eval_target_scale, arr[:n_primes]))
 
 
 def eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes):
@@ -1162,16 +1172,9 @@ def eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, sca
     _fill): the interpolant of amplitude^(1 / 2^r) cos(2 pi (K u - phase) / 2^r), r double-angle steps, the last one's tail
     constant amplitude - offset.  eval_mod_plan is (1/4, 1 / 2 pi, 0).  Returns a PolyEvalPlan like poly_eval_plan."""
     lib = _lib.load()
-    pr = [int(p) for p in primes]
-    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
-    args = (int(K), int(degree), int(double_angle), float(phase), float(amplitude), float(offset), int(level), float(scale),
-            float(target_scale), arr, len(pr))
-    count = ctypes.c_int(0)
-    _check(lib.hegpu_eval_trig_plan_size(*args, ctypes.byref(count)))
-    steps = (_lib.PolyStep * count.value)()
-    _check(lib.hegpu_eval_trig_plan_fill(*args, steps, count.value))
-    last = steps[count.value - 1]
-    return PolyEvalPlan(steps, last.level, last.scale, last.level + 1 + last.rescale_after)
+    arr, n_primes = _primes_array(primes)
+    return _step_plan(lib.hegpu_eval_trig_plan_size, lib.hegpu_eval_trig_plan_fill, int(K), int(degree), int(double_angle),
+                      float(phase), float(amplitude), float(offset), int(level), float(scale), float(target_scale), arr, n_primes)
 
 
 # (ratio, phase, amplitude, offset) of the slim family: alpha + A cos(2 pi (a / ratio - phi)); ratio None: the caller's
@@ -1187,16 +1190,13 @@ SLIM_FUNCTIONS = {
 }
 
 
-class SlimBootstrapPlan:
+class SlimBootstrapPlan(_RefreshPlan):
     """The plan of a slim, bit or gate refresh (slim_bootstrap_plan): c is the hegpu_slim_bootstrap_plan, trig the
     PolyEvalPlan it names; the other attributes are c's fields, arrays cut to their piece counts."""
 
     def __init__(self, c, trig):
-        self.c, self.trig = c, trig
-        for name, _t in c._fields_:
-            setattr(self, name, getattr(c, name))
-        self.cts_scale, self.cts_label = list(c.cts_scale)[:c.cts_pieces], list(c.cts_label)[:c.cts_pieces]
-        self.stc_scale, self.stc_label = list(c.stc_scale)[:c.stc_pieces], list(c.stc_label)[:c.stc_pieces]
+        super().__init__(c)
+        self.trig = trig
 
 
 def slim_bootstrap_plan(primes, scale, cts_level, function="slim", cts_pieces=3, stc_pieces=3, ratio=256.0, K=12, degree=30,
@@ -1207,17 +1207,16 @@ def slim_bootstrap_plan(primes, scale, cts_level, function="slim", cts_pieces=3,
     tuple; ratio: for "slim" only.  Returns a SlimBootstrapPlan: in_level, stc_scale / cts_scale (what each factor's diagonals
     are encoded at), raise_scale, eval_level, out_level, out_scale, trig."""
     lib = _lib.load()
-    pr = [int(p) for p in primes]
-    arr = (ctypes.c_uint64 * max(len(pr), 1))(*pr)
+    arr, n_primes = _primes_array(primes)
     arithmetic = function == "slim"
     rho, phase, amplitude, offset = SLIM_FUNCTIONS[function] if isinstance(function, str) else function
     cfg = _lib.SlimBootstrapConfig(float(scale), float(ratio if rho is None else rho), float(phase), float(amplitude),
                                    float(offset), int(K), int(degree), int(double_angle), int(cts_level), int(cts_pieces),
                                    int(stc_pieces), int(arithmetic), 0)
     c = _lib.SlimBootstrapPlan()
-    _check(lib.hegpu_slim_bootstrap_plan_fill(ctypes.byref(cfg), arr, len(pr), ctypes.byref(c)))
+    _check(lib.hegpu_slim_bootstrap_plan_fill(ctypes.byref(cfg), arr, n_primes, ctypes.byref(c)))
     return SlimBootstrapPlan(c, eval_trig_plan(c.K, c.degree, c.double_angle, c.phase, c.amplitude, c.offset, c.eval_level,
-                                               c.eval_in_scale, c.eval_target_scale, pr))
+                                               c.eval_in_scale, c.eval_target_scale, arr[:n_primes]))
 
 
 def ks_launch_forms():

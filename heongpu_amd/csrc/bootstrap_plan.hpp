@@ -15,6 +15,7 @@
 //   merge  drops one limb; SlotToCoeff, factor g encoded at stc_scale[g]  label D at out_level
 //          = (D / stc_in_scale)^(1/P) q_(stc_level - 1 - g)
 #pragma once
+#include "../../include/hegpu.h"
 #include <cstdint>
 #include <vector>
 
@@ -23,34 +24,16 @@ namespace host {
 
 constexpr int BOOTSTRAP_MAX_PIECES = 5; // the factorisation of the special FFT has 2 .. 5 pieces (encoding_transform.hpp)
 
-// The layouts are the C ABI's hegpu_bootstrap_config / hegpu_bootstrap_plan (include/hegpu.h), field for field.
-struct BootstrapConfig {
-    double scale;         // D, the caller's scale
-    double message_ratio; // q_0 / D' aimed at (EvalModConfig::message_ratio_, default 256)
-    int32_t K;            // the raise's overflow I stays below K in magnitude (EvalModConfig::K_, default 16)
-    int32_t sine_degree;  // EvalModConfig::sine_deg_, default 30
-    int32_t double_angle; // EvalModConfig::double_angle_, default 3
-    int32_t cts_level;    // EncodingMatrixConfig::level_start_ of CoeffToSlot: the level the raise goes to
-    int32_t cts_pieces;
-    int32_t eval_level;   // EvalModConfig::level_start_
-    int32_t stc_level;    // EncodingMatrixConfig::level_start_ of SlotToCoeff (the merge drops to stc_level - 1)
-    int32_t stc_pieces;
-};
-
-struct BootstrapPlan {
-    uint64_t k1;
-    int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces, out_level;
-    int32_t K, sine_degree, double_angle;
-    int32_t reserved;
-    double raise_scale;                      // q_0 K
-    double cts_scale[BOOTSTRAP_MAX_PIECES];  // the scale factor f's diagonals are encoded at (level cts_level - f)
-    double cts_label[BOOTSTRAP_MAX_PIECES];  // the ciphertext's label after factor f and its rescale
-    double eval_in_scale, eval_target_scale, eval_out_scale;
-    double stc_in_scale;                     // the relabelled result of EvalMod
-    double stc_scale[BOOTSTRAP_MAX_PIECES];  // factor g's diagonals (level stc_level - 1 - g)
-    double stc_label[BOOTSTRAP_MAX_PIECES];
-    double out_scale;                        // D to the rounding of doubles
-};
+// The configs and plans are the C ABI's structs (include/hegpu.h states every field).
+using BootstrapConfig = ::hegpu_bootstrap_config;
+using BootstrapPlan = ::hegpu_bootstrap_plan;
+using SlimBootstrapConfig = ::hegpu_slim_bootstrap_config;
+using SlimBootstrapPlan = ::hegpu_slim_bootstrap_plan;
+static_assert(sizeof(BootstrapPlan::cts_scale) == BOOTSTRAP_MAX_PIECES * sizeof(double) &&
+                  sizeof(BootstrapPlan::stc_label) == BOOTSTRAP_MAX_PIECES * sizeof(double) &&
+                  sizeof(SlimBootstrapPlan::stc_scale) == BOOTSTRAP_MAX_PIECES * sizeof(double) &&
+                  sizeof(SlimBootstrapPlan::cts_label) == BOOTSTRAP_MAX_PIECES * sizeof(double),
+              "the plans of hegpu.h hold BOOTSTRAP_MAX_PIECES factors per transform");
 
 // std::invalid_argument: fewer levels than P_cts + 1 + bit_length(degree) + r + 1 + P_stc and one limb left, start levels
 // that do not follow from one another, K < 1, ratio D > q_0, a scale or ratio that is not positive and finite, a piece
@@ -67,31 +50,6 @@ BootstrapPlan bootstrap_plan(const BootstrapConfig& cfg, const std::vector<uint6
 //   CoeffToSlot as above, then conj, then x + conj x dropping a limb    slot j holds u_j (real), level eval_level
 //   trig plan (K, degree, r, phase, amplitude, offset)              offset + amplitude cos(2 pi (a / ratio - phase))
 //   out    at out_level = eval_level - bit_length(degree) - r, labelled eval_out_scale (/ ratio if `arithmetic`)
-// The layouts are the C ABI's hegpu_slim_bootstrap_config / hegpu_slim_bootstrap_plan, field for field.
-struct SlimBootstrapConfig {
-    double scale;      // D, the caller's scale
-    double ratio;      // q_0 / (the scale of the coefficients at the raise): 256 by default for slim, 2 for bits, 3 for gates
-    double phase, amplitude, offset;
-    int32_t K, degree, double_angle;
-    int32_t cts_level, cts_pieces, stc_pieces;
-    int32_t arithmetic; // 1: the result is relabelled by 1 / ratio (slim); 0: it is the function's value (bit, gates)
-    int32_t reserved;
-};
-
-struct SlimBootstrapPlan {
-    int32_t in_level, stc_pieces, cts_level, cts_pieces, eval_level, out_level;
-    int32_t K, degree, double_angle;
-    int32_t reserved;
-    double stc_scale[BOOTSTRAP_MAX_PIECES]; // factor g's diagonals (level in_level - g)
-    double stc_label[BOOTSTRAP_MAX_PIECES];
-    double raise_scale;                     // q_0 K
-    double cts_scale[BOOTSTRAP_MAX_PIECES];
-    double cts_label[BOOTSTRAP_MAX_PIECES];
-    double ratio, phase, amplitude, offset;
-    double eval_in_scale, eval_target_scale, eval_out_scale;
-    double out_scale;
-};
-
 // std::invalid_argument: fewer levels than P_cts + 1 + bit_length(degree) + r and one limb left, a chain of fewer than
 // P_stc + 1 limbs, ratio < 2, a piece count outside [2, 5], a factor scale below 1, a scale that is not positive and
 // finite, what eval_trig_plan refuses.

@@ -17,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 #include <cstring>
+#include <functional>
 #include <sys/random.h>
 #include <memory>
 #include <new>
@@ -519,10 +520,36 @@ int hegpu_encoding_transform_fill(int coeff_count, int inverse, int pieces, int 
     });
 }
 
-// host only: the evaluation order of a polynomial on a ciphertext (poly_eval.hpp)
-static_assert(sizeof(hegpu_poly_step) == sizeof(host::PolyStep) && offsetof(hegpu_poly_step, w) == offsetof(host::PolyStep, w) &&
-                  offsetof(hegpu_poly_step, scale) == offsetof(host::PolyStep, scale),
-              "hegpu_poly_step is host::PolyStep");
+// host only: the step plans (poly_eval.hpp) and the refresh plans (bootstrap_plan.hpp).  The three step-plan families
+// share one size and one fill: `make` is the family's planner over the caller's arguments, `who` the name in the messages.
+using MakePlan = std::function<std::vector<host::PolyStep>()>;
+static int plan_size(const MakePlan& make, const char* who, int* n_steps)
+{
+    return guarded([&]() -> int {
+        if (!n_steps) return fail(HEGPU_E_INVALID, std::string(who) + "_size: null argument");
+        *n_steps = (int) make().size();
+        return 0;
+    });
+}
+
+static int plan_fill(const MakePlan& make, const char* who, hegpu_poly_step* steps, int n_steps)
+{
+    return guarded([&]() -> int {
+        if (!steps) return fail(HEGPU_E_INVALID, std::string(who) + "_fill: null argument");
+        const std::vector<host::PolyStep> plan = make();
+        if (n_steps != (int) plan.size())
+            return fail(HEGPU_E_INVALID, std::string(who) + "_fill: n_steps is not what hegpu_" + who + "_size gives");
+        std::copy(plan.begin(), plan.end(), steps);
+        return 0;
+    });
+}
+
+static std::vector<uint64_t> primes_of(const uint64_t* primes, int n_primes, const char* who)
+{
+    if (!primes || n_primes < 1) throw std::invalid_argument(std::string(who) + ": null argument");
+    return std::vector<uint64_t>(primes, primes + n_primes);
+}
+
 static std::vector<host::PolyStep> poly_plan_of(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level,
                                                 double scale, double target_scale, const uint64_t* primes, int n_primes)
 {
@@ -537,138 +564,65 @@ static std::vector<host::PolyStep> poly_plan_of(int basis, const double* coeffs,
 int hegpu_poly_eval_plan_size(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
                               double target_scale, const uint64_t* primes, int n_primes, int* n_steps)
 {
-    return guarded([&]() -> int {
-        if (!n_steps) return fail(HEGPU_E_INVALID, "poly_eval_plan_size: null argument");
-        const std::vector<host::PolyStep> plan =
-            poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes);
-        *n_steps = (int) plan.size();
-        return 0;
-    });
+    return plan_size([&] { return poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes); },
+                     "poly_eval_plan", n_steps);
 }
 
 int hegpu_poly_eval_plan_fill(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
                               double target_scale, const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps)
 {
-    return guarded([&]() -> int {
-        if (!steps) return fail(HEGPU_E_INVALID, "poly_eval_plan_fill: null argument");
-        const std::vector<host::PolyStep> plan =
-            poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes);
-        if (n_steps != (int) plan.size())
-            return fail(HEGPU_E_INVALID, "poly_eval_plan_fill: n_steps is not what hegpu_poly_eval_plan_size gives");
-        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
-        return 0;
-    });
-}
-
-// host only: EvalMod as a plan (poly_eval.hpp)
-static std::vector<host::PolyStep> eval_mod_plan_of(int K, int degree, int double_angle, int level, double scale,
-                                                    double target_scale, const uint64_t* primes, int n_primes)
-{
-    if (!primes || n_primes < 1) throw std::invalid_argument("eval_mod_plan: null argument");
-    return host::eval_mod_plan(K, degree, double_angle, level, scale, target_scale,
-                               std::vector<uint64_t>(primes, primes + n_primes));
+    return plan_fill([&] { return poly_plan_of(basis, coeffs, n_coeffs, max_deg, lead, level, scale, target_scale, primes, n_primes); },
+                     "poly_eval_plan", steps, n_steps);
 }
 
 int hegpu_eval_mod_plan_size(int K, int degree, int double_angle, int level, double scale, double target_scale,
                              const uint64_t* primes, int n_primes, int* n_steps)
 {
-    return guarded([&]() -> int {
-        if (!n_steps) return fail(HEGPU_E_INVALID, "eval_mod_plan_size: null argument");
-        const std::vector<host::PolyStep> plan =
-            eval_mod_plan_of(K, degree, double_angle, level, scale, target_scale, primes, n_primes);
-        *n_steps = (int) plan.size();
-        return 0;
-    });
+    return plan_size([&] { return host::eval_mod_plan(K, degree, double_angle, level, scale, target_scale,
+                                                      primes_of(primes, n_primes, "eval_mod_plan")); },
+                     "eval_mod_plan", n_steps);
 }
 
 int hegpu_eval_mod_plan_fill(int K, int degree, int double_angle, int level, double scale, double target_scale,
                              const uint64_t* primes, int n_primes, hegpu_poly_step* steps, int n_steps)
 {
-    return guarded([&]() -> int {
-        if (!steps) return fail(HEGPU_E_INVALID, "eval_mod_plan_fill: null argument");
-        const std::vector<host::PolyStep> plan =
-            eval_mod_plan_of(K, degree, double_angle, level, scale, target_scale, primes, n_primes);
-        if (n_steps != (int) plan.size())
-            return fail(HEGPU_E_INVALID, "eval_mod_plan_fill: n_steps is not what hegpu_eval_mod_plan_size gives");
-        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
-        return 0;
-    });
-}
-
-// host only: the scale labels of the CKKS refresh (bootstrap_plan.hpp)
-static_assert(sizeof(hegpu_bootstrap_config) == sizeof(host::BootstrapConfig) && sizeof(hegpu_bootstrap_plan) == sizeof(host::BootstrapPlan) &&
-                  offsetof(hegpu_bootstrap_config, cts_level) == offsetof(host::BootstrapConfig, cts_level) &&
-                  offsetof(hegpu_bootstrap_plan, raise_scale) == offsetof(host::BootstrapPlan, raise_scale) &&
-                  offsetof(hegpu_bootstrap_plan, eval_in_scale) == offsetof(host::BootstrapPlan, eval_in_scale) &&
-                  offsetof(hegpu_bootstrap_plan, out_scale) == offsetof(host::BootstrapPlan, out_scale),
-              "hegpu_bootstrap_config / _plan are host::BootstrapConfig / BootstrapPlan");
-int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64_t* primes, int n_primes, hegpu_bootstrap_plan* plan)
-{
-    return guarded([&]() -> int {
-        if (!config || !primes || !plan || n_primes < 1) return fail(HEGPU_E_INVALID, "bootstrap_plan_fill: null argument");
-        host::BootstrapConfig cfg;
-        std::memcpy(&cfg, config, sizeof(cfg));
-        const host::BootstrapPlan pl = host::bootstrap_plan(cfg, std::vector<uint64_t>(primes, primes + n_primes));
-        std::memcpy(plan, &pl, sizeof(pl));
-        return 0;
-    });
-}
-
-// host only: the cosine with a phase and an offset (poly_eval.hpp) and the plan of the slim refreshes (bootstrap_plan.hpp)
-static std::vector<host::PolyStep> eval_trig_plan_of(int K, int degree, int double_angle, double phase, double amplitude,
-                                                     double offset, int level, double scale, double target_scale,
-                                                     const uint64_t* primes, int n_primes)
-{
-    if (!primes || n_primes < 1) throw std::invalid_argument("eval_trig_plan: null argument");
-    return host::eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale,
-                                std::vector<uint64_t>(primes, primes + n_primes));
+    return plan_fill([&] { return host::eval_mod_plan(K, degree, double_angle, level, scale, target_scale,
+                                                      primes_of(primes, n_primes, "eval_mod_plan")); },
+                     "eval_mod_plan", steps, n_steps);
 }
 
 int hegpu_eval_trig_plan_size(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
                               double scale, double target_scale, const uint64_t* primes, int n_primes, int* n_steps)
 {
-    return guarded([&]() -> int {
-        if (!n_steps) return fail(HEGPU_E_INVALID, "eval_trig_plan_size: null argument");
-        const std::vector<host::PolyStep> plan =
-            eval_trig_plan_of(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes, n_primes);
-        *n_steps = (int) plan.size();
-        return 0;
-    });
+    return plan_size([&] { return host::eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale,
+                                                       primes_of(primes, n_primes, "eval_trig_plan")); },
+                     "eval_trig_plan", n_steps);
 }
 
 int hegpu_eval_trig_plan_fill(int K, int degree, int double_angle, double phase, double amplitude, double offset, int level,
                               double scale, double target_scale, const uint64_t* primes, int n_primes,
                               hegpu_poly_step* steps, int n_steps)
 {
+    return plan_fill([&] { return host::eval_trig_plan(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale,
+                                                       primes_of(primes, n_primes, "eval_trig_plan")); },
+                     "eval_trig_plan", steps, n_steps);
+}
+
+int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64_t* primes, int n_primes, hegpu_bootstrap_plan* plan)
+{
     return guarded([&]() -> int {
-        if (!steps) return fail(HEGPU_E_INVALID, "eval_trig_plan_fill: null argument");
-        const std::vector<host::PolyStep> plan =
-            eval_trig_plan_of(K, degree, double_angle, phase, amplitude, offset, level, scale, target_scale, primes, n_primes);
-        if (n_steps != (int) plan.size())
-            return fail(HEGPU_E_INVALID, "eval_trig_plan_fill: n_steps is not what hegpu_eval_trig_plan_size gives");
-        std::memcpy(steps, plan.data(), plan.size() * sizeof(host::PolyStep));
+        if (!config || !primes || !plan || n_primes < 1) return fail(HEGPU_E_INVALID, "bootstrap_plan_fill: null argument");
+        *plan = host::bootstrap_plan(*config, std::vector<uint64_t>(primes, primes + n_primes));
         return 0;
     });
 }
 
-static_assert(sizeof(hegpu_slim_bootstrap_config) == sizeof(host::SlimBootstrapConfig) &&
-                  sizeof(hegpu_slim_bootstrap_plan) == sizeof(host::SlimBootstrapPlan) &&
-                  offsetof(hegpu_slim_bootstrap_config, cts_level) == offsetof(host::SlimBootstrapConfig, cts_level) &&
-                  offsetof(hegpu_slim_bootstrap_config, arithmetic) == offsetof(host::SlimBootstrapConfig, arithmetic) &&
-                  offsetof(hegpu_slim_bootstrap_plan, raise_scale) == offsetof(host::SlimBootstrapPlan, raise_scale) &&
-                  offsetof(hegpu_slim_bootstrap_plan, ratio) == offsetof(host::SlimBootstrapPlan, ratio) &&
-                  offsetof(hegpu_slim_bootstrap_plan, eval_in_scale) == offsetof(host::SlimBootstrapPlan, eval_in_scale) &&
-                  offsetof(hegpu_slim_bootstrap_plan, out_scale) == offsetof(host::SlimBootstrapPlan, out_scale),
-              "hegpu_slim_bootstrap_config / _plan are host::SlimBootstrapConfig / SlimBootstrapPlan");
 int hegpu_slim_bootstrap_plan_fill(const hegpu_slim_bootstrap_config* config, const uint64_t* primes, int n_primes,
                                    hegpu_slim_bootstrap_plan* plan)
 {
     return guarded([&]() -> int {
         if (!config || !primes || !plan || n_primes < 1) return fail(HEGPU_E_INVALID, "slim_bootstrap_plan_fill: null argument");
-        host::SlimBootstrapConfig cfg;
-        std::memcpy(&cfg, config, sizeof(cfg));
-        const host::SlimBootstrapPlan pl = host::slim_bootstrap_plan(cfg, std::vector<uint64_t>(primes, primes + n_primes));
-        std::memcpy(plan, &pl, sizeof(pl));
+        *plan = host::slim_bootstrap_plan(*config, std::vector<uint64_t>(primes, primes + n_primes));
         return 0;
     });
 }
@@ -1303,11 +1257,10 @@ size_t hegpu_ckks_poly_eval_workspace_bytes(const hegpu_context* ctx, const hegp
                                             int batch)
 {
     if (!ctx || batch <= 0 || ctx->c.scheme != SCHEME_CKKS) return 0;
-    const host::PolyStep* p = reinterpret_cast<const host::PolyStep*>(plan);
     size_t bytes = 0;
     (void) guarded([&]() -> int { // no exception may cross the C boundary (the check keeps tables of n_steps entries)
-        if (!ops_poly_eval_check(ctx->c, p, n_steps, depth))
-            bytes = ops_poly_eval_workspace_elems(ctx->c, p, n_steps, depth, batch) * sizeof(u64);
+        if (!ops_poly_eval_check(ctx->c, plan, n_steps, depth))
+            bytes = ops_poly_eval_workspace_elems(ctx->c, plan, n_steps, depth, batch) * sizeof(u64);
         return 0;
     });
     return bytes;
@@ -1321,18 +1274,17 @@ int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
     if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (int r = check_items(batch, 2, "poly_eval")) return r;
     if (!ct || !out || !plan || !relin_key || !ws) return fail(HEGPU_E_INVALID, "poly_eval: null argument");
-    const host::PolyStep* p = reinterpret_cast<const host::PolyStep*>(plan);
     return guarded([&]() -> int {
-        if (const char* why = ops_poly_eval_check(ctx->c, p, n_steps, depth))
+        if (const char* why = ops_poly_eval_check(ctx->c, plan, n_steps, depth))
             return fail(HEGPU_E_INVALID, std::string("poly_eval: ") + why);
-        if (int r = check_leaf_weights(p, n_steps, "poly_eval")) return r;
-        const host::PolyStep& last = p[n_steps - 1];
+        if (int r = check_leaf_weights(plan, n_steps, "poly_eval")) return r;
+        const hegpu_poly_step& last = plan[n_steps - 1];
         const uint64_t out_words = ct_words(ctx->c, last.level + 1 + (last.rescale_after ? 1 : 0));
         if (spans_overlap(ct, cs, level_words(ctx->c, depth), out, so, out_words, batch))
             return fail(HEGPU_E_INVALID, "poly_eval: out must not overlap ct");
         if (int r = check_workspace(ws, ws_bytes, hegpu_ckks_poly_eval_workspace_bytes(ctx, plan, n_steps, depth, batch)))
             return r;
-        return hip_ret(op_ckks_poly_eval(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, n_steps, (const u64*) relin_key, depth,
+        return hip_ret(op_ckks_poly_eval(ctx->c, (const u64*) ct, cs, (u64*) out, so, plan, n_steps, (const u64*) relin_key, depth,
                                          batch, (u64*) ws, (hipStream_t) stream),
                        "hegpu_ckks_poly_eval");
     });
@@ -1492,43 +1444,90 @@ int hegpu_ckks_slot_to_coeff(hegpu_context* ctx, const uint64_t* c0, uint64_t c0
     });
 }
 
-// ---- the CKKS refresh.  Everything is checked on the host tables, before the context is uploaded: a refusal needs no device.
-static int bootstrap_check(const hegpu_context* ctx, const hegpu_bootstrap_plan* plan, const hegpu_poly_step* eval_mod,
-                           int n_steps, const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc,
-                           int stc_count, int batch)
+// ---- the CKKS refresh and the slim family.  Everything is checked on the host tables, before the context is uploaded: a
+// refusal needs no device.  The two entries share their checks.  A RefreshKind is what differs between them there, a
+// Refresh the arguments they have in common.
+extern "C++" {
+template <typename Plan>
+struct RefreshKind {
+    const char* who; // the name in the messages
+    const char* (*plan_check)(const Context&, const Plan&, const host::PolyStep*, int);
+    int32_t Plan::*stc_start; // the level of SlotToCoeff's first factor
+    int stc_boundary;         // factors_check's: the regular SlotToCoeff merges the two halves first, the slim one has one input
+};
+static const RefreshKind<hegpu_bootstrap_plan> REGULAR_REFRESH{"bootstrap", ops_bootstrap_check, &hegpu_bootstrap_plan::stc_level, 1};
+static const RefreshKind<hegpu_slim_bootstrap_plan> SLIM_REFRESH{"slim_bootstrap", ops_slim_bootstrap_check,
+                                                                 &hegpu_slim_bootstrap_plan::in_level, 0};
+template <typename Plan>
+struct Refresh {
+    const RefreshKind<Plan>& kind;
+    const hegpu_context* ctx;
+    const Plan* plan;
+    const hegpu_poly_step* steps; // the EvalMod or trig plan
+    int n_steps;
+    const hegpu_linear_factor *cts, *stc;
+    int cts_count, stc_count, batch;
+};
+
+template <typename Plan>
+static int refresh_check(const Refresh<Plan>& r)
 {
-    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
-    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
-    if (!plan || !eval_mod || !cts || !stc) return fail(HEGPU_E_INVALID, "bootstrap: null argument");
-    if (int r = check_items(batch, 4, "bootstrap")) return r;
-    host::BootstrapPlan p;
-    std::memcpy(&p, plan, sizeof(p));
-    if (const char* why = ops_bootstrap_check(ctx->c, p, reinterpret_cast<const host::PolyStep*>(eval_mod), n_steps))
-        return fail(HEGPU_E_INVALID, std::string("bootstrap: ") + why);
-    if (cts_count != p.cts_pieces || stc_count != p.stc_pieces)
-        return fail(HEGPU_E_INVALID, "bootstrap: as many factors as the plan has pieces");
-    const int Q = ctx->c.Q_size;
-    if (int r = factors_check(ctx, cts, p.cts_pieces, Q - 1 - p.cts_level, "bootstrap (CoeffToSlot)")) return r;
-    if (int r = factors_check(ctx, stc, p.stc_pieces, Q - 1 - p.stc_level, "bootstrap (SlotToCoeff)")) return r;
-    return 0;
+    const std::string who = r.kind.who;
+    if (!r.ctx) return fail(HEGPU_E_INVALID, "null context");
+    if (int e = check_scheme(r.ctx->c, SCHEME_CKKS)) return e;
+    if (!r.plan || !r.steps || !r.cts || !r.stc) return fail(HEGPU_E_INVALID, who + ": null argument");
+    if (int e = check_items(r.batch, 4, r.kind.who)) return e;
+    const Plan& p = *r.plan;
+    if (const char* why = r.kind.plan_check(r.ctx->c, p, r.steps, r.n_steps)) return fail(HEGPU_E_INVALID, who + ": " + why);
+    if (r.cts_count != p.cts_pieces || r.stc_count != p.stc_pieces)
+        return fail(HEGPU_E_INVALID, who + ": as many factors as the plan has pieces");
+    const int Q = r.ctx->c.Q_size;
+    if (int e = factors_check(r.ctx, r.cts, p.cts_pieces, Q - 1 - p.cts_level, (who + " (CoeffToSlot)").c_str())) return e;
+    return factors_check(r.ctx, r.stc, p.stc_pieces, Q - 1 - p.*r.kind.stc_start, (who + " (SlotToCoeff)").c_str(),
+                         r.kind.stc_boundary);
 }
+
+// the size query: 0 for arguments the check refuses; elems(cts, stc): the words of the sequence for the checked ones
+template <typename Plan, typename Elems>
+static size_t refresh_workspace_bytes(const Refresh<Plan>& r, Elems&& elems)
+{
+    size_t bytes = 0;
+    (void) guarded([&]() -> int { // no exception may cross the C boundary
+        if (!refresh_check(r))
+            bytes = elems(factors_of(r.cts, r.cts_count).data(), factors_of(r.stc, r.stc_count).data()) * sizeof(u64);
+        return 0;
+    });
+    return bytes;
+}
+
+// What both entries do after refresh_check and the null check of their own arguments.  in, in2: the inputs (an entry with
+// one passes it twice); res: the room `out` needs; need: the size query's answer; out_rule, ws_rule: the refusals of an
+// overlap, which name the entry's inputs.
+template <typename Plan, typename Launch>
+static int refresh_run(const Refresh<Plan>& r, hegpu_context* ctx, const Span& in, const Span& in2, const Span& res, const void* ws,
+                       size_t ws_bytes, size_t need, const char* out_rule, const char* ws_rule, Launch&& launch)
+{
+    const std::string who = r.kind.who;
+    if (int e = check_leaf_weights(r.steps, r.n_steps, r.kind.who)) return e;
+    if (r.batch > 1 && res.stride < res.item) return fail(HEGPU_E_INVALID, who + ": out_stride too small");
+    if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
+    if (overlaps_any(res, {in, in2}, r.batch)) return fail(HEGPU_E_INVALID, who + ": " + out_rule);
+    if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in, in2}, r.batch))
+        return fail(HEGPU_E_INVALID, who + ": " + ws_rule);
+    NEED_CTX(ctx);
+    return launch();
+}
+} // extern "C++"
 
 size_t hegpu_ckks_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_bootstrap_plan* plan,
                                             const hegpu_poly_step* eval_mod, int n_steps, const hegpu_linear_factor* cts,
                                             int cts_count, const hegpu_linear_factor* stc, int stc_count, int switch_keys,
                                             int batch)
 {
-    size_t bytes = 0;
-    (void) guarded([&]() -> int { // no exception may cross the C boundary
-        if (bootstrap_check(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count, batch)) return 0;
-        host::BootstrapPlan p;
-        std::memcpy(&p, plan, sizeof(p));
-        bytes = ops_bootstrap_workspace_elems(ctx->c, p, reinterpret_cast<const host::PolyStep*>(eval_mod), n_steps,
-                                              factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
-                                              switch_keys != 0, batch) * sizeof(u64);
-        return 0;
+    const Refresh<hegpu_bootstrap_plan> r{REGULAR_REFRESH, ctx, plan, eval_mod, n_steps, cts, stc, cts_count, stc_count, batch};
+    return refresh_workspace_bytes(r, [&](const LinearFactor* c, const LinearFactor* s) {
+        return ops_bootstrap_workspace_elems(ctx->c, *plan, eval_mod, n_steps, c, s, switch_keys != 0, batch);
     });
-    return bytes;
 }
 
 int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
@@ -1538,67 +1537,33 @@ int hegpu_ckks_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, ui
                          int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
     return guarded([&]() -> int {
-        if (int r = bootstrap_check(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count, batch)) return r;
+        const Refresh<hegpu_bootstrap_plan> r{REGULAR_REFRESH, ctx, plan, eval_mod, n_steps, cts, stc, cts_count, stc_count, batch};
+        if (int e = refresh_check(r)) return e;
         if (!ct || !out || !conj_key || !relin_key || !ws) return fail(HEGPU_E_INVALID, "bootstrap: null argument");
         if (!swk_dense_to_sparse != !swk_sparse_to_dense)
             return fail(HEGPU_E_INVALID, "bootstrap: both switch keys (dense to sparse, sparse to dense) or neither");
-        host::BootstrapPlan p;
-        std::memcpy(&p, plan, sizeof(p));
-        const host::PolyStep* steps = reinterpret_cast<const host::PolyStep*>(eval_mod);
-        if (int r = check_leaf_weights(steps, n_steps, "bootstrap")) return r;
-        const Span in{ct, cs, ct_words(ctx->c, 1)}, res{out, so, ct_words(ctx->c, p.out_level + 2)}; // before the last rescale
-        if (batch > 1 && so < res.item) return fail(HEGPU_E_INVALID, "bootstrap: out_stride too small");
+        const Span in{ct, cs, ct_words(ctx->c, 1)}, res{out, so, ct_words(ctx->c, plan->out_level + 2)}; // before the last rescale
         const size_t need = hegpu_ckks_bootstrap_workspace_bytes(ctx, plan, eval_mod, n_steps, cts, cts_count, stc, stc_count,
                                                                  swk_dense_to_sparse != nullptr, batch);
-        if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
-        if (overlaps_any(res, {in}, batch)) return fail(HEGPU_E_INVALID, "bootstrap: out must not overlap ct");
-        if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in}, batch))
-            return fail(HEGPU_E_INVALID, "bootstrap: the workspace must overlap neither out nor ct");
-        NEED_CTX(ctx);
-        return hip_ret(op_ckks_bootstrap(ctx->c, (const u64*) ct, cs, (u64*) out, so, p, steps, n_steps,
-                                         factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
-                                         (const u64*) conj_key, (const u64*) relin_key, (const u64*) swk_dense_to_sparse,
-                                         (const u64*) swk_sparse_to_dense, batch, (u64*) ws, (hipStream_t) stream),
-                       "hegpu_ckks_bootstrap");
+        return refresh_run(r, ctx, in, in, res, ws, ws_bytes, need, "out must not overlap ct",
+                           "the workspace must overlap neither out nor ct", [&]() -> int {
+            return hip_ret(op_ckks_bootstrap(ctx->c, (const u64*) ct, cs, (u64*) out, so, *plan, eval_mod, n_steps,
+                                             factors_of(cts, cts_count).data(), factors_of(stc, stc_count).data(),
+                                             (const u64*) conj_key, (const u64*) relin_key, (const u64*) swk_dense_to_sparse,
+                                             (const u64*) swk_sparse_to_dense, batch, (u64*) ws, (hipStream_t) stream),
+                           "hegpu_ckks_bootstrap");
+        });
     });
-}
-
-// ---- the slim family of refreshes, checked like the refresh above
-static int slim_bootstrap_check(const hegpu_context* ctx, const hegpu_slim_bootstrap_plan* plan, const hegpu_poly_step* trig,
-                                int n_steps, const hegpu_linear_factor* cts, int cts_count, const hegpu_linear_factor* stc,
-                                int stc_count, int batch)
-{
-    if (!ctx) return fail(HEGPU_E_INVALID, "null context");
-    if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
-    if (!plan || !trig || !cts || !stc) return fail(HEGPU_E_INVALID, "slim_bootstrap: null argument");
-    if (int r = check_items(batch, 4, "slim_bootstrap")) return r;
-    host::SlimBootstrapPlan p;
-    std::memcpy(&p, plan, sizeof(p));
-    if (const char* why = ops_slim_bootstrap_check(ctx->c, p, reinterpret_cast<const host::PolyStep*>(trig), n_steps))
-        return fail(HEGPU_E_INVALID, std::string("slim_bootstrap: ") + why);
-    if (cts_count != p.cts_pieces || stc_count != p.stc_pieces)
-        return fail(HEGPU_E_INVALID, "slim_bootstrap: as many factors as the plan has pieces");
-    const int Q = ctx->c.Q_size;
-    if (int r = factors_check(ctx, cts, p.cts_pieces, Q - 1 - p.cts_level, "slim_bootstrap (CoeffToSlot)")) return r;
-    if (int r = factors_check(ctx, stc, p.stc_pieces, Q - 1 - p.in_level, "slim_bootstrap (SlotToCoeff)", 0)) return r;
-    return 0;
 }
 
 size_t hegpu_ckks_slim_bootstrap_workspace_bytes(const hegpu_context* ctx, const hegpu_slim_bootstrap_plan* plan,
                                                  const hegpu_poly_step* trig, int n_steps, const hegpu_linear_factor* cts,
                                                  int cts_count, const hegpu_linear_factor* stc, int stc_count, int batch)
 {
-    size_t bytes = 0;
-    (void) guarded([&]() -> int { // no exception may cross the C boundary
-        if (slim_bootstrap_check(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch)) return 0;
-        host::SlimBootstrapPlan p;
-        std::memcpy(&p, plan, sizeof(p));
-        bytes = ops_slim_bootstrap_workspace_elems(ctx->c, p, reinterpret_cast<const host::PolyStep*>(trig), n_steps,
-                                                   factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
-                                                   batch) * sizeof(u64);
-        return 0;
+    const Refresh<hegpu_slim_bootstrap_plan> r{SLIM_REFRESH, ctx, plan, trig, n_steps, cts, stc, cts_count, stc_count, batch};
+    return refresh_workspace_bytes(r, [&](const LinearFactor* c, const LinearFactor* s) {
+        return ops_slim_bootstrap_workspace_elems(ctx->c, *plan, trig, n_steps, c, s, batch);
     });
-    return bytes;
 }
 
 int hegpu_ckks_slim_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, const uint64_t* ct2, uint64_t cs2,
@@ -1608,28 +1573,21 @@ int hegpu_ckks_slim_bootstrap(hegpu_context* ctx, const uint64_t* ct, uint64_t c
                               size_t ws_bytes, hegpu_stream stream)
 {
     return guarded([&]() -> int {
-        if (int r = slim_bootstrap_check(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch)) return r;
+        const Refresh<hegpu_slim_bootstrap_plan> r{SLIM_REFRESH, ctx, plan, trig, n_steps, cts, stc, cts_count, stc_count, batch};
+        if (int e = refresh_check(r)) return e;
         if (!ct || !out || !conj_key || !relin_key || !ws) return fail(HEGPU_E_INVALID, "slim_bootstrap: null argument");
-        host::SlimBootstrapPlan p;
-        std::memcpy(&p, plan, sizeof(p));
-        const host::PolyStep* steps = reinterpret_cast<const host::PolyStep*>(trig);
-        if (int r = check_leaf_weights(steps, n_steps, "slim_bootstrap")) return r;
-        const host::PolyStep& last = steps[n_steps - 1];
-        const uint64_t in_words = ct_words(ctx->c, p.in_level + 1);
+        const uint64_t in_words = ct_words(ctx->c, plan->in_level + 1);
         const Span in{ct, cs, in_words}, in2{ct2 ? ct2 : ct, ct2 ? cs2 : cs, in_words};
-        const Span res{out, so, ct_words(ctx->c, p.out_level + 1 + (last.rescale_after ? 1 : 0))};
-        if (batch > 1 && so < res.item) return fail(HEGPU_E_INVALID, "slim_bootstrap: out_stride too small");
+        const Span res{out, so, ct_words(ctx->c, plan->out_level + 1 + (trig[n_steps - 1].rescale_after ? 1 : 0))};
         const size_t need = hegpu_ckks_slim_bootstrap_workspace_bytes(ctx, plan, trig, n_steps, cts, cts_count, stc, stc_count, batch);
-        if (!need || ws_bytes < need) return fail(HEGPU_E_INVALID, "workspace too small");
-        if (overlaps_any(res, {in, in2}, batch)) return fail(HEGPU_E_INVALID, "slim_bootstrap: out must overlap neither ct nor ct2");
-        if (overlaps_any({(const uint64_t*) ws, 0, need / sizeof(u64)}, {res, in, in2}, batch))
-            return fail(HEGPU_E_INVALID, "slim_bootstrap: the workspace must overlap neither out nor ct nor ct2");
-        NEED_CTX(ctx);
-        return hip_ret(op_ckks_slim_bootstrap(ctx->c, (const u64*) ct, cs, (const u64*) ct2, cs2, (u64*) out, so, p, steps, n_steps,
-                                              factors_of(cts, p.cts_pieces).data(), factors_of(stc, p.stc_pieces).data(),
-                                              (const u64*) conj_key, (const u64*) relin_key, batch, (u64*) ws,
-                                              (hipStream_t) stream),
-                       "hegpu_ckks_slim_bootstrap");
+        return refresh_run(r, ctx, in, in2, res, ws, ws_bytes, need, "out must overlap neither ct nor ct2",
+                           "the workspace must overlap neither out nor ct nor ct2", [&]() -> int {
+            return hip_ret(op_ckks_slim_bootstrap(ctx->c, (const u64*) ct, cs, (const u64*) ct2, cs2, (u64*) out, so, *plan, trig,
+                                                  n_steps, factors_of(cts, cts_count).data(), factors_of(stc, stc_count).data(),
+                                                  (const u64*) conj_key, (const u64*) relin_key, batch, (u64*) ws,
+                                                  (hipStream_t) stream),
+                           "hegpu_ckks_slim_bootstrap");
+        });
     });
 }
 

@@ -14,6 +14,7 @@
 //   * the threshold of the conditional rescale of q (:4545) is target_scale / 2; the reference compares with the scale
 //     of its bootstrapping context, which is the scale it calls the evaluator with.
 #pragma once
+#include "../../include/hegpu.h"
 #include <complex>
 #include <cstdint>
 #include <vector>
@@ -26,23 +27,10 @@ enum { POLY_STEP_POWER = 0, POLY_STEP_LEAF = 1, POLY_STEP_COMBINE = 2 };
 enum { POLY_TAIL_NONE = -1, POLY_TAIL_ONE = -2 }; // PolyStep::c of a POWER step that subtracts no register
 constexpr int POLY_LEAF_MAX = 15;                 // power terms of one leaf: 15 products and w_0 fit the 128-bit sum
 
-// The layout is the C ABI's hegpu_poly_step (include/hegpu.h), field for field.
-struct PolyStep {
-    int32_t kind;  // POLY_STEP_*
-    int32_t dst;   // the register written (= 1 + the step's position)
-    int32_t a, b;  // POWER: dst = reg[a] * reg[b]; COMBINE: dst = reg[a] * reg[b] + reg[c] (a = q, b = the giant power)
-    int32_t c;     // POWER: POLY_TAIL_NONE (monomial), POLY_TAIL_ONE (2 dst - 1) or the register of 2 dst - reg[c]; COMBINE: r
-    int32_t level; // of dst
-    int32_t mul_level;      // POWER, COMBINE: the level of the product (the lower of its operands', after q's rescale)
-    int32_t rescale_first;  // COMBINE: 1 = reg[a] is rescaled before the product
-    int32_t rescale_after;  // the polynomial's last step only: 1 = dst is rescaled once more; level and scale are those after it
-    int32_t n_terms;        // LEAF: number of power terms, <= POLY_LEAF_MAX
-    int32_t term_reg[POLY_LEAF_MAX];
-    double scale;           // of dst
-    double tail_const;      // POWER with POLY_TAIL_ONE: the real constant subtracted from part 0 (= scale: the one)
-    double w0[2];           // LEAF: round(c_0 * leaf_scale), (re, im)
-    double w[POLY_LEAF_MAX][2]; // LEAF: round(c_i * (leaf_scale / scale_i)) per term
-};
+// One step of a plan is the C ABI's struct (include/hegpu.h states every field); kind is a POLY_STEP_*.
+using PolyStep = ::hegpu_poly_step;
+static_assert(sizeof(PolyStep::term_reg) / sizeof(int32_t) == POLY_LEAF_MAX && sizeof(PolyStep::w) / sizeof(double[2]) == POLY_LEAF_MAX,
+              "a leaf of hegpu_poly_step holds POLY_LEAF_MAX terms");
 
 // std::invalid_argument: degree < 2, basis not one of the two, max_deg < degree, a non-finite coefficient or scale, a
 // scale <= 0, a leaf of more than POLY_LEAF_MAX power terms, fewer levels than the schedule spends (a level below 0, or

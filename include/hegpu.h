@@ -458,17 +458,20 @@ enum { HEGPU_POLY_MONOMIAL = 0, HEGPU_POLY_CHEBYSHEV = 1 };
 enum { HEGPU_POLY_POWER = 0, HEGPU_POLY_LEAF = 1, HEGPU_POLY_COMBINE = 2 };
 enum { HEGPU_POLY_TAIL_NONE = -1, HEGPU_POLY_TAIL_ONE = -2 };
 typedef struct hegpu_poly_step {
+    /* kind: HEGPU_POLY_POWER / _LEAF / _COMBINE; dst: the register written (= 1 + the step's position);
+     * a, b: POWER: dst = reg[a] * reg[b]; COMBINE: dst = reg[a] * reg[b] + reg[c] (a = q, b = the giant power);
+     * c: POWER: HEGPU_POLY_TAIL_NONE (monomial), HEGPU_POLY_TAIL_ONE (2 dst - 1) or the register of 2 dst - reg[c]; COMBINE: r */
     int32_t kind, dst, a, b, c;
     int32_t level;         /* of dst */
-    int32_t mul_level;     /* POWER, COMBINE */
-    int32_t rescale_first; /* COMBINE */
-    int32_t rescale_after; /* COMBINE: the polynomial's last step */
-    int32_t n_terms;       /* LEAF, <= 15 */
+    int32_t mul_level;     /* POWER, COMBINE: the level of the product (the lower of its operands', after q's rescale) */
+    int32_t rescale_first; /* COMBINE: 1 = reg[a] is rescaled before the product */
+    int32_t rescale_after; /* the polynomial's last step only: 1 = dst is rescaled once more; level and scale are those after it */
+    int32_t n_terms;       /* LEAF: number of power terms, <= 15 */
     int32_t term_reg[15];
     double scale;          /* of dst */
-    double tail_const;     /* POWER with HEGPU_POLY_TAIL_ONE */
-    double w0[2];          /* LEAF (re, im) */
-    double w[15][2];
+    double tail_const;     /* POWER with HEGPU_POLY_TAIL_ONE: the real constant subtracted from part 0 (= scale: the one) */
+    double w0[2];          /* LEAF: round(c_0 * leaf_scale), (re, im) */
+    double w[15][2];       /* LEAF: round(c_i * (leaf_scale / scale_i)) per term */
 } hegpu_poly_step;
 int hegpu_poly_eval_plan_size(int basis, const double* coeffs, int n_coeffs, int max_deg, int lead, int level, double scale,
                               double target_scale, const uint64_t* primes, int n_primes, int* n_steps);
@@ -540,8 +543,13 @@ int hegpu_ckks_poly_eval(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_str
  * stc_pieces and one limb left, K < 1, ratio D > q_0, a scale or ratio that is not positive and finite, piece counts
  * outside [2, 5], start levels that do not follow from one another, what hegpu_eval_mod_plan_* refuses. */
 typedef struct hegpu_bootstrap_config {
+    /* scale: D, the caller's scale; message_ratio: q_0 / D' aimed at (EvalModConfig::message_ratio_, default 256) */
     double scale, message_ratio;
+    /* K: the raise's overflow I stays below K in magnitude (EvalModConfig::K_, default 16); sine_degree: EvalModConfig::sine_deg_,
+     * default 30; double_angle: EvalModConfig::double_angle_, default 3 */
     int32_t K, sine_degree, double_angle;
+    /* cts_level: EncodingMatrixConfig::level_start_ of CoeffToSlot, the level the raise goes to; eval_level:
+     * EvalModConfig::level_start_; stc_level: EncodingMatrixConfig::level_start_ of SlotToCoeff (the merge drops to stc_level - 1) */
     int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces;
 } hegpu_bootstrap_config;
 typedef struct hegpu_bootstrap_plan {
@@ -549,12 +557,14 @@ typedef struct hegpu_bootstrap_plan {
     int32_t cts_level, cts_pieces, eval_level, stc_level, stc_pieces, out_level;
     int32_t K, sine_degree, double_angle;
     int32_t reserved;
-    double raise_scale;
+    double raise_scale; /* q_0 K */
+    /* cts_scale[f]: the scale factor f's diagonals are encoded at (level cts_level - f); cts_label[f]: the ciphertext's label
+     * after factor f and its rescale.  The factorisation of the special FFT has 2 .. 5 pieces. */
     double cts_scale[5], cts_label[5];
     double eval_in_scale, eval_target_scale, eval_out_scale;
-    double stc_in_scale;
-    double stc_scale[5], stc_label[5];
-    double out_scale;
+    double stc_in_scale; /* the relabelled result of EvalMod */
+    double stc_scale[5], stc_label[5]; /* factor g's diagonals (level stc_level - 1 - g) and the label after it */
+    double out_scale; /* D to the rounding of doubles */
 } hegpu_bootstrap_plan;
 int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64_t* primes, int n_primes,
                               hegpu_bootstrap_plan* plan);
@@ -618,6 +628,8 @@ int hegpu_eval_trig_plan_fill(int K, int degree, int double_angle, double phase,
                               double scale, double target_scale, const uint64_t* primes, int n_primes,
                               hegpu_poly_step* steps, int n_steps);
 typedef struct hegpu_slim_bootstrap_config {
+    /* scale: D, the caller's scale; ratio: q_0 / (the scale of the coefficients at the raise): 256 by default for slim, 2 for
+     * bits, 3 for gates */
     double scale, ratio;
     double phase, amplitude, offset;
     int32_t K, degree, double_angle;
@@ -629,8 +641,8 @@ typedef struct hegpu_slim_bootstrap_plan {
     int32_t in_level, stc_pieces, cts_level, cts_pieces, eval_level, out_level;
     int32_t K, degree, double_angle;
     int32_t reserved;
-    double stc_scale[5], stc_label[5];
-    double raise_scale;
+    double stc_scale[5], stc_label[5]; /* factor g's diagonals (level in_level - g) and the label after it */
+    double raise_scale; /* q_0 K */
     double cts_scale[5], cts_label[5];
     double ratio, phase, amplitude, offset;
     double eval_in_scale, eval_target_scale, eval_out_scale;

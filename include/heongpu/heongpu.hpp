@@ -2745,32 +2745,10 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         tc.less_key_mode_ = false;
         tc.CtoS_level_ = ctos;
         tc.StoC_level_ = stoc;
-        HEEncoder<S> encoder(context_);
-        const int n = (int) context_->n, slots = n >> 1;
-        for (int inverse = 1; inverse >= 0; inverse--) {
-            const int pieces = inverse ? tc.CtoS_piece_ : tc.StoC_piece_;
-            const int start = inverse ? ctos : stoc + 1;
-            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
-            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
-            for (int p = 0; p < pieces; p++) {
-                std::vector<int> offsets(counts[p]);
-                std::vector<double> values((size_t) 2 * counts[p] * slots);
-                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
-                std::map<int, std::vector<Complex64>> diag;
-                for (int d = 0; d < counts[p]; d++) {
-                    std::vector<Complex64> v((size_t) slots);
-                    for (int t = 0; t < slots; t++)
-                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
-                    diag[offsets[d]] = std::move(v);
-                }
-                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder, scale, start + p, 0,
-                                                               ExecutionOptions(), strides[p]);
-                for (int sh : lt->required_shifts())
-                    if (std::find(tc.key_indexs_.begin(), tc.key_indexs_.end(), sh) == tc.key_indexs_.end())
-                        tc.key_indexs_.push_back(sh);
-                (inverse ? tc.CtoS_factors_ : tc.StoC_factors_).push_back(std::move(lt));
-            }
-        }
+        // factor p at depth start + p, every one at `scale`
+        const std::vector<double> scales((size_t) std::max(tc.CtoS_piece_, tc.StoC_piece_), scale);
+        build_factors(1, tc.CtoS_piece_, ctos, scales.data(), tc.CtoS_factors_, tc.key_indexs_);
+        build_factors(0, tc.StoC_piece_, stoc + 1, scales.data(), tc.StoC_factors_, tc.key_indexs_);
         tc.generated_ = true;
     }
 
@@ -2795,8 +2773,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         detail::Workspace ws(hegpu_ckks_encoding_transform_workspace_bytes(context_->handle(), fa.f.data(), P, cipher.depth_, 1),
                              o.stream_);
         DeviceVector<Data64> m0(words, o.stream_), m1(words, o.stream_);
-        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
-        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        const uint64_t* conj = conjugation_key(galois_key);
         detail::check(hegpu_ckks_coeff_to_slot(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m0.data(),
                                                (uint64_t*) m1.data(), 0, fa.f.data(), P, conj, cipher.depth_, 1, ws.data(),
                                                ws.bytes, o.stream_));
@@ -2862,19 +2839,15 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         detail::OpScope storage_scope(o); // storage manager: stage HOST-stored operands, place the results
         check_plain_two_part(cipher);
         if (!cipher.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
-        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
-            throw std::invalid_argument("Relinkey does not belong to this context!");
+        check_relin_key(relin_key);
         const int Q = context_->Q_size, level = Q - 1 - cipher.depth_;
-        std::vector<uint64_t> primes((size_t) Q);
-        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        const std::vector<uint64_t> primes = context_primes();
         const int basis = pol.type_ == PolyType::MONOMIAL ? HEGPU_POLY_MONOMIAL : HEGPU_POLY_CHEBYSHEV;
         const double* cf = reinterpret_cast<const double*>(pol.coeffs_.data());
-        int n_steps = 0;
-        detail::check(hegpu_poly_eval_plan_size(basis, cf, (int) pol.coeffs_.size(), pol.max_deg_, pol.lead_ ? 1 : 0, level,
-                                                cipher.scale_, target_scale, primes.data(), Q, &n_steps)); // too few levels: invalid_argument
-        std::vector<hegpu_poly_step> plan((size_t) n_steps);
-        detail::check(hegpu_poly_eval_plan_fill(basis, cf, (int) pol.coeffs_.size(), pol.max_deg_, pol.lead_ ? 1 : 0, level,
-                                                cipher.scale_, target_scale, primes.data(), Q, plan.data(), n_steps));
+        const std::vector<hegpu_poly_step> plan = // too few levels: invalid_argument
+            step_plan(hegpu_poly_eval_plan_size, hegpu_poly_eval_plan_fill, basis, cf, (int) pol.coeffs_.size(), pol.max_deg_,
+                      pol.lead_ ? 1 : 0, level, cipher.scale_, target_scale, primes.data(), Q);
+        const int n_steps = (int) plan.size();
         const hegpu_poly_step& last = plan.back();
         const size_t n = context_->n;
         detail::Workspace ws(hegpu_ckks_poly_eval_workspace_bytes(context_->handle(), plan.data(), n_steps, cipher.depth_, 1),
@@ -2883,13 +2856,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         detail::check(hegpu_ckks_poly_eval(context_->handle(), (const uint64_t*) cipher.data(), 0, (uint64_t*) m.data(), 0,
                                            plan.data(), n_steps, (const uint64_t*) relin_key.data(), cipher.depth_, 1,
                                            ws.data(), ws.bytes, o.stream_));
-        Ciphertext<S> result(context_);
-        emit(cipher, result, std::move(m));
-        result.depth_ = Q - 1 - last.level;
-        result.scale_ = last.scale;
-        result.rescale_required_ = false;
-        result.relinearization_required_ = false;
-        return result;
+        return evaluated(cipher, std::move(m), last.level, last.scale);
     }
 
     // host/ckks/operator.cu:6906-7000 (hegpu_bootstrap_plan_fill): the plan of the refresh for ciphertexts
@@ -2908,8 +2875,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (em.sine_type_ != SineType::COS1) throw std::invalid_argument("Unsupported sine type!");
         if (em.arcsine_deg_ != 0) throw std::invalid_argument("The arcsine correction is not supported!");
         const int Q = context_->Q_size;
-        std::vector<uint64_t> primes((size_t) Q);
-        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        const std::vector<uint64_t> primes = context_primes();
         hegpu_bootstrap_config cfg{};
         cfg.scale = scale;
         cfg.message_ratio = em.message_ratio_;
@@ -2923,39 +2889,11 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         cfg.stc_pieces = config.stc_config_.piece_;
         BootV2 b;
         detail::check(hegpu_bootstrap_plan_fill(&cfg, primes.data(), Q, &b.plan));
-        int n_steps = 0;
-        detail::check(hegpu_eval_mod_plan_size(b.plan.K, b.plan.sine_degree, b.plan.double_angle, b.plan.eval_level,
-                                               b.plan.eval_in_scale, b.plan.eval_target_scale, primes.data(), Q, &n_steps));
-        b.eval_mod.resize((size_t) n_steps);
-        detail::check(hegpu_eval_mod_plan_fill(b.plan.K, b.plan.sine_degree, b.plan.double_angle, b.plan.eval_level,
-                                               b.plan.eval_in_scale, b.plan.eval_target_scale, primes.data(), Q,
-                                               b.eval_mod.data(), n_steps));
-        HEEncoder<S> encoder(context_);
-        const int n = (int) context_->n, slots = n >> 1;
-        for (int inverse = 1; inverse >= 0; inverse--) {
-            const int pieces = inverse ? b.plan.cts_pieces : b.plan.stc_pieces;
-            const int first_level = inverse ? b.plan.cts_level : b.plan.stc_level - 1;
-            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
-            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
-            for (int p = 0; p < pieces; p++) {
-                std::vector<int> offsets(counts[p]);
-                std::vector<double> values((size_t) 2 * counts[p] * slots);
-                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
-                std::map<int, std::vector<Complex64>> diag;
-                for (int d = 0; d < counts[p]; d++) {
-                    std::vector<Complex64> v((size_t) slots);
-                    for (int t = 0; t < slots; t++)
-                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
-                    diag[offsets[d]] = std::move(v);
-                }
-                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder,
-                                                               inverse ? b.plan.cts_scale[p] : b.plan.stc_scale[p],
-                                                               Q - 1 - (first_level - p), 0, ExecutionOptions(), strides[p]);
-                for (int sh : lt->required_shifts())
-                    if (std::find(b.key_indexs.begin(), b.key_indexs.end(), sh) == b.key_indexs.end()) b.key_indexs.push_back(sh);
-                (inverse ? b.cts : b.stc).push_back(std::move(lt));
-            }
-        }
+        b.eval_mod = step_plan(hegpu_eval_mod_plan_size, hegpu_eval_mod_plan_fill, b.plan.K, b.plan.sine_degree, b.plan.double_angle,
+                               b.plan.eval_level, b.plan.eval_in_scale, b.plan.eval_target_scale, primes.data(), Q);
+        // factor p at depth Q - 1 - (first_level - p), first_level = cts_level resp. stc_level - 1
+        build_factors(1, b.plan.cts_pieces, Q - 1 - b.plan.cts_level, b.plan.cts_scale, b.cts, b.key_indexs);
+        build_factors(0, b.plan.stc_pieces, Q - 1 - (b.plan.stc_level - 1), b.plan.stc_scale, b.stc, b.key_indexs);
         b.scale = scale;
         b.generated = true;
         boot_v2_ = std::move(b);
@@ -2980,15 +2918,13 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         detail::OpScope storage_scope(options); // storage manager: stage HOST-stored operands, place the results
         check_plain_two_part(input1);
         if (!input1.in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
-        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
-            throw std::invalid_argument("Relinkey does not belong to this context!");
+        check_relin_key(relin_key);
         if (!swk_dense_to_sparse != !swk_sparse_to_dense)
             throw std::invalid_argument("Both switch keys (dense to sparse, sparse to dense) or neither!");
         for (Switchkey<S>* k : {swk_dense_to_sparse, swk_sparse_to_dense})
             if (k && !k->switch_key_generated_) throw std::logic_error("Switchkey is not generated!");
         FactorArgs fc(*this, boot_v2_.cts, galois_key), fs(*this, boot_v2_.stc, galois_key);
-        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
-        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        const uint64_t* conj = conjugation_key(galois_key);
         const hegpu_bootstrap_plan& p = boot_v2_.plan;
         const int n_steps = (int) boot_v2_.eval_mod.size();
         const uint64_t* down = swk_dense_to_sparse ? (const uint64_t*) swk_dense_to_sparse->data() : nullptr;
@@ -3002,13 +2938,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                                            boot_v2_.eval_mod.data(), n_steps, fc.f.data(), p.cts_pieces, fs.f.data(),
                                            p.stc_pieces, conj, (const uint64_t*) relin_key.data(), down, up, 1, ws.data(),
                                            ws.bytes, options.stream_));
-        Ciphertext<S> result(context_);
-        emit(input1, result, std::move(m));
-        result.depth_ = context_->Q_size - 1 - p.out_level;
-        result.scale_ = p.out_scale;
-        result.rescale_required_ = false;
-        result.relinearization_required_ = false;
-        return result;
+        return evaluated(input1, std::move(m), p.out_level, p.out_scale);
     }
 
     // ---- the slim family (host/ckks/operator.cu:6800-6900, :7226-7330): SlotToCoeff first at the bottom
@@ -3048,8 +2978,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             throw std::runtime_error("Bootstrapping parameters is locked after generation and cannot be modified.");
         detail::require_generated(context_);
         const int Q = context_->Q_size;
-        std::vector<uint64_t> primes((size_t) Q);
-        for (int i = 0; i < Q; i++) primes[(size_t) i] = context_->prime_vector_[i].value;
+        const std::vector<uint64_t> primes = context_primes();
         // (phi, A, alpha) of alpha + A cos(2 pi (a / ratio - phi)), include/hegpu.h
         static const double family[SLIM_FAMILY_SIZE][3] = {
             {0.25, 1.0 / (2.0 * 3.14159265358979323846), 0.0}, {1.0 / 2, 1.0 / 2, 1.0 / 2},
@@ -3074,43 +3003,15 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             cfg.arithmetic = arithmetic ? 1 : 0;
             hegpu_slim_bootstrap_plan& p = b.plan[fn];
             detail::check(hegpu_slim_bootstrap_plan_fill(&cfg, primes.data(), Q, &p));
-            int n_steps = 0;
-            detail::check(hegpu_eval_trig_plan_size(p.K, p.degree, p.double_angle, p.phase, p.amplitude, p.offset, p.eval_level,
-                                                    p.eval_in_scale, p.eval_target_scale, primes.data(), Q, &n_steps));
-            b.trig[fn].resize((size_t) n_steps);
-            detail::check(hegpu_eval_trig_plan_fill(p.K, p.degree, p.double_angle, p.phase, p.amplitude, p.offset, p.eval_level,
-                                                    p.eval_in_scale, p.eval_target_scale, primes.data(), Q, b.trig[fn].data(),
-                                                    n_steps));
+            b.trig[fn] = step_plan(hegpu_eval_trig_plan_size, hegpu_eval_trig_plan_fill, p.K, p.degree, p.double_angle, p.phase,
+                                   p.amplitude, p.offset, p.eval_level, p.eval_in_scale, p.eval_target_scale, primes.data(), Q);
             b.first = b.first < 0 ? fn : b.first;
         }
         // the factors depend on the function through its ratio alone: one set serves every plan of the set
         const hegpu_slim_bootstrap_plan& p0 = b.plan[b.first];
-        HEEncoder<S> encoder(context_);
-        const int n = (int) context_->n, slots = n >> 1;
-        for (int inverse = 1; inverse >= 0; inverse--) {
-            const int pieces = inverse ? p0.cts_pieces : p0.stc_pieces;
-            const int first_level = inverse ? p0.cts_level : p0.in_level;
-            std::vector<int> strides(pieces), stages(pieces), counts(pieces);
-            detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
-            for (int p = 0; p < pieces; p++) {
-                std::vector<int> offsets(counts[p]);
-                std::vector<double> values((size_t) 2 * counts[p] * slots);
-                detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
-                std::map<int, std::vector<Complex64>> diag;
-                for (int d = 0; d < counts[p]; d++) {
-                    std::vector<Complex64> v((size_t) slots);
-                    for (int t = 0; t < slots; t++)
-                        v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
-                    diag[offsets[d]] = std::move(v);
-                }
-                auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder,
-                                                               inverse ? p0.cts_scale[p] : p0.stc_scale[p],
-                                                               Q - 1 - (first_level - p), 0, ExecutionOptions(), strides[p]);
-                for (int sh : lt->required_shifts())
-                    if (std::find(b.key_indexs.begin(), b.key_indexs.end(), sh) == b.key_indexs.end()) b.key_indexs.push_back(sh);
-                (inverse ? b.cts : b.stc).push_back(std::move(lt));
-            }
-        }
+        // factor p at depth Q - 1 - (first_level - p), first_level = cts_level resp. in_level
+        build_factors(1, p0.cts_pieces, Q - 1 - p0.cts_level, p0.cts_scale, b.cts, b.key_indexs);
+        build_factors(0, p0.stc_pieces, Q - 1 - p0.in_level, p0.stc_scale, b.stc, b.key_indexs);
         b.generated = true;
         slim_ = std::move(b);
     }
@@ -3131,11 +3032,9 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
             check_plain_two_part(*in);
             if (!in->in_ntt_domain_) throw std::invalid_argument("Ciphertext should be in NTT domain");
         }
-        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
-            throw std::invalid_argument("Relinkey does not belong to this context!");
+        check_relin_key(relin_key);
         FactorArgs fc(*this, slim_.cts, galois_key), fs(*this, slim_.stc, galois_key);
-        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
-        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        const uint64_t* conj = conjugation_key(galois_key);
         const std::vector<hegpu_poly_step>& trig = slim_.trig[function];
         const int n_steps = (int) trig.size();
         const hegpu_poly_step& last = trig.back();
@@ -3148,36 +3047,97 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                                                 &p, trig.data(), n_steps, fc.f.data(), p.cts_pieces, fs.f.data(), p.stc_pieces,
                                                 conj, (const uint64_t*) relin_key.data(), 1, ws.data(), ws.bytes,
                                                 options.stream_));
-        Ciphertext<S> result(context_);
-        emit(input1, result, std::move(m));
-        result.depth_ = context_->Q_size - 1 - p.out_level;
-        result.scale_ = p.out_scale;
-        result.rescale_required_ = false;
-        result.relinearization_required_ = false;
-        return result;
+        return evaluated(input1, std::move(m), p.out_level, p.out_scale);
     }
 
   private:
+    // the factors of both transforms and every shift they rotate by
+    struct RefreshFactors {
+        std::vector<std::shared_ptr<LinearTransform<S>>> cts, stc;
+        std::vector<int> key_indexs;
+    };
     // what generate_slim_family_params leaves for slim_family_bootstrapping: a plan per function of the set, one set of factors
-    struct SlimBoot {
+    struct SlimBoot : RefreshFactors {
         bool generated = false;
         int first = -1;
         hegpu_slim_bootstrap_plan plan[SLIM_FAMILY_SIZE]{};
         std::vector<hegpu_poly_step> trig[SLIM_FAMILY_SIZE];
-        std::vector<std::shared_ptr<LinearTransform<S>>> cts, stc;
-        std::vector<int> key_indexs;
     };
     SlimBoot slim_;
     // what generate_bootstrapping_params_v2 leaves for regular_bootstrapping_v2
-    struct BootV2 {
+    struct BootV2 : RefreshFactors {
         bool generated = false;
         double scale = 0.0;
         hegpu_bootstrap_plan plan{};
         std::vector<hegpu_poly_step> eval_mod;
-        std::vector<std::shared_ptr<LinearTransform<S>>> cts, stc;
-        std::vector<int> key_indexs;
     };
     BootV2 boot_v2_;
+    // One chain of factors of the encoder's special FFT (hegpu_encoding_transform_shape / _fill; inverse: CoeffToSlot) in the
+    // order they are applied: factor p, its diagonals encoded at scales[p] and depth `depth` + p, is appended to `factors`,
+    // the shifts it rotates by to `key_indexs`.
+    void build_factors(int inverse, int pieces, int depth, const double* scales,
+                       std::vector<std::shared_ptr<LinearTransform<S>>>& factors, std::vector<int>& key_indexs)
+    {
+        HEEncoder<S> encoder(context_);
+        const int n = (int) context_->n, slots = n >> 1;
+        std::vector<int> strides(pieces), stages(pieces), counts(pieces);
+        detail::check(hegpu_encoding_transform_shape(n, inverse, pieces, strides.data(), stages.data(), counts.data()));
+        for (int p = 0; p < pieces; p++) {
+            std::vector<int> offsets(counts[p]);
+            std::vector<double> values((size_t) 2 * counts[p] * slots);
+            detail::check(hegpu_encoding_transform_fill(n, inverse, pieces, p, counts[p], offsets.data(), values.data()));
+            std::map<int, std::vector<Complex64>> diag;
+            for (int d = 0; d < counts[p]; d++) {
+                std::vector<Complex64> v((size_t) slots);
+                for (int t = 0; t < slots; t++)
+                    v[t] = Complex64(values[2 * ((size_t) d * slots + t)], values[2 * ((size_t) d * slots + t) + 1]);
+                diag[offsets[d]] = std::move(v);
+            }
+            auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder, scales[p], depth + p, 0, ExecutionOptions(),
+                                                           strides[p]);
+            for (int sh : lt->required_shifts())
+                if (std::find(key_indexs.begin(), key_indexs.end(), sh) == key_indexs.end()) key_indexs.push_back(sh);
+            factors.push_back(std::move(lt));
+        }
+    }
+    std::vector<uint64_t> context_primes() const
+    {
+        std::vector<uint64_t> primes((size_t) context_->Q_size);
+        for (size_t i = 0; i < primes.size(); i++) primes[i] = context_->prime_vector_[i].value;
+        return primes;
+    }
+    // a step plan of the C ABI: size(args..., &n_steps), then fill(args..., steps, n_steps)
+    template <typename Size, typename Fill, typename... Args>
+    static std::vector<hegpu_poly_step> step_plan(Size size, Fill fill, Args... args)
+    {
+        int n_steps = 0;
+        detail::check(size(args..., &n_steps));
+        std::vector<hegpu_poly_step> plan((size_t) n_steps);
+        detail::check(fill(args..., plan.data(), n_steps));
+        return plan;
+    }
+    void check_relin_key(Relinkey<S>& relin_key) const
+    {
+        if (!relin_key.relin_key_generated_ || relin_key.size() != detail::KeySwitchShape(context_).size())
+            throw std::invalid_argument("Relinkey does not belong to this context!");
+    }
+    const uint64_t* conjugation_key(Galoiskey<S>& galois_key) const
+    {
+        const uint64_t* conj = detail::key_for(galois_key, galois_key.galois_elt_zero);
+        if (!conj) throw std::invalid_argument("Galois key not present! (conjugation)");
+        return conj;
+    }
+    // the result of a step plan or a refresh: `m` with in's other properties, relinearized and rescaled
+    Ciphertext<S> evaluated(const Ciphertext<S>& in, DeviceVector<Data64>&& m, int level, double scale) const
+    {
+        Ciphertext<S> result(context_);
+        emit(in, result, std::move(m));
+        result.depth_ = context_->Q_size - 1 - level;
+        result.scale_ = scale;
+        result.rescale_required_ = false;
+        result.relinearization_required_ = false;
+        return result;
+    }
     void check_plain_two_part(const Ciphertext<S>& a) const
     {
         if (a.relinearization_required_ || a.cipher_size_ != 2)
