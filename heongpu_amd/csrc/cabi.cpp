@@ -812,6 +812,20 @@ static int check_items(int batch, int k, const char* who) // the entries for whi
 }
 static int check_depth(const Context& c, int depth) { return require(depth >= 0 && depth < c.Q_size, "invalid depth"); }
 static int check_workspace(const void* ws, size_t have, size_t need) { return require(ws && have >= need, "workspace too small"); }
+// The entries a caller's capture must not record.  One that draws randomness advances its generator's counter on the host:
+// captured once and replayed, it would hand every replay the same (seed, counter) -- the same a, noise and u.  One that
+// synchronises invalidates the capture.  Asked first: before anything is queued and before the counter moves.
+static const char* const DRAWS = "draws randomness, and every replay would draw the same";
+static const char* const SYNCS = "synchronises, which a capture does not allow";
+static int check_not_capturing(hegpu_stream stream, const char* who, const char* why)
+{
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing((hipStream_t) stream, &status);
+    if (e != hipSuccess) return hip_ret(e, who);
+    if (status == hipStreamCaptureStatusNone) return 0;
+    return fail(HEGPU_E_LOGIC, std::string(who) + ": the stream is being captured and this entry " + why +
+                                   "; call it outside the capture");
+}
 // words of a ciphertext of `parts` polynomials at `limbs` limbs
 static uint64_t ct_words(const Context& c, int limbs, int parts = 2) { return (uint64_t) parts * limbs * c.n; }
 static uint64_t level_words(const Context& c, int depth) { return ct_words(c, c.Q_size - depth); } // two parts at `depth`
@@ -1704,6 +1718,7 @@ static int check_kg(const hegpu_context* ctx, const hegpu_rng* rng, int op, cons
 int hegpu_generate_secret_key(hegpu_context* ctx, hegpu_rng* rng, int hamming_weight, uint64_t* sk, void* ws,
                               size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_generate_secret_key", SYNCS)) return r; // (and it draws)
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_KEYGEN_SECRET, ws, ws_bytes)) return r;
     if (hamming_weight <= 0 || hamming_weight > (int) ctx->c.n)
@@ -1715,6 +1730,7 @@ int hegpu_generate_secret_key(hegpu_context* ctx, hegpu_rng* rng, int hamming_we
 int hegpu_generate_public_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* sk, uint64_t* pk, void* ws,
                               size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_generate_public_key", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_KEYGEN_PUBLIC, ws, ws_bytes)) return r;
     return hip_ret(op_gen_public_key(ctx->c, rng->r, (const u64*) sk, (u64*) pk, (u64*) ws, (hipStream_t) stream),
@@ -1724,6 +1740,7 @@ int hegpu_generate_public_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
 int hegpu_generate_relin_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* sk, uint64_t* rk, void* ws,
                              size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_generate_relin_key", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
     return hip_ret(op_gen_switch_key(ctx->c, rng->r, (const u64*) sk, 0, nullptr, (u64*) rk, (u64*) ws,
@@ -1734,6 +1751,7 @@ int hegpu_generate_relin_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t*
 int hegpu_generate_switch_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* new_sk, const uint64_t* old_sk,
                               uint64_t* swk, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_generate_switch_key", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
     if (!old_sk) return fail(HEGPU_E_INVALID, "null old secret key");
@@ -1745,6 +1763,7 @@ int hegpu_generate_switch_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
 int hegpu_generate_galois_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* sk, int galois_elt, uint64_t* gk,
                               void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_generate_galois_key", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_KEYGEN_SWITCH, ws, ws_bytes)) return r;
     if (!galois_elt_ok(ctx->c, galois_elt)) return fail(HEGPU_E_INVALID, "galois element must be odd and below 2N");
@@ -1756,6 +1775,7 @@ int hegpu_generate_galois_key(hegpu_context* ctx, hegpu_rng* rng, const uint64_t
 int hegpu_ckks_encrypt(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* pk, const uint64_t* plain, uint64_t* ct,
                        void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_ckks_encrypt", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_scheme(ctx->c, SCHEME_CKKS)) return r;
     if (int r = check_kg(ctx, rng, OP_CKKS_ENCRYPT, ws, ws_bytes)) return r;
@@ -1778,6 +1798,7 @@ int hegpu_ckks_decrypt(hegpu_context* ctx, const uint64_t* ct, const uint64_t* s
 int hegpu_bfv_encrypt(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* pk, const uint64_t* plain, uint64_t* ct,
                       void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_bfv_encrypt", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_scheme(ctx->c, SCHEME_BFV)) return r;
     if (int r = check_kg(ctx, rng, OP_BFV_ENCRYPT, ws, ws_bytes)) return r;
@@ -1820,6 +1841,7 @@ static int check_shares(const uint64_t* const* shares, int k, const void* out)
 int hegpu_mpc_public_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, uint64_t* share,
                                void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_public_key_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
@@ -1831,6 +1853,7 @@ int hegpu_mpc_public_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rn
 int hegpu_mpc_relin_key_share_round1(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk,
                                      uint64_t* u_out, uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_relin_key_share_round1", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share || !u_out) return fail(HEGPU_E_INVALID, "null argument");
@@ -1843,6 +1866,7 @@ int hegpu_mpc_relin_key_share_round2(hegpu_context* ctx, hegpu_rng* rng, const u
                                      const uint64_t* round1_sum, uint64_t* share, void* ws, size_t ws_bytes,
                                      hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_relin_key_share_round2", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_kg(ctx, rng, OP_MPC_KEY_SHARE, ws, ws_bytes)) return r;
     if (!sk || !u || !round1_sum || !share) return fail(HEGPU_E_INVALID, "null argument");
@@ -1855,6 +1879,7 @@ int hegpu_mpc_relin_key_share_round2(hegpu_context* ctx, hegpu_rng* rng, const u
 int hegpu_mpc_galois_key_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* rng, const uint64_t* sk, int galois_elt,
                                uint64_t* share, void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_galois_key_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_mpc_kg(ctx, crs, rng, ws, ws_bytes)) return r;
     if (!sk || !share) return fail(HEGPU_E_INVALID, "null argument");
@@ -1892,6 +1917,7 @@ int hegpu_mpc_relin_key_finish(hegpu_context* ctx, const uint64_t* const* round2
 int hegpu_mpc_ckks_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
                                  const uint64_t* sk, int depth, uint64_t* share, int batch, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_ckks_decrypt_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
@@ -1917,6 +1943,7 @@ int hegpu_mpc_ckks_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_
 int hegpu_mpc_bfv_decrypt_share(hegpu_context* ctx, hegpu_rng* rng, const uint64_t* ct, uint64_t cs,
                                 const uint64_t* sk, uint64_t* share, int batch, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_bfv_decrypt_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = check_op(ctx, SCHEME_BFV, 0, 0, batch, nullptr, 0)) return leave(r);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
@@ -1940,6 +1967,9 @@ int hegpu_mpc_bfv_decrypt_merge(hegpu_context* ctx, const uint64_t* ct, uint64_t
 }
 
 // ---- collective refresh.  The checks every entry shares; the workspace row may be empty (a share needs none)
+// The two merges take the common generator only to derive the public a of the shares again; they draw nothing of their
+// own and stay capturable.  A replay derives the a of the captured call: the shares of every replay must come from a
+// common generator as far advanced as the one the capture was given.
 // Unlike the operators, the depth and the common generator are looked at before an empty batch leaves.
 static int check_refresh(const hegpu_context* ctx, int want_scheme, int op, int depth, int batch, const hegpu_rng* crs,
                          const void* ws, size_t ws_bytes)
@@ -1982,6 +2012,7 @@ int hegpu_mpc_ckks_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* 
                                  const uint64_t* sk, int depth, int mask_bits, uint64_t* share, int batch, void* ws,
                                  size_t ws_bytes, hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_ckks_refresh_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = require(!crs || crs != rng, "crs and rng must be different generators: the party's mask and errors are private"))
         return r;
@@ -2013,6 +2044,7 @@ int hegpu_mpc_bfv_refresh_share(hegpu_context* ctx, hegpu_rng* crs, hegpu_rng* r
                                 const uint64_t* sk, uint64_t* share, int batch, void* ws, size_t ws_bytes,
                                 hegpu_stream stream)
 {
+    if (int r = check_not_capturing(stream, "hegpu_mpc_bfv_refresh_share", DRAWS)) return r;
     NEED_CTX(ctx);
     if (int r = require(!crs || crs != rng, "crs and rng must be different generators: the party's mask and errors are private"))
         return r;
@@ -2577,6 +2609,7 @@ static int32_t encode_to_torus32(uint32_t mu, uint32_t m_size)
 int hegpu_tfhe_prepare_bootkey(hegpu_tfhe_context* ctx, const uint64_t* boot_key, uint64_t* prepared,
                                hegpu_stream stream)
 {
+    if (int rc = check_not_capturing(stream, "hegpu_tfhe_prepare_bootkey", SYNCS)) return rc;
     TFHE_NEED(ctx);
     const TfheDev& p = ctx->p;
     const u64 polys = (u64) p.n * (p.k + 1) * p.bk_l * (p.k + 1);
@@ -2588,6 +2621,8 @@ int hegpu_tfhe_prepare_bootkey(hegpu_tfhe_context* ctx, const uint64_t* boot_key
 
 // A query, not part of any launch path: the header word of a prepared key, read after the device has drained (so that it
 // is ordered behind whatever stream wrote the buffer).  Every failure is -1 (error codes leaked out as "formats").
+// It takes no stream, so check_not_capturing has nothing to ask: during a capture the drain itself fails, the answer is -1
+// and the capture is lost (include/hegpu.h says so).
 int hegpu_tfhe_prepared_format(hegpu_tfhe_context* ctx, const uint64_t* prepared, int refresh)
 {
     (void) refresh; // nothing is remembered any more (kept for the ABI)
@@ -2640,6 +2675,7 @@ int hegpu_tfhe_gate_precompute(hegpu_tfhe_context* ctx, int gate, int32_t* out_a
 
 int hegpu_tfhe_status(hegpu_tfhe_context* ctx, hegpu_stream stream)
 {
+    if (int rc = check_not_capturing(stream, "hegpu_tfhe_status", SYNCS)) return rc;
     TFHE_NEED(ctx);
     hipError_t e = hipStreamSynchronize((hipStream_t) stream);
     if (e != hipSuccess) return hip_ret(e, "hegpu_tfhe_status");
@@ -2713,6 +2749,7 @@ static const double TFHE_IH = 1.1547005383792517; // sqrt(16/12), see drbg_torus
 int hegpu_tfhe_generate_secret_key(hegpu_tfhe_context* ctx, hegpu_rng* rng, int32_t* lwe_key, int32_t* tlwe_key,
                                    hegpu_stream stream)
 {
+    if (int rc = check_not_capturing(stream, "hegpu_tfhe_generate_secret_key", DRAWS)) return rc;
     TFHE_NEED(ctx);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     const u64 s0 = rng->r.stream;
@@ -2726,6 +2763,7 @@ int hegpu_tfhe_generate_bootstrapping_key(hegpu_tfhe_context* ctx, hegpu_rng* rn
                                           const int32_t* tlwe_key, uint64_t* boot_key, int32_t* ks_a, int32_t* ks_b,
                                           void* ws, size_t ws_bytes, hegpu_stream stream)
 {
+    if (int rc = check_not_capturing(stream, "hegpu_tfhe_generate_bootstrapping_key", DRAWS)) return rc;
     TFHE_NEED(ctx);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     const TfheDev& p = ctx->p;
@@ -2744,6 +2782,7 @@ int hegpu_tfhe_generate_bootstrapping_key(hegpu_tfhe_context* ctx, hegpu_rng* rn
 int hegpu_tfhe_encrypt(hegpu_tfhe_context* ctx, hegpu_rng* rng, const int32_t* lwe_key, const int32_t* messages,
                        int shape, int32_t* out_a, int32_t* out_b, hegpu_stream stream)
 {
+    if (int rc = check_not_capturing(stream, "hegpu_tfhe_encrypt", DRAWS)) return rc;
     TFHE_NEED(ctx);
     if (!rng) return fail(HEGPU_E_INVALID, "null random generator");
     if (shape <= 0) return fail(HEGPU_E_INVALID, "shape must be positive");

@@ -1174,6 +1174,24 @@ hipError_t tfhe_gate_pre(int* out_a, int* out_b, const int* a1, const int* b1, c
     return hipGetLastError();
 }
 
+// The split forms of the key switching add their partial sums onto cleared outputs.  Cleared by a kernel, not by
+// hipMemsetAsync: the runtime replays a captured memset node of 16 bytes or more with a stale fill value from the second
+// replay on (tests/test_gpu_graph_replay.py::test_tfhe_key_switching_batched), and these entries are capturable.
+__global__ __launch_bounds__(256) void k_tfhe_clear_sample(int* __restrict__ out_a, int* __restrict__ out_b, size_t na,
+                                                           size_t nb)
+{
+    const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (i < na) out_a[i] = 0;
+    if (i < nb) out_b[i] = 0;
+}
+
+static hipError_t tfhe_clear_sample(int* out_a, int* out_b, int shape, int n, hipStream_t st)
+{
+    const size_t na = (size_t) shape * n, nb = (size_t) shape; // n >= 1: the grid of out_a covers out_b
+    hipLaunchKernelGGL(k_tfhe_clear_sample, dim3((unsigned) ((na + 255) / 256)), dim3(256), 0, st, out_a, out_b, na, nb);
+    return hipGetLastError();
+}
+
 hipError_t tfhe_key_switching(const TfheDev& p, const int* in_a, const int* in_b, int* out_a, int* out_b,
                               const int* ks_a, const int* ks_b, int shape, int ks_batched, int ks_pieces, hipStream_t st)
 {
@@ -1200,8 +1218,7 @@ hipError_t tfhe_key_switching(const TfheDev& p, const int* in_a, const int* in_b
         pieces = (Nk + chunk - 1) / chunk;
         const dim3 grid((unsigned) groups, (unsigned) pieces);
         if (pieces > 1) {
-            hipError_t e = hipMemsetAsync(out_a, 0, (size_t) shape * p.n * sizeof(int), st);
-            if (e == hipSuccess) e = hipMemsetAsync(out_b, 0, (size_t) shape * sizeof(int), st);
+            const hipError_t e = tfhe_clear_sample(out_a, out_b, shape, p.n, st);
             if (e != hipSuccess) return e;
         }
 #define KS_LAUNCH(GB)                                                                                                      \
@@ -1228,8 +1245,7 @@ hipError_t tfhe_key_switching(const TfheDev& p, const int* in_a, const int* in_b
     if (pieces > 1) {
         const int chunk = (Nk + pieces - 1) / pieces;
         pieces = (Nk + chunk - 1) / chunk;
-        hipError_t e = hipMemsetAsync(out_a, 0, (size_t) shape * p.n * sizeof(int), st);
-        if (e == hipSuccess) e = hipMemsetAsync(out_b, 0, (size_t) shape * sizeof(int), st);
+        const hipError_t e = tfhe_clear_sample(out_a, out_b, shape, p.n, st);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_tfhe_key_switching<true>, dim3(shape, pieces), dim3(256), 0, st, in_a, in_b, out_a, out_b, ks_a,
                            ks_b, p.ks_base_bit, p.ks_length, p.n, Nk, chunk);

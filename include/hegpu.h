@@ -262,8 +262,34 @@ int hegpu_fast_floor(hegpu_context* ctx, const uint64_t* in, uint64_t in_stride,
 /* ------------------------------------------------------------------ operators
  * HEArithmeticOperator<S> sequences, batched over independent ciphertexts.
  * `ws` is a caller-provided device workspace of at least
- * hegpu_workspace_bytes(ctx, op, depth, batch) bytes (no allocation happens
- * inside, so the calls are hipGraph-capturable). */
+ * hegpu_workspace_bytes(ctx, op, depth, batch) bytes.
+ *
+ * Streams and capture.  Every entry of this header with a `stream` argument
+ * issues all its work on that stream, and only there; it allocates nothing
+ * and takes its temporaries from `ws`.  Host arrays (keys, elements, index
+ * tables, plans) are read before the call returns.
+ * Every such entry may be recorded into a hipGraph and replayed, on a context
+ * that is uploaded and after one call outside the capture (module loading),
+ * except two groups:
+ *   - the entries that draw randomness: every entry that takes a hegpu_rng*
+ *     (hegpu_generate_*, hegpu_*_encrypt, the hegpu_mpc_*_share entries,
+ *     hegpu_tfhe_generate_* and hegpu_tfhe_encrypt).  The generator's
+ *     counter advances on the host at the call: a replay would draw the same
+ *     a, noise and u again, and two encryptions with the same randomness leak
+ *     the difference of their messages;
+ *   - the entries that synchronise: hegpu_generate_secret_key,
+ *     hegpu_tfhe_prepare_bootkey, hegpu_tfhe_status and
+ *     hegpu_tfhe_prepared_format.
+ * On a stream that is being captured these return HEGPU_E_LOGIC (the message
+ * says "draws randomness" or "synchronises") before anything is queued and
+ * before the generator's counter moves; the capture stays valid.
+ * hegpu_tfhe_prepared_format takes no stream and cannot ask: called during a
+ * capture it returns -1 and the capture is lost.
+ * hegpu_mpc_ckks_refresh_merge / hegpu_mpc_bfv_refresh_merge take the common
+ * generator only to derive the public `a` of the shares again; they draw
+ * nothing of their own and are capturable.  A replay derives the `a` of the
+ * captured call, so the shares of every replay must come from a common
+ * generator as far advanced as the one the capture was given. */
 enum {
     HEGPU_OP_CKKS_RELIN = 1,
     HEGPU_OP_CKKS_RESCALE = 2,

@@ -66,6 +66,106 @@ def items_of(view, stride, words, count):
     return np.stack([got[i * stride:i * stride + words] for i in range(count)])
 
 
+POISON = 0x0BADC0DE0BADC0DE  # what outputs and workspaces hold before a call of side_stream_and_graph_parity
+_busy = []
+
+
+def _bits(x):
+    """a numpy array as the integers of its element size: what the device buffers hold"""
+    x = np.ascontiguousarray(x)
+    assert x.dtype.itemsize in (4, 8), x.dtype
+    return x.reshape(-1).view(np.int64 if x.dtype.itemsize == 8 else np.int32)
+
+
+def side_stream_and_graph_parity(torch, operands, call, cases, pad=1):
+    """The promise of include/hegpu.h -- an entry issues all its work on the caller's stream, allocates nothing and does
+    not synchronise -- tested on a stream that is not the null stream, eagerly and from a captured graph.
+
+    operands: name -> (items, kind) as in test_gpu_operand_layout.py: equally long numpy arrays of 8-byte elements (or of
+    int32: the TFHE samples), one per item of the batch, and "in", "out", "inout" or "ws".  The arrays give the sizes and
+    the warm-up's inputs (zeros are valid input to every entry).  call(d, s) issues the entries on torch's current stream,
+    given the device buffers (int64 or int32 tensors) and the item strides by name.  cases: two or more (inputs, want):
+    name -> items written over the "in" / "inout" operands, name -> per item the expected leading elements of the "out" /
+    "inout" operands, compared bit for bit.
+
+    Every 8-byte operand lies in a buffer of its own between sentinel words, its items `pad` words further apart than
+    they are long (laid_out); int32 operands are packed.
+      1. warm-up on a side stream: lazy module loading and the function-attribute statics run outside the capture;
+      2. the first case eagerly on the side stream while the null stream is busy with long fills queued just before;
+         outputs and workspaces hold POISON and the results are read back on the side stream, so a launch or a memset
+         that went to the null stream runs late and shows;
+      3. POISON again, then the call captured on the side stream alone (torch.cuda.CUDAGraph; no fork or join);
+      4. every case: inputs written over the captured buffers, POISON over outputs and workspaces, replay, synchronise,
+         compare.  The cases differ from each other and from the warm-up, so nothing left over from an earlier run passes.
+    An entry that leaves its stream, allocates or synchronises ends the capture in an error; work that fell outside the
+    graph shows as a wrong result at replay.  The sentinels around every operand must hold throughout.
+    Returns (d, s) for checks of the caller's own."""
+    assert len(cases) >= 2
+    dev, d, s, words = {}, {}, {}, {}
+    for name, (items, kind) in operands.items():
+        assert kind in ("in", "out", "inout", "ws"), kind
+        rows = [_bits(x) for x in items]
+        words[name] = len(rows[0])
+        if rows[0].dtype == np.int64:
+            d[name], s[name], intact = laid_out([r.view(np.uint64) for r in rows], 0, pad)
+        else:
+            d[name], s[name], intact = torch.from_numpy(np.concatenate(rows)).cuda(), words[name], lambda: True
+        dev[name] = intact
+
+    def put(name, rows):
+        for i, x in enumerate(rows):
+            d[name][i * s[name]:i * s[name] + x.numel()].copy_(x)
+
+    def load(inputs):
+        for name, (items, kind) in operands.items():
+            if kind in ("out", "ws"):
+                fill = POISON if d[name].dtype == torch.int64 else POISON & 0x7FFFFFFF
+                put(name, [torch.full((words[name],), fill, dtype=d[name].dtype, device="cuda")] * len(items))
+            elif name in inputs:
+                assert len(inputs[name]) == len(items)
+                put(name, [torch.from_numpy(_bits(x)).cuda() for x in inputs[name]])
+        torch.cuda.synchronize()
+
+    def compare(want, tag, stream=None):
+        # the results are fetched on `stream` alone where one is given: work that went to another stream is not waited for
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            if stream is None:
+                torch.cuda.synchronize()
+            fetched = {name: d[name].detach().cpu().numpy() for name in want}
+        torch.cuda.synchronize()
+        for name, intact in dev.items():
+            assert intact(), (tag, "written outside the operand " + name)
+        for name, rows in want.items():
+            got = fetched[name]
+            for b, w in enumerate(rows):
+                w = _bits(w)
+                assert np.array_equal(got[b * s[name]:b * s[name] + len(w)], w), (tag, name, b)
+
+    if not _busy:
+        _busy.append(torch.empty(1 << 26, dtype=torch.int64, device="cuda"))  # 512 MiB: one fill takes about 0.2 ms
+    side = torch.cuda.Stream()
+    load({})
+    with torch.cuda.stream(side):
+        call(d, s)
+    torch.cuda.synchronize()
+    inputs, want = cases[0]
+    load(inputs)
+    for i in range(8):  # the null stream is busy for a millisecond or more; the side stream does not wait for it
+        _busy[0].fill_(i)
+    with torch.cuda.stream(side):
+        call(d, s)
+    compare(want, "eager on a side stream", side)
+    load({})
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        call(d, s)
+    for i, (inputs, want) in enumerate(cases):
+        load(inputs)
+        graph.replay()
+        compare(want, "replay %d" % i)
+    return d, s
+
+
 import contextlib  # noqa: E402
 
 
