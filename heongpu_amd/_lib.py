@@ -28,7 +28,8 @@ class LinearFactor(ctypes.Structure):
     """hegpu_linear_factor: the matrix arguments of hegpu_ckks_linear_transform for one factor of a sequence"""
     _fields_ = [("diags", ctypes.c_void_p), ("n_diag", c_int), ("index", ctypes.POINTER(c_int)), ("n1", c_int), ("n2", c_int),
                 ("baby_keys", ctypes.POINTER(ctypes.c_void_p)), ("baby_elts", ctypes.POINTER(c_int)),
-                ("giant_keys", ctypes.POINTER(ctypes.c_void_p)), ("giant_elts", ctypes.POINTER(c_int))]
+                ("giant_keys", ctypes.POINTER(ctypes.c_void_p)), ("giant_elts", ctypes.POINTER(c_int)),
+                ("giant_parent", ctypes.POINTER(c_int))]
 
 
 class PolyStep(ctypes.Structure):
@@ -152,6 +153,11 @@ SIGNATURES = [
     ("hegpu_ckks_linear_transform", c_int,
      [voidp, u64p, u64, u64p, u64, u64p, c_int, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(ctypes.c_void_p),
       ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_int), c_int, c_int, voidp, c_size_t, voidp]),
+    ("hegpu_giant_step_chain", c_int, [ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    ("hegpu_ckks_linear_transform_chained", c_int,
+     [voidp, u64p, u64, u64p, u64, u64p, c_int, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(ctypes.c_void_p),
+      ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_int, c_int,
+      voidp, c_size_t, voidp]),
     ("hegpu_encoding_transform_shape", c_int,
      [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     ("hegpu_encoding_transform_fill", c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), voidp]),

@@ -376,16 +376,25 @@ class Context(_Handle):
         return int(self._lib.hegpu_ckks_linear_transform_workspace_bytes(self._h, n1, n2, depth, batch))
 
     def ckks_linear_transform(self, ct, cs, out, so, diags, n_diag, index, baby_keys, baby_elts, giant_keys, giant_elts,
-                              depth, batch, ws, stream=None):
-        """hegpu_ckks_linear_transform: keys = lists of device tensors (None where the element is 0)"""
+                              depth, batch, ws, stream=None, giant_parent=None):
+        """hegpu_ckks_linear_transform: keys = lists of device tensors (None where the element is 0).  giant_parent (a list
+        of n2 term numbers, -1 = a root; giant_step_chain): hegpu_ckks_linear_transform_chained, giant_keys / giant_elts
+        are then the links of the chain"""
         n1, n2 = len(baby_elts), len(giant_elts)
         ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
         bk = (ctypes.c_void_p * n1)(*[(_ptr(k) if k is not None else None) for k in baby_keys])
         gk = (ctypes.c_void_p * n2)(*[(_ptr(k) if k is not None else None) for k in giant_keys])
         be = (ctypes.c_int * n1)(*[int(g) for g in baby_elts])
         ge = (ctypes.c_int * n2)(*[int(g) for g in giant_elts])
-        self._call("ckks_linear_transform", _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2, bk, be, gk,
-                   ge, depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
+        if giant_parent is None:
+            self._call("ckks_linear_transform", _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2, bk, be, gk,
+                       ge, depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
+            return
+        if len(giant_parent) != n2:
+            raise ValueError("giant_parent has one entry per giant step")
+        gp = (ctypes.c_int * max(n2, 1))(*[int(p) for p in giant_parent])
+        self._call("ckks_linear_transform_chained", _ptr(ct), cs, _ptr(out), so, _ptr(diags), n_diag, ix, n1, n2, bk, be,
+                   gk, ge, gp, depth, batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     def ckks_conj_split(self, x, xs, xc, xcs, out0, out1, so, depth, out_depth, batch=1, stream=None):
         """hegpu_ckks_conj_split: out0 = x + xc, out1 = div_i(x - xc) on the Q - out_depth kept limbs"""
@@ -445,12 +454,25 @@ class Context(_Handle):
                    batch, _ptr(ws), _ws_bytes(ws), stream=stream)
 
     @staticmethod
-    def linear_factors(factors):
+    def linear_factors(factors, chained=False, galois_key=None, n=None):
         """the hegpu_linear_factor array of a sequence entry.  factors: one (diags, n_diag, index, baby_keys, baby_elts,
-        giant_keys, giant_elts) per matrix, the arguments of ckks_linear_transform.  Returns (array, keep-alive)."""
+        giant_keys, giant_elts) per matrix, the arguments of ckks_linear_transform, or the same with giant_parent as an
+        eighth entry (None = direct), giant_keys / giant_elts then being the links.  Returns (array, keep-alive).
+        chained=True: every factor is (diags, n_diag, index, baby_keys, baby_elts, giant_shifts) with the plan's giant
+        shifts; its links come from giant_step_chain over N = n, their keys from galois_key(elt) -> device key.  Returns
+        (array, keep-alive, link_shifts): the distinct non-zero link shifts, all the giant-step keys the factors need."""
+        needed = set()
+        if chained:
+            made = []
+            for diags, n_diag, index, baby_keys, baby_elts, giant_shifts in factors:
+                keys, elts, parent, links = chained_giant_steps(giant_shifts, n, galois_key)
+                needed.update(s for s in links if s)
+                made.append((diags, n_diag, index, baby_keys, baby_elts, keys, elts, parent))
+            factors = made
         arr = (_lib.LinearFactor * len(factors))()
         keep = []
-        for f, (diags, n_diag, index, baby_keys, baby_elts, giant_keys, giant_elts) in zip(arr, factors):
+        for f, factor in zip(arr, factors):
+            diags, n_diag, index, baby_keys, baby_elts, giant_keys, giant_elts = factor[:7]
             n1, n2 = len(baby_elts), len(giant_elts)
             ix = (ctypes.c_int * (n1 * n2))(*[int(v) for row in index for v in row])
             bk = (ctypes.c_void_p * n1)(*[(_ptr(k) if k is not None else None) for k in baby_keys])
@@ -460,7 +482,13 @@ class Context(_Handle):
             f.diags, f.n_diag, f.index, f.n1, f.n2 = _ptr(diags), n_diag, ix, n1, n2
             f.baby_keys, f.baby_elts, f.giant_keys, f.giant_elts = bk, be, gk, ge
             keep += [ix, bk, gk, be, ge, diags, baby_keys, giant_keys]
-        return arr, keep
+            if len(factor) > 7 and factor[7] is not None:
+                if len(factor[7]) != n2:
+                    raise ValueError("giant_parent has one entry per giant step")
+                gp = (ctypes.c_int * n2)(*[int(p) for p in factor[7]])
+                f.giant_parent = gp
+                keep.append(gp)
+        return (arr, keep, sorted(needed)) if chained else (arr, keep)
 
     def encoding_transform_workspace_bytes(self, factors, depth, batch):
         arr, _keep = self.linear_factors(factors)
@@ -497,12 +525,14 @@ class Context(_Handle):
                    _ptr(swk_dense_to_sparse), _ptr(swk_sparse_to_dense), batch, _ptr(ws),
                    _ws_bytes(ws) if ws is not None else 0, stream=stream)
 
-    def bootstrap_factors(self, plan, galois_key, encode=None):
+    def bootstrap_factors(self, plan, galois_key, encode=None, chained=False):
         """The two factor lists of Context.ckks_bootstrap from a BootstrapPlan: the factorisation of the special FFT
         (encoding_transform_factors), each factor's baby-step/giant-step plan (linear_transform_plan) and its diagonals
         encoded at the level and scale the plan gives them.  galois_key(elt) -> device key of a Galois element;
         encode(values, scale, limbs) -> packed residues [limbs][N] of one diagonal (default: ckks_encode_ex mode 1).
-        Returns (cts, stc, galois_elts): the lists and every element used, the conjugation 2N - 1 included."""
+        Returns (cts, stc, galois_elts): the lists and every element used, the conjugation 2N - 1 included.
+        chained=True: every factor's giant steps are chained (giant_step_chain); the factors carry giant_parent and their
+        links, and galois_elts is the reduced set: baby steps, links and the conjugation."""
         import torch
         n, slots = self.n, self.n // 2
         if encode is None:
@@ -525,9 +555,11 @@ class Context(_Handle):
                 order = np.argsort([k % slots for k in g.offsets])  # the plan numbers the diagonals by k mod slots
                 packed = torch.cat([encode(np.roll(g.diagonals[order[p]], -lp.pre_rotation[p]), scales[f], limbs)
                                     for p in range(len(order))])
-                baby, giant = [key(s) for s in lp.baby_shifts], [key(s) for s in lp.giant_shifts]
+                chain = giant_step_chain(lp.giant_shifts, slots) if chained else None
+                baby = [key(s) for s in lp.baby_shifts]
+                giant = [key(s) for s in (chain.link_shifts if chained else lp.giant_shifts)]
                 out.append((packed, len(order), lp.index, [k for k, _ in baby], [e for _, e in baby], [k for k, _ in giant],
-                            [e for _, e in giant]))
+                            [e for _, e in giant]) + ((chain.parent,) if chained else ()))
             return out
 
         # a SlimBootstrapPlan's SlotToCoeff starts at the input's own level: there is no merge below it
@@ -537,10 +569,10 @@ class Context(_Handle):
         elts.add(2 * n - 1)
         return cts, stc, sorted(elts)
 
-    def slim_bootstrap_factors(self, plan, galois_key, encode=None):
+    def slim_bootstrap_factors(self, plan, galois_key, encode=None, chained=False):
         """bootstrap_factors for a SlimBootstrapPlan (slim_bootstrap_plan): the same factorisation and encoder, SlotToCoeff
         factor g at level plan.in_level - g and scale plan.stc_scale[g].  Returns (cts, stc, galois_elts)."""
-        return self.bootstrap_factors(plan, galois_key, encode)
+        return self.bootstrap_factors(plan, galois_key, encode, chained)
 
     def slim_bootstrap_workspace_bytes(self, plan, cts, stc, batch):
         """hegpu_ckks_slim_bootstrap_workspace_bytes; plan: a SlimBootstrapPlan, cts / stc as for linear_factors"""
@@ -1051,6 +1083,33 @@ def linear_transform_plan(diag_indices, slots, n1=None, stride=1):
         index[giant.index(q // n1)][baby.index(q % n1)] = pos
     return LinearTransformPlan(len(baby), len(giant), index, [stride * i for i in baby], [stride * j * n1 for j in giant],
                                [-stride * (q // n1) * n1 for q in qs])
+
+
+GiantStepChain = collections.namedtuple("GiantStepChain", "parent link_shifts")
+
+
+def giant_step_chain(giant_shifts, slots):
+    """The chain of a plan's giant steps (host only; hegpu_giant_step_chain): a Horner fold over the signed shifts.  The
+    non-negative shifts, ascending, each hang on the one before; the negative ones, from the one nearest zero outwards,
+    likewise, the first of them on the zero shift if there is one.  Returns
+      parent         per giant step the term it is folded into, -1 for a root
+      link_shifts    per giant step its shift minus its parent's, in [0, slots); for a root its own shift
+    the giant_parent of Context.ckks_linear_transform and the rotations of its links.  The links a term crosses add up to
+    its giant shift, so linear_transform_plan's pre_rotation stays valid."""
+    shifts = [int(s) for s in giant_shifts]
+    n2 = len(shifts)
+    arr = (ctypes.c_int * max(n2, 1))(*shifts)
+    parent, links = (ctypes.c_int * max(n2, 1))(), (ctypes.c_int * max(n2, 1))()
+    _check(_lib.load().hegpu_giant_step_chain(arr, n2, int(slots), parent, links))
+    return GiantStepChain(list(parent)[:n2], list(links)[:n2])
+
+
+def chained_giant_steps(giant_shifts, n, galois_key):
+    """The giant-step arguments of a chained transform at degree n: (keys, elts, parent, link_shifts) with the keys of
+    the links from galois_key(elt) -> device key (None where a link does not rotate)."""
+    chain = giant_step_chain(giant_shifts, n // 2)
+    elts = [steps_to_galois_elt(s, n, 5) if s else 0 for s in chain.link_shifts]
+    return [galois_key(e) if e else None for e in elts], elts, chain.parent, chain.link_shifts
 
 
 EncodingTransformPiece = collections.namedtuple("EncodingTransformPiece", "stride stages offsets diagonals")

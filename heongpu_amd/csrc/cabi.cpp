@@ -520,6 +520,14 @@ int hegpu_encoding_transform_fill(int coeff_count, int inverse, int pieces, int 
     });
 }
 
+int hegpu_giant_step_chain(const int* giant_shifts, int n2, int slots, int* parent, int* link_shifts)
+{
+    return guarded([&]() -> int {
+        host::giant_step_chain(giant_shifts, n2, slots, parent, link_shifts);
+        return 0;
+    });
+}
+
 // host only: the step plans (poly_eval.hpp) and the refresh plans (bootstrap_plan.hpp).  The three step-plan families
 // share one size and one fill: `make` is the family's planner over the caller's arguments, `who` the name in the messages.
 using MakePlan = std::function<std::vector<host::PolyStep>()>;
@@ -843,6 +851,12 @@ static int check_galois_list(const Context& c, const uint64_t* const* keys, cons
 }
 // the baby-step / giant-step shape: 16 products per 128-bit sum, 256 indices by value
 static bool bsgs_shape_ok(int n1, int n2) { return n1 >= 1 && n1 <= 16 && n2 >= 1 && n2 <= 16; }
+// the parent table of chained giant steps (null, or all -1: the direct mode); after check_galois_list of the giant steps
+static int check_giant_chain(const int* parent, int n2, const uint64_t* const* keys, const int* elts, const char* who)
+{
+    const char* why = ops_giant_chain_check(parent, n2, (const u64* const*) keys, elts);
+    return why ? fail(HEGPU_E_INVALID, std::string(who) + ": " + why) : 0;
+}
 static int check_diag_index(const int* index, int n1, int n2, int n_diag, const char* who) // [n2][n1]: a packed diagonal or -1
 {
     for (int k = 0; k < n1 * n2; k++)
@@ -1193,6 +1207,16 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                 const uint64_t* const* giant_keys, const int* giant_elts, int depth, int batch, void* ws,
                                 size_t ws_bytes, hegpu_stream stream)
 {
+    return hegpu_ckks_linear_transform_chained(ctx, ct, cs, out, so, diags, n_diag, index, n1, n2, baby_keys, baby_elts,
+                                               giant_keys, giant_elts, nullptr, depth, batch, ws, ws_bytes, stream);
+}
+
+int hegpu_ckks_linear_transform_chained(hegpu_context* ctx, const uint64_t* ct, uint64_t cs, uint64_t* out, uint64_t so,
+                                        const uint64_t* diags, int n_diag, const int* index, int n1, int n2,
+                                        const uint64_t* const* baby_keys, const int* baby_elts,
+                                        const uint64_t* const* giant_keys, const int* giant_elts, const int* giant_parent,
+                                        int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream)
+{
     NEED_CTX(ctx);
     if (int r = check_op(ctx, SCHEME_CKKS, 0, depth, batch, nullptr, 0)) return leave(r);
     if (!bsgs_shape_ok(n1, n2)) return fail(HEGPU_E_INVALID, "linear_transform: n1 and n2 lie in [1, 16]");
@@ -1202,6 +1226,7 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
     if (int r = check_grid(batch, 2, "linear_transform")) return r;
     if (int r = check_galois_list(ctx->c, baby_keys, baby_elts, n1, "linear_transform")) return r;
     if (int r = check_galois_list(ctx->c, giant_keys, giant_elts, n2, "linear_transform")) return r;
+    if (int r = check_giant_chain(giant_parent, n2, giant_keys, giant_elts, "linear_transform")) return r;
     const uint64_t words = level_words(ctx->c, depth);
     if (spans_overlap(ct, cs, words, out, so, words, batch))
         return fail(HEGPU_E_INVALID, "linear_transform: out must not overlap ct");
@@ -1210,7 +1235,7 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
     return hip_ret(op_ckks_linear_transform(ctx->c, (const u64*) ct, cs, (u64*) out, so, (const u64*) diags, n_diag, index,
                                             n1, n2, (const u64* const*) baby_keys, baby_elts,
                                             (const u64* const*) giant_keys, giant_elts, depth, batch, (u64*) ws,
-                                            (hipStream_t) stream),
+                                            (hipStream_t) stream, giant_parent),
                    "hegpu_ckks_linear_transform");
 }
 
@@ -1387,6 +1412,7 @@ static int factors_check(const hegpu_context* ctx, const hegpu_linear_factor* f,
         if (int r = check_diag_index(a.index, a.n1, a.n2, a.n_diag, who)) return r;
         if (int r = check_galois_list(ctx->c, a.baby_keys, a.baby_elts, a.n1, who)) return r;
         if (int r = check_galois_list(ctx->c, a.giant_keys, a.giant_elts, a.n2, who)) return r;
+        if (int r = check_giant_chain(a.giant_parent, a.n2, a.giant_keys, a.giant_elts, who)) return r;
     }
     return 0;
 }
@@ -1397,7 +1423,7 @@ static std::vector<LinearFactor> factors_of(const hegpu_linear_factor* f, int co
     for (int k = 0; k < count; k++)
         v[(size_t) k] = LinearFactor{(const u64*) f[k].diags, f[k].n_diag, f[k].index, f[k].n1, f[k].n2,
                                      (const u64* const*) f[k].baby_keys, f[k].baby_elts,
-                                     (const u64* const*) f[k].giant_keys, f[k].giant_elts};
+                                     (const u64* const*) f[k].giant_keys, f[k].giant_elts, f[k].giant_parent};
     return v;
 }
 

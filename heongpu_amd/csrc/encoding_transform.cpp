@@ -2,6 +2,7 @@
 // dense n x n matrix is 8 GB at N = 2^16, a group of five stages is 63 diagonals of n values.
 #include "encoding_transform.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <stdexcept>
@@ -107,6 +108,29 @@ EncodingTransformPiece encoding_transform_piece(int n_power, bool inverse, int p
         out.diags.push_back(*d.second);
     }
     return out;
+}
+
+void giant_step_chain(const int* giant_shifts, int n2, int slots, int* parent, int* link_shifts)
+{
+    if (!giant_shifts || !parent || !link_shifts) throw std::invalid_argument("giant_step_chain: null argument");
+    if (n2 < 1 || n2 > 16) throw std::invalid_argument("giant_step_chain: n2 lies in [1, 16]");
+    if (slots < 1 || (slots & (slots - 1))) throw std::invalid_argument("giant_step_chain: the slot count is a power of two");
+    std::vector<std::pair<int, int>> order; // (signed shift, term)
+    for (int j = 0; j < n2; j++) {
+        const int s = giant_shifts[j];
+        if (s < 0 || s >= slots) throw std::invalid_argument("giant_step_chain: a shift outside [0, slots)");
+        order.emplace_back(s > slots / 2 ? s - slots : s, j);
+    }
+    std::stable_sort(order.begin(), order.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    size_t first = 0; // the first non-negative shift
+    while (first < order.size() && order[first].first < 0) first++;
+    auto link = [&](size_t at, const std::pair<int, int>* to) {
+        parent[order[at].second] = to ? to->second : -1;
+        link_shifts[order[at].second] = ((order[at].first - (to ? to->first : 0)) % slots + slots) % slots;
+    };
+    for (size_t at = first; at < order.size(); at++) link(at, at > first ? &order[at - 1] : nullptr);
+    const bool zero = first < order.size() && order[first].first == 0;
+    for (size_t at = first; at-- > 0;) link(at, at + 1 < first ? &order[at + 1] : zero ? &order[first] : nullptr);
 }
 
 } // namespace host

@@ -28,5 +28,15 @@ struct EncodingTransformPiece {
 // [2, 17], pieces outside [2, 5] or more pieces than stages, piece outside [0, pieces)
 EncodingTransformPiece encoding_transform_piece(int n_power, bool inverse, int pieces, int piece);
 
+// The chain of a transform's giant steps: a Horner fold over the signed shifts.  Each of the n2 shifts,
+// given in [0, slots), is taken as its signed representative in (-slots/2, slots/2].  The non-negative ones, ascending,
+// each have the one before as parent; the negative ones, from the one nearest zero outwards, likewise, and the first of
+// them hangs on the zero shift if there is one.  parent[j] = -1: a root.  link_shifts[j] in [0, slots): term j's signed
+// shift minus its parent's (a root's own shift), the rotation of op_ckks_linear_transform's link j.  The rotations a term
+// meets on its way to the result add up to its own shift, so the pre-rotated diagonals of the direct plan stay valid, and
+// giant steps that are dense on both sides of zero -- the groups of the special FFT -- need two distinct links.
+// std::invalid_argument: n2 outside [1, 16], slots no power of two, a shift outside [0, slots), a null argument.
+void giant_step_chain(const int* giant_shifts, int n2, int slots, int* parent, int* link_shifts);
+
 } // namespace host
 } // namespace hegpu

@@ -960,13 +960,122 @@ size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, in
     return linear_transform_ws(c, n1, n2, depth, batch).total;
 }
 
+// ---- chained giant steps: giant_parent makes a forest of the n2 terms, giant_elts[j] / giant_keys[j] are term j's link
+// to its parent (a root's: to the result).  ops_giant_chain_check: nullptr, or what is wrong with the table.
+static bool giant_chain_given(const int* giant_parent, int n2)
+{
+    if (!giant_parent) return false;
+    for (int j = 0; j < n2; j++)
+        if (giant_parent[j] != -1) return true;
+    return false;
+}
+
+// the links to the root above term j, -1 if the walk does not end within n2 steps (a term that is its own ancestor)
+static int giant_chain_depth(const int* giant_parent, int n2, int j)
+{
+    int d = 0;
+    for (int at = giant_parent[j]; at != -1; at = giant_parent[at])
+        if (++d >= n2) return -1;
+    return d;
+}
+
+const char* ops_giant_chain_check(const int* giant_parent, int n2, const u64* const* giant_keys, const int* giant_elts)
+{
+    if (!giant_chain_given(giant_parent, n2)) return nullptr; // the direct mode: op_ckks_linear_transform's own checks
+    for (int j = 0; j < n2; j++)
+        if (giant_parent[j] < -1 || giant_parent[j] >= n2) return "a giant-step parent outside [-1, n2)";
+    for (int j = 0; j < n2; j++)
+        if (giant_chain_depth(giant_parent, n2, j) < 0) return "a giant step is its own ancestor";
+    for (int j = 0; j < n2; j++)
+        if (giant_elts[j] != 0 && !giant_keys[j]) return "Galois key not present!";
+    return nullptr;
+}
+
+// S_j = inner_j + sum over the children k of j of galois(giant_elts[k], S_k); out = sum over the roots r of
+// galois(giant_elts[r], S_r).  Deepest terms first.  The 2 n2 ciphertext places of A and B hold at most one value per term
+// (its inner sum, its folded sum or the rotation of that) and the target of the launch in flight, so a free place always
+// exists: a fold never writes over one of its terms (rns_ckks_sum_terms' out is __restrict__), apply_galois never over its
+// input.  A single root writes `out` itself.
+static hipError_t giant_chain_fold(const Context& c, u64* A, u64 a_stride, u64* B, u64 b_stride, u64* out, u64 so,
+                                   int n2, const u64* const* giant_keys, const int* giant_elts, const int* giant_parent,
+                                   int depth, int batch, u64* ks, hipStream_t st)
+{
+    const int l = c.Q_size - depth;
+    const u64 ct_words = (u64) 2 * l * c.n;
+    const Mod* mods = c.plan_qp.mods;
+    // places 0 .. n2 - 1: B, n2 .. 2 n2 - 1: A; place j holds inner sum j
+    auto at = [&](int p) { return p < n2 ? B + (u64) p * ct_words : A + (u64) (p - n2) * ct_words; };
+    auto stride = [&](int p) { return p < n2 ? b_stride : a_stride; };
+    bool used[32] = {};
+    auto take = [&]() {
+        int p = 0;
+        while (used[p]) p++; // n2 + 1 of 2 n2 places are in use at the most
+        used[p] = true;
+        return p;
+    };
+    int place[16], level[16], roots = 0, deepest = 0;
+    for (int j = 0; j < n2; j++) {
+        place[j] = j;
+        used[j] = true;
+        level[j] = giant_chain_depth(giant_parent, n2, j);
+        if (level[j] < 0) return hipErrorInvalidValue;
+        if (giant_elts[j] != 0 && !giant_keys[j]) return hipErrorInvalidValue;
+        deepest = std::max(deepest, level[j]);
+        roots += giant_parent[j] == -1;
+    }
+    const u64* terms[16];
+    u64 strides[16];
+    for (int d = deepest; d >= 0; d--)
+        for (int j = 0; j < n2; j++) {
+            if (level[j] != d) continue;
+            const bool last = d == 0 && roots == 1; // the only root: what it writes last is the result
+            // fold the children, which are rotated already
+            int count = 0, spent[16];
+            for (int k = 0; k < n2; k++)
+                if (giant_parent[k] == j) spent[count++] = k;
+            if (count) {
+                terms[0] = at(place[j]);
+                strides[0] = stride(place[j]);
+                for (int i = 0; i < count; i++) {
+                    terms[i + 1] = at(place[spent[i]]);
+                    strides[i + 1] = stride(place[spent[i]]);
+                }
+                const bool to_out = last && giant_elts[j] == 0;
+                const int p = to_out ? -1 : take();
+                TRY(rns_ckks_sum_terms(terms, strides, count + 1, to_out ? out : at(p), to_out ? so : stride(p), mods, c.n_power,
+                                       l, batch, st));
+                used[place[j]] = false;
+                for (int i = 0; i < count; i++) used[place[spent[i]]] = false;
+                place[j] = p;
+            }
+            // the link to the parent (a root's: to the result)
+            if (giant_elts[j] != 0) {
+                const int p = last ? -1 : take();
+                TRY(op_ckks_apply_galois(c, at(place[j]), stride(place[j]), last ? out : at(p), last ? so : stride(p),
+                                         giant_keys[j], giant_elts[j], depth, batch, ks, st));
+                used[place[j]] = false;
+                place[j] = p;
+            }
+        }
+    if (roots == 1) return hipSuccess;
+    int count = 0;
+    for (int j = 0; j < n2; j++)
+        if (giant_parent[j] == -1) {
+            terms[count] = at(place[j]);
+            strides[count++] = stride(place[j]);
+        }
+    return rns_ckks_sum_terms(terms, strides, count, out, so, mods, c.n_power, l, batch, st);
+}
+
 hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* diags,
                                     int n_diag, const int* index, int n1, int n2, const u64* const* baby_keys,
                                     const int* baby_elts, const u64* const* giant_keys, const int* giant_elts, int depth,
-                                    int batch, u64* ws, hipStream_t st)
+                                    int batch, u64* ws, hipStream_t st, const int* giant_parent)
 {
     if (batch <= 0) return hipSuccess; // an empty batch is a no-op, not an invalid launch
     if (n1 < 1 || n1 > 16 || n2 < 1 || n2 > 16) return hipErrorInvalidValue;
+    const bool chained = giant_chain_given(giant_parent, n2);
+    if (chained && ops_giant_chain_check(giant_parent, n2, giant_keys, giant_elts)) return hipErrorInvalidValue;
     const int l = c.Q_size - depth;
     const u64 ct_words = (u64) 2 * l * c.n;
     const LinearTransformWs w = linear_transform_ws(c, n1, n2, depth, batch);
@@ -988,6 +1097,9 @@ hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64
     TRY(rns_ckks_diag_mac(rot, rot_stride, n1, diags, n_diag, index, n2, direct ? out : B, direct ? so : w.b_stride, mods,
                           c.n_power, l, batch, st));
     if (direct) return hipSuccess;
+    if (chained) // (n2 >= 2: a term has a parent)
+        return giant_chain_fold(c, A, w.a_stride, B, w.b_stride, out, so, n2, giant_keys, giant_elts, giant_parent, depth,
+                                batch, ks, st);
     // 3. giant rotations into A (the baby rotations are spent; apply_galois forbids out == in)
     const u64* terms[16];
     u64 strides[16];
@@ -1040,7 +1152,7 @@ static hipError_t encoding_transform_chain(const Context& c, const u64*& cur, u6
         }
         TRY(op_ckks_linear_transform(c, cur, cur_stride, dst, ds, f[k].diags, f[k].n_diag, f[k].index, f[k].n1, f[k].n2,
                                      f[k].baby_keys, f[k].baby_elts, f[k].giant_keys, f[k].giant_elts, d0 + k, batch,
-                                     step_ws, st));
+                                     step_ws, st, f[k].giant_parent));
         TRY(op_ckks_rescale(c, dst, ds, d0 + k, batch, step_ws, st));
         cur = dst;
         cur_stride = ds;

@@ -56,12 +56,24 @@ hipError_t op_ckks_rotate_hoisted(const Context& c, const u64* ct, u64 cs, u64* 
 //   out = sum_j galois(giant_elts[j], sum_i diags[index[j][i]] (.) galois(baby_elts[i], ct))
 // hoisted baby rotations -> one rns_ckks_diag_mac launch for all n2 inner sums -> one apply_galois per giant step with a
 // non-zero element -> one k-way sum.  index / keys / elts: HOST arrays ([n2][n1], [n1], [n2]; element 0 = identity, its
-// key is ignored).  Not rescaled.  Workspace: ops_linear_transform_workspace_elems.
+// key is ignored).  Not rescaled.  Workspace: ops_linear_transform_workspace_elems, the same in both modes.
+//
+// Chained giant steps: giant_parent, a HOST array [n2], makes a forest of the terms (-1 = a root; nullptr
+// or all -1 = the direct mode above, unchanged).  giant_elts[j] / giant_keys[j] are then term j's LINK, to its parent or,
+// for a root, to the result:
+//   S_j = inner_j + sum over the children k of j of galois(giant_elts[k], S_k),   out = sum over the roots r of
+//   galois(giant_elts[r], S_r)
+// deepest terms first, one op_ckks_apply_galois per link with a non-zero element and one rns_ckks_sum_terms per term with
+// children (and one over the roots if there are several).  With host::giant_step_chain's table the links of one factor
+// need two keys where the direct mode needs n2 - 1, for the same number of key switches.
+// ops_giant_chain_check: nullptr, or what is wrong with the table (a parent outside [-1, n2), a term that is its own
+// ancestor, a non-zero link element without a key).
 size_t ops_linear_transform_workspace_elems(const Context& c, int n1, int n2, int depth, int batch);
+const char* ops_giant_chain_check(const int* giant_parent, int n2, const u64* const* giant_keys, const int* giant_elts);
 hipError_t op_ckks_linear_transform(const Context& c, const u64* ct, u64 cs, u64* out, u64 so, const u64* diags,
                                     int n_diag, const int* index, int n1, int n2, const u64* const* baby_keys,
                                     const int* baby_elts, const u64* const* giant_keys, const int* giant_elts, int depth,
-                                    int batch, u64* ws, hipStream_t st);
+                                    int batch, u64* ws, hipStream_t st, const int* giant_parent = nullptr);
 
 // ---- CoeffToSlot / SlotToCoeff (reference coeff_to_slot / slot_to_coeff, ckks/operator.cu:3566-3663,
 // :3809-3891): a chain of op_ckks_linear_transform + op_ckks_rescale over the factors of the encoder's special FFT, and
@@ -76,6 +88,7 @@ struct LinearFactor {
     const int* baby_elts;
     const u64* const* giant_keys;
     const int* giant_elts;
+    const int* giant_parent = nullptr; // chained giant steps: see op_ckks_linear_transform
 };
 // two ciphertexts of the start depth per item + the largest linear-transform workspace of the chain
 size_t ops_encoding_transform_workspace_elems(const Context& c, const LinearFactor* f, int count, int depth, int batch);

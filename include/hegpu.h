@@ -393,6 +393,35 @@ int hegpu_ckks_linear_transform(hegpu_context* ctx, const uint64_t* ct, uint64_t
                                 const uint64_t* const* baby_keys, const int* baby_elts,
                                 const uint64_t* const* giant_keys, const int* giant_elts, int depth, int batch, void* ws,
                                 size_t ws_bytes, hegpu_stream stream);
+/* Chained giant steps: the same product over a reduced set of Galois keys (this backend's own schedule; the reference's
+ * less_key_mode, multiply_matrix_less_memory, host/ckks/operator.cu:3399-3496, rotates inner sum j by the first giant
+ * step j times, O(n2^2) key switches -- this one keeps the n2 - 1 of the direct mode).
+ *
+ * hegpu_giant_step_chain (HOST ONLY, no context, no device): the Horner fold over a plan's giant shifts.  Each shift in
+ * [0, slots) is taken as its signed representative in (-slots/2, slots/2].  The non-negative shifts, ascending, each have
+ * the one before as parent; the negative ones, from the one nearest zero outwards, likewise, the first of them hanging on
+ * the zero shift if there is one.  parent[j] = -1: a root.  link_shifts[j] in [0, slots): term j's signed shift minus its
+ * parent's, for a root its own shift.  The links a term crosses add up to its shift modulo slots, so the plan's
+ * pre-rotated diagonals stay as they are; giant steps that are dense on both sides of zero need two distinct links.
+ * HEGPU_E_INVALID: n2 outside [1, 16], slots no power of two, a shift outside [0, slots), a null argument.
+ *
+ * hegpu_ckks_linear_transform_chained: hegpu_ckks_linear_transform with giant_parent, a HOST array [n2].  NULL, or all
+ * -1, is hegpu_ckks_linear_transform itself (which is this entry with NULL).  Otherwise giant_elts[j] / giant_keys[j]
+ * describe term j's LINK (element 0 = no rotation, its key is ignored) and
+ *   S_j = inner_j + sum over the children k of j of galois(giant_elts[k], S_k)
+ *   out = sum over the roots r of galois(giant_elts[r], S_r)
+ * evaluated deepest terms first: one hegpu_ckks_apply_galois per link with a non-zero element, one sum per term with
+ * children, one over the roots if there are several.  Bit-identical to the same composition of the single entries
+ * (hegpu_ckks_rotate_hoisted, hegpu_cipherplain_multiplication + hegpu_addition per diagonal, hegpu_ckks_apply_galois per
+ * link, hegpu_addition).  The workspace is hegpu_ckks_linear_transform_workspace_bytes in both modes.
+ * HEGPU_E_INVALID, nothing launched: what hegpu_ckks_linear_transform refuses, a parent outside [-1, n2), a term that is
+ * its own ancestor, a non-zero link element with a null key. */
+int hegpu_giant_step_chain(const int* giant_shifts, int n2, int slots, int* parent, int* link_shifts);
+int hegpu_ckks_linear_transform_chained(hegpu_context* ctx, const uint64_t* ct, uint64_t ct_stride, uint64_t* out,
+                                        uint64_t out_stride, const uint64_t* diags, int n_diag, const int* index, int n1,
+                                        int n2, const uint64_t* const* baby_keys, const int* baby_elts,
+                                        const uint64_t* const* giant_keys, const int* giant_elts, const int* giant_parent,
+                                        int depth, int batch, void* ws, size_t ws_bytes, hegpu_stream stream);
 /* ---- CoeffToSlot / SlotToCoeff (HEArithmeticOperator<CKKS>::coeff_to_slot / slot_to_coeff, host/ckks/operator.cu:
  * 3566-3663 and 3809-3891; the context of generate_encoding_transform_context, :6686-6800).
  *
@@ -425,9 +454,10 @@ int hegpu_ckks_conj_split(hegpu_context* ctx, const uint64_t* x, uint64_t x_stri
 int hegpu_ckks_conj_merge(hegpu_context* ctx, const uint64_t* c0, uint64_t c0_stride, const uint64_t* c1,
                           uint64_t c1_stride, uint64_t* out, uint64_t out_stride, int depth, int out_depth, int batch,
                           hegpu_stream stream);
-/* One factor of a sequence: exactly the matrix arguments of hegpu_ckks_linear_transform (all arrays HOST, keys and
- * diagonals DEVICE).  The diagonals of factor k are encoded at the depth the chain has reached: depth + k for
- * CoeffToSlot, depth + 1 + k for SlotToCoeff. */
+/* One factor of a sequence: exactly the matrix arguments of hegpu_ckks_linear_transform_chained (all arrays HOST, keys
+ * and diagonals DEVICE).  The diagonals of factor k are encoded at the depth the chain has reached: depth + k for
+ * CoeffToSlot, depth + 1 + k for SlotToCoeff.  giant_parent: NULL (a zeroed field) = the direct mode, the arguments of
+ * hegpu_ckks_linear_transform; otherwise the factor's giant steps are chained and giant_keys / giant_elts are its links. */
 typedef struct hegpu_linear_factor {
     const uint64_t* diags;
     int n_diag;
@@ -437,6 +467,7 @@ typedef struct hegpu_linear_factor {
     const int* baby_elts;
     const uint64_t* const* giant_keys;
     const int* giant_elts;
+    const int* giant_parent;
 } hegpu_linear_factor;
 /* coeff_to_slot: per factor hegpu_ckks_linear_transform + hegpu_ckks_rescale_inplace (depth -> depth + count), then
  * hegpu_ckks_apply_galois with the element 2N - 1 and conj_key, then hegpu_ckks_conj_split to depth + count + 1 -- the
@@ -445,8 +476,10 @@ typedef struct hegpu_linear_factor {
  * slot_to_coeff: hegpu_ckks_conj_merge from depth to depth + 1 (the reference spends a level on its product with i),
  * then count x (linear transform, rescale).  The last product is written to out and rescaled there: out needs room for
  * [2][Q - depth - count][N] per item and holds [2][Q - depth - count - 1][N] on return.
- * Both are bit-identical to the same chain of single entries.  HEGPU_E_INVALID, outputs untouched: count < 1,
- * depth + count + 1 >= Q, an output overlapping an input, what hegpu_ckks_linear_transform refuses in a factor, a
+ * Both are bit-identical to the same chain of single entries (a factor with giant_parent:
+ * hegpu_ckks_linear_transform_chained, itself bit-identical to the same composition of single entries).  HEGPU_E_INVALID,
+ * outputs untouched: count < 1, depth + count + 1 >= Q, an output overlapping an input, what
+ * hegpu_ckks_linear_transform_chained refuses in a factor, a
  * workspace below hegpu_ckks_encoding_transform_workspace_bytes (0 for arguments it cannot size). */
 size_t hegpu_ckks_encoding_transform_workspace_bytes(const hegpu_context* ctx, const hegpu_linear_factor* factors,
                                                      int count, int depth, int batch);
@@ -600,7 +633,8 @@ int hegpu_bootstrap_plan_fill(const hegpu_bootstrap_config* config, const uint64
  * hegpu_ckks_mod_raise to plan->cts_level -> with switch keys the same key switch with swk_sparse_to_dense there ->
  * hegpu_ckks_coeff_to_slot (cts: cts_count = plan->cts_pieces factors) -> ONE hegpu_ckks_poly_eval of eval_mod over the
  * 2 * batch halves -> hegpu_ckks_slot_to_coeff (stc: stc_count = plan->stc_pieces factors).  Bit-identical to that chain of single entries
- * (the multiplication: hegpu_ckks_constant_op, HEGPU_CONST_MUL).  out needs room for [2][out_level + 2][N] per item and
+ * (the multiplication: hegpu_ckks_constant_op, HEGPU_CONST_MUL; a factor with giant_parent:
+ * hegpu_ckks_linear_transform_chained, bit-identical to the same composition of single entries).  out needs room for [2][out_level + 2][N] per item and
  * holds [2][out_level + 1][N] on return, at depth Q - 1 - out_level and scale plan->out_scale.
  * HEGPU_E_INVALID before anything is queued, out untouched: exactly one of the two switch keys, a plan, EvalMod plan or
  * factor list that does not fit the context or one another, a workspace below hegpu_ckks_bootstrap_workspace_bytes (0 for
@@ -686,7 +720,8 @@ int hegpu_ckks_conj_real(hegpu_context* ctx, const uint64_t* x, uint64_t x_strid
  * allocated: with ct2 one addition of the two into the workspace -> per SlotToCoeff factor hegpu_ckks_linear_transform +
  * hegpu_ckks_rescale_inplace, down to level 0 -> hegpu_ckks_mod_raise to plan->cts_level -> per CoeffToSlot factor the same
  * pair -> hegpu_ckks_apply_galois (2N - 1, conj_key) -> hegpu_ckks_conj_real dropping one limb -> ONE hegpu_ckks_poly_eval
- * of trig at batch `batch` into out.  Bit-identical to that chain of single entries (the sum: hegpu_addition).  No switch
+ * of trig at batch `batch` into out.  Bit-identical to that chain of single entries (the sum: hegpu_addition; a factor with
+ * giant_parent: hegpu_ckks_linear_transform_chained, bit-identical to the same composition of single entries).  No switch
  * keys: a sparse secret is the caller's business.  out needs room for [2][out_level + 1 + rescale_after of trig's last
  * step][N] per item and holds [2][out_level + 1][N] on return, at depth Q - 1 - out_level and scale plan->out_scale.
  * HEGPU_E_INVALID before anything is queued, out untouched: a plan, trig plan or factor list that does not fit the context

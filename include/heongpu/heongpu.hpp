@@ -2120,6 +2120,10 @@ template <> class HEEncoder<Scheme::CKKS> { // host/ckks/encoder.cuh: N/2 comple
 // rotated by -j n1 before it is encoded, so that rot(j n1, diag' * rot(i, v)) = diag_k * rot(k, v).  With a stride (a
 // group of FFT stages: every diagonal index is a multiple of it) the plan is made over k / stride: k = stride (j n1 + i),
 // baby shifts stride i, giant shifts stride j n1.
+// chain_giant_steps: the giant steps are chained (hegpu_giant_step_chain, hegpu_ckks_linear_transform_chained): each inner
+// sum is folded into its neighbour nearer zero and travels over the differences of neighbouring giant shifts.  The
+// diagonals, the number of key switches and the result's meaning are those of the direct mode; required_shifts() holds
+// the links in the place of the giant shifts -- for giant steps that are dense around zero two keys, not n2 - 1.
 template <Scheme S> class LinearTransform;
 template <> class LinearTransform<Scheme::CKKS> {
     static constexpr Scheme S = Scheme::CKKS;
@@ -2128,25 +2132,33 @@ template <> class LinearTransform<Scheme::CKKS> {
     // n1: the baby-step period; 0 = the power of two nearest the square root of the number of diagonals (the larger one
     // on a tie), at most 16.  Diagonals shorter than N/2 are padded with zeros.
     LinearTransform(HEContext<S> context, const std::map<int, std::vector<Complex64>>& diagonals, HEEncoder<S>& encoder,
-                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1)
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1,
+                    bool chain_giant_steps = false)
         : context_(std::move(context))
     {
-        build(diagonals, encoder, scale, depth, n1, o, stride);
+        build(diagonals, encoder, scale, depth, n1, o, stride, chain_giant_steps);
     }
     LinearTransform(HEContext<S> context, const std::map<int, std::vector<double>>& diagonals, HEEncoder<S>& encoder,
-                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1)
+                    double scale, int depth = 0, int n1 = 0, const ExecutionOptions& o = ExecutionOptions(), int stride = 1,
+                    bool chain_giant_steps = false)
         : context_(std::move(context))
     {
-        build(diagonals, encoder, scale, depth, n1, o, stride);
+        build(diagonals, encoder, scale, depth, n1, o, stride, chain_giant_steps);
     }
-    // the rotations linear_transform needs a Galois key of their own for (no key chains there)
+    // the rotations linear_transform needs a Galois key of their own for (no power-of-two chains there): the baby shifts
+    // and the giant shifts, with chain_giant_steps the links of the chain in their place
     std::vector<int> required_shifts() const
     {
         std::vector<int> v;
         for (int sh : baby_shifts_) if (sh) v.push_back(sh);
-        for (int sh : giant_shifts_) if (sh && std::find(v.begin(), v.end(), sh) == v.end()) v.push_back(sh);
+        for (int sh : link_shifts()) if (sh && std::find(v.begin(), v.end(), sh) == v.end()) v.push_back(sh);
         return v;
     }
+    bool chained() const noexcept { return !giant_parent_.empty(); }
+    // per giant step the rotation linear_transform applies to it: its own shift, or with chain_giant_steps its link
+    const std::vector<int>& link_shifts() const noexcept { return chained() ? link_shifts_ : giant_shifts_; }
+    // hegpu_ckks_linear_transform_chained's giant_parent: nullptr = direct
+    const int* giant_parent() const noexcept { return chained() ? giant_parent_.data() : nullptr; }
     double scale() const noexcept { return scale_; }
     int depth() const noexcept { return depth_; }
     int n1() const noexcept { return (int) baby_shifts_.size(); }
@@ -2159,7 +2171,7 @@ template <> class LinearTransform<Scheme::CKKS> {
 
   private:
     template <typename T> void build(const std::map<int, std::vector<T>>& diagonals, HEEncoder<S>& encoder, double scale,
-                                     int depth, int n1, const ExecutionOptions& o, int stride)
+                                     int depth, int n1, const ExecutionOptions& o, int stride, bool chain_giant_steps)
     {
         detail::require_generated(context_);
         if (depth < 0 || depth >= context_->Q_size) throw std::invalid_argument("Invalid depth!");
@@ -2217,10 +2229,18 @@ template <> class LinearTransform<Scheme::CKKS> {
         giant_shifts_.clear();
         for (int i : babies) baby_shifts_.push_back(stride * i);
         for (int j : giants) giant_shifts_.push_back(stride * j * n1);
+        giant_parent_.clear();
+        link_shifts_.clear();
+        if (chain_giant_steps) {
+            giant_parent_.resize(giant_shifts_.size());
+            link_shifts_.resize(giant_shifts_.size());
+            detail::check(hegpu_giant_step_chain(giant_shifts_.data(), (int) giant_shifts_.size(), slots, giant_parent_.data(),
+                                                 link_shifts_.data()));
+        }
     }
     HEContext<S> context_;
     DeviceVector<Data64> diags_;
-    std::vector<int> index_, baby_shifts_, giant_shifts_;
+    std::vector<int> index_, baby_shifts_, giant_shifts_, giant_parent_, link_shifts_;
     double scale_ = 0;
     int depth_ = 0, n_diag_ = 0;
 };
@@ -2258,7 +2278,8 @@ struct CKKSEncodingTransformConfig {
     int StoC_piece_;       // [2, 5]
     int CtoS_start_level_; // ciphertext level where CoeffToSlot starts
     int StoC_start_level_; // ciphertext level where SlotToCoeff starts
-    bool less_key_mode_;
+    bool less_key_mode_;   // the reference's own key chain: refused (HEArithmeticOperator::set_chained_giant_steps is this
+                           // backend's reduced key set)
     CKKSEncodingTransformConfig(int CtoS_piece = 3, int StoC_piece = 3, bool less_key_mode = true)
         : CtoS_piece_(CtoS_piece), StoC_piece_(StoC_piece), CtoS_start_level_(-1), StoC_start_level_(-1),
           less_key_mode_(less_key_mode)
@@ -2355,7 +2376,7 @@ struct BootstrappingConfig {
     int CtoS_piece_;      // Default: 3
     int StoC_piece_;      // Default: 3
     int taylor_number_;   // Default: 11
-    bool less_key_mode_;  // Default: false
+    bool less_key_mode_;  // Default: false; carried, unused (the reduced key set: set_chained_giant_steps)
     BootstrappingConfig(int CtoS = 3, int StoC = 3, int taylor = 11, bool less_key_mode = false)
         : CtoS_piece_(CtoS), StoC_piece_(StoC), taylor_number_(taylor), less_key_mode_(less_key_mode)
     {
@@ -2683,7 +2704,8 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
     // reference's multiply_matrix (ckks/operator.cu:2803-2895) is private to its bootstrapping and takes pre-baked index
     // tensors.  The result is not rescaled: scale_ = in.scale_ * lt.scale(), rescale_required_ = true.  Every shift of
     // lt.required_shifts() needs a Galois key of its own: a power-of-two chain would silently multiply the key
-    // switches, so a missing key is std::invalid_argument here.
+    // switches, so a missing key is std::invalid_argument here.  A LinearTransform built with chain_giant_steps goes
+    // through hegpu_ckks_linear_transform_chained with its parent table.
     void linear_transform(Ciphertext<S>& in, LinearTransform<S>& lt, Galoiskey<S>& galois_key, Ciphertext<S>& out,
                           const ExecutionOptions& o = ExecutionOptions())
     {
@@ -2702,19 +2724,29 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         keys_of(lt, galois_key, keys, elts, "Galois key not present! (build the Galoiskey from required_shifts())");
         detail::Workspace ws(hegpu_ckks_linear_transform_workspace_bytes(context_->handle(), n1, n2, in.depth_, 1), o.stream_);
         DeviceVector<Data64> m(2 * n * l, o.stream_);
-        detail::check(hegpu_ckks_linear_transform(context_->handle(), (const uint64_t*) in.data(), 0, (uint64_t*) m.data(), 0,
-                                                  (const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1,
-                                                  n2, keys.data(), elts.data(), keys.data() + n1, elts.data() + n1,
-                                                  in.depth_, 1, ws.data(), ws.bytes, o.stream_));
+        detail::check(hegpu_ckks_linear_transform_chained(context_->handle(), (const uint64_t*) in.data(), 0,
+                                                          (uint64_t*) m.data(), 0, (const uint64_t*) lt.data(),
+                                                          lt.diagonal_count(), lt.index().data(), n1, n2, keys.data(),
+                                                          elts.data(), keys.data() + n1, elts.data() + n1, lt.giant_parent(),
+                                                          in.depth_, 1, ws.data(), ws.bytes, o.stream_));
         const double sc = in.scale_ * lt.scale();
         emit(in, out, std::move(m));
         out.scale_ = sc;
         out.rescale_required_ = true;
     }
 
+    // The reduced Galois key set, this backend's own switch, off by default.  Read when factors are built, by
+    // generate_encoding_transform_context, generate_bootstrapping_params, generate_bootstrapping_params_v2 and the logic
+    // operator's generate_bootstrapping_params: the giant steps of every factor are then chained (LinearTransform's
+    // chain_giant_steps), and key_indexs_ / bootstrapping_key_indexs() hold the baby steps and the links -- a subset of the
+    // direct set, with the same number of key switches.
+    void set_chained_giant_steps(bool on) noexcept { chained_giant_steps_ = on; }
+    bool chained_giant_steps() const noexcept { return chained_giant_steps_; }
+
     // host/ckks/operator.cu:6686-6800.  The factors are the groups of the encoder's special FFT
     // (hegpu_encoding_transform_fill), every diagonal encoded at `scale`; the half of CoeffToSlot's real / imaginary
-    // split is in its matrices.  The key-chain variant (less_key_mode) is not provided: std::invalid_argument.
+    // split is in its matrices.  The reference's key-chain variant (less_key_mode: its own key set, O(n2^2) key switches)
+    // is not provided: std::invalid_argument; see set_chained_giant_steps above.
     void generate_encoding_transform_context(CKKSEncodingTransformContext& tc, const double scale,
                                              const CKKSEncodingTransformConfig& config = CKKSEncodingTransformConfig())
     {
@@ -2723,7 +2755,8 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (config.CtoS_piece_ < 2 || config.CtoS_piece_ > 5) throw std::out_of_range("CtoS_piece must be in range [2, 5]");
         if (config.StoC_piece_ < 2 || config.StoC_piece_ > 5) throw std::out_of_range("StoC_piece must be in range [2, 5]");
         if (config.less_key_mode_)
-            throw std::invalid_argument("less_key_mode is not supported: every rotation takes a Galois key of its own");
+            throw std::invalid_argument("less_key_mode is not supported: every rotation takes a Galois key of its own "
+                                        "(the reduced key set of this backend: set_chained_giant_steps)");
         const int Q = context_->Q_size;
         const int ctos = config.CtoS_start_level_ < 0 ? 0 : config.CtoS_start_level_;
         const int stoc = config.StoC_start_level_ < 0 ? ctos + config.CtoS_piece_ + 1 : config.StoC_start_level_;
@@ -3072,9 +3105,10 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         std::vector<hegpu_poly_step> eval_mod;
     };
     BootV2 boot_v2_;
+    bool chained_giant_steps_ = false; // set_chained_giant_steps
     // One chain of factors of the encoder's special FFT (hegpu_encoding_transform_shape / _fill; inverse: CoeffToSlot) in the
     // order they are applied: factor p, its diagonals encoded at scales[p] and depth `depth` + p, is appended to `factors`,
-    // the shifts it rotates by to `key_indexs`.
+    // the shifts it rotates by to `key_indexs`.  With set_chained_giant_steps(true) the factors' giant steps are chained.
     void build_factors(int inverse, int pieces, int depth, const double* scales,
                        std::vector<std::shared_ptr<LinearTransform<S>>>& factors, std::vector<int>& key_indexs)
     {
@@ -3094,7 +3128,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                 diag[offsets[d]] = std::move(v);
             }
             auto lt = std::make_shared<LinearTransform<S>>(context_, diag, encoder, scales[p], depth + p, 0, ExecutionOptions(),
-                                                           strides[p]);
+                                                           strides[p], chained_giant_steps_);
             for (int sh : lt->required_shifts())
                 if (std::find(key_indexs.begin(), key_indexs.end(), sh) == key_indexs.end()) key_indexs.push_back(sh);
             factors.push_back(std::move(lt));
@@ -3145,7 +3179,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         if (a.rescale_required_) throw std::invalid_argument("Ciphertext should be rescaled first!");
         require_words(context_, a, 2);
     }
-    // the keys and Galois elements of a LinearTransform's baby steps, then its giant steps (a zero shift takes none); a
+    // the keys and Galois elements of a LinearTransform's baby steps, then its giant steps or their links (a zero shift takes none); a
     // power-of-two chain would silently multiply the key switches, so a missing key is std::invalid_argument(`hint`)
     void keys_of(const LinearTransform<S>& lt, Galoiskey<S>& gk, std::vector<const uint64_t*>& keys, std::vector<int>& elts,
                  const char* hint) const
@@ -3154,7 +3188,7 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
         keys.assign(n1 + n2, nullptr);
         elts.assign(n1 + n2, 0);
         for (int i = 0; i < n1 + n2; i++) {
-            const int shift = i < n1 ? lt.baby_shifts()[i] : lt.giant_shifts()[i - n1];
+            const int shift = i < n1 ? lt.baby_shifts()[i] : lt.link_shifts()[i - n1];
             if (shift == 0) continue;
             keys[i] = detail::key_for_shift(gk, shift, (int) context_->n, elts[i]);
             if (!keys[i]) throw std::invalid_argument(hint);
@@ -3173,7 +3207,8 @@ template <Scheme S> class HEArithmeticOperator { // host/{bfv,ckks}/operator.cuh
                 const int n1 = lt.n1(), n2 = lt.n2();
                 op.keys_of(lt, gk, keys[k], elts[k], "Galois key not present! (build the Galoiskey from key_indexs_)");
                 f[k] = hegpu_linear_factor{(const uint64_t*) lt.data(), lt.diagonal_count(), lt.index().data(), n1, n2,
-                                           keys[k].data(), elts[k].data(), keys[k].data() + n1, elts[k].data() + n1};
+                                           keys[k].data(), elts[k].data(), keys[k].data() + n1, elts[k].data() + n1,
+                                           lt.giant_parent()};
             }
         }
     };
@@ -4335,6 +4370,9 @@ template <> class HELogicOperator<Scheme::CKKS> : public detail::LogicOperatorBa
     // sequence of the arithmetic operator with ratio 2 (bit) or 3 (gates) and the function's cosine.  The reference's
     // checks and texts are kept; its departures are HEArithmeticOperator::generate_bootstrapping_params's.  The
     // *_approximation members stay undeclared: they take a mid-pipeline ciphertext that does not exist here.
+    // set_chained_giant_steps: the arithmetic operator's switch (the reduced Galois key set), read by the call below
+    void set_chained_giant_steps(bool on) noexcept { arithmetic_.set_chained_giant_steps(on); }
+    bool chained_giant_steps() const noexcept { return arithmetic_.chained_giant_steps(); }
     void generate_bootstrapping_params(const double scale, const BootstrappingConfig& config,
                                        const logic_bootstrapping_type& boot_type)
     {

@@ -3,7 +3,9 @@ modulus raise, the two key switches around it, CoeffToSlot, EvalMod over both ha
 (keys, diagonals and input: the time does not depend on the values), and checks that the entry equals the chain bit for
 bit.  Degree 30, r = 3, K = 12, ratio 256, scale 2^40, three pieces each way.  It asserts nothing but that equality.
 
-    python tools/bootstrap_bench.py [--iters 10] [--log-n 16] [--limbs 17] [--batch 1] [--no-switch-keys]
+    python tools/bootstrap_bench.py [--iters 10] [--log-n 16] [--limbs 17] [--batch 1] [--no-switch-keys] [--chained]
+
+--chained: the giant steps of every factor are chained (bootstrap_factors(chained=True)): the reduced Galois key set.
 
 The chain {60, 50 x (limbs - 1)} | {60}; the plan spends 3 + 1 + 8 + 1 + 3 limbs and needs one left, so 17 is the
 shortest chain that fits.  Each timed call is bracketed by events on the stream; the median is reported.  `bench.py`
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--limbs", type=int, default=17)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--no-switch-keys", action="store_true")
+    ap.add_argument("--chained", action="store_true", help="chain the giant steps of every factor")
     a = ap.parse_args()
     import torch
     import heongpu_amd as hg
@@ -36,7 +39,8 @@ def main():
     key_words = c.switch_key_digits() * 2 * c.Q_prime_size * n
     pool = [rand(key_words) for _ in range(3)]
     conj, relin, d2s, s2d = (rand(key_words) for _ in range(4))
-    cts, stc, elts = c.bootstrap_factors(plan, lambda e: pool[e % 3], lambda values, scale, limbs: rand(limbs * n))
+    cts, stc, elts = c.bootstrap_factors(plan, lambda e: pool[e % 3], lambda values, scale, limbs: rand(limbs * n),
+                                         chained=a.chained)
     ct = rand(B * 2 * n)
     room = 2 * (plan.out_level + 2) * n
     out, want = torch.zeros(B * room, dtype=torch.int64, device="cuda"), torch.zeros(B * room, dtype=torch.int64, device="cuda")
@@ -109,7 +113,8 @@ def main():
     equal = bool(torch.equal(out.view(B, room)[:, :ow], want.view(B, room)[:, :ow]))
     res = {"shape": {"n": n, "limbs": Q, "batch": B, "switch_keys": with_keys, "k1": plan.k1,
                      "diagonals": [f[1] for f in cts + stc], "n1_n2": [(len(f[4]), len(f[6])) for f in cts + stc],
-                     "galois_keys": len(elts), "eval_mod_steps": len(plan.eval_mod.steps)},
+                     "giant_steps": "chained" if a.chained else "direct", "galois_keys": len(elts),
+                     "galois_key_bytes": len(elts) * key_words * 8, "eval_mod_steps": len(plan.eval_mod.steps)},
            "equal": equal,
            "bootstrap_ms": timed(entry), "chain_ms": timed(chain), "multiply_and_raise_ms": timed(part_raise)}
     if with_keys:

@@ -4,7 +4,10 @@ keys), and the two passes at the real / imaginary boundary (hegpu_ckks_conj_spli
 compositions from hegpu_addition and hegpu_ckks_mult_i on the same inputs.  Next to the passes it prints the bytes they
 must move and the time that takes at the copy rate of profiles/r6_final/copy_bw.txt.  It asserts nothing.
 
-    python tools/encoding_transform_bench.py [--iters 10] [--batch 8]
+    python tools/encoding_transform_bench.py [--iters 10] [--batch 8] [--chained] [--pieces 3]
+
+--chained: the factors' giant steps are chained (giant_step_chain; hegpu_linear_factor.giant_parent).  The line also
+carries the distinct rotation keys of the mode and their bytes.
 
 With W = batch * N * 8 bytes (one limb of every item) and l limbs: the split reads 4 l W and writes 4 l W; its composition
 moves 4 + 2 (addition), 4 + 2 (subtraction) and 2 + 2 (mult_i) l W.  The merge reads 4 l W and writes 2 l W; its
@@ -25,10 +28,13 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8, help="items of the boundary passes")
     ap.add_argument("--seq-batch", type=int, default=1, help="items of the two sequences")
+    ap.add_argument("--chained", action="store_true", help="chain the giant steps of every factor")
+    ap.add_argument("--pieces", type=int, default=3)
+    ap.add_argument("--only-sequences", action="store_true", help="skip the boundary passes")
     a = ap.parse_args()
     import torch
     import heongpu_amd as hg
-    n, Q, pieces = 1 << 16, 16, 3
+    n, Q, pieces = 1 << 16, 16, a.pieces
     c = hg.Context.from_bit_sizes(hg.CKKS, n, [60] + [50] * (Q - 1), [60], sec=hg.SEC_NONE)
     c.upload()
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -65,10 +71,12 @@ def main():
         for f, grp in enumerate(hg.encoding_transform_factors(n, inverse, pieces)):
             plan = hg.linear_transform_plan(grp.offsets, n // 2, stride=grp.stride)
             l = Q - (first_depth + f)
+            chain = hg.giant_step_chain(plan.giant_shifts, n // 2)
+            giant = chain.link_shifts if a.chained else plan.giant_shifts
             out.append((rand(len(grp.offsets) * l * n), len(grp.offsets), plan.index, [key(s) for s in plan.baby_shifts],
                         [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in plan.baby_shifts],
-                        [key(s) for s in plan.giant_shifts],
-                        [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in plan.giant_shifts]))
+                        [key(s) for s in giant], [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in giant])
+                       + ((chain.parent,) if a.chained else ()))
             shape.append({"stages": grp.stages, "stride": grp.stride, "diagonals": len(grp.offsets), "n1": plan.n1, "n2": plan.n2})
         return out, shape
 
@@ -76,7 +84,9 @@ def main():
     sb = a.seq_batch
     conj = rand(key_words)
     ctos, res["coeff_to_slot_factors"] = factors(True, 0)
-    stoc, res["slot_to_coeff_factors"] = factors(False, 5)
+    stoc, res["slot_to_coeff_factors"] = factors(False, pieces + 2)
+    res["giant_steps"] = "chained" if a.chained else "direct"
+    res["rotation_keys"] = {"count": len(keys), "bytes": len(keys) * key_words * 8}
     words0 = 2 * Q * n
     ct = rand(sb * words0)
     ow = 2 * (Q - pieces - 1) * n
@@ -84,11 +94,15 @@ def main():
     ws = torch.empty(c.encoding_transform_workspace_bytes(ctos, 0, sb) // 8, dtype=torch.int64, device="cuda")
     res["coeff_to_slot_ms"] = timed(lambda: c.ckks_coeff_to_slot(ct, words0, out0, out1, ow, ctos, conj, 0, sb, ws))
     del ws
-    room = 2 * (Q - 4 - pieces) * n
+    room = 2 * (Q - 2 * pieces - 1) * n
     back = torch.empty(sb * room, dtype=torch.int64, device="cuda")
-    ws = torch.empty(c.encoding_transform_workspace_bytes(stoc, 4, sb) // 8, dtype=torch.int64, device="cuda")
-    res["slot_to_coeff_ms"] = timed(lambda: c.ckks_slot_to_coeff(out0, ow, out1, ow, back, room, stoc, 4, sb, ws))
+    ws = torch.empty(c.encoding_transform_workspace_bytes(stoc, pieces + 1, sb) // 8, dtype=torch.int64,
+                     device="cuda")
+    res["slot_to_coeff_ms"] = timed(lambda: c.ckks_slot_to_coeff(out0, ow, out1, ow, back, room, stoc, pieces + 1, sb, ws))
     del ws, keys
+    if a.only_sequences:
+        print(json.dumps(res))
+        return
 
     # the boundary passes at the depth CoeffToSlot reaches them (3) and SlotToCoeff starts (4), one limb dropped
     batch = a.batch

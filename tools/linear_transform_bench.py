@@ -5,7 +5,10 @@ per giant step, addition), and the one-pass kernel hegpu_ckks_diag_mac against t
 composition alone.  Next to the kernel's time it prints the bytes the kernel must move and the ratio to the copy rates
 of profiles/r6_final/copy_bw.txt.  It asserts nothing.
 
-    python tools/linear_transform_bench.py [--iters 10]
+    python tools/linear_transform_bench.py [--iters 10] [--chained] [--diagonals 32] [--period 8]
+
+--chained: the fused entry runs with chained giant steps (hegpu_ckks_linear_transform_chained over giant_step_chain);
+the composition stays the direct one.  The line also carries the distinct rotation keys of the mode and their bytes.
 
 With W = batch * N * 8 bytes (one limb of every item), l = 16: the kernel reads the n1 rotated ciphertexts (2 l W each)
 and writes the n2 inner sums (2 l W each); the diagonals are l N * 8 bytes each, shared by the items: read from HBM at
@@ -25,10 +28,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--chained", action="store_true", help="chain the giant steps of the fused entry")
+    ap.add_argument("--diagonals", type=int, default=32)
+    ap.add_argument("--period", type=int, default=8)
     a = ap.parse_args()
     import torch
     import heongpu_amd as hg
-    n, Q, batch, n_diag, period = 1 << 16, 16, a.batch, 32, 8
+    n, Q, batch, n_diag, period = 1 << 16, 16, a.batch, a.diagonals, a.period
     c = hg.Context.from_bit_sizes(hg.CKKS, n, [60] + [50] * (Q - 1), [60], sec=hg.SEC_NONE)
     c.upload()
     g = torch.Generator(device="cuda").manual_seed(1)
@@ -42,10 +48,13 @@ def main():
 
     ct, diags = rand(batch * words), rand(n_diag * l * n).reshape(n_diag, l * n)
     key_words = c.switch_key_digits() * 2 * c.Q_prime_size * n
-    keys = {s: rand(key_words) for s in set(plan.baby_shifts + plan.giant_shifts) if s}
+    chain = hg.giant_step_chain(plan.giant_shifts, n // 2)
+    keys = {s: rand(key_words) for s in set(plan.baby_shifts + plan.giant_shifts + chain.link_shifts) if s}
     belts = [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in plan.baby_shifts]
     gelts = [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in plan.giant_shifts]
     bkeys, gkeys = [keys.get(s) for s in plan.baby_shifts], [keys.get(s) for s in plan.giant_shifts]
+    lelts = [hg.steps_to_galois_elt(s, n, 5) if s else 0 for s in chain.link_shifts]
+    lkeys = [keys.get(s) for s in chain.link_shifts]
     out = torch.empty(batch * words, dtype=torch.int64, device="cuda")
     ws = torch.empty(c.linear_transform_workspace_bytes(n1, n2, 0, batch) // 8, dtype=torch.int64, device="cuda")
     rot = torch.empty(batch * n1 * words, dtype=torch.int64, device="cuda")
@@ -69,7 +78,11 @@ def main():
         return {"median": ms[len(ms) // 2], "min": ms[0], "max": ms[-1]}
 
     def fused():
-        c.ckks_linear_transform(ct, words, out, words, diags, n_diag, plan.index, bkeys, belts, gkeys, gelts, 0, batch, ws)
+        if a.chained:
+            c.ckks_linear_transform(ct, words, out, words, diags, n_diag, plan.index, bkeys, belts, lkeys, lelts, 0, batch, ws,
+                                    giant_parent=chain.parent)
+        else:
+            c.ckks_linear_transform(ct, words, out, words, diags, n_diag, plan.index, bkeys, belts, gkeys, gelts, 0, batch, ws)
 
     def hoisted():
         c.ckks_rotate_hoisted(ct, words, rot, n1 * words, bkeys, belts, 0, batch, kws)
@@ -109,6 +122,9 @@ def main():
 
     W = batch * n * 8
     res = {"shape": {"n": n, "limbs": l, "batch": batch, "diagonals": n_diag, "n1": n1, "n2": n2}}
+    used = {s for s in plan.baby_shifts + (chain.link_shifts if a.chained else plan.giant_shifts) if s}
+    res["giant_steps"] = "chained" if a.chained else "direct"
+    res["rotation_keys"] = {"count": len(used), "bytes": len(used) * key_words * 8}
     res["fused_entry_ms"] = timed(fused)
     res["composition_ms"] = timed(composition)
     res["rotate_hoisted_ms"] = timed(hoisted)
